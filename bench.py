@@ -2,7 +2,7 @@
 """
 bench.py -- rays/sec of the pixelNeRF-YOLO rendering hot path on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -106,6 +106,37 @@ def describe(workload="c2"):
         "flop_per_ray_projected": flop_per_ray(workload, True),
         "config": {"workload": WORKLOADS[workload][7], "rays_per_frame": side * side},
     }
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write the timed path's last-step outputs as DIR/<name>.npy (float32, float64 kept as float64), so
+    that two builds run with the same arguments (hence the same inputs) can be compared output for output.  If the arrays
+    exceed 64 MB in all, the arrays are kept whole from the smallest up while they fit an equal share of what is left, and
+    each larger one is replaced by a fixed, seeded sample of its flattened elements (the same indices in every run of the
+    same configuration)."""
+    import numpy as np
+    import torch
+    host = {}
+    for name, a in arrays.items():
+        if torch.is_tensor(a):
+            a = a.detach().cpu()
+            a = a.numpy() if a.dtype == torch.float64 else a.float().numpy()
+        a = np.asarray(a)
+        host[name] = np.array(a, dtype=np.float64 if a.dtype == np.float64 else np.float32, order="C")
+    if sum(a.nbytes for a in host.values()) > DUMP_BUDGET_BYTES:
+        left, n_left = DUMP_BUDGET_BYTES, len(host)
+        for name in sorted(host, key=lambda k: (host[k].nbytes, k)):
+            a, share = host[name], left // n_left
+            if a.nbytes > share:
+                idx = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+                host[name] = a.reshape(-1)[idx]
+            left, n_left = left - host[name].nbytes, n_left - 1
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def c3_leg(dev, args, steps=3):
@@ -243,7 +274,9 @@ def train_main(args):
     all_rays = gen_rays(tgt, W, H, torch.tensor(FOCAL128), Z_NEAR, Z_FAR, device=dev).reshape(SB, -1, 8)
     gt_all = torch.from_numpy(rs.uniform(0, 1, size=(SB, H * W, 3)).astype(np.float32)).to(dev)
 
-    def step(i):
+    last_out = {}
+
+    def step(i, keep=False):
         pix = torch.from_numpy(np.random.RandomState(1000 + i + 7919 * rank).randint(0, H * W, size=(SB, RB))).to(dev)
         rays = torch.gather(all_rays, 1, pix[..., None].expand(-1, -1, 8))
         gt = torch.gather(gt_all, 1, pix[..., None].expand(-1, -1, 3))
@@ -255,6 +288,8 @@ def train_main(args):
         if world > 1:
             pdist.allreduce_gradients(params)   # one 27 MB collective (staged through the host under the gloo rehearsal)
         opt.step()
+        if keep:   # --dump-outputs: the rendered outputs of this step (detached: the graph is not kept alive)
+            last_out.update({"%s_%s" % (p_, k): v.detach() for p_ in out for k, v in out[p_].items()})
         return loss
 
     def fence():
@@ -285,7 +320,7 @@ def train_main(args):
     step_ms, t_prev = [], t0
     curve = []
     for i in range(steps):
-        loss = step(100 + i)
+        loss = step(100 + i, keep=bool(args.dump_outputs) and i == steps - 1)
         if os.environ.get("PNYOLO_BENCH_LOSSES"):   # diagnostic: the loss of every step (device scalars, read after the loop)
             curve.append(loss.detach())
         f = net.last_mlp_stats(full=True)     # NOTE: reading event times waits for the step
@@ -312,6 +347,11 @@ def train_main(args):
         elapsed = float(tmax.item())
     net.enable_kernel_timing(False)
     assert bool(torch.isfinite(loss))
+    if args.dump_outputs and rank == 0:
+        # the last timed step: its loss, rendered outputs and the parameter gradients its backward filled
+        arrays = dict(last_out, loss=loss.detach())
+        arrays.update({"grad_" + k: p_.grad for k, p_ in net.named_parameters() if p_.requires_grad and p_.grad is not None})
+        dump_outputs(args.dump_outputs, arrays)
     names = ["forward (projected latent)", "stash forward (reference order)", "dX chain", "weight-gradient GEMMs + reduce"]
     # the scenes of the super-batch run on side streams, so per-kernel event times overlap: utilisation is priced
     # against the step's WALL time (a lower bound on the kernels' own efficiency)
@@ -384,6 +424,9 @@ def main():
                     help="render (default, the bench line) or train: one optimisation step of the reference's trainer "
                          "(train/trainlib/PixelNerfTrainer.py:58-156) on the C2 model")
     ap.add_argument("--describe", action="store_true", help="print the workload description and exit (no GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB in all); the inputs are the same in every run with the same arguments")
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="multi-rank REHEARSAL on a one-GPU box: every rank uses device 0 and the exchange goes over gloo "
                          "(RCCL refuses duplicate devices); checks the launch / sharding / gather mechanics, the line is "
@@ -568,6 +611,12 @@ def main():
         step()
     elapsed, acc, rgb, depth = timed(args.steps)
     assert bool(torch.isfinite(rgb).all()) and bool(torch.isfinite(depth).all())
+    if args.dump_outputs and rank == 0:
+        # the last timed step's frame (c4: the whole gathered frame; c2 / c3 over several ranks: also every rank's tile)
+        arrays = {"rgb": rgb, "depth": depth}
+        if exchange:
+            arrays["gathered_rgb_depth"] = gathered
+        dump_outputs(args.dump_outputs, arrays)
     projected = acc["projected"]
 
     # HBM-side traffic of the dominant kernel cannot be counted from inside this process: it is the

@@ -1,8 +1,21 @@
 import os
 import sys
 
-import numpy as np
-import pytest
+# The suite's CPU arithmetic (the oracle, held to tests/golden/ bit for bit in places) is pinned to kernels that round the
+# same on Intel and AMD x86-64 CPUs with AVX-512: ATen's AVX-512 kernels, oneDNN capped at its base AVX-512 kernels (no
+# AMX / AVX-512 FP16 variants, which only some CPUs have), MKL's conditional-numerical-reproducibility COMPATIBLE branch
+# (its other branches differ between vendors in exp()), on a fixed number of threads.  The defaults pick kernels by CPU
+# model and thread count, and exp() and the convolutions then differ in the last bits.  tools/make_golden.py captures
+# under the same settings.  Set before torch is imported.
+CPU_ARITHMETIC_ENV = {"ATEN_CPU_CAPABILITY": "avx512", "MKL_CBWR": "COMPATIBLE", "ONEDNN_MAX_CPU_ISA": "AVX512_CORE"}
+CPU_THREADS = 8
+os.environ.update(CPU_ARITHMETIC_ENV)
+
+import numpy as np  # noqa: E402
+import pytest  # noqa: E402
+import torch  # noqa: E402
+
+torch.set_num_threads(CPU_THREADS)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -28,9 +28,14 @@ import os
 import sys
 import types
 
-import numpy as np
-import torch
-import torch.nn as nn
+# the CPU arithmetic the suite runs under (tests/conftest.py CPU_ARITHMETIC_ENV, CPU_THREADS): set before torch is imported
+os.environ.update({"ATEN_CPU_CAPABILITY": "avx512", "MKL_CBWR": "COMPATIBLE", "ONEDNN_MAX_CPU_ISA": "AVX512_CORE"})
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.nn as nn  # noqa: E402
+
+torch.set_num_threads(8)
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_SRC = "/root/reference/src"
