@@ -42,7 +42,7 @@ typedef enum pny_status {
     PNY_ERR_STATE = -2,    /* call order (e.g. render before weights / latent / cameras) */
     PNY_ERR_HIP = -3,      /* HIP runtime error (message carries hipGetErrorString) */
     PNY_ERR_NOGPU = -4,    /* no gfx950 device visible */
-    PNY_ERR_RANGE = -5     /* an earlier F16X2 launch met a value outside the f16 range (pny_model_range_status) */
+    PNY_ERR_RANGE = -5     /* an earlier F16X2 / F16 launch met a value outside the f16 range (pny_model_range_status) */
 } pny_status;
 
 typedef struct pny_model pny_model;
@@ -258,7 +258,7 @@ int pny_scene_project(pny_scene* s, pny_stream stream);
  * 1.7e-6 vs 1.8e-6 at K = 512 on the network's magnitudes) at 5.3x its matrix rate; held to the same 1e-4 bar by the
  * same golden vectors.  Values beyond the f16 range (|x| > 65504 in an activation or weight) are NOT representable: use
  * F32 for such models (AUTO does so by itself when a WEIGHT loaded at pny_model_finalize is outside the range; weights changed
- * through pny_model_refresh and activations are not checked).  AUTO (default; env PNYOLO_MLP_PRECISION=f32|f16x2 overrides at scene creation) otherwise
+ * through pny_model_refresh and activations are not checked).  AUTO (default; env PNYOLO_MLP_PRECISION=f32|f16x2|f16 overrides at scene creation) otherwise
  * equals F16X2: every projected launch, whatever its size, so that a ray's result does not depend on the batch it is rendered
  * in.  Launches without projection (training forward, the reference operation order, batches below the projection
  * threshold) always run F32; models with more than 6 residual blocks or combine_layer = 0 always run F32.
@@ -270,11 +270,26 @@ int pny_scene_project(pny_scene* s, pny_stream stream);
 #define PNY_PRECISION_F32 0
 #define PNY_PRECISION_F16X2 1
 #define PNY_PRECISION_AUTO 2
+/* F16 (opt-in, outside the 1e-4 parity claim): the no-grad projected forward launches of the scene -- pny_render, pny_query,
+ * pny_yolo_render, coarse and fine MLP, single and grouped scenes -- run on the f16 matrix cores with ONE f16 plane per operand
+ * (round to nearest) and fp32 accumulation: one v_mfma_f32_32x32x16_f16 per product instead of three and 2 bytes per weight
+ * instead of 4 (csrc/mlp_h1.hip, one 64-sample tile shape for every launch size, so a ray's result still does not depend on
+ * the batch it is rendered in).  Measured on MI355X: 1.84x the F16X2 kernel's speed on the C2 frame
+ * (MLP kernel 42.8 vs 78.7 ms); max |error| 2.8e-3 on RGB / sigma against the reference's goldens, 77 dB PSNR against
+ * an F32 render.  Everything else
+ * on an F16 scene behaves exactly as AUTO: the training forward (stash) and every backward (gradients are bit-identical to an
+ * AUTO scene's), the latent projection, and the fallbacks to fp32 (more than 6 blocks, combine_layer = 0, weights outside
+ * the f16 range at finalize, unprojected launches).  The single-plane weight images are built when a scene of the model is
+ * first set to F16 (a device synchronisation) and from then on kept current by pny_model_finalize / pny_model_refresh;
+ * models without F16 scenes hold none.  The range guard below applies as for F16X2 (the plane has the range of F16X2's
+ * first plane).  Env PNYOLO_MLP_PRECISION=f16 selects it at scene creation. */
+#define PNY_PRECISION_F16 3
 int pny_scene_set_precision(pny_scene* s, int mode);
-/* 1 when the last MLP launch of the scene ran the F16X2 kernel. */
+/* The kernel family of the last MLP launch of the scene: 0 fp32, 1 the F16X2 (split-f16) kernel, 2 the F16 (single-plane)
+ * kernel.  Non-zero = an f16-family kernel ran and the range guard applies. */
 int pny_scene_last_precision(pny_scene* s, int* f16x2);
 
-/* Run-time guard of the F16X2 arithmetic's range.  The split operands are f16 planes: a value of magnitude >= 65520 (or an
+/* Run-time guard of the F16X2 (and F16) arithmetic's range.  The split operands are f16 planes: a value of magnitude >= 65520 (or an
  * infinity) has no f16 representation, and a launch that meets one returns garbage where the reference -- fp32 throughout,
  * src/model/resnetfc.py:134-186; it only prints when its output holds a NaN, src/model/models.py:174-270 -- still returns
  * numbers.  Every F16X2 kernel therefore reports what it meets into one word per model that the host can read at any time

@@ -308,6 +308,70 @@ static int pack_mlp(pny_model* m, const std::string& pre, MlpWeights& w, MlpWeig
     return 0;
 }
 
+// Single-plane f16 images for PNY_PRECISION_F16 (mlp_h1.hip): per 16-k step [n-tile][lane] x 8 halves, lane l holding
+// f16(W[32 nt + (l & 31)][16 j + 8 (l >> 5) + 0..7]) -- by definition plane 0 of the split image (pack_layer_h2), so they are
+// copied out of the split images on the device (pack.hip PACK_H1) and are current whenever those are.  Built once a scene of
+// the model is set to F16; from then on every pny_model_finalize rebuilds them and every pny_model_refresh repacks them right
+// behind the split images on its stream.  A model that never runs F16 holds no such images and pays nothing for them.
+static int build_h1_images(pny_model* m) {
+    m->h1_ready = false;
+    if (!m->finalized) return 0;   // pny_model_finalize builds them
+    PNY_HIP(hipSetDevice(m->desc.device));
+    const int nb = m->desc.n_blocks, nmlp = m->desc.has_fine ? 2 : 1;
+    const size_t per_mlp = ((size_t)D_IN_PAD + 2ull * nb * HID) * HID;   // halves
+    int rc;
+    if ((rc = m->h1_packed.reserve(nmlp * per_mlp * sizeof(_Float16)))) return rc;
+    std::vector<PackJob> jobs;
+    _Float16* p = reinterpret_cast<_Float16*>(m->h1_packed.p);
+    auto add = [&](const float* h2_image, int k_pad, const float** slot) {
+        PackJob j;
+        memset(&j, 0, sizeof(j));
+        j.kind = PACK_H1;
+        j.src = h2_image;
+        j.dst = reinterpret_cast<float*>(p);
+        j.n_out = HID;
+        j.k_pad = k_pad;
+        j.count = (k_pad / 16) * (HID / 32) * 64;   // 16-byte fragments
+        m->h1_max_elems = std::max(m->h1_max_elems, (long long)j.count);
+        jobs.push_back(j);
+        *slot = reinterpret_cast<const float*>(p);
+        p += (size_t)k_pad * HID;
+    };
+    m->h1_max_elems = 0;
+    for (int f = 0; f < nmlp; ++f) {
+        const MlpWeightsT& wt = f ? m->fine_t : m->coarse_t;
+        add(wt.h2_in, D_IN_PAD, &m->h1_in[f]);
+        for (int b = 0; b < nb; ++b) {
+            add(wt.h2_fc0[b], HID, &m->h1_fc0[f][b]);
+            add(wt.h2_fc1[b], HID, &m->h1_fc1[f][b]);
+        }
+    }
+    if (nmlp == 1) {
+        m->h1_in[1] = m->h1_in[0];
+        for (int b = 0; b < nb; ++b) {
+            m->h1_fc0[1][b] = m->h1_fc0[0][b];
+            m->h1_fc1[1][b] = m->h1_fc1[0][b];
+        }
+    }
+    if ((rc = m->h1_jobs.reserve(jobs.size() * sizeof(PackJob)))) return rc;
+    // once per model (and finalize): wait for every stream that may still rewrite the split images or read older images
+    PNY_HIP(hipDeviceSynchronize());
+    PNY_HIP(hipMemcpy(m->h1_jobs.p, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice));
+    m->n_h1_jobs = (int)jobs.size();
+    launch_repack(reinterpret_cast<const PackJob*>(m->h1_jobs.p), m->n_h1_jobs, m->h1_max_elems, nullptr, m->range_flag);
+    PNY_HIP(hipGetLastError());
+    PNY_HIP(hipDeviceSynchronize());
+    m->h1_ready = true;
+    return 0;
+}
+
+namespace pny {
+int want_h1_images(pny_model* m) {
+    m->want_h1 = true;
+    return m->h1_ready ? 0 : build_h1_images(m);
+}
+}  // namespace pny
+
 // ---------------------------------------------------------------------------------- C ABI
 extern "C" {
 
@@ -344,6 +408,8 @@ void pny_model_destroy(pny_model* m) {
     if (!m) return;
     m->packed.release();
     m->repack_jobs.release();
+    m->h1_packed.release();
+    m->h1_jobs.release();
     m->d_absmax.release();
     m->enc_batch_work.release();
     m->enc_batch_lat.release();
@@ -389,6 +455,7 @@ int pny_model_finalize(pny_model* m) {
     int rc;
     m->repack.clear();
     m->repack_ready = false;
+    m->h1_ready = false;
     PNY_HIP(hipDeviceSynchronize());  // a re-finalize must not overwrite weights a running kernel reads
     m->f16_weights_ok = true;
     if ((rc = pack_mlp(m, "mlp_coarse.", m->coarse, m->coarse_t, plan))) return rc;
@@ -440,6 +507,7 @@ int pny_model_finalize(pny_model* m) {
         m->has_encoder = true;
     }
     m->finalized = true;
+    if (m->want_h1 && (rc = build_h1_images(m))) return rc;
     return PNY_OK;
 }
 
@@ -516,6 +584,8 @@ int pny_model_refresh(pny_model* m, pny_stream stream) {
         s->order_ev_valid = false;
     }
     launch_repack(reinterpret_cast<const PackJob*>(m->repack_jobs.p), m->n_repack_jobs, m->repack_max_elems, st, m->range_flag);
+    if (m->h1_ready)   // single-plane images (F16 scenes): copied out of the split images just rewritten, same stream
+        launch_repack(reinterpret_cast<const PackJob*>(m->h1_jobs.p), m->n_h1_jobs, m->h1_max_elems, st, m->range_flag);
     PNY_HIP(hipGetLastError());
     ++m->generation;   // projected maps of every scene are stale
     return PNY_OK;
@@ -536,11 +606,13 @@ int pny_scene_create(pny_scene** out, pny_model* m) {
         if (!strcmp(e, "off")) s->zp_mode = PNY_PROJECTION_OFF;
         if (!strcmp(e, "on")) s->zp_mode = PNY_PROJECTION_ON;
     }
-    if (const char* e = getenv("PNYOLO_MLP_PRECISION")) {  // process-wide default: f32 | f16x2 | auto
+    if (const char* e = getenv("PNYOLO_MLP_PRECISION")) {  // process-wide default: f32 | f16x2 | f16 | auto
         if (!strcmp(e, "f32")) s->precision = PNY_PRECISION_F32;
         if (!strcmp(e, "f16x2")) s->precision = PNY_PRECISION_F16X2;
+        if (!strcmp(e, "f16")) s->precision = PNY_PRECISION_F16;
     }
     *out = s;
+    if (s->precision == PNY_PRECISION_F16) return want_h1_images(m);
     return PNY_OK;
 }
 
@@ -811,7 +883,7 @@ int check_ready(pny_scene* s, const char* who) {
     const unsigned bits = s->precision == PNY_PRECISION_F32 ? 0u : range_bits(s->m);
     if (bits) {
         if (bits & PNY_RANGE_WEIGHT) s->m->f16_weights_ok = false;   // AUTO scenes run F32 from here on
-        return fail(PNY_ERR_RANGE, std::string(who) + ": an earlier F16X2 launch left the f16 range (" +
+        return fail(PNY_ERR_RANGE, std::string(who) + ": an earlier f16 (F16X2 / F16) launch left the f16 range (" +
                                        std::string(bits & PNY_RANGE_ACTIVATION ? "activation " : "") +
                                        std::string(bits & PNY_RANGE_GRADIENT ? "gradient " : "") +
                                        std::string(bits & PNY_RANGE_WEIGHT ? "weight " : "") +
@@ -1005,6 +1077,7 @@ static int run_mlp(pny_scene* s, int mode, const float* xyz, const float* dirs, 
             s->last_flops_ref += mlp_flops_per_point(d, obj_views(s), true) * (double)n_points;
             s->last_projected = use_h2;
             s->last_f16x2 = use_h2;
+            s->last_prec = use_h2 ? 1 : 0;   // (F16 scenes: the training forward runs as AUTO)
             s->last_launches += 1;
             return 0;
         }
@@ -1019,18 +1092,32 @@ static int run_mlp(pny_scene* s, int mode, const float* xyz, const float* dirs, 
     const bool use_h2 = a.zp && mlp_h2_supports(d.n_blocks, d.combine_layer) && s->precision != PNY_PRECISION_F32 &&
                         (s->m->f16_weights_ok || s->precision == PNY_PRECISION_F16X2);
     if (use_h2) variant = MLP_8x64;
+    // single-plane kernel (PNY_PRECISION_F16, mlp_h1.hip): wherever an F16 scene would run the split kernel, in its one
+    // 64-sample shape for every launch size (never the split or wide shapes)
+    const bool use_h1 = use_h2 && s->precision == PNY_PRECISION_F16;
+    if (use_h1) {
+        if ((rc = want_h1_images(s->m))) return rc;
+        const int f = (fine_w && d.has_fine) ? 1 : 0;
+        a.w_base = s->m->h1_packed.f();
+        a.w_bytes = (unsigned)s->m->h1_packed.bytes;
+        a.h2_in = s->m->h1_in[f];
+        for (int b = 0; b < d.n_blocks; ++b) {
+            a.h2_fc0[b] = s->m->h1_fc0[f][b];
+            a.h2_fc1[b] = s->m->h1_fc1[f][b];
+        }
+    }
     // Split shape of the f16x2 kernel (mlp_h2s.hip: 32-sample tiles, 4-wave workgroups, two per CU): the same arithmetic per
     // sample, bit for bit.  Measured (profiles/r02zk_split_sweep.log): a launch that gives every CU at most ONE 32-sample tile
     // takes 0.40-0.43 ms against 0.47-0.51 ms on 64-sample tiles; as soon as two workgroups share a CU the doubled weight
     // stream per sample costs more than the overlap of their phases returns (full C2 frame: 61.7 vs 39.9 ms per launch).
     // So: launches of at most 32 x CUs points.  PNYOLO_H2_SPLIT=0|1 overrides.
-    bool use_h2s = use_h2 && n_points <= 32ll * mlp_max_grid(MLP_8x64);
-    if (use_h2)
+    bool use_h2s = use_h2 && !use_h1 && n_points <= 32ll * mlp_max_grid(MLP_8x64);
+    if (use_h2 && !use_h1)
         if (const char* e = getenv("PNYOLO_H2_SPLIT")) use_h2s = atoi(e) != 0;
     // wide shape (mlp_h2w.hip: 4 waves x 512 registers, 16 x 16 x 32 MFMAs): launches that give every CU more than one tile
-    bool use_h2w = use_h2 && !use_h2s && mlp_h2w_supports(d.n_blocks, d.combine_layer) && h2w_default();
+    bool use_h2w = use_h2 && !use_h1 && !use_h2s && mlp_h2w_supports(d.n_blocks, d.combine_layer) && h2w_default();
     int h2w_mode = 1;   // 1: 4 waves x 512 registers (mlp_h2w.hip), 2: 8 waves x 256 (mlp_h2n.hip)
-    if (use_h2 && !use_h2s)
+    if (use_h2 && !use_h1 && !use_h2s)
         if (const char* e = getenv("PNYOLO_H2_WIDE")) {
             h2w_mode = atoi(e);
             use_h2w = h2w_mode != 0 && mlp_h2w_supports(d.n_blocks, d.combine_layer);
@@ -1054,7 +1141,9 @@ static int run_mlp(pny_scene* s, int mode, const float* xyz, const float* dirs, 
         }
         PNY_HIP(hipEventRecord(s->ev[s->ev_used], st));
     }
-    if (use_h2s)
+    if (use_h1)
+        launch_mlp_h1(a, grid, st);
+    else if (use_h2s)
         launch_mlp_h2s(a, grid, st);
     else if (use_h2w && h2w_mode == 2)
         launch_mlp_h2n(a, grid, st);
@@ -1070,6 +1159,7 @@ static int run_mlp(pny_scene* s, int mode, const float* xyz, const float* dirs, 
         s->ev_used += 2;
     }
     s->last_f16x2 = use_h2;
+    s->last_prec = use_h1 ? 2 : use_h2 ? 1 : 0;
     s->last_flops += mlp_flops_per_point(d, obj_views(s), a.zp == nullptr) * (double)n_points;
     s->last_flops_ref += mlp_flops_per_point(d, obj_views(s), true) * (double)n_points;
     s->last_projected = a.zp != nullptr;
@@ -1234,10 +1324,12 @@ int pny_scene_set_projection(pny_scene* s, int mode) {
 
 int pny_scene_set_precision(pny_scene* s, int mode) {
     if (!s) return fail(PNY_ERR_ARG, "pny_scene_set_precision: null scene");
-    if (mode != PNY_PRECISION_F32 && mode != PNY_PRECISION_F16X2 && mode != PNY_PRECISION_AUTO)
-        return fail(PNY_ERR_ARG, "pny_scene_set_precision: mode must be PNY_PRECISION_{F32,F16X2,AUTO}");
+    if (mode != PNY_PRECISION_F32 && mode != PNY_PRECISION_F16X2 && mode != PNY_PRECISION_AUTO && mode != PNY_PRECISION_F16)
+        return fail(PNY_ERR_ARG, "pny_scene_set_precision: mode must be PNY_PRECISION_{F32,F16X2,AUTO,F16}");
+    // (F16, F16X2 and AUTO project alike: only a switch to or from F32 re-projects)
     if ((mode == PNY_PRECISION_F32) != (s->precision == PNY_PRECISION_F32)) s->zp_valid[0] = s->zp_valid[1] = false;   // re-project in the new arithmetic
     s->precision = mode;
+    if (mode == PNY_PRECISION_F16) return want_h1_images(s->m);
     return PNY_OK;
 }
 
@@ -1252,7 +1344,7 @@ int pny_model_range_status(pny_model* m, unsigned* bits, int clear) {
 
 int pny_scene_last_precision(pny_scene* s, int* f16x2) {
     if (!s || !f16x2) return fail(PNY_ERR_ARG, "pny_scene_last_precision: null argument");
-    *f16x2 = s->last_f16x2 ? 1 : 0;
+    *f16x2 = s->last_prec;
     return PNY_OK;
 }
 

@@ -162,6 +162,15 @@ struct pny_model {
     bool f16_weights_ok = true;   // every MLP weight is representable in the f16 range (checked at finalize; AUTO precision needs it)
     unsigned* range_flag = nullptr;           // pinned host word the f16x2 kernels report PNY_RANGE_* bits into (pny_model_range_status)
     uint64_t generation = 0;                  // bumped by every finalize (scenes re-project)
+    // single-plane f16 images of lin_in / fc_0 / fc_1 for PNY_PRECISION_F16 (mlp_h1.hip): built only once a scene of the model
+    // is set to F16 (api.hip build_h1_images), then kept current by every finalize and refresh; [0] coarse, [1] fine MLP
+    bool want_h1 = false, h1_ready = false;
+    DevBuf h1_packed, h1_jobs;
+    int n_h1_jobs = 0;
+    long long h1_max_elems = 0;
+    const float* h1_in[2] = {nullptr, nullptr};
+    const float* h1_fc0[2][MAX_BLOCKS] = {};
+    const float* h1_fc1[2][MAX_BLOCKS] = {};
 };
 
 struct pny_scene {
@@ -181,6 +190,7 @@ struct pny_scene {
     float* latent_grad = nullptr;   // (ns, hl, wl, L) caller-owned accumulator of d loss / d latent (pny_scene_bind_latent_grad)
     int precision = PNY_PRECISION_AUTO;   // matrix arithmetic of projected launches (pny_scene_set_precision)
     bool last_f16x2 = false;
+    int last_prec = 0;    // pny_scene_last_precision: 0 fp32, 1 split-f16 (F16X2), 2 single-plane f16 (F16) kernel
     bool last_projected = false;
     double last_flops_ref = 0.0;
     // timing of the MLP launches of the last call
@@ -218,6 +228,8 @@ namespace pny {
 int enter_stream(pny_scene* s, hipStream_t st);
 int check_ready(pny_scene* s, const char* who);
 int view_blocks(const pny_model_desc& d);
+// single-plane f16 images (PNY_PRECISION_F16): marks the model as using them and builds them if it is finalized
+int want_h1_images(pny_model* m);
 inline int obj_views(const pny_scene* s) { return s->ns / (s->n_objs > 0 ? s->n_objs : 1); }   // views per object
 StashLayout stash_layout(const pny_model_desc& d, int ns, int L);
 // projected latent maps of the coarse (0) / fine (1) MLP, computed if stale; force = regardless of the scene's mode

@@ -29,6 +29,12 @@
 // STASH = true is the training forward (the backward's operand stash written from prologue and epilogues).
 // This file is compiled with -fno-slp-vectorize (csrc/Makefile).  Phase timing: -DPNY_H2_STAMP
 // (tools/h2_variant_build.sh).
+//
+// -DPNY_H2_PLANES=1 (mlp_h1.hip) is the single-plane kernel of PNY_PRECISION_F16: x = f16(x), w = f16(w), one
+// v_mfma_f32_32x32x16_f16 per accumulator tile and 16 k (fp32 accumulation), weights packed per 16-k step as
+// [n-tile][lane] x 16 bytes (2 bytes per weight; api.hip build_h1_images).  The LDS layout stays the one above: relu(.) goes to
+// plane slot 0 only, and slot 1 keeps its one job of staging the second half of each fp32 projection quad -- the projection
+// is added in fp32 exactly as in the two-plane kernel, at the same 152 KiB of LDS.  Render / query launches only.
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
@@ -39,7 +45,9 @@
 // The same source is the SPLIT shape's translation unit (mlp_h2s.hip: -DPNY_H2_SPLIT with PNY_H2_NT = 4, PNY_H2_MT = 1;
 // mlp_h2_core.h): 4 waves, 32-sample tiles, 65 KiB of LDS and two workgroups per CU; render only (no STASH instantiation: the
 // backward's stash is laid out on 64-sample tiles), biases read from global memory instead of an LDS table.
-#ifdef PNY_H2_SPLIT
+#if PNY_H2_PLANES == 1
+#define PNY_H2_KERNEL pny_mlp_h1_kernel
+#elif defined(PNY_H2_SPLIT)
 #define PNY_H2_KERNEL pny_mlp_h2s_kernel
 #else
 #define PNY_H2_KERNEL pny_mlp_h2_kernel
@@ -177,10 +185,15 @@ __device__ __forceinline__ void h2epilogue(f32x16 (&acc)[h2::NT][h2::MT], const 
                 const float r0 = relu1(x0), r1 = relu1(x1), r2 = relu1(x2), r3 = relu1(x3);
                 rmax = fmaxf(fmaxf(rmax, fmaxf(r0, r1)), fmaxf(r2, r3));   // f16-range guard (two v_max3_f32 per quad)
                 if constexpr (STASH) stash_store(stash, stash_lane, stash_off + (unsigned)(((8 * nt + 2 * q) * TM + 32 * mt) * 16), r0, r1, r2, r3);
+#if PNY_H2_PLANES == 1
+                (void)s1;
+                *reinterpret_cast<h4*>(s0) = cvt4(r0, r1, r2, r3);
+#else
                 h4 p0, p1;
                 split4(r0, r1, r2, r3, p0, p1);
                 *reinterpret_cast<h4*>(s0) = p0;
                 *reinterpret_cast<h4*>(s1) = p1;
+#endif
             }
         }
     }
@@ -271,15 +284,21 @@ __device__ __forceinline__ void h2prologue(const MlpArgs& a, int v, long long ti
     }
     float rmax = 0.f;   // f16-range guard: lin_in's inputs (coordinates, view directions) go through the same split
     for (int g = part; g < D_IN_PAD / 4; g += NPART) {
-        h4 p0, p1;
         const float e0 = input_entry(4 * g + 0, xr, vd, a.freq_factor, a.num_freqs), e1 = input_entry(4 * g + 1, xr, vd, a.freq_factor, a.num_freqs);
         const float e2 = input_entry(4 * g + 2, xr, vd, a.freq_factor, a.num_freqs), e3 = input_entry(4 * g + 3, xr, vd, a.freq_factor, a.num_freqs);
         rmax = fmaxf(fmaxf(rmax, fmaxf(fabsf(e0), fabsf(e1))), fmaxf(fabsf(e2), fabsf(e3)));
+#if PNY_H2_PLANES == 1
+        if constexpr (STASH) stash_store(stash, (unsigned)((g * TM + m) * 16), stash_xin, e0, e1, e2, e3);
+        char* s0 = planes + (g >> 1) * (2 * ROW_BYTES) + m * 16 + 8 * (g & 1);
+        *reinterpret_cast<h4*>(s0) = cvt4(e0, e1, e2, e3);
+#else
+        h4 p0, p1;
         split4(e0, e1, e2, e3, p0, p1);
         if constexpr (STASH) stash_store(stash, (unsigned)((g * TM + m) * 16), stash_xin, e0, e1, e2, e3);   // lin_in's B operand, [feature/4][sample]
         char* s0 = planes + (g >> 1) * (2 * ROW_BYTES) + m * 16 + 8 * (g & 1);
         *reinterpret_cast<h4*>(s0) = p0;
         *reinterpret_cast<h4*>(s0 + ROW_BYTES) = p1;
+#endif
     }
     if (__builtin_expect(!(rmax < 65520.0f), 0)) range_report(range_flag, 1u);
 #ifdef PNY_H2_EXP_STAGGER
@@ -574,6 +593,17 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
 #pragma unroll 4
             for (int kg = 0; kg < HID / 8; ++kg) {
                 const h8 x0 = *reinterpret_cast<const h8*>(planes + kg * (2 * ROW_BYTES) + m * 16);
+#if PNY_H2_PLANES == 1
+                const float4 wa = wrow[2 * kg], wb = wrow[2 * kg + 1];
+                sum += (float)x0[0] * wa.x;
+                sum += (float)x0[1] * wa.y;
+                sum += (float)x0[2] * wa.z;
+                sum += (float)x0[3] * wa.w;
+                sum += (float)x0[4] * wb.x;
+                sum += (float)x0[5] * wb.y;
+                sum += (float)x0[6] * wb.z;
+                sum += (float)x0[7] * wb.w;
+#else
                 const h8 x1 = *reinterpret_cast<const h8*>(planes + kg * (2 * ROW_BYTES) + ROW_BYTES + m * 16);
                 const float4 wa = wrow[2 * kg], wb = wrow[2 * kg + 1];
                 sum += ((float)x0[0] + (float)x1[0]) * wa.x;
@@ -584,6 +614,7 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
                 sum += ((float)x0[5] + (float)x1[5]) * wb.y;
                 sum += ((float)x0[6] + (float)x1[6]) * wb.z;
                 sum += ((float)x0[7] + (float)x1[7]) * wb.w;
+#endif
             }
             sum += a.w.b_out[o];
             if (!a.yolo) {
@@ -608,7 +639,7 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
 #endif
 }
 
-#ifndef PNY_H2_SPLIT
+#if !defined(PNY_H2_SPLIT) && PNY_H2_PLANES == 2
 bool mlp_h2_supports(int n_blocks, int combine_layer) { return n_blocks <= h2::MAX_NB && combine_layer >= 1; }
 #endif
 
@@ -655,7 +686,10 @@ static void launch_mlp_h2_t(const MlpArgs& a, int grid, hipStream_t st) {
 #endif
 }
 
-#ifdef PNY_H2_SPLIT
+#if PNY_H2_PLANES == 1
+// single-plane images in a.h2_in / a.h2_fc0 / a.h2_fc1 and their buffer in a.w_base / a.w_bytes; 64-sample tiles
+void launch_mlp_h1(const MlpArgs& a, int grid, hipStream_t st) { launch_mlp_h2_t<false>(a, grid, st); }
+#elif defined(PNY_H2_SPLIT)
 // 32-sample tiles, two workgroups per CU: a.n_tiles counts 32-sample tiles, grid <= 2 x CUs
 void launch_mlp_h2s(const MlpArgs& a, int grid, hipStream_t st) { launch_mlp_h2_t<false>(a, grid, st); }
 #else

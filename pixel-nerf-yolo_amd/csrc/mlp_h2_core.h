@@ -1,7 +1,8 @@
 // The split-f16 GEMM machinery shared by the f16x2 forward kernel (mlp_h2.hip) and the f16x2 backward chain (mlp_bwd_h2.hip):
 // tile constants, the per-wave weight stream of [16-k step][n-tile][plane][lane] x 16-byte fragments behind a static-slot
 // register ring, the GEMM loop over the LDS activation planes, the fp32 -> two f16 planes split.  See mlp_h2.hip for the
-// layouts and DESIGN.md 4.0 for the arithmetic.
+// layouts and DESIGN.md 4.0 for the arithmetic.  -DPNY_H2_PLANES=1 (mlp_h1.hip) selects the single-plane arithmetic of
+// PNY_PRECISION_F16: one f16 plane per operand, one MFMA per accumulator tile and 16 k.
 #pragma once
 #include "mlp_core.h"
 
@@ -11,8 +12,15 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
 namespace h2 {
+#ifndef PNY_H2_PLANES
+#define PNY_H2_PLANES 2   // f16 planes per operand: 2 = split fp32 (F16X2), 1 = plain f16 (F16, mlp_h1.hip)
+#endif
 #ifndef PNY_H2_WD
+#if PNY_H2_PLANES == 1
+#define PNY_H2_WD 4  // one plane per slot: depth 4 in the registers of the two-plane depth-2 ring
+#else
 #define PNY_H2_WD 2  // measured: 4 is 7 % faster inside the GEMMs, but its 32 more ring registers spill in the gather phase (-17 % overall)
+#endif
 #endif
 // Tile shape of the translation unit (a wave owns NT n-tiles of 32 features x MT m-tiles of 32 samples; NT * MT = 4):
 //   2 x 2 (default): 8 waves, 64-sample tiles, one workgroup per CU (152 KiB of LDS) -- mlp_h2.hip, mlp_bwd_h2.hip;
@@ -25,10 +33,13 @@ namespace h2 {
 #define PNY_H2_MT 2
 #endif
 constexpr int NT = PNY_H2_NT, MT = PNY_H2_MT, TM = 32 * MT, THREADS = 64 * (16 / NT), WD = PNY_H2_WD;  // WD = ring depth in 16-k steps
+constexpr int PL = PNY_H2_PLANES;
 static_assert(NT * MT == 4 && 16 % NT == 0, "tile shape");
+static_assert(PL == 1 || PL == 2, "planes");
 constexpr bool LDS_BIAS = (NT == 2 && MT == 2);   // the bias table lives in LDS (22 KiB); the split shape reads biases from global
 constexpr int ROW_BYTES = TM * 16;          // one plane of one row (8 features x TM samples x f16)
 constexpr int ACT_BYTES = 64 * 2 * ROW_BYTES;  // activation buffer: [row = feature / 8][plane][sample] x 16 bytes (128 KiB at TM = 64)
+                                               // (PL = 1: slot 1 of a row only stages the fp32 projection, see mlp_h2.hip)
 constexpr int TAP_BYTES = 32 * TM;             // tap table
 constexpr int MAX_NB = LDS_BIAS ? 6 : MAX_BLOCKS;   // bias table: (1 + 2 n_blocks) x 512 floats must fit the 160 KiB with the rest
 __host__ __device__ constexpr int lds_bytes(int n_blocks) { return ACT_BYTES + TAP_BYTES + (LDS_BIAS ? (1 + 2 * n_blocks) * HID * 4 : 0); }
@@ -36,12 +47,12 @@ using C = Cfg<NT, MT>;
 }  // namespace h2
 
 struct H2Seg {
-    unsigned off;  // byte offset of fragment (step 0, this wave's first n-tile, plane 0) in the weight blob
+    unsigned off;  // byte offset of fragment (step 0, this wave's first n-tile, plane 0) in the weight blob (PL planes per n-tile)
     int jn;        // 16-k steps
 };
 __device__ __forceinline__ H2Seg h2seg(const WStream& ws, const float* packed, int jn, int wave) {
     H2Seg s;
-    s.off = (unsigned)(reinterpret_cast<const char*>(packed) - ws.base) + (unsigned)((h2::NT * wave) * 2 * 64) * 16u;
+    s.off = (unsigned)(reinterpret_cast<const char*>(packed) - ws.base) + (unsigned)((h2::NT * wave) * h2::PL * 64) * 16u;
     s.jn = jn;
     return s;
 }
@@ -51,11 +62,11 @@ __device__ __forceinline__ H2Seg h2seg(const WStream& ws, const float* packed, i
 #endif
 // fragment (step j, local n-tile nt, plane p): this lane's 16 bytes = 8 halves W[32 nt_g + (l & 31)][16 j + 8 (l >> 5) + 0..7]
 __device__ __forceinline__ h8 h2load(const WStream& ws, unsigned seg_off, int nt, int p, int j) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(ws.rsrc, ws.lane_off, seg_off + (unsigned)(((j * 16 + nt) * 2 + p) * 64) * 16u, PNY_H2_WAUX);
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(ws.rsrc, ws.lane_off, seg_off + (unsigned)(((j * 16 + nt) * h2::PL + p) * 64) * 16u, PNY_H2_WAUX);
     return __builtin_bit_cast(h8, v);
 }
 struct H2Ring {
-    h8 f[h2::WD][h2::NT][2];
+    h8 f[h2::WD][h2::NT][h2::PL];
 };
 __device__ __forceinline__ void h2ring_fill(H2Ring& r, const WStream& ws, const H2Seg& s) {
 #pragma unroll
@@ -64,12 +75,12 @@ __device__ __forceinline__ void h2ring_fill(H2Ring& r, const WStream& ws, const 
 #pragma unroll
         for (int nt = 0; nt < h2::NT; ++nt)
 #pragma unroll
-            for (int p = 0; p < 2; ++p) r.f[d][nt][p] = h2load(ws, s.off, nt, p, j);
+            for (int p = 0; p < h2::PL; ++p) r.f[d][nt][p] = h2load(ws, s.off, nt, p, j);
     }
 #pragma unroll
     for (int nt = 0; nt < h2::NT; ++nt)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) r.f[h2::WD - 1][nt][p] = h8{0, 0, 0, 0, 0, 0, 0, 0};
+        for (int p = 0; p < h2::PL; ++p) r.f[h2::WD - 1][nt][p] = h8{0, 0, 0, 0, 0, 0, 0, 0};
 }
 
 // acc += W_slice . act over segment `cur` (its 16-k steps a multiple of the ring depth); leaves the ring holding the first
@@ -95,10 +106,63 @@ __device__ __forceinline__ f32x16 h2mfma(h8 a, h8 b, f32x16 c) { return __builti
 struct NoSide {
     __device__ __forceinline__ void operator()() const {}
 };
+// The single-plane GEMM (PL = 1): per step and accumulator tile ONE MFMA, x1 w1.  The step's weight loads (WD - 1 steps ahead)
+// and the LDS reads of the next step's B fragments ride in one group of NT x MT independent MFMAs, fenced like h2gemm's.
+template <class Side>
+__device__ __forceinline__ void h1gemm(f32x16 (&acc)[h2::NT][h2::MT], H2Ring& r, const WStream& ws, const H2Seg& cur,
+                                       const H2Seg& next, const char* planes, int lane, Side side) {
+    using namespace h2;
+    const int m0 = lane & 31, hh = lane >> 5;
+    const char* bp = planes + hh * (2 * ROW_BYTES) + m0 * 16;   // row 2 j + hh, slot 0, sample m0
+    const int jn = cur.jn, jl = jn - 1;
+    h8 B[2][MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) B[0][mt] = *reinterpret_cast<const h8*>(bp + 32 * mt * 16);
+    for (int j = 0; j < jn; j += WD) {
+        if (j == WD) side();
+#pragma unroll
+        for (int d = 0; d < WD; ++d) {
+            const int jd = j + d;
+            const int j1 = (jd + 1 < jl) ? jd + 1 : jl;
+            const char* bj = bp + j1 * (4 * ROW_BYTES);
+            __builtin_amdgcn_sched_barrier(0);
+            const int dp = (d + WD - 1) % WD;
+            const int jj = jd - 1 + WD;
+            const bool in_cur = jj < jn;
+            const int jx = in_cur ? jj : jj - jn;
+            const unsigned src = in_cur ? cur.off : next.off;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) r.f[dp][nt][0] = h2load(ws, src, nt, 0, jx);
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) B[(d + 1) & 1][mt] = *reinterpret_cast<const h8*>(bj + 32 * mt * 16);
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt)
+                    acc[nt][mt] = h2mfma(r.f[d][nt][0], B[d & 1][mt], acc[nt][mt]);
+#ifndef PNY_H2_NOSCHED
+#pragma unroll
+            for (int i = 0; i < NT * MT; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, PNY_H2_MFMA_PER, 0);
+                if (i < MT) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // next step's B fragments first (LDS latency)
+                if (i < NT) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // the step's weight loads
+                __builtin_amdgcn_sched_group_barrier(0x006, 2, 0);
+            }
+#endif
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) asm volatile("" ::"v"(B[d & 1][mt]));
+        }
+    }
+}
+
 template <class Side = NoSide>
 __device__ __forceinline__ void h2gemm(f32x16 (&acc)[h2::NT][h2::MT], H2Ring& r, const WStream& ws, const H2Seg& cur,
                                        const H2Seg& next, const char* planes, int lane, Side side = Side()) {
     using namespace h2;
+#if PNY_H2_PLANES == 1
+    h1gemm(acc, r, ws, cur, next, planes, lane, side);
+#else
     const int m0 = lane & 31, hh = lane >> 5;
     const char* bp = planes + hh * (2 * ROW_BYTES) + m0 * 16;   // row 2 j + hh, plane 0, sample m0
     const int jn = cur.jn, jl = jn - 1;
@@ -188,6 +252,7 @@ __device__ __forceinline__ void h2gemm(f32x16 (&acc)[h2::NT][h2::MT], H2Ring& r,
                 for (int p = 0; p < 2; ++p) asm volatile("" ::"v"(B[d & 1][mt][p]));
         }
     }
+#endif
 }
 
 // split 4 fp32 values into the two f16 planes (round to nearest)
@@ -218,6 +283,14 @@ __device__ __forceinline__ void split4(float a, float b, float c, float d, h4& p
     split2(c, d, u0.y, u1.y);
     p0 = __builtin_bit_cast(h4, u0);
     p1 = __builtin_bit_cast(h4, u1);
+}
+
+// 4 fp32 values to one f16 plane (round to nearest even; two v_cvt_pk_f16_f32): the operand of the single-plane kernel
+__device__ __forceinline__ h4 cvt4(float a, float b, float c, float d) {
+    uint2 u;
+    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(u.x) : "v"(a), "v"(b));
+    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(u.y) : "v"(c), "v"(d));
+    return __builtin_bit_cast(h4, u);
 }
 
 template <int NT_, int MT_>

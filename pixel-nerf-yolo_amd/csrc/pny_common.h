@@ -106,7 +106,7 @@ struct MlpArgs {
 };
 
 // ---- device-side weight repack (pack.hip): the packed operand layouts rebuilt from the live parameter tensors
-enum { PACK_A = 0, PACK_AT = 1, PACK_NT = 2, PACK_COPY = 3, PACK_ADD2 = 4, PACK_H2 = 5, PACK_NTT = 6, PACK_H2T = 7, PACK_H3 = 8 };
+enum { PACK_A = 0, PACK_AT = 1, PACK_NT = 2, PACK_COPY = 3, PACK_ADD2 = 4, PACK_H2 = 5, PACK_NTT = 6, PACK_H2T = 7, PACK_H3 = 8, PACK_H1 = 9 };
 struct PackJob {
     const float* src;
     const float* src2;
@@ -208,6 +208,7 @@ void launch_latent_grad(const MlpArgs& a, const float* dy_stash, const StashLayo
                         hipStream_t st, const unsigned* dy_absmax = nullptr);
 bool mlp_h2_supports(int n_blocks, int combine_layer);
 void launch_mlp_h2(const MlpArgs& a, int grid, hipStream_t st);
+void launch_mlp_h1(const MlpArgs& a, int grid, hipStream_t st);    // mlp_h1.hip: single f16 plane per operand (PNY_PRECISION_F16), 64-sample tiles
 void launch_mlp_h2s(const MlpArgs& a, int grid, hipStream_t st);   // mlp_h2s.hip: a.n_tiles in 32-sample tiles, grid <= 2 x CUs
 void launch_mlp_h2_stash(const MlpArgs& a, int grid, hipStream_t st);   // + the backward's operand stash (a.stash_x, a.lay)     // 8x64 shape, projected latent, split-f16 operands (mlp_h2.hip)
 bool mlp_h2w_supports(int n_blocks, int combine_layer);

@@ -124,7 +124,8 @@ SIGNATURES = {
 _lib = None
 ABI_VERSION = 11
 PROJECTION = {"off": 0, "on": 1, "auto": 2}
-PRECISION = {"f32": 0, "f16x2": 1, "auto": 2}
+PRECISION = {"f32": 0, "f16x2": 1, "auto": 2, "f16": 3}   # f16: opt-in single-plane mode, outside the 1e-4 parity bar
+LAST_PRECISION = {0: "f32", 1: "f16x2", 2: "f16"}   # pny_scene_last_precision
 
 
 RANGE_BITS = {1: "activation", 2: "gradient", 4: "weight"}   # include/pnyolo.h PNY_RANGE_*
@@ -135,7 +136,7 @@ class PnyError(RuntimeError):
 
 
 class PnyRangeError(PnyError):
-    """An F16X2 launch met a value outside the f16 range (include/pnyolo.h pny_model_range_status)."""
+    """An f16 (F16X2 / F16) launch met a value outside the f16 range (include/pnyolo.h pny_model_range_status)."""
 
 
 def build(verbose=False):

@@ -272,7 +272,7 @@ class PixelNeRFNet(nn.Module):
         self._synced_key = None
         self._dev_bound = False
         self._timing = False
-        # What a no-grad call does when one of its F16X2 launches met a value outside the f16 range (include/pnyolo.h
+        # What a no-grad call does when one of its f16 (F16X2 / F16) launches met a value outside the f16 range (include/pnyolo.h
         # pny_model_range_status): 'relaunch' (default) = wait for the call, and if the guard fired repeat it on the fp32
         # kernels with a warning, keeping the scenes pinned to f32 from then on; 'raise' = wait and raise PnyRangeError;
         # 'lazy' = do not wait: the next library call on the model fails with PNY_ERR_RANGE (what training calls always do --
@@ -462,9 +462,11 @@ class PixelNeRFNet(nn.Module):
         return self
 
     def set_matrix_precision(self, mode):
-        """'auto' | 'f32' | 'f16x2' (include/pnyolo.h pny_scene_set_precision): the matrix arithmetic of projected
+        """'auto' | 'f32' | 'f16x2' | 'f16' (include/pnyolo.h pny_scene_set_precision): the matrix arithmetic of projected
         launches -- fp32 MFMA, or fp32 operands split into two f16 planes on the f16 matrix cores (same measured
-        error, 5.3x the matrix rate).  Launches without projection always run fp32."""
+        error, 5.3x the matrix rate).  'f16' (opt-in, outside the 1e-4 parity bar) runs no-grad projected
+        launches on ONE f16 plane per operand; training forwards and backwards of an 'f16' model run as 'auto'.
+        Launches without projection always run fp32.  Applies to every scene handle, the grouped one included."""
         if mode not in _lib.PRECISION:
             raise ValueError("matrix precision must be one of %s" % sorted(_lib.PRECISION))
         self._precision = mode
@@ -481,7 +483,7 @@ class PixelNeRFNet(nn.Module):
         return int(v.value)
 
     def check_f16_range(self):
-        """Wait for the device and raise PnyRangeError if an F16X2 launch left the f16 range since the last clear."""
+        """Wait for the device and raise PnyRangeError if an f16 (F16X2 / F16) launch left the f16 range since the last clear."""
         if self._h_model is None:
             return
         torch.cuda.synchronize(self._device())
@@ -492,7 +494,7 @@ class PixelNeRFNet(nn.Module):
     @staticmethod
     def _range_message(bits):
         what = ", ".join(n for b, n in sorted(_lib.RANGE_BITS.items()) if bits & b)
-        return ("an F16X2 launch met a value outside the f16 range (%s: |x| >= 65520, infinite or NaN); its results are "
+        return ("an f16 (F16X2 / F16) launch met a value outside the f16 range (%s: |x| >= 65520, infinite or NaN); its results are "
                 "invalid.  Pin the fp32 kernels with net.set_matrix_precision('f32') (or PNYOLO_MLP_PRECISION=f32)" % what)
 
     def guard_f16_range(self, call):
@@ -522,11 +524,18 @@ class PixelNeRFNet(nn.Module):
         return call()
 
     def last_launch_f16x2(self, scene=0):
-        """True when the last MLP launch of scene `scene` ran the f16x2 kernel."""
+        """True when the last MLP launch of scene `scene` ran an f16-family kernel (f16x2 or f16): the range guard applies."""
+        return self._last_precision_code(scene) != 0
+
+    def last_launch_precision(self, scene=0):
+        """The arithmetic of the last MLP launch of scene `scene`: 'f32' | 'f16x2' | 'f16'."""
+        return _lib.LAST_PRECISION[self._last_precision_code(scene)]
+
+    def _last_precision_code(self, scene):
         v = C.c_int(0)
         h = self._h_group if (self._last_call_group and self._group is not None) else self._scene(scene)
         check(_lib.load().pny_scene_last_precision(h, C.byref(v)))
-        return bool(v.value)
+        return int(v.value)
 
     def project_latent(self):
         """Compute the projected maps of the encoded scenes now (otherwise done lazily by the first
