@@ -284,10 +284,29 @@ int pny_scene_project(pny_scene* s, pny_stream stream);
  * models without F16 scenes hold none.  The range guard below applies as for F16X2 (the plane has the range of F16X2's
  * first plane).  Env PNYOLO_MLP_PRECISION=f16 selects it at scene creation. */
 #define PNY_PRECISION_F16 3
+/* F16_TRAIN (opt-in, outside the 1e-4 parity claim): mixed-precision training -- F16 for the forward AND the backward.  No-grad
+ * projected forwards run exactly as on an F16 scene (the same kernel, bit-identical results).  The training forward
+ * (pny_scene_stash_next_render) runs the single-plane kernel's STASH instantiation and writes its own fp32 values to the
+ * unchanged stash; the dX chain (csrc/mlp_bwd_h1.hip), the weight-gradient GEMMs (pny_dw_gemm_h1_kernel) and the latent
+ * gradient (latent_grad_h1_kernel) multiply ONE f16 plane per operand with fp32 accumulation, in the same power-of-two scaled
+ * gradient domains as F16X2 (per tile in the chain, per launch in the GEMMs): gradients stay deterministic and scale exactly
+ * with the loss; parameters, gradients and optimizer state stay fp32.  The fp32 fallbacks of AUTO apply unchanged, and
+ * PNYOLO_BWD_PRECISION=f32|f16x2 still overrides the backward.  A deferred flush (pny_model_flush_weight_grads) runs
+ * single-plane only when every contributing scene ran the F16_TRAIN backward; with an F32 contributor it runs fp32,
+ * otherwise split-f16.  The transposed single-plane images the chain needs (plane 0 of the split transposed images) are built
+ * when a scene of the model is first set to F16_TRAIN and kept current like F16's.  The range guard applies as for F16X2:
+ * training calls fail with PNY_ERR_RANGE.  When the stash reservation is missed, the backward recomputes the forward with the
+ * fp32 stash kernel, as under AUTO.  Measured errors and speed: DESIGN.md 4.7.  Env PNYOLO_MLP_PRECISION=f16_train
+ * selects it at scene creation.  (4 is not used: it stays an invalid mode, as it was before F16_TRAIN.) */
+#define PNY_PRECISION_F16_TRAIN 5
 int pny_scene_set_precision(pny_scene* s, int mode);
 /* The kernel family of the last MLP launch of the scene: 0 fp32, 1 the F16X2 (split-f16) kernel, 2 the F16 (single-plane)
  * kernel.  Non-zero = an f16-family kernel ran and the range guard applies. */
 int pny_scene_last_precision(pny_scene* s, int* f16x2);
+/* The same codes for the dX chain of the last backward of the scene (or grouped scene): 0 fp32, 1 split-f16, 2 single-plane
+ * (F16_TRAIN).  The weight-gradient GEMMs of an immediate backward run the same arithmetic; a deferred flush decides at
+ * pny_model_flush_weight_grads (see F16_TRAIN above).  0 before any backward. */
+int pny_scene_last_backward_precision(pny_scene* s, int* code);
 
 /* Run-time guard of the F16X2 (and F16) arithmetic's range.  The split operands are f16 planes: a value of magnitude >= 65520 (or an
  * infinity) has no f16 representation, and a launch that meets one returns garbage where the reference -- fp32 throughout,
@@ -423,6 +442,9 @@ int pny_scene_stash_next_render(pny_scene* s, int enable);
 int pny_model_flush_weight_grads(pny_model* m, int accumulate, pny_stream stream);
 /* GEMM FLOPs and HIP-event time of the last flush. */
 int pny_model_last_flush_stats(pny_model* m, double* flops, double* kernel_ms);
+/* The arithmetic of the last flush's weight-gradient GEMM: 0 fp32, 1 split-f16, 2 single-plane (every contributor ran the
+ * F16_TRAIN backward; see PNY_PRECISION_F16_TRAIN). */
+int pny_model_last_flush_precision(pny_model* m, int* code);
 
 /* Introspection for bench.py --mode train: GEMM FLOPs (2/MAC, unpadded) and HIP-event times (pny_scene_enable_timing)
  * of the three MLP kernels of the last pny_render_backward / pny_query_backward on this scene:

@@ -318,7 +318,8 @@ static int build_h1_images(pny_model* m) {
     if (!m->finalized) return 0;   // pny_model_finalize builds them
     PNY_HIP(hipSetDevice(m->desc.device));
     const int nb = m->desc.n_blocks, nmlp = m->desc.has_fine ? 2 : 1;
-    const size_t per_mlp = ((size_t)D_IN_PAD + 2ull * nb * HID) * HID;   // halves
+    // halves: lin_in (K = 64) + 2 nb 512 x 512 layers; the transposed set (F16_TRAIN) is as large (lin_out^T: K = 64)
+    const size_t per_mlp = ((size_t)D_IN_PAD + 2ull * nb * HID) * HID * (m->want_h1t ? 2 : 1);
     int rc;
     if ((rc = m->h1_packed.reserve(nmlp * per_mlp * sizeof(_Float16)))) return rc;
     std::vector<PackJob> jobs;
@@ -346,11 +347,22 @@ static int build_h1_images(pny_model* m) {
             add(wt.h2_fc1[b], HID, &m->h1_fc1[f][b]);
         }
     }
+    for (int f = 0; f < nmlp && m->want_h1t; ++f) {   // the chain's W^T images: the same [16-k step][n-tile][plane][lane] layout, 512 rows
+        const MlpWeightsT& wt = f ? m->fine_t : m->coarse_t;
+        add(wt.h2T_out, D_IN_PAD, &m->h1T_out[f]);
+        for (int b = 0; b < nb; ++b) {
+            add(wt.h2T_fc0[b], HID, &m->h1T_fc0[f][b]);
+            add(wt.h2T_fc1[b], HID, &m->h1T_fc1[f][b]);
+        }
+    }
     if (nmlp == 1) {
         m->h1_in[1] = m->h1_in[0];
+        m->h1T_out[1] = m->h1T_out[0];
         for (int b = 0; b < nb; ++b) {
             m->h1_fc0[1][b] = m->h1_fc0[0][b];
             m->h1_fc1[1][b] = m->h1_fc1[0][b];
+            m->h1T_fc0[1][b] = m->h1T_fc0[0][b];
+            m->h1T_fc1[1][b] = m->h1T_fc1[0][b];
         }
     }
     if ((rc = m->h1_jobs.reserve(jobs.size() * sizeof(PackJob)))) return rc;
@@ -366,9 +378,11 @@ static int build_h1_images(pny_model* m) {
 }
 
 namespace pny {
-int want_h1_images(pny_model* m) {
+int want_h1_images(pny_model* m, bool transposed) {
+    const bool more = transposed && !m->want_h1t;   // (the transposed set joins an existing buffer: rebuild the whole)
     m->want_h1 = true;
-    return m->h1_ready ? 0 : build_h1_images(m);
+    m->want_h1t = m->want_h1t || transposed;
+    return (m->h1_ready && !more) ? 0 : build_h1_images(m);
 }
 }  // namespace pny
 
@@ -610,9 +624,11 @@ int pny_scene_create(pny_scene** out, pny_model* m) {
         if (!strcmp(e, "f32")) s->precision = PNY_PRECISION_F32;
         if (!strcmp(e, "f16x2")) s->precision = PNY_PRECISION_F16X2;
         if (!strcmp(e, "f16")) s->precision = PNY_PRECISION_F16;
+        if (!strcmp(e, "f16_train")) s->precision = PNY_PRECISION_F16_TRAIN;
     }
     *out = s;
-    if (s->precision == PNY_PRECISION_F16) return want_h1_images(m);
+    if (s->precision == PNY_PRECISION_F16 || s->precision == PNY_PRECISION_F16_TRAIN)
+        return want_h1_images(m, s->precision == PNY_PRECISION_F16_TRAIN);
     return PNY_OK;
 }
 
@@ -1056,6 +1072,19 @@ static int run_mlp(pny_scene* s, int mode, const float* xyz, const float* dirs, 
                 use_h2 = a.zp != nullptr;
                 if (use_h2) a.tap_stride = a.zp_stride;
             }
+            // F16_TRAIN: the single-plane kernel's STASH instantiation (mlp_h1t.hip) wherever the split one would run
+            const bool use_h1 = use_h2 && s->precision == PNY_PRECISION_F16_TRAIN;
+            if (use_h1) {
+                if ((rc = want_h1_images(m, true))) return rc;
+                const int f = (fine_w && d.has_fine) ? 1 : 0;
+                a.w_base = m->h1_packed.f();
+                a.w_bytes = (unsigned)m->h1_packed.bytes;
+                a.h2_in = m->h1_in[f];
+                for (int b = 0; b < d.n_blocks; ++b) {
+                    a.h2_fc0[b] = m->h1_fc0[f][b];
+                    a.h2_fc1[b] = m->h1_fc1[f][b];
+                }
+            }
             if (s->timing) {
                 while ((int)s->ev.size() < s->ev_used + 2) {
                     hipEvent_t e;
@@ -1064,7 +1093,9 @@ static int run_mlp(pny_scene* s, int mode, const float* xyz, const float* dirs, 
                 }
                 PNY_HIP(hipEventRecord(s->ev[s->ev_used], st));
             }
-            if (use_h2)
+            if (use_h1)
+                launch_mlp_h1_stash(a, grid, st);
+            else if (use_h2)
                 launch_mlp_h2_stash(a, grid, st);
             else
                 launch_mlp_stash(a, grid, st);
@@ -1077,7 +1108,7 @@ static int run_mlp(pny_scene* s, int mode, const float* xyz, const float* dirs, 
             s->last_flops_ref += mlp_flops_per_point(d, obj_views(s), true) * (double)n_points;
             s->last_projected = use_h2;
             s->last_f16x2 = use_h2;
-            s->last_prec = use_h2 ? 1 : 0;   // (F16 scenes: the training forward runs as AUTO)
+            s->last_prec = use_h1 ? 2 : use_h2 ? 1 : 0;   // (F16 scenes: the training forward runs as AUTO)
             s->last_launches += 1;
             return 0;
         }
@@ -1094,9 +1125,10 @@ static int run_mlp(pny_scene* s, int mode, const float* xyz, const float* dirs, 
     if (use_h2) variant = MLP_8x64;
     // single-plane kernel (PNY_PRECISION_F16, mlp_h1.hip): wherever an F16 scene would run the split kernel, in its one
     // 64-sample shape for every launch size (never the split or wide shapes)
-    const bool use_h1 = use_h2 && s->precision == PNY_PRECISION_F16;
+    // (F16_TRAIN scenes: the same kernel, so their no-grad results are F16's bit for bit)
+    const bool use_h1 = use_h2 && (s->precision == PNY_PRECISION_F16 || s->precision == PNY_PRECISION_F16_TRAIN);
     if (use_h1) {
-        if ((rc = want_h1_images(s->m))) return rc;
+        if ((rc = want_h1_images(s->m, s->precision == PNY_PRECISION_F16_TRAIN))) return rc;
         const int f = (fine_w && d.has_fine) ? 1 : 0;
         a.w_base = s->m->h1_packed.f();
         a.w_bytes = (unsigned)s->m->h1_packed.bytes;
@@ -1324,12 +1356,13 @@ int pny_scene_set_projection(pny_scene* s, int mode) {
 
 int pny_scene_set_precision(pny_scene* s, int mode) {
     if (!s) return fail(PNY_ERR_ARG, "pny_scene_set_precision: null scene");
-    if (mode != PNY_PRECISION_F32 && mode != PNY_PRECISION_F16X2 && mode != PNY_PRECISION_AUTO && mode != PNY_PRECISION_F16)
-        return fail(PNY_ERR_ARG, "pny_scene_set_precision: mode must be PNY_PRECISION_{F32,F16X2,AUTO,F16}");
-    // (F16, F16X2 and AUTO project alike: only a switch to or from F32 re-projects)
+    if (mode != PNY_PRECISION_F32 && mode != PNY_PRECISION_F16X2 && mode != PNY_PRECISION_AUTO && mode != PNY_PRECISION_F16 &&
+        mode != PNY_PRECISION_F16_TRAIN)
+        return fail(PNY_ERR_ARG, "pny_scene_set_precision: mode must be PNY_PRECISION_{F32,F16X2,AUTO,F16,F16_TRAIN}");
+    // (F16_TRAIN, F16, F16X2 and AUTO project alike: only a switch to or from F32 re-projects)
     if ((mode == PNY_PRECISION_F32) != (s->precision == PNY_PRECISION_F32)) s->zp_valid[0] = s->zp_valid[1] = false;   // re-project in the new arithmetic
     s->precision = mode;
-    if (mode == PNY_PRECISION_F16) return want_h1_images(s->m);
+    if (mode == PNY_PRECISION_F16 || mode == PNY_PRECISION_F16_TRAIN) return want_h1_images(s->m, mode == PNY_PRECISION_F16_TRAIN);
     return PNY_OK;
 }
 
@@ -1345,6 +1378,12 @@ int pny_model_range_status(pny_model* m, unsigned* bits, int clear) {
 int pny_scene_last_precision(pny_scene* s, int* f16x2) {
     if (!s || !f16x2) return fail(PNY_ERR_ARG, "pny_scene_last_precision: null argument");
     *f16x2 = s->last_prec;
+    return PNY_OK;
+}
+
+int pny_scene_last_backward_precision(pny_scene* s, int* code) {
+    if (!s || !code) return fail(PNY_ERR_ARG, "pny_scene_last_backward_precision: null argument");
+    *code = s->last_bwd_prec;
     return PNY_OK;
 }
 

@@ -145,6 +145,9 @@ struct pny_model {
     long long defer_cap[2] = {0, 0}, defer_used[2] = {0, 0};
     DevBuf d_absmax;                         // two words: running max |dY| of the deferred tiles per MLP (train_api.hip)
     bool defer_dw_f32 = false;               // a scene pinned to F32 contributed: the flush runs the fp32 weight-gradient GEMM
+    bool defer_dw_h2 = false;                // a split-f16 scene contributed: a flush without F32 contributors runs split-f16,
+                                             // one with F16_TRAIN contributors only the single-plane GEMM
+    int last_flush_prec = 0;                 // pny_model_last_flush_precision: 0 fp32, 1 split-f16, 2 single-plane GEMM
     hipStream_t aux_stream = nullptr;        // side stream of the weight-gradient GEMMs' clipped tiles (mlp_bwd.hip launch_dw_gemm)
     hipEvent_t aux_fork = nullptr, aux_join = nullptr;
     uint64_t defer_epoch = 0;                // bumped by every pny_model_defer_weight_grads(enable)
@@ -171,6 +174,12 @@ struct pny_model {
     const float* h1_in[2] = {nullptr, nullptr};
     const float* h1_fc0[2][MAX_BLOCKS] = {};
     const float* h1_fc1[2][MAX_BLOCKS] = {};
+    // ... and of the TRANSPOSED matrices (plane 0 of the PACK_H2T images) for the single-plane backward chain of
+    // PNY_PRECISION_F16_TRAIN (mlp_bwd_h1.hip), in the same buffer: built only once a scene is set to F16_TRAIN
+    bool want_h1t = false;
+    const float* h1T_out[2] = {nullptr, nullptr};
+    const float* h1T_fc0[2][MAX_BLOCKS] = {};
+    const float* h1T_fc1[2][MAX_BLOCKS] = {};
 };
 
 struct pny_scene {
@@ -191,6 +200,7 @@ struct pny_scene {
     int precision = PNY_PRECISION_AUTO;   // matrix arithmetic of projected launches (pny_scene_set_precision)
     bool last_f16x2 = false;
     int last_prec = 0;    // pny_scene_last_precision: 0 fp32, 1 split-f16 (F16X2), 2 single-plane f16 (F16) kernel
+    int last_bwd_prec = 0;   // pny_scene_last_backward_precision: the same codes for the dX chain of the last backward
     bool last_projected = false;
     double last_flops_ref = 0.0;
     // timing of the MLP launches of the last call
@@ -229,7 +239,7 @@ int enter_stream(pny_scene* s, hipStream_t st);
 int check_ready(pny_scene* s, const char* who);
 int view_blocks(const pny_model_desc& d);
 // single-plane f16 images (PNY_PRECISION_F16): marks the model as using them and builds them if it is finalized
-int want_h1_images(pny_model* m);
+int want_h1_images(pny_model* m, bool transposed = false);   // transposed: also the chain's images (PNY_PRECISION_F16_TRAIN)
 inline int obj_views(const pny_scene* s) { return s->ns / (s->n_objs > 0 ? s->n_objs : 1); }   // views per object
 StashLayout stash_layout(const pny_model_desc& d, int ns, int L);
 // projected latent maps of the coarse (0) / fine (1) MLP, computed if stale; force = regardless of the scene's mode

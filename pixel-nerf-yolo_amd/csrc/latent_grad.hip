@@ -307,9 +307,11 @@ __global__ __launch_bounds__(64 * LG_NW) void latent_grad_h2_kernel(const MlpArg
 }
 
 void launch_latent_grad(const MlpArgs& a, const float* dy_stash, const StashLayout& lay, const float* w_cat, float* grad, int nvb,
-                        hipStream_t st, const unsigned* dy_absmax) {
+                        hipStream_t st, const unsigned* dy_absmax, int planes) {
     const long long blocks = (long long)a.n_tiles * a.NS * (a.L / 256);
-    if (dy_absmax && a.n_tiles >= 2) {
+    if (dy_absmax && planes == 1)   // single-plane (PNY_PRECISION_F16_TRAIN; latent_grad_h1.hip)
+        launch_latent_grad_h1(a, dy_stash, lay, w_cat, grad, nvb, st, dy_absmax);
+    else if (dy_absmax && a.n_tiles >= 2) {
         const long long pairs = (long long)((a.n_tiles + 1) / 2) * a.NS * (a.L / 256);
         hipLaunchKernelGGL(latent_grad_h2_kernel<2>, dim3((unsigned)pairs), dim3(64 * LG_NW), 0, st, a, dy_stash, lay, w_cat, grad, nvb, dy_absmax);
     } else if (dy_absmax)

@@ -543,7 +543,7 @@ __global__ __launch_bounds__(256) void pny_dw_reduce_kernel(const DwTarget* __re
 // the bulk instead of forming a tail of 60 workgroups on 256 CUs.
 void launch_dw_gemm(const DwJob* jobs_dev, const DwItem* items_dev, int n_part, int n_full, const float* x_stash,
                     const float* dy_stash, long long x_tile, long long dy_tile, float* partial, float* bias_partial, hipStream_t st,
-                    hipStream_t aux, hipEvent_t ev_fork, hipEvent_t ev_join, const unsigned* dy_absmax) {
+                    hipStream_t aux, hipEvent_t ev_fork, hipEvent_t ev_join, const unsigned* dy_absmax, int planes) {
     static bool attr_set[64] = {};
     int dev_ = 0;
     (void)hipGetDevice(&dev_);
@@ -562,18 +562,22 @@ void launch_dw_gemm(const DwJob* jobs_dev, const DwItem* items_dev, int n_part, 
     const bool fork = n_part > 0 && n_full > 0 && aux && ev_fork && ev_join;
     hipStream_t sp = st;
     if (fork && hipEventRecord(ev_fork, st) == hipSuccess && hipStreamWaitEvent(aux, ev_fork, 0) == hipSuccess) sp = aux;
-    if (n_part > 0 && dy_absmax)   // split-f16 matrix path (dY scaled by the tracked maximum)
-        hipLaunchKernelGGL(pny_dw_gemm_h2_kernel<false>, dim3(n_part), dim3(512), DWH_LDS_BYTES, sp, jobs_dev, items_dev, x_stash, dy_stash,
-                           x_tile, dy_tile, partial, bias_partial, dy_absmax);
-    else if (n_part > 0)
-        hipLaunchKernelGGL(pny_dw_gemm_kernel<false>, dim3(n_part), dim3(512), DW_LDS_BYTES, sp, jobs_dev, items_dev, x_stash, dy_stash,
-                           x_tile, dy_tile, partial, bias_partial);
-    if (n_full > 0 && dy_absmax)
-        hipLaunchKernelGGL(pny_dw_gemm_h2_kernel<true>, dim3(n_full), dim3(512), DWH_LDS_BYTES, st, jobs_dev, items_dev + n_part, x_stash,
-                           dy_stash, x_tile, dy_tile, partial, bias_partial, dy_absmax);
-    else if (n_full > 0)
-        hipLaunchKernelGGL(pny_dw_gemm_kernel<true>, dim3(n_full), dim3(512), DW_LDS_BYTES, st, jobs_dev, items_dev + n_part, x_stash,
-                           dy_stash, x_tile, dy_tile, partial, bias_partial);
+    if (dy_absmax && planes == 1) {   // single-plane f16 matrix path (PNY_PRECISION_F16_TRAIN; dw_gemm_h1.hip), the same scale
+        launch_dw_gemm_h1(jobs_dev, items_dev, n_part, n_full, x_stash, dy_stash, x_tile, dy_tile, partial, bias_partial, st, sp, dy_absmax);
+    } else {
+        if (n_part > 0 && dy_absmax)   // split-f16 matrix path (dY scaled by the tracked maximum)
+            hipLaunchKernelGGL(pny_dw_gemm_h2_kernel<false>, dim3(n_part), dim3(512), DWH_LDS_BYTES, sp, jobs_dev, items_dev, x_stash,
+                               dy_stash, x_tile, dy_tile, partial, bias_partial, dy_absmax);
+        else if (n_part > 0)
+            hipLaunchKernelGGL(pny_dw_gemm_kernel<false>, dim3(n_part), dim3(512), DW_LDS_BYTES, sp, jobs_dev, items_dev, x_stash,
+                               dy_stash, x_tile, dy_tile, partial, bias_partial);
+        if (n_full > 0 && dy_absmax)
+            hipLaunchKernelGGL(pny_dw_gemm_h2_kernel<true>, dim3(n_full), dim3(512), DWH_LDS_BYTES, st, jobs_dev, items_dev + n_part,
+                               x_stash, dy_stash, x_tile, dy_tile, partial, bias_partial, dy_absmax);
+        else if (n_full > 0)
+            hipLaunchKernelGGL(pny_dw_gemm_kernel<true>, dim3(n_full), dim3(512), DW_LDS_BYTES, st, jobs_dev, items_dev + n_part,
+                               x_stash, dy_stash, x_tile, dy_tile, partial, bias_partial);
+    }
     if (sp != st) {
         (void)hipEventRecord(ev_join, aux);
         (void)hipStreamWaitEvent(st, ev_join, 0);

@@ -12,10 +12,24 @@
 //     residual chain within a few binades; scenes pinned to F32 run pny_mlp_bwd_kernel).
 //   * The running max |dY| for the weight-gradient GEMM's own scale (pny_dw_gemm_h2_kernel) is taken on the TRUE values.
 // Compiled without SLP vectorisation like mlp_h2.hip (csrc/Makefile).
+//
+// -DPNY_H2_PLANES=1 (mlp_bwd_h1.hip) is the single-plane chain of PNY_PRECISION_F16_TRAIN, pny_mlp_bwd_h1_kernel: dY^T goes to
+// plane slot 0 only (f16, round to nearest), the transposed weights are single-plane images (plane 0 of PACK_H2T; api.hip
+// build_h1_images), one MFMA per accumulator tile and 16 k (h1gemm).  The scaled domain stays, and its headroom for ONE
+// plane: the upper limit is unchanged (a value 2^11 above the head's 2^4..2^5 reaches 65504 and overflows; reported as
+// PNY_RANGE_GRADIENT through the stash maximum); the lower limit is no longer the second plane's absolute 2^-25 but f16's
+// normal range: full 11-bit relative precision down to 2^-14, i.e. 2^18 below the head, subnormal (losing relative
+// precision gradually) below that.  Relative error per operand 2^-12 instead of ~2^-22.
 #include <cstring>
 
 #include "mlp_bwd_core.h"
 #include "mlp_h2_core.h"
+
+#if PNY_H2_PLANES == 1
+#define PNY_BWD_KERNEL pny_mlp_bwd_h1_kernel
+#else
+#define PNY_BWD_KERNEL pny_mlp_bwd_h2_kernel
+#endif
 
 namespace pny {
 
@@ -39,11 +53,15 @@ __device__ __forceinline__ void bh_store(const Acc (&acc)[h2::NT][h2::MT], char*
             for (int q = 0; q < 4; ++q) {
                 const float x0 = acc[nt][mt][4 * q + 0], x1 = acc[nt][mt][4 * q + 1], x2 = acc[nt][mt][4 * q + 2], x3 = acc[nt][mt][4 * q + 3];
                 if (TO_LDS) {
+                    char* s0 = base + (4 * nt + q) * (2 * ROW_BYTES) + 32 * mt * 16;
+#if PNY_H2_PLANES == 1
+                    *reinterpret_cast<h4*>(s0) = cvt4(x0, x1, x2, x3);
+#else
                     h4 p0, p1;
                     split4(x0, x1, x2, x3, p0, p1);
-                    char* s0 = base + (4 * nt + q) * (2 * ROW_BYTES) + 32 * mt * 16;
                     *reinterpret_cast<h4*>(s0) = p0;
                     *reinterpret_cast<h4*>(s0 + ROW_BYTES) = p1;
+#endif
                 }
                 if (TO_GLOBAL) {
                     const float4 v = make_float4(x0 * inv_sigma, x1 * inv_sigma, x2 * inv_sigma, x3 * inv_sigma);
@@ -87,7 +105,7 @@ __device__ __forceinline__ void bh_block(bh_acc (&dh)[h2::NT][h2::MT], H2Ring& r
 }
 }  // namespace
 
-__global__ __launch_bounds__(h2::THREADS, 2) void pny_mlp_bwd_h2_kernel(const BwdArgs a) {
+__global__ __launch_bounds__(h2::THREADS, 2) void PNY_BWD_KERNEL(const BwdArgs a) {
     using namespace h2;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     char* planes = smem_raw;
@@ -172,11 +190,15 @@ __global__ __launch_bounds__(h2::THREADS, 2) void pny_mlp_bwd_h2_kernel(const Bw
         for (int i = 0; i < NQ; ++i) {
             const int idx = tid + i * THREADS;
             const int kg = idx / TM, m = idx % TM;
+            char* s0 = planes + (kg >> 1) * (2 * ROW_BYTES) + m * 16 + 8 * (kg & 1);
+#if PNY_H2_PLANES == 1
+            *reinterpret_cast<h4*>(s0) = cvt4(hv[i].x * sigma, hv[i].y * sigma, hv[i].z * sigma, hv[i].w * sigma);
+#else
             h4 p0, p1;
             split4(hv[i].x * sigma, hv[i].y * sigma, hv[i].z * sigma, hv[i].w * sigma, p0, p1);
-            char* s0 = planes + (kg >> 1) * (2 * ROW_BYTES) + m * 16 + 8 * (kg & 1);
             *reinterpret_cast<h4*>(s0) = p0;
             *reinterpret_cast<h4*>(s0 + ROW_BYTES) = p1;
+#endif
         }
         __syncthreads();
         bh_acc dh[NT][MT];
@@ -232,16 +254,20 @@ __global__ __launch_bounds__(h2::THREADS, 2) void pny_mlp_bwd_h2_kernel(const Bw
     }
 }
 
+#if PNY_H2_PLANES == 1
+void launch_mlp_bwd_h1(const BwdArgs& a, int grid, hipStream_t st) {
+#else
 void launch_mlp_bwd_h2(const BwdArgs& a, int grid, hipStream_t st) {
+#endif
     static bool attr_set[64] = {};
     int dev_ = 0;
     (void)hipGetDevice(&dev_);
     dev_ &= 63;
     if (!attr_set[dev_]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pny_mlp_bwd_h2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BH_LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(PNY_BWD_KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, BH_LDS);
         attr_set[dev_] = true;
     }
-    hipLaunchKernelGGL(pny_mlp_bwd_h2_kernel, dim3(grid), dim3(h2::THREADS), BH_LDS, st, a);
+    hipLaunchKernelGGL(PNY_BWD_KERNEL, dim3(grid), dim3(h2::THREADS), BH_LDS, st, a);
 }
 
 }  // namespace pny

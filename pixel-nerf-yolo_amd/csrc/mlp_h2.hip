@@ -34,7 +34,8 @@
 // v_mfma_f32_32x32x16_f16 per accumulator tile and 16 k (fp32 accumulation), weights packed per 16-k step as
 // [n-tile][lane] x 16 bytes (2 bytes per weight; api.hip build_h1_images).  The LDS layout stays the one above: relu(.) goes to
 // plane slot 0 only, and slot 1 keeps its one job of staging the second half of each fp32 projection quad -- the projection
-// is added in fp32 exactly as in the two-plane kernel, at the same 152 KiB of LDS.  Render / query launches only.
+// is added in fp32 exactly as in the two-plane kernel, at the same 152 KiB of LDS.  Its STASH instantiation is the training
+// forward of PNY_PRECISION_F16_TRAIN: the stash layout is unchanged and holds this kernel's own fp32 values.
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
@@ -686,7 +687,10 @@ static void launch_mlp_h2_t(const MlpArgs& a, int grid, hipStream_t st) {
 #endif
 }
 
-#if PNY_H2_PLANES == 1
+#if PNY_H2_PLANES == 1 && defined(PNY_H1_STASH)
+// training forward of PNY_PRECISION_F16_TRAIN (mlp_h1t.hip): as launch_mlp_h2_stash, with the single-plane images
+void launch_mlp_h1_stash(const MlpArgs& a, int grid, hipStream_t st) { launch_mlp_h2_t<true>(a, grid, st); }
+#elif PNY_H2_PLANES == 1
 // single-plane images in a.h2_in / a.h2_fc0 / a.h2_fc1 and their buffer in a.w_base / a.w_bytes; 64-sample tiles
 void launch_mlp_h1(const MlpArgs& a, int grid, hipStream_t st) { launch_mlp_h2_t<false>(a, grid, st); }
 #elif defined(PNY_H2_SPLIT)

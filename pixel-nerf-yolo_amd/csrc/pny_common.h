@@ -189,9 +189,16 @@ void launch_depth_grad_gather(const int* sel, const float* dz, const float* g_in
 void launch_yolo_aggregate_bwd(const float* raw, const float* g, long long n, int k, int na, float* d_raw, hipStream_t st);
 void launch_mlp_bwd(const BwdArgs& a, int grid, hipStream_t st);
 void launch_mlp_bwd_h2(const BwdArgs& a, int grid, hipStream_t st);   // mlp_bwd_h2.hip: needs a.h2T_*
+void launch_mlp_bwd_h1(const BwdArgs& a, int grid, hipStream_t st);   // mlp_bwd_h1.hip: a.h2T_* = single-plane images in a.w_base
+// planes (with dy_absmax): 2 = split-f16 GEMM (pny_dw_gemm_h2_kernel), 1 = single-plane (pny_dw_gemm_h1_kernel, F16_TRAIN)
 void launch_dw_gemm(const DwJob* jobs_dev, const DwItem* items_dev, int n_part, int n_full, const float* x_stash,
                     const float* dy_stash, long long x_tile, long long dy_tile, float* partial, float* bias_partial, hipStream_t st,
-                    hipStream_t aux, hipEvent_t ev_fork, hipEvent_t ev_join, const unsigned* dy_absmax = nullptr);
+                    hipStream_t aux, hipEvent_t ev_fork, hipEvent_t ev_join, const unsigned* dy_absmax = nullptr, int planes = 2);
+void launch_dw_gemm_h1(const DwJob* jobs_dev, const DwItem* items_dev, int n_part, int n_full, const float* x_stash,   // dw_gemm_h1.hip
+                       const float* dy_stash, long long x_tile, long long dy_tile, float* partial, float* bias_partial, hipStream_t st,
+                       hipStream_t sp, const unsigned* dy_absmax);
+void launch_latent_grad_h1(const MlpArgs& a, const float* dy_stash, const StashLayout& lay, const float* w_cat, float* grad, int nvb,
+                           hipStream_t st, const unsigned* dy_absmax);   // latent_grad_h1.hip
 void launch_dw_reduce(const DwTarget* targets_dev, int n_targets, long long max_elems, const float* partial,
                       const float* bias_partial, int accumulate, hipStream_t st);
 void launch_composite_bwd(const float* rays, const float* z, const float* samp, const float* noise, long long n, int k,
@@ -203,13 +210,15 @@ int mlp_pick_variant(long long n_points);           // shape for a launch of n_p
 void launch_mlp(const MlpArgs& a, int variant, int grid, hipStream_t st);
 void launch_mlp_stash(const MlpArgs& a, int grid, hipStream_t st);  // 8x64 shape, reference op order, writes a.stash_x
 // latent gradient (latent_grad.hip): a.tap_stride must be a.L; grad is (NS, Hl, Wl, L) channel-last, added into
-// dy_absmax (device word, the chain kernel's running max |dY|) selects the split-f16 kernel; null: fp32 MFMA
+// dy_absmax (device word, the chain kernel's running max |dY|) selects the split-f16 kernel (planes = 1: the single-plane
+// kernel of F16_TRAIN); null: fp32 MFMA
 void launch_latent_grad(const MlpArgs& a, const float* dy_stash, const StashLayout& lay, const float* w_cat, float* grad, int nvb,
-                        hipStream_t st, const unsigned* dy_absmax = nullptr);
+                        hipStream_t st, const unsigned* dy_absmax = nullptr, int planes = 2);
 bool mlp_h2_supports(int n_blocks, int combine_layer);
 void launch_mlp_h2(const MlpArgs& a, int grid, hipStream_t st);
 void launch_mlp_h1(const MlpArgs& a, int grid, hipStream_t st);    // mlp_h1.hip: single f16 plane per operand (PNY_PRECISION_F16), 64-sample tiles
 void launch_mlp_h2s(const MlpArgs& a, int grid, hipStream_t st);   // mlp_h2s.hip: a.n_tiles in 32-sample tiles, grid <= 2 x CUs
+void launch_mlp_h1_stash(const MlpArgs& a, int grid, hipStream_t st);   // mlp_h1.hip STASH instantiation (PNY_PRECISION_F16_TRAIN)
 void launch_mlp_h2_stash(const MlpArgs& a, int grid, hipStream_t st);   // + the backward's operand stash (a.stash_x, a.lay)     // 8x64 shape, projected latent, split-f16 operands (mlp_h2.hip)
 bool mlp_h2w_supports(int n_blocks, int combine_layer);
 void launch_mlp_h2n(const MlpArgs& a, int grid, hipStream_t st);   // mlp_h2n.hip: the same kernel as 8 waves x 256 registers

@@ -197,14 +197,15 @@ void build_items(TrainPlan& p, int n_tiles, int cus, std::vector<DwItem>& items,
 }
 
 // Matrix arithmetic of the backward's GEMMs (dX chain and weight gradients): the scene's precision setting (F32 pins the fp32
-// MFMA; anything else = split f16: mlp_bwd_h2.hip pny_mlp_bwd_h2_kernel, mlp_bwd.hip pny_dw_gemm_h2_kernel); env
-// PNYOLO_BWD_PRECISION=f32|f16x2 overrides (read at every call: tests vary it).
-bool bwd_use_h2(const pny_scene* s) {
+// MFMA; F16_TRAIN = single-plane f16: mlp_bwd_h1.hip, dw_gemm_h1.hip, latent_grad_h1.hip; anything else = split f16:
+// mlp_bwd_h2.hip pny_mlp_bwd_h2_kernel, mlp_bwd.hip pny_dw_gemm_h2_kernel); env PNYOLO_BWD_PRECISION=f32|f16x2 overrides (read
+// at every call: tests vary it).  0 fp32, 1 split f16, 2 single-plane f16.
+int bwd_prec(const pny_scene* s) {
     if (const char* e = getenv("PNYOLO_BWD_PRECISION")) {
-        if (!strcmp(e, "f32")) return false;
-        if (!strcmp(e, "f16x2")) return true;
+        if (!strcmp(e, "f32")) return 0;
+        if (!strcmp(e, "f16x2")) return 1;
     }
-    return s->precision != PNY_PRECISION_F32;
+    return s->precision == PNY_PRECISION_F32 ? 0 : s->precision == PNY_PRECISION_F16_TRAIN ? 2 : 1;
 }
 
 // A zeroed device word (or two) for the chain kernels' atomic max
@@ -229,7 +230,7 @@ size_t stash_budget_bytes() {
 // dy_absmax: the chain kernels' running max |dY| of these tiles (device), or null for the fp32 matrix path
 int run_weight_grads(pny_model* m, TrainPlan& plan, int n_tiles, const float* x_stash, const float* dy_stash, DevBuf& partial,
                      DevBuf& bias, DevBuf& tables, PinnedStage& stage, int accumulate, hipStream_t st,
-                     const unsigned* dy_absmax = nullptr) {
+                     const unsigned* dy_absmax = nullptr, int planes = 2) {
     if (!m->aux_stream) {
         PNY_HIP(hipStreamCreateWithFlags(&m->aux_stream, hipStreamNonBlocking));
         PNY_HIP(hipEventCreateWithFlags(&m->aux_fork, hipEventDisableTiming));
@@ -259,7 +260,7 @@ int run_weight_grads(pny_model* m, TrainPlan& plan, int n_tiles, const float* x_
     char* tb = reinterpret_cast<char*>(tables.p);
     launch_dw_gemm(reinterpret_cast<const DwJob*>(tb), reinterpret_cast<const DwItem*>(tb + o_items), (int)items.size() - n_full,
                    n_full, x_stash, dy_stash, plan.lay.x_tile, plan.lay.dy_tile, partial.f(), bias.f(), st, m->aux_stream,
-                   m->aux_fork, m->aux_join, dy_absmax);
+                   m->aux_fork, m->aux_join, dy_absmax, planes);
     PNY_HIP(hipGetLastError());
     long long max_elems = 0;
     for (const DwTarget& t : plan.targets) max_elems = std::max(max_elems, (long long)t.rows * t.cols + t.rows);
@@ -326,10 +327,14 @@ int mlp_backward(pny_scene* s, int mode, const float* xyz, const float* dirs, co
     if ((rc = s->out_tmp.reserve((size_t)chunk_pts * d.d_out * sizeof(float)))) return rc;
     // running max |dY| for the split-f16 weight-gradient GEMM: per model and MLP in deferred mode (every scene's chain adds
     // to it, zeroed again by the flush), per scene otherwise (zeroed in front of every chunk's chain)
-    const bool dw_h2 = bwd_use_h2(s);
+    const int bprec = bwd_prec(s);
+    const bool dw_h2 = bprec != 0;
+    const bool h1 = bprec == 2 && m->f16_weights_ok;   // single-plane chain, latent gradient and (immediate) weight gradients
+    if (h1 && (rc = want_h1_images(m, true))) return rc;
     unsigned* absmax = nullptr;
     if (defer || have_x) {
         if (!dw_h2) m->defer_dw_f32 = true;
+        if (dw_h2 && !h1) m->defer_dw_h2 = true;
         if ((rc = ensure_absmax(m->d_absmax, 2 * sizeof(unsigned)))) return rc;
         absmax = reinterpret_cast<unsigned*>(m->d_absmax.p) + which;
     } else if (dw_h2) {
@@ -405,15 +410,28 @@ int mlp_backward(pny_scene* s, int mode, const float* xyz, const float* dirs, co
         b.dy_absmax = absmax;
         b.range_flag = m->range_flag;
         if (absmax && !(defer || have_x)) PNY_HIP(hipMemsetAsync(absmax, 0, sizeof(unsigned), st));
-        if (dw_h2 && m->f16_weights_ok) {   // split-f16 chain (weights beyond the f16 range: fp32 chain)
+        if (h1) {   // single-plane chain: the transposed single-plane images in the model's h1 buffer
+            const int f = (fine_w && d.has_fine) ? 1 : 0;
+            b.w_base = m->h1_packed.f();
+            b.w_bytes = (unsigned)m->h1_packed.bytes;
+            b.h2T_out = m->h1T_out[f];
+            for (int i = 0; i < d.n_blocks; ++i) {
+                b.h2T_fc0[i] = m->h1T_fc0[f][i];
+                b.h2T_fc1[i] = m->h1T_fc1[f][i];
+            }
+            launch_mlp_bwd_h1(b, grid, st);
+            s->last_bwd_prec = 2;
+        } else if (dw_h2 && m->f16_weights_ok) {   // split-f16 chain (weights beyond the f16 range: fp32 chain)
             b.h2T_out = wt.h2T_out;
             for (int i = 0; i < d.n_blocks; ++i) {
                 b.h2T_fc0[i] = wt.h2T_fc0[i];
                 b.h2T_fc1[i] = wt.h2T_fc1[i];
             }
             launch_mlp_bwd_h2(b, grid, st);
+            s->last_bwd_prec = 1;
         } else {
             launch_mlp_bwd(b, grid, st);
+            s->last_bwd_prec = 0;
         }
         PNY_HIP(hipGetLastError());
         if ((rc = stamp())) return rc;
@@ -453,13 +471,13 @@ int mlp_backward(pny_scene* s, int mode, const float* xyz, const float* dirs, co
         if (s->latent_grad && view_blocks(d) > 0) {
             if (!wt.wzT_cat) return fail(PNY_ERR_STATE, "latent gradient: transposed lin_z weights are missing");
             if (s->L % 256) return fail(PNY_ERR_ARG, "latent gradient: d_latent must be a multiple of 256");
-            launch_latent_grad(a, dy_base, plan.lay, wt.wzT_cat, s->latent_grad, view_blocks(d), st, dw_h2 ? absmax : nullptr);
+            launch_latent_grad(a, dy_base, plan.lay, wt.wzT_cat, s->latent_grad, view_blocks(d), st, dw_h2 ? absmax : nullptr, h1 ? 1 : 2);
             PNY_HIP(hipGetLastError());
         }
         // 3. weight-gradient GEMMs over the two stashes + deterministic split reduction into the bound gradients
         if (!defer && !have_x &&
             (rc = run_weight_grads(m, plan, n_tiles, x_base, dy_base, s->dw_partial, s->dw_bias, s->dw_tables, s->table_stage,
-                                   (accumulate || p0 > 0) ? 1 : 0, st, absmax)))
+                                   (accumulate || p0 > 0) ? 1 : 0, st, absmax, h1 ? 1 : 2)))
             return rc;
         if ((rc = stamp())) return rc;
     }
@@ -535,10 +553,13 @@ int pny_model_flush_weight_grads(pny_model* m, int accumulate, pny_stream stream
         if (m->defer_used[w] > 0) {
             TrainPlan plan = build_plan(m, m->defer_ns, d.d_latent, w ? "mlp_fine." : "mlp_coarse.");
             const unsigned* absmax = (m->d_absmax.p && !m->defer_dw_f32) ? reinterpret_cast<const unsigned*>(m->d_absmax.p) + w : nullptr;
+            // single-plane GEMM only when every contributor ran the F16_TRAIN backward (any F32 one: fp32, else split-f16)
+            const int planes = m->defer_dw_h2 ? 2 : 1;
             if ((rc = run_weight_grads(m, plan, (int)m->defer_used[w], m->dx_stash[w].f(), m->ddy_stash[w].f(), m->d_partial[w],
-                                       m->d_bias[w], m->d_tables[w], m->d_stage[w], accumulate, st, absmax)))
+                                       m->d_bias[w], m->d_tables[w], m->d_stage[w], accumulate, st, absmax, planes)))
                 return rc;
             m->flush_flops += fwd * 64.0 * (double)m->defer_used[w];
+            m->last_flush_prec = absmax ? (planes == 1 ? 2 : 1) : 0;
             m->flush_launches += 1;
         }
         PNY_HIP(hipEventRecord(m->flush_ev[2 * w + 1], st));
@@ -546,7 +567,13 @@ int pny_model_flush_weight_grads(pny_model* m, int accumulate, pny_stream stream
         if (m->d_absmax.p)   // the next step's chains start from 0
             PNY_HIP(hipMemsetAsync(reinterpret_cast<unsigned*>(m->d_absmax.p) + w, 0, sizeof(unsigned), st));
     }
-    if (!only_f) m->defer_dw_f32 = false;   // (a fine-only flush is followed by the coarse-only one of the same step)
+    if (!only_f) m->defer_dw_f32 = m->defer_dw_h2 = false;   // (a fine-only flush is followed by the coarse-only one of the same step)
+    return PNY_OK;
+}
+
+int pny_model_last_flush_precision(pny_model* m, int* code) {
+    if (!m || !code) return fail(PNY_ERR_ARG, "pny_model_last_flush_precision: null argument");
+    *code = m->last_flush_prec;
     return PNY_OK;
 }
 

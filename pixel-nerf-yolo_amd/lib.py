@@ -99,6 +99,7 @@ SIGNATURES = {
     "pny_scene_set_precision": (C.c_int, [C.c_void_p, C.c_int]),
     "pny_scene_bind_latent_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pny_scene_last_precision": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "pny_scene_last_backward_precision": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "pny_model_range_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.c_int]),
     "pny_trunk_train_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "pny_trunk_train_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -113,6 +114,7 @@ SIGNATURES = {
     "pny_scene_stash_next_render": (C.c_int, [C.c_void_p, C.c_int]),
     "pny_model_flush_weight_grads": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "pny_model_last_flush_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "pny_model_last_flush_precision": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "pny_model_bind_grad": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p]),
     "pny_query_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "pny_composite_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
@@ -124,8 +126,9 @@ SIGNATURES = {
 _lib = None
 ABI_VERSION = 11
 PROJECTION = {"off": 0, "on": 1, "auto": 2}
-PRECISION = {"f32": 0, "f16x2": 1, "auto": 2, "f16": 3}   # f16: opt-in single-plane mode, outside the 1e-4 parity bar
-LAST_PRECISION = {0: "f32", 1: "f16x2", 2: "f16"}   # pny_scene_last_precision
+# f16: opt-in single-plane mode for no-grad launches, f16_train: the same for training too; both outside the 1e-4 parity bar
+PRECISION = {"f32": 0, "f16x2": 1, "auto": 2, "f16": 3, "f16_train": 5}
+LAST_PRECISION = {0: "f32", 1: "f16x2", 2: "f16"}   # pny_scene_last_precision, pny_scene_last_backward_precision
 
 
 RANGE_BITS = {1: "activation", 2: "gradient", 4: "weight"}   # include/pnyolo.h PNY_RANGE_*

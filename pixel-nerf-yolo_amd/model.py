@@ -466,6 +466,9 @@ class PixelNeRFNet(nn.Module):
         launches -- fp32 MFMA, or fp32 operands split into two f16 planes on the f16 matrix cores (same measured
         error, 5.3x the matrix rate).  'f16' (opt-in, outside the 1e-4 parity bar) runs no-grad projected
         launches on ONE f16 plane per operand; training forwards and backwards of an 'f16' model run as 'auto'.
+        'f16_train' (opt-in, outside the parity bar) runs no-grad launches as 'f16' and training too on one
+        f16 plane per operand: the stashing forward, the dX chain, the weight and latent gradients (fp32 accumulation,
+        power-of-two gradient scaling inside the library, fp32 parameters and gradients).
         Launches without projection always run fp32.  Applies to every scene handle, the grouped one included."""
         if mode not in _lib.PRECISION:
             raise ValueError("matrix precision must be one of %s" % sorted(_lib.PRECISION))
@@ -530,6 +533,14 @@ class PixelNeRFNet(nn.Module):
     def last_launch_precision(self, scene=0):
         """The arithmetic of the last MLP launch of scene `scene`: 'f32' | 'f16x2' | 'f16'."""
         return _lib.LAST_PRECISION[self._last_precision_code(scene)]
+
+    def last_backward_precision(self, scene=0):
+        """The arithmetic of the dX chain of the last backward of scene `scene` (or of the grouped scene, when the last
+        call was grouped): 'f32' | 'f16x2' | 'f16' (include/pnyolo.h pny_scene_last_backward_precision)."""
+        v = C.c_int(0)
+        h = self._h_group if (self._last_call_group and self._group is not None) else self._scene(scene)
+        check(_lib.load().pny_scene_last_backward_precision(h, C.byref(v)))
+        return _lib.LAST_PRECISION[int(v.value)]
 
     def _last_precision_code(self, scene):
         v = C.c_int(0)
@@ -675,6 +686,13 @@ class PixelNeRFNet(nn.Module):
         a, b = C.c_double(), C.c_double()
         check(_lib.load().pny_model_last_flush_stats(self._h_model, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def last_flush_precision(self):
+        """The arithmetic of the last deferred weight-gradient flush's GEMM: 'f32' | 'f16x2' | 'f16'
+        (include/pnyolo.h pny_model_last_flush_precision)."""
+        v = C.c_int(0)
+        check(_lib.load().pny_model_last_flush_precision(self._h_model, C.byref(v)))
+        return _lib.LAST_PRECISION[int(v.value)]
 
     def invalidate_weights(self):
         """Force a re-upload of the parameters at the next call.  Needed after writes that PyTorch does not version:
