@@ -25,8 +25,8 @@ import torch.nn.functional as F
 f32 = torch.float32
 
 
-def T(x):
-    return torch.as_tensor(x, dtype=f32)
+def T(x, dtype=None):
+    return torch.as_tensor(x, dtype=f32 if dtype is None else dtype)
 
 
 # ----------------------------------------------------------------------------- rays
@@ -361,31 +361,38 @@ def _bn(sd, name, x, training=False):
                         sd[name + ".bias"], training=training, momentum=0.1, eps=1e-5)
 
 
-def _block(sd, p, x, stride, training=False):
+def _block(sd, p, x, stride, training=False, relu=torch.relu):
     idt = x
     if (p + "downsample.0.weight") in sd:
         idt = _bn(sd, p + "downsample.1", F.conv2d(x, sd[p + "downsample.0.weight"], stride=stride), training)
-    out = torch.relu(_bn(sd, p + "bn1", F.conv2d(x, sd[p + "conv1.weight"], stride=stride, padding=1), training))
+    out = relu(_bn(sd, p + "bn1", F.conv2d(x, sd[p + "conv1.weight"], stride=stride, padding=1), training))
     out = _bn(sd, p + "bn2", F.conv2d(out, sd[p + "conv2.weight"], padding=1), training)
-    return torch.relu(out + idt)
+    return relu(out + idt)
 
 
-def spatial_encoder(sd, images, prefix="encoder.model.", use_first_pool=True, training=False):
+def spatial_encoder(sd, images, prefix="encoder.model.", use_first_pool=True, training=False, dtype=None, relu=None):
     """src/model/encoder.py:139-173 with num_layers=4, use_first_pool; batch norm in eval() mode, or -- training=True, the
     trunk as train/train.py leaves it without --freeze_enc -- on batch statistics (running statistics of `sd` stepped in place):
     conv1/bn1/relu -> L0; maxpool, layer1 -> L1; layer2 -> L2; layer3 -> L3; every level
     bilinearly upsampled (align_corners=True) to L0's size; channel concat (64+64+128+256).
     ResNet-34 BasicBlock layout [3,4,6] restated from the public architecture (torchvision is
-    absent: PARITY UNPINNED at that boundary).  Returns (latent NCHW, [levels])."""
-    sd = {k[len(prefix):]: T(v) for k, v in sd.items() if k.startswith(prefix)}
-    x = T(images)
-    x = torch.relu(_bn(sd, "bn1", F.conv2d(x, sd["conv1.weight"], stride=2, padding=3), training))
+    absent: PARITY UNPINNED at that boundary).  Returns (latent NCHW, [levels]).
+    dtype: the arithmetic (None = f32; torch.float64 = the high-precision arbiter of the GPU trunk tests); parameters and images are
+    converted differentiably, so leaves of another dtype still receive their gradients, and a float64 state's running
+    statistics are stepped in place like a float32 one's.
+    relu: a trace aid -- the function every relu of the trunk calls, in forward order (None = torch.relu): a hook that records
+    the pre-activations or sets one unit's mask the other way (what an fp32 evaluation does to a unit within its rounding of
+    zero)."""
+    sd = {k[len(prefix):]: T(v, dtype) for k, v in sd.items() if k.startswith(prefix)}
+    x = T(images, dtype)
+    relu = torch.relu if relu is None else relu
+    x = relu(_bn(sd, "bn1", F.conv2d(x, sd["conv1.weight"], stride=2, padding=3), training))
     levels = [x]
     if use_first_pool:  # encoder.py:145-146 (sn64.conf sets use_first_pool = False)
         x = F.max_pool2d(x, 3, 2, 1)
     for li, n in ((1, 3), (2, 4), (3, 6)):
         for b in range(n):
-            x = _block(sd, "layer%d.%d." % (li, b), x, 2 if (b == 0 and li > 1) else 1, training)
+            x = _block(sd, "layer%d.%d." % (li, b), x, 2 if (b == 0 and li > 1) else 1, training, relu)
         levels.append(x)
     size = levels[0].shape[-2:]
     ups = [F.interpolate(l, size, mode="bilinear", align_corners=True) for l in levels]

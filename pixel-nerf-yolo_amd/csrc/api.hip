@@ -532,6 +532,7 @@ int pny_model_bind_param(pny_model* m, const char* name, const float* param_dev)
     else
         m->params_dev.erase(name);
     m->repack_ready = false;
+    if (strncmp(name, "encoder.model.", 14) == 0) trunk_params_rebound(m->trunk);
     return PNY_OK;
 }
 

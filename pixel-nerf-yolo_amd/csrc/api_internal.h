@@ -116,6 +116,7 @@ struct MlpWeightsT {
 namespace pny {
 struct TrunkTrain;                       // training-mode trunk: saved activations and scratch (encoder_train.hip)
 void trunk_release(TrunkTrain* t);
+void trunk_params_rebound(TrunkTrain* t);   // a trunk parameter was bound to new storage: re-resolve its pointers
 }  // namespace pny
 
 using namespace pny;  // private header of host-side translation units only

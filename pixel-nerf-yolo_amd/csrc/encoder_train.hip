@@ -573,6 +573,9 @@ struct TrunkTrain {
     // scratch buffer says when the side stream's last reader of it is done
     hipStream_t side = nullptr;
     hipEvent_t ev_ready = nullptr, ev_join = nullptr, ev_buf[NSCR] = {};
+    // pack-job table: host copy (the source of the stream-ordered upload), and events after the last upload / pack launch
+    std::vector<TrunkPackJob> host_jobs;
+    hipEvent_t ev_upload = nullptr, ev_pack = nullptr;
     bool pend[NSCR] = {};
     bool have_forward = false;
     bool bn_eval = false;    // batch norm on the running statistics (modules in eval() mode under autograd)
@@ -590,6 +593,8 @@ void trunk_release(TrunkTrain* t) {
     if (t->side) (void)hipStreamDestroy(t->side);
     if (t->ev_ready) (void)hipEventDestroy(t->ev_ready);
     if (t->ev_join) (void)hipEventDestroy(t->ev_join);
+    if (t->ev_upload) (void)hipEventDestroy(t->ev_upload);
+    if (t->ev_pack) (void)hipEventDestroy(t->ev_pack);
     for (auto& e : t->ev_buf)
         if (e) (void)hipEventDestroy(e);
     delete t;
@@ -731,9 +736,24 @@ static int trunk_plan(pny_model* m, TrunkTrain& T, int n, int height, int width)
     return 0;
 }
 
-static int trunk_upload_jobs(pny_model* m, TrunkTrain& T) {
+// pny_model_bind_param on a trunk parameter: the pack-job table holds the device pointers of the conv weights it resolved, so a
+// parameter that moved to new storage (load_state_dict(assign=True), p.data = ...) must be resolved again at the next forward
+void trunk_params_rebound(TrunkTrain* t) {
+    if (t) t->n_jobs = 0;
+}
+
+static int trunk_upload_jobs(pny_model* m, TrunkTrain& T, hipStream_t st) {
     std::vector<TrunkPackJob> jobs;
     int rc;
+    // stream-ordered (no device-wide wait): a table uploaded before may still be read by the pack launch of an earlier forward
+    // on another stream, and the previous upload may still be reading host_jobs (rare: after a re-bind or a new shape)
+    if (!T.ev_upload) {
+        PNY_HIP(hipEventCreateWithFlags(&T.ev_upload, hipEventDisableTiming));
+        PNY_HIP(hipEventCreateWithFlags(&T.ev_pack, hipEventDisableTiming));
+    } else {
+        PNY_HIP(hipEventSynchronize(T.ev_upload));     // the previous upload has read host_jobs
+        PNY_HIP(hipStreamWaitEvent(st, T.ev_pack, 0));  // ... and the last pack launch (any stream) the old table
+    }
     for (TrunkUnit& u : T.units) {
         const float* w = nullptr;
         if ((rc = find_param(m, u.conv + ".weight", &w))) return rc;
@@ -757,7 +777,9 @@ static int trunk_upload_jobs(pny_model* m, TrunkTrain& T) {
         }
     }
     if ((rc = T.jobs.reserve(jobs.size() * sizeof(TrunkPackJob)))) return rc;
-    PNY_HIP(hipMemcpy(T.jobs.p, jobs.data(), jobs.size() * sizeof(TrunkPackJob), hipMemcpyHostToDevice));
+    T.host_jobs = jobs;
+    PNY_HIP(hipMemcpyAsync(T.jobs.p, T.host_jobs.data(), jobs.size() * sizeof(TrunkPackJob), hipMemcpyHostToDevice, st));
+    PNY_HIP(hipEventRecord(T.ev_upload, st));
     T.n_jobs = (int)jobs.size();
     return 0;
 }
@@ -811,7 +833,7 @@ int trunk_train_forward(pny_model* m, const float* images, int n, int height, in
     T.bn_eval = bn_eval != 0;
     int rc;
     if ((rc = trunk_plan(m, T, n, height, width))) return rc;
-    if (T.n_jobs == 0 && (rc = trunk_upload_jobs(m, T))) return rc;
+    if (T.n_jobs == 0 && (rc = trunk_upload_jobs(m, T, st))) return rc;
     T.have_forward = false;
     // weights of this step: one launch rebuilds every packed operand from the live parameters
     {
@@ -820,6 +842,7 @@ int trunk_train_forward(pny_model* m, const float* images, int n, int height, in
         int bx = (mx + 255) / 256;
         if (bx > 128) bx = 128;
         hipLaunchKernelGGL(trunk_pack_kernel, dim3(bx, T.n_jobs), dim3(256), 0, st, reinterpret_cast<const TrunkPackJob*>(T.jobs.p));
+        PNY_HIP(hipEventRecord(T.ev_pack, st));
     }
     const long long npx = (long long)n * height * width;
     hipLaunchKernelGGL(trunk_image_to_nhwc4_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, st, images, T.img4, n, height * width);

@@ -721,6 +721,14 @@ class PixelNeRFNet(nn.Module):
             self.num_views_per_obj = 1
         NS, SB = self.num_views_per_obj, self.num_objs
         H, W = int(images.shape[-2]), int(images.shape[-1])
+        trains_trunk = (latent is None and not self.encoder.use_custom_resnet and torch.is_grad_enabled() and self.training
+                        and not self.stop_encoder_grad and any(p.requires_grad for p in self.encoder.parameters()))
+        aten_trunk = trains_trunk and not self._native_trunk_training()
+        if latent is None and not self.encoder.use_custom_resnet and not aten_trunk and (H < 32 or W < 32):
+            # the library's trunks (pny_scene_encode, pny_trunk_train_forward) need every level of the pyramid at least 2 x 2;
+            # only the ATen training graph (forward_torch: PNYOLO_TRUNK=torch, or batch norm modules in mixed modes) takes any size
+            raise ValueError("encode(): the library's ResNet-34 trunk needs images of at least 32 x 32 pixels, got %d x %d "
+                             "(H x W); pass the latent via encode(..., latent=...) instead" % (H, W))
         # focal / principal point formats: reference models.py:125-148
         focal = torch.as_tensor(focal, dtype=torch.float32).cpu()
         if focal.dim() == 0:
@@ -748,9 +756,8 @@ class PixelNeRFNet(nn.Module):
         # Encoder training (the reference's default: train/train.py without --freeze_enc): the trunk runs on the library's training
         # kernels under autograd (_TrunkFunction; the ATen graph forward_torch as the alternative) and its output enters like a
         # supplied latent; the render backward returns d loss / d latent to it
-        if (latent is None and not self.encoder.use_custom_resnet and torch.is_grad_enabled() and self.training
-                and not self.stop_encoder_grad and any(p.requires_grad for p in self.encoder.parameters())):
-            if self._native_trunk_training():
+        if trains_trunk:
+            if not aten_trunk:
                 tp = self._trunk_trainable()
                 latent = _TrunkFunction.apply(self, images.detach().to(dev, torch.float32).contiguous(), *[p for _, p in tp])
             else:   # (batch norm modules in eval() mode under autograd, or parameters the library cannot read in place)
@@ -938,6 +945,9 @@ class _TrunkFunction(torch.autograd.Function):
         bn_eval = not bns[0].training
         check(L.pny_trunk_train_forward(net._h_model, ptr(images), n, H, W, float(bns[0].momentum), int(bn_eval), ptr(lat),
                                         stream_of(dev)))
+        # The library keeps the saved activations of ONE training forward per model: a later forward replaces them, and the
+        # backward of this graph must then refuse instead of differentiating against the other forward's activations
+        net._trunk_generation = ctx.generation = getattr(net, "_trunk_generation", 0) + 1
         if not bn_eval:
             with torch.no_grad():
                 for b in bns:
@@ -951,22 +961,32 @@ class _TrunkFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_lat):
         net = ctx.net
+        if getattr(net, "_trunk_generation", None) != ctx.generation:
+            raise RuntimeError("the library's training trunk holds the activations of a later encode() than this graph's: a "
+                               "training encode() was superseded before its backward (call backward() before the next "
+                               "training encode(), or PNYOLO_TRUNK=torch for gradient accumulation over several encodes)")
         L = _lib.load()
         dev = net._device()
         h = net._h_model
         sizes = [int(np.prod(s)) for s in ctx.shapes]
         offs = np.concatenate([[0], np.cumsum([(s + 63) // 64 * 64 for s in sizes])]).astype(np.int64)
+        ev, net._lat_grad_event = getattr(net, "_lat_grad_event", None), None
+        ev = ev[0] if ev is not None and ev[1]() is d_lat and d_lat._version == ev[2] else None
         d_lat = d_lat.detach().to(dev, torch.float32).contiguous()
         # The trunk's backward needs d loss / d latent and nothing else of the renderer's backward: it runs on a stream of its
         # own that starts behind the point where the latent gradient was complete (render._RenderFunction.backward records it
         # in front of the MLPs' weight-gradient flush), beside that flush; the caller's stream takes it back at the end.
+        # The event covers only the tensor that render backward returned: when autograd summed d_lat from several consumers
+        # (two renders, another loss term on the latent, bind_parallel's per-device shares) or the event is a leftover of
+        # another latent's render, d_lat is another tensor, written on the caller's stream after the event -- wait for that.
         main = torch.cuda.current_stream(dev)
         side = getattr(net, "_trunk_stream", None)
         if os.environ.get("PNYOLO_TRUNK_STREAM", "1") == "0":
             side = main
         elif side is None or side.device != dev:
             side = net._trunk_stream = torch.cuda.Stream(dev)
-        ev, net._lat_grad_event = getattr(net, "_lat_grad_event", None), None
+        # (which of the two orderings ran, for the tests: "event" overlaps the weight-gradient flush, "stream" waits for it)
+        net._last_trunk_wait = "same stream" if side is main else ("event" if ev is not None else "stream")
         if side is not main:
             if ev is not None:
                 side.wait_event(ev)
@@ -1018,6 +1038,7 @@ class _QueryFunction(torch.autograd.Function):
             check(L.pny_query_backward(net._scene(sb), ptr(ctx.xyz[sb]), ptr(ctx.dirs[sb]), ctx.xyz.shape[1], int(use_coarse),
                                        ptr(g_out[sb]), 1, st))
         extra = () if lat_grad is None else (net.end_latent_grad(lat_grad, ctx.lat_meta, SB),)
+        net._lat_grad_event = None      # (unmarked: a trunk backward behind this one waits for the whole stream)
         return (None, None, None, None, None) + tuple(grads) + extra
 
 

@@ -16,6 +16,7 @@ explicit tensors instead (parity mode, consumed by the next call).
 """
 import ctypes as C
 import os
+import weakref
 
 import torch
 
@@ -287,6 +288,19 @@ class _MultiDeviceYoloWrapper(_MultiDeviceRenderWrapper):
         return torch.cat([o.to(dev0) for _, _, o in outs], dim=0)
 
 
+def _mark_latent_grad(model, extra, dev):
+    """Record where on the current stream the latent gradient `extra` (this backward's d loss / d latent, if any) is complete,
+    together with a weak reference to that very tensor and its version: model._TrunkFunction.backward starts behind the event
+    only when the gradient it receives IS that tensor, unmodified (autograd adds another consumer's gradient into it in place
+    when it can), and otherwise waits for the whole stream.  A backward without a latent gradient
+    clears the mark."""
+    model._lat_grad_event = None
+    if extra:
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        model._lat_grad_event = (ev, weakref.ref(extra[0]), extra[0]._version)
+
+
 class _RenderFunction(torch.autograd.Function):
     """NeRFRenderer.forward under autograd: forward = the ordinary pny_render (with its z / per-sample outputs kept),
     backward = pny_render_backward per scene, which accumulates into gradient buffers bound to the MLP parameters."""
@@ -363,9 +377,7 @@ class _RenderFunction(torch.autograd.Function):
             check(L.pny_render_backward(model._h_group, ptr(sv["rays"]), SB * B, C.byref(sv["opts"][0]), C.byref(s_), C.byref(g_),
                                         acc, stream_of(dev)))
             extra = () if lat_grad is None else (model.end_latent_grad(lat_grad, ctx.lat_meta, SB, group=True),)
-            if lat_grad is not None:
-                model._lat_grad_event = torch.cuda.Event()
-                model._lat_grad_event.record(torch.cuda.current_stream(dev))
+            _mark_latent_grad(model, extra, dev)
             check(L.pny_model_flush_weight_grads(model._h_model, 1, stream_of(dev)))
             check(L.pny_model_defer_weight_grads(model._h_model, 0, 0, 0, 0))
             return (None, None, None, None, None) + tuple(grads) + extra
@@ -413,9 +425,7 @@ class _RenderFunction(torch.autograd.Function):
         # d loss / d latent is complete here, BEFORE the weight-gradient flush is enqueued: the encoder's backward (the trunk's
         # kernels, model._TrunkFunction) starts behind this point on its own stream and runs beside the flush
         extra = () if lat_grad is None else (model.end_latent_grad(lat_grad, ctx.lat_meta, SB),)
-        if lat_grad is not None:
-            model._lat_grad_event = torch.cuda.Event()
-            model._lat_grad_event.record(torch.cuda.current_stream(dev))
+        _mark_latent_grad(model, extra, dev)
         if deferred:
             check(L.pny_model_flush_weight_grads(model._h_model, 1 | (16 if split else 0), stream_of(dev)))
             if fstream is not None:
@@ -756,6 +766,7 @@ class _YoloRenderFunction(torch.autograd.Function):
         check(L.pny_yolo_render_backward(net._scene(0), ptr(sv["rays"]), sv["rays"].shape[0], sv["n_coarse"], ptr(sv["u"]),
                                          sv["seed"], ptr(sv["raw"]), ptr(g_out), 1, stream_of(dev)))
         extra = () if lat_grad is None else (net.end_latent_grad(lat_grad, ctx.lat_meta, 1),)
+        net._lat_grad_event = None      # (unmarked: a trunk backward behind this one waits for the whole stream)
         return (None, None, None) + tuple(grads) + extra
 
 

@@ -52,6 +52,37 @@ def oracle_scene(g, seed):
     return orc.Scene(mc, mf, lat, g["src_poses"], g["focal"], g["c"][None], W, H)
 
 
+RTOL = 1e-4      # every gradient tensor within 1e-4 x its own max |.| (gradients sum 10^4..10^5 fp32 products)
+
+
+def grad_check(name, got, ref, rtol=RTOL):
+    ref = torch.as_tensor(np.asarray(ref), dtype=torch.float32)
+    scale = max(float(ref.abs().max()), 1e-20)
+    err = float((got.detach().cpu().float() - ref).abs().max())
+    assert err <= rtol * scale, "%s: max |err| %.3e vs max |grad| %.3e (ratio %.2e)" % (name, err, scale, err / scale)
+    return err / scale
+
+
+def compare_param_grads(net, sc, which=("mlp_coarse", "mlp_fine"), rtol=RTOL):
+    worst = 0.0
+    for pre in which:
+        mlp, ref = getattr(net, pre), getattr(sc, pre)
+        if mlp is None:
+            continue
+        for k, p in mlp.named_parameters():
+            assert p.grad is not None, pre + "." + k
+            r = ref[k].grad if ref[k].grad is not None else torch.zeros_like(ref[k])
+            worst = max(worst, grad_check(pre + "." + k, p.grad, r, rtol))
+    return worst
+
+
+def render_loss(out, gt, with_depth=False):
+    loss = torch.nn.functional.mse_loss(out["coarse"]["rgb"], gt) + torch.nn.functional.mse_loss(out["fine"]["rgb"], gt)
+    if with_depth:
+        loss = loss + 0.1 * out["fine"]["depth"].mean() + 0.05 * out["coarse"]["depth"].square().mean()
+    return loss
+
+
 def maxabs(a, b):
     a = torch.as_tensor(np.asarray(a.detach().cpu() if torch.is_tensor(a) else a), dtype=torch.float32)
     b = torch.as_tensor(np.asarray(b.detach().cpu() if torch.is_tensor(b) else b), dtype=torch.float32)

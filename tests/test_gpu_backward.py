@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import pnyolo_oracle as orc
-from helpers import DEV, clean_points, clean_rays, dt, load_mlp, maxabs
+from helpers import DEV, RTOL, clean_points, clean_rays, compare_param_grads, dt, grad_check, load_mlp, maxabs, render_loss
 from pixel_nerf_yolo_amd import conf as pconf
 from pixel_nerf_yolo_amd import lib as plib
 from pixel_nerf_yolo_amd import synth
@@ -21,7 +21,6 @@ from pixel_nerf_yolo_amd.model import make_model
 from pixel_nerf_yolo_amd.render import NeRFRenderer
 
 pytestmark = pytest.mark.gpu
-RTOL = 1e-4
 
 
 @pytest.fixture(autouse=True, params=["dw_f32", "dw_f16x2"])
@@ -38,14 +37,6 @@ def training_forward_arithmetic(request, monkeypatch):
     # (csrc/mlp_bwd_h2.hip, pny_dw_gemm_h2_kernel: gradients scaled by powers of two), the latter being the default of scenes
     # that are not pinned to F32.  Same oracle, same tolerances; EVERY test of this module runs under both.
     monkeypatch.setenv("PNYOLO_BWD_PRECISION", "f32" if request.param == "dw_f32" else "f16x2")
-
-
-def grad_check(name, got, ref, rtol=RTOL):
-    ref = torch.as_tensor(np.asarray(ref), dtype=torch.float32)
-    scale = max(float(ref.abs().max()), 1e-20)
-    err = float((got.detach().cpu().float() - ref).abs().max())
-    assert err <= rtol * scale, "%s: max |err| %.3e vs max |grad| %.3e (ratio %.2e)" % (name, err, scale, err / scale)
-    return err / scale
 
 
 # --------------------------------------------------------------------------- composite
@@ -139,19 +130,6 @@ def scene_pair(ns, H, W, L, d_out, n_blocks, combine_layer, seed, yolo=False, la
     return net, sc
 
 
-def compare_param_grads(net, sc, which=("mlp_coarse", "mlp_fine"), rtol=RTOL):
-    worst = 0.0
-    for pre in which:
-        mlp, ref = getattr(net, pre), getattr(sc, pre)
-        if mlp is None:
-            continue
-        for k, p in mlp.named_parameters():
-            assert p.grad is not None, pre + "." + k
-            r = ref[k].grad if ref[k].grad is not None else torch.zeros_like(ref[k])
-            worst = max(worst, grad_check(pre + "." + k, p.grad, r, rtol))
-    return worst
-
-
 @pytest.mark.parametrize("cfg", [
     dict(ns=2, L=512, d_out=4, n_blocks=5, combine_layer=3, n=200),        # the shipped multi-view shape
     dict(ns=3, L=512, d_out=4, n_blocks=5, combine_layer=3, n=65),         # ragged tile
@@ -228,13 +206,6 @@ def test_query_backward_yolo_mode():
 
 
 # --------------------------------------------------------------------------- render backward
-def render_loss(out, gt, with_depth=False):
-    loss = torch.nn.functional.mse_loss(out["coarse"]["rgb"], gt) + torch.nn.functional.mse_loss(out["fine"]["rgb"], gt)
-    if with_depth:
-        loss = loss + 0.1 * out["fine"]["depth"].mean() + 0.05 * out["coarse"]["depth"].square().mean()
-    return loss
-
-
 @pytest.mark.parametrize("with_depth,detach", [(False, True), (True, True), (False, False), (True, False)])
 def test_render_backward_vs_oracle(with_depth, detach):
     """The trainer's loss (MSE on coarse.rgb + MSE on fine.rgb, PixelNerfTrainer.py:133-156) through the renderer.
@@ -906,7 +877,8 @@ def test_encoder_training_gradients_vs_oracle_autograd(trunk, monkeypatch):
     convolutions, batch norm, pool, pyramid, forward and backward; `trunk` = native) or, PNYOLO_TRUNK=torch, as a torch graph
     of the same modules; either way the HIP renderer's backward returns d loss / d latent to it.  Batch norm in eval() mode here
     on both sides (the reference's pretrained statistics; batch statistics: the next test); trunk parameter gradients against
-    torch.autograd through the oracle's trunk + renderer, MLP gradients from the same backward."""
+    torch.autograd through the oracle's trunk + renderer, MLP gradients from the same backward.  (Other shapes, re-bound
+    parameters, superseded forwards and shared latents: tests/test_gpu_trunk.py.)"""
     monkeypatch.setenv("PNYOLO_TRUNK", trunk)
     if trunk == "torch":
         # MIOpen's Winograd / CK convolutions put the latent ~1e-5 from the oracle's, enough to flip a relu unit of the MLPs that
@@ -990,7 +962,8 @@ def test_trunk_training_batch_statistics_vs_oracle_autograd(use_first_pool):
     statistics up afterwards.  use_first_pool = False is conf/exp/sn64.conf (no max-pool in front of layer1).
     (The trunk's gradient is as discontinuous in its relu inputs as the MLP's: with seed 1803 and no pool one unit sits within
     fp32 rounding of zero -- this path and ATen's then differ by 3e-4 on one tensor, and BOTH differ from the same graph in
-    fp64 by 3e-2, tools/debug/trunk_err.py; the seeds used here have no such unit: 2e-6 on every tensor.)"""
+    fp64 by 3e-2, tools/debug/trunk_err.py; the seeds used here have no such unit: 2e-6 on every tensor.)  Odd, non-square
+    and larger shapes against an fp64 oracle: tests/test_gpu_trunk.py."""
     SB, ns, H, W = 2, 2, 64, 64
     seed = 1803 if use_first_pool else 2803
     c = pconf.default_mv()

@@ -31,13 +31,7 @@ lat_ref = orc.spatial_encoder(enc_t, images.reshape(-1, 3, H, W), use_first_pool
 (lat_ref * G).sum().backward()
 import torch.nn.functional as F
 def enc64_run():
-    T0 = orc.T
-    orc.T = lambda v: v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
-    try:
-        out = orc.spatial_encoder(enc64, images.reshape(-1, 3, H, W).double(), use_first_pool=pool, training=True)[0]
-    finally:
-        orc.T = T0
-    return out
+    return orc.spatial_encoder(enc64, images.reshape(-1, 3, H, W), use_first_pool=pool, training=True, dtype=torch.float64)[0]
 l64 = enc64_run(); (l64 * G.double()).sum().backward()
 print("latent: hip vs fp32 oracle %.2e, fp32 oracle vs fp64 %.2e, hip vs fp64 %.2e (max |lat| %.2f)" % (
     float((lat.detach().cpu() - lat_ref.detach()).abs().max()), float((lat_ref.detach().double() - l64.detach()).abs().max()),
