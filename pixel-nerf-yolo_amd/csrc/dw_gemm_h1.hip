@@ -1,189 +1,5 @@
-// The weight-gradient GEMM of PNY_PRECISION_F16_TRAIN: pny_dw_gemm_h2_kernel (mlp_bwd.hip) with ONE f16 plane per operand --
-// dW_l[n][k] = sum_samples dY_l[s][n] X_l[s][k], both operands rounded to f16 (dY after the launch's power-of-two scale, X the
-// fp32 stash as it is), one v_mfma_f32_32x32x16_f16 per product and 16 samples instead of three, fp32 accumulation.  Everything
-// else is the split kernel's: the work items and split-K partial tiles (train_api.hip build_items), the per-launch scale that
-// puts max |dY| at 2^13..2^14 (so elements down to 2^-27 of the maximum stay normal f16), the fp32 bias sums, the
-// deterministic reduction (pny_dw_reduce_kernel).  The LDS images are the split kernel's with one plane: [c = 0..3][feature
-// 0..255 (+1 pad)] x 16 bytes per operand, two buffers = 64.25 KiB.  A kernel of its own translation unit, so that the machine
-// code of the split kernel stays as it is.
-#include "mlp_bwd_core.h"
-
-namespace pny {
-
-namespace {
-typedef _Float16 dw1h8 __attribute__((ext_vector_type(8)));
-constexpr int DW1_TILE = 256;                                // output tile (as mlp_bwd.hip DW_TILE)
-constexpr int DW1_CS = 257;                                  // 16-byte entries per c row (256 features + 1 pad)
-constexpr int DW1_PLANE = 4 * DW1_CS;                        // entries per operand image
-constexpr int DW1_BUF = 2 * DW1_PLANE;                       // entries per buffer: A, X
-constexpr size_t DW1_LDS_BYTES = (size_t)2 * DW1_BUF * 16;   // 65792
-
-// two fp32 values to one f16 pair (round to nearest even)
-__device__ __forceinline__ unsigned dw1_cvt2(float a, float b) {
-    unsigned p;
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(p) : "v"(a), "v"(b));
-    return p;
-}
-}  // namespace
-
-template <bool FULL>   // FULL: complete 256 x 256 tiles, predicate-free; otherwise rows / columns beyond the job are zero-filled and skipped
-__global__ __launch_bounds__(512, 2) void pny_dw_gemm_h1_kernel(const DwJob* __restrict__ jobs, const DwItem* __restrict__ items,
-                                                                const float* __restrict__ x_stash,
-                                                                const float* __restrict__ dy_stash, long long x_tile,
-                                                                long long dy_tile, float* __restrict__ partial,
-                                                                float* __restrict__ bias_partial,
-                                                                const unsigned* __restrict__ dy_absmax) {
-    extern __shared__ __attribute__((aligned(16))) float dw1_lds[];
-    uint4* lds = reinterpret_cast<uint4*>(dw1_lds);
-    const DwItem it = items[blockIdx.x];
-    const DwJob jb = jobs[it.job];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 2, wc = wave & 3, hh = lane >> 5, l31 = lane & 31;
-    const int row0 = it.mt * DW1_TILE, col0 = it.nt * DW1_TILE;
-
-    // scale = 2^(13 - floor(log2(max |dY|))), clamped to the normal range
-    float scale = 1.0f, inv_scale = 1.0f;
-    {
-        const unsigned mb = *dy_absmax;
-        int e = (int)((mb >> 23) & 0xffu) - 127;
-        if (mb != 0u && e > -100 && e < 100) {
-            scale = __uint_as_float((unsigned)(127 + 13 - e) << 23);
-            inv_scale = __uint_as_float((unsigned)(127 - 13 + e) << 23);
-        }
-    }
-
-    f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    // staging role of this thread: operand (waves 0..3: A = dY, waves 4..7: X), feature quad fq of the tile, sample group c
-    const int op = wave >> 2;
-    const int fq = (tid & 255) >> 2, c = tid & 3;
-    const float sc = op == 0 ? scale : 1.0f;
-    const bool want_bias = op == 0 && it.nt == 0;
-    float bs[4] = {0.f, 0.f, 0.f, 0.f};
-    float4 r[8];
-    const int extent = op == 0 ? jb.a_rows - row0 : jb.x_cols - col0;
-    const bool q_load = FULL || 4 * fq < extent, q_write = FULL || 4 * fq < ((extent + 31) & ~31);
-    bool live_a[4], live_x[2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) live_a[i] = FULL || row0 + wr * 128 + 32 * i < jb.a_rows;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) live_x[j] = FULL || col0 + wc * 64 + 32 * j < jb.x_cols;
-    auto fetch = [&](int h) {
-        const int tv = it.tv_lo + (h >> 1), half = h & 1;
-        const int tile = tv / jb.n_views, v = tv - tile * jb.n_views;
-        const float* rec = op == 0 ? dy_stash + (long long)tile * dy_tile + jb.a_off + (long long)v * jb.a_view
-                                   : x_stash + (long long)tile * x_tile + jb.x_off + (long long)v * jb.x_view;
-        const float4* g = reinterpret_cast<const float4*>(rec) + ((op == 0 ? row0 : col0) / 4 + fq) * 64 + 32 * half + c;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) r[i] = q_load ? g[4 * i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    auto stage = [&](int b) {
-        uint4* img = lds + b * DW1_BUF + op * DW1_PLANE + c * DW1_CS + 4 * fq;
-        if (!q_write) return;
-        if (want_bias) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {   // (asm: keeps the SLP vectoriser from packing these into v_pk_add_f32 beside the MFMAs)
-                asm("v_add_f32 %0, %1, %0" : "+v"(bs[0]) : "v"(r[i].x));
-                asm("v_add_f32 %0, %1, %0" : "+v"(bs[1]) : "v"(r[i].y));
-                asm("v_add_f32 %0, %1, %0" : "+v"(bs[2]) : "v"(r[i].z));
-                asm("v_add_f32 %0, %1, %0" : "+v"(bs[3]) : "v"(r[i].w));
-            }
-        }
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            float v[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = (f == 0 ? r[i].x : f == 1 ? r[i].y : f == 2 ? r[i].z : r[i].w) * sc;
-            img[f] = make_uint4(dw1_cvt2(v[0], v[1]), dw1_cvt2(v[2], v[3]), dw1_cvt2(v[4], v[5]), dw1_cvt2(v[6], v[7]));
-        }
-    };
-    const int n_half = 2 * (it.tv_hi - it.tv_lo);
-    if (n_half > 0) {
-        fetch(0);
-        stage(0);
-        if (n_half > 1) fetch(1);
-        __syncthreads();
-    }
-    auto mm = [&](int cb) {   // the MFMAs of one half on buffer cb
-        const uint4* pa = lds + cb * DW1_BUF + hh * DW1_CS + wr * 128 + l31;
-        const uint4* px = lds + cb * DW1_BUF + DW1_PLANE + hh * DW1_CS + wc * 64 + l31;
-#pragma unroll
-        for (int st = 0; st < 2; ++st) {       // 16 samples per step: this lane's 8 are group c = 2 st + hh
-            dw1h8 a1[4] = {}, x1[2] = {};
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (FULL || live_a[i]) a1[i] = __builtin_bit_cast(dw1h8, pa[2 * st * DW1_CS + 32 * i]);
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                if (FULL || live_x[j]) x1[j] = __builtin_bit_cast(dw1h8, px[2 * st * DW1_CS + 32 * j]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    if (FULL || (live_a[i] && live_x[j])) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1[i], x1[j], acc[i][j], 0, 0, 0);
-        }
-    };
-    for (int h = 0; h < n_half; ++h) {
-        const int cb = h & 1;
-        if (h + 1 < n_half) {
-            stage(cb ^ 1);                     // half h + 1: every wave left that buffer at the previous barrier
-            if (h + 2 < n_half) fetch(h + 2);
-        }
-        mm(cb);
-        __syncthreads();
-    }
-    float* P = partial + it.part_off;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            if (!FULL && !(live_a[i] && live_x[j])) continue;
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) {
-                const int row = row0 + wr * 128 + 32 * i + 8 * (rr >> 2) + 4 * hh + (rr & 3);
-                const int col = col0 + wc * 64 + 32 * j + l31;
-                if (FULL || (row < jb.a_rows && col < jb.x_cols)) P[(long long)row * jb.x_cols + col] = acc[i][j][rr] * inv_scale;
-            }
-        }
-    if (want_bias) {   // the four lanes c = 0..3 of a feature quad hold the sums of their own samples
-        float* B = bias_partial + it.bias_off;
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            float t = bs[f];
-            t += __shfl_xor(t, 1, 64);
-            t += __shfl_xor(t, 2, 64);
-            if (c == 0 && (FULL || row0 + 4 * fq + f < jb.a_rows)) B[row0 + 4 * fq + f] = t;
-        }
-    }
-}
-
-// launch_dw_gemm's split (mlp_bwd.hip) for the single-plane kernel: n_part clipped items first on `sp`, n_full complete tiles on `st`
-void launch_dw_gemm_h1(const DwJob* jobs_dev, const DwItem* items_dev, int n_part, int n_full, const float* x_stash,
-                       const float* dy_stash, long long x_tile, long long dy_tile, float* partial, float* bias_partial, hipStream_t st,
-                       hipStream_t sp, const unsigned* dy_absmax) {
-    static bool attr_set[64] = {};
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
-    dev_ &= 63;
-    if (!attr_set[dev_]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pny_dw_gemm_h1_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)DW1_LDS_BYTES);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pny_dw_gemm_h1_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)DW1_LDS_BYTES);
-        attr_set[dev_] = true;
-    }
-    if (n_part > 0)
-        hipLaunchKernelGGL(pny_dw_gemm_h1_kernel<false>, dim3(n_part), dim3(512), DW1_LDS_BYTES, sp, jobs_dev, items_dev, x_stash, dy_stash,
-                           x_tile, dy_tile, partial, bias_partial, dy_absmax);
-    if (n_full > 0)
-        hipLaunchKernelGGL(pny_dw_gemm_h1_kernel<true>, dim3(n_full), dim3(512), DW1_LDS_BYTES, st, jobs_dev, items_dev + n_part, x_stash,
-                           dy_stash, x_tile, dy_tile, partial, bias_partial, dy_absmax);
-}
-
-}  // namespace pny
+// The weight-gradient GEMM of PNY_PRECISION_F16_TRAIN: dw_gemm_h2.hip with ONE f16 plane per operand (pny_dw_gemm_h1_kernel),
+// one v_mfma_f32_32x32x16_f16 per product and 16 samples, fp32 accumulation, the same per-launch power-of-two scale of dY
+// (dw_gemm_h2.hip header).
+#define PNY_H2_PLANES 1
+#include "dw_gemm_h2.hip"

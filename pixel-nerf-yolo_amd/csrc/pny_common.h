@@ -94,10 +94,6 @@ struct MlpArgs {
     const float* h2_in;
     const float* h2_fc0[MAX_BLOCKS];
     const float* h2_fc1[MAX_BLOCKS];
-    // the same layers in the 16 x 16 x 32 MFMA's operand order (mlp_h2w.hip; api.hip pack_layer_h3)
-    const float* h3_in;
-    const float* h3_fc0[MAX_BLOCKS];
-    const float* h3_fc1[MAX_BLOCKS];
     // f16-range guard (include/pnyolo.h pny_model_range_status): host-visible word the f16x2 kernels OR PNY_RANGE_* bits into
     unsigned* range_flag;
     // Source-view cameras travel in the kernel-argument segment (NS entries used; 64 B each): a launch carries its own
@@ -106,7 +102,7 @@ struct MlpArgs {
 };
 
 // ---- device-side weight repack (pack.hip): the packed operand layouts rebuilt from the live parameter tensors
-enum { PACK_A = 0, PACK_AT = 1, PACK_NT = 2, PACK_COPY = 3, PACK_ADD2 = 4, PACK_H2 = 5, PACK_NTT = 6, PACK_H2T = 7, PACK_H3 = 8, PACK_H1 = 9 };
+enum { PACK_A = 0, PACK_AT = 1, PACK_NT = 2, PACK_COPY = 3, PACK_ADD2 = 4, PACK_H2 = 5, PACK_NTT = 6, PACK_H2T = 7, PACK_H1 = 9 };
 struct PackJob {
     const float* src;
     const float* src2;
@@ -194,11 +190,13 @@ void launch_mlp_bwd_h1(const BwdArgs& a, int grid, hipStream_t st);   // mlp_bwd
 void launch_dw_gemm(const DwJob* jobs_dev, const DwItem* items_dev, int n_part, int n_full, const float* x_stash,
                     const float* dy_stash, long long x_tile, long long dy_tile, float* partial, float* bias_partial, hipStream_t st,
                     hipStream_t aux, hipEvent_t ev_fork, hipEvent_t ev_join, const unsigned* dy_absmax = nullptr, int planes = 2);
-void launch_dw_gemm_h1(const DwJob* jobs_dev, const DwItem* items_dev, int n_part, int n_full, const float* x_stash,   // dw_gemm_h1.hip
+// the f16 paths of launch_dw_gemm, one per plane count (dw_gemm_h2.hip; dw_gemm_h1.hip): clipped items on sp, complete ones on st
+void launch_dw_gemm_h2(const DwJob* jobs_dev, const DwItem* items_dev, int n_part, int n_full, const float* x_stash,
                        const float* dy_stash, long long x_tile, long long dy_tile, float* partial, float* bias_partial, hipStream_t st,
                        hipStream_t sp, const unsigned* dy_absmax);
-void launch_latent_grad_h1(const MlpArgs& a, const float* dy_stash, const StashLayout& lay, const float* w_cat, float* grad, int nvb,
-                           hipStream_t st, const unsigned* dy_absmax);   // latent_grad_h1.hip
+void launch_dw_gemm_h1(const DwJob* jobs_dev, const DwItem* items_dev, int n_part, int n_full, const float* x_stash,
+                       const float* dy_stash, long long x_tile, long long dy_tile, float* partial, float* bias_partial, hipStream_t st,
+                       hipStream_t sp, const unsigned* dy_absmax);
 void launch_dw_reduce(const DwTarget* targets_dev, int n_targets, long long max_elems, const float* partial,
                       const float* bias_partial, int accumulate, hipStream_t st);
 void launch_composite_bwd(const float* rays, const float* z, const float* samp, const float* noise, long long n, int k,
@@ -214,15 +212,17 @@ void launch_mlp_stash(const MlpArgs& a, int grid, hipStream_t st);  // 8x64 shap
 // kernel of F16_TRAIN); null: fp32 MFMA
 void launch_latent_grad(const MlpArgs& a, const float* dy_stash, const StashLayout& lay, const float* w_cat, float* grad, int nvb,
                         hipStream_t st, const unsigned* dy_absmax = nullptr, int planes = 2);
+// the f16 paths of launch_latent_grad, one per plane count (latent_grad_h2.hip; latent_grad_h1.hip)
+void launch_latent_grad_h2(const MlpArgs& a, const float* dy_stash, const StashLayout& lay, const float* w_cat, float* grad, int nvb,
+                           hipStream_t st, const unsigned* dy_absmax);
+void launch_latent_grad_h1(const MlpArgs& a, const float* dy_stash, const StashLayout& lay, const float* w_cat, float* grad, int nvb,
+                           hipStream_t st, const unsigned* dy_absmax);
 bool mlp_h2_supports(int n_blocks, int combine_layer);
 void launch_mlp_h2(const MlpArgs& a, int grid, hipStream_t st);
 void launch_mlp_h1(const MlpArgs& a, int grid, hipStream_t st);    // mlp_h1.hip: single f16 plane per operand (PNY_PRECISION_F16), 64-sample tiles
 void launch_mlp_h2s(const MlpArgs& a, int grid, hipStream_t st);   // mlp_h2s.hip: a.n_tiles in 32-sample tiles, grid <= 2 x CUs
 void launch_mlp_h1_stash(const MlpArgs& a, int grid, hipStream_t st);   // mlp_h1.hip STASH instantiation (PNY_PRECISION_F16_TRAIN)
 void launch_mlp_h2_stash(const MlpArgs& a, int grid, hipStream_t st);   // + the backward's operand stash (a.stash_x, a.lay)     // 8x64 shape, projected latent, split-f16 operands (mlp_h2.hip)
-bool mlp_h2w_supports(int n_blocks, int combine_layer);
-void launch_mlp_h2n(const MlpArgs& a, int grid, hipStream_t st);   // mlp_h2n.hip: the same kernel as 8 waves x 256 registers
-void launch_mlp_h2w(const MlpArgs& a, int grid, hipStream_t st);   // mlp_h2w.hip: 4 waves x 512 registers, needs a.h3_*; 64-sample tiles
 int mlp_max_grid(int variant);      // resident workgroups = persistent grid size
 int mlp_tile_samples(int variant);  // samples per workgroup tile (32 or 64)
 size_t mlp_scratch_floats();

@@ -198,7 +198,7 @@ void build_items(TrainPlan& p, int n_tiles, int cus, std::vector<DwItem>& items,
 
 // Matrix arithmetic of the backward's GEMMs (dX chain and weight gradients): the scene's precision setting (F32 pins the fp32
 // MFMA; F16_TRAIN = single-plane f16: mlp_bwd_h1.hip, dw_gemm_h1.hip, latent_grad_h1.hip; anything else = split f16:
-// mlp_bwd_h2.hip pny_mlp_bwd_h2_kernel, mlp_bwd.hip pny_dw_gemm_h2_kernel); env PNYOLO_BWD_PRECISION=f32|f16x2 overrides (read
+// mlp_bwd_h2.hip pny_mlp_bwd_h2_kernel, dw_gemm_h2.hip pny_dw_gemm_h2_kernel); env PNYOLO_BWD_PRECISION=f32|f16x2 overrides (read
 // at every call: tests vary it).  0 fp32, 1 split f16, 2 single-plane f16.
 int bwd_prec(const pny_scene* s) {
     if (const char* e = getenv("PNYOLO_BWD_PRECISION")) {

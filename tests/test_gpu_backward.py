@@ -167,7 +167,7 @@ def test_query_backward_vs_oracle_autograd(cfg):
 @pytest.mark.parametrize("gscale", [1e-9, 3e-4, 7e5])
 def test_weight_gradients_f16x2_any_gradient_scale(gscale, monkeypatch):
     """The split-f16 weight-gradient GEMM multiplies dY by a power of two taken from the chain kernel's running max |dY|
-    (csrc/mlp_bwd.hip pny_dw_gemm_h2_kernel): an upstream gradient 1e-9 or 7e5 times larger gives the same gradients times
+    (csrc/dw_gemm_h2.hip pny_dw_gemm_h2_kernel): an upstream gradient 1e-9 or 7e5 times larger gives the same gradients times
     that factor (f16 alone has neither the range nor the denormal precision for it), and they agree with the fp32 MFMA's."""
     n = 200
     net, _ = scene_pair(2, 32, 40, 512, 4, 5, 3, 1234)
