@@ -86,11 +86,11 @@ def gen_rays_yolo(poses, width, height, focal, c, z_near, z_far):
 # ----------------------------------------------------------------------------- sampling
 def sample_coarse(rays, n_coarse, u, lindisp=False):
     """src/render/nerf.py:104-121 (same arithmetic in src/render/yolo.py:15-26).
-    u (N,Kc) ~ U[0,1) is the renderer's first random draw (unconditional, also in eval)."""
+    u (N,Kc) ~ U[0,1) is the renderer's first random draw (unconditional, also in eval).  The arithmetic is rays' dtype."""
     near, far = rays[:, 6:7], rays[:, 7:8]
     step = 1.0 / n_coarse
-    t = torch.linspace(0, 1 - step, n_coarse, dtype=f32)[None, :].repeat(rays.shape[0], 1)
-    t = t + T(u) * step
+    t = torch.linspace(0, 1 - step, n_coarse, dtype=rays.dtype)[None, :].repeat(rays.shape[0], 1)
+    t = t + T(u, rays.dtype) * step
     if not lindisp:
         return near * (1 - t) + far * t
     return 1 / (1 / near * (1 - t) + 1 / far * t)
@@ -102,9 +102,9 @@ def sample_fine(rays, weights, u, u2, n_coarse, lindisp=False):
     pdf = w / torch.sum(w, -1, keepdim=True)
     cdf = torch.cumsum(pdf, -1)
     cdf = torch.cat([torch.zeros_like(cdf[:, :1]), cdf], -1)
-    inds = torch.searchsorted(cdf, T(u).contiguous(), right=True).float() - 1.0
+    inds = torch.searchsorted(cdf, T(u, cdf.dtype).contiguous(), right=True).to(cdf.dtype) - 1.0
     inds = torch.clamp_min(inds, 0.0)
-    t = (inds + T(u2)) / n_coarse
+    t = (inds + T(u2, cdf.dtype)) / n_coarse
     near, far = rays[:, 6:7], rays[:, 7:8]
     if not lindisp:
         return near * (1 - t) + far * t
@@ -114,7 +114,7 @@ def sample_fine(rays, weights, u, u2, n_coarse, lindisp=False):
 def sample_fine_depth(rays, depth, g, depth_std):
     """src/render/nerf.py:156-167.  g (N,Kfd) ~ N(0,1): the 4th random draw."""
     z = depth[:, None].repeat(1, g.shape[1])
-    z = z + T(g) * depth_std
+    z = z + T(g, z.dtype) * depth_std
     return torch.max(torch.min(z, rays[:, 7:8]), rays[:, 6:7])
 
 
@@ -126,7 +126,7 @@ def composite(rays, z, out, white_bkgd, sigma_noise=None):
     deltas = torch.cat([z[:, 1:] - z[:, :-1], rays[:, 7:8] - z[:, -1:]], -1)
     rgbs, sigmas = out[..., :3], out[..., 3]
     if sigma_noise is not None:
-        sigmas = sigmas + T(sigma_noise)
+        sigmas = sigmas + T(sigma_noise, sigmas.dtype)
     alphas = 1 - torch.exp(-deltas * torch.relu(sigmas))
     shifted = torch.cat([torch.ones_like(alphas[:, :1]), 1 - alphas + 1e-10], -1)
     Tr = torch.cumprod(shifted, -1)
@@ -151,29 +151,31 @@ def yolo_aggregate(out, n_anchors=3):
 # ----------------------------------------------------------------------------- model pieces
 def positional_encoding(x, num_freqs=6, freq_factor=1.5):
     """src/model/code.py:11-42: out = [x, sin(f0 x), sin(f0 x + pi/2), sin(f1 x), ...] with the
-    argument formed as fp32 (phase + x*freq); cos is obtained as sin(. + pi/2)."""
-    freqs = freq_factor * 2.0 ** torch.arange(0, num_freqs)
-    fr = torch.repeat_interleave(freqs, 2).view(1, -1, 1).to(f32)
-    ph = torch.zeros(2 * num_freqs)
+    argument formed as fp32 (phase + x*freq; float64 for a float64 x); cos is obtained as sin(. + pi/2)."""
+    dt = torch.float64 if x.dtype == torch.float64 else f32
+    freqs = freq_factor * 2.0 ** torch.arange(0, num_freqs, dtype=dt)
+    fr = torch.repeat_interleave(freqs, 2).view(1, -1, 1).to(dt)
+    ph = torch.zeros(2 * num_freqs, dtype=dt)
     ph[1::2] = math.pi * 0.5
-    ph = ph.view(1, -1, 1).to(f32)
+    ph = ph.view(1, -1, 1).to(dt)
     e = x.unsqueeze(1).repeat(1, num_freqs * 2, 1)
     e = torch.sin(ph + e * fr)
     return torch.cat((x, e.view(x.shape[0], -1)), dim=-1)
 
 
-def encode_cameras(poses, focal, c, width, height, yolo=False):
+def encode_cameras(poses, focal, c, width, height, yolo=False, dtype=None):
     """src/model/models.py:115-148: cam->world poses inverted analytically to world->cam
     [R^T | -R^T t] (YOLO mode: extrinsics used as given); focal -> (.,2) with fy negated
-    (non-YOLO); principal point defaults to the image centre."""
-    poses = T(poses).reshape(-1, 4, 4)
+    (non-YOLO); principal point defaults to the image centre.  dtype: the arithmetic (None = f32)."""
+    dt = f32 if dtype is None else dtype
+    poses = T(poses, dt).reshape(-1, 4, 4)
     if not yolo:
         rot = poses[:, :3, :3].transpose(1, 2)
         trans = -torch.bmm(rot, poses[:, :3, 3:])
         w2c = torch.cat((rot, trans), dim=-1)
     else:
         w2c = poses[:, :3, :4].clone()
-    focal = T(focal)
+    focal = T(focal, dt)
     if focal.dim() == 0:
         focal = focal[None, None].repeat(1, 2)
     elif focal.dim() == 1:
@@ -183,9 +185,9 @@ def encode_cameras(poses, focal, c, width, height, yolo=False):
     if not yolo:
         focal[..., 1] *= -1.0
     if c is None:
-        c = torch.tensor([[width * 0.5, height * 0.5]], dtype=f32)
+        c = torch.tensor([[width * 0.5, height * 0.5]], dtype=dt)
     else:
-        c = T(c)
+        c = T(c, dt)
         if c.dim() == 0:
             c = c[None, None].repeat(1, 2)
         elif c.dim() == 1:
@@ -193,15 +195,18 @@ def encode_cameras(poses, focal, c, width, height, yolo=False):
     return w2c, focal, c
 
 
-def index_latent(latent, uv, width, height):
+def index_latent(latent, uv, width, height, dtype=None):
     """src/model/encoder.py:79-108 with index_padding=zeros (conf/default.conf:49),
     align_corners=True, bilinear.  latent (NS,L,Hl,Wl); uv (NS,P,2) in image pixels.
     Returns (NS,P,L).  The bilinear lookup (F.grid_sample in the reference) is written out
-    tap by tap: unnormalise ((g+1)/2)*(size-1), floor, 4 weighted taps, out-of-range taps = 0."""
+    tap by tap: unnormalise ((g+1)/2)*(size-1), floor, 4 weighted taps, out-of-range taps = 0.
+    dtype: the arithmetic (None = f32); latent and uv are converted differentiably."""
+    dt = f32 if dtype is None else dtype
+    latent, uv = T(latent, dt), T(uv, dt)
     NS, L, Hl, Wl = latent.shape
-    ls = torch.tensor([Wl, Hl], dtype=f32)
+    ls = torch.tensor([Wl, Hl], dtype=dt)
     ls = ls / (ls - 1) * 2.0  # latent_scaling, encoder.py:170-172 (fp32 arithmetic)
-    scale = ls / torch.tensor([width, height], dtype=f32)
+    scale = ls / torch.tensor([width, height], dtype=dt)
     g = uv * scale - 1.0
     ix = ((g[..., 0] + 1) / 2) * (Wl - 1)
     iy = ((g[..., 1] + 1) / 2) * (Hl - 1)
@@ -223,7 +228,7 @@ def index_latent(latent, uv, width, height):
         zero = torch.zeros_like(xi)
         idx = (torch.where(ok, yi, zero) * Wl + torch.where(ok, xi, zero)).long()
         v = torch.gather(lat, 1, idx.unsqueeze(-1).expand(-1, -1, L))
-        return v * (w * ok.to(f32)).unsqueeze(-1)
+        return v * (w * ok.to(dt)).unsqueeze(-1)
 
     return tap(x0, y0, w_nw) + tap(x1, y0, w_ne) + tap(x0, y1, w_sw) + tap(x1, y1, w_se)
 
@@ -245,9 +250,13 @@ def _relu(t, rows_per_point):
     return torch.relu(t)
 
 
-def resnetfc(sd, z, x, ns, n_blocks=5, combine_layer=3):
+def resnetfc(sd, z, x, ns, n_blocks=5, combine_layer=3, dtype=None):
     """src/model/resnetfc.py:134-186 (+ :53-62 block, util.py:489-499 combine):
-    rows ordered view-major within a scene: row = v*B + b.  z (ns*B,L), x (ns*B,d_in)."""
+    rows ordered view-major within a scene: row = v*B + b.  z (ns*B,L), x (ns*B,d_in).
+    dtype: the arithmetic (None = f32); parameters and inputs are converted differentiably."""
+    if dtype is not None:
+        sd = {k: T(v, dtype) for k, v in sd.items()}
+        z, x = T(z, dtype), T(x, dtype)
     h = _lin(sd, "lin_in", x)
     nv = ns
     for blk in range(n_blocks):
@@ -267,24 +276,30 @@ class Scene:
     (src/model/models.py:74-87,114-148; src/model/encoder.py:73-76,169-172)."""
 
     def __init__(self, mlp_coarse, mlp_fine, latent, poses, focal, c, width, height, yolo=False,
-                 n_blocks=5, combine_layer=3):
-        self.mlp_coarse = {k: T(v) for k, v in mlp_coarse.items()}
-        self.mlp_fine = None if mlp_fine is None else {k: T(v) for k, v in mlp_fine.items()}
-        self.latent = T(latent)
-        self.w2c, self.focal, self.c = encode_cameras(poses, focal, c, width, height, yolo)
+                 n_blocks=5, combine_layer=3, dtype=None):
+        """dtype: the arithmetic of query / render / yolo_render on this scene (None = f32; torch.float64 = the
+        high-precision arbiter of the GPU gradient sweeps).  Parameter and latent tensors assigned after construction
+        may be of any dtype: they are converted differentiably where they are used."""
+        self.dtype = f32 if dtype is None else dtype
+        self.mlp_coarse = {k: T(v, dtype) for k, v in mlp_coarse.items()}
+        self.mlp_fine = None if mlp_fine is None else {k: T(v, dtype) for k, v in mlp_fine.items()}
+        self.latent = T(latent, dtype)
+        self.w2c, self.focal, self.c = encode_cameras(poses, focal, c, width, height, yolo, dtype)
         self.width, self.height = width, height
         self.yolo = yolo
         self.ns = self.latent.shape[0]
         self.n_blocks, self.combine_layer = n_blocks, combine_layer
 
 
-def query(scene, xyz, viewdirs, coarse=True):
+def query(scene, xyz, viewdirs, coarse=True, dtype=None):
     """src/model/models.py:153-318 for SB=1 with the shipped flags (use_xyz, normalize_z,
     use_code, use_viewdirs, not use_code_viewdirs).  xyz, viewdirs (B,3) -> (B,d_out):
-    [sigmoid rgb, relu sigma], or the raw vector in YOLO mode."""
-    xyz, viewdirs = T(xyz), T(viewdirs)
+    [sigmoid rgb, relu sigma], or the raw vector in YOLO mode.  dtype: the arithmetic (None = the scene's)."""
+    dt = getattr(scene, "dtype", f32) if dtype is None else dtype
+    xyz, viewdirs = T(xyz, dt), T(viewdirs, dt)
     ns, B = scene.ns, xyz.shape[0]
-    R, t = scene.w2c[:, :, :3], scene.w2c[:, :, 3]
+    w2c = T(scene.w2c, dt)
+    R, t = w2c[:, :, :3], w2c[:, :, 3]
     xr = torch.matmul(R[:, None], xyz[None, :, :, None])[..., 0]  # (ns,B,3) rotation only
     xc = xr + t[:, None]
     code = positional_encoding(xr.reshape(-1, 3))
@@ -294,41 +309,43 @@ def query(scene, xyz, viewdirs, coarse=True):
         uv = -xc[:, :, :2] / xc[:, :, 2:]
     else:
         uv = xc[:, :, :2] / xc[:, :, 2:]
-    foc = scene.focal if scene.focal.shape[0] > 1 else scene.focal.expand(ns, 2)
-    cc = scene.c if scene.c.shape[0] > 1 else scene.c.expand(ns, 2)
+    foc, cc = T(scene.focal, dt), T(scene.c, dt)
+    foc = foc if foc.shape[0] > 1 else foc.expand(ns, 2)
+    cc = cc if cc.shape[0] > 1 else cc.expand(ns, 2)
     uv = uv * foc[:, None] + cc[:, None]
-    lat = index_latent(scene.latent, uv, scene.width, scene.height).reshape(ns * B, -1)
+    lat = index_latent(scene.latent, uv, scene.width, scene.height, dt).reshape(ns * B, -1)
     if scene.yolo:
         behind = (xc[:, :, 2] >= 0).reshape(-1, 1)  # models.py:224,254-264: zero where z >= 0 or NaN
         lat = torch.where(behind | torch.isnan(lat), torch.zeros_like(lat), lat)
     sd = scene.mlp_coarse if (coarse or scene.mlp_fine is None) else scene.mlp_fine
-    out = resnetfc(sd, lat, x_in, ns, scene.n_blocks, scene.combine_layer)
+    out = resnetfc(sd, lat, x_in, ns, scene.n_blocks, scene.combine_layer, dt)
     if scene.yolo:
         return out
     return torch.cat([torch.sigmoid(out[:, :3]), torch.relu(out[:, 3:4])], dim=-1)
 
 
-def _query_rays(scene, rays, z, coarse, chunk):
+def _query_rays(scene, rays, z, coarse, chunk, dtype=None):
     N, K = z.shape
     pts = (rays[:, None, :3] + z.unsqueeze(2) * rays[:, None, 3:6]).reshape(-1, 3)
     dirs = rays[:, None, 3:6].expand(-1, K, -1).reshape(-1, 3)
-    outs = [query(scene, pts[i:i + chunk], dirs[i:i + chunk], coarse) for i in range(0, pts.shape[0], chunk)]
+    outs = [query(scene, pts[i:i + chunk], dirs[i:i + chunk], coarse, dtype) for i in range(0, pts.shape[0], chunk)]
     return torch.cat(outs, 0).reshape(N, K, -1)
 
 
 def render(scene, rays, n_coarse, n_fine, n_fine_depth, u_coarse, u_fine=None, u_fine2=None, g_depth=None,
            depth_std=0.01, white_bkgd=True, lindisp=False, chunk=50000, detach_fine_depth=False, noise_coarse=None,
-           noise_fine=None):
+           noise_fine=None, dtype=None):
     """src/render/nerf.py:257-309 (forward) for SB=1: coarse pass, then fine pass on
     sort(cat(z_coarse, z_fine, z_depth)) with the fine MLP.  The four random draws are inputs.
     Under autograd the reference detaches the coarse weights for importance sampling (nerf.py:132) but NOT the coarse
     depth the depth samples are centred on (nerf.py:296-298): the fine loss reaches the coarse MLP through the sample
     positions.  detach_fine_depth=True cuts that path (a test aid for the stages of the backward pass; the default is
-    the reference's behaviour)."""
-    rays = T(rays)
+    the reference's behaviour).  dtype: the arithmetic (None = the scene's)."""
+    dt = getattr(scene, "dtype", f32) if dtype is None else dtype
+    rays = T(rays, dt)
     res = {}
     zc = sample_coarse(rays, n_coarse, u_coarse, lindisp)
-    oc = _query_rays(scene, rays, zc, True, chunk)
+    oc = _query_rays(scene, rays, zc, True, chunk, dt)
     wc, rgbc, dc = composite(rays, zc, oc, white_bkgd, noise_coarse)
     res["coarse"] = dict(z=zc, out=oc, weights=wc, rgb=rgbc, depth=dc)
     if n_fine > 0:
@@ -338,18 +355,19 @@ def render(scene, rays, n_coarse, n_fine, n_fine_depth, u_coarse, u_fine=None, u
         if n_fine_depth > 0:
             samps.append(sample_fine_depth(rays, dc.detach() if detach_fine_depth else dc, g_depth, depth_std))
         zf, _ = torch.sort(torch.cat(samps, dim=-1), dim=-1)
-        of = _query_rays(scene, rays, zf, False, chunk)
+        of = _query_rays(scene, rays, zf, False, chunk, dt)
         wf, rgbf, df = composite(rays, zf, of, white_bkgd, noise_fine)
         res["fine"] = dict(z=zf, out=of, weights=wf, rgb=rgbf, depth=df)
     return res
 
 
-def yolo_render(scene, rays, n_coarse, u_coarse, n_anchors=3, chunk=50000):
+def yolo_render(scene, rays, n_coarse, u_coarse, n_anchors=3, chunk=50000, dtype=None):
     """src/render/yolo.py:37-114: coarse sampling only, raw MLP vectors, probability-weighted
-    aggregation along each ray."""
-    rays = T(rays)
+    aggregation along each ray.  dtype: the arithmetic (None = the scene's)."""
+    dt = getattr(scene, "dtype", f32) if dtype is None else dtype
+    rays = T(rays, dt)
     z = sample_coarse(rays, n_coarse, u_coarse)
-    raw = _query_rays(scene, rays, z, True, chunk)
+    raw = _query_rays(scene, rays, z, True, chunk, dt)
     return dict(z=z, raw=raw, out=yolo_aggregate(raw, n_anchors))
 
 

@@ -52,6 +52,56 @@ def oracle_scene(g, seed):
     return orc.Scene(mc, mf, lat, g["src_poses"], g["focal"], g["c"][None], W, H)
 
 
+# --------------------------------------------------------------------------- MLP (query) backward
+def scene_pair(ns, H, W, L, d_out, n_blocks, combine_layer, seed, yolo=False, lat_hw=None, lat_grad=False, dtype=None,
+               yolo_flip=True, with_net=True):
+    """The same seeded scene as a HIP net (trainable MLP, frozen encoder) and as oracle state with requires_grad.
+    lat_grad: the latent is a leaf that requires grad on both sides (net.test_latent on the GPU, sc.latent on the CPU).
+    dtype: the oracle's arithmetic and the dtype of its leaves (None = f32; torch.float64 = the arbiter of the shape sweeps).
+    yolo_flip=False (YOLO mode): world->cam extrinsics of cameras looking down -z, so that the scene lies at z < 0, where YOLO
+    mode keeps the latent (models.py:224,254-264 zero it at z >= 0); the default flips y / z, which puts the scene at z > 0.
+    with_net=False: the oracle scene alone (net is None; no GPU needed)."""
+    import pnyolo_oracle as orc
+    c = pconf.yolo() if yolo else pconf.default_mv()
+    m = c.d["model"]
+    if L != 512 and not yolo:
+        m["encoder"]["backbone"] = "custom"
+    m["mlp_coarse"].update({"n_blocks": n_blocks, "combine_layer": combine_layer})
+    if not yolo:
+        m["mlp_fine"].update({"n_blocks": n_blocks, "combine_layer": combine_layer})
+    net = make_model(c["model"], stop_encoder_grad=True)
+    sd_c = synth.mlp_state(seed + 1, d_latent=L, d_out=d_out, n_blocks=n_blocks, combine_layer=combine_layer)
+    net.mlp_coarse.load_state_dict({k: torch.from_numpy(v) for k, v in sd_c.items()})
+    sd_f = None
+    if net.mlp_fine is not None:
+        sd_f = synth.mlp_state(seed + 2, d_latent=L, d_out=d_out, n_blocks=n_blocks, combine_layer=combine_layer)
+        net.mlp_fine.load_state_dict({k: torch.from_numpy(v) for k, v in sd_f.items()})
+    hl, wl = lat_hw or (H // 2, W // 2)
+    lat = synth.latent(seed + 3, ns, L, hl, wl)
+    if yolo:
+        src_c2w, _ = synth.scene_cameras(ns, radius=4.0, phi=-25.0)
+        flipyz = np.diag([1.0, -1.0, -1.0, 1.0] if yolo_flip else [1.0, 1.0, 1.0, 1.0]).astype(np.float32)
+        poses = np.stack([np.linalg.inv(p @ flipyz) for p in src_c2w]).astype(np.float32)
+        focal, cc = torch.tensor([[40.0, 44.0]]), torch.tensor([[W * 0.5, H * 0.5 - 2]])
+    else:
+        poses, _ = synth.scene_cameras(ns)
+        focal, cc = torch.tensor(0.9 * W), torch.tensor([[W * 0.5, H * 0.5]])
+    if with_net:
+        net = net.to(DEV).train()
+        net.test_latent = torch.from_numpy(lat).to(DEV).requires_grad_() if lat_grad else torch.from_numpy(lat)
+        net.encode(torch.zeros(1, ns, 3, H, W), torch.from_numpy(poses)[None], focal, c=cc, latent=net.test_latent)
+    else:
+        net = None
+    leaf_dt = torch.float32 if dtype is None else dtype
+    mc = {k: torch.from_numpy(v).to(leaf_dt).requires_grad_() for k, v in sd_c.items()}
+    mf = None if sd_f is None else {k: torch.from_numpy(v).to(leaf_dt).requires_grad_() for k, v in sd_f.items()}
+    sc = orc.Scene(mc, mf, lat, poses, focal, cc, W, H, yolo=yolo, n_blocks=n_blocks, combine_layer=combine_layer, dtype=dtype)
+    sc.mlp_coarse, sc.mlp_fine = mc, mf          # Scene() re-wraps tensors: keep the leaves
+    if lat_grad:
+        sc.latent = torch.from_numpy(lat).to(leaf_dt).requires_grad_()
+    return net, sc
+
+
 RTOL = 1e-4      # every gradient tensor within 1e-4 x its own max |.| (gradients sum 10^4..10^5 fp32 products)
 
 

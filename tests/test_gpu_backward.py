@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import pnyolo_oracle as orc
-from helpers import DEV, RTOL, clean_points, clean_rays, compare_param_grads, dt, grad_check, load_mlp, maxabs, render_loss
+from helpers import DEV, RTOL, clean_points, clean_rays, compare_param_grads, dt, grad_check, load_mlp, maxabs, render_loss, scene_pair
 from pixel_nerf_yolo_amd import conf as pconf
 from pixel_nerf_yolo_amd import lib as plib
 from pixel_nerf_yolo_amd import synth
@@ -91,45 +91,6 @@ AMBIG_DEFAULT = float(os.environ.get("PNYOLO_TEST_AMBIG_DEFAULT", "3e-5"))
 
 
 # --------------------------------------------------------------------------- MLP (query) backward
-def scene_pair(ns, H, W, L, d_out, n_blocks, combine_layer, seed, yolo=False, lat_hw=None, lat_grad=False):
-    """The same seeded scene as a HIP net (trainable MLP, frozen encoder) and as oracle state with requires_grad.
-    lat_grad: the latent is a leaf that requires grad on both sides (net.test_latent on the GPU, sc.latent on the CPU)."""
-    c = pconf.yolo() if yolo else pconf.default_mv()
-    m = c.d["model"]
-    if L != 512 and not yolo:
-        m["encoder"]["backbone"] = "custom"
-    m["mlp_coarse"].update({"n_blocks": n_blocks, "combine_layer": combine_layer})
-    if not yolo:
-        m["mlp_fine"].update({"n_blocks": n_blocks, "combine_layer": combine_layer})
-    net = make_model(c["model"], stop_encoder_grad=True)
-    sd_c = synth.mlp_state(seed + 1, d_latent=L, d_out=d_out, n_blocks=n_blocks, combine_layer=combine_layer)
-    net.mlp_coarse.load_state_dict({k: torch.from_numpy(v) for k, v in sd_c.items()})
-    sd_f = None
-    if net.mlp_fine is not None:
-        sd_f = synth.mlp_state(seed + 2, d_latent=L, d_out=d_out, n_blocks=n_blocks, combine_layer=combine_layer)
-        net.mlp_fine.load_state_dict({k: torch.from_numpy(v) for k, v in sd_f.items()})
-    net = net.to(DEV).train()
-    hl, wl = lat_hw or (H // 2, W // 2)
-    lat = synth.latent(seed + 3, ns, L, hl, wl)
-    if yolo:
-        src_c2w, _ = synth.scene_cameras(ns, radius=4.0, phi=-25.0)
-        flipyz = np.diag([1.0, -1.0, -1.0, 1.0]).astype(np.float32)
-        poses = np.stack([np.linalg.inv(p @ flipyz) for p in src_c2w]).astype(np.float32)
-        focal, cc = torch.tensor([[40.0, 44.0]]), torch.tensor([[W * 0.5, H * 0.5 - 2]])
-    else:
-        poses, _ = synth.scene_cameras(ns)
-        focal, cc = torch.tensor(0.9 * W), torch.tensor([[W * 0.5, H * 0.5]])
-    net.test_latent = torch.from_numpy(lat).to(DEV).requires_grad_() if lat_grad else torch.from_numpy(lat)
-    net.encode(torch.zeros(1, ns, 3, H, W), torch.from_numpy(poses)[None], focal, c=cc, latent=net.test_latent)
-    mc = {k: torch.from_numpy(v).requires_grad_() for k, v in sd_c.items()}
-    mf = None if sd_f is None else {k: torch.from_numpy(v).requires_grad_() for k, v in sd_f.items()}
-    sc = orc.Scene(mc, mf, lat, poses, focal, cc, W, H, yolo=yolo, n_blocks=n_blocks, combine_layer=combine_layer)
-    sc.mlp_coarse, sc.mlp_fine = mc, mf          # Scene() re-wraps tensors: keep the leaves
-    if lat_grad:
-        sc.latent = torch.from_numpy(lat).requires_grad_()
-    return net, sc
-
-
 @pytest.mark.parametrize("cfg", [
     dict(ns=2, L=512, d_out=4, n_blocks=5, combine_layer=3, n=200),        # the shipped multi-view shape
     dict(ns=3, L=512, d_out=4, n_blocks=5, combine_layer=3, n=65),         # ragged tile
