@@ -375,9 +375,26 @@ int pny_model_bind_grad(pny_model* m, const char* name, float* grad_dev);
  * (src/model/resnetfc.py:176-182), i.e. what reaches `encoder.latent` in the reference when the encoder trains:
  * grad_dev is a caller-owned, caller-zeroed fp32 buffer of the latent's shape in the library's layout (ns, Hl, Wl, L)
  * (channel-last); every backward call on the scene ADDS into it (float atomics: reproducible to fp32 rounding, not bit for
- * bit).  NULL unbinds.  d_latent must be a multiple of 256.  The gradient is handed to whatever produced the latent
- * (pny_scene_set_latent): pny_trunk_train_backward for the library's trunk, the caller's own backbone otherwise. */
+ * bit, unless the model is deterministic: pny_model_set_deterministic).  NULL unbinds.  d_latent must be a multiple of 256.
+ * The gradient is handed to whatever produced the latent (pny_scene_set_latent): pny_trunk_train_backward for the library's
+ * trunk, the caller's own backbone otherwise. */
 int pny_scene_bind_latent_grad(pny_scene* s, float* grad_dev);
+
+/* Deterministic latent gradient (opt-in; default off).  enable != 0: from the next backward on, every scene of the model
+ * (grouped scenes included) computes the latent gradient of pny_render_backward, pny_yolo_render_backward and
+ * pny_query_backward without float atomics: each launch sums its contributions exactly, as 64-bit fixed-point integers on a
+ * per-launch power-of-two scale chosen from a proven bound (csrc/latent_grad_det.hip), and adds the sum to grad_dev once.
+ * The GEMM and its arithmetic (fp32, split f16, single-plane f16: pny_scene_set_precision) are those of the default path;
+ * the result agrees with it to fp32 rounding.  Every other gradient of the library is deterministic already, so with this
+ * mode a training step's gradients -- MLP parameters, latent, and the trunk's (computed from the latent gradient) -- are
+ * guaranteed:
+ *   - bit-identical across runs on the same GPU model, library build and launch shape (rays, samples, scenes, chunking);
+ *   - NOT bit-identical across different chunkings (PNYOLO_STASH_GB) or batchings: every launch rounds its sum to fp32.
+ * Cost: DESIGN.md 4.4 item 7.  A non-finite max |dY| or lin_z weight makes the launch's whole latent gradient NaN. */
+int pny_model_set_deterministic(pny_model* m, int enable);
+/* Which path the last backward of the scene that had a bound latent gradient took: 1 deterministic, 0 float atomics
+ * (0 before any). */
+int pny_scene_last_latent_grad_mode(pny_scene* s, int* deterministic);
 
 /* Backward of pny_query: d_out_dev (n, d_out) = dL/d(out).  accumulate = 0 overwrites the bound gradients of the
  * selected MLP, 1 adds to them. */

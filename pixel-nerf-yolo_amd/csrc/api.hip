@@ -612,7 +612,7 @@ void pny_scene_destroy(pny_scene* s) {
     s->zp[0].release();
     s->zp[1].release();
     for (DevBuf* b : {&s->dy_absmax, &s->x_stash, &s->dy_stash, &s->dw_partial, &s->dw_bias, &s->dw_tables, &s->d_samp, &s->out_tmp, &s->dz_tmp,
-                      &s->sel_tmp, &s->gdepth_tmp})
+                      &s->sel_tmp, &s->gdepth_tmp, &s->lg_fixed, &s->lg_words})
         b->release();
     for (auto e : s->ev) (void)hipEventDestroy(e);
     for (auto e : s->bev) (void)hipEventDestroy(e);

@@ -146,6 +146,7 @@ struct pny_model {
     bool defer_dw_h2 = false;                // a split-f16 scene contributed: a flush without F32 contributors runs split-f16,
                                              // one with F16_TRAIN contributors only the single-plane GEMM
     int last_flush_prec = 0;                 // pny_model_last_flush_precision: 0 fp32, 1 split-f16, 2 single-plane GEMM
+    bool deterministic = false;              // pny_model_set_deterministic: the latent gradient of every scene is bit-reproducible
     hipStream_t aux_stream = nullptr;        // side stream of the weight-gradient GEMMs' clipped tiles (mlp_bwd.hip launch_dw_gemm)
     hipEvent_t aux_fork = nullptr, aux_join = nullptr;
     uint64_t defer_epoch = 0;                // bumped by every pny_model_defer_weight_grads(enable)
@@ -210,6 +211,11 @@ struct pny_scene {
     // stream the last call on this scene was enqueued on (see enter_stream)
     // training workspace (train_api.hip)
     DevBuf dy_absmax;                        // one word: running max |dY| of the chunk in flight (non-deferred backward)
+    // deterministic latent gradient (latent_grad_det.hip): the (ns, hl, wl, L) int64 fixed-point accumulator (all zero between
+    // launches), and 32 bytes of scratch: the launch's scale (2 doubles), max |lin_z^T|, this scene's running max |dY| and the
+    // copy of it the launch's GEMM scales by
+    DevBuf lg_fixed, lg_words;
+    int last_lg_det = 0;                     // pny_scene_last_latent_grad_mode
     DevBuf x_stash, dy_stash, dw_partial, dw_bias, dw_tables, d_samp, out_tmp, dz_tmp, sel_tmp, gdepth_tmp;
     PinnedStage table_stage;
     // "stash in the forward": the next pny_render evaluates the MLPs with the STASH instantiation straight into the

@@ -10,16 +10,20 @@
 // weights [lin_z[0]^T | lin_z[1]^T | ...] as the packed A operand (api.hip pack_mlp, kept current by pny_model_refresh);
 // the epilogue turns the accumulators through LDS and scatters 64 consecutive latent channels of one sample per atomic
 // instruction into the sample's four taps (float atomics).  The sum order over samples is therefore not fixed: latent gradients are reproducible to fp32
-// rounding, not bit for bit (the MLP parameter gradients stay deterministic).
+// rounding, not bit for bit (the MLP parameter gradients stay deterministic).  The deterministic mode (pny_model_set_deterministic)
+// builds this source once more with -DPNY_LG_FIXED (latent_grad_det.hip, latent_grad_fx.h): the same GEMM, whose epilogue adds
+// each contribution as a 64-bit fixed-point integer instead -- integer addition is associative, so the order does not matter.
 // A workgroup (4 waves) owns 64 samples x 256 latent channels, a wave 64 x 64 (2 x 2 tiles of 32 x 32).
 #include "mlp_core.h"
+#include "latent_grad_fx.h"
 
 namespace pny {
 
 constexpr int LG_KC = 32, LG_NW = 4;
 
-__global__ __launch_bounds__(64 * LG_NW) void latent_grad_kernel(const MlpArgs a, const float* __restrict__ dy_stash, const StashLayout lay,
-                                                                 const float* __restrict__ w_cat, float* __restrict__ grad, int nvb) {
+__global__ __launch_bounds__(64 * LG_NW) void PNY_LG32_KERNEL(const MlpArgs a, const float* __restrict__ dy_stash, const StashLayout lay,
+                                                              const float* __restrict__ w_cat, PNY_LG_OUT* __restrict__ grad, int nvb PNY_LG_FX_ARG) {
+    PNY_LG_FX_LOAD
     __shared__ float4 bt[2][LG_KC / 4][64 + 1];
     __shared__ __attribute__((aligned(16))) float tr[LG_NW][32][68];   // epilogue: [wave][sample of the half][channel], 16-byte aligned rows
     __shared__ int tap_off[64][4];
@@ -103,7 +107,7 @@ __global__ __launch_bounds__(64 * LG_NW) void latent_grad_kernel(const MlpArgs a
     // scatter.  In accumulator layout a lane holds 4 channels of ONE sample, i.e. a wave instruction would touch 32 different
     // pixels' lines; the wave's 64 channels x 32 samples are turned through LDS instead, so that one atomic instruction
     // adds 64 CONSECUTIVE channels of one sample's tap (two 128-byte lines): 16x fewer line operations at the L2
-    float* gv = grad + (size_t)vabs * a.Hl * a.Wl * a.L + 32 * nt0 + lane;
+    PNY_LG_OUT* gv = grad + (size_t)vabs * a.Hl * a.Wl * a.L + 32 * nt0 + lane;
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
         __syncthreads();   // (the staging buffers / the previous half's rows are no longer read)
@@ -124,19 +128,28 @@ __global__ __launch_bounds__(64 * LG_NW) void latent_grad_kernel(const MlpArgs a
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float wk = tap_w[32 * mt + m][k];     // wave-uniform
-                if (wk != 0.0f) unsafeAtomicAdd(gv + tap_off[32 * mt + m][k], wk * val);
+                if (wk != 0.0f) PNY_LG_ADD(gv + tap_off[32 * mt + m][k], wk * val);
             }
         }
     }
 }
 
+#ifdef PNY_LG_FIXED
+// the fp32 GEMM of the deterministic mode (launch_latent_grad_det): grad is the scene's fixed-point accumulator, fx its scale
+void launch_latent_grad_f32_det(const MlpArgs& a, const float* dy_stash, const StashLayout& lay, const float* w_cat, unsigned long long* grad,
+                                int nvb, hipStream_t st, const double* fx) {
+    hipLaunchKernelGGL(PNY_LG32_KERNEL, dim3((unsigned)((long long)a.n_tiles * a.NS * (a.L / 256))), dim3(64 * LG_NW), 0, st, a, dy_stash,
+                       lay, w_cat, grad, nvb, fx);
+}
+#else
 void launch_latent_grad(const MlpArgs& a, const float* dy_stash, const StashLayout& lay, const float* w_cat, float* grad, int nvb,
                         hipStream_t st, const unsigned* dy_absmax, int planes) {
     if (dy_absmax)   // f16 matrix paths (latent_grad_h2.hip): split (2) or single-plane (1, PNY_PRECISION_F16_TRAIN)
         (planes == 1 ? launch_latent_grad_h1 : launch_latent_grad_h2)(a, dy_stash, lay, w_cat, grad, nvb, st, dy_absmax);
     else
-        hipLaunchKernelGGL(latent_grad_kernel, dim3((unsigned)((long long)a.n_tiles * a.NS * (a.L / 256))), dim3(64 * LG_NW), 0, st, a,
+        hipLaunchKernelGGL(PNY_LG32_KERNEL, dim3((unsigned)((long long)a.n_tiles * a.NS * (a.L / 256))), dim3(64 * LG_NW), 0, st, a,
                            dy_stash, lay, w_cat, grad, nvb);
 }
+#endif
 
 }  // namespace pny

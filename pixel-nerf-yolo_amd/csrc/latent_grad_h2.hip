@@ -9,14 +9,23 @@
 // plane per operand -- the fp32 lin_z^T image rounded to f16 in registers, the scaled dY rounded to f16 in LDS, one MFMA per
 // accumulator tile and 16 k instead of three.  The tiles, two-tile workgroups, inverse scale on the tap weights and
 // float-atomic scatter are the same (reproducible to fp32 rounding, not bit for bit, like the other latent-gradient kernels).
+// -DPNY_LG_FIXED (latent_grad_h2_det.hip, latent_grad_h1_det.hip) is the deterministic mode's build: the epilogue adds 64-bit
+// fixed-point integers instead (latent_grad_fx.h).
 #include "mlp_core.h"
+#include "latent_grad_fx.h"
 
 #ifndef PNY_H2_PLANES
 #define PNY_H2_PLANES 2
 #endif
-#if PNY_H2_PLANES == 1
+#if PNY_H2_PLANES == 1 && defined(PNY_LG_FIXED)
+#define PNY_LG_KERNEL latent_grad_h1_det_kernel
+#define PNY_LG_LAUNCH launch_latent_grad_h1_det
+#elif PNY_H2_PLANES == 1
 #define PNY_LG_KERNEL latent_grad_h1_kernel
 #define PNY_LG_LAUNCH launch_latent_grad_h1
+#elif defined(PNY_LG_FIXED)
+#define PNY_LG_KERNEL latent_grad_h2_det_kernel
+#define PNY_LG_LAUNCH launch_latent_grad_h2_det
 #else
 #define PNY_LG_KERNEL latent_grad_h2_kernel
 #define PNY_LG_LAUNCH launch_latent_grad_h2
@@ -51,8 +60,9 @@ __device__ __forceinline__ void lg_split2(float a, float b, unsigned& p0, unsign
 // wave, 33 KB of staging): half the weight bytes per sample.  TPW = 1 is kept for launches with a single tile.
 template <int TPW>
 __global__ __launch_bounds__(64 * LG_NW) void PNY_LG_KERNEL(const MlpArgs a, const float* __restrict__ dy_stash, const StashLayout lay,
-                                                            const float* __restrict__ w_cat, float* __restrict__ grad, int nvb,
-                                                            const unsigned* __restrict__ dy_absmax) {
+                                                            const float* __restrict__ w_cat, PNY_LG_OUT* __restrict__ grad, int nvb,
+                                                            const unsigned* __restrict__ dy_absmax PNY_LG_FX_ARG) {
+    PNY_LG_FX_LOAD
     constexpr int TS = 64 * TPW, MT = 2 * TPW;      // samples and 32-sample m-tiles of the workgroup
     __shared__ uint2 bp[2][PNY_H2_PLANES][LG_KC / 4][TS + 1];   // [buffer][plane][k / 4][sample]
     __shared__ __attribute__((aligned(16))) float tr[LG_NW][32][68];
@@ -201,7 +211,7 @@ __global__ __launch_bounds__(64 * LG_NW) void PNY_LG_KERNEL(const MlpArgs a, con
     }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-        float* gv = grad + (size_t)vabs_of[mt >> 1] * a.Hl * a.Wl * a.L + 32 * nt0 + lane;
+        PNY_LG_OUT* gv = grad + (size_t)vabs_of[mt >> 1] * a.Hl * a.Wl * a.L + 32 * nt0 + lane;
         __syncthreads();
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt)
@@ -220,21 +230,21 @@ __global__ __launch_bounds__(64 * LG_NW) void PNY_LG_KERNEL(const MlpArgs a, con
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float wk = tap_w[32 * mt + m][k];
-                if (wk != 0.0f) unsafeAtomicAdd(gv + tap_off[32 * mt + m][k], wk * val);
+                if (wk != 0.0f) PNY_LG_ADD(gv + tap_off[32 * mt + m][k], wk * val);
             }
         }
     }
 }
 
-// launch_latent_grad's share (latent_grad.hip) for this plane count
-void PNY_LG_LAUNCH(const MlpArgs& a, const float* dy_stash, const StashLayout& lay, const float* w_cat, float* grad, int nvb,
-                   hipStream_t st, const unsigned* dy_absmax) {
+// launch_latent_grad's share (latent_grad.hip) for this plane count (PNY_LG_FIXED: launch_latent_grad_det's, latent_grad_det.hip)
+void PNY_LG_LAUNCH(const MlpArgs& a, const float* dy_stash, const StashLayout& lay, const float* w_cat, PNY_LG_OUT* grad, int nvb,
+                   hipStream_t st, const unsigned* dy_absmax PNY_LG_FX_ARG) {
     if (a.n_tiles >= 2) {
         const long long pairs = (long long)((a.n_tiles + 1) / 2) * a.NS * (a.L / 256);
-        hipLaunchKernelGGL(PNY_LG_KERNEL<2>, dim3((unsigned)pairs), dim3(64 * LG_NW), 0, st, a, dy_stash, lay, w_cat, grad, nvb, dy_absmax);
+        hipLaunchKernelGGL(PNY_LG_KERNEL<2>, dim3((unsigned)pairs), dim3(64 * LG_NW), 0, st, a, dy_stash, lay, w_cat, grad, nvb, dy_absmax PNY_LG_FX_PASS);
     } else {
         const long long blocks = (long long)a.n_tiles * a.NS * (a.L / 256);
-        hipLaunchKernelGGL(PNY_LG_KERNEL<1>, dim3((unsigned)blocks), dim3(64 * LG_NW), 0, st, a, dy_stash, lay, w_cat, grad, nvb, dy_absmax);
+        hipLaunchKernelGGL(PNY_LG_KERNEL<1>, dim3((unsigned)blocks), dim3(64 * LG_NW), 0, st, a, dy_stash, lay, w_cat, grad, nvb, dy_absmax PNY_LG_FX_PASS);
     }
 }
 

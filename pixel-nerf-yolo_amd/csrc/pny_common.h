@@ -217,6 +217,16 @@ void launch_latent_grad_h2(const MlpArgs& a, const float* dy_stash, const StashL
                            hipStream_t st, const unsigned* dy_absmax);
 void launch_latent_grad_h1(const MlpArgs& a, const float* dy_stash, const StashLayout& lay, const float* w_cat, float* grad, int nvb,
                            hipStream_t st, const unsigned* dy_absmax);
+// deterministic latent gradient (latent_grad_det.hip, pny_model_set_deterministic): the GEMM of launch_latent_grad's arithmetic
+// `arith` (0 fp32, 1 split f16, 2 single-plane f16) adds 64-bit fixed-point integers into acc (acc_elems words, zero on entry
+// and on return: the scene's (NS, Hl, Wl, L) accumulator), and acc / S is then added to grad.  dy_absmax: the running max |dY|
+// of exactly this launch's chain (never a word another stream may still raise: it sets S, the split-f16 kernels' scale too);
+// the launch resets it to 0 for the next chain.  words: 32 bytes of device scratch, zero before the first launch.
+int launch_latent_grad_det(const MlpArgs& a, const float* dy_stash, const StashLayout& lay, const float* w_cat, float* grad, int nvb,
+                           hipStream_t st, unsigned* dy_absmax, int arith, unsigned long long* acc, long long acc_elems,
+                           void* words);
+// atomicMax(*dst, *src) on the device (a running max |dY| handed on to a shared word)
+void launch_absmax_fold(unsigned* dst, const unsigned* src, hipStream_t st);
 bool mlp_h2_supports(int n_blocks, int combine_layer);
 void launch_mlp_h2(const MlpArgs& a, int grid, hipStream_t st);
 void launch_mlp_h1(const MlpArgs& a, int grid, hipStream_t st);    // mlp_h1.hip: single f16 plane per operand (PNY_PRECISION_F16), 64-sample tiles

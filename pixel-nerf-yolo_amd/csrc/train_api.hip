@@ -341,6 +341,24 @@ int mlp_backward(pny_scene* s, int mode, const float* xyz, const float* dirs, co
         if ((rc = ensure_absmax(s->dy_absmax, sizeof(unsigned)))) return rc;
         absmax = reinterpret_cast<unsigned*>(s->dy_absmax.p);
     }
+    // Deterministic latent gradient (pny_model_set_deterministic, latent_grad_det.hip): the chain tracks this scene's own running
+    // max |dY| (handed on to `absmax` behind it), which sets the launch's fixed-point scale; the scene's int64 accumulator is
+    // all zero between launches
+    const bool lg_det = m->deterministic && s->latent_grad && view_blocks(d) > 0;
+    const long long lg_elems = (long long)s->ns * s->hl * s->wl * s->L;
+    unsigned* lg_max = nullptr;
+    if (lg_det) {   // (zeroed on THIS stream: a plain hipMemset would be ordered on the null stream, behind other scenes' work)
+        if (!s->lg_words.p) {
+            if ((rc = s->lg_words.reserve(32))) return rc;
+            PNY_HIP(hipMemsetAsync(s->lg_words.p, 0, 32, st));
+        }
+        lg_max = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(s->lg_words.p) + 20);
+        const size_t need = (size_t)lg_elems * sizeof(unsigned long long);
+        if (s->lg_fixed.bytes < need) {
+            if ((rc = s->lg_fixed.reserve(need))) return rc;
+            PNY_HIP(hipMemsetAsync(s->lg_fixed.p, 0, need, st));
+        }
+    }
     auto stamp = [&]() -> int {   // kernel timing for bench.py (pny_scene_enable_timing)
         if (!s->timing) return 0;
         if ((int)s->bev.size() <= s->bev_used) {
@@ -410,6 +428,10 @@ int mlp_backward(pny_scene* s, int mode, const float* xyz, const float* dirs, co
         b.dy_absmax = absmax;
         b.range_flag = m->range_flag;
         if (absmax && !(defer || have_x)) PNY_HIP(hipMemsetAsync(absmax, 0, sizeof(unsigned), st));
+        if (lg_det) {   // (lg_max is 0 here: zeroed at allocation and reset by every deterministic launch, latent_grad_det.hip)
+            b.dy_absmax = lg_max;
+            if (!absmax) b.range_flag = nullptr;   // (the fp32 path keeps its semantics: no f16 range guard)
+        }
         if (h1) {   // single-plane chain: the transposed single-plane images in the model's h1 buffer
             const int f = (fine_w && d.has_fine) ? 1 : 0;
             b.w_base = m->h1_packed.f();
@@ -434,6 +456,7 @@ int mlp_backward(pny_scene* s, int mode, const float* xyz, const float* dirs, co
             s->last_bwd_prec = 0;
         }
         PNY_HIP(hipGetLastError());
+        if (lg_det && absmax) launch_absmax_fold(absmax, lg_max, st);
         if ((rc = stamp())) return rc;
         // 2b. gradient w.r.t. the depths of the selected samples through the MLP inputs (fine pass of a render)
         if (dz_sel && mode == 1) {
@@ -471,7 +494,15 @@ int mlp_backward(pny_scene* s, int mode, const float* xyz, const float* dirs, co
         if (s->latent_grad && view_blocks(d) > 0) {
             if (!wt.wzT_cat) return fail(PNY_ERR_STATE, "latent gradient: transposed lin_z weights are missing");
             if (s->L % 256) return fail(PNY_ERR_ARG, "latent gradient: d_latent must be a multiple of 256");
-            launch_latent_grad(a, dy_base, plan.lay, wt.wzT_cat, s->latent_grad, view_blocks(d), st, dw_h2 ? absmax : nullptr, h1 ? 1 : 2);
+            if (lg_det) {
+                if ((rc = launch_latent_grad_det(a, dy_base, plan.lay, wt.wzT_cat, s->latent_grad, view_blocks(d), st, lg_max,
+                                                 !dw_h2 ? 0 : h1 ? 2 : 1, reinterpret_cast<unsigned long long*>(s->lg_fixed.p),
+                                                 lg_elems, s->lg_words.p)))
+                    return rc;
+            } else {
+                launch_latent_grad(a, dy_base, plan.lay, wt.wzT_cat, s->latent_grad, view_blocks(d), st, dw_h2 ? absmax : nullptr, h1 ? 1 : 2);
+            }
+            s->last_lg_det = lg_det ? 1 : 0;
             PNY_HIP(hipGetLastError());
         }
         // 3. weight-gradient GEMMs over the two stashes + deterministic split reduction into the bound gradients
@@ -491,6 +522,18 @@ extern "C" {
 int pny_scene_bind_latent_grad(pny_scene* s, float* grad_dev) {
     if (!s) return fail(PNY_ERR_ARG, "pny_scene_bind_latent_grad: null scene");
     s->latent_grad = grad_dev;
+    return PNY_OK;
+}
+
+int pny_model_set_deterministic(pny_model* m, int enable) {
+    if (!m) return fail(PNY_ERR_ARG, "pny_model_set_deterministic: null model");
+    m->deterministic = enable != 0;
+    return PNY_OK;
+}
+
+int pny_scene_last_latent_grad_mode(pny_scene* s, int* deterministic) {
+    if (!s || !deterministic) return fail(PNY_ERR_ARG, "pny_scene_last_latent_grad_mode: null argument");
+    *deterministic = s->last_lg_det;
     return PNY_OK;
 }
 

@@ -280,6 +280,7 @@ class PixelNeRFNet(nn.Module):
         self.f16_range_policy = os.environ.get("PNYOLO_F16_RANGE", "relaunch")
         self._projection = None  # None = library default (auto, or env PNYOLO_PROJECTION)
         self._precision = None   # None = library default (auto, or env PNYOLO_MLP_PRECISION)
+        self._deterministic = "auto"   # set_deterministic: the latent gradient's path, decided at every backward
 
     # ---------------------------------------------------------------- native plumbing
     def _device(self):
@@ -477,6 +478,38 @@ class PixelNeRFNet(nn.Module):
             check(_lib.load().pny_scene_set_precision(s, _lib.PRECISION[mode]))
         return self
 
+    def set_deterministic(self, mode):
+        """'auto' | True | False: whether d loss / d latent is computed bit-reproducibly (include/pnyolo.h
+        pny_model_set_deterministic: exact fixed-point sums instead of float atomics; the one gradient of the library that is
+        not deterministic otherwise).  'auto' (default) follows torch.use_deterministic_algorithms at every backward.  False
+        under torch's flag makes a backward that computes a latent gradient raise, as torch's own nondeterministic ops do
+        (a warning under warn_only).  Applies to every scene handle and to bind_parallel's replicas."""
+        if not (mode is True or mode is False or (isinstance(mode, str) and mode == "auto")):
+            raise ValueError("deterministic mode must be 'auto', True or False, not %r" % (mode,))
+        self._deterministic = mode
+        return self
+
+    def _latent_grad_deterministic(self):
+        """Decide the latent gradient's path for the backward about to run (set_deterministic) and hand it to the library."""
+        flag = torch.are_deterministic_algorithms_enabled()
+        det = flag if self._deterministic == "auto" else self._deterministic
+        if flag and not det:
+            msg = ("the latent gradient of PixelNeRFNet (float-atomic scatter) does not have a deterministic implementation "
+                   "under set_deterministic(False), but torch.use_deterministic_algorithms(True) is set: call "
+                   "net.set_deterministic(True) or 'auto'")
+            if not torch.is_deterministic_algorithms_warn_only_enabled():
+                raise RuntimeError(msg)
+            warnings.warn(msg)
+        check(_lib.load().pny_model_set_deterministic(self._h_model, int(det)))
+
+    def last_latent_grad_deterministic(self, scene=0):
+        """True when the last backward of scene `scene` (or of the grouped scene, when the last call was grouped) that
+        computed a latent gradient took the deterministic path (include/pnyolo.h pny_scene_last_latent_grad_mode)."""
+        v = C.c_int(0)
+        h = self._h_group if (self._last_call_group and self._group is not None) else self._scene(scene)
+        check(_lib.load().pny_scene_last_latent_grad_mode(h, C.byref(v)))
+        return bool(v.value)
+
     def range_status(self, clear=False):
         """Bits (include/pnyolo.h PNY_RANGE_*) the F16X2 kernels of this model have reported so far; does not synchronise."""
         if self._h_model is None:
@@ -619,6 +652,7 @@ class PixelNeRFNet(nn.Module):
         """Zeroed (SB * NS, Hl, Wl, L) accumulator bound slice by slice to the scenes (pny_scene_bind_latent_grad), or whole to
         the grouped scene."""
         n_lat, l_ch, hl, wl = meta[0]
+        self._latent_grad_deterministic()
         buf = torch.zeros(n_lat, hl, wl, l_ch, device=self._device(), dtype=torch.float32)
         if group:
             check(_lib.load().pny_scene_bind_latent_grad(self._h_group, ptr(buf)))

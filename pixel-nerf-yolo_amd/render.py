@@ -88,6 +88,7 @@ class _MultiDeviceRenderWrapper(torch.nn.Module):
                 pr.requires_grad_(pm.requires_grad)
             r._projection, r._precision = net._projection, net._precision
             self._replicas[i] = r
+        r._deterministic = net._deterministic   # (every call: a setting changed after the replica was made holds too)
         key = (net._weights_key(), net._encode_epoch)
         if self._seen[i] != key:
             if self._seen[i] is not None and self._seen[i][0] != key[0]:
