@@ -434,6 +434,11 @@ typedef struct pny_render_grads {
  * weight-gradient flush (pny_model_flush_weight_grads with bit 32) between the two. */
 int pny_render_backward(pny_scene* s, const float* rays_dev, int64_t n, const pny_render_opts* opts,
                         const pny_render_saved* saved, const pny_render_grads* grads, int accumulate, pny_stream stream);
+/* Test / debugging aid: where the last pny_render_backward on this scene (with n_fine_depth > 0 and saved->depth_coarse) found
+ * the forward's depth samples.  sel_dev (count = n * n_fine_depth int32, device): ray * (n_coarse + n_fine) + position in the
+ * sorted fine depths, or -1 for a sample that the forward clamped to [near, far] (no gradient passes the clamp).  A sample
+ * strictly inside (near, far) always has a position.  PNY_ERR_STATE when count is not that backward's n * n_fine_depth. */
+int pny_scene_last_depth_sel(pny_scene* s, int32_t* sel_dev, int64_t count, pny_stream stream);
 
 /* Backward of pny_yolo_render (src/render/yolo.py:96-114 aggregation + the MLP; caller: train/trainlib/YoloTrainer.py:160-186):
  * raw_dev (n, K, A*7) = the forward's raw_dev output, g_out_dev (n, A, 7) = dL/d(out); the sample depths are re-created

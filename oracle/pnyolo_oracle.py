@@ -498,3 +498,91 @@ def tp_fp_fn(targets, preds, nms_iou, nms_t, match_iou):
         if max(float(iou_xywh(tb[2:], pb[2:])) for pb in p) < m32:
             fn += 1
     return tp, fp, fn
+
+
+# ----------------------------------------------------------------------------- seeded random draws
+# The renderers' DEFAULT source of draws: Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy
+# as 1, 2, 3", SC'11) evaluated inside the kernels at (seed, stream, index).  Restated here from the paper's round
+# function and the documented counter layout -- NOT parsed from pixel-nerf-yolo_amd/csrc/pny_rng.h: the tests are that
+# two independent writings agree (tests/test_cpu_philox.py, tests/test_gpu_seeded.py).
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57            # the two round multipliers
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85            # key increments per round (golden ratio, sqrt(3) - 1)
+PHILOX_COUNTER3 = 0x9E3779B9                             # the renderer's fixed fourth counter word
+STREAM_COARSE, STREAM_FINE, STREAM_FINE2, STREAM_DEPTH = 1, 2, 3, 4   # third counter word: which draw of the renderer
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10.  counter: four words, key: two words; each a Python int or an integer array (broadcast against each
+    other).  Returns the four output words as numpy uint64 arrays holding 32-bit values."""
+    import numpy as np
+    m32 = np.uint64(0xFFFFFFFF)
+    s32 = np.uint64(32)
+    c0, c1, c2, c3 = [np.asarray(x, dtype=np.uint64) & m32 for x in counter]
+    k0, k1 = [np.asarray(x, dtype=np.uint64) & m32 for x in key]
+    for _ in range(10):
+        p0 = np.uint64(PHILOX_M0) * c0            # 32 x 32 -> 64 bits: exact in uint64
+        p1 = np.uint64(PHILOX_M1) * c2
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & m32, (p0 >> s32) ^ c3 ^ k1, p0 & m32
+        k0 = (k0 + np.uint64(PHILOX_W0)) & m32
+        k1 = (k1 + np.uint64(PHILOX_W1)) & m32
+    return c0, c1, c2, c3
+
+
+def _philox_words(seed, stream, counter_idx):
+    import numpy as np
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    ci = np.asarray(counter_idx, dtype=np.uint64)
+    return philox4x32_10((ci & np.uint64(0xFFFFFFFF), ci >> np.uint64(32), int(stream), PHILOX_COUNTER3),
+                         (seed & 0xFFFFFFFF, seed >> 32))
+
+
+def _u01(x):
+    """Top 24 bits of a word as a multiple of 2^-24 in [0, 1): exact in fp32 and in fp64."""
+    import numpy as np
+    return (x >> np.uint64(8)).astype(np.float64) * 2.0 ** -24
+
+
+def philox_uniform(seed, stream, idx):
+    """The uniform in [0, 1) at position idx of a stream: four per counter (counter = idx // 4, word = idx % 4).
+    float32, exact."""
+    import numpy as np
+    idx = np.asarray(idx, dtype=np.uint64)
+    w = np.stack(_philox_words(seed, stream, idx >> np.uint64(2)), -1)
+    return _u01(np.take_along_axis(w, (idx & np.uint64(3)).astype(np.int64)[..., None], -1)[..., 0]).astype(np.float32)
+
+
+def philox_normal_inputs(seed, stream, idx):
+    """(u1 in (0, 1], u2 in [0, 1)) of the Box-Muller normal at idx: two normals per counter (counter = idx // 2), normal
+    idx % 2 takes words 2 * (idx % 2) and 2 * (idx % 2) + 1; u1 = 1 - u01(first word).  float64, exact in fp32."""
+    import numpy as np
+    idx = np.asarray(idx, dtype=np.uint64)
+    w = np.stack(_philox_words(seed, stream, idx >> np.uint64(1)), -1)
+    lane = (np.uint64(2) * (idx & np.uint64(1))).astype(np.int64)[..., None]
+    u1 = 1.0 - _u01(np.take_along_axis(w, lane, -1)[..., 0])
+    u2 = _u01(np.take_along_axis(w, lane + 1, -1)[..., 0])
+    return u1, u2
+
+
+def philox_normal(seed, stream, idx):
+    """Box-Muller normal at idx: sqrt(-2 ln u1) cos(2 pi u2), evaluated in float64.  Returns (float64, rounded to float32).
+    |g| <= sqrt(2 * 24 * ln 2) = 5.77."""
+    import numpy as np
+    u1, u2 = philox_normal_inputs(seed, stream, idx)
+    g = np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+    return g, g.astype(np.float32)
+
+
+def seeded_draws(seed, n, kc, kf, kfd):
+    """Every draw of one seeded render launch over n rays, with the kernels' index layouts (ray * columns + column, rays
+    numbered within the launch): u_coarse (n, kc), u_fine and u_fine2 (n, kf - kfd), g_depth (n, kfd), float32,
+    as render() / yolo_render() take them."""
+    import numpy as np
+
+    def index(cols):
+        return (np.arange(n, dtype=np.uint64)[:, None] * np.uint64(max(cols, 0))
+                + np.arange(max(cols, 0), dtype=np.uint64)[None, :])
+    kimp = max(kf - kfd, 0)
+    return dict(u_coarse=philox_uniform(seed, STREAM_COARSE, index(kc)),
+                u_fine=philox_uniform(seed, STREAM_FINE, index(kimp)),
+                u_fine2=philox_uniform(seed, STREAM_FINE2, index(kimp)),
+                g_depth=philox_normal(seed, STREAM_DEPTH, index(kfd))[1])

@@ -217,6 +217,7 @@ struct pny_scene {
     DevBuf lg_fixed, lg_words;
     int last_lg_det = 0;                     // pny_scene_last_latent_grad_mode
     DevBuf x_stash, dy_stash, dw_partial, dw_bias, dw_tables, d_samp, out_tmp, dz_tmp, sel_tmp, gdepth_tmp;
+    long long sel_count = 0;                 // entries of sel_tmp the last pny_render_backward wrote (pny_scene_last_depth_sel)
     PinnedStage table_stage;
     // "stash in the forward": the next pny_render evaluates the MLPs with the STASH instantiation straight into the
     // model-level stash (deferred mode); what each pass wrote is remembered for the backward of the same epoch

@@ -725,6 +725,7 @@ int pny_render_backward(pny_scene* s, const float* rays_dev, int64_t n, const pn
             dz = s->dz_tmp.f();
             sel = reinterpret_cast<int*>(s->sel_tmp.p);
             launch_locate_depth_samples(rays_dev, sv->depth_coarse, o->g_depth_dev, o->seed, sv->z_fine, n, kt, kfd, o->depth_std, sel, st);
+            s->sel_count = (long long)n * kfd;
         }
         launch_composite_bwd(rays_dev, sv->z_fine, sv->sample_fine, o->sigma_noise_fine_dev, n, kt, o->white_bkgd, g->rgb_fine,
                              g->depth_fine, g->weights_fine, s->d_samp.f(), dz, st);
@@ -748,6 +749,16 @@ int pny_render_backward(pny_scene* s, const float* rays_dev, int64_t n, const pn
                                sv->sample_coarse, immediate)))
             return rc;
     }
+    return PNY_OK;
+}
+
+int pny_scene_last_depth_sel(pny_scene* s, int32_t* sel_dev, int64_t count, pny_stream stream) {
+    if (!s || !sel_dev) return fail(PNY_ERR_ARG, "pny_scene_last_depth_sel: null argument");
+    if (count != s->sel_count || !s->sel_tmp.p)
+        return fail(PNY_ERR_STATE, "pny_scene_last_depth_sel: count differs from the last backward's n * n_fine_depth (or none ran)");
+    PNY_HIP(hipSetDevice(s->m->desc.device));
+    if (count > 0)
+        PNY_HIP(hipMemcpyAsync(sel_dev, s->sel_tmp.p, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return PNY_OK;
 }
 

@@ -285,3 +285,51 @@ def _clean_rays(sc, rays, kc, kf, kfd, draws, n, chunk=160, ambig=1e-5, **kw):
         if len(found) >= n:
             return np.asarray(found[:n])
     raise AssertionError("not enough unambiguous rays (%d of %d)" % (len(found), N))
+
+
+# --------------------------------------------------------------------------- seeded (Philox) draws
+def renderer_seed(ren, call=1, sb=0):
+    """The seed NeRFRenderer / YoloRenderer document for their `call`-th call from now (render.py: base_seed + 7919 * _calls,
+    _calls counted from 1; `+ sb` per object in the per-object super-batch form), written out here a second time."""
+    return (int(ren.base_seed) + 7919 * (int(ren._calls) + call) + sb) & 0xFFFFFFFFFFFFFFFF
+
+
+def clean_ray_mask(sc, rays, kc, kf, kfd, draws, ambig=1e-5, chunk=160, **kw):
+    """Boolean (n,) mask of the rays all of whose relu inputs (both passes, traced through the oracle) satisfy |h| >= ambig.
+    For seeded renders: a draw depends on the ray's index in the launch, so unclean rays cannot be left out of the launch --
+    they are rendered on both sides and given zero loss weight."""
+    import pnyolo_oracle as orc
+    N = rays.shape[0]
+    ok = torch.ones(N, dtype=torch.bool)
+    for lo in range(0, N, chunk):
+        hi = min(N, lo + chunk)
+        orc.RELU_TRACE = []
+        with torch.no_grad():
+            orc.render(sc, rays[lo:hi], kc, kf, kfd, draws["u_coarse"][lo:hi], draws["u_fine"][lo:hi], draws["u_fine2"][lo:hi],
+                       draws["g_depth"][lo:hi], **kw)
+        for t in orc.RELU_TRACE:
+            ok[lo:hi] &= t.reshape(hi - lo, -1).min(dim=1)[0] >= ambig
+        orc.RELU_TRACE = None
+    return ok
+
+
+# The seeded backward comparison (tests/test_gpu_seeded.py) and its CPU-side precondition (tests/test_cpu_philox.py): the scene
+# of test_render_backward_vs_oracle (every depth sample inside (near, far)), 96 candidate rays in launch order, the first seed
+# of a renderer with base_seed 45: 54 unambiguous rays (base seeds 1..49 give 33..54).  Few samples per ray: a ray is out if ANY
+# relu input of its (2 kc + kf) samples x views x units is within the margin.
+SEEDED_BWD = dict(ns=2, H=32, W=32, kc=6, kf=4, kfd=2, n=96, net_seed=700, base_seed=45, near=0.3, far=1.8)
+
+
+def seeded_bwd_case(with_net, base_seed=None, lat_grad=False):
+    """(net, sc, rays (n, 8), draws, weight (n,) in {0, 1}, seed): the scenario of SEEDED_BWD.  draws are the oracle's
+    restatement of what the kernels generate for the renderer's first call; weight marks the unambiguous rays."""
+    import pnyolo_oracle as orc
+    c = SEEDED_BWD
+    net, sc = scene_pair(c["ns"], c["H"], c["W"], 512, 4, 5, 3, c["net_seed"], with_net=with_net, lat_grad=lat_grad)
+    _, tgt = synth.scene_cameras(c["ns"])
+    cand = orc.gen_rays(tgt[None], c["W"], c["H"], 0.9 * c["W"], c["near"], c["far"])[0].reshape(-1, 8)
+    rays = cand[torch.from_numpy(np.random.RandomState(31).choice(cand.shape[0], c["n"], replace=False))]
+    seed = ((c["base_seed"] if base_seed is None else base_seed) + 7919) & 0xFFFFFFFFFFFFFFFF
+    draws = orc.seeded_draws(seed, c["n"], c["kc"], c["kf"], c["kfd"])
+    weight = clean_ray_mask(sc, rays, c["kc"], c["kf"], c["kfd"], draws).float()
+    return net, sc, rays, draws, weight, seed
