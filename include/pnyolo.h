@@ -473,6 +473,31 @@ int pny_model_last_flush_precision(pny_model* m, int* code);
  * [0] stash forward (reference operation order), [1] dX chain, [2] weight-gradient GEMMs (+ reduction). */
 int pny_scene_last_backward_stats(pny_scene* s, double flops[3], double kernel_ms[3]);
 
+/* ---- optimizer: Adam over every tensor of a parameter group in ONE launch (csrc/optim.hip), with the packed operands of a
+ * model rebuilt behind it.  The arithmetic is torch.optim.Adam's (no amsgrad, no maximize), per element in fp32:
+ *   g = grad (+ weight_decay * p);  m += (g - m) * (1 - beta1);  v = v * beta2 + g * g * (1 - beta2);
+ *   p -= (lr / (1 - beta1^step)) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * with the scalars computed in double on the host.  Bit-reproducible (no atomics).  A handle is bound to one device.
+ * pny_optim_add_tensor registers one tensor of `count` fp32 elements (parameter and both moments: device memory, 4-byte
+ * aligned, borrowed for the handle's life) and returns its index (>= 0) or a negative status.
+ * pny_optim_adam_step steps the tensors [first, first + n): grads_dev (host array of n device pointers, read during the call
+ * only) gives each tensor's gradient, NULL = this tensor takes no step.  `step` is the 1-based count of the step being taken
+ * (the same for every tensor of the call).  Asynchronous on `stream`; nothing waits for the device (the first step after
+ * pny_optim_add_tensor uploads the work tables synchronously).  model may be NULL; otherwise the packed operands of `model`
+ * are rebuilt behind the update on the same stream (what pny_model_refresh does, with its preconditions), so that the next
+ * launch of any scene of the model sees the stepped weights and a weight moved out of the f16 range is reported
+ * (PNY_RANGE_WEIGHT) by the step that moved it.  Not for graph capture. */
+typedef struct pny_optim pny_optim;
+typedef struct pny_adam_hyper {
+    double lr, beta1, beta2, eps, weight_decay;
+    int64_t step;
+} pny_adam_hyper;
+int pny_optim_create(pny_optim** out, int device);
+void pny_optim_destroy(pny_optim* o);
+int pny_optim_add_tensor(pny_optim* o, float* param_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t count);
+int pny_optim_adam_step(pny_optim* o, const pny_adam_hyper* h, float* const* grads_dev, int first, int n, pny_model* model,
+                        pny_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,25 @@ struct PackJob {
 };
 void launch_repack(const PackJob* jobs_dev, int n_jobs, long long max_elems, hipStream_t st, unsigned* range_flag = nullptr);
 
+// ---- optimizer (optim.hip): one Adam launch over every tensor of a parameter group
+enum { ADAM_CHUNK = 16384 };   // elements per workgroup: 256 lanes x 16 float4
+struct AdamTensor {            // device-resident, fixed while the optimizer lives
+    float* p;
+    float* m;
+    float* v;
+    long long count;
+};
+struct AdamChunk {             // device-resident work table: elements [offset, offset + count) of tensor `tensor`
+    int tensor, count;
+    long long offset;
+};
+struct AdamScalars {           // rounded to fp32 once on the host (optim_api.hip)
+    float step_size, one_minus_beta1, beta2, one_minus_beta2, bc2_sqrt, eps, weight_decay;
+};
+// grads: one pointer per tensor of [first, ...), indexed tensor - first; host-pinned, device-readable; null = no step
+void launch_adam(const AdamTensor* tensors_dev, const AdamChunk* chunks_dev, int n_chunks, float* const* grads, int first,
+                 const AdamScalars& sc, hipStream_t st);
+
 // ---- backward pass (mlp_bwd.hip)
 struct BwdArgs {
     // TRANSPOSED packed weights (A operands of dX^T = W^T dY^T), inside the model's packed blob

@@ -51,6 +51,11 @@ class RenderGrads(C.Structure):
                                           "weights_fine")]
 
 
+class AdamHyper(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("step", C.c_int64)]
+
+
 # name -> (restype, argtypes); every symbol include/pnyolo.h declares
 SIGNATURES = {
     "pny_version": (C.c_int, []),
@@ -124,6 +129,11 @@ SIGNATURES = {
     "pny_render_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(RenderOpts), C.POINTER(RenderSaved),
                                       C.POINTER(RenderGrads), C.c_int, C.c_void_p]),
     "pny_scene_last_depth_sel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "pny_optim_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
+    "pny_optim_destroy": (None, [C.c_void_p]),
+    "pny_optim_add_tensor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "pny_optim_adam_step": (C.c_int, [C.c_void_p, C.POINTER(AdamHyper), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p,
+                                      C.c_void_p]),
 }
 
 _lib = None
