@@ -67,44 +67,18 @@ int mark_stream_point(pny_scene* s, hipStream_t st) {
 }
 }  // namespace pny
 
-// ---------------------------------------------------------------------------------- packing
-// A-operand order of v_mfma_f32_32x32x2_f32 for H^T = W X^T (see mlp.hip): for k-iteration j (8
-// inputs), n-tile nt (32 output features), lane l, component r:
-//     Wp[((j*NT + nt)*64 + l)*4 + r] = W[32 nt + (l & 31)][8 j + 4 (l >> 5) + r]   (0 beyond K)
-// k-iteration-major: the 16 KiB that ALL waves of a workgroup need for iteration j are contiguous,
-// so the 16 per-wave streams of a CU walk the same pages together (measured +1 % over n-tile-major,
-// where each stream strides through its own 64 KiB region).
-static void pack_layer(const float* W, int n_out, int k_in, int k_pad, std::vector<float>& dst) {
-    const int J = k_pad / 8, NT = n_out / 32;
-    const size_t base = dst.size();
-    dst.resize(base + (size_t)NT * J * 64 * 4);
-    float* o = dst.data() + base;
-    for (int j = 0; j < J; ++j)
-        for (int nt = 0; nt < NT; ++nt)
-            for (int l = 0; l < 64; ++l)
-                for (int r = 0; r < 4; ++r) {
-                    const int n = 32 * nt + (l & 31), k = 8 * j + 4 * (l >> 5) + r;
-                    *o++ = (k < k_in) ? W[(size_t)n * k_in + k] : 0.0f;
-                }
-}
+// ---------------------------------------------------------------------------------- packed weights
+// The operand layouts are pack.hip's: this file lays the images out in one allocation and lists, per image, the job that
+// builds it from the state_dict tensor(s) it comes from (RepackEntry).  pny_model_finalize runs the jobs on uploaded copies
+// of the tensors, pny_model_refresh on the live parameters.
 
-// Split-f16 image of a layer for mlp_h2.hip: w = w1 + w2, w1 = f16(w), w2 = f16(w - w1) (round to nearest); per 16-k step
-// [n-tile][plane][lane] x 8 halves, lane l holding W[32 nt + (l & 31)][16 j + 8 (l >> 5) + 0..7].  4 bytes per weight.
-static void pack_layer_h2(const float* W, int n_out, int k_in, int k_pad, std::vector<float>& dst) {
-    const int J = k_pad / 16, NT = n_out / 32;
-    const size_t base = dst.size();
-    dst.resize(base + (size_t)J * NT * 2 * 64 * 4);
-    _Float16* o = reinterpret_cast<_Float16*>(dst.data() + base);
-    for (int j = 0; j < J; ++j)
-        for (int nt = 0; nt < NT; ++nt)
-            for (int p = 0; p < 2; ++p)
-                for (int l = 0; l < 64; ++l)
-                    for (int r = 0; r < 8; ++r) {
-                        const int n = 32 * nt + (l & 31), k = 16 * j + 8 * (l >> 5) + r;
-                        const float w = (k < k_in) ? W[(size_t)n * k_in + k] : 0.0f;
-                        const _Float16 w1 = (_Float16)w;
-                        *o++ = p == 0 ? w1 : (_Float16)(w - (float)w1);
-                    }
+// 16-byte elements a job of `kind` writes (PackJob::count); PACK_COPY / PACK_ADD2 count floats.  An image is 4 floats per element.
+static int pack_count(int kind, int n_out, int k_in, int k_pad, int count) {
+    if (kind == PACK_A || kind == PACK_NT || kind == PACK_H2) return (n_out / 32) * (k_pad / 8) * 64;
+    if (kind == PACK_AT || kind == PACK_H2T) return (k_in / 32) * (k_pad / 8) * 64;   // the matrix is W^T: k_in rows, K = n_out padded
+    if (kind == PACK_NTT) return (n_out / 32) * (k_in / 8) * 64;
+    if (kind == PACK_H1) return (k_pad / 16) * (n_out / 32) * 64;
+    return count;
 }
 
 static const HostTensor* find(const pny_model* m, const std::string& name) {
@@ -121,161 +95,164 @@ static int need(const pny_model* m, const std::string& name, std::vector<int64_t
 }
 
 struct PackPlan {
-    std::vector<float> blob;
-    std::vector<std::pair<const float**, size_t>> fix;  // pointer slot -> offset in blob
-    size_t add_plain(const std::vector<float>& v) {
-        // keep every sub-buffer 64-byte aligned
-        while (blob.size() % 16) blob.push_back(0.f);
-        const size_t off = blob.size();
-        blob.insert(blob.end(), v.begin(), v.end());
+    size_t floats = 0;                                  // size of the packed allocation so far
+    std::vector<std::pair<const float**, size_t>> fix;  // pointer slot -> float offset in it
+    size_t reserve(size_t n) {
+        floats = (floats + 15) / 16 * 16;   // keep every sub-buffer 64-byte aligned
+        const size_t off = floats;
+        floats += n;
         return off;
     }
 };
 
+// Lays out the images of one MLP: validates the tensors, appends one RepackEntry per image to m->repack and records where
+// each pointer of `w` / `wt` will point.  No bytes are produced here.
 static int pack_mlp(pny_model* m, const std::string& pre, MlpWeights& w, MlpWeightsT& wt, PackPlan& plan) {
     const pny_model_desc& d = m->desc;
     const int d_in = 3 + 6 * d.num_freqs + 3;
     const int nvb = d.combine_layer < d.n_blocks ? d.combine_layer : d.n_blocks;
     const HostTensor* t = nullptr;
     int rc;
-    auto packed = [&](const std::string& name, int k_in, int k_pad, const float** slot) -> int {
-        if ((rc = need(m, name, {HID, k_in}, &t))) return rc;
-        while (plan.blob.size() % 16) plan.blob.push_back(0.f);
-        const size_t off = plan.blob.size();
-        pack_layer(t->data.data(), HID, k_in, k_pad, plan.blob);
-        plan.fix.push_back({slot, off});
-        m->repack.push_back({PACK_A, name, "", off, nullptr, HID, k_in, k_pad, 0});
-        return 0;
-    };
-    auto plain = [&](const std::string& name, std::vector<int64_t> shape, const float** slot) -> int {
+    // one image of tensor `name` (`shape`: (n_out, k_in) of a matrix kind); PACK_COPY / PACK_ADD2 keep the tensor's own order
+    auto add = [&](int kind, const std::string& name, const std::string& name2, std::vector<int64_t> shape, int k_pad,
+                   const float** slot) -> int {
+        const HostTensor* t2 = nullptr;
         if ((rc = need(m, name, shape, &t))) return rc;
-        const size_t off = plan.add_plain(t->data);
-        plan.fix.push_back({slot, off});
-        m->repack.push_back({PACK_COPY, name, "", off, nullptr, 0, 0, 0, (int)t->data.size()});
+        if (!name2.empty() && (rc = need(m, name2, shape, &t2))) return rc;
+        const bool plain = kind == PACK_COPY || kind == PACK_ADD2;
+        RepackEntry e{kind, name, name2, 0, nullptr, 0, 0, 0, 0};
+        if (plain) {
+            e.count = (int)t->data.size();
+        } else {
+            e.n_out = (int)shape[0];
+            e.k_in = (int)shape[1];
+            e.k_pad = k_pad;
+        }
+        if (kind == PACK_H2 || kind == PACK_H2T)
+            for (float v : t->data)
+                if (!(std::fabs(v) <= 65504.0f)) m->f16_weights_ok = false;   // out of the f16 range (or NaN): AUTO stays on fp32
+        e.dst_off = plan.reserve((plain ? 1 : 4) * (size_t)pack_count(kind, e.n_out, e.k_in, e.k_pad, e.count));
+        plan.fix.push_back({slot, e.dst_off});
+        m->repack.push_back(e);
         return 0;
     };
     // `x = x + lin_z[b](z)` (resnetfc.py:176-182) happens right after lin_in (b = 0) or right after
     // the previous block's fc_1 (b > 0): its bias is folded into that layer's bias here, so the kernel
     // has one bias vector per GEMM chain link and no separate bias pass.
-    auto plain_plus = [&](const std::string& name, const std::string& extra, const float** slot) -> int {
-        const HostTensor* t2 = nullptr;
-        if ((rc = need(m, name, {HID}, &t))) return rc;
-        std::vector<float> sum = t->data;
-        if (!extra.empty()) {
-            if ((rc = need(m, extra, {HID}, &t2))) return rc;
-            for (int i = 0; i < HID; ++i) sum[i] += t2->data[i];
-        }
-        const size_t off = plan.add_plain(sum);
-        plan.fix.push_back({slot, off});
-        m->repack.push_back({extra.empty() ? PACK_COPY : PACK_ADD2, name, extra, off, nullptr, 0, 0, 0, HID});
-        return 0;
+    auto bias_plus = [&](const std::string& name, const std::string& extra, const float** slot) -> int {
+        return add(extra.empty() ? PACK_COPY : PACK_ADD2, name, extra, {HID}, 0, slot);
     };
     auto zbias = [&](int b) { return b < nvb ? pre + "lin_z." + std::to_string(b) + ".bias" : std::string(); };
-    if ((rc = packed(pre + "lin_in.weight", d_in, D_IN_PAD, &w.w_in))) return rc;
-    if ((rc = plain_plus(pre + "lin_in.bias", zbias(0), &w.b_in))) return rc;
+    auto block = [&](int b) { return pre + "blocks." + std::to_string(b); };
+    if ((rc = add(PACK_A, pre + "lin_in.weight", "", {HID, d_in}, D_IN_PAD, &w.w_in))) return rc;
+    if ((rc = bias_plus(pre + "lin_in.bias", zbias(0), &w.b_in))) return rc;
     for (int b = 0; b < nvb; ++b) {
         const std::string p = pre + "lin_z." + std::to_string(b);
-        if ((rc = packed(p + ".weight", d.d_latent, d.d_latent, &w.w_z[b]))) return rc;
+        if ((rc = add(PACK_A, p + ".weight", "", {HID, d.d_latent}, d.d_latent, &w.w_z[b]))) return rc;
         w.b_z[b] = nullptr;  // folded
     }
     for (int b = 0; b < d.n_blocks; ++b) {
-        const std::string p = pre + "blocks." + std::to_string(b);
-        if ((rc = packed(p + ".fc_0.weight", HID, HID, &w.w_fc0[b]))) return rc;
-        if ((rc = plain(p + ".fc_0.bias", {HID}, &w.b_fc0[b]))) return rc;
-        if ((rc = packed(p + ".fc_1.weight", HID, HID, &w.w_fc1[b]))) return rc;
-        if ((rc = plain_plus(p + ".fc_1.bias", zbias(b + 1), &w.b_fc1[b]))) return rc;
+        if ((rc = add(PACK_A, block(b) + ".fc_0.weight", "", {HID, HID}, HID, &w.w_fc0[b]))) return rc;
+        if ((rc = add(PACK_COPY, block(b) + ".fc_0.bias", "", {HID}, 0, &w.b_fc0[b]))) return rc;
+        if ((rc = add(PACK_A, block(b) + ".fc_1.weight", "", {HID, HID}, HID, &w.w_fc1[b]))) return rc;
+        if ((rc = bias_plus(block(b) + ".fc_1.bias", zbias(b + 1), &w.b_fc1[b]))) return rc;
     }
-    if ((rc = plain(pre + "lin_out.weight", {d.d_out, HID}, &w.w_out))) return rc;
-    if ((rc = plain(pre + "lin_out.bias", {d.d_out}, &w.b_out))) return rc;
-    // transposed copies for the backward chain (dX^T = W^T dY^T, mlp_bwd.hip): same operand order, W^T as the matrix
-    auto packedT = [&](const std::string& name, int n_out, int k_in, const float** slot) -> int {
-        if ((rc = need(m, name, {n_out, k_in}, &t))) return rc;
-        std::vector<float> wtr((size_t)n_out * k_in);
-        for (int n = 0; n < n_out; ++n)
-            for (int k = 0; k < k_in; ++k) wtr[(size_t)k * n_out + n] = t->data[(size_t)n * k_in + k];
-        while (plan.blob.size() % 16) plan.blob.push_back(0.f);
-        const size_t off = plan.blob.size();
-        // W^T is (k_in x n_out): its rows (the GEMM's outputs) must be 512; its K (= n_out) is padded to a ring multiple
-        pack_layer(wtr.data(), k_in, n_out, n_out == HID ? HID : D_IN_PAD, plan.blob);
-        plan.fix.push_back({slot, off});
-        m->repack.push_back({PACK_AT, name, "", off, nullptr, n_out, k_in, n_out == HID ? HID : D_IN_PAD, 0});
-        return 0;
-    };
+    if ((rc = add(PACK_COPY, pre + "lin_out.weight", "", {d.d_out, HID}, 0, &w.w_out))) return rc;
+    if ((rc = add(PACK_COPY, pre + "lin_out.bias", "", {d.d_out}, 0, &w.b_out))) return rc;
     // split-f16 images for the f16x2 kernel (mlp_h2.hip)
-    auto packed_h2 = [&](const std::string& name, int k_in, int k_pad, const float** slot) -> int {
-        if ((rc = need(m, name, {HID, k_in}, &t))) return rc;
-        for (float v : t->data)
-            if (!(std::fabs(v) <= 65504.0f)) m->f16_weights_ok = false;   // out of the f16 range (or NaN): AUTO stays on fp32
-        while (plan.blob.size() % 16) plan.blob.push_back(0.f);
-        const size_t off = plan.blob.size();
-        pack_layer_h2(t->data.data(), HID, k_in, k_pad, plan.blob);
-        plan.fix.push_back({slot, off});
-        m->repack.push_back({PACK_H2, name, "", off, nullptr, HID, k_in, k_pad, 0});
-        return 0;
-    };
-    if ((rc = packed_h2(pre + "lin_in.weight", d_in, D_IN_PAD, &wt.h2_in))) return rc;
+    if ((rc = add(PACK_H2, pre + "lin_in.weight", "", {HID, d_in}, D_IN_PAD, &wt.h2_in))) return rc;
     for (int b = 0; b < d.n_blocks; ++b) {
-        const std::string p = pre + "blocks." + std::to_string(b);
-        if ((rc = packed_h2(p + ".fc_0.weight", HID, HID, &wt.h2_fc0[b]))) return rc;
-        if ((rc = packed_h2(p + ".fc_1.weight", HID, HID, &wt.h2_fc1[b]))) return rc;
+        if ((rc = add(PACK_H2, block(b) + ".fc_0.weight", "", {HID, HID}, HID, &wt.h2_fc0[b]))) return rc;
+        if ((rc = add(PACK_H2, block(b) + ".fc_1.weight", "", {HID, HID}, HID, &wt.h2_fc1[b]))) return rc;
     }
-    // stacked transposed lin_z for the latent gradient (latent_grad.hip): W_cat[c][b * 512 + f] = lin_z[b].weight[f][c],
-    // n-tile-major [c / 32][k-iteration][lane] float4 like the projection weights (encoder.hip build_pixel_linear)
+    // stacked transposed lin_z for the latent gradient (latent_grad.hip): W_cat[c][b * 512 + f] = lin_z[b].weight[f][c], one
+    // n-tile-major image of K = nvb * 512 in which block b owns k-iterations [64 b, 64 b + 64) of every n-tile
     wt.wzT_cat = nullptr;
     if (nvb > 0) {
-        const int Lc = d.d_latent, Kc = nvb * HID, Jc = Kc / 8;
-        while (plan.blob.size() % 16) plan.blob.push_back(0.f);
-        const size_t off = plan.blob.size();
-        plan.blob.resize(off + (size_t)Lc * Kc);
+        const int Lc = d.d_latent, Kc = nvb * HID;
+        const size_t off = plan.reserve((size_t)Lc * Kc);
         for (int b = 0; b < nvb; ++b) {
             const std::string name = pre + "lin_z." + std::to_string(b) + ".weight";
             if ((rc = need(m, name, {HID, Lc}, &t))) return rc;
-            for (int nt = 0; nt < Lc / 32; ++nt)
-                for (int jl = 0; jl < HID / 8; ++jl)
-                    for (int l = 0; l < 64; ++l)
-                        for (int r = 0; r < 4; ++r) {
-                            const int c = 32 * nt + (l & 31), f = 8 * jl + 4 * (l >> 5) + r;
-                            plan.blob[off + (((size_t)nt * Jc + b * (HID / 8) + jl) * 64 + l) * 4 + r] = t->data[(size_t)f * Lc + c];
-                        }
             m->repack.push_back({PACK_NTT, name, "", off + (size_t)b * (HID / 8) * 64 * 4, nullptr, Lc, HID, Kc, 0});
         }
         plan.fix.push_back({&wt.wzT_cat, off});
     }
-    // ... and of the TRANSPOSED matrices for the f16x2 backward chain (mlp_bwd_h2.hip): W^T is (k_in x n_out), K = n_out
-    auto packed_h2T = [&](const std::string& name, int n_out, int k_in, const float** slot) -> int {
-        if ((rc = need(m, name, {n_out, k_in}, &t))) return rc;
-        std::vector<float> wtr((size_t)n_out * k_in);
-        for (int n = 0; n < n_out; ++n)
-            for (int k = 0; k < k_in; ++k) wtr[(size_t)k * n_out + n] = t->data[(size_t)n * k_in + k];
-        for (float v : t->data)
-            if (!(std::fabs(v) <= 65504.0f)) m->f16_weights_ok = false;
-        const int k_pad = n_out == HID ? HID : D_IN_PAD;
-        while (plan.blob.size() % 16) plan.blob.push_back(0.f);
-        const size_t off = plan.blob.size();
-        pack_layer_h2(wtr.data(), k_in, n_out, k_pad, plan.blob);
-        plan.fix.push_back({slot, off});
-        m->repack.push_back({PACK_H2T, name, "", off, nullptr, n_out, k_in, k_pad, 0});
-        return 0;
-    };
+    // transposed images for the backward chain (dX^T = W^T dY^T, mlp_bwd.hip), fp32 and split-f16 (mlp_bwd_h2.hip): W^T is
+    // (k_in x n_out), its rows (the GEMM's outputs) must be 512; its K (= n_out) is padded to a ring multiple
     if (d.d_out > D_IN_PAD) return fail(PNY_ERR_ARG, "d_out > 64");
-    if ((rc = plain(pre + "lin_in.weight", {HID, d_in}, &wt.w_in_plain))) return rc;
-    if ((rc = packedT(pre + "lin_out.weight", d.d_out, HID, &wt.wT_out))) return rc;
+    if ((rc = add(PACK_COPY, pre + "lin_in.weight", "", {HID, d_in}, 0, &wt.w_in_plain))) return rc;
+    if ((rc = add(PACK_AT, pre + "lin_out.weight", "", {d.d_out, HID}, D_IN_PAD, &wt.wT_out))) return rc;
     for (int b = 0; b < d.n_blocks; ++b) {
-        const std::string p = pre + "blocks." + std::to_string(b);
-        if ((rc = packedT(p + ".fc_0.weight", HID, HID, &wt.wT_fc0[b]))) return rc;
-        if ((rc = packedT(p + ".fc_1.weight", HID, HID, &wt.wT_fc1[b]))) return rc;
+        if ((rc = add(PACK_AT, block(b) + ".fc_0.weight", "", {HID, HID}, HID, &wt.wT_fc0[b]))) return rc;
+        if ((rc = add(PACK_AT, block(b) + ".fc_1.weight", "", {HID, HID}, HID, &wt.wT_fc1[b]))) return rc;
     }
-    if ((rc = packed_h2T(pre + "lin_out.weight", d.d_out, HID, &wt.h2T_out))) return rc;
+    if ((rc = add(PACK_H2T, pre + "lin_out.weight", "", {d.d_out, HID}, D_IN_PAD, &wt.h2T_out))) return rc;
     for (int b = 0; b < d.n_blocks; ++b) {
-        const std::string p = pre + "blocks." + std::to_string(b);
-        if ((rc = packed_h2T(p + ".fc_0.weight", HID, HID, &wt.h2T_fc0[b]))) return rc;
-        if ((rc = packed_h2T(p + ".fc_1.weight", HID, HID, &wt.h2T_fc1[b]))) return rc;
+        if ((rc = add(PACK_H2T, block(b) + ".fc_0.weight", "", {HID, HID}, HID, &wt.h2T_fc0[b]))) return rc;
+        if ((rc = add(PACK_H2T, block(b) + ".fc_1.weight", "", {HID, HID}, HID, &wt.h2T_fc1[b]))) return rc;
     }
     return 0;
 }
 
+// m->repack -> the job table of one launch_repack; `src` holds the device address of every state_dict tensor by name
+static int build_pack_jobs(const pny_model* m, const std::map<std::string, const float*>& src, std::vector<PackJob>& jobs,
+                           long long& max_elems) {
+    jobs.clear();
+    max_elems = 0;
+    for (const RepackEntry& e : m->repack) {
+        auto it = src.find(e.name);
+        if (it == src.end()) return fail(PNY_ERR_STATE, "pny_model_refresh: no device pointer bound for '" + e.name + "'");
+        PackJob j;
+        memset(&j, 0, sizeof(j));
+        j.kind = e.kind;
+        j.src = it->second;
+        if (!e.name2.empty()) {
+            auto it2 = src.find(e.name2);
+            if (it2 == src.end()) return fail(PNY_ERR_STATE, "pny_model_refresh: no device pointer bound for '" + e.name2 + "'");
+            j.src2 = it2->second;
+        }
+        j.dst = e.dst_abs ? e.dst_abs : m->packed.f() + e.dst_off;
+        j.n_out = e.n_out;
+        j.k_in = e.k_in;
+        j.k_pad = e.k_pad;
+        j.count = pack_count(e.kind, e.n_out, e.k_in, e.k_pad, e.count);
+        max_elems = std::max(max_elems, (long long)j.count);
+        jobs.push_back(j);
+    }
+    return 0;
+}
+
+// pny_model_finalize: every image of m->repack built by the device packer from copies of the state_dict tensors uploaded
+// into `stage`.  Synchronous; the caller releases `stage` and `table` whatever the outcome.
+static int pack_from_host(pny_model* m, DevBuf& stage, DevBuf& table) {
+    std::map<std::string, size_t> at;   // tensor -> float offset in `stage` (several entries name the same tensor)
+    size_t total = 0;
+    for (const RepackEntry& e : m->repack)
+        for (const std::string* name : {&e.name, &e.name2})
+            if (!name->empty() && at.emplace(*name, total).second) total += m->host.at(*name).data.size();
+    int rc;
+    if ((rc = stage.reserve(total * sizeof(float)))) return rc;
+    std::map<std::string, const float*> src;
+    for (const auto& kv : at) {
+        const std::vector<float>& v = m->host.at(kv.first).data;
+        PNY_HIP(hipMemcpy(stage.f() + kv.second, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+        src[kv.first] = stage.f() + kv.second;
+    }
+    std::vector<PackJob> jobs;
+    long long max_elems;
+    if ((rc = build_pack_jobs(m, src, jobs, max_elems))) return rc;
+    if ((rc = table.reserve(jobs.size() * sizeof(PackJob)))) return rc;
+    PNY_HIP(hipMemcpy(table.p, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice));
+    // no range word: a weight outside the f16 range at finalize clears f16_weights_ok (pack_mlp) and reports nothing
+    launch_repack(reinterpret_cast<const PackJob*>(table.p), (int)jobs.size(), max_elems, nullptr, nullptr);
+    PNY_HIP(hipGetLastError());
+    PNY_HIP(hipDeviceSynchronize());
+    return 0;
+}
+
 // Single-plane f16 images for PNY_PRECISION_F16 (mlp_h1.hip): per 16-k step [n-tile][lane] x 8 halves, lane l holding
-// f16(W[32 nt + (l & 31)][16 j + 8 (l >> 5) + 0..7]) -- by definition plane 0 of the split image (pack_layer_h2), so they are
+// f16(W[32 nt + (l & 31)][16 j + 8 (l >> 5) + 0..7]) -- by definition plane 0 of the split image (pack.hip PACK_H2), so they are
 // copied out of the split images on the device (pack.hip PACK_H1) and are current whenever those are.  Built once a scene of
 // the model is set to F16; from then on every pny_model_finalize rebuilds them and every pny_model_refresh repacks them right
 // behind the split images on its stream.  A model that never runs F16 holds no such images and pays nothing for them.
@@ -298,7 +275,7 @@ static int build_h1_images(pny_model* m) {
         j.dst = reinterpret_cast<float*>(p);
         j.n_out = HID;
         j.k_pad = k_pad;
-        j.count = (k_pad / 16) * (HID / 32) * 64;   // 16-byte fragments
+        j.count = pack_count(PACK_H1, HID, 0, k_pad, 0);
         m->h1_max_elems = std::max(m->h1_max_elems, (long long)j.count);
         jobs.push_back(j);
         *slot = reinterpret_cast<const float*>(p);
@@ -440,9 +417,9 @@ int pny_model_finalize(pny_model* m) {
     m->f16_weights_ok = true;
     if ((rc = pack_mlp(m, "mlp_coarse.", m->coarse, m->coarse_t, plan))) return rc;
     if (m->desc.has_fine && (rc = pack_mlp(m, "mlp_fine.", m->fine, m->fine_t, plan))) return rc;
-    if (plan.blob.size() * sizeof(float) >= (1ull << 31)) return fail(PNY_ERR_ARG, "packed weights exceed the 2 GiB raw-buffer range");
-    if ((rc = m->packed.reserve(plan.blob.size() * sizeof(float)))) return rc;
-    PNY_HIP(hipMemcpy(m->packed.p, plan.blob.data(), plan.blob.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (plan.floats * sizeof(float) >= (1ull << 31)) return fail(PNY_ERR_ARG, "packed weights exceed the 2 GiB raw-buffer range");
+    if ((rc = m->packed.reserve(plan.floats * sizeof(float)))) return rc;
+    PNY_HIP(hipMemset(m->packed.p, 0, plan.floats * sizeof(float)));   // the alignment gaps between the images stay zero
     for (auto& f : plan.fix) *f.first = m->packed.f() + f.second;
     if (!m->desc.has_fine) {
         m->fine = m->coarse;
@@ -458,10 +435,8 @@ int pny_model_finalize(pny_model* m) {
         if (nvb > 0) {
             for (int f = 0; f < (m->desc.has_fine ? 2 : 1); ++f) {
                 const std::string pre = f ? "mlp_fine." : "mlp_coarse.";
-                std::vector<const float*> mats;
-                for (int b = 0; b < nvb; ++b) mats.push_back(find(m, pre + "lin_z." + std::to_string(b) + ".weight")->data.data());
                 std::string err;
-                if (!build_pixel_linear(mats.data(), nvb, HID, m->desc.d_latent, &m->zproj[f], &m->zproj_allocs, &err))
+                if (!build_pixel_linear(nvb, HID, m->desc.d_latent, &m->zproj[f], &m->zproj_allocs, &err))
                     return fail(PNY_ERR_HIP, "latent projection weights: " + err);
                 for (int b = 0; b < nvb; ++b)   // stacked along the output rows: block b owns n-tiles [16 b, 16 b + 16)
                     m->repack.push_back({PACK_NT, pre + "lin_z." + std::to_string(b) + ".weight", "", 0,
@@ -472,6 +447,11 @@ int pny_model_finalize(pny_model* m) {
             m->has_zproj = true;
         }
     }
+    DevBuf stage, table;
+    rc = pack_from_host(m, stage, table);
+    stage.release();
+    table.release();
+    if (rc) return rc;
     ++m->generation;
     m->has_encoder = false;
     if (find(m, "encoder.model.conv1.weight")) {
@@ -510,34 +490,8 @@ int pny_model_refresh(pny_model* m, pny_stream stream) {
     int rc;
     if (!m->repack_ready) {   // resolve names -> bound device pointers, upload the job table (once per binding)
         std::vector<PackJob> jobs;
-        long long max_elems = 0;
-        for (const RepackEntry& e : m->repack) {
-            auto it = m->params_dev.find(e.name);
-            if (it == m->params_dev.end()) return fail(PNY_ERR_STATE, "pny_model_refresh: no device pointer bound for '" + e.name + "'");
-            PackJob j;
-            memset(&j, 0, sizeof(j));
-            j.kind = e.kind;
-            j.src = it->second;
-            if (!e.name2.empty()) {
-                auto it2 = m->params_dev.find(e.name2);
-                if (it2 == m->params_dev.end()) return fail(PNY_ERR_STATE, "pny_model_refresh: no device pointer bound for '" + e.name2 + "'");
-                j.src2 = it2->second;
-            }
-            j.dst = e.dst_abs ? e.dst_abs : m->packed.f() + e.dst_off;
-            j.n_out = e.n_out;
-            j.k_in = e.k_in;
-            j.k_pad = e.k_pad;
-            if (e.kind == PACK_A || e.kind == PACK_NT || e.kind == PACK_H2)
-                j.count = (e.n_out / 32) * (e.k_pad / 8) * 64;       // 16-byte elements
-            else if (e.kind == PACK_AT || e.kind == PACK_H2T)
-                j.count = (e.k_in / 32) * (e.k_pad / 8) * 64;
-            else if (e.kind == PACK_NTT)
-                j.count = (e.n_out / 32) * (e.k_in / 8) * 64;
-            else
-                j.count = e.count;
-            max_elems = std::max(max_elems, (long long)j.count);
-            jobs.push_back(j);
-        }
+        long long max_elems;
+        if ((rc = build_pack_jobs(m, m->params_dev, jobs, max_elems))) return rc;
         if ((rc = m->repack_jobs.reserve(jobs.size() * sizeof(PackJob)))) return rc;
         PNY_HIP(hipMemcpy(m->repack_jobs.p, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice));
         m->n_repack_jobs = (int)jobs.size();

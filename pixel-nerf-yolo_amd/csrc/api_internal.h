@@ -83,8 +83,8 @@ struct PinnedStage {
     }
 };
 
-// One packed sub-buffer of the model and how to rebuild it from the state_dict tensor(s) it came from: recorded by
-// pny_model_finalize, replayed on the device by pny_model_refresh (pack.hip).
+// One packed sub-buffer of the model and how to build it from the state_dict tensor(s) it comes from (pack.hip): recorded by
+// pny_model_finalize, which runs it on uploaded copies of the tensors; pny_model_refresh runs it on the live parameters.
 struct RepackEntry {
     int kind;
     std::string name, name2;

@@ -31,10 +31,9 @@ struct EncoderWeights {
 };
 
 // Pixel-wise linear map over a channel-last tensor, out[p][n] = sum_k W[n][k] in[p][k], run by the
-// same implicit-GEMM kernel as a 1x1 convolution (scale 1, shift 0, no relu).  `mats` are nmat
-// row-major (rows x k) matrices stacked along n; rows*nmat must be a multiple of 64, k of 8.
-bool build_pixel_linear(const float* const* mats, int nmat, int rows, int k, ConvLayer* out, std::vector<float*>* allocs,
-                        std::string* err);
+// same implicit-GEMM kernel as a 1x1 convolution (scale 1, shift 0, no relu).  W is nmat row-major (rows x k) matrices
+// stacked along n; rows*nmat must be a multiple of 64, k of 8.  Allocates the layer; the caller fills `w` (pack.hip PACK_NT).
+bool build_pixel_linear(int nmat, int rows, int k, ConvLayer* out, std::vector<float*>* allocs, std::string* err);
 // f16x2: split-f16 matrix products (pixel_linear_h2_kernel) instead of the fp32 MFMA
 bool run_pixel_linear(const ConvLayer& L, const float* in, long long npix, float* out, hipStream_t st, bool f16x2 = false);
 

@@ -6,7 +6,7 @@
 // out^T[cout][pixel] = W[cout][(ky,kx,ci)] * patch^T, with channel-last activations so that a
 // B-operand fragment (4 consecutive input channels of one tap) is one 16-byte load and an
 // accumulator quad (4 consecutive output channels of one pixel) is one 16-byte store; weights
-// are pre-packed in lane order like the MLP's (api.hip pack_layer).  Batch norm is applied in
+// are pre-packed in lane order like the MLP's (pack.hip PACK_NT).  Batch norm is applied in
 // the epilogue as x*scale + shift, then the residual add and relu -- one kernel per conv.
 // The pyramid is upsampled (bilinear, align_corners=True) and concatenated directly into the
 // channel-last latent the MLP kernel gathers from.
@@ -534,7 +534,7 @@ static bool build_conv(const EncoderWeights::Getter& get, const std::string& con
     L.pad = pad;
     const int K = k * k * L.cin_p;
     L.J = (K + 7) / 8;
-    // K order (ky, kx, ci); A-operand lane order as in api.hip pack_layer
+    // K order (ky, kx, ci); A-operand lane order, n-tile-major as pack.hip PACK_NT
     std::vector<float> pk((size_t)(cout / 32) * L.J * 64 * 4);
     size_t o = 0;
     for (int nt = 0; nt < cout / 32; ++nt)
@@ -557,8 +557,7 @@ static bool build_conv(const EncoderWeights::Getter& get, const std::string& con
     return upload(pk, &L.w, allocs, err) && upload(sc, &L.scale, allocs, err) && upload(sh, &L.shift, allocs, err);
 }
 
-bool build_pixel_linear(const float* const* mats, int nmat, int rows, int k, ConvLayer* out, std::vector<float*>* allocs,
-                        std::string* err) {
+bool build_pixel_linear(int nmat, int rows, int k, ConvLayer* out, std::vector<float*>* allocs, std::string* err) {
     const int cout = nmat * rows;
     if (cout % 64 || k % 8) {
         *err = "pixel-linear map needs rows*nmat % 64 == 0 and k % 8 == 0";
@@ -571,17 +570,13 @@ bool build_pixel_linear(const float* const* mats, int nmat, int rows, int k, Con
     L.stride = 1;
     L.pad = 0;
     L.J = k / 8;
-    std::vector<float> pk((size_t)(cout / 32) * L.J * 64 * 4);
-    size_t o = 0;
-    for (int nt = 0; nt < cout / 32; ++nt)
-        for (int j = 0; j < L.J; ++j)
-            for (int l = 0; l < 64; ++l) {
-                const int n = 32 * nt + (l & 31), kk = 8 * j + 4 * (l >> 5);
-                const float* row = mats[n / rows] + (size_t)(n % rows) * k + kk;
-                for (int r = 0; r < 4; ++r) pk[o++] = row[r];
-            }
+    if (hipMalloc((void**)&L.w, (size_t)cout * k * sizeof(float)) != hipSuccess) {
+        *err = "device allocation of the pixel-linear weights failed";
+        return false;
+    }
+    allocs->push_back(L.w);
     const std::vector<float> one((size_t)cout, 1.0f), zero((size_t)cout, 0.0f);
-    return upload(pk, &L.w, *allocs, err) && upload(one, &L.scale, *allocs, err) && upload(zero, &L.shift, *allocs, err);
+    return upload(one, &L.scale, *allocs, err) && upload(zero, &L.shift, *allocs, err);
 }
 
 bool EncoderWeights::build(const Getter& get, const std::string& pre, std::string* err) {

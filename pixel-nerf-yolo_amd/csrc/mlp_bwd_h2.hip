@@ -1,7 +1,7 @@
 // The backward dX chain on the f16 matrix cores with split fp32 operands (gfx950): pny_mlp_bwd_kernel (mlp_bwd.hip) with the
 // matrix products of mlp_h2.hip.  What is differentiated, which tensors go to the dY stash and in which layout is unchanged
 // (reference src/model/resnetfc.py:53-62,134-186, src/model/models.py:312-317; mlp_bwd.hip header); what changes:
-//   * dX^T[k][m] = W^T[k][n] dY^T[n][m] with the TRANSPOSED weights as split-f16 images (api.hip pack_mlp, PACK_H2T) streaming
+//   * dX^T[k][m] = W^T[k][n] dY^T[n][m] with the TRANSPOSED weights as split-f16 images (pack.hip PACK_H2T) streaming
 //     through the 2-step register ring of mlp_h2_core.h, and dY^T as two f16 planes in the LDS activation buffer
 //     ([n / 8][plane][sample] x 16 bytes): x1 w1 + x2 w1 + x1 w2 on v_mfma_f32_32x32x16_f16, fp32 accumulation.
 //   * Gradients have no fixed magnitude and f16 has 40 binades: every tile works in a SCALED domain.  sigma = the power of two

@@ -110,7 +110,7 @@ __device__ __forceinline__ void mfma_iter(f32x16 (&acc)[NT][MT], const f32x4 (&a
 // fragments in flight and runs ACROSS layer boundaries: while a GEMM drains, the ring already fills
 // with the head of the next layer's slice (WSeg next), so neither the epilogue/barrier phase nor the
 // head of a GEMM waits on memory.
-// Packed layout (api.hip pack_layer): k-iteration-major, [j][n-tile 0..15][lane] float4.
+// Packed layout (pack.hip PACK_A): k-iteration-major, [j][n-tile 0..15][lane] float4.
 // The packed weights of both MLPs are ONE allocation, addressed through a raw buffer resource: a fragment
 // load is buffer_load_dwordx4 with the resource in SGPRs, a loop-invariant lane offset (16*lane) in one
 // VGPR and the fragment's byte offset in an SGPR -- the per-iteration address arithmetic is SALU only.
@@ -375,7 +375,7 @@ __device__ __forceinline__ void slab_load(f32x16 (&t)[NT][MT], const float* slab
 
 // One pre-activation residual block (reference resnetfc.py:53-62):
 //   net = fc_0(relu(h)); h = h + fc_1(relu(net))
-// b_fc1 already contains the next block's lin_z bias (folded on the host, api.hip).
+// b_fc1 already contains the next block's lin_z bias (folded when the weights are packed, pack.hip PACK_ADD2).
 // `after` is the weight segment that follows this block in the stream.  With slab != nullptr the
 // other views' running sum is fetched into the (then dead) net registers underneath the fc_1
 // GEMM and added to h afterwards.  ADDZ: the LDS buffer holds this block's interpolated lin_z output

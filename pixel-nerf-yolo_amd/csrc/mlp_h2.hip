@@ -384,11 +384,11 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
     auto fc0seg = [&](int b) { return h2seg(ws, a.h2_fc0[b], HID / 16, wave); };
     auto fc1seg = [&](int b) { return h2seg(ws, a.h2_fc1[b], HID / 16, wave); };
 #endif
-    // bias applied at the entry of block b (b = n_blocks: before lin_out): b_in, or the previous block's b_fc1 -- the host
-    // (api.hip pack_mlp) has folded the block's lin_z bias into either
+    // bias applied at the entry of block b (b = n_blocks: before lin_out): b_in, or the previous block's b_fc1 -- the
+    // packing (pack.hip PACK_ADD2) has folded the block's lin_z bias into either
     auto entry_bias = [&](int b) -> const float* {
         if constexpr (LDS_BIAS) return bias_tab + (b == 0 ? 0 : 2 * b) * HID;
-        return b == 0 ? a.w.b_in : a.w.b_fc1[b - 1];   // (folded with the block's lin_z bias by api.hip pack_mlp)
+        return b == 0 ? a.w.b_in : a.w.b_fc1[b - 1];   // (folded with the block's lin_z bias, pack.hip PACK_ADD2)
     };
     auto fc0_bias = [&](int b) -> const float* {
         if constexpr (LDS_BIAS) return bias_tab + (1 + 2 * b) * HID;

@@ -1,8 +1,25 @@
-// Device-side rebuild of the packed weight operands from the live parameter tensors (pny_model_refresh): after an
-// optimizer step the MFMA A-operand images of every layer (forward order, transposed order for the backward chain, the
-// n-tile-major order of the latent projection), the folded biases and the plain copies are regenerated by ONE launch
-// that reads the parameters where PyTorch keeps them -- no state_dict round trip through the host (27 MB of repacking and
-// a synchronous upload per step before).  Layouts: api.hip pack_layer / encoder.hip build_pixel_linear.
+// The packed weight operands of the fused MLP and of the latent projection, and the ONE kernel that builds them from the
+// state_dict tensors: pny_model_finalize runs it on uploaded copies, pny_model_refresh (after an optimizer step) on the
+// live parameter tensors where PyTorch keeps them -- no state_dict round trip through the host (27 MB of repacking and a
+// synchronous upload per step before).  This file is the description of the formats; api.hip only lays the images out
+// and lists the jobs (pack_mlp), encoder.hip build_pixel_linear allocates the projection weights.  A job writes `count`
+// 16-byte elements, element i as below; W is the (n_out x k_in) row-major tensor, K padded with zeros to k_pad.
+//
+// PACK_A   A-operand order of v_mfma_f32_32x32x2_f32 for H^T = W X^T (mlp.hip): k-iteration j (8 inputs), n-tile nt (32
+//          output features), lane l, component r:  dst[((j*16 + nt)*64 + l)*4 + r] = W[32 nt + (l & 31)][8 j + 4 (l >> 5) + r].
+//          k-iteration-major: the 16 KiB that ALL waves of a workgroup need for iteration j are contiguous, so the 16
+//          per-wave streams of a CU walk the same pages together (measured +1 % over n-tile-major, where each stream strides
+//          through its own 64 KiB region).
+// PACK_AT  the same with W^T as the matrix, for the backward chain (dX^T = W^T dY^T, mlp_bwd.hip): W^T is (k_in x n_out),
+//          its rows (the GEMM's outputs) are 512 and its K (= n_out) is padded to k_pad.
+// PACK_NT  the same elements n-tile-major, [n-tile][k-iteration][lane]: the projection weights (encoder.hip, one job per
+//          stacked lin_z block) -- the order of the trunk's convolution weights.
+// PACK_NTT W^T n-tile-major as one block of a wider image: the stacked lin_z^T of the latent gradient (latent_grad.hip).
+// PACK_H2  split-f16 image for mlp_h2.hip: w = w1 + w2, w1 = f16(w), w2 = f16(w - w1) (round to nearest); per 16-k step j
+//          [n-tile][plane][lane] x 8 halves, lane l holding W[32 nt + (l & 31)][16 j + 8 (l >> 5) + 0..7].  4 bytes per weight.
+// PACK_H2T the same of W^T (mlp_bwd_h2.hip).
+// PACK_H1  plane 0 of a PACK_H2 / PACK_H2T image, 2 bytes per weight (mlp_h1.hip, mlp_bwd_h1.hip).
+// PACK_COPY / PACK_ADD2  the tensor as stored / the sum of two (a lin_z bias folded into the bias before it); count floats.
 #include "pny_common.h"
 
 namespace pny {
@@ -16,7 +33,7 @@ __global__ __launch_bounds__(256) void repack_kernel(const PackJob* __restrict__
             jb.dst[i] = jb.src[i];
         } else if (jb.kind == PACK_ADD2) {
             jb.dst[i] = jb.src[i] + jb.src2[i];
-        } else if (jb.kind == PACK_NTT) {  // transposed block of the stacked lin_z^T (api.hip pack_mlp): dst already points at the
+        } else if (jb.kind == PACK_NTT) {  // transposed block of the stacked lin_z^T: dst already points at the
             const int l = (int)(i & 63);   // block's first k-iteration; n_out = d_latent, k_in = 512, k_pad = total K
             const int jl = (int)((i >> 6) % (jb.k_in / 8)), nt = (int)((i >> 6) / (jb.k_in / 8));
             const int c = 32 * nt + (l & 31), f = 8 * jl + 4 * (l >> 5);
@@ -24,7 +41,7 @@ __global__ __launch_bounds__(256) void repack_kernel(const PackJob* __restrict__
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = jb.src[(size_t)(f + r) * jb.n_out + c];
             reinterpret_cast<float4*>(jb.dst)[((size_t)nt * (jb.k_pad / 8) + jl) * 64 + l] = make_float4(v[0], v[1], v[2], v[3]);
-        } else if (jb.kind == PACK_H2 || jb.kind == PACK_H2T) {   // [16-k step][n-tile 0..15][plane][lane] x 8 halves (api.hip pack_layer_h2)
+        } else if (jb.kind == PACK_H2 || jb.kind == PACK_H2T) {   // [16-k step][n-tile 0..15][plane][lane] x 8 halves
             const int l = (int)(i & 63), p = (int)((i >> 6) & 1), nt = (int)((i >> 7) & 15), j = (int)(i >> 11);
             const int row = 32 * nt + (l & 31), col = 16 * j + 8 * (l >> 5);
             typedef _Float16 h8 __attribute__((ext_vector_type(8)));

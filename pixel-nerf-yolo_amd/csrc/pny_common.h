@@ -23,7 +23,7 @@ struct Cam {
 };
 
 // Device pointers of one packed ResnetFC (reference resnetfc.py:66-132).  512-wide layers are
-// stored in MFMA A-operand order (see pack_layer in api.hip); lin_out stays row-major.
+// stored in MFMA A-operand order (pack.hip PACK_A); lin_out stays row-major.
 struct MlpWeights {
     const float* w_in;
     const float* b_in;
@@ -90,7 +90,7 @@ struct MlpArgs {
     // training: activation stash written by the STASH instantiation (launch_mlp_stash); null otherwise
     float* stash_x;
     StashLayout lay;
-    // split-f16 operand images of lin_in / fc_0 / fc_1 (mlp_h2.hip; api.hip pack_layer_h2), inside the same blob as `w`
+    // split-f16 operand images of lin_in / fc_0 / fc_1 (mlp_h2.hip; pack.hip PACK_H2), inside the same blob as `w`
     const float* h2_in;
     const float* h2_fc0[MAX_BLOCKS];
     const float* h2_fc1[MAX_BLOCKS];
@@ -101,7 +101,7 @@ struct MlpArgs {
     Cam cams[MAX_VIEWS];
 };
 
-// ---- device-side weight repack (pack.hip): the packed operand layouts rebuilt from the live parameter tensors
+// ---- weight packing (pack.hip): the packed operand layouts, built from the state_dict tensors on the device
 enum { PACK_A = 0, PACK_AT = 1, PACK_NT = 2, PACK_COPY = 3, PACK_ADD2 = 4, PACK_H2 = 5, PACK_NTT = 6, PACK_H2T = 7, PACK_H1 = 9 };
 struct PackJob {
     const float* src;

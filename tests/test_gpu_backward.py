@@ -376,8 +376,9 @@ def test_training_gradients_reference_golden(golden):
 
 def test_device_refresh_equals_full_reupload():
     """After in-place parameter updates (optimizer.step()) the packed weights are rebuilt on the device from the live
-    tensors (pny_model_refresh); the result must equal a full host re-pack (pny_model_finalize) bit for bit: forward
-    outputs of both MLPs (projected and reference order) and a backward pass."""
+    tensors (pny_model_refresh); the result must equal a full re-upload (pny_model_finalize: the same device packer on
+    uploaded copies of the state_dict tensors) bit for bit: forward outputs of both MLPs (projected and reference order) and
+    a backward pass."""
     ns, H, W = 2, 32, 32
     net, _ = scene_pair(ns, H, W, 512, 4, 5, 3, 1300)
     rs = np.random.RandomState(8)

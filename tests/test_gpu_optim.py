@@ -285,7 +285,7 @@ def mlp_params(net):
 
 
 def fresh_copy(setup_fn, seed, net, precision):
-    """A second, freshly built net that receives `net`'s parameter values through load_state_dict: the host pack and
+    """A second, freshly built net that receives `net`'s parameter values through load_state_dict: the upload and
     finalize path."""
     other = setup_fn(seed)
     if precision != "auto":
