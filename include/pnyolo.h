@@ -147,6 +147,48 @@ int pny_gen_rays_range(const float* poses_host, int b, int width, int height, co
                        const float c[2], float z_near, float z_far, int yolo_mode, int64_t first_ray,
                        int64_t n_rays, float* out_dev, pny_stream stream);
 
+/* The ray batch of one training step and its ground truth, for all SB objects in ONE launch: what
+ * PixelNerfTrainer.calc_losses prepares per object (train/trainlib/PixelNerfTrainer.py:76-123: util.gen_rays of every
+ * pixel of every view, an NHWC copy of images * 0.5 + 0.5, CPU pixel indices from torch.randint :112 or util.bbox_sample
+ * src/util/util.py:222-237, two gathers), computed for the n_rays pixels per object it keeps.  Model-free, like
+ * pny_gen_rays, whose ray arithmetic it shares: a sampled ray has the bits of that pixel's row of pny_gen_rays. */
+typedef struct pny_train_batch_desc {
+    int32_t n_objs;      /* SB */
+    int32_t n_views;     /* NV views per object */
+    int32_t height;
+    int32_t width;
+    int32_t n_rays;      /* B = ray_batch_size, per object */
+    float z_near;
+    float z_far;
+    int32_t focal_rows;  /* focal_dev is (focal_rows, focal_cols): rows 1 (all objects) or SB (per object), */
+    int32_t focal_cols;  /* cols 1 (fx = fy) or 2 (fx, fy) */
+    int32_t c_rows;      /* c_dev is (c_rows, 2): 1 or SB; ignored when c_dev is NULL */
+    uint64_t seed;       /* seeded mode (draws == NULL): Philox key */
+    uint64_t draw_offset; /* seeded mode: ray r of object s uses draw index draw_offset + s * B + r, so object s of a call
+                          * equals object 0 of a one-object call with draw_offset = s * B */
+} pny_train_batch_desc;
+/* Replay mode: the caller's draws, (SB, B) each, on the device.  Uniform mode reads pix_inds_dev (flat index into
+ * (NV, H, W)); bbox mode reads image_ids_dev and u_x_dev, u_y_dev in [0, 1).  The ones the mode reads must be non-NULL.
+ * Values outside their range are clamped to it (memory safety; the call cannot look at them without waiting). */
+typedef struct pny_train_batch_draws {
+    const int64_t* pix_inds_dev;
+    const int64_t* image_ids_dev;
+    const float* u_x_dev;
+    const float* u_y_dev;
+} pny_train_batch_draws;
+/* images_dev (SB, NV, 3, H, W) in [-1, 1]; poses_dev (SB, NV, 4, 4) cam->world; focal_dev, c_dev as the descriptor says
+ * (c_dev NULL: (W / 2, H / 2)); bboxes_dev (SB, NV, 4) `cmin rmin cmax rmax`, NULL = uniform over all pixels of all views.
+ * bbox mode: view ~ U{0..NV-1}, x = trunc(u_x * (cmax + 1 - cmin) + cmin), y likewise from rows, in fp32 without fused
+ * multiply-add, then clamped into the image (never reached by a box inside it).  draws NULL = seeded: integers are
+ * (uint64) w * n >> 32 of one 32-bit Philox word (bias <= n / 2^32; NV * H * W < 2^32 is required), u_x / u_y 24-bit
+ * uniforms, on four streams of their own.  Writes rays_dev (SB, B, 8) 16-byte aligned, rgb_gt_dev (SB, B, 3) =
+ * images * 0.5 + 0.5 and, unless NULL, pix_dev (SB, B, 3) int32 [view, y, x].  All device pointers; one kernel enqueued on
+ * `stream`, no allocation, no copy, no synchronisation.  PNY_ERR_ARG on a bad shape or a NULL required pointer. */
+int pny_sample_train_batch(const pny_train_batch_desc* desc, const float* images_dev, const float* poses_dev,
+                           const float* focal_dev, const float* c_dev, const float* bboxes_dev,
+                           const pny_train_batch_draws* draws, float* rays_dev, float* rgb_gt_dev, int32_t* pix_dev,
+                           pny_stream stream);
+
 /* PixelNeRFNet.forward for one scene (src/model/models.py:153-318):
  * xyz_dev, viewdirs_dev (n,3) world space -> out_dev (n,d_out) = [sigmoid rgb, relu sigma]
  * (YOLO mode: raw).  coarse=0 selects mlp_fine when the model has one. */

@@ -806,6 +806,42 @@ int pny_gen_rays(const float* poses_host, int b, int width, int height, const fl
                               (int64_t)b * width * height, out_dev, stream);
 }
 
+int pny_sample_train_batch(const pny_train_batch_desc* d, const float* images_dev, const float* poses_dev,
+                           const float* focal_dev, const float* c_dev, const float* bboxes_dev,
+                           const pny_train_batch_draws* draws, float* rays_dev, float* rgb_gt_dev, int32_t* pix_dev,
+                           pny_stream stream) {
+    const char* who = "pny_sample_train_batch: ";
+    if (!d || !images_dev || !poses_dev || !focal_dev || !rays_dev || !rgb_gt_dev)
+        return fail(PNY_ERR_ARG, std::string(who) + "null argument");
+    if (d->n_objs < 1 || d->n_views < 1 || d->height < 1 || d->width < 1 || d->n_rays < 1)
+        return fail(PNY_ERR_ARG, std::string(who) + "bad shape");
+    if ((int64_t)d->n_objs * d->n_rays > INT32_MAX) return fail(PNY_ERR_ARG, std::string(who) + "more than 2^31 - 1 rays");
+    // (also what keeps a seeded flat index inside one 32-bit Philox word's reach)
+    if ((int64_t)d->n_views * d->height * d->width > (int64_t)UINT32_MAX)
+        return fail(PNY_ERR_ARG, std::string(who) + "NV * H * W must be below 2^32");
+    if ((d->focal_rows != 1 && d->focal_rows != d->n_objs) || (d->focal_cols != 1 && d->focal_cols != 2))
+        return fail(PNY_ERR_ARG, std::string(who) + "focal must be (1 | SB, 1 | 2)");
+    if (c_dev && d->c_rows != 1 && d->c_rows != d->n_objs) return fail(PNY_ERR_ARG, std::string(who) + "c must be (1 | SB, 2)");
+    if (draws && (bboxes_dev ? (!draws->image_ids_dev || !draws->u_x_dev || !draws->u_y_dev) : !draws->pix_inds_dev))
+        return fail(PNY_ERR_ARG, std::string(who) + (bboxes_dev ? "bbox mode replays image_ids_dev, u_x_dev and u_y_dev"
+                                                                : "uniform mode replays pix_inds_dev"));
+    if (reinterpret_cast<uintptr_t>(rays_dev) & 15) return fail(PNY_ERR_ARG, std::string(who) + "rays_dev must be 16-byte aligned");
+    TrainBatchArgs a;
+    a.sb = d->n_objs, a.nv = d->n_views, a.h = d->height, a.w = d->width, a.b = d->n_rays;
+    a.znear = d->z_near, a.zfar = d->z_far;
+    a.focal_rows = d->focal_rows, a.focal_cols = d->focal_cols, a.c_rows = c_dev ? d->c_rows : 1;
+    a.seed = d->seed, a.draw_offset = draws ? 0 : d->draw_offset;
+    a.images = images_dev, a.poses = poses_dev, a.focal = focal_dev, a.c = c_dev, a.bboxes = bboxes_dev;
+    a.pix_inds = draws && !bboxes_dev ? draws->pix_inds_dev : nullptr;
+    a.image_ids = draws && bboxes_dev ? draws->image_ids_dev : nullptr;
+    a.u_x = draws && bboxes_dev ? draws->u_x_dev : nullptr;
+    a.u_y = draws && bboxes_dev ? draws->u_y_dev : nullptr;
+    a.rays = rays_dev, a.rgb = rgb_gt_dev, a.pix = pix_dev;
+    launch_train_batch(a, (hipStream_t)stream);
+    PNY_HIP(hipGetLastError());
+    return PNY_OK;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------- MLP launch

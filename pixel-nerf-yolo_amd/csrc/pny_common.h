@@ -267,6 +267,19 @@ void launch_sample_fine(const float* rays, const float* zc, const float* w, cons
 void launch_yolo_aggregate(const float* raw, long long n, int k, int na, float* out, hipStream_t st);
 void launch_gen_rays(const float* cam16_host, int b, int w, int h, float znear, float zfar, int yolo, float* out,
                      hipStream_t st, long long first, long long count);
+// train_batch_kernel's argument block (render_kernels.hip); every pointer is a device pointer
+struct TrainBatchArgs {
+    int sb, nv, h, w, b;
+    float znear, zfar;
+    int focal_rows, focal_cols, c_rows;       // focal (focal_rows, focal_cols), c (c_rows, 2): one row = broadcast
+    uint64_t seed, draw_offset;
+    const float *images, *poses, *focal, *c, *bboxes;   // c null: image centre; bboxes null: uniform mode
+    const int64_t *pix_inds, *image_ids;      // replayed draws (null: Philox draws from seed)
+    const float *u_x, *u_y;
+    float *rays, *rgb;
+    int32_t* pix;                             // may be null
+};
+void launch_train_batch(const TrainBatchArgs& a, hipStream_t st);
 void launch_nchw_to_nhwc(const float* in, float* out, int n, int c, int hw, hipStream_t st);
 void launch_nhwc_to_nchw(const float* in, float* out, int n, int c, int hw, hipStream_t st);
 

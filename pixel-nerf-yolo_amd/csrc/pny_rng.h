@@ -52,7 +52,17 @@ __device__ __forceinline__ float normal_at(uint64_t seed, uint32_t stream, uint6
     const float u2 = u01(r[2 * (idx & 1) + 1]);
     return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
 }
-enum { STREAM_COARSE = 1, STREAM_FINE = 2, STREAM_FINE2 = 3, STREAM_DEPTH = 4 };
-
+// An integer in [0, n) at position idx of a stream, from ONE 32-bit word w (four per counter, laid out like uniform_at) as
+// (uint64) w * n >> 32.  Valid for 1 <= n < 2^32; value v is hit by floor or ceil of 2^32 / n words, so the bias against a
+// uniform draw is at most n / 2^32 (2e-4 at the 819 200 pixels of 50 views of 128 x 128).  Not derived from the 24-bit u01,
+// which cannot reach every value once n exceeds 2^24.
+__device__ __forceinline__ uint32_t index_at(uint64_t seed, uint32_t stream, uint64_t idx, uint32_t n) {
+    uint32_t r[4];
+    Philox(seed).draw(idx >> 2, stream, r);
+    return (uint32_t)(((uint64_t)r[idx & 3] * n) >> 32);
+}
+// 1-4: the renderer's depth draws.  5-8: the training batch's pixel draws (pny_train_batch.h), draw index s * B + r.
+enum { STREAM_COARSE = 1, STREAM_FINE = 2, STREAM_FINE2 = 3, STREAM_DEPTH = 4,
+       STREAM_BATCH_PIX = 5, STREAM_BATCH_VIEW = 6, STREAM_BATCH_X = 7, STREAM_BATCH_Y = 8 };
 
 }  // namespace pny

@@ -3,6 +3,7 @@
 // that a render call never leaves the device and never launches an ATen op.
 #include "pny_common.h"
 #include "pny_rng.h"
+#include "pny_train_batch.h"
 
 namespace pny {
 
@@ -300,6 +301,25 @@ struct GenRaysCams {              // no device staging buffer, no copy, nothing 
     float cam[GEN_RAYS_IMGS][16];
 };
 
+// The ray of pixel (x, y) through a pinhole camera c (cam16, yolo=0): the unit direction in camera space, and the row
+// [origin, R d, near, far] written as two 16-byte words.  One copy of the arithmetic for gen_rays_kernel and
+// train_batch_kernel, so a sampled training ray carries the bits of the same pixel of a full gen_rays call.
+__device__ __forceinline__ void pinhole_dir(const float* c, int x, int y, float& d0, float& d1, float& d2) {
+    d0 = ((float)x - c[14]) / c[12];
+    d1 = -(((float)y - c[15]) / c[13]);
+    d2 = -1.0f;
+    const float nrm = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
+    d0 /= nrm;
+    d1 /= nrm;
+    d2 /= nrm;
+}
+__device__ __forceinline__ void store_ray(const float* c, float d0, float d1, float d2, float znear, float zfar,
+                                          float* row) {
+    float4* o = reinterpret_cast<float4*>(row);  // hipMalloc / torch allocations: rows are 32-byte aligned
+    o[0] = make_float4(c[9], c[10], c[11], c[0] * d0 + c[1] * d1 + c[2] * d2);
+    o[1] = make_float4(c[3] * d0 + c[4] * d1 + c[5] * d2, c[6] * d0 + c[7] * d1 + c[8] * d2, znear, zfar);
+}
+
 // Pixels [first, first + count) of the flattened (img, y, x) index space of images [img0, img0 + GEN_RAYS_IMGS).
 __global__ void gen_rays_kernel(const GenRaysCams cams, int img0, int w, int h, float znear, float zfar, int yolo,
                                 long long first, long long count, float* __restrict__ out) {
@@ -313,22 +333,14 @@ __global__ void gen_rays_kernel(const GenRaysCams cams, int img0, int w, int h, 
     const float* c = cams.cam[img - img0];
     float d0, d1, d2;
     if (!yolo) {
-        d0 = ((float)x - c[14]) / c[12];
-        d1 = -(((float)y - c[15]) / c[13]);
-        d2 = -1.0f;
-        const float nrm = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
-        d0 /= nrm;
-        d1 /= nrm;
-        d2 /= nrm;
+        pinhole_dir(c, x, y, d0, d1, d2);
     } else {
         const float px = (float)x + 0.49f, py = (float)y + 0.49f;
         d0 = c[12] * px + c[14];
         d1 = c[13] * py + c[15];
         d2 = 1.0f;
     }
-    float4* o = reinterpret_cast<float4*>(out + i * 8);  // hipMalloc / torch allocations: rows are 32-byte aligned
-    o[0] = make_float4(c[9], c[10], c[11], c[0] * d0 + c[1] * d1 + c[2] * d2);
-    o[1] = make_float4(c[3] * d0 + c[4] * d1 + c[5] * d2, c[6] * d0 + c[7] * d1 + c[8] * d2, znear, zfar);
+    store_ray(c, d0, d1, d2, znear, zfar, out + i * 8);
 }
 
 // cam16_host: b x 16 floats (host).  Rays [first, first + count) of the (b, h, w) pixel grid -> out (count, 8).
@@ -348,6 +360,68 @@ void launch_gen_rays(const float* cam16_host, int b, int w, int h, float znear, 
         hipLaunchKernelGGL(gen_rays_kernel, dim3((unsigned)((hi - lo + 255) / 256)), dim3(256), 0, st, cams, img0, w, h,
                            znear, zfar, yolo, lo, hi - lo, out + (lo - first) * 8);
     }
+}
+
+// ------------------------------------------------------------------ training batch
+// What PixelNerfTrainer.calc_losses:76-123 of the reference prepares per object -- all rays of all views, an NHWC copy of
+// the images, CPU pixel indices, two gathers -- for the B pixels per object it keeps: one thread per (object s, ray r) picks
+// its pixel (pny_train_batch.h), computes that pixel's ray from poses[s, view] (cam->world) and reads its colour.
+// Cameras and boxes come from device memory (SB * NV of them do not fit a kernel-argument segment).  focal (focal_rows,
+// focal_cols) and c (c_rows, 2; null = image centre) are broadcast (one row) or per object; fx, fy, cx, cy enter the ray as
+// pny_gen_rays passes them.  Replayed draws (pix_inds | image_ids, u_x, u_y) when given, else Philox draws at index
+// draw_offset + s * B + r.
+__global__ __launch_bounds__(256) void train_batch_kernel(const TrainBatchArgs a) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)a.sb * a.b) return;
+    const int s = (int)(i / a.b);
+    const uint64_t di = a.draw_offset + (uint64_t)i;
+    BatchPixel p;
+    if (!a.bboxes) {
+        const int64_t flat = a.pix_inds ? a.pix_inds[i] : seeded_flat(a.seed, di, (uint32_t)((int64_t)a.nv * a.h * a.w));
+        p = pixel_from_flat(flat, a.nv, a.h, a.w);
+    } else {
+        const int view = a.image_ids ? clamp_view(a.image_ids[i], a.nv) : seeded_view(a.seed, di, a.nv);
+        const float ux = a.u_x ? a.u_x[i] : seeded_u_x(a.seed, di);
+        const float uy = a.u_y ? a.u_y[i] : seeded_u_y(a.seed, di);
+        p = pixel_from_bbox(view, ux, uy, a.bboxes + ((size_t)s * a.nv + view) * 4, a.h, a.w);
+    }
+    const float* P = a.poses + ((size_t)s * a.nv + p.view) * 16;
+    float c[16];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) c[3 * r + q] = P[4 * r + q];
+        c[9 + r] = P[4 * r + 3];
+    }
+    const float* f = a.focal + (size_t)(a.focal_rows > 1 ? s : 0) * a.focal_cols;
+    c[12] = f[0];
+    c[13] = f[a.focal_cols - 1];
+    if (a.c) {
+        const float* cc = a.c + (size_t)(a.c_rows > 1 ? s : 0) * 2;
+        c[14] = cc[0];
+        c[15] = cc[1];
+    } else {
+        c[14] = (float)a.w * 0.5f;
+        c[15] = (float)a.h * 0.5f;
+    }
+    float d0, d1, d2;
+    pinhole_dir(c, p.x, p.y, d0, d1, d2);
+    store_ray(c, d0, d1, d2, a.znear, a.zfar, a.rays + i * 8);
+    const size_t plane = (size_t)a.h * a.w;
+    const float* img = a.images + ((size_t)s * a.nv + p.view) * 3 * plane + (size_t)p.y * a.w + p.x;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) a.rgb[i * 3 + ch] = img[ch * plane] * 0.5f + 0.5f;
+    if (a.pix) {
+        a.pix[i * 3 + 0] = p.view;
+        a.pix[i * 3 + 1] = p.y;
+        a.pix[i * 3 + 2] = p.x;
+    }
+}
+
+void launch_train_batch(const TrainBatchArgs& a, hipStream_t st) {
+    const long long n = (long long)a.sb * a.b;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(train_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
 }
 
 // ------------------------------------------------------------------ layout repack

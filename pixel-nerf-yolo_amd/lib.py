@@ -56,6 +56,16 @@ class AdamHyper(C.Structure):
                 ("weight_decay", C.c_double), ("step", C.c_int64)]
 
 
+class TrainBatchDesc(C.Structure):
+    _fields_ = [("n_objs", C.c_int32), ("n_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("n_rays", C.c_int32), ("z_near", C.c_float), ("z_far", C.c_float), ("focal_rows", C.c_int32),
+                ("focal_cols", C.c_int32), ("c_rows", C.c_int32), ("seed", C.c_uint64), ("draw_offset", C.c_uint64)]
+
+
+class TrainBatchDraws(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("pix_inds_dev", "image_ids_dev", "u_x_dev", "u_y_dev")]
+
+
 # name -> (restype, argtypes); every symbol include/pnyolo.h declares
 SIGNATURES = {
     "pny_version": (C.c_int, []),
@@ -81,6 +91,8 @@ SIGNATURES = {
                                C.c_int, C.c_void_p, C.c_void_p]),
     "pny_gen_rays_range": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, C.c_float, C.c_float,
                                      C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "pny_sample_train_batch": (C.c_int, [C.POINTER(TrainBatchDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(TrainBatchDraws), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pny_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "pny_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(RenderOpts), C.POINTER(RenderOut),
                              C.c_void_p]),

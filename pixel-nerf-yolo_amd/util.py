@@ -2,6 +2,8 @@
 Ray generation and the YOLO detection tail with the reference's signatures (src/util/util.py:240-278 ``gen_rays``,
 :808-876 ``gen_rays_yolo``), executed by libpnyolo's gen_rays kernel.  Output lives on a CUDA
 device (that of ``poses``, or the current one when ``poses`` is a CPU tensor as at the reference's call sites).
+``sample_train_batch`` is the trainer's ray batch and ground truth in one launch (no counterpart function in the reference:
+it replaces the per-object loop of train/trainlib/PixelNerfTrainer.py:76-123).
 """
 import ctypes as C
 
@@ -82,6 +84,78 @@ def gen_rays_yolo(poses, width, height, focal, c, z_near, z_far, device=None):
     check(_lib.load().pny_gen_rays(ptr(p), B, int(width), int(height), _pair(focal, "focal"), _pair(c, "c"),
                                    float(z_near), float(z_far), 1, ptr(out), stream_of(dev)))
     return out
+
+
+# ------------------------------------------------------------------ training batch
+def _dev_f32(t, dev):
+    """fp32, contiguous, on dev: in place when it already is, else an asynchronous copy (no wait on the host)."""
+    return torch.as_tensor(t).detach().to(dev, torch.float32, non_blocking=True).contiguous()
+
+
+def _dev_i64(t, dev):
+    return torch.as_tensor(t).detach().to(dev, torch.int64, non_blocking=True).contiguous()
+
+
+def sample_train_batch(images, poses, focal, z_near, z_far, ray_batch_size, c=None, bboxes=None, seed=None, draws=None,
+                       draw_offset=0):
+    """
+    The rays of one training step and their ground truth for all SB objects, in one kernel launch: what the reference's
+    PixelNerfTrainer.calc_losses:76-123 prepares per object (gen_rays of every view, an NHWC copy of the images, CPU pixel
+    indices, two gathers) for the ray_batch_size pixels per object it keeps.  Nothing of size NV * H * W is written and the
+    host waits for nothing: GPU inputs are used in place, CPU ``poses`` / ``focal`` / ``c`` / ``bboxes`` are copied over
+    asynchronously.
+
+    :param images (SB, NV, 3, H, W) in [-1, 1];  poses (SB, NV, 4, 4) camera-to-world
+    :param focal scalar, (SB,) one per object, (1, 2) or (SB, 2);  c None (image centre), (2,), (1, 2) or (SB, 2)
+    :param bboxes None: uniform over all pixels of all views (PixelNerfTrainer.py:112); (SB, NV, 4) `cmin rmin cmax rmax`:
+           util.bbox_sample (src/util/util.py:222-237)
+    :param seed 64-bit Philox seed of the draws; None takes one per call from torch's default (CPU) generator, so
+           torch.manual_seed governs a run.  Ray r of object s uses draw index draw_offset + s * ray_batch_size + r.
+    :param draws replay instead: {"pix_inds": (SB, B) int64} (uniform) or {"image_ids": (SB, B) int64, "u_x", "u_y":
+           (SB, B) float32} (bbox) -- the values torch.randint / torch.rand gave the reference
+    :return rays (SB, B, 8), rgb_gt (SB, B, 3) = images * 0.5 + 0.5 at the pixels, pix (SB, B, 3) int32 [view, y, x]
+    """
+    dev = _device_of(images, None)
+    SB, NV, ch, H, W = images.shape
+    assert ch == 3 and tuple(poses.shape) == (SB, NV, 4, 4), "images (SB, NV, 3, H, W), poses (SB, NV, 4, 4)"
+    B = int(ray_batch_size)
+    img, p = _dev_f32(images, dev), _dev_f32(poses, dev)
+    f = _dev_f32(focal, dev)
+    if f.dim() <= 1:
+        assert f.numel() in (1, SB), "focal: a scalar, (SB,), (1, 2) or (SB, 2)"
+        f = f.reshape(-1, 1)
+    assert f.dim() == 2 and f.shape[0] in (1, SB) and f.shape[1] in (1, 2), "focal: a scalar, (SB,), (1, 2) or (SB, 2)"
+    cc = None
+    if c is not None:
+        cc = _dev_f32(c, dev).reshape(-1, 2)
+        assert cc.shape[0] in (1, SB), "c: (2,), (1, 2) or (SB, 2)"
+    bb = None
+    if bboxes is not None:
+        bb = _dev_f32(bboxes, dev)
+        assert tuple(bb.shape) == (SB, NV, 4), "bboxes (SB, NV, 4)"
+    desc = _lib.TrainBatchDesc(n_objs=SB, n_views=NV, height=H, width=W, n_rays=B, z_near=float(z_near), z_far=float(z_far),
+                               focal_rows=f.shape[0], focal_cols=f.shape[1], c_rows=1 if cc is None else cc.shape[0],
+                               seed=0, draw_offset=int(draw_offset))
+    dr, keep = None, []
+    if draws is not None:
+        assert seed is None, "draws replay the pixel choice: a seed has no effect"
+        names = ("image_ids", "u_x", "u_y") if bb is not None else ("pix_inds",)
+        assert set(draws) == set(names), "draws must hold exactly %s" % (names,)
+        keep = [(_dev_f32 if n.startswith("u_") else _dev_i64)(draws[n], dev) for n in names]
+        assert all(tuple(t.shape) == (SB, B) for t in keep), "draws are (SB, ray_batch_size)"
+        dr = _lib.TrainBatchDraws(**{n + "_dev": t.data_ptr() for n, t in zip(names, keep)})
+    elif seed is None:
+        hi, lo = torch.randint(0, 2 ** 32, (2,), dtype=torch.int64).tolist()   # the CPU generator: nothing to wait for
+        desc.seed = (hi << 32) | lo
+    else:
+        desc.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    rays = torch.empty(SB, B, 8, device=dev, dtype=torch.float32)
+    rgb_gt = torch.empty(SB, B, 3, device=dev, dtype=torch.float32)
+    pix = torch.empty(SB, B, 3, device=dev, dtype=torch.int32)
+    check(_lib.load().pny_sample_train_batch(C.byref(desc), ptr(img), ptr(p), ptr(f), ptr(cc), ptr(bb),
+                                             None if dr is None else C.byref(dr), ptr(rays), ptr(rgb_gt),
+                                             C.c_void_p(pix.data_ptr()), stream_of(dev)))
+    return rays, rgb_gt, pix
 
 
 # ------------------------------------------------------------------ YOLO detection tail
