@@ -540,6 +540,54 @@ int pny_optim_add_tensor(pny_optim* o, float* param_dev, float* exp_avg_dev, flo
 int pny_optim_adam_step(pny_optim* o, const pny_adam_hyper* h, float* const* grads_dev, int first, int n, pny_model* model,
                         pny_stream stream);
 
+/* ---- training losses: the terms and, on request, the gradient w.r.t. the predictions in ONE launch each (csrc/loss.hip).
+ * Model-free, raw device pointers, enqueued on `stream`; nothing waits for the device and the terms stay on the device.  Sums
+ * are accumulated in fp64 in a fixed order without float atomics: the same inputs give the same bits on every run.  The
+ * first call on a stream allocates that stream's reduction workspace (a few KB, kept); not for graph capture.
+ * PNY_ERR_ARG on a NULL required pointer or a non-positive size.
+ *
+ * pny_rgb_loss: the rgb terms of PixelNerfTrainer.calc_losses (train/trainlib/PixelNerfTrainer.py:147-154) with the
+ * criteria of model/loss.py:92-104 (MSELoss or L1Loss, reduction "mean"), over n contiguous fp32 elements each:
+ *   rc = lambda_coarse * mean(e(coarse, gt));  rf = lambda_fine * mean(e(fine, gt));  t = rc + rf
+ *   e(x, g) = (x - g)^2, or |x - g| where the pass's use_l1 is set.  fine_dev NULL = no fine pass: rf = 0, t = rc.
+ * terms_dev[3] = {rc, rf, t}.  d_coarse_dev / d_fine_dev (n each, or NULL) receive dt/dcoarse and dt/dfine:
+ * lambda * 2 (x - g) / n, or lambda * sign(x - g) / n with sign(0) = 0. */
+typedef struct pny_rgb_loss_desc {
+    int32_t use_l1_coarse; /* conf loss.rgb.use_l1 */
+    int32_t use_l1_fine;   /* conf loss.rgb_fine.use_l1 */
+    float lambda_coarse;   /* conf loss.lambda_coarse */
+    float lambda_fine;     /* conf loss.lambda_fine */
+} pny_rgb_loss_desc;
+int pny_rgb_loss(const pny_rgb_loss_desc* desc, const float* coarse_dev, const float* fine_dev, const float* gt_dev, int64_t n,
+                 float* terms_dev, float* d_coarse_dev, float* d_fine_dev, pny_stream stream);
+
+/* pny_yolo_loss: YoloLoss.forward (src/model/loss.py:121-163, util.iou src/util/util.py:582-608).
+ * pred_dev (cells, A, 5 + C) rows [p_obj, x, y, w, h, C class logits]; target_dev (cells, A, 6) rows [obj, x, y, w, h, class];
+ * anchors_dev (A, 2) (w, h), on the device.  Per (cell, anchor):
+ *   obj == 0: no-object term -max(log(1 - p_obj), -100) (BCELoss's clamp);
+ *   obj == 1: object term (p_obj - iou * obj)^2 with iou of [sigmoid(x), sigmoid(y), exp(w) aw, exp(h) ah] and target[1:5],
+ *             a constant for the gradient; box term (sigmoid(x) - tx)^2, (sigmoid(y) - ty)^2, (w - log(1e-6 + tw / aw))^2,
+ *             (h - log(1e-6 + th / ah))^2; class term logsumexp(logits) - logits[class];
+ *   any other obj (the dataset's -1 for ignored anchors): nothing.
+ * Means: no-object over n_noobj, object and class over n_obj, box over 4 n_obj.  n_obj == 0: the three object terms are
+ * exactly 0 (the reference returns a CPU torch.tensor(0) there).  n_noobj == 0: the no-object term and the total are NaN, as
+ * ATen's mean over nothing.  A class outside [0, C) reads nothing out of bounds and makes the class term, the total and that
+ * cell's logit gradients NaN (ATen raises a device assert there).  Unlike loss.py:145,147, pred and target are not modified.
+ * terms_dev[5] = {total, box, object, no_object, class}, total = the weighted sum, the others unweighted as the reference
+ * returns them.  counts_dev[2] (or NULL) = {n_obj, n_noobj}.  d_pred_dev (cells, A, 5 + C) (or NULL) = dtotal/dpred as
+ * autograd gives it for the reference (BCE backward p / max(p (1 - p), 1e-12) / n_noobj); every element is written, zeros where no
+ * gradient arrives.  cells * A must be below 2^31. */
+typedef struct pny_yolo_loss_desc {
+    int32_t num_anchors;   /* A = num_anchors_per_scale */
+    int32_t num_classes;   /* C = pred's last dimension - 5 */
+    float box_loss;        /* conf yolo.weights.* (loss.py:165-179) */
+    float object_loss;
+    float no_object_loss;
+    float class_loss;
+} pny_yolo_loss_desc;
+int pny_yolo_loss(const pny_yolo_loss_desc* desc, const float* pred_dev, const float* target_dev, const float* anchors_dev,
+                  int64_t cells, float* terms_dev, int32_t* counts_dev, float* d_pred_dev, pny_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,84 @@
+// C entry points of the training losses (include/pnyolo.h, "training losses" section; kernels in loss.hip): argument checks,
+// the per-stream reduction workspace, one launch.
+#include <map>
+#include <mutex>
+#include <string>
+#include <utility>
+
+#include "api_internal.h"
+#include "pny_loss.h"
+
+using namespace pny;
+
+namespace {
+
+// The ticket counter and the partial-sum table of a launch, one per (device, stream): launches on one stream follow one
+// another, so they can share it; launches on different streams may overlap and get their own.  Allocated on the first call on
+// a stream and zeroed ON that stream (no host wait); never freed (a few KB per stream the process ever used).
+std::mutex g_ws_mutex;
+std::map<std::pair<int, hipStream_t>, void*> g_ws;
+
+int loss_workspace(hipStream_t st, unsigned** ticket, double** partials) {
+    int dev = 0;
+    PNY_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_ws_mutex);
+    void*& p = g_ws[std::make_pair(dev, st)];
+    if (!p) {
+        void* q = nullptr;
+        PNY_HIP(hipMalloc(&q, LOSS_WS_BYTES));
+        hipError_t e = hipMemsetAsync(q, 0, LOSS_WS_BYTES, st);
+        if (e != hipSuccess) {
+            (void)hipFree(q);
+            return hip_fail(e, "hipMemsetAsync(loss workspace)");
+        }
+        p = q;
+    }
+    *ticket = reinterpret_cast<unsigned*>(p);
+    *partials = reinterpret_cast<double*>(reinterpret_cast<char*>(p) + 256);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pny_rgb_loss(const pny_rgb_loss_desc* desc, const float* coarse_dev, const float* fine_dev, const float* gt_dev, int64_t n,
+                 float* terms_dev, float* d_coarse_dev, float* d_fine_dev, pny_stream stream) {
+    const char* who = "pny_rgb_loss: ";
+    if (!desc || !coarse_dev || !gt_dev || !terms_dev) return fail(PNY_ERR_ARG, std::string(who) + "null argument");
+    if (n <= 0) return fail(PNY_ERR_ARG, std::string(who) + "n must be positive");
+    if (d_fine_dev && !fine_dev) return fail(PNY_ERR_ARG, std::string(who) + "d_fine_dev without fine_dev");
+    RgbLossArgs a;
+    a.coarse = coarse_dev, a.fine = fine_dev, a.gt = gt_dev, a.n = n;
+    a.l1_coarse = desc->use_l1_coarse != 0, a.l1_fine = desc->use_l1_fine != 0;
+    a.lambda_coarse = desc->lambda_coarse, a.lambda_fine = desc->lambda_fine;
+    a.terms = terms_dev, a.d_coarse = d_coarse_dev, a.d_fine = d_fine_dev;
+    int rc;
+    if ((rc = loss_workspace((hipStream_t)stream, &a.ticket, &a.partials))) return rc;
+    launch_rgb_loss(a, (hipStream_t)stream);
+    PNY_HIP(hipGetLastError());
+    return PNY_OK;
+}
+
+int pny_yolo_loss(const pny_yolo_loss_desc* desc, const float* pred_dev, const float* target_dev, const float* anchors_dev,
+                  int64_t cells, float* terms_dev, int32_t* counts_dev, float* d_pred_dev, pny_stream stream) {
+    const char* who = "pny_yolo_loss: ";
+    if (!desc || !pred_dev || !target_dev || !anchors_dev || !terms_dev) return fail(PNY_ERR_ARG, std::string(who) + "null argument");
+    if (cells <= 0) return fail(PNY_ERR_ARG, std::string(who) + "cells must be positive");
+    if (desc->num_anchors < 1) return fail(PNY_ERR_ARG, std::string(who) + "num_anchors must be at least 1");
+    if (desc->num_classes < 1) return fail(PNY_ERR_ARG, std::string(who) + "num_classes must be at least 1");
+    if (cells > (int64_t)INT32_MAX / desc->num_anchors)   // (the counts are int32)
+        return fail(PNY_ERR_ARG, std::string(who) + "more than 2^31 - 1 (cell, anchor) pairs");
+    YoloLossArgs a;
+    a.pred = pred_dev, a.target = target_dev, a.anchors = anchors_dev;
+    a.items = cells * desc->num_anchors, a.A = desc->num_anchors, a.C = desc->num_classes;
+    a.w_box = desc->box_loss, a.w_obj = desc->object_loss, a.w_noobj = desc->no_object_loss, a.w_cls = desc->class_loss;
+    a.terms = terms_dev, a.counts = counts_dev, a.d_pred = d_pred_dev;
+    int rc;
+    if ((rc = loss_workspace((hipStream_t)stream, &a.ticket, &a.partials))) return rc;
+    launch_yolo_loss(a, (hipStream_t)stream);
+    PNY_HIP(hipGetLastError());
+    return PNY_OK;
+}
+
+}  // extern "C"

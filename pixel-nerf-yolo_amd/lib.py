@@ -66,6 +66,15 @@ class TrainBatchDraws(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("pix_inds_dev", "image_ids_dev", "u_x_dev", "u_y_dev")]
 
 
+class RgbLossDesc(C.Structure):
+    _fields_ = [("use_l1_coarse", C.c_int32), ("use_l1_fine", C.c_int32), ("lambda_coarse", C.c_float), ("lambda_fine", C.c_float)]
+
+
+class YoloLossDesc(C.Structure):
+    _fields_ = [("num_anchors", C.c_int32), ("num_classes", C.c_int32), ("box_loss", C.c_float), ("object_loss", C.c_float),
+                ("no_object_loss", C.c_float), ("class_loss", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/pnyolo.h declares
 SIGNATURES = {
     "pny_version": (C.c_int, []),
@@ -146,6 +155,10 @@ SIGNATURES = {
     "pny_optim_add_tensor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "pny_optim_adam_step": (C.c_int, [C.c_void_p, C.POINTER(AdamHyper), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p,
                                       C.c_void_p]),
+    "pny_rgb_loss": (C.c_int, [C.POINTER(RgbLossDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p]),
+    "pny_yolo_loss": (C.c_int, [C.POINTER(YoloLossDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
