@@ -34,12 +34,17 @@ using namespace pny;
 // call arrives on a DIFFERENT stream than the previous call on the same scene, the new stream is made to wait for
 // everything the previous call enqueued (one event record + one stream wait, paid only on a stream switch).
 namespace pny {
+// the scene's order event, created on first use
+static int order_event(pny_scene* s, const char* what) {
+    if (!s->order_ev && hipEventCreateWithFlags(&s->order_ev, hipEventDisableTiming) != hipSuccess) {
+        s->order_ev = nullptr;
+        return hip_fail(hipGetLastError(), what);
+    }
+    return 0;
+}
 int enter_stream(pny_scene* s, hipStream_t st) {
     if (s->has_last_stream && s->last_stream != st) {
-        if (!s->order_ev && hipEventCreateWithFlags(&s->order_ev, hipEventDisableTiming) != hipSuccess) {
-            s->order_ev = nullptr;
-            return hip_fail(hipGetLastError(), "hipEventCreate(stream order)");
-        }
+        if (int rc = order_event(s, "hipEventCreate(stream order)")) return rc;
         if (s->order_ev_valid) {   // recorded right behind the previous call's work (mark_stream_point)
             PNY_HIP(hipStreamWaitEvent(st, s->order_ev, 0));
         } else if (hipEventRecord(s->order_ev, s->last_stream) == hipSuccess) {
@@ -57,10 +62,7 @@ int enter_stream(pny_scene* s, hipStream_t st) {
 // for exactly this point and not for whatever else the first stream has been given in between (pny_scenes_encode: the scenes
 // of a super-batch are encoded on one stream and rendered on one stream each).
 int mark_stream_point(pny_scene* s, hipStream_t st) {
-    if (!s->order_ev && hipEventCreateWithFlags(&s->order_ev, hipEventDisableTiming) != hipSuccess) {
-        s->order_ev = nullptr;
-        return hip_fail(hipGetLastError(), "hipEventCreate(stream order)");
-    }
+    if (int rc = order_event(s, "hipEventCreate(stream order)")) return rc;
     PNY_HIP(hipEventRecord(s->order_ev, st));
     s->order_ev_valid = true;
     return 0;
@@ -109,8 +111,7 @@ struct PackPlan {
 // each pointer of `w` / `wt` will point.  No bytes are produced here.
 static int pack_mlp(pny_model* m, const std::string& pre, MlpWeights& w, MlpWeightsT& wt, PackPlan& plan) {
     const pny_model_desc& d = m->desc;
-    const int d_in = 3 + 6 * d.num_freqs + 3;
-    const int nvb = d.combine_layer < d.n_blocks ? d.combine_layer : d.n_blocks;
+    const int d_in = pny::d_in(d), nvb = view_blocks(d);
     const HostTensor* t = nullptr;
     int rc;
     // one image of tensor `name` (`shape`: (n_out, k_in) of a matrix kind); PACK_COPY / PACK_ADD2 keep the tensor's own order
@@ -160,10 +161,10 @@ static int pack_mlp(pny_model* m, const std::string& pre, MlpWeights& w, MlpWeig
     if ((rc = add(PACK_COPY, pre + "lin_out.weight", "", {d.d_out, HID}, 0, &w.w_out))) return rc;
     if ((rc = add(PACK_COPY, pre + "lin_out.bias", "", {d.d_out}, 0, &w.b_out))) return rc;
     // split-f16 images for the f16x2 kernel (mlp_h2.hip)
-    if ((rc = add(PACK_H2, pre + "lin_in.weight", "", {HID, d_in}, D_IN_PAD, &wt.h2_in))) return rc;
+    if ((rc = add(PACK_H2, pre + "lin_in.weight", "", {HID, d_in}, D_IN_PAD, &wt.h2.in))) return rc;
     for (int b = 0; b < d.n_blocks; ++b) {
-        if ((rc = add(PACK_H2, block(b) + ".fc_0.weight", "", {HID, HID}, HID, &wt.h2_fc0[b]))) return rc;
-        if ((rc = add(PACK_H2, block(b) + ".fc_1.weight", "", {HID, HID}, HID, &wt.h2_fc1[b]))) return rc;
+        if ((rc = add(PACK_H2, block(b) + ".fc_0.weight", "", {HID, HID}, HID, &wt.h2.fc0[b]))) return rc;
+        if ((rc = add(PACK_H2, block(b) + ".fc_1.weight", "", {HID, HID}, HID, &wt.h2.fc1[b]))) return rc;
     }
     // stacked transposed lin_z for the latent gradient (latent_grad.hip): W_cat[c][b * 512 + f] = lin_z[b].weight[f][c], one
     // n-tile-major image of K = nvb * 512 in which block b owns k-iterations [64 b, 64 b + 64) of every n-tile
@@ -187,10 +188,10 @@ static int pack_mlp(pny_model* m, const std::string& pre, MlpWeights& w, MlpWeig
         if ((rc = add(PACK_AT, block(b) + ".fc_0.weight", "", {HID, HID}, HID, &wt.wT_fc0[b]))) return rc;
         if ((rc = add(PACK_AT, block(b) + ".fc_1.weight", "", {HID, HID}, HID, &wt.wT_fc1[b]))) return rc;
     }
-    if ((rc = add(PACK_H2T, pre + "lin_out.weight", "", {d.d_out, HID}, D_IN_PAD, &wt.h2T_out))) return rc;
+    if ((rc = add(PACK_H2T, pre + "lin_out.weight", "", {d.d_out, HID}, D_IN_PAD, &wt.h2.T_out))) return rc;
     for (int b = 0; b < d.n_blocks; ++b) {
-        if ((rc = add(PACK_H2T, block(b) + ".fc_0.weight", "", {HID, HID}, HID, &wt.h2T_fc0[b]))) return rc;
-        if ((rc = add(PACK_H2T, block(b) + ".fc_1.weight", "", {HID, HID}, HID, &wt.h2T_fc1[b]))) return rc;
+        if ((rc = add(PACK_H2T, block(b) + ".fc_0.weight", "", {HID, HID}, HID, &wt.h2.T_fc0[b]))) return rc;
+        if ((rc = add(PACK_H2T, block(b) + ".fc_1.weight", "", {HID, HID}, HID, &wt.h2.T_fc1[b]))) return rc;
     }
     return 0;
 }
@@ -283,31 +284,27 @@ static int build_h1_images(pny_model* m) {
     };
     m->h1_max_elems = 0;
     for (int f = 0; f < nmlp; ++f) {
-        const MlpWeightsT& wt = f ? m->fine_t : m->coarse_t;
-        add(wt.h2_in, D_IN_PAD, &m->h1_in[f]);
+        const F16Images& h2 = f16_images(m, f != 0, false);
+        F16Images& h1 = m->h1[f];
+        h1 = F16Images{};
+        h1.base = m->h1_packed.f();
+        h1.bytes = m->h1_packed.bytes;
+        add(h2.in, D_IN_PAD, &h1.in);
         for (int b = 0; b < nb; ++b) {
-            add(wt.h2_fc0[b], HID, &m->h1_fc0[f][b]);
-            add(wt.h2_fc1[b], HID, &m->h1_fc1[f][b]);
+            add(h2.fc0[b], HID, &h1.fc0[b]);
+            add(h2.fc1[b], HID, &h1.fc1[b]);
         }
     }
     for (int f = 0; f < nmlp && m->want_h1t; ++f) {   // the chain's W^T images: the same [16-k step][n-tile][plane][lane] layout, 512 rows
-        const MlpWeightsT& wt = f ? m->fine_t : m->coarse_t;
-        add(wt.h2T_out, D_IN_PAD, &m->h1T_out[f]);
+        const F16Images& h2 = f16_images(m, f != 0, false);
+        F16Images& h1 = m->h1[f];
+        add(h2.T_out, D_IN_PAD, &h1.T_out);
         for (int b = 0; b < nb; ++b) {
-            add(wt.h2T_fc0[b], HID, &m->h1T_fc0[f][b]);
-            add(wt.h2T_fc1[b], HID, &m->h1T_fc1[f][b]);
+            add(h2.T_fc0[b], HID, &h1.T_fc0[b]);
+            add(h2.T_fc1[b], HID, &h1.T_fc1[b]);
         }
     }
-    if (nmlp == 1) {
-        m->h1_in[1] = m->h1_in[0];
-        m->h1T_out[1] = m->h1T_out[0];
-        for (int b = 0; b < nb; ++b) {
-            m->h1_fc0[1][b] = m->h1_fc0[0][b];
-            m->h1_fc1[1][b] = m->h1_fc1[0][b];
-            m->h1T_fc0[1][b] = m->h1T_fc0[0][b];
-            m->h1T_fc1[1][b] = m->h1T_fc1[0][b];
-        }
-    }
+    if (nmlp == 1) m->h1[1] = m->h1[0];
     if ((rc = m->h1_jobs.reserve(jobs.size() * sizeof(PackJob)))) return rc;
     // once per model (and finalize): wait for every stream that may still rewrite the split images or read older images
     PNY_HIP(hipDeviceSynchronize());
@@ -342,7 +339,7 @@ int pny_model_create(pny_model** out, const pny_model_desc* desc) {
     if (desc->combine_layer < 0) return fail(PNY_ERR_ARG, "pny_model_create: combine_layer < 0");
     if (desc->d_latent < 128 || desc->d_latent % 128) return fail(PNY_ERR_ARG, "pny_model_create: d_latent must be a positive multiple of 128");
     if (desc->d_out < 1 || desc->d_out > 64) return fail(PNY_ERR_ARG, "pny_model_create: d_out out of range [1,64]");
-    if (3 + 6 * desc->num_freqs + 3 > D_IN_PAD || desc->num_freqs < 0) return fail(PNY_ERR_ARG, "pny_model_create: num_freqs too large (d_in must be <= 64)");
+    if (d_in(*desc) > D_IN_PAD || desc->num_freqs < 0) return fail(PNY_ERR_ARG, "pny_model_create: num_freqs too large (d_in must be <= 64)");
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
         return fail(PNY_ERR_NOGPU, "pny_model_create: no HIP device visible (this library has no CPU path)");
@@ -421,6 +418,10 @@ int pny_model_finalize(pny_model* m) {
     if ((rc = m->packed.reserve(plan.floats * sizeof(float)))) return rc;
     PNY_HIP(hipMemset(m->packed.p, 0, plan.floats * sizeof(float)));   // the alignment gaps between the images stay zero
     for (auto& f : plan.fix) *f.first = m->packed.f() + f.second;
+    for (MlpWeightsT* wt : {&m->coarse_t, &m->fine_t}) {
+        wt->h2.base = m->packed.f();
+        wt->h2.bytes = m->packed.bytes;
+    }
     if (!m->desc.has_fine) {
         m->fine = m->coarse;
         m->fine_t = m->coarse_t;
@@ -431,7 +432,7 @@ int pny_model_finalize(pny_model* m) {
     m->zproj_allocs.clear();
     m->has_zproj = false;
     {
-        const int nvb = m->desc.combine_layer < m->desc.n_blocks ? m->desc.combine_layer : m->desc.n_blocks;
+        const int nvb = view_blocks(m->desc);
         if (nvb > 0) {
             for (int f = 0; f < (m->desc.has_fine ? 2 : 1); ++f) {
                 const std::string pre = f ? "mlp_fine." : "mlp_coarse.";
@@ -501,10 +502,7 @@ int pny_model_refresh(pny_model* m, pny_stream stream) {
     // order this stream behind the last call of every scene that may still read the packed weights on another stream
     for (pny_scene* s : m->scenes) {
         if (s->has_last_stream && s->last_stream != st) {
-            if (!s->order_ev && hipEventCreateWithFlags(&s->order_ev, hipEventDisableTiming) != hipSuccess) {
-                s->order_ev = nullptr;
-                return hip_fail(hipGetLastError(), "hipEventCreate(refresh order)");
-            }
+            if ((rc = order_event(s, "hipEventCreate(refresh order)"))) return rc;
             if (hipEventRecord(s->order_ev, s->last_stream) == hipSuccess)
                 PNY_HIP(hipStreamWaitEvent(st, s->order_ev, 0));
             else
@@ -617,6 +615,28 @@ int pny_scene_set_groups(pny_scene* s, int n_objs) {
     return PNY_OK;
 }
 
+// a new latent is in place: its shape, and the projected maps are stale
+static void set_latent_shape(pny_scene* s, int ns, int L, int hl, int wl) {
+    s->ns = ns;
+    s->L = L;
+    s->hl = hl;
+    s->wl = wl;
+    s->have_latent = true;
+    s->zp_valid[0] = s->zp_valid[1] = false;
+}
+
+// what pny_scene_encode and pny_scenes_encode ask of the model and the images; selects the device, returns the latent's size
+static int encode_check(const std::string& who, const pny_model* m, int ns, int height, int width, int* hl, int* wl) {
+    if (!m->finalized) return fail(PNY_ERR_STATE, who + ": call pny_model_finalize first");
+    if (!m->has_encoder) return fail(PNY_ERR_STATE, who + ": no encoder.model.* weights were loaded");
+    if (m->desc.d_latent != 512) return fail(PNY_ERR_ARG, who + ": ResNet-34 trunk yields 512 channels; model d_latent differs");
+    if (ns < 1 || ns > MAX_VIEWS || height < 32 || width < 32) return fail(PNY_ERR_ARG, who + ": bad shape");
+    PNY_HIP(hipSetDevice(m->desc.device));
+    encoder_latent_size(height, width, hl, wl);
+    if ((long long)*hl * *wl * 512 >= (1ll << 31)) return fail(PNY_ERR_ARG, who + ": latent too large for 32-bit tap offsets");
+    return 0;
+}
+
 int pny_scene_set_latent(pny_scene* s, const float* latent_dev, int ns, int channels, int hl, int wl, pny_stream stream) {
     if (!s || !latent_dev) return fail(PNY_ERR_ARG, "pny_scene_set_latent: null argument");
     if (channels != s->m->desc.d_latent) return fail(PNY_ERR_ARG, "pny_scene_set_latent: channel count != model d_latent");
@@ -628,26 +648,14 @@ int pny_scene_set_latent(pny_scene* s, const float* latent_dev, int ns, int chan
     if ((rc = s->latent.reserve((size_t)ns * channels * hl * wl * sizeof(float)))) return rc;
     launch_nchw_to_nhwc(latent_dev, s->latent.f(), ns, channels, hl * wl, (hipStream_t)stream);
     PNY_HIP(hipGetLastError());
-    s->ns = ns;
-    s->L = channels;
-    s->hl = hl;
-    s->wl = wl;
-    s->have_latent = true;
-    s->zp_valid[0] = s->zp_valid[1] = false;
+    set_latent_shape(s, ns, channels, hl, wl);
     return PNY_OK;
 }
 
 int pny_scene_encode(pny_scene* s, const float* images_dev, int ns, int height, int width, pny_stream stream) {
     if (!s || !images_dev) return fail(PNY_ERR_ARG, "pny_scene_encode: null argument");
-    if (!s->m->finalized) return fail(PNY_ERR_STATE, "pny_scene_encode: call pny_model_finalize first");
-    if (!s->m->has_encoder) return fail(PNY_ERR_STATE, "pny_scene_encode: no encoder.model.* weights were loaded");
-    if (s->m->desc.d_latent != 512) return fail(PNY_ERR_ARG, "pny_scene_encode: ResNet-34 trunk yields 512 channels; model d_latent differs");
-    if (ns < 1 || ns > MAX_VIEWS || height < 32 || width < 32) return fail(PNY_ERR_ARG, "pny_scene_encode: bad shape");
-    PNY_HIP(hipSetDevice(s->m->desc.device));
-    int hl = 0, wl = 0;
-    encoder_latent_size(height, width, &hl, &wl);
-    if ((long long)hl * wl * 512 >= (1ll << 31)) return fail(PNY_ERR_ARG, "pny_scene_encode: latent too large for 32-bit tap offsets");
-    int rc;
+    int hl = 0, wl = 0, rc;
+    if ((rc = encode_check("pny_scene_encode", s->m, ns, height, width, &hl, &wl))) return rc;
     if ((rc = enter_stream(s, (hipStream_t)stream))) return rc;
     if ((rc = s->latent.reserve((size_t)ns * 512 * hl * wl * sizeof(float)))) return rc;
     const bool pool = s->m->desc.enc_use_first_pool != 0;
@@ -655,12 +663,7 @@ int pny_scene_encode(pny_scene* s, const float* images_dev, int ns, int height, 
     std::string err;
     if (!encoder_forward(s->m->enc, images_dev, ns, height, width, pool, s->enc_work.f(), s->latent.f(), (hipStream_t)stream, &err))
         return fail(PNY_ERR_HIP, "pny_scene_encode: " + err);
-    s->ns = ns;
-    s->L = 512;
-    s->hl = hl;
-    s->wl = wl;
-    s->have_latent = true;
-    s->zp_valid[0] = s->zp_valid[1] = false;
+    set_latent_shape(s, ns, 512, hl, wl);
     return PNY_OK;
 }
 
@@ -670,16 +673,9 @@ int pny_scenes_encode(pny_scene** scenes, int n_scenes, const float* images_dev,
         if (!scenes[i] || scenes[i]->m != scenes[0]->m) return fail(PNY_ERR_ARG, "pny_scenes_encode: scenes must share one model");
     if (n_scenes == 1) return pny_scene_encode(scenes[0], images_dev, ns, height, width, stream);
     pny_model* m = scenes[0]->m;
-    if (!m->finalized) return fail(PNY_ERR_STATE, "pny_scenes_encode: call pny_model_finalize first");
-    if (!m->has_encoder) return fail(PNY_ERR_STATE, "pny_scenes_encode: no encoder.model.* weights were loaded");
-    if (m->desc.d_latent != 512) return fail(PNY_ERR_ARG, "pny_scenes_encode: ResNet-34 trunk yields 512 channels; model d_latent differs");
-    if (ns < 1 || ns > MAX_VIEWS || height < 32 || width < 32) return fail(PNY_ERR_ARG, "pny_scenes_encode: bad shape");
-    PNY_HIP(hipSetDevice(m->desc.device));
-    int hl = 0, wl = 0;
-    encoder_latent_size(height, width, &hl, &wl);
-    if ((long long)hl * wl * 512 >= (1ll << 31)) return fail(PNY_ERR_ARG, "pny_scenes_encode: latent too large for 32-bit tap offsets");
+    int hl = 0, wl = 0, rc;
+    if ((rc = encode_check("pny_scenes_encode", m, ns, height, width, &hl, &wl))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    int rc;
     const size_t lat_bytes = (size_t)ns * 512 * hl * wl * sizeof(float);
     for (int i = 0; i < n_scenes; ++i) {
         if ((rc = enter_stream(scenes[i], st))) return rc;
@@ -698,12 +694,7 @@ int pny_scenes_encode(pny_scene** scenes, int n_scenes, const float* images_dev,
         pny_scene* s = scenes[i];
         PNY_HIP(hipMemcpyAsync(s->latent.p, reinterpret_cast<const char*>(m->enc_batch_lat.p) + lat_bytes * (size_t)i, lat_bytes,
                                hipMemcpyDeviceToDevice, st));
-        s->ns = ns;
-        s->L = 512;
-        s->hl = hl;
-        s->wl = wl;
-        s->have_latent = true;
-        s->zp_valid[0] = s->zp_valid[1] = false;
+        set_latent_shape(s, ns, 512, hl, wl);
     }
     for (int i = 0; i < n_scenes; ++i)
         if ((rc = mark_stream_point(scenes[i], st))) return rc;
@@ -876,34 +867,100 @@ int check_ready(pny_scene* s, const char* who) {
 int view_blocks(const pny_model_desc& d) { return d.combine_layer < d.n_blocks ? d.combine_layer : d.n_blocks; }
 }  // namespace pny
 
-// GEMM FLOPs (2 per MAC, unpadded) per query point: as the reference computes it (with_lin_z) or as the
-// projected-latent variant executes it (lin_z moved to the per-scene projection).
-static double mlp_flops_per_point(const pny_model_desc& d, int ns, bool with_lin_z) {
-    const int d_in = 3 + 6 * d.num_freqs + 3;
+namespace pny {
+double mlp_flops_per_point(const pny_model_desc& d, int ns, MlpPass pass) {
     const int nvb = view_blocks(d);
-    const double per_view = (double)d_in * HID + (with_lin_z ? (double)nvb * d.d_latent * HID : 0.0) + 2.0 * nvb * HID * HID;
+    const double per_view = (pass == PASS_CHAIN ? 0.0 : (double)d_in(d) * HID) +
+                            (pass == PASS_FORWARD ? (double)nvb * d.d_latent * HID : 0.0) + 2.0 * nvb * HID * HID;
     const double post = 2.0 * (d.n_blocks - nvb) * HID * HID + (double)HID * d.d_out;
     return 2.0 * (ns * per_view + post);
 }
+}  // namespace pny
+
+// ---------------------------------------------------------------------------------- routing
+// Which kernel an MLP launch runs and on which latent, decided here and nowhere else (run_mlp launches what it says,
+// ensure_projection projects when and how it says).  The rules are those of include/pnyolo.h pny_scene_set_precision /
+// pny_scene_set_projection:
+//   * f16 kernels read the projected latent only, exist for the shapes mlp_h2_supports accepts, and are never taken by a scene
+//     pinned to F32.  Weights beyond the f16 range (f16_weights_ok false) keep every scene but one pinned to F16X2 off them.
+//   * Single-plane f16 wherever the split kernel would run: no-grad launches of F16 and F16_TRAIN scenes, stashing (training)
+//     forwards of F16_TRAIN scenes only -- an F16 scene trains as AUTO, on the split kernel.
+//   * A plain launch is projected when the scene's mode says so; AUTO projects every launch of a scene whose launches can run
+//     f16 (f16_default below), else launches of at least 2 x hl x wl points.  A stashing forward ignores the mode: it forces
+//     the projection when it can run f16 (which there also needs L % 128 == 0), and otherwise runs fp32 on the raw latent.
+//   * f16_default differs from "can run f16" in one case, on purpose: an F16X2 scene of a model whose weights left the f16 range
+//     runs the split kernel where it is projected, but AUTO projection keeps the 2 x hl x wl threshold and the projection
+//     itself stays on the fp32 matrix path.
+//   * Split f16 on 32-sample tiles (mlp_h2s.hip: 4-wave workgroups, two per CU, the same arithmetic per sample bit for bit)
+//     only for no-grad split-f16 launches of at most 32 x CUs points.  Measured (profiles/r02zk_split_sweep.log): a launch
+//     that gives every CU at most ONE 32-sample tile takes 0.40-0.43 ms against 0.47-0.51 ms on 64-sample tiles; as soon as
+//     two workgroups share a CU the doubled weight stream per sample costs more than the overlap of their phases returns (full
+//     C2 frame: 61.7 vs 39.9 ms per launch).  PNYOLO_H2_SPLIT=0|1 overrides.
+//   * PNYOLO_GRID (diagnostic: fewer resident workgroups) caps plain launches only.  Both variables are read at every call.
+enum MlpKernel { K_F32_8x64 = MLP_8x64, K_F32_16x64 = MLP_16x64, K_F32_8x32 = MLP_8x32, K_H2, K_H2S, K_H1 };
+struct MlpRoute {
+    MlpKernel kernel;
+    Prec prec;        // its arithmetic
+    bool stash;       // STASH instantiation: writes the backward's operands into the model-level reservation
+    bool projected;   // reads the projected latent maps
+    int tile;         // samples per workgroup tile
+    int grid_cap;     // resident workgroups
+};
+
+static bool f16_default(const pny_scene* s) {
+    const pny_model* m = s->m;
+    return s->precision != PNY_PRECISION_F32 && m->f16_weights_ok && mlp_h2_supports(m->desc.n_blocks, m->desc.combine_layer);
+}
+
+// whether a launch of n_points reads projected maps (force: whatever the scene's mode says)
+static bool wants_projection(const pny_scene* s, long long n_points, bool force) {
+    if (!s->m->has_zproj) return false;
+    if ((long long)s->hl * s->wl * view_blocks(s->m->desc) * HID >= (1ll << 31)) return false;   // 32-bit tap offsets: stay direct
+    if (force) return true;
+    if (s->zp_mode == PNY_PROJECTION_OFF) return false;
+    return s->zp_mode != PNY_PROJECTION_AUTO || f16_default(s) || n_points >= 2ll * s->hl * s->wl;
+}
+
+// stash: a stashing forward was asked for AND the reservation has room for it (otherwise the plain forward runs)
+static MlpRoute route_mlp(const pny_scene* s, long long n_points, bool stash) {
+    const pny_model_desc& d = s->m->desc;
+    const int prec = s->precision;
+    const bool can_f16 = prec != PNY_PRECISION_F32 && (s->m->f16_weights_ok || prec == PNY_PRECISION_F16X2) &&
+                         mlp_h2_supports(d.n_blocks, d.combine_layer) && (!stash || s->L % 128 == 0);
+    MlpRoute r;
+    r.stash = stash;
+    r.projected = stash ? can_f16 && wants_projection(s, n_points, true) : wants_projection(s, n_points, false);
+    const bool f16 = r.projected && can_f16;
+    const bool h1 = f16 && (prec == PNY_PRECISION_F16_TRAIN || (prec == PNY_PRECISION_F16 && !stash));
+    bool h2s = f16 && !h1 && !stash && n_points <= 32ll * mlp_max_grid(MLP_8x64);
+    if (f16 && !h1 && !stash)
+        if (const char* e = getenv("PNYOLO_H2_SPLIT")) h2s = atoi(e) != 0;
+    const int shape = (f16 || stash) ? MLP_8x64 : mlp_pick_variant(n_points);   // (the STASH instantiations are 8x64)
+    r.kernel = h1 ? K_H1 : h2s ? K_H2S : f16 ? K_H2 : MlpKernel(shape);
+    r.prec = h1 ? PREC_H1 : f16 ? PREC_H2 : PREC_F32;
+    r.tile = h2s ? 32 : mlp_tile_samples(shape);
+    r.grid_cap = h2s ? 2 * mlp_max_grid(MLP_8x64) : mlp_max_grid(shape);
+    if (!stash)
+        if (const char* e = getenv("PNYOLO_GRID")) {
+            const int g = atoi(e);
+            if (g > 0 && g < r.grid_cap) r.grid_cap = g;
+        }
+    return r;
+}
 
 // Projected latent: zp[v][y][x][b*512 + n] = sum_k lin_z[b].weight[n][k] * latent[v][y][x][k], computed
-// once per (scene latent, weights) on the caller's stream and cached.  AUTO uses it when the launch has
-// at least twice as many points as the latent has pixels per view (the projection costs one lin_z per
-// PIXEL instead of one per (sample, view); tiny training-size batches on large maps stay direct).
+// once per (scene latent, weights) on the caller's stream and cached.  AUTO (wants_projection): with the f16x2 kernel
+// available every launch is projected -- a lone 64-sample tile on it (0.5 ms) beats the 32-sample fp32 shape on the
+// unprojected latent (1.0 ms) even with the one-off projection of the scene (0.3 ms per MLP at C2), and a ray's result then
+// never depends on the size of the batch it is rendered in.  Without it (F32 scenes, more than 6 blocks): when the launch
+// has at least twice as many points as the latent has pixels per view (the projection costs one lin_z per PIXEL instead of
+// one per (sample, view); tiny training-size batches on large maps stay direct).
 namespace pny {
 int ensure_projection(pny_scene* s, int which, long long n_points, hipStream_t st, const float** zp, bool force) {
     *zp = nullptr;
     const pny_model* m = s->m;
-    if (!m->has_zproj) return 0;
-    if (!force && s->zp_mode == PNY_PROJECTION_OFF) return 0;
-    // AUTO: with the f16x2 kernel available every launch is projected -- a lone 64-sample tile on it (0.5 ms) beats the
-    // 32-sample fp32 shape on the unprojected latent (1.0 ms) even with the one-off projection of the scene (0.3 ms per MLP
-    // at C2), and a ray's result then never depends on the size of the batch it is rendered in.  Without it (F32 scenes,
-    // more than 6 blocks): project when the launch has at least 2x as many points as the latent has pixels per view.
-    const bool h2_ok = s->precision != PNY_PRECISION_F32 && m->f16_weights_ok && mlp_h2_supports(m->desc.n_blocks, m->desc.combine_layer);
-    if (!force && s->zp_mode == PNY_PROJECTION_AUTO && !h2_ok && n_points < 2ll * s->hl * s->wl) return 0;
+    if (!wants_projection(s, n_points, force)) return 0;
     const int nvb = view_blocks(m->desc);
-    if ((long long)s->hl * s->wl * nvb * HID >= (1ll << 31)) return 0;  // 32-bit tap offsets: stay direct
     if (s->zp_generation != m->generation) {
         s->zp_valid[0] = s->zp_valid[1] = false;
         s->zp_generation = m->generation;
@@ -914,7 +971,7 @@ int ensure_projection(pny_scene* s, int which, long long n_points, hipStream_t s
         int rc;
         if ((rc = s->zp[which].reserve((size_t)npix * nvb * HID * sizeof(float)))) return rc;
         // scenes whose projected launches run the f16x2 kernel project on the split-f16 matrix path too
-        if (!run_pixel_linear(m->zproj[which], s->latent.f(), npix, s->zp[which].f(), st, h2_ok))
+        if (!run_pixel_linear(m->zproj[which], s->latent.f(), npix, s->zp[which].f(), st, f16_default(s)))
             return fail(PNY_ERR_HIP, "latent projection launch failed");
         s->zp_valid[which] = true;
     }
@@ -931,16 +988,8 @@ int fill_mlp_args(pny_scene* s, int mode, const float* xyz, const float* dirs, c
     memset(&a, 0, sizeof(a));
     const bool fine_w = !(coarse || !d.has_fine || !s->m->use_fine);
     a.w = fine_w ? s->m->fine : s->m->coarse;
-    {
-        const MlpWeightsT& wt = fine_w ? s->m->fine_t : s->m->coarse_t;
-        a.h2_in = wt.h2_in;
-        for (int b = 0; b < d.n_blocks; ++b) {
-            a.h2_fc0[b] = wt.h2_fc0[b];
-            a.h2_fc1[b] = wt.h2_fc1[b];
-        }
-    }
-    a.w_base = s->m->packed.f();
-    a.w_bytes = (unsigned)s->m->packed.bytes;
+    a.n_blocks = d.n_blocks;
+    use_images(a, f16_images(s->m, fine_w, false));   // (in the packed blob, like `w`)
     a.range_flag = s->m->range_flag;
     a.latent = s->latent.f();
     a.zp = nullptr;
@@ -965,7 +1014,6 @@ int fill_mlp_args(pny_scene* s, int mode, const float* xyz, const float* dirs, c
     a.L = s->L;
     a.Hl = s->hl;
     a.Wl = s->wl;
-    a.n_blocks = d.n_blocks;
     a.combine_layer = d.combine_layer;
     a.d_out = d.d_out;
     a.yolo = d.yolo;
@@ -988,153 +1036,70 @@ int fill_mlp_args(pny_scene* s, int mode, const float* xyz, const float* dirs, c
 }
 }  // namespace pny
 
+// One MLP evaluation of a query / render call.  stash_pass (pny_scene_stash_next_render; 0 coarse, 1 fine pass of the
+// render): the training forward -- the STASH instantiation of the routed kernel (64-sample tiles) writes every GEMM operand
+// into the tiles this pass takes from the model-level reservation, and the backward of the same reservation epoch then
+// starts at the dX chain (the f16 instantiations read the projected latent for the forward and gather the raw latent once more
+// per view for lin_z's weight gradient; the same stash layout and contents).  Without room in the reservation the plain
+// forward runs and the backward recomputes.
 static int run_mlp(pny_scene* s, int mode, const float* xyz, const float* dirs, const float* rays, const float* z,
                    int K, long long n_points, int coarse, float* out, hipStream_t st, int stash_pass = -1) {
     if (n_points == 0) return 0;
-    const pny_model_desc& d = s->m->desc;
+    pny_model* m = s->m;
+    const pny_model_desc& d = m->desc;
     MlpArgs a;
     int rc;
     if ((rc = fill_mlp_args(s, mode, xyz, dirs, rays, z, K, n_points, coarse, out, &a))) return rc;
-    const bool fine_w = !(coarse || !d.has_fine || !s->m->use_fine);
+    const bool fine_w = !(coarse || !d.has_fine || !m->use_fine);
+    const int which = fine_w ? 1 : 0;
+    bool room = false;
     if (stash_pass >= 0) {
-        // Training forward (pny_scene_stash_next_render): the STASH instantiation (reference operation order, 64-sample
-        // tiles) writes every GEMM operand into the tiles this pass takes from the model-level reservation; the backward
-        // of the same reservation epoch then starts at the dX chain.
-        pny_model* m = s->m;
-        const int which = fine_w ? 1 : 0;
+        s->stashed[stash_pass].valid = false;
+        room = m->defer && obj_views(s) == m->defer_ns && m->defer_used[which] + a.n_tiles <= m->defer_cap[which];
+    }
+    const MlpRoute r = route_mlp(s, n_points, room);
+    if (r.stash) {
         pny_scene::StashedPass& sp = s->stashed[stash_pass];
-        sp.valid = false;
-        if (m->defer && obj_views(s) == m->defer_ns && m->defer_used[which] + a.n_tiles <= m->defer_cap[which]) {
-            a.lay = stash_layout(d, obj_views(s), s->L);
-            a.stash_x = m->dx_stash[which].f() + m->defer_used[which] * a.lay.x_tile;
-            sp.valid = true;
-            sp.epoch = m->defer_epoch;
-            sp.which = which;
-            sp.tile0 = m->defer_used[which];
-            sp.tiles = a.n_tiles;
-            sp.n_points = n_points;
-            m->defer_used[which] += a.n_tiles;
-            const int grid = std::min(mlp_max_grid(MLP_8x64), a.n_tiles);
-            // f16x2 variant of the stashing forward (mlp_h2.hip, STASH instantiation): projected latent for the forward, the
-            // raw latent gathered once more per view for lin_z's weight gradient; the same stash layout and contents
-            bool use_h2 = false;
-            if (s->precision != PNY_PRECISION_F32 && (m->f16_weights_ok || s->precision == PNY_PRECISION_F16X2) &&
-                mlp_h2_supports(d.n_blocks, d.combine_layer) && s->L % 128 == 0) {
-                if ((rc = ensure_projection(s, fine_w ? 1 : 0, n_points, st, &a.zp, true))) return rc;
-                use_h2 = a.zp != nullptr;
-                if (use_h2) a.tap_stride = a.zp_stride;
-            }
-            // F16_TRAIN: the single-plane kernel's STASH instantiation (mlp_h1t.hip) wherever the split one would run
-            const bool use_h1 = use_h2 && s->precision == PNY_PRECISION_F16_TRAIN;
-            if (use_h1) {
-                if ((rc = want_h1_images(m, true))) return rc;
-                const int f = (fine_w && d.has_fine) ? 1 : 0;
-                a.w_base = m->h1_packed.f();
-                a.w_bytes = (unsigned)m->h1_packed.bytes;
-                a.h2_in = m->h1_in[f];
-                for (int b = 0; b < d.n_blocks; ++b) {
-                    a.h2_fc0[b] = m->h1_fc0[f][b];
-                    a.h2_fc1[b] = m->h1_fc1[f][b];
-                }
-            }
-            if (s->timing) {
-                while ((int)s->ev.size() < s->ev_used + 2) {
-                    hipEvent_t e;
-                    PNY_HIP(hipEventCreate(&e));
-                    s->ev.push_back(e);
-                }
-                PNY_HIP(hipEventRecord(s->ev[s->ev_used], st));
-            }
-            if (use_h1)
-                launch_mlp_h1_stash(a, grid, st);
-            else if (use_h2)
-                launch_mlp_h2_stash(a, grid, st);
-            else
-                launch_mlp_stash(a, grid, st);
-            PNY_HIP(hipGetLastError());
-            if (s->timing) {
-                PNY_HIP(hipEventRecord(s->ev[s->ev_used + 1], st));
-                s->ev_used += 2;
-            }
-            s->last_flops += mlp_flops_per_point(d, obj_views(s), !use_h2) * (double)n_points;
-            s->last_flops_ref += mlp_flops_per_point(d, obj_views(s), true) * (double)n_points;
-            s->last_projected = use_h2;
-            s->last_f16x2 = use_h2;
-            s->last_prec = use_h1 ? 2 : use_h2 ? 1 : 0;   // (F16 scenes: the training forward runs as AUTO)
-            s->last_launches += 1;
-            return 0;
-        }
-        // no room in the reservation: plain forward, the backward recomputes
+        a.lay = stash_layout(d, obj_views(s), s->L);
+        a.stash_x = m->dx_stash[which].f() + m->defer_used[which] * a.lay.x_tile;
+        sp.valid = true;
+        sp.epoch = m->defer_epoch;
+        sp.which = which;
+        sp.tile0 = m->defer_used[which];
+        sp.tiles = a.n_tiles;
+        sp.n_points = n_points;
+        m->defer_used[which] += a.n_tiles;
     }
-    if ((rc = ensure_projection(s, fine_w ? 1 : 0, n_points, st, &a.zp))) return rc;
-    a.tap_stride = a.zp ? a.zp_stride : s->L;
-    int variant = mlp_pick_variant(n_points);
-    // f16x2 kernel (split-f16 operands, mlp_h2.hip): every projected launch unless the scene is pinned to F32 -- one
-    // arithmetic for all projected launches keeps a ray's result independent of the batch it is rendered in (ray
-    // sharding stays bit-exact); a lone 64-sample h2 tile is also faster than the 32-sample fp32 shape it replaces.
-    const bool use_h2 = a.zp && mlp_h2_supports(d.n_blocks, d.combine_layer) && s->precision != PNY_PRECISION_F32 &&
-                        (s->m->f16_weights_ok || s->precision == PNY_PRECISION_F16X2);
-    if (use_h2) variant = MLP_8x64;
-    // single-plane kernel (PNY_PRECISION_F16, mlp_h1.hip): wherever an F16 scene would run the split kernel, in its one
-    // 64-sample shape for every launch size (never the split shape)
-    // (F16_TRAIN scenes: the same kernel, so their no-grad results are F16's bit for bit)
-    const bool use_h1 = use_h2 && (s->precision == PNY_PRECISION_F16 || s->precision == PNY_PRECISION_F16_TRAIN);
-    if (use_h1) {
-        if ((rc = want_h1_images(s->m, s->precision == PNY_PRECISION_F16_TRAIN))) return rc;
-        const int f = (fine_w && d.has_fine) ? 1 : 0;
-        a.w_base = s->m->h1_packed.f();
-        a.w_bytes = (unsigned)s->m->h1_packed.bytes;
-        a.h2_in = s->m->h1_in[f];
-        for (int b = 0; b < d.n_blocks; ++b) {
-            a.h2_fc0[b] = s->m->h1_fc0[f][b];
-            a.h2_fc1[b] = s->m->h1_fc1[f][b];
-        }
+    if (r.projected) {
+        if ((rc = ensure_projection(s, which, n_points, st, &a.zp, r.stash))) return rc;
+        a.tap_stride = a.zp_stride;
     }
-    // Split shape of the f16x2 kernel (mlp_h2s.hip: 32-sample tiles, 4-wave workgroups, two per CU): the same arithmetic per
-    // sample, bit for bit.  Measured (profiles/r02zk_split_sweep.log): a launch that gives every CU at most ONE 32-sample tile
-    // takes 0.40-0.43 ms against 0.47-0.51 ms on 64-sample tiles; as soon as two workgroups share a CU the doubled weight
-    // stream per sample costs more than the overlap of their phases returns (full C2 frame: 61.7 vs 39.9 ms per launch).
-    // So: launches of at most 32 x CUs points.  PNYOLO_H2_SPLIT=0|1 overrides.
-    bool use_h2s = use_h2 && !use_h1 && n_points <= 32ll * mlp_max_grid(MLP_8x64);
-    if (use_h2 && !use_h1)
-        if (const char* e = getenv("PNYOLO_H2_SPLIT")) use_h2s = atoi(e) != 0;
-    const int tm = use_h2s ? 32 : mlp_tile_samples(variant);
-    const long long tiles = (n_points + tm - 1) / tm;
+    if (r.kernel == K_H1) {   // (F16_TRAIN scenes: the same no-grad kernel as F16's, so their no-grad results are F16's bit for bit)
+        if ((rc = want_h1_images(m, s->precision == PNY_PRECISION_F16_TRAIN))) return rc;
+        use_images(a, f16_images(m, fine_w, true));
+    }
+    const long long tiles = (n_points + r.tile - 1) / r.tile;
     if (tiles > 0x7fffffffll) return fail(PNY_ERR_ARG, "too many points for one launch");
     a.n_tiles = (int)tiles;
-    a.idx32 = (tiles * tm) < 0xffffffffll;
-    int grid = use_h2s ? 2 * mlp_max_grid(MLP_8x64) : mlp_max_grid(variant);
-    if (const char* e = getenv("PNYOLO_GRID")) {  // diagnostic: fewer resident workgroups
-        const int g = atoi(e);
-        if (g > 0 && g < grid) grid = g;
+    a.idx32 = (tiles * r.tile) < 0xffffffffll;
+    const int grid = (int)std::min<long long>(r.grid_cap, tiles);
+    if ((rc = stamp_event(s->timing, s->ev, s->ev_used, st))) return rc;
+    switch (r.kernel) {
+    case K_H1: (r.stash ? launch_mlp_h1_stash : launch_mlp_h1)(a, grid, st); break;
+    case K_H2: (r.stash ? launch_mlp_h2_stash : launch_mlp_h2)(a, grid, st); break;
+    case K_H2S: launch_mlp_h2s(a, grid, st); break;
+    default:
+        if (r.stash)
+            launch_mlp_stash(a, grid, st);
+        else
+            launch_mlp(a, r.kernel, grid, st);
     }
-    if (tiles < grid) grid = (int)tiles;
-    if (s->timing) {
-        while ((int)s->ev.size() < s->ev_used + 2) {
-            hipEvent_t e;
-            PNY_HIP(hipEventCreate(&e));
-            s->ev.push_back(e);
-        }
-        PNY_HIP(hipEventRecord(s->ev[s->ev_used], st));
-    }
-    if (use_h1)
-        launch_mlp_h1(a, grid, st);
-    else if (use_h2s)
-        launch_mlp_h2s(a, grid, st);
-    else if (use_h2)
-        launch_mlp_h2(a, grid, st);
-    else
-        launch_mlp(a, variant, grid, st);
     PNY_HIP(hipGetLastError());
-    if (s->timing) {
-        PNY_HIP(hipEventRecord(s->ev[s->ev_used + 1], st));
-        s->ev_used += 2;
-    }
-    s->last_f16x2 = use_h2;
-    s->last_prec = use_h1 ? 2 : use_h2 ? 1 : 0;
-    s->last_flops += mlp_flops_per_point(d, obj_views(s), a.zp == nullptr) * (double)n_points;
-    s->last_flops_ref += mlp_flops_per_point(d, obj_views(s), true) * (double)n_points;
-    s->last_projected = a.zp != nullptr;
+    if ((rc = stamp_event(s->timing, s->ev, s->ev_used, st))) return rc;
+    s->last_prec = r.prec;
+    s->last_projected = r.projected;
+    s->last_flops += mlp_flops_per_point(d, obj_views(s), r.projected ? PASS_FORWARD_PROJECTED : PASS_FORWARD) * (double)n_points;
+    s->last_flops_ref += mlp_flops_per_point(d, obj_views(s), PASS_FORWARD) * (double)n_points;
     s->last_launches += 1;
     return 0;
 }

@@ -93,6 +93,27 @@ struct RepackEntry {
     int n_out, k_in, k_pad, count;
 };
 
+// The 0 / 1 / 2 codes pny_scene_last_precision, pny_scene_last_backward_precision and pny_model_last_flush_precision report, and
+// the matrix arithmetic of a kernel wherever the host code has to name it
+enum Prec { PREC_F32 = 0, PREC_H2 = 1 /* split f16 (F16X2) */, PREC_H1 = 2 /* single-plane f16 (F16, F16_TRAIN) */ };
+// planes per operand of the f16 weight- and latent-gradient GEMMs (ignored by their fp32 paths)
+inline int gemm_planes(Prec p) { return p == PREC_H1 ? 1 : 2; }
+
+// One set of f16 operand images of an MLP and the allocation they live in (raw-buffer addressing): lin_in / fc_0 / fc_1 as the
+// forward kernels read them (mlp_h2.hip, mlp_h1.hip) and lin_out / fc_0 / fc_1 transposed for the backward chain
+// (mlp_bwd_h2.hip, mlp_bwd_h1.hip).  Either the split-f16 images (MlpWeightsT::h2, in the model's packed blob) or the
+// single-plane ones (pny_model::h1, a buffer of their own).
+struct F16Images {
+    const float* in;
+    const float* fc0[MAX_BLOCKS];
+    const float* fc1[MAX_BLOCKS];
+    const float* T_out;
+    const float* T_fc0[MAX_BLOCKS];
+    const float* T_fc1[MAX_BLOCKS];
+    const float* base;
+    size_t bytes;
+};
+
 // transposed packed weights of one MLP (A operands of the backward chain, mlp_bwd.hip)
 struct MlpWeightsT {
     const float* w_in_plain;  // lin_in.weight as stored (512, d_in): input gradients (mlp_bwd.hip mlp_dz_kernel)
@@ -100,13 +121,41 @@ struct MlpWeightsT {
     const float* wT_fc0[MAX_BLOCKS];
     const float* wT_fc1[MAX_BLOCKS];
     const float* wzT_cat;     // [lin_z[0]^T | lin_z[1]^T | ...] (d_latent x n_view_blocks * 512), n-tile-major (latent_grad.hip)
-    const float* h2_in;       // split-f16 images (mlp_h2.hip)
-    const float* h2_fc0[MAX_BLOCKS];
-    const float* h2_fc1[MAX_BLOCKS];
-    const float* h2T_out;     // split-f16 images of the transposed matrices (mlp_bwd_h2.hip)
-    const float* h2T_fc0[MAX_BLOCKS];
-    const float* h2T_fc1[MAX_BLOCKS];
+    F16Images h2;             // split-f16 images (pack.hip PACK_H2 / PACK_H2T)
 };
+
+// the launch's f16 operand images (and the allocation the kernel addresses them in)
+inline void use_images(MlpArgs& a, const F16Images& im) {
+    a.w_base = im.base;
+    a.w_bytes = (unsigned)im.bytes;
+    a.h2_in = im.in;
+    for (int b = 0; b < a.n_blocks; ++b) {
+        a.h2_fc0[b] = im.fc0[b];
+        a.h2_fc1[b] = im.fc1[b];
+    }
+}
+inline void use_images(BwdArgs& a, const F16Images& im) {
+    a.w_base = im.base;
+    a.w_bytes = (unsigned)im.bytes;
+    a.h2T_out = im.T_out;
+    for (int b = 0; b < a.n_blocks; ++b) {
+        a.h2T_fc0[b] = im.T_fc0[b];
+        a.h2T_fc1[b] = im.T_fc1[b];
+    }
+}
+
+// Kernel timing (pny_scene_enable_timing): records the next event of `ev` on `st`, creating it on first use.  A timed launch
+// is bracketed by two calls.
+inline int stamp_event(bool timing, std::vector<hipEvent_t>& ev, int& used, hipStream_t st) {
+    if (!timing) return 0;
+    if ((int)ev.size() <= used) {
+        hipEvent_t e;
+        PNY_HIP(hipEventCreate(&e));
+        ev.push_back(e);
+    }
+    PNY_HIP(hipEventRecord(ev[used++], st));
+    return 0;
+}
 
 }  // namespace pny
 
@@ -145,7 +194,7 @@ struct pny_model {
     bool defer_dw_f32 = false;               // a scene pinned to F32 contributed: the flush runs the fp32 weight-gradient GEMM
     bool defer_dw_h2 = false;                // a split-f16 scene contributed: a flush without F32 contributors runs split-f16,
                                              // one with F16_TRAIN contributors only the single-plane GEMM
-    int last_flush_prec = 0;                 // pny_model_last_flush_precision: 0 fp32, 1 split-f16, 2 single-plane GEMM
+    Prec last_flush_prec = PREC_F32;         // pny_model_last_flush_precision: the flush's GEMM
     bool deterministic = false;              // pny_model_set_deterministic: the latent gradient of every scene is bit-reproducible
     hipStream_t aux_stream = nullptr;        // side stream of the weight-gradient GEMMs' clipped tiles (mlp_bwd.hip launch_dw_gemm)
     hipEvent_t aux_fork = nullptr, aux_join = nullptr;
@@ -170,15 +219,10 @@ struct pny_model {
     DevBuf h1_packed, h1_jobs;
     int n_h1_jobs = 0;
     long long h1_max_elems = 0;
-    const float* h1_in[2] = {nullptr, nullptr};
-    const float* h1_fc0[2][MAX_BLOCKS] = {};
-    const float* h1_fc1[2][MAX_BLOCKS] = {};
     // ... and of the TRANSPOSED matrices (plane 0 of the PACK_H2T images) for the single-plane backward chain of
     // PNY_PRECISION_F16_TRAIN (mlp_bwd_h1.hip), in the same buffer: built only once a scene is set to F16_TRAIN
     bool want_h1t = false;
-    const float* h1T_out[2] = {nullptr, nullptr};
-    const float* h1T_fc0[2][MAX_BLOCKS] = {};
-    const float* h1T_fc1[2][MAX_BLOCKS] = {};
+    F16Images h1[2] = {};
 };
 
 struct pny_scene {
@@ -197,9 +241,8 @@ struct pny_scene {
     int zp_mode = PNY_PROJECTION_AUTO;
     float* latent_grad = nullptr;   // (ns, hl, wl, L) caller-owned accumulator of d loss / d latent (pny_scene_bind_latent_grad)
     int precision = PNY_PRECISION_AUTO;   // matrix arithmetic of projected launches (pny_scene_set_precision)
-    bool last_f16x2 = false;
-    int last_prec = 0;    // pny_scene_last_precision: 0 fp32, 1 split-f16 (F16X2), 2 single-plane f16 (F16) kernel
-    int last_bwd_prec = 0;   // pny_scene_last_backward_precision: the same codes for the dX chain of the last backward
+    Prec last_prec = PREC_F32;       // pny_scene_last_precision: the kernel of the last MLP launch
+    Prec last_bwd_prec = PREC_F32;   // pny_scene_last_backward_precision: the dX chain of the last backward
     bool last_projected = false;
     double last_flops_ref = 0.0;
     // timing of the MLP launches of the last call
@@ -243,8 +286,18 @@ namespace pny {
 int enter_stream(pny_scene* s, hipStream_t st);
 int check_ready(pny_scene* s, const char* who);
 int view_blocks(const pny_model_desc& d);
+inline int d_in(const pny_model_desc& d) { return 3 + 6 * d.num_freqs + 3; }   // xyz, its positional code, view direction
+// GEMM FLOPs (2 per MAC, unpadded) per query point over ns views: the forward as the reference computes it, the forward as the
+// projected-latent variant executes it (lin_z moved to the per-scene projection), the backward's dX chain.  Every forward
+// GEMM has one weight-gradient GEMM of the same size.
+enum MlpPass { PASS_FORWARD, PASS_FORWARD_PROJECTED, PASS_CHAIN };
+double mlp_flops_per_point(const pny_model_desc& d, int ns, MlpPass pass);
 // single-plane f16 images (PNY_PRECISION_F16): marks the model as using them and builds them if it is finalized
 int want_h1_images(pny_model* m, bool transposed = false);   // transposed: also the chain's images (PNY_PRECISION_F16_TRAIN)
+// the f16 images of the coarse / fine MLP: split, or single-plane (valid after want_h1_images)
+inline const F16Images& f16_images(const pny_model* m, bool fine, bool single_plane) {
+    return single_plane ? m->h1[fine ? 1 : 0] : (fine ? m->fine_t : m->coarse_t).h2;
+}
 inline int obj_views(const pny_scene* s) { return s->ns / (s->n_objs > 0 ? s->n_objs : 1); }   // views per object
 StashLayout stash_layout(const pny_model_desc& d, int ns, int L);
 // projected latent maps of the coarse (0) / fine (1) MLP, computed if stale; force = regardless of the scene's mode

@@ -45,7 +45,7 @@ float* grad_of(const pny_model* m, const std::string& name) {
 TrainPlan build_plan(const pny_model* m, int ns, int L, const std::string& pre) {
     const pny_model_desc& d = m->desc;
     const int nb = d.n_blocks, nvb = view_blocks(d), npost = nb - nvb;
-    const int d_in = 3 + 6 * d.num_freqs + 3;
+    const int d_in = pny::d_in(d);
     TrainPlan p;
     p.lay = stash_layout(d, ns, L);
     StashLayout& l = p.lay;
@@ -196,16 +196,24 @@ void build_items(TrainPlan& p, int n_tiles, int cus, std::vector<DwItem>& items,
     *bias_floats = boff;
 }
 
-// Matrix arithmetic of the backward's GEMMs (dX chain and weight gradients): the scene's precision setting (F32 pins the fp32
-// MFMA; F16_TRAIN = single-plane f16: mlp_bwd_h1.hip, dw_gemm_h1.hip, latent_grad_h1.hip; anything else = split f16:
+// Matrix arithmetic of the backward's GEMMs, decided here for all of them.  Asked for: the scene's precision setting (F32 pins
+// the fp32 MFMA; F16_TRAIN = single-plane f16: mlp_bwd_h1.hip, dw_gemm_h1.hip, latent_grad_h1.hip; anything else = split f16:
 // mlp_bwd_h2.hip pny_mlp_bwd_h2_kernel, dw_gemm_h2.hip pny_dw_gemm_h2_kernel); env PNYOLO_BWD_PRECISION=f32|f16x2 overrides (read
-// at every call: tests vary it).  0 fp32, 1 split f16, 2 single-plane f16.
-int bwd_prec(const pny_scene* s) {
+// at every call: tests vary it).  The dX chain reads the weights' f16 images, so weights beyond the f16 range put it on fp32;
+// the weight- and latent-gradient GEMMs read activations and gradients only and stay on split f16 then, scaled by the max |dY|
+// the chain tracks for them.
+struct BwdRoute {
+    Prec chain;          // dX-chain kernel
+    bool track_absmax;   // the chain tracks max |dY|: the gradient GEMMs run f16
+    Prec gemm() const { return !track_absmax ? PREC_F32 : chain == PREC_H1 ? PREC_H1 : PREC_H2; }   // weight and latent gradients
+};
+BwdRoute route_bwd(const pny_scene* s) {
+    Prec want = s->precision == PNY_PRECISION_F32 ? PREC_F32 : s->precision == PNY_PRECISION_F16_TRAIN ? PREC_H1 : PREC_H2;
     if (const char* e = getenv("PNYOLO_BWD_PRECISION")) {
-        if (!strcmp(e, "f32")) return 0;
-        if (!strcmp(e, "f16x2")) return 1;
+        if (!strcmp(e, "f32")) want = PREC_F32;
+        if (!strcmp(e, "f16x2")) want = PREC_H2;
     }
-    return s->precision == PNY_PRECISION_F32 ? 0 : s->precision == PNY_PRECISION_F16_TRAIN ? 2 : 1;
+    return {s->m->f16_weights_ok ? want : PREC_F32, want != PREC_F32};
 }
 
 // A zeroed device word (or two) for the chain kernels' atomic max
@@ -327,17 +335,15 @@ int mlp_backward(pny_scene* s, int mode, const float* xyz, const float* dirs, co
     if ((rc = s->out_tmp.reserve((size_t)chunk_pts * d.d_out * sizeof(float)))) return rc;
     // running max |dY| for the split-f16 weight-gradient GEMM: per model and MLP in deferred mode (every scene's chain adds
     // to it, zeroed again by the flush), per scene otherwise (zeroed in front of every chunk's chain)
-    const int bprec = bwd_prec(s);
-    const bool dw_h2 = bprec != 0;
-    const bool h1 = bprec == 2 && m->f16_weights_ok;   // single-plane chain, latent gradient and (immediate) weight gradients
-    if (h1 && (rc = want_h1_images(m, true))) return rc;
+    const BwdRoute r = route_bwd(s);
+    if (r.chain == PREC_H1 && (rc = want_h1_images(m, true))) return rc;
     unsigned* absmax = nullptr;
     if (defer || have_x) {
-        if (!dw_h2) m->defer_dw_f32 = true;
-        if (dw_h2 && !h1) m->defer_dw_h2 = true;
+        if (r.gemm() == PREC_F32) m->defer_dw_f32 = true;
+        if (r.gemm() == PREC_H2) m->defer_dw_h2 = true;
         if ((rc = ensure_absmax(m->d_absmax, 2 * sizeof(unsigned)))) return rc;
         absmax = reinterpret_cast<unsigned*>(m->d_absmax.p) + which;
-    } else if (dw_h2) {
+    } else if (r.track_absmax) {
         if ((rc = ensure_absmax(s->dy_absmax, sizeof(unsigned)))) return rc;
         absmax = reinterpret_cast<unsigned*>(s->dy_absmax.p);
     }
@@ -359,25 +365,12 @@ int mlp_backward(pny_scene* s, int mode, const float* xyz, const float* dirs, co
             PNY_HIP(hipMemsetAsync(s->lg_fixed.p, 0, need, st));
         }
     }
-    auto stamp = [&]() -> int {   // kernel timing for bench.py (pny_scene_enable_timing)
-        if (!s->timing) return 0;
-        if ((int)s->bev.size() <= s->bev_used) {
-            hipEvent_t e;
-            PNY_HIP(hipEventCreate(&e));
-            s->bev.push_back(e);
-        }
-        PNY_HIP(hipEventRecord(s->bev[s->bev_used++], st));
-        return 0;
-    };
-    {   // GEMM FLOPs (2 per MAC, unpadded) of the three kernels, per query point
-        const int nvb_ = view_blocks(d), npost_ = d.n_blocks - nvb_, d_in_ = 3 + 6 * d.num_freqs + 3;
-        const double per_view_f = (double)d_in_ * HID + (double)nvb_ * s->L * HID + 2.0 * nvb_ * HID * HID;
-        const double post_f = 2.0 * npost_ * HID * HID + (double)HID * d.d_out;
-        const double fwd = 2.0 * (obj_views(s) * per_view_f + post_f);
-        const double chain = 2.0 * (obj_views(s) * 2.0 * nvb_ * HID * HID + 2.0 * npost_ * HID * HID + (double)HID * d.d_out);
-        if (!have_x) s->bwd_flops[0] += fwd * (double)n_points;   // the forward already stashed: nothing is recomputed
-        s->bwd_flops[1] += chain * (double)n_points;
-        s->bwd_flops[2] += fwd * (double)n_points;   // every forward GEMM has one weight-gradient GEMM of the same size
+    auto stamp = [&]() { return stamp_event(s->timing, s->bev, s->bev_used, st); };   // kernel timing for bench.py
+    {   // GEMM FLOPs of the three kernels
+        const double fwd = mlp_flops_per_point(d, obj_views(s), PASS_FORWARD) * (double)n_points;
+        if (!have_x) s->bwd_flops[0] += fwd;   // the forward already stashed: nothing is recomputed
+        s->bwd_flops[1] += mlp_flops_per_point(d, obj_views(s), PASS_CHAIN) * (double)n_points;
+        s->bwd_flops[2] += fwd;   // every forward GEMM has one weight-gradient GEMM of the same size
     }
     const float* zp_maps = nullptr;
     if (dz_sel && view_blocks(d) > 0) {
@@ -432,29 +425,10 @@ int mlp_backward(pny_scene* s, int mode, const float* xyz, const float* dirs, co
             b.dy_absmax = lg_max;
             if (!absmax) b.range_flag = nullptr;   // (the fp32 path keeps its semantics: no f16 range guard)
         }
-        if (h1) {   // single-plane chain: the transposed single-plane images in the model's h1 buffer
-            const int f = (fine_w && d.has_fine) ? 1 : 0;
-            b.w_base = m->h1_packed.f();
-            b.w_bytes = (unsigned)m->h1_packed.bytes;
-            b.h2T_out = m->h1T_out[f];
-            for (int i = 0; i < d.n_blocks; ++i) {
-                b.h2T_fc0[i] = m->h1T_fc0[f][i];
-                b.h2T_fc1[i] = m->h1T_fc1[f][i];
-            }
-            launch_mlp_bwd_h1(b, grid, st);
-            s->last_bwd_prec = 2;
-        } else if (dw_h2 && m->f16_weights_ok) {   // split-f16 chain (weights beyond the f16 range: fp32 chain)
-            b.h2T_out = wt.h2T_out;
-            for (int i = 0; i < d.n_blocks; ++i) {
-                b.h2T_fc0[i] = wt.h2T_fc0[i];
-                b.h2T_fc1[i] = wt.h2T_fc1[i];
-            }
-            launch_mlp_bwd_h2(b, grid, st);
-            s->last_bwd_prec = 1;
-        } else {
-            launch_mlp_bwd(b, grid, st);
-            s->last_bwd_prec = 0;
-        }
+        // the chain's f16 images: split in the packed blob, single-plane in the model's h1 buffer (none: the fp32 chain)
+        if (r.chain != PREC_F32) use_images(b, f16_images(m, fine_w, r.chain == PREC_H1));
+        (r.chain == PREC_H1 ? launch_mlp_bwd_h1 : r.chain == PREC_H2 ? launch_mlp_bwd_h2 : launch_mlp_bwd)(b, grid, st);
+        s->last_bwd_prec = r.chain;
         PNY_HIP(hipGetLastError());
         if (lg_det && absmax) launch_absmax_fold(absmax, lg_max, st);
         if ((rc = stamp())) return rc;
@@ -471,7 +445,7 @@ int mlp_backward(pny_scene* s, int mode, const float* xyz, const float* dirs, co
             dz.z = z;
             dz.K = K;
             dz.w_in = wt.w_in_plain;
-            dz.d_in = 3 + 6 * d.num_freqs + 3;
+            dz.d_in = d_in(d);
             dz.zp = zp_maps;
             dz.zp_stride = view_blocks(d) * HID;
             dz.NS = obj_views(s);
@@ -496,11 +470,12 @@ int mlp_backward(pny_scene* s, int mode, const float* xyz, const float* dirs, co
             if (s->L % 256) return fail(PNY_ERR_ARG, "latent gradient: d_latent must be a multiple of 256");
             if (lg_det) {
                 if ((rc = launch_latent_grad_det(a, dy_base, plan.lay, wt.wzT_cat, s->latent_grad, view_blocks(d), st, lg_max,
-                                                 !dw_h2 ? 0 : h1 ? 2 : 1, reinterpret_cast<unsigned long long*>(s->lg_fixed.p),
+                                                 r.gemm(), reinterpret_cast<unsigned long long*>(s->lg_fixed.p),
                                                  lg_elems, s->lg_words.p)))
                     return rc;
             } else {
-                launch_latent_grad(a, dy_base, plan.lay, wt.wzT_cat, s->latent_grad, view_blocks(d), st, dw_h2 ? absmax : nullptr, h1 ? 1 : 2);
+                launch_latent_grad(a, dy_base, plan.lay, wt.wzT_cat, s->latent_grad, view_blocks(d), st, r.track_absmax ? absmax : nullptr,
+                                   gemm_planes(r.gemm()));
             }
             s->last_lg_det = lg_det ? 1 : 0;
             PNY_HIP(hipGetLastError());
@@ -508,7 +483,7 @@ int mlp_backward(pny_scene* s, int mode, const float* xyz, const float* dirs, co
         // 3. weight-gradient GEMMs over the two stashes + deterministic split reduction into the bound gradients
         if (!defer && !have_x &&
             (rc = run_weight_grads(m, plan, n_tiles, x_base, dy_base, s->dw_partial, s->dw_bias, s->dw_tables, s->table_stage,
-                                   (accumulate || p0 > 0) ? 1 : 0, st, absmax, h1 ? 1 : 2)))
+                                   (accumulate || p0 > 0) ? 1 : 0, st, absmax, gemm_planes(r.gemm()))))
             return rc;
         if ((rc = stamp())) return rc;
     }
@@ -584,9 +559,7 @@ int pny_model_flush_weight_grads(pny_model* m, int accumulate, pny_stream stream
     for (int i = 0; i < 4; ++i)
         if (!m->flush_ev[i]) PNY_HIP(hipEventCreate(&m->flush_ev[i]));
     const pny_model_desc& d = m->desc;
-    const int nvb_ = view_blocks(d), npost_ = d.n_blocks - nvb_, d_in_ = 3 + 6 * d.num_freqs + 3;
-    const double per_view_f = (double)d_in_ * HID + (double)nvb_ * d.d_latent * HID + 2.0 * nvb_ * HID * HID;
-    const double fwd = 2.0 * (m->defer_ns * per_view_f + 2.0 * npost_ * HID * HID + (double)HID * d.d_out);
+    const double fwd = mlp_flops_per_point(d, m->defer_ns, PASS_FORWARD);
     // bits 16 / 32 of `accumulate`: only mlp_coarse's / only mlp_fine's stash (0: both)
     const bool only_c = (accumulate & 16) != 0, only_f = (accumulate & 32) != 0;
     accumulate &= 1;
@@ -597,12 +570,12 @@ int pny_model_flush_weight_grads(pny_model* m, int accumulate, pny_stream stream
             TrainPlan plan = build_plan(m, m->defer_ns, d.d_latent, w ? "mlp_fine." : "mlp_coarse.");
             const unsigned* absmax = (m->d_absmax.p && !m->defer_dw_f32) ? reinterpret_cast<const unsigned*>(m->d_absmax.p) + w : nullptr;
             // single-plane GEMM only when every contributor ran the F16_TRAIN backward (any F32 one: fp32, else split-f16)
-            const int planes = m->defer_dw_h2 ? 2 : 1;
+            const Prec gemm = !absmax ? PREC_F32 : m->defer_dw_h2 ? PREC_H2 : PREC_H1;
             if ((rc = run_weight_grads(m, plan, (int)m->defer_used[w], m->dx_stash[w].f(), m->ddy_stash[w].f(), m->d_partial[w],
-                                       m->d_bias[w], m->d_tables[w], m->d_stage[w], accumulate, st, absmax, planes)))
+                                       m->d_bias[w], m->d_tables[w], m->d_stage[w], accumulate, st, absmax, gemm_planes(gemm))))
                 return rc;
             m->flush_flops += fwd * 64.0 * (double)m->defer_used[w];
-            m->last_flush_prec = absmax ? (planes == 1 ? 2 : 1) : 0;
+            m->last_flush_prec = gemm;
             m->flush_launches += 1;
         }
         PNY_HIP(hipEventRecord(m->flush_ev[2 * w + 1], st));
