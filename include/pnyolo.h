@@ -189,6 +189,43 @@ int pny_sample_train_batch(const pny_train_batch_desc* desc, const float* images
                            const pny_train_batch_draws* draws, float* rays_dev, float* rgb_gt_dev, int32_t* pix_dev,
                            pny_stream stream);
 
+/* The rays and target cells of one YOLO training step for ONE object, over all scales and selected views, in ONE launch:
+ * what YoloTrainer.calc_losses prepares per scale (train/trainlib/YoloTrainer.py:93-129: NV host->device copies of the
+ * target grids, stack, util.gen_rays_yolo src/util/util.py:808-876 of the selected views at the scale's grid size, two
+ * indexings by image_ord, two reshapes).  The reference's loop does not index the targets per object (:83), so one object
+ * per call is the contract; a caller with several objects calls once per object.  Model-free, like pny_gen_rays, whose
+ * yolo_mode = 1 arithmetic it shares: a ray of scale s has the bits of the same pixel of
+ * pny_gen_rays_range(poses[view], 1, Ws, Hs, focal / cell, c / cell, ..., yolo_mode = 1). */
+#define PNY_YOLO_BATCH_MAX_VIEWS 16
+#define PNY_YOLO_BATCH_MAX_SCALES 4
+typedef struct pny_yolo_batch_desc {
+    int32_t n_views_all;   /* NV: views the object has (rows of poses_host, first dimension of every target grid) */
+    int32_t n_views;       /* NS: selected views, 1 .. PNY_YOLO_BATCH_MAX_VIEWS */
+    int32_t height;        /* full-resolution image */
+    int32_t width;
+    int32_t n_scales;      /* 1 .. PNY_YOLO_BATCH_MAX_SCALES */
+    int32_t cell_sizes[PNY_YOLO_BATCH_MAX_SCALES]; /* scale s is the grid of Hs = height / cell, Ws = width / cell (integer division) */
+    int32_t n_anchors;     /* A = num_anchors_per_scale, 1 .. 64 */
+    float z_near;
+    float z_far;
+} pny_yolo_batch_desc;
+/* poses_host (NV, 4, 4): world->cam extrinsics, as pny_gen_rays takes them with yolo_mode = 1.  view_ids_host (NS): the
+ * object's row of image_ord -- any order, repeats allowed; an id outside [0, NV) is PNY_ERR_ARG.  focal[2], c[2]: the
+ * full-resolution intrinsics; each scale's focal / cell and c / cell are formed in fp32 (an IEEE division, what the
+ * reference's tensor division gives; for a power-of-two cell also what a multiplication by 1 / cell gives).
+ * targets_dev[n_scales]: device pointers to the (NV, Hs, Ws, A, 6) fp32 target grids.
+ * Writes rays_dev (R, 8), 16-byte aligned, and targets_out_dev (R, A, 6), R = NS * sum_s Hs Ws: scale s occupies rows
+ * [off[s], off[s + 1]), inside a scale the rows are ordered (position in view_ids, y, x) -- the reference's reshape(-1, 8) /
+ * reshape(-1, A, 6).  offsets_host (n_scales + 1 int64, host) receives off.  One kernel enqueued on `stream` (the selected
+ * cameras and the scales' intrinsics travel as kernel arguments); no allocation, no copy, no synchronisation.
+ * With rays_dev and targets_out_dev both NULL the call only fills offsets_host from the descriptor (how a caller sizes the
+ * two buffers): the other pointers are not looked at and nothing is launched.
+ * PNY_ERR_ARG before anything is launched: n_scales outside 1 .. 4, NS outside 1 .. 16 (the call never launches twice), A outside 1 .. 64, a cell
+ * below 1 or larger than the image, a NULL pointer, an unaligned rays_dev, a singular pose, a zero focal length. */
+int pny_yolo_train_batch(const pny_yolo_batch_desc* desc, const float* poses_host, const int64_t* view_ids_host,
+                         const float focal[2], const float c[2], const float* const* targets_dev, float* rays_dev,
+                         float* targets_out_dev, int64_t* offsets_host, pny_stream stream);
+
 /* PixelNeRFNet.forward for one scene (src/model/models.py:153-318):
  * xyz_dev, viewdirs_dev (n,3) world space -> out_dev (n,d_out) = [sigmoid rgb, relu sigma]
  * (YOLO mode: raw).  coarse=0 selects mlp_fine when the model has one. */
@@ -587,6 +624,38 @@ typedef struct pny_yolo_loss_desc {
 } pny_yolo_loss_desc;
 int pny_yolo_loss(const pny_yolo_loss_desc* desc, const float* pred_dev, const float* target_dev, const float* anchors_dev,
                   int64_t cells, float* terms_dev, int32_t* counts_dev, float* d_pred_dev, pny_stream stream);
+
+/* ---- NaN / Inf monitor: the finiteness tests of a YOLO training step without a host wait (csrc/finite.hip).  Replaces the
+ * `if torch.isnan(x).any()` / `torch.isinf(x).any()` tests on the render and the targets (train/trainlib/YoloTrainer.py:
+ * 163-178) and the two per-parameter generator expressions over p.grad (:188-194), each of which is two launches and a
+ * blocking read.  ONE kernel scans a table of fp32 tensors (a value is non-finite when its exponent bits are all ones; a
+ * non-zero mantissa makes it a NaN) and records what it meets per caller-chosen group in two int32 words on the device:
+ *   flags_dev[2 * group]      bits: PNY_FINITE_NAN = a NaN was seen, PNY_FINITE_INF = a +-Inf was seen
+ *   flags_dev[2 * group + 1]  first: the lowest table index of a tensor in which either was seen; INT32_MAX after reset
+ * combined with atomic OR / MIN: the words do not depend on the execution order and stay set across calls until
+ * pny_finite_reset.  A scan that meets nothing writes nothing.  flags_dev holds 2 * (largest group + 1) words, 4-byte aligned;
+ * the host reads it when it wants to (one copy per step).  Tensors are fp32, 4-byte aligned, any size; a count of 0 is legal.
+ * pny_finite_add_tensor registers a tensor in the handle's table, which is kept on the device (for buffers whose address
+ * is stable: gradients), and returns its table index (>= 0) or a negative status; it copies the entry to the device before it
+ * returns (registration is not part of a step; should growing the table fail, the handle is left empty and every tensor has
+ * to be registered again).  pny_finite_check scans the registered tensors [first, first + n) in one
+ * launch; the index recorded is the table index.  pny_finite_check_tensors scans up to PNY_FINITE_MAX_IMMEDIATE tensors given
+ * in host arrays (for the fresh render and target tensors of a mini-batch): pointers, counts and groups travel as kernel
+ * arguments, the index recorded is the position in the arrays; the same kernel body.  pny_finite_reset sets n_groups pairs
+ * to {0, INT32_MAX}.  The check and reset calls enqueue one kernel on `stream` (pny_finite_check_tensors and pny_finite_reset
+ * on the current device) and neither allocate, copy nor wait.  PNY_ERR_ARG: a NULL pointer with a count > 0, a negative
+ * count or group, n above the limit, a range outside the table, NULL or unaligned flags_dev. */
+#define PNY_FINITE_NAN 1
+#define PNY_FINITE_INF 2
+#define PNY_FINITE_MAX_IMMEDIATE 8
+typedef struct pny_finite pny_finite;
+int pny_finite_create(pny_finite** out, int device);
+void pny_finite_destroy(pny_finite* f);
+int pny_finite_add_tensor(pny_finite* f, const float* dev, int64_t count, int group);
+int pny_finite_check(pny_finite* f, int first, int n, int32_t* flags_dev, pny_stream stream);
+int pny_finite_check_tensors(const float* const* ptrs, const int64_t* counts, const int32_t* groups, int n, int32_t* flags_dev,
+                             pny_stream stream);
+int pny_finite_reset(int32_t* flags_dev, int n_groups, pny_stream stream);
 
 #ifdef __cplusplus
 }

@@ -833,6 +833,66 @@ int pny_sample_train_batch(const pny_train_batch_desc* d, const float* images_de
     return PNY_OK;
 }
 
+int pny_yolo_train_batch(const pny_yolo_batch_desc* d, const float* poses_host, const int64_t* view_ids_host, const float focal[2],
+                         const float c[2], const float* const* targets_dev, float* rays_dev, float* targets_out_dev,
+                         int64_t* offsets_host, pny_stream stream) {
+    const std::string who = "pny_yolo_train_batch: ";
+    if (!d || !offsets_host) return fail(PNY_ERR_ARG, who + "null argument");
+    const bool query = !rays_dev && !targets_out_dev;   // size query: offsets_host only
+    if (!query && (!poses_host || !view_ids_host || !focal || !c || !targets_dev || !rays_dev || !targets_out_dev))
+        return fail(PNY_ERR_ARG, who + "null argument");
+    if (d->n_scales < 1 || d->n_scales > PNY_YOLO_BATCH_MAX_SCALES) return fail(PNY_ERR_ARG, who + "n_scales must be 1 .. 4");
+    if (d->n_views < 1 || d->n_views > PNY_YOLO_BATCH_MAX_VIEWS)
+        return fail(PNY_ERR_ARG, who + "n_views must be 1 .. 16 (one launch carries at most 16 selected cameras)");
+    if (d->n_views_all < 1 || d->height < 1 || d->width < 1) return fail(PNY_ERR_ARG, who + "bad shape");
+    if (d->n_anchors < 1 || d->n_anchors > 64) return fail(PNY_ERR_ARG, who + "bad shape: n_anchors must be 1 .. 64");
+    if ((reinterpret_cast<uintptr_t>(rays_dev) & 15) || (reinterpret_cast<uintptr_t>(targets_out_dev) & 3))
+        return fail(PNY_ERR_ARG, who + "rays_dev must be 16-byte aligned (targets_out_dev 4-byte)");
+    YoloBatchArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_scales = d->n_scales, a.row = d->n_anchors * 6;
+    a.znear = d->z_near, a.zfar = d->z_far;
+    a.rays = rays_dev, a.targets_out = targets_out_dev;
+    if (!query && (focal[0] == 0.f || focal[1] == 0.f)) return fail(PNY_ERR_ARG, who + "zero focal length");
+    for (int s = 0; s < d->n_scales; ++s) {
+        const int cell = d->cell_sizes[s];
+        if (cell < 1 || cell > d->height || cell > d->width)
+            return fail(PNY_ERR_ARG, who + "every cell size must be 1 .. min(height, width)");
+        a.hs[s] = d->height / cell, a.ws[s] = d->width / cell;
+        a.off[s + 1] = a.off[s] + (long long)d->n_views * a.hs[s] * a.ws[s];
+        if ((long long)d->n_views_all * a.hs[s] * a.ws[s] > INT32_MAX) return fail(PNY_ERR_ARG, who + "more than 2^31 - 1 cells in a grid");
+        if (query) continue;
+        if (!targets_dev[s] || (reinterpret_cast<uintptr_t>(targets_dev[s]) & 3)) return fail(PNY_ERR_ARG, who + "null or unaligned target grid");
+        a.targets[s] = targets_dev[s];
+        // the scale's intrinsics in fp32 (YoloTrainer.py:107-108), then Kinv's entries exactly as pny_gen_rays_range forms them
+        const float fx = focal[0] / (float)cell, fy = focal[1] / (float)cell, cx = c[0] / (float)cell, cy = c[1] / (float)cell;
+        a.kinv[s][0] = (float)(1.0 / fx);
+        a.kinv[s][1] = (float)(1.0 / fy);
+        a.kinv[s][2] = (float)(-(double)cx / fx);
+        a.kinv[s][3] = (float)(-(double)cy / fy);
+    }
+    if (a.off[d->n_scales] * a.row > INT32_MAX) return fail(PNY_ERR_ARG, who + "more than 2^31 - 1 target values");
+    if (query) {
+        for (int s = 0; s <= d->n_scales; ++s) offsets_host[s] = a.off[s];
+        return PNY_OK;
+    }
+    for (int i = 0; i < d->n_views; ++i) {
+        const int64_t v = view_ids_host[i];
+        if (v < 0 || v >= d->n_views_all) return fail(PNY_ERR_ARG, who + "view id outside [0, n_views_all)");
+        double inv[16];
+        if (!invert4(poses_host + 16 * v, inv)) return fail(PNY_ERR_ARG, who + "singular extrinsic matrix");
+        for (int r = 0; r < 3; ++r) {
+            for (int q = 0; q < 3; ++q) a.pose[i][3 * r + q] = (float)inv[4 * r + q];
+            a.pose[i][9 + r] = (float)inv[4 * r + 3];
+        }
+        a.view_id[i] = (int)v;
+    }
+    for (int s = 0; s <= d->n_scales; ++s) offsets_host[s] = a.off[s];
+    launch_yolo_train_batch(a, (hipStream_t)stream);
+    PNY_HIP(hipGetLastError());
+    return PNY_OK;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------- MLP launch

@@ -280,6 +280,20 @@ struct TrainBatchArgs {
     int32_t* pix;                             // may be null
 };
 void launch_train_batch(const TrainBatchArgs& a, hipStream_t st);
+// yolo_train_batch_kernel's argument block (render_kernels.hip): the selected cameras and the scales' intrinsics by value
+// (1 KB of the kernel-argument segment: nothing is staged on the device), the grids and the outputs as device pointers
+struct YoloBatchArgs {
+    float pose[PNY_YOLO_BATCH_MAX_VIEWS][12];    // selected view i: M 3x3 row-major (camera direction -> world), origin(3)
+    float kinv[PNY_YOLO_BATCH_MAX_SCALES][4];    // scale s: 1/fx, 1/fy, -cx/fx, -cy/fy of (focal / cell, c / cell), as gen_rays' cam16[12..15]
+    int view_id[PNY_YOLO_BATCH_MAX_VIEWS];       // selected view i -> its index in the (NV, ...) target grids
+    int hs[PNY_YOLO_BATCH_MAX_SCALES], ws[PNY_YOLO_BATCH_MAX_SCALES];
+    long long off[PNY_YOLO_BATCH_MAX_SCALES + 1];   // scale s owns rays [off[s], off[s + 1]); off[n_scales] = R
+    const float* targets[PNY_YOLO_BATCH_MAX_SCALES];   // (NV, hs, ws, row)
+    int n_scales, row;                           // row = A * 6 floats per cell
+    float znear, zfar;
+    float *rays, *targets_out;                   // (R, 8), (R, row)
+};
+void launch_yolo_train_batch(const YoloBatchArgs& a, hipStream_t st);
 void launch_nchw_to_nhwc(const float* in, float* out, int n, int c, int hw, hipStream_t st);
 void launch_nhwc_to_nchw(const float* in, float* out, int n, int c, int hw, hipStream_t st);
 

@@ -313,6 +313,14 @@ __device__ __forceinline__ void pinhole_dir(const float* c, int x, int y, float&
     d1 /= nrm;
     d2 /= nrm;
 }
+// The same for yolo=1: Kinv [x + .49, y + .49, 1], not normalised (c[12..15] hold the entries of Kinv).  One copy for
+// gen_rays_kernel and yolo_train_batch_kernel.
+__device__ __forceinline__ void yolo_dir(const float* c, int x, int y, float& d0, float& d1, float& d2) {
+    const float px = (float)x + 0.49f, py = (float)y + 0.49f;
+    d0 = c[12] * px + c[14];
+    d1 = c[13] * py + c[15];
+    d2 = 1.0f;
+}
 __device__ __forceinline__ void store_ray(const float* c, float d0, float d1, float d2, float znear, float zfar,
                                           float* row) {
     float4* o = reinterpret_cast<float4*>(row);  // hipMalloc / torch allocations: rows are 32-byte aligned
@@ -332,14 +340,10 @@ __global__ void gen_rays_kernel(const GenRaysCams cams, int img0, int w, int h, 
     const int y = pix / w, x = pix - y * w;
     const float* c = cams.cam[img - img0];
     float d0, d1, d2;
-    if (!yolo) {
+    if (!yolo)
         pinhole_dir(c, x, y, d0, d1, d2);
-    } else {
-        const float px = (float)x + 0.49f, py = (float)y + 0.49f;
-        d0 = c[12] * px + c[14];
-        d1 = c[13] * py + c[15];
-        d2 = 1.0f;
-    }
+    else
+        yolo_dir(c, x, y, d0, d1, d2);
     store_ray(c, d0, d1, d2, znear, zfar, out + i * 8);
 }
 
@@ -422,6 +426,61 @@ void launch_train_batch(const TrainBatchArgs& a, hipStream_t st) {
     const long long n = (long long)a.sb * a.b;
     if (n <= 0) return;
     hipLaunchKernelGGL(train_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+}
+
+// ------------------------------------------------------------------ YOLO training batch
+// What YoloTrainer.calc_losses:93-129 of the reference prepares per scale -- gen_rays_yolo of the selected views at the
+// scale's grid size, the target grids indexed by image_ord, both flattened -- for all scales and views at once.  Rows are
+// ordered (scale, position in view_ids, y, x); thread r computes ray r with gen_rays_kernel's arithmetic (yolo_dir, store_ray:
+// the same bits as that pixel of a per-scale gen_rays call with the scale's Kinv).  The targets need no per-cell index: the
+// cells of one (scale, selected view) are contiguous in the grid AND in the output, hs * ws * row floats each, so the gather
+// is n_scales * NS segment copies; element e of the flat (R, row) output is located from its row and copied by thread
+// e mod (grid size), a coalesced 4-byte stream on both sides.  (A segment starts at a multiple of `row` floats -- 72 bytes
+// for three anchors -- so source and destination do not share a 16-byte phase in general; the copy is a few hundred KB at
+// most, and 4-byte accesses are aligned for every A.)
+__device__ __forceinline__ int yolo_batch_scale(const YoloBatchArgs& a, long long r) {
+    int s = 0;
+#pragma unroll
+    for (int k = 1; k < PNY_YOLO_BATCH_MAX_SCALES; ++k) s += (k < a.n_scales && r >= a.off[k]) ? 1 : 0;
+    return s;
+}
+
+__global__ __launch_bounds__(256) void yolo_train_batch_kernel(const YoloBatchArgs a) {
+    const long long R = a.off[a.n_scales];
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < R) {
+        const int s = yolo_batch_scale(a, t);
+        const int per = a.hs[s] * a.ws[s];
+        const long long q = t - a.off[s];
+        const int i = (int)(q / per);
+        const int pix = (int)(q - (long long)i * per);
+        const int y = pix / a.ws[s], x = pix - y * a.ws[s];
+        float c[16];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) c[k] = a.pose[i][k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c[12 + k] = a.kinv[s][k];
+        float d0, d1, d2;
+        yolo_dir(c, x, y, d0, d1, d2);
+        store_ray(c, d0, d1, d2, a.znear, a.zfar, a.rays + t * 8);
+    }
+    const long long total = R * a.row, stride = (long long)gridDim.x * blockDim.x;
+    for (long long e = t; e < total; e += stride) {
+        const long long r = e / a.row;
+        const int k = (int)(e - r * a.row);
+        const int s = yolo_batch_scale(a, r);
+        const int per = a.hs[s] * a.ws[s];
+        const long long q = r - a.off[s];
+        const int i = (int)(q / per);
+        const long long cell = (long long)a.view_id[i] * per + (q - (long long)i * per);
+        a.targets_out[e] = a.targets[s][cell * a.row + k];
+    }
+}
+
+void launch_yolo_train_batch(const YoloBatchArgs& a, hipStream_t st) {
+    const long long n = a.off[a.n_scales];
+    if (n <= 0) return;
+    hipLaunchKernelGGL(yolo_train_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
 }
 
 // ------------------------------------------------------------------ layout repack

@@ -66,6 +66,12 @@ class TrainBatchDraws(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("pix_inds_dev", "image_ids_dev", "u_x_dev", "u_y_dev")]
 
 
+class YoloBatchDesc(C.Structure):
+    _fields_ = [("n_views_all", C.c_int32), ("n_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("n_scales", C.c_int32), ("cell_sizes", C.c_int32 * 4), ("n_anchors", C.c_int32), ("z_near", C.c_float),
+                ("z_far", C.c_float)]
+
+
 class RgbLossDesc(C.Structure):
     _fields_ = [("use_l1_coarse", C.c_int32), ("use_l1_fine", C.c_int32), ("lambda_coarse", C.c_float), ("lambda_fine", C.c_float)]
 
@@ -102,6 +108,8 @@ SIGNATURES = {
                                      C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "pny_sample_train_batch": (C.c_int, [C.POINTER(TrainBatchDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(TrainBatchDraws), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pny_yolo_train_batch": (C.c_int, [C.POINTER(YoloBatchDesc), C.c_void_p, c_i64_p, c_float_p, c_float_p, C.POINTER(C.c_void_p),
+                                       C.c_void_p, C.c_void_p, c_i64_p, C.c_void_p]),
     "pny_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "pny_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(RenderOpts), C.POINTER(RenderOut),
                              C.c_void_p]),
@@ -159,6 +167,12 @@ SIGNATURES = {
                                C.c_void_p, C.c_void_p]),
     "pny_yolo_loss": (C.c_int, [C.POINTER(YoloLossDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]),
+    "pny_finite_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
+    "pny_finite_destroy": (None, [C.c_void_p]),
+    "pny_finite_add_tensor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
+    "pny_finite_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pny_finite_check_tensors": (C.c_int, [C.POINTER(C.c_void_p), c_i64_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p]),
+    "pny_finite_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
 }
 
 _lib = None
@@ -170,6 +184,8 @@ LAST_PRECISION = {0: "f32", 1: "f16x2", 2: "f16"}   # pny_scene_last_precision, 
 
 
 RANGE_BITS = {1: "activation", 2: "gradient", 4: "weight"}   # include/pnyolo.h PNY_RANGE_*
+YOLO_BATCH_MAX_VIEWS, YOLO_BATCH_MAX_SCALES = 16, 4           # PNY_YOLO_BATCH_MAX_*
+FINITE_NAN, FINITE_INF, FINITE_MAX_IMMEDIATE = 1, 2, 8        # PNY_FINITE_*
 
 
 class PnyError(RuntimeError):

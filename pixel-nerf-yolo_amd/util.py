@@ -3,7 +3,9 @@ Ray generation and the YOLO detection tail with the reference's signatures (src/
 :808-876 ``gen_rays_yolo``), executed by libpnyolo's gen_rays kernel.  Output lives on a CUDA
 device (that of ``poses``, or the current one when ``poses`` is a CPU tensor as at the reference's call sites).
 ``sample_train_batch`` is the trainer's ray batch and ground truth in one launch (no counterpart function in the reference:
-it replaces the per-object loop of train/trainlib/PixelNerfTrainer.py:76-123).
+it replaces the per-object loop of train/trainlib/PixelNerfTrainer.py:76-123).  ``yolo_train_batch`` /
+``stage_yolo_targets`` and ``FiniteMonitor`` are the same for the YOLO trainer: the batch of train/trainlib/YoloTrainer.py:93-129
+in one launch, and its NaN / Inf tests (:163-194) without a host wait.
 """
 import ctypes as C
 
@@ -156,6 +158,186 @@ def sample_train_batch(images, poses, focal, z_near, z_far, ray_batch_size, c=No
                                              None if dr is None else C.byref(dr), ptr(rays), ptr(rgb_gt),
                                              C.c_void_p(pix.data_ptr()), stream_of(dev)))
     return rays, rgb_gt, pix
+
+
+# ------------------------------------------------------------------ YOLO training batch
+def stage_yolo_targets(all_bboxes, device):
+    """
+    The dataset's target grids on the device, one tensor per scale: ``all_bboxes`` is data["bboxes"] as the reference's
+    trainer receives it -- an NV-long list of num_scales-long tuples of (1, Hs, Ws, A, 6) tensors -- and the result a
+    num_scales-long list of (NV, Hs, Ws, A, 6) fp32 tensors on ``device``, what YoloTrainer.py:97-101 builds per scale.  One
+    stack on the host and ONE copy per scale instead of NV * num_scales copies.
+    """
+    dev = torch.device(device)
+    out = []
+    for s in range(len(all_bboxes[0])):
+        grid = torch.stack([torch.as_tensor(view[s]) for view in all_bboxes]).squeeze(1)
+        out.append(grid.to(dev, torch.float32, non_blocking=True).contiguous())
+    return out
+
+
+def yolo_train_batch(poses, view_ids, focal, c, targets, height, width, cell_sizes, z_near, z_far, device=None):
+    """
+    The rays and target cells of one YOLO training step for one object, over all scales and selected views, in one kernel
+    launch: what the reference's YoloTrainer.calc_losses:93-129 prepares per scale (gen_rays_yolo at the scale's grid size,
+    the grids indexed by image_ord, both flattened).
+
+    :param poses (NV, 4, 4) world-to-camera extrinsics of all views of the object, on the CPU as the dataset gives them
+    :param view_ids (NS,) the object's row of image_ord: 1 .. 16 view indices, any order, repeats allowed
+    :param focal (2), c (2) full-resolution intrinsics; a scale uses focal / cell and c / cell
+    :param targets num_scales device tensors (NV, H // cell, W // cell, A, 6): stage_yolo_targets
+    :return (rays_per_scale, targets_per_scale): lists of views (NS * Hs * Ws, 8) and (NS * Hs * Ws, A, 6) into two flat
+            buffers, rows ordered (position in view_ids, y, x).  torch.split(rays_per_scale[s].unsqueeze(0), ray_batch_size,
+            dim=1) gives the trainer's mini-batches.
+    """
+    dev = _device_of(targets[0], device)
+    cells = [int(v) for v in cell_sizes]
+    ids = torch.as_tensor(view_ids, dtype=torch.int64).detach().cpu().reshape(-1).contiguous()
+    assert 1 <= len(cells) <= _lib.YOLO_BATCH_MAX_SCALES and len(targets) == len(cells), "one target grid per scale, 1 .. 4 scales"
+    NV, NS, A = poses.shape[0], ids.numel(), targets[0].shape[3]
+    grids = []
+    for t, cell in zip(targets, cells):
+        assert t.device == dev and t.dtype == torch.float32 and t.is_contiguous(), "targets: contiguous fp32 on the device"
+        assert 1 <= cell <= min(height, width) and tuple(t.shape) == (NV, height // cell, width // cell, A, 6), \
+            "a target grid is (NV, H // cell, W // cell, A, 6)"
+        grids.append(t.data_ptr())
+    off = [0]
+    for cell in cells:
+        off.append(off[-1] + NS * (height // cell) * (width // cell))
+    desc = _lib.YoloBatchDesc(n_views_all=NV, n_views=NS, height=int(height), width=int(width), n_scales=len(cells),
+                              cell_sizes=(C.c_int32 * 4)(*cells), n_anchors=A, z_near=float(z_near), z_far=float(z_far))
+    p = poses.detach().to("cpu", torch.float32).contiguous()
+    rays = torch.empty(off[-1], 8, device=dev, dtype=torch.float32)
+    tout = torch.empty(off[-1], A, 6, device=dev, dtype=torch.float32)
+    got = (C.c_int64 * (len(cells) + 1))()
+    with torch.cuda.device(dev):
+        check(_lib.load().pny_yolo_train_batch(C.byref(desc), ptr(p), C.cast(ids.data_ptr(), _lib.c_i64_p), _pair(focal, "focal"),
+                                               _pair(c, "c"), (C.c_void_p * len(grids))(*grids), ptr(rays), ptr(tout), got,
+                                               stream_of(dev)))
+    assert list(got) == off
+    return [rays[a:b] for a, b in zip(off, off[1:])], [tout[a:b] for a, b in zip(off, off[1:])]
+
+
+class FiniteMonitor:
+    """
+    The NaN / Inf tests of a training step without a host wait (include/pnyolo.h pny_finite_*): every ``check`` is one kernel
+    launch that ORs what it finds into two int32 words per group on the device, and ``report`` is the step's single read.
+    Replaces the reference's `if torch.isnan(x).any()` / `torch.isinf(x).any()` tests (YoloTrainer.py:163-194).
+
+        mon = FiniteMonitor(("render", "targets", "grads"), device)
+        mon.watch("grads", list(net.parameters()), names, grads=True)
+        ... per mini-batch:  mon.check("render", render); mon.check("targets", bboxes_gt); loss.backward(); mon.check("grads")
+        ... per step:        bad = mon.report(); mon.reset()
+
+    Tensors are contiguous fp32 on the monitor's device.  A group is either watched or checked with tensors given in the
+    call, not both: `first` is a row of the registered table for the one and a position in the call for the other.
+    """
+
+    def __init__(self, groups, device):
+        self.groups = list(groups)
+        assert len(set(self.groups)) == len(self.groups) and self.groups, "group names must be distinct"
+        self.device = _device_of(torch.empty(0), device)
+        if self.device.index is None:                      # "cuda": the current device, by its index (tensors carry one)
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.flags = torch.empty(len(self.groups), 2, device=self.device, dtype=torch.int32)   # [bits, first] per group
+        self._watched = {}     # group -> dict(tensors, names, grads, ptrs, first)
+        self._names = {}       # table index -> name (this handle)
+        self._h = None
+        self._new_handle()
+        self.reset()
+
+    def _new_handle(self):
+        L = _lib.load()
+        if self._h is not None:
+            L.pny_finite_destroy(self._h)
+        self._h = C.c_void_p()
+        check(L.pny_finite_create(C.byref(self._h), self.device.index))
+        self._names, self._rows = {}, 0
+        for w in self._watched.values():
+            w["ptrs"] = None
+
+    def close(self):
+        if self._h is not None:
+            _lib.load().pny_finite_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _buffers(self, w):
+        ts = [(t.grad if w["grads"] else t) for t in w["tensors"]]
+        for t in ts:
+            assert t is None or (t.device == self.device and t.dtype == torch.float32 and t.is_contiguous()), \
+                "FiniteMonitor takes contiguous fp32 tensors on its device"
+        return ts
+
+    def watch(self, group, tensors, names=None, grads=False):
+        """Registers the buffers `check(group)` scans.  grads=True: the buffer of each tensor is its `.grad` at the time of
+        the check (None: nothing to scan).  names: what `report` calls them (default: their position)."""
+        tensors = list(tensors)
+        names = [str(n) for n in names] if names is not None else ["%s[%d]" % (group, i) for i in range(len(tensors))]
+        assert len(names) == len(tensors)
+        self._watched[group] = dict(tensors=tensors, names=names, grads=bool(grads), ptrs=None, first=0)
+
+    def _register(self, group, w, bufs, ptrs):
+        L = _lib.load()
+        g = self.groups.index(group)
+        w["first"] = self._rows
+        for t, name in zip(bufs, w["names"]):
+            i = L.pny_finite_add_tensor(self._h, None if t is None else C.c_void_p(t.data_ptr()), 0 if t is None else t.numel(), g)
+            if i < 0:
+                check(i)
+            self._names[i] = name
+            self._rows = i + 1
+        w["ptrs"] = ptrs
+
+    def check(self, group, *tensors):
+        """check(group, t0, t1, ...): scans up to 8 tensors now.  check(group): scans the watched buffers of the group, which
+        are registered again first when one of them has moved (a new .grad after zero_grad(set_to_none=True))."""
+        L = _lib.load()
+        g = self.groups.index(group)
+        with torch.cuda.device(self.device):
+            if tensors:
+                assert group not in self._watched, "group %r is watched: check it without tensors" % (group,)
+                assert len(tensors) <= _lib.FINITE_MAX_IMMEDIATE, "at most 8 tensors per immediate check: watch() larger sets"
+                n = len(tensors)
+                for t in tensors:
+                    assert t.device == self.device and t.dtype == torch.float32 and t.is_contiguous(), \
+                        "FiniteMonitor takes contiguous fp32 tensors on its device"
+                check(L.pny_finite_check_tensors((C.c_void_p * n)(*[t.data_ptr() for t in tensors]),
+                                                 (C.c_int64 * n)(*[t.numel() for t in tensors]), (C.c_int32 * n)(*([g] * n)), n,
+                                                 C.c_void_p(self.flags.data_ptr()), stream_of(self.device)))
+                return
+            w = self._watched[group]
+            bufs = self._buffers(w)
+            ptrs = [(0, 0) if t is None else (t.data_ptr(), t.numel()) for t in bufs]
+            if ptrs != w["ptrs"]:
+                self._register(group, w, bufs, ptrs)
+            check(L.pny_finite_check(self._h, w["first"], len(bufs), C.c_void_p(self.flags.data_ptr()), stream_of(self.device)))
+
+    def reset(self):
+        """Clears the flags (one launch).  Also the moment a table that re-registration has grown is started afresh: no flag
+        word refers to an old row then."""
+        live = sum(len(w["tensors"]) for w in self._watched.values())
+        if self._rows > 4 * live + 64:
+            self._new_handle()
+        with torch.cuda.device(self.device):
+            check(_lib.load().pny_finite_reset(C.c_void_p(self.flags.data_ptr()), len(self.groups), stream_of(self.device)))
+
+    def report(self):
+        """The step's one device-to-host read -> {group: (has_nan, has_inf, name of the first tensor hit or None)}.  For a
+        watched group the name is the watched tensor's; for immediate checks it is `group[i]`, i the position in the call."""
+        words = self.flags.cpu().tolist()
+        out = {}
+        for group, (bits, first) in zip(self.groups, words):
+            name = None
+            if bits:
+                name = self._names.get(first) if group in self._watched else "%s[%d]" % (group, first)
+            out[group] = (bool(bits & _lib.FINITE_NAN), bool(bits & _lib.FINITE_INF), name)
+        return out
 
 
 # ------------------------------------------------------------------ YOLO detection tail
