@@ -16,14 +16,61 @@ struct ConvLayer {
     int cin = 0, cin_p = 0, cout = 0, k = 0, stride = 1, pad = 0, J = 0;
 };
 
+// ---------------------------------------------------------------------------------- the trunk, described once
+// torchvision's ResNet-34 up to layer3 as its convolution + batch-norm units in execution order: the stem, then per BasicBlock
+// [downsample,] conv1, conv2.  Inference (encoder.hip) and training (encoder_train.hip) both walk this table:
+//   downsample  idt = bn(conv(x))              (else idt = x)
+//   conv1       a   = relu(bn(conv(x)))
+//   conv2       x   = relu(bn(conv(a)) + idt); the last unit of a level is that level's output
+enum class TrunkRole { stem, downsample, conv1, conv2 };
+struct TrunkConv {
+    std::string conv, bn;   // state-dict names below the trunk's prefix ("layer2.0.conv1", "layer2.0.bn1")
+    int cin, cout, k, stride, pad;
+    int level;              // pyramid level 1..3, 0 for the stem
+    TrunkRole role;
+    bool level_end;         // its output is the level's output
+};
+const std::vector<TrunkConv>& trunk_table();   // built once
+ConvLayer conv_geometry(const TrunkConv& c);   // a unit as conv_mfma_kernel runs it: ci padded to fours, K to eights; no operands yet
+
+// pyramid level channels and their offsets in the 512-channel latent
+constexpr int TRUNK_CH[4] = {64, 64, 128, 256}, TRUNK_COFF[4] = {0, 64, 128, 256}, TRUNK_LATENT = 512;
+struct Pyramid {
+    int h[4], w[4];
+};
+Pyramid pyramid(int height, int width, bool use_first_pool);
+int conv_out(int in, int k, int s, int p);
+void encoder_latent_size(int height, int width, int* hl, int* wl);
+
+// Packed A operand of a convolution, [rows/32][J][64][4]: element r of lane l in k-iteration j of row tile nt is row
+// n = 32 nt + (l & 31), reduction index kk = 8 j + 4 (l >> 5) + r.  These give its source offset in the (cout, cin, k, k)
+// weight tensor, or -1 where the operand is zero padding.
+//   forward image:    rows = co, K = (ky, kx, ci) with ci padded to cin_p
+//   transposed image: rows = ci, K = (ky', kx', co) with FLIPPED taps, W_t[ci][(ky', kx', co)] = W[co][ci][k-1-ky'][k-1-kx']
+__host__ __device__ inline long long conv_pack_src(int n, int kk, int cin, int cin_p, int k) {
+    const int tap = kk / cin_p, ci = kk - tap * cin_p;
+    return tap < k * k && ci < cin ? ((long long)n * cin + ci) * (k * k) + tap : -1;
+}
+__host__ __device__ inline long long conv_pack_src_t(int n, int kk, int cin, int cout, int k) {
+    const int tap = kk / cout, co = kk - tap * cout;
+    return tap < k * k ? ((long long)co * cin + n) * (k * k) + (k * k - 1 - tap) : -1;
+}
+
+// Lays buffers of floats out in one allocation, each rounded up to 64 floats.  With a null base it only counts: the sizing and
+// the carving of a workspace are one pass.
+struct Carver {
+    float* base = nullptr;
+    size_t off = 0;
+    float* take(size_t count) {
+        float* p = base ? base + off : nullptr;
+        off += (count + 63) & ~(size_t)63;
+        return p;
+    }
+};
+
+// Inference weights: one folded conv + bn layer per entry of trunk_table(), in its order
 struct EncoderWeights {
-    ConvLayer conv1;
-    // layer1..3: per block conv1, conv2 and optional downsample
-    struct Block {
-        ConvLayer c1, c2, ds;
-        bool has_ds = false;
-    };
-    std::vector<Block> layers[3];
+    std::vector<ConvLayer> convs;
     std::vector<float*> allocs;
     using Getter = std::function<bool(const std::string&, const float**, std::vector<int64_t>*)>;
     bool build(const Getter& get, const std::string& prefix, std::string* err);
@@ -41,8 +88,14 @@ bool run_pixel_linear(const ConvLayer& L, const float* in, long long npix, float
 // hout / wout explicit; dil_shift > 0 reads the input as if 2^dil_shift - 1 zeros stood between its samples.
 bool run_conv_ex(const ConvLayer& L, const float* in, int n, int hin, int win, int hout, int wout, int dil_shift, const float* resid,
                  int relu, float* out, hipStream_t st);
-int conv_out(int in, int k, int s, int p);
-void encoder_latent_size(int height, int width, int* hl, int* wl);
+// The trunk's other forward kernels (encoder.hip), shared by inference and training:
+// images (n,3,H,W) NCHW -> (n,H,W,4) channel-last with a zero 4th channel
+void launch_image_to_nhwc4(const float* images, float* out, int n, int height, int width, hipStream_t st);
+// max_pool2d(3, stride 2, pad 1) in front of layer1: level 0 of the pyramid -> level 1's size
+void launch_first_pool(const float* l0, float* out, int n, const Pyramid& d, hipStream_t st);
+// every pyramid level resampled (bilinear, align_corners=True) to level 0's size into the channel-last latent
+void launch_pyramid_to_latent(const float* const level_out[4], float* latent_nhwc, int n, const Pyramid& d, hipStream_t st);
+
 size_t encoder_workspace_bytes(int ns, int height, int width, bool use_first_pool);
 // images (ns,3,H,W) NCHW -> latent (ns, H0, W0, 512) channel-last
 bool encoder_forward(const EncoderWeights& w, const float* images, int ns, int height, int width, bool use_first_pool,

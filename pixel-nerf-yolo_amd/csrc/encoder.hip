@@ -510,15 +510,16 @@ static bool upload(const std::vector<float>& v, float** out, std::vector<float*>
     return true;
 }
 
-static bool build_conv(const EncoderWeights::Getter& get, const std::string& conv, const std::string& bn, int cin,
-                       int cout, int k, int stride, int pad, ConvLayer& L, std::vector<float*>& allocs,
-                       std::string* err) {
+static bool build_conv(const EncoderWeights::Getter& get, const std::string& pre, const TrunkConv& c, ConvLayer& L,
+                       std::vector<float*>& allocs, std::string* err) {
+    const int cin = c.cin, cout = c.cout, k = c.k;
     const float* w = nullptr;
     std::vector<int64_t> shp;
-    if (!get(conv + ".weight", &w, &shp) || shp != std::vector<int64_t>{cout, cin, k, k}) {
-        *err = "missing or mis-shaped '" + conv + ".weight'";
+    if (!get(pre + c.conv + ".weight", &w, &shp) || shp != std::vector<int64_t>{cout, cin, k, k}) {
+        *err = "missing or mis-shaped '" + pre + c.conv + ".weight'";
         return false;
     }
+    const std::string bn = pre + c.bn;
     const float *g = nullptr, *b = nullptr, *mu = nullptr, *var = nullptr;
     std::vector<int64_t> s1;
     if (!get(bn + ".weight", &g, &s1) || !get(bn + ".bias", &b, &s1) || !get(bn + ".running_mean", &mu, &s1) ||
@@ -526,33 +527,23 @@ static bool build_conv(const EncoderWeights::Getter& get, const std::string& con
         *err = "missing or mis-shaped batch-norm tensors '" + bn + ".*'";
         return false;
     }
-    L.cin = cin;
-    L.cin_p = (cin + 3) / 4 * 4;
-    L.cout = cout;
-    L.k = k;
-    L.stride = stride;
-    L.pad = pad;
-    const int K = k * k * L.cin_p;
-    L.J = (K + 7) / 8;
-    // K order (ky, kx, ci); A-operand lane order, n-tile-major as pack.hip PACK_NT
+    L = conv_geometry(c);
+    // A-operand lane order, n-tile-major as pack.hip PACK_NT
     std::vector<float> pk((size_t)(cout / 32) * L.J * 64 * 4);
     size_t o = 0;
     for (int nt = 0; nt < cout / 32; ++nt)
         for (int j = 0; j < L.J; ++j)
             for (int l = 0; l < 64; ++l)
                 for (int r = 0; r < 4; ++r) {
-                    const int n = 32 * nt + (l & 31), kk = 8 * j + 4 * (l >> 5) + r;
-                    const int tap = kk / L.cin_p, ci = kk % L.cin_p;
-                    float val = 0.f;
-                    if (tap < k * k && ci < cin) val = w[(((size_t)n * cin + ci) * k + tap / k) * k + tap % k];
-                    pk[o++] = val;
+                    const long long src = conv_pack_src(32 * nt + (l & 31), 8 * j + 4 * (l >> 5) + r, cin, L.cin_p, k);
+                    pk[o++] = src >= 0 ? w[src] : 0.f;
                 }
     std::vector<float> sc(cout), sh(cout);
-    for (int c = 0; c < cout; ++c) {
+    for (int ch = 0; ch < cout; ++ch) {
         // ATen's inference batch norm: alpha = weight / sqrt(var + eps); beta = bias - mean * alpha
-        const float invstd = 1.0f / std::sqrt(var[c] + 1e-5f);
-        sc[c] = g[c] * invstd;
-        sh[c] = b[c] - mu[c] * sc[c];
+        const float invstd = 1.0f / std::sqrt(var[ch] + 1e-5f);
+        sc[ch] = g[ch] * invstd;
+        sh[ch] = b[ch] - mu[ch] * sc[ch];
     }
     return upload(pk, &L.w, allocs, err) && upload(sc, &L.scale, allocs, err) && upload(sh, &L.shift, allocs, err);
 }
@@ -579,35 +570,50 @@ bool build_pixel_linear(int nmat, int rows, int k, ConvLayer* out, std::vector<f
     return upload(one, &L.scale, *allocs, err) && upload(zero, &L.shift, *allocs, err);
 }
 
+const std::vector<TrunkConv>& trunk_table() {
+    static const std::vector<TrunkConv> table = [] {
+        std::vector<TrunkConv> t;
+        t.push_back({"conv1", "bn1", 3, 64, 7, 2, 3, 0, TrunkRole::stem, true});
+        const int nblk[3] = {3, 4, 6};   // BasicBlocks of layer1..3; their widths are the pyramid's
+        for (int lv = 1; lv <= 3; ++lv)
+            for (int b = 0; b < nblk[lv - 1]; ++b) {
+                const std::string p = "layer" + std::to_string(lv) + "." + std::to_string(b) + ".";
+                const int cout = TRUNK_CH[lv], cin = b == 0 ? TRUNK_CH[lv - 1] : cout;
+                const int stride = (b == 0 && lv > 1) ? 2 : 1;
+                if (stride != 1 || cin != cout) t.push_back({p + "downsample.0", p + "downsample.1", cin, cout, 1, stride, 0, lv, TrunkRole::downsample, false});
+                t.push_back({p + "conv1", p + "bn1", cin, cout, 3, stride, 1, lv, TrunkRole::conv1, false});
+                t.push_back({p + "conv2", p + "bn2", cout, cout, 3, 1, 1, lv, TrunkRole::conv2, b + 1 == nblk[lv - 1]});
+            }
+        return t;
+    }();
+    return table;
+}
+
+ConvLayer conv_geometry(const TrunkConv& c) {
+    ConvLayer L;
+    L.cin = c.cin;
+    L.cin_p = (c.cin + 3) / 4 * 4;
+    L.cout = c.cout;
+    L.k = c.k;
+    L.stride = c.stride;
+    L.pad = c.pad;
+    L.J = (c.k * c.k * L.cin_p + 7) / 8;
+    return L;
+}
+
 bool EncoderWeights::build(const Getter& get, const std::string& pre, std::string* err) {
     release();
-    if (!build_conv(get, pre + "conv1", pre + "bn1", 3, 64, 7, 2, 3, conv1, allocs, err)) return false;
-    const int couts[3] = {64, 128, 256}, nblk[3] = {3, 4, 6};
-    int cin = 64;
-    for (int li = 0; li < 3; ++li) {
-        layers[li].clear();
-        for (int b = 0; b < nblk[li]; ++b) {
-            Block blk;
-            const std::string p = pre + "layer" + std::to_string(li + 1) + "." + std::to_string(b) + ".";
-            const int stride = (b == 0 && li > 0) ? 2 : 1;
-            const int bc = (b == 0) ? cin : couts[li];
-            if (!build_conv(get, p + "conv1", p + "bn1", bc, couts[li], 3, stride, 1, blk.c1, allocs, err)) return false;
-            if (!build_conv(get, p + "conv2", p + "bn2", couts[li], couts[li], 3, 1, 1, blk.c2, allocs, err)) return false;
-            blk.has_ds = (b == 0 && (stride != 1 || bc != couts[li]));
-            if (blk.has_ds &&
-                !build_conv(get, p + "downsample.0", p + "downsample.1", bc, couts[li], 1, stride, 0, blk.ds, allocs, err))
-                return false;
-            layers[li].push_back(blk);
-        }
-        cin = couts[li];
-    }
+    const std::vector<TrunkConv>& table = trunk_table();
+    convs.resize(table.size());
+    for (size_t i = 0; i < table.size(); ++i)
+        if (!build_conv(get, pre, table[i], convs[i], allocs, err)) return false;
     return true;
 }
 
 void EncoderWeights::release() {
     for (float* p : allocs) (void)hipFree(p);
     allocs.clear();
-    for (auto& l : layers) l.clear();
+    convs.clear();
 }
 
 int conv_out(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
@@ -617,13 +623,9 @@ void encoder_latent_size(int height, int width, int* hl, int* wl) {
     *wl = conv_out(width, 7, 2, 3);
 }
 
-struct Dims {
-    int h[4], w[4];
-};
-static Dims pyramid(int height, int width, bool use_first_pool) {
-    Dims d;
-    d.h[0] = conv_out(height, 7, 2, 3);
-    d.w[0] = conv_out(width, 7, 2, 3);
+Pyramid pyramid(int height, int width, bool use_first_pool) {
+    Pyramid d;
+    encoder_latent_size(height, width, &d.h[0], &d.w[0]);
     // reference encoder.py:145-146: the max-pool in front of layer1 is optional (sn64.conf skips it)
     d.h[1] = use_first_pool ? conv_out(d.h[0], 3, 2, 1) : d.h[0];
     d.w[1] = use_first_pool ? conv_out(d.w[0], 3, 2, 1) : d.w[0];
@@ -634,15 +636,23 @@ static Dims pyramid(int height, int width, bool use_first_pool) {
     return d;
 }
 
-static size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
+// The inference workspace: buffers of a level: [0],[2] alternate as block outputs ([1][0] first holds the pooled input),
+// [1] = conv1 output, [3] = downsampled identity
+struct EncoderWork {
+    float *img4, *l0, *buf[4][4];
+};
+static size_t encoder_layout(float* work, int ns, int height, int width, const Pyramid& d, EncoderWork* E) {
+    Carver c{work};
+    E->img4 = c.take((size_t)ns * height * width * 4);
+    E->l0 = c.take((size_t)ns * d.h[0] * d.w[0] * TRUNK_CH[0]);
+    for (int i = 1; i < 4; ++i)
+        for (int b = 0; b < 4; ++b) E->buf[i][b] = c.take((size_t)ns * d.h[i] * d.w[i] * TRUNK_CH[i]);
+    return c.off;
+}
 
 size_t encoder_workspace_bytes(int ns, int height, int width, bool use_first_pool) {
-    const Dims d = pyramid(height, width, use_first_pool);
-    size_t fl = align64((size_t)ns * height * width * 4);          // nhwc4 image
-    fl += align64((size_t)ns * d.h[0] * d.w[0] * 64);              // level 0
-    const int ch[4] = {64, 64, 128, 256};
-    for (int i = 1; i < 4; ++i) fl += 4 * align64((size_t)ns * d.h[i] * d.w[i] * ch[i]);  // x, tmp, out, ds
-    return fl * sizeof(float);
+    EncoderWork E;
+    return encoder_layout(nullptr, ns, height, width, pyramid(height, width, use_first_pool), &E) * sizeof(float);
 }
 
 static bool run_conv(const ConvLayer& L, const float* in, int n, int hin, int win, const float* resid, int relu,
@@ -729,67 +739,68 @@ bool run_pixel_linear(const ConvLayer& L, const float* in, long long npix, float
     return run_conv(L, in, 1, 1, (int)npix, nullptr, 0, out, st);
 }
 
+void launch_image_to_nhwc4(const float* images, float* out, int n, int height, int width, hipStream_t st) {
+    const long long npx = (long long)n * height * width;
+    hipLaunchKernelGGL(image_to_nhwc4_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, st, images, out, n, height * width);
+}
+
+void launch_first_pool(const float* l0, float* out, int n, const Pyramid& d, hipStream_t st) {
+    const long long npool = (long long)n * d.h[1] * d.w[1] * (TRUNK_CH[0] / 4);
+    hipLaunchKernelGGL(maxpool_kernel, dim3((unsigned)((npool + 255) / 256)), dim3(256), 0, st, l0, out, n, d.h[0], d.w[0], TRUNK_CH[0],
+                       d.h[1], d.w[1]);
+}
+
+void launch_pyramid_to_latent(const float* const level_out[4], float* lat, int n, const Pyramid& d, hipStream_t st) {
+    for (int lv = 0; lv < 4; ++lv) {   // identity for level 0
+        const long long np = (long long)n * d.h[0] * d.w[0] * (TRUNK_CH[lv] / 4);
+        hipLaunchKernelGGL(upsample_concat_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, level_out[lv], lat, n, d.h[lv],
+                           d.w[lv], TRUNK_CH[lv], d.h[0], d.w[0], TRUNK_LATENT, TRUNK_COFF[lv]);
+    }
+}
+
 bool encoder_forward(const EncoderWeights& W, const float* images, int ns, int height, int width, bool use_first_pool,
                      float* work, float* lat, hipStream_t st, std::string* err) {
-    const Dims d = pyramid(height, width, use_first_pool);
-    size_t off = 0;
-    auto carve = [&](size_t n) {
-        float* p = work + off;
-        off += align64(n);
-        return p;
-    };
-    float* img4 = carve((size_t)ns * height * width * 4);
-    float* l0 = carve((size_t)ns * d.h[0] * d.w[0] * 64);
-    const int ch[4] = {64, 64, 128, 256};
-    float* buf[4][4];
-    for (int i = 1; i < 4; ++i)
-        for (int b = 0; b < 4; ++b) buf[i][b] = carve((size_t)ns * d.h[i] * d.w[i] * ch[i]);
-
+    const Pyramid d = pyramid(height, width, use_first_pool);
+    EncoderWork E;
+    encoder_layout(work, ns, height, width, d, &E);
     auto bad = [&]() {
         *err = std::string("encoder kernel launch failed: ") + hipGetErrorString(hipGetLastError());
         return false;
     };
-    const long long npx = (long long)ns * height * width;
-    hipLaunchKernelGGL(image_to_nhwc4_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, st, images, img4, ns,
-                       height * width);
-    if (!run_conv(W.conv1, img4, ns, height, width, nullptr, 1, l0, st)) return bad();
-    if (use_first_pool) {
-        const long long npool = (long long)ns * d.h[1] * d.w[1] * 16;
-        hipLaunchKernelGGL(maxpool_kernel, dim3((unsigned)((npool + 255) / 256)), dim3(256), 0, st, l0, buf[1][0], ns,
-                           d.h[0], d.w[0], 64, d.h[1], d.w[1]);
-    }
+    const std::vector<TrunkConv>& table = trunk_table();
+    launch_image_to_nhwc4(images, E.img4, ns, height, width, st);
+    if (!run_conv(W.convs[0], E.img4, ns, height, width, nullptr, 1, E.l0, st)) return bad();
+    if (use_first_pool) launch_first_pool(E.l0, E.buf[1][0], ns, d, st);
 
-    const float* level_out[4] = {l0, nullptr, nullptr, nullptr};
-    const float* x = use_first_pool ? buf[1][0] : l0;
+    const float* level_out[4] = {E.l0, nullptr, nullptr, nullptr};
+    const float* x = use_first_pool ? E.buf[1][0] : E.l0;   // the current block's input
+    const float* idt = x;                                   // ... and its identity branch
     int hin = d.h[1], win = d.w[1];
-    for (int li = 0; li < 3; ++li) {
-        const int lv = li + 1;
-        // buffers of a level: [0],[2] alternate as block outputs ([1][0] first holds the pooled
-        // input), [1] = conv1 output, [3] = downsampled identity
-        for (size_t b = 0; b < W.layers[li].size(); ++b) {
-            const EncoderWeights::Block& B = W.layers[li][b];
-            const float* idt = x;
-            if (B.has_ds) {
-                if (!run_conv(B.ds, x, ns, hin, win, nullptr, 0, buf[lv][3], st)) return bad();
-                idt = buf[lv][3];
+    for (size_t i = 1; i < table.size(); ++i) {
+        const TrunkConv& c = table[i];
+        const ConvLayer& L = W.convs[i];
+        float* const* buf = E.buf[c.level];
+        switch (c.role) {
+            case TrunkRole::stem: break;
+            case TrunkRole::downsample:
+                if (!run_conv(L, x, ns, hin, win, nullptr, 0, buf[3], st)) return bad();
+                idt = buf[3];
+                break;
+            case TrunkRole::conv1:
+                if (!run_conv(L, x, ns, hin, win, nullptr, 1, buf[1], st)) return bad();
+                hin = conv_out(hin, L.k, L.stride, L.pad);
+                win = conv_out(win, L.k, L.stride, L.pad);
+                break;
+            case TrunkRole::conv2: {
+                float* dst = (x == buf[0]) ? buf[2] : buf[0];
+                if (!run_conv(L, buf[1], ns, hin, win, idt, 1, dst, st)) return bad();
+                x = idt = dst;
+                if (c.level_end) level_out[c.level] = x;
+                break;
             }
-            if (!run_conv(B.c1, x, ns, hin, win, nullptr, 1, buf[lv][1], st)) return bad();
-            const int ho = conv_out(hin, 3, B.c1.stride, 1), wo = conv_out(win, 3, B.c1.stride, 1);
-            float* dst = (x == buf[lv][0]) ? buf[lv][2] : buf[lv][0];
-            if (!run_conv(B.c2, buf[lv][1], ns, ho, wo, idt, 1, dst, st)) return bad();
-            x = dst;
-            hin = ho;
-            win = wo;
         }
-        level_out[lv] = x;
     }
-    // pyramid -> latent: every level resampled to level 0's size (identity for level 0)
-    const int coff[4] = {0, 64, 128, 256};
-    for (int lv = 0; lv < 4; ++lv) {
-        const long long np = (long long)ns * d.h[0] * d.w[0] * (ch[lv] / 4);
-        hipLaunchKernelGGL(upsample_concat_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st,
-                           level_out[lv], lat, ns, d.h[lv], d.w[lv], ch[lv], d.h[0], d.w[0], 512, coff[lv]);
-    }
+    launch_pyramid_to_latent(level_out, lat, ns, d, st);
     if (hipGetLastError() != hipSuccess) return bad();
     return true;
 }

@@ -32,9 +32,8 @@ namespace pny {
 typedef float f32x16t __attribute__((ext_vector_type(16)));
 
 // ------------------------------------------------------------------------------------------------ weight repack
-// kind 0: forward A-operand image [cout/32][J][64][4], K = (ky, kx, ci) padded to cin_p (encoder.hip build_conv);
-// kind 1: the transposed convolution's image: rows = ci (cin of the convolution), K = (ky', kx', co) with FLIPPED taps,
-//         W_t[ci][(ky', kx', co)] = W[co][ci][k-1-ky'][k-1-kx'];  J = k k cout / 8
+// kind 0: the forward A-operand image, kind 1: the transposed convolution's (rows = cin of the convolution, J = k k cout / 8);
+// both layouts: encoder.h conv_pack_src / conv_pack_src_t
 struct TrunkPackJob {
     const float* src;   // (cout, cin, k, k) as PyTorch keeps it
     float* dst;
@@ -43,23 +42,14 @@ struct TrunkPackJob {
 
 __global__ __launch_bounds__(256) void trunk_pack_kernel(const TrunkPackJob* __restrict__ jobs) {
     const TrunkPackJob jb = jobs[blockIdx.y];
-    const int kk2 = jb.k * jb.k;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < jb.count; i += gridDim.x * blockDim.x) {
         const int l = i & 63, j = (i >> 6) % jb.J, nt = (i >> 6) / jb.J;
         const int n = 32 * nt + (l & 31), k0 = 8 * j + 4 * (l >> 5);
         float v[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int kk = k0 + r;
-            float val = 0.f;
-            if (jb.kind == 0) {
-                const int tap = kk / jb.cin_p, ci = kk - tap * jb.cin_p;
-                if (tap < kk2 && ci < jb.cin) val = jb.src[((size_t)n * jb.cin + ci) * kk2 + tap];
-            } else {
-                const int tap = kk / jb.cout, co = kk - tap * jb.cout;
-                if (tap < kk2) val = jb.src[((size_t)co * jb.cin + n) * kk2 + (kk2 - 1 - tap)];   // flipped in y and x
-            }
-            v[r] = val;
+            const long long src = jb.kind == 0 ? conv_pack_src(n, k0 + r, jb.cin, jb.cin_p, jb.k) : conv_pack_src_t(n, k0 + r, jb.cin, jb.cout, jb.k);
+            v[r] = src >= 0 ? jb.src[src] : 0.f;
         }
         reinterpret_cast<float4*>(jb.dst)[i] = make_float4(v[0], v[1], v[2], v[3]);
     }
@@ -483,84 +473,28 @@ __global__ void add2_kernel(const float* __restrict__ a, const float* __restrict
     reinterpret_cast<float4*>(dst)[i] = v;
 }
 
-// (n, h, w, 4) image -> same kernel as encoder.hip's (declared there as a __global__; re-stated to keep the units separate)
-__global__ void trunk_image_to_nhwc4_kernel(const float* __restrict__ in, float* __restrict__ out, int n, int hw) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)n * hw) return;
-    const int img = (int)(i / hw), p = (int)(i - (long long)img * hw);
-    const float* s = in + (size_t)img * 3 * hw + p;
-    *reinterpret_cast<float4*>(out + i * 4) = make_float4(s[0], s[hw], s[2 * (size_t)hw], 0.f);
-}
-__global__ void trunk_maxpool_kernel(const float* __restrict__ in, float* __restrict__ out, int n, int hin, int win, int c, int hout,
-                                     int wout) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int cq = c / 4;
-    if (i >= (long long)n * hout * wout * cq) return;
-    const int q = (int)(i % cq);
-    long long p = i / cq;
-    const int ox = (int)(p % wout);
-    p /= wout;
-    const int oy = (int)(p % hout), img = (int)(p / hout);
-    float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-    for (int dy = 0; dy < 3; ++dy)
-        for (int dx = 0; dx < 3; ++dx) {
-            const int iy = oy * 2 - 1 + dy, ix = ox * 2 - 1 + dx;
-            if (iy < 0 || iy >= hin || ix < 0 || ix >= win) continue;
-            const float4 v = *reinterpret_cast<const float4*>(in + (((size_t)img * hin + iy) * win + ix) * c + 4 * q);
-            m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
-        }
-    *reinterpret_cast<float4*>(out + i * 4) = m;
-}
-__global__ void trunk_upsample_concat_kernel(const float* __restrict__ in, float* __restrict__ lat, int n, int hin, int win, int c,
-                                             int h0, int w0, int ctot, int coff) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int cq = c / 4;
-    if (i >= (long long)n * h0 * w0 * cq) return;
-    const int q = (int)(i % cq);
-    long long p = i / cq;
-    const int ox = (int)(p % w0);
-    p /= w0;
-    const int oy = (int)(p % h0), img = (int)(p / h0);
-    const float sy = h0 > 1 ? (float)(hin - 1) / (float)(h0 - 1) : 0.f;
-    const float sx = w0 > 1 ? (float)(win - 1) / (float)(w0 - 1) : 0.f;
-    const float fy = sy * (float)oy, fx = sx * (float)ox;
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < hin - 1 ? 1 : 0), x1 = x0 + (x0 < win - 1 ? 1 : 0);
-    const float ly1 = fy - (float)y0, lx1 = fx - (float)x0;
-    const float ly0 = 1.0f - ly1, lx0 = 1.0f - lx1;
-    const float* b = in + (size_t)img * hin * win * c + 4 * q;
-    const float4 v00 = *reinterpret_cast<const float4*>(b + ((size_t)y0 * win + x0) * c);
-    const float4 v01 = *reinterpret_cast<const float4*>(b + ((size_t)y0 * win + x1) * c);
-    const float4 v10 = *reinterpret_cast<const float4*>(b + ((size_t)y1 * win + x0) * c);
-    const float4 v11 = *reinterpret_cast<const float4*>(b + ((size_t)y1 * win + x1) * c);
-    float4 o;
-    o.x = ly0 * (lx0 * v00.x + lx1 * v01.x) + ly1 * (lx0 * v10.x + lx1 * v11.x);
-    o.y = ly0 * (lx0 * v00.y + lx1 * v01.y) + ly1 * (lx0 * v10.y + lx1 * v11.y);
-    o.z = ly0 * (lx0 * v00.z + lx1 * v01.z) + ly1 * (lx0 * v10.z + lx1 * v11.z);
-    o.w = ly0 * (lx0 * v00.w + lx1 * v01.w) + ly1 * (lx0 * v10.w + lx1 * v11.w);
-    *reinterpret_cast<float4*>(lat + (((size_t)img * h0 + oy) * w0 + ox) * ctot + coff + 4 * q) = o;
-}
-
 // ------------------------------------------------------------------------------------------------ host side
 // One convolution + batch norm of the trunk, with everything the backward needs
 struct TrunkUnit {
+    const TrunkConv* c = nullptr; // its entry of trunk_table()
     std::string conv, bn;         // state_dict prefixes ("encoder.model.layer1.0.conv1", "...bn1")
-    int cin, cin_p, cout, k, stride, pad;
+    ConvLayer fwd, bwd;           // the convolution on the packed live weights, scale 1 / shift 0; the transposed convolution of
+                                  // its input gradient (flipped, transposed filters; bwd.w null where that is never needed)
     int hin, win, hout, wout;
     const float* x = nullptr;     // input activation (n, hin, win, cin_p)
     const float* resid = nullptr; // residual added before the relu (or null)
     bool relu = true;
     float *y = nullptr, *out = nullptr, *mean = nullptr, *invstd = nullptr;
-    float *w_fwd = nullptr, *w_t = nullptr;   // packed operands (forward; transposed-flipped for the input gradient)
-    int J = 0, Jt = 0;
 };
+// a packed operand's size in 16-byte elements
+static int pack_count(const ConvLayer& L) { return (L.cout / 32) * L.J * 64; }
 
 struct TrunkTrain {
     DevBuf work, packs, jobs, part, dwpart, ones;
     std::vector<TrunkUnit> units;
     int n = 0, height = 0, width = 0;
     bool pool = true;
-    int h[4] = {0, 0, 0, 0}, w[4] = {0, 0, 0, 0};
+    Pyramid d = {};
     float* img4 = nullptr;
     float* pooled = nullptr;
     const float* level_out[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -600,7 +534,6 @@ void trunk_release(TrunkTrain* t) {
     delete t;
 }
 
-static size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }
 static void dw_split(const TrunkUnit& u, int n, int* splits, long long* chunk);
 
 static int find_param(pny_model* m, const std::string& name, const float** out) {
@@ -614,6 +547,31 @@ static float* find_grad(pny_model* m, const std::string& name) {
     return it == m->grads.end() ? nullptr : it->second;
 }
 
+// The work buffer (image, per unit y / out / mean / invstd, pooled level, gradient scratch, level gradients, latent) and the
+// packed operands, laid out from `work` / `packs`; null: sizes only.  Sizes in floats.
+static void trunk_layout(TrunkTrain& T, float* work, float* packs, size_t* work_fl, size_t* packs_fl) {
+    const size_t n = T.n;
+    Carver c{work}, pk{packs};
+    T.img4 = c.take(n * T.height * T.width * 4);
+    size_t max_act = n * T.d.h[0] * T.d.w[0] * TRUNK_CH[0];
+    for (TrunkUnit& u : T.units) {
+        const size_t act = n * u.hout * u.wout * u.fwd.cout;
+        u.y = c.take(act);
+        u.out = c.take(act);
+        u.mean = c.take(u.fwd.cout);
+        u.invstd = c.take(u.fwd.cout);
+        max_act = std::max(max_act, act);
+        u.fwd.w = pk.take((size_t)pack_count(u.fwd) * 4);
+        u.bwd.w = u.fwd.cin >= 32 ? pk.take((size_t)pack_count(u.bwd) * 4) : nullptr;   // conv1's input gradient (the images) is never needed
+    }
+    T.pooled = c.take(n * T.d.h[1] * T.d.w[1] * TRUNK_CH[0]);
+    for (float*& p : T.scr) p = c.take(max_act);
+    for (int lv = 0; lv < 4; ++lv) T.d_level[lv] = c.take(n * T.d.h[lv] * T.d.w[lv] * TRUNK_CH[lv]);
+    T.lat_nhwc = c.take(n * T.d.h[0] * T.d.w[0] * TRUNK_LATENT);
+    *work_fl = c.off;
+    *packs_fl = pk.off;
+}
+
 // lays out units, activations and packs for n images of height x width; (re)allocates when the shape changed
 static int trunk_plan(pny_model* m, TrunkTrain& T, int n, int height, int width) {
     const bool pool = m->desc.enc_use_first_pool != 0;
@@ -623,102 +581,44 @@ static int trunk_plan(pny_model* m, TrunkTrain& T, int n, int height, int width)
     T.height = height;
     T.width = width;
     T.pool = pool;
-    T.h[0] = conv_out(height, 7, 2, 3);
-    T.w[0] = conv_out(width, 7, 2, 3);
-    T.h[1] = pool ? conv_out(T.h[0], 3, 2, 1) : T.h[0];
-    T.w[1] = pool ? conv_out(T.w[0], 3, 2, 1) : T.w[0];
-    for (int i = 2; i < 4; ++i) {
-        T.h[i] = conv_out(T.h[i - 1], 3, 2, 1);
-        T.w[i] = conv_out(T.w[i - 1], 3, 2, 1);
-    }
-    const std::string pre = "encoder.model.";
-    auto unit = [&](const std::string& conv, const std::string& bn, int cin, int cout, int k, int stride, int pad, int hin, int win) {
+    T.d = pyramid(height, width, pool);
+    int hin = height, win = width;
+    for (const TrunkConv& c : trunk_table()) {
         TrunkUnit u;
-        u.conv = pre + conv;
-        u.bn = pre + bn;
-        u.cin = cin;
-        u.cin_p = (cin + 3) / 4 * 4;
-        u.cout = cout;
-        u.k = k;
-        u.stride = stride;
-        u.pad = pad;
+        u.c = &c;
+        u.conv = "encoder.model." + c.conv;
+        u.bn = "encoder.model." + c.bn;
+        u.fwd = conv_geometry(c);
+        u.bwd.cin = u.bwd.cin_p = c.cout;
+        u.bwd.cout = c.cin;
+        u.bwd.k = c.k;
+        u.bwd.stride = 1;
+        u.bwd.pad = c.k - 1 - c.pad;
+        u.bwd.J = c.k * c.k * c.cout / 8;
         u.hin = hin;
         u.win = win;
-        u.hout = conv_out(hin, k, stride, pad);
-        u.wout = conv_out(win, k, stride, pad);
-        u.J = (k * k * u.cin_p + 7) / 8;
-        u.Jt = k * k * cout / 8;
+        u.hout = conv_out(hin, c.k, c.stride, c.pad);
+        u.wout = conv_out(win, c.k, c.stride, c.pad);
         T.units.push_back(u);
-    };
-    unit("conv1", "bn1", 3, 64, 7, 2, 3, height, width);
-    const int couts[3] = {64, 128, 256}, nblk[3] = {3, 4, 6};
-    int cin = 64, hin = T.h[1], win = T.w[1];
-    for (int li = 0; li < 3; ++li)
-        for (int b = 0; b < nblk[li]; ++b) {
-            const std::string p = "layer" + std::to_string(li + 1) + "." + std::to_string(b) + ".";
-            const int stride = (b == 0 && li > 0) ? 2 : 1;
-            const int bc = b == 0 ? cin : couts[li];
-            if (b == 0 && (stride != 1 || bc != couts[li])) unit(p + "downsample.0", p + "downsample.1", bc, couts[li], 1, stride, 0, hin, win);
-            unit(p + "conv1", p + "bn1", bc, couts[li], 3, stride, 1, hin, win);
-            hin = conv_out(hin, 3, stride, 1);
-            win = conv_out(win, 3, stride, 1);
-            unit(p + "conv2", p + "bn2", couts[li], couts[li], 3, 1, 1, hin, win);
-            if (b + 1 == nblk[li]) cin = couts[li];
-        }
-    // ---- workspace: image, per unit y / out / mean / invstd, pooled level, gradient scratch, latent
-    size_t fl = al64((size_t)n * height * width * 4);
-    size_t max_act = 0;
-    for (const TrunkUnit& u : T.units) {
-        const size_t act = (size_t)n * u.hout * u.wout * u.cout;
-        fl += 2 * al64(act) + 2 * al64((size_t)u.cout);
-        max_act = std::max(max_act, act);
+        // the next unit's input: a block's downsample and conv1 read the same activation; layer1 reads the (pooled) stem
+        if (c.role == TrunkRole::stem) hin = T.d.h[1], win = T.d.w[1];
+        else if (c.role != TrunkRole::downsample) hin = u.hout, win = u.wout;
     }
-    max_act = std::max(max_act, (size_t)n * T.h[0] * T.w[0] * 64);
-    fl += al64((size_t)n * T.h[1] * T.w[1] * 64);                   // pooled level 0
-    fl += TrunkTrain::NSCR * al64(max_act);                           // gradient scratch pool
-    const int ch[4] = {64, 64, 128, 256};
-    for (int lv = 0; lv < 4; ++lv) fl += al64((size_t)n * T.h[lv] * T.w[lv] * ch[lv]);
-    fl += al64((size_t)n * T.h[0] * T.w[0] * 512);
+    size_t work_fl, packs_fl;
+    trunk_layout(T, nullptr, nullptr, &work_fl, &packs_fl);
     int rc;
-    if ((rc = T.work.reserve(fl * sizeof(float)))) return rc;
-    size_t off = 0;
-    auto carve = [&](size_t cnt) {
-        float* p = T.work.f() + off;
-        off += al64(cnt);
-        return p;
-    };
-    T.img4 = carve((size_t)n * height * width * 4);
-    for (TrunkUnit& u : T.units) {
-        const size_t act = (size_t)n * u.hout * u.wout * u.cout;
-        u.y = carve(act);
-        u.out = carve(act);
-        u.mean = carve(u.cout);
-        u.invstd = carve(u.cout);
-    }
-    T.pooled = carve((size_t)n * T.h[1] * T.w[1] * 64);
-    for (int i = 0; i < TrunkTrain::NSCR; ++i) T.scr[i] = carve(max_act);
-    for (int lv = 0; lv < 4; ++lv) T.d_level[lv] = carve((size_t)n * T.h[lv] * T.w[lv] * ch[lv]);
-    T.lat_nhwc = carve((size_t)n * T.h[0] * T.w[0] * 512);
-    // ---- packed operands
-    size_t pk = 0;
-    for (TrunkUnit& u : T.units) pk += al64((size_t)(u.cout / 32) * u.J * 256) + (u.cin >= 32 ? al64((size_t)(u.cin / 32) * u.Jt * 256) : 0);
-    if ((rc = T.packs.reserve(pk * sizeof(float)))) return rc;
-    size_t po = 0;
-    for (TrunkUnit& u : T.units) {
-        u.w_fwd = T.packs.f() + po;
-        po += al64((size_t)(u.cout / 32) * u.J * 256);
-        u.w_t = nullptr;
-        if (u.cin >= 32) {   // conv1's input gradient (the images) is never needed
-            u.w_t = T.packs.f() + po;
-            po += al64((size_t)(u.cin / 32) * u.Jt * 256);
-        }
-    }
+    if ((rc = T.work.reserve(work_fl * sizeof(float))) || (rc = T.packs.reserve(packs_fl * sizeof(float)))) return rc;
+    trunk_layout(T, T.work.f(), T.packs.f(), &work_fl, &packs_fl);
     // ones / zeros for the raw convolution (scale 1, shift 0)
     if ((rc = T.ones.reserve(512 * sizeof(float)))) return rc;
     {
         std::vector<float> v(512, 0.f);
         for (int i = 0; i < 256; ++i) v[i] = 1.0f;
         PNY_HIP(hipMemcpy(T.ones.p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+        for (TrunkUnit& u : T.units) {
+            u.fwd.scale = u.bwd.scale = T.ones.f();
+            u.fwd.shift = u.bwd.shift = T.ones.f() + 256;
+        }
     }
     if ((rc = T.part.reserve((size_t)BN_MAXB * 2 * 256 * sizeof(float)))) return rc;
     {   // the largest weight-gradient partial buffer of any unit (never reallocated while a side-stream launch may read it)
@@ -727,7 +627,7 @@ static int trunk_plan(pny_model* m, TrunkTrain& T, int n, int height, int width)
             int sp;
             long long ch_;
             dw_split(u, n, &sp, &ch_);
-            mx = std::max(mx, (size_t)sp * u.cout * u.k * u.k * u.cin_p);
+            mx = std::max(mx, (size_t)sp * u.fwd.cout * u.fwd.k * u.fwd.k * u.fwd.cin_p);
         }
         if ((rc = T.dwpart.reserve(mx * sizeof(float)))) return rc;
     }
@@ -757,22 +657,13 @@ static int trunk_upload_jobs(pny_model* m, TrunkTrain& T, hipStream_t st) {
     for (TrunkUnit& u : T.units) {
         const float* w = nullptr;
         if ((rc = find_param(m, u.conv + ".weight", &w))) return rc;
-        TrunkPackJob j;
-        j.src = w;
-        j.dst = u.w_fwd;
-        j.kind = 0;
-        j.cout = u.cout;
-        j.cin = u.cin;
-        j.cin_p = u.cin_p;
-        j.k = u.k;
-        j.J = u.J;
-        j.count = (u.cout / 32) * u.J * 64;
+        TrunkPackJob j = {w, u.fwd.w, 0, u.fwd.cout, u.fwd.cin, u.fwd.cin_p, u.fwd.k, u.fwd.J, pack_count(u.fwd)};
         jobs.push_back(j);
-        if (u.w_t) {
-            j.dst = u.w_t;
+        if (u.bwd.w) {
+            j.dst = u.bwd.w;
             j.kind = 1;
-            j.J = u.Jt;
-            j.count = (u.cin / 32) * u.Jt * 64;
+            j.J = u.bwd.J;
+            j.count = pack_count(u.bwd);
             jobs.push_back(j);
         }
     }
@@ -793,18 +684,7 @@ static void bn_grid(long long P, int* B, long long* chunk) {
 }
 
 static int unit_forward(pny_model* m, TrunkTrain& T, TrunkUnit& u, float momentum, hipStream_t st) {
-    ConvLayer L;
-    L.w = u.w_fwd;
-    L.scale = T.ones.f();
-    L.shift = T.ones.f() + 256;
-    L.cin = u.cin;
-    L.cin_p = u.cin_p;
-    L.cout = u.cout;
-    L.k = u.k;
-    L.stride = u.stride;
-    L.pad = u.pad;
-    L.J = u.J;
-    if (!run_conv_ex(L, u.x, T.n, u.hin, u.win, u.hout, u.wout, 0, nullptr, 0, u.y, st)) return fail(PNY_ERR_HIP, "trunk training: convolution launch failed");
+    if (!run_conv_ex(u.fwd, u.x, T.n, u.hin, u.win, u.hout, u.wout, 0, nullptr, 0, u.y, st)) return fail(PNY_ERR_HIP, "trunk training: convolution launch failed");
     const long long P = (long long)T.n * u.hout * u.wout;
     int B;
     long long chunk;
@@ -814,11 +694,12 @@ static int unit_forward(pny_model* m, TrunkTrain& T, TrunkUnit& u, float momentu
     if ((rc = find_param(m, u.bn + ".weight", &gamma)) || (rc = find_param(m, u.bn + ".bias", &beta)) ||
         (rc = find_param(m, u.bn + ".running_mean", &rm)) || (rc = find_param(m, u.bn + ".running_var", &rv)))
         return rc;
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(B), dim3(BN_THREADS), 0, st, u.y, P, u.cout, chunk, T.part.f());
-    const long long total = P * (u.cout / 4);
+    const int C = u.fwd.cout;
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(B), dim3(BN_THREADS), 0, st, u.y, P, C, chunk, T.part.f());
+    const long long total = P * (C / 4);
     long long grid = (total + BN_THREADS - 1) / BN_THREADS;
     if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)grid), dim3(BN_THREADS), 0, st, u.y, T.part.f(), B, P, u.cout, gamma, beta, u.resid,
+    hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)grid), dim3(BN_THREADS), 0, st, u.y, T.part.f(), B, P, C, gamma, beta, u.resid,
                        u.relu ? 1 : 0, u.out, u.mean, u.invstd, const_cast<float*>(rm), const_cast<float*>(rv), momentum, 1e-5f,
                        T.bn_eval ? 1 : 0);
     PNY_HIP(hipGetLastError());
@@ -838,61 +719,37 @@ int trunk_train_forward(pny_model* m, const float* images, int n, int height, in
     // weights of this step: one launch rebuilds every packed operand from the live parameters
     {
         int mx = 0;
-        for (const TrunkUnit& u : T.units) mx = std::max(mx, std::max((u.cout / 32) * u.J * 64, u.w_t ? (u.cin / 32) * u.Jt * 64 : 0));
+        for (const TrunkUnit& u : T.units) mx = std::max(mx, std::max(pack_count(u.fwd), u.bwd.w ? pack_count(u.bwd) : 0));
         int bx = (mx + 255) / 256;
         if (bx > 128) bx = 128;
         hipLaunchKernelGGL(trunk_pack_kernel, dim3(bx, T.n_jobs), dim3(256), 0, st, reinterpret_cast<const TrunkPackJob*>(T.jobs.p));
         PNY_HIP(hipEventRecord(T.ev_pack, st));
     }
-    const long long npx = (long long)n * height * width;
-    hipLaunchKernelGGL(trunk_image_to_nhwc4_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, st, images, T.img4, n, height * width);
-    size_t ui = 0;
-    TrunkUnit& u0 = T.units[ui++];
-    u0.x = T.img4;
-    u0.resid = nullptr;
-    u0.relu = true;
-    if ((rc = unit_forward(m, T, u0, momentum, st))) return rc;
-    T.level_out[0] = u0.out;
-    const float* x = u0.out;
-    if (T.pool) {
-        const long long np = (long long)n * T.h[1] * T.w[1] * 16;
-        hipLaunchKernelGGL(trunk_maxpool_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, u0.out, T.pooled, n, T.h[0], T.w[0], 64,
-                           T.h[1], T.w[1]);
-        x = T.pooled;
-    }
-    const int nblk[3] = {3, 4, 6};
-    for (int li = 0; li < 3; ++li) {
-        for (int b = 0; b < nblk[li]; ++b) {
-            const float* idt = x;
-            if (T.units[ui].k == 1) {   // downsample branch: bn(conv1x1(x)), no relu
-                TrunkUnit& ud = T.units[ui++];
-                ud.x = x;
-                ud.resid = nullptr;
-                ud.relu = false;
-                if ((rc = unit_forward(m, T, ud, momentum, st))) return rc;
-                idt = ud.out;
-            }
-            TrunkUnit& u1 = T.units[ui++];
-            u1.x = x;
-            u1.resid = nullptr;
-            u1.relu = true;
-            if ((rc = unit_forward(m, T, u1, momentum, st))) return rc;
-            TrunkUnit& u2 = T.units[ui++];
-            u2.x = u1.out;
-            u2.resid = idt;
-            u2.relu = true;
-            if ((rc = unit_forward(m, T, u2, momentum, st))) return rc;
-            x = u2.out;
+    launch_image_to_nhwc4(images, T.img4, n, height, width, st);
+    const float *x = T.img4, *idt = nullptr, *a1 = nullptr;   // the block's input, its identity branch, conv1's output
+    for (TrunkUnit& u : T.units) {
+        const TrunkRole role = u.c->role;
+        u.x = role == TrunkRole::conv2 ? a1 : x;
+        u.resid = role == TrunkRole::conv2 ? idt : nullptr;
+        u.relu = role != TrunkRole::downsample;   // downsample branch: bn(conv1x1(x)), no relu
+        if ((rc = unit_forward(m, T, u, momentum, st))) return rc;
+        switch (role) {
+            case TrunkRole::stem:
+                x = u.out;
+                if (T.pool) {
+                    launch_first_pool(u.out, T.pooled, n, T.d, st);
+                    x = T.pooled;
+                }
+                idt = x;
+                break;
+            case TrunkRole::downsample: idt = u.out; break;
+            case TrunkRole::conv1: a1 = u.out; break;
+            case TrunkRole::conv2: x = idt = u.out; break;
         }
-        T.level_out[li + 1] = x;
+        if (u.c->level_end) T.level_out[u.c->level] = u.out;
     }
-    const int ch[4] = {64, 64, 128, 256}, coff[4] = {0, 64, 128, 256};
-    for (int lv = 0; lv < 4; ++lv) {
-        const long long np = (long long)n * T.h[0] * T.w[0] * (ch[lv] / 4);
-        hipLaunchKernelGGL(trunk_upsample_concat_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, T.level_out[lv], T.lat_nhwc, n,
-                           T.h[lv], T.w[lv], ch[lv], T.h[0], T.w[0], 512, coff[lv]);
-    }
-    launch_nhwc_to_nchw(T.lat_nhwc, latent_nchw, n, 512, T.h[0] * T.w[0], st);
+    launch_pyramid_to_latent(T.level_out, T.lat_nhwc, n, T.d, st);
+    launch_nhwc_to_nchw(T.lat_nhwc, latent_nchw, n, TRUNK_LATENT, T.d.h[0] * T.d.w[0], st);
     PNY_HIP(hipGetLastError());
     T.have_forward = true;
     return 0;
@@ -901,8 +758,8 @@ int trunk_train_forward(pny_model* m, const float* images, int n, int height, in
 // pixel slices of a unit's weight-gradient GEMM: ~4 waves per CU in all, at least 128 pixels per slice
 static void dw_split(const TrunkUnit& u, int n, int* splits, long long* chunk) {
     const long long npix = (long long)n * u.hout * u.wout;
-    const int Kp = u.k * u.k * u.cin_p;
-    const long long base = (long long)(u.cout / 64) * ((Kp + 127) / 128);
+    const int Kp = u.fwd.k * u.fwd.k * u.fwd.cin_p;
+    const long long base = (long long)(u.fwd.cout / 64) * ((Kp + 127) / 128);
     long long sp = (1024 + base - 1) / base;
     const long long max_splits = std::max(1ll, npix / 128);
     if (sp > max_splits) sp = max_splits;
@@ -921,30 +778,31 @@ static int unit_weight_grad(pny_model* m, TrunkTrain& T, const TrunkUnit& u, con
         PNY_HIP(hipStreamWaitEvent(T.side, T.ev_ready, 0));
         st = T.side;
     }
+    const ConvLayer& L = u.fwd;
     DwcArgs a;
     a.dy = dy;
     a.x = u.x;
     a.n = T.n;
     a.hin = u.hin;
     a.win = u.win;
-    a.cin_p = u.cin_p;
+    a.cin_p = L.cin_p;
     a.hout = u.hout;
     a.wout = u.wout;
-    a.cout = u.cout;
-    a.k = u.k;
-    a.stride = u.stride;
-    a.pad = u.pad;
-    a.Kp = u.k * u.k * u.cin_p;
+    a.cout = L.cout;
+    a.k = L.k;
+    a.stride = L.stride;
+    a.pad = L.pad;
+    a.Kp = L.k * L.k * L.cin_p;
     a.ntiles = (a.Kp + 127) / 128;
     a.npix = (long long)T.n * u.hout * u.wout;
-    const long long base = (long long)(u.cout / 64) * a.ntiles;
+    const long long base = (long long)(L.cout / 64) * a.ntiles;
     dw_split(u, T.n, &a.splits, &a.chunk);
-    if ((size_t)a.splits * u.cout * a.Kp * sizeof(float) > T.dwpart.bytes) return fail(PNY_ERR_STATE, "trunk backward: weight-gradient partials larger than planned");
+    if ((size_t)a.splits * L.cout * a.Kp * sizeof(float) > T.dwpart.bytes) return fail(PNY_ERR_STATE, "trunk backward: weight-gradient partials larger than planned");
     a.partial = T.dwpart.f();
     const long long items = base * a.splits;
     hipLaunchKernelGGL(conv_dw_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, a);
-    const int tot = u.cout * u.cin * u.k * u.k;
-    hipLaunchKernelGGL(conv_dw_reduce_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, T.dwpart.f(), a.splits, u.cout, u.cin, u.cin_p, u.k,
+    const int tot = L.cout * L.cin * L.k * L.k;
+    hipLaunchKernelGGL(conv_dw_reduce_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, T.dwpart.f(), a.splits, L.cout, L.cin, L.cin_p, L.k,
                        a.Kp, dw);
     PNY_HIP(hipGetLastError());
     if (T.side)
@@ -961,6 +819,7 @@ static int unit_weight_grad(pny_model* m, TrunkTrain& T, const TrunkUnit& u, con
 static int unit_backward(pny_model* m, TrunkTrain& T, TrunkUnit& u, const float* d_out, float* dy_buf, float* g_buf, float* dx_buf,
                          const float* dx_add, hipStream_t st) {
     const long long P = (long long)T.n * u.hout * u.wout;
+    const int C = u.fwd.cout;
     int B;
     long long chunk;
     bn_grid(P, &B, &chunk);
@@ -968,29 +827,17 @@ static int unit_backward(pny_model* m, TrunkTrain& T, TrunkUnit& u, const float*
     int rc;
     if ((rc = find_param(m, u.bn + ".weight", &gamma))) return rc;
     const float* mask = u.relu ? u.out : nullptr;
-    hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(B), dim3(BN_THREADS), 0, st, d_out, mask, u.y, u.mean, u.invstd, P, u.cout, chunk, T.part.f());
-    const long long total = P * (u.cout / 4);
+    hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(B), dim3(BN_THREADS), 0, st, d_out, mask, u.y, u.mean, u.invstd, P, C, chunk, T.part.f());
+    const long long total = P * (C / 4);
     long long grid = (total + BN_THREADS - 1) / BN_THREADS;
     if (grid > 1024) grid = 1024;
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)grid), dim3(BN_THREADS), 0, st, d_out, mask, u.y, u.mean, u.invstd, gamma, T.part.f(), B,
-                       P, u.cout, dy_buf, g_buf, find_grad(m, u.bn + ".weight"), find_grad(m, u.bn + ".bias"), T.bn_eval ? 1 : 0);
+                       P, C, dy_buf, g_buf, find_grad(m, u.bn + ".weight"), find_grad(m, u.bn + ".bias"), T.bn_eval ? 1 : 0);
     PNY_HIP(hipGetLastError());
     if ((rc = unit_weight_grad(m, T, u, dy_buf, st))) return rc;
-    if (dx_buf) {
-        ConvLayer L;
-        L.w = u.w_t;
-        L.scale = T.ones.f();
-        L.shift = T.ones.f() + 256;
-        L.cin = L.cin_p = u.cout;
-        L.cout = u.cin;
-        L.k = u.k;
-        L.stride = 1;
-        L.pad = u.k - 1 - u.pad;
-        L.J = u.Jt;
-        const int sh = u.stride == 2 ? 1 : 0;
-        if (!run_conv_ex(L, dy_buf, T.n, u.hout, u.wout, u.hin, u.win, sh, dx_add, 0, dx_buf, st))
-            return fail(PNY_ERR_HIP, "trunk training: transposed convolution launch failed");
-    }
+    // a stride-2 convolution's gradient is read as a dilated input
+    if (dx_buf && !run_conv_ex(u.bwd, dy_buf, T.n, u.hout, u.wout, u.hin, u.win, u.fwd.stride == 2 ? 1 : 0, dx_add, 0, dx_buf, st))
+        return fail(PNY_ERR_HIP, "trunk training: transposed convolution launch failed");
     return 0;
 }
 
@@ -1002,16 +849,15 @@ int trunk_train_backward(pny_model* m, const float* d_latent_nchw, hipStream_t s
     int rc;
     // pyramid: level gradients from the latent's channel groups
     float* d_lat = T.lat_nhwc;   // (the forward's channel-last latent is no longer needed)
-    launch_nchw_to_nhwc(d_latent_nchw, d_lat, n, 512, T.h[0] * T.w[0], st);
-    const int ch[4] = {64, 64, 128, 256}, coff[4] = {0, 64, 128, 256};
+    const Pyramid& d = T.d;
+    launch_nchw_to_nhwc(d_latent_nchw, d_lat, n, TRUNK_LATENT, d.h[0] * d.w[0], st);
     for (int lv = 0; lv < 4; ++lv) {
-        const long long np = (long long)n * T.h[lv] * T.w[lv] * (ch[lv] / 4);
+        const long long np = (long long)n * d.h[lv] * d.w[lv] * (TRUNK_CH[lv] / 4);
         hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, d_lat, (const float*)nullptr, T.d_level[lv], n,
-                           T.h[lv], T.w[lv], ch[lv], T.h[0], T.w[0], 512, coff[lv]);
+                           d.h[lv], d.w[lv], TRUNK_CH[lv], d.h[0], d.w[0], TRUNK_LATENT, TRUNK_COFF[lv]);
     }
     // residual layers, last to first.  g_x = gradient w.r.t. the current block's output.  Scratch: a pool of NSCR buffers of
     // the largest activation; at most four are live at any point.
-    const int nblk[3] = {3, 4, 6};
     if (!T.side && !getenv("PNYOLO_TRUNK_NO_SIDE_STREAM")) {
         PNY_HIP(hipStreamCreateWithFlags(&T.side, hipStreamNonBlocking));
         PNY_HIP(hipEventCreateWithFlags(&T.ev_ready, hipEventDisableTiming));
@@ -1038,55 +884,54 @@ int trunk_train_backward(pny_model* m, const float* d_latent_nchw, hipStream_t s
         for (int i = 0; i < TrunkTrain::NSCR; ++i)
             if (T.scr[i] == ptr) used[i] = false;
     };
-    const float* g_x = T.d_level[3];
+    const float* g_x = T.d_level[T.units.back().c->level];
     size_t ui = T.units.size();
-    for (int li = 2; li >= 0; --li) {
-        for (int b = nblk[li] - 1; b >= 0; --b) {
-            TrunkUnit& u2 = T.units[--ui];
-            TrunkUnit& u1 = T.units[--ui];
-            TrunkUnit* ud = (ui > 0 && T.units[ui - 1].k == 1) ? &T.units[--ui] : nullptr;
-            // conv2 / bn2: upstream g_x through relu(out); g = the masked gradient = gradient of the identity branch
-            float *dy2 = grab(), *g = grab(), *d_a1 = grab();
-            if (!dy2 || !g || !d_a1) return fail(PNY_ERR_STATE, "trunk backward: scratch pool exhausted");
-            if ((rc = unit_backward(m, T, u2, g_x, dy2, g, d_a1, nullptr, st))) return rc;
-            drop(g_x);
-            drop(dy2);
-            // conv1 / bn1: upstream d_a1 through relu(a1); without a downsample branch the identity gradient g joins here
-            float *dy1 = grab(), *dx = grab();
-            if (!dy1 || !dx) return fail(PNY_ERR_STATE, "trunk backward: scratch pool exhausted");
-            if ((rc = unit_backward(m, T, u1, d_a1, dy1, nullptr, dx, ud ? nullptr : g, st))) return rc;
-            drop(d_a1);
-            drop(dy1);
-            if (ud) {   // downsample branch: upstream g (no relu behind its batch norm); its input gradient is added to dx
-                float *dyd = grab(), *dx2 = grab();
-                if (!dyd || !dx2) return fail(PNY_ERR_STATE, "trunk backward: scratch pool exhausted");
-                if ((rc = unit_backward(m, T, *ud, g, dyd, nullptr, dx2, dx, st))) return rc;
-                drop(dyd);
-                drop(dx);
-                dx = dx2;
-            }
-            drop(g);
-            g_x = dx;
-        }
-        // the layer's input is the previous level's output, which also fed the pyramid (levels 2 and 1; level 0 goes through the pool)
-        if (li > 0) {
+    while (ui > 1) {   // block by block down to the stem
+        TrunkUnit& u2 = T.units[--ui];
+        TrunkUnit& u1 = T.units[--ui];
+        TrunkUnit* ud = T.units[ui - 1].c->role == TrunkRole::downsample ? &T.units[--ui] : nullptr;
+        // a level's output also fed the pyramid (levels 2 and 1; the last level's gradient is the pyramid's alone, level 0 goes through the pool)
+        if (u2.c->level_end && &u2 != &T.units.back()) {
+            const int lv = u2.c->level;
             float* sum = grab();
             if (!sum) return fail(PNY_ERR_STATE, "trunk backward: scratch pool exhausted");
-            const long long n4 = (long long)n * T.h[li] * T.w[li] * ch[li] / 4;
-            hipLaunchKernelGGL(add2_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, g_x, (const float*)T.d_level[li], sum, n4);
+            const long long n4 = (long long)n * d.h[lv] * d.w[lv] * TRUNK_CH[lv] / 4;
+            hipLaunchKernelGGL(add2_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, g_x, (const float*)T.d_level[lv], sum, n4);
             drop(g_x);
             g_x = sum;
         }
+        // conv2 / bn2: upstream g_x through relu(out); g = the masked gradient = gradient of the identity branch
+        float *dy2 = grab(), *g = grab(), *d_a1 = grab();
+        if (!dy2 || !g || !d_a1) return fail(PNY_ERR_STATE, "trunk backward: scratch pool exhausted");
+        if ((rc = unit_backward(m, T, u2, g_x, dy2, g, d_a1, nullptr, st))) return rc;
+        drop(g_x);
+        drop(dy2);
+        // conv1 / bn1: upstream d_a1 through relu(a1); without a downsample branch the identity gradient g joins here
+        float *dy1 = grab(), *dx = grab();
+        if (!dy1 || !dx) return fail(PNY_ERR_STATE, "trunk backward: scratch pool exhausted");
+        if ((rc = unit_backward(m, T, u1, d_a1, dy1, nullptr, dx, ud ? nullptr : g, st))) return rc;
+        drop(d_a1);
+        drop(dy1);
+        if (ud) {   // downsample branch: upstream g (no relu behind its batch norm); its input gradient is added to dx
+            float *dyd = grab(), *dx2 = grab();
+            if (!dyd || !dx2) return fail(PNY_ERR_STATE, "trunk backward: scratch pool exhausted");
+            if ((rc = unit_backward(m, T, *ud, g, dyd, nullptr, dx2, dx, st))) return rc;
+            drop(dyd);
+            drop(dx);
+            dx = dx2;
+        }
+        drop(g);
+        g_x = dx;
     }
     // level 0: through the max-pool (or directly), plus its pyramid share
     float* d_l0 = grab();
     TrunkUnit& u0 = T.units[0];
     if (T.pool) {
-        const long long np = (long long)n * T.h[0] * T.w[0] * 16;
+        const long long np = (long long)n * d.h[0] * d.w[0] * 16;
         hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, u0.out, g_x, (const float*)T.d_level[0], d_l0, n,
-                           T.h[0], T.w[0], 64, T.h[1], T.w[1]);
+                           d.h[0], d.w[0], 64, d.h[1], d.w[1]);
     } else {
-        const long long n4 = (long long)n * T.h[0] * T.w[0] * 16;
+        const long long n4 = (long long)n * d.h[0] * d.w[0] * 16;
         hipLaunchKernelGGL(add2_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, g_x, (const float*)T.d_level[0], d_l0, n4);
     }
     drop(g_x);
