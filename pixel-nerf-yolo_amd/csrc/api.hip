@@ -1121,7 +1121,7 @@ static int run_mlp(pny_scene* s, int mode, const float* xyz, const float* dirs, 
     if (r.stash) {
         pny_scene::StashedPass& sp = s->stashed[stash_pass];
         a.lay = stash_layout(d, obj_views(s), s->L);
-        a.stash_x = m->dx_stash[which].f() + m->defer_used[which] * a.lay.x_tile;
+        a.stash_x = a.lay.x_record(m->dx_stash[which].f(), m->defer_used[which]);
         sp.valid = true;
         sp.epoch = m->defer_epoch;
         sp.which = which;

@@ -299,7 +299,7 @@ inline const F16Images& f16_images(const pny_model* m, bool fine, bool single_pl
     return single_plane ? m->h1[fine ? 1 : 0] : (fine ? m->fine_t : m->coarse_t).h2;
 }
 inline int obj_views(const pny_scene* s) { return s->ns / (s->n_objs > 0 ? s->n_objs : 1); }   // views per object
-StashLayout stash_layout(const pny_model_desc& d, int ns, int L);
+inline StashLayout stash_layout(const pny_model_desc& d, int ns, int L) { return stash_layout(d.n_blocks, d.combine_layer, ns, L); }
 // projected latent maps of the coarse (0) / fine (1) MLP, computed if stale; force = regardless of the scene's mode
 int ensure_projection(pny_scene* s, int which, long long n_points, hipStream_t st, const float** zp, bool force = false);
 // MlpArgs of a launch on this scene in the reference's operation order (no projected latent); tiles of 64 samples

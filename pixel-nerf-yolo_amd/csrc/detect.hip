@@ -270,20 +270,13 @@ int pny_nms(const float* boxes_dev, int n, double iou_threshold, double threshol
         return PNY_ERR_ARG;
     }
     const size_t lds = nms_lds_bytes(n > 0 ? n : 1);
-    static size_t max_set[64] = {};  // per device, as launch_sample_fine keeps it: the attribute belongs to the device's code object
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev &= 63;
-    if (lds > max_set[dev]) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(nms_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {  // refuse here, not through the launch that would fail next
-            (void)hipGetLastError();
-            set_error("pny_nms: n = " + std::to_string(n) + " needs " + std::to_string(lds) +
-                      " bytes of dynamic LDS and the device refused that limit (" + hipGetErrorString(e) + ")");
-            return PNY_ERR_HIP;
-        }
-        max_set[dev] = lds;
+    static LdsLimit limit;
+    const hipError_t e = limit.raise(lds, nms_kernel);
+    if (e != hipSuccess) {  // refuse here, not through the launch that would fail next
+        (void)hipGetLastError();
+        set_error("pny_nms: n = " + std::to_string(n) + " needs " + std::to_string(lds) +
+                  " bytes of dynamic LDS and the device refused that limit (" + hipGetErrorString(e) + ")");
+        return PNY_ERR_HIP;
     }
     hipLaunchKernelGGL(nms_kernel, dim3(1), dim3(NMS_THREADS), lds, (hipStream_t)stream, boxes_dev, n,
                        (float)iou_threshold, threshold, kept_dev, meta_dev, highest_conf_dev);

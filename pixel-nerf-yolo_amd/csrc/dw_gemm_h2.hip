@@ -76,15 +76,8 @@ __global__ __launch_bounds__(512, 2) void PNY_DWG_KERNEL(const DwJob* __restrict
     const int row0 = it.mt * DWH_TILE, col0 = it.nt * DWH_TILE;
 
     // scale = 2^(13 - floor(log2(max |dY|))), clamped to the normal range
-    float scale = 1.0f, inv_scale = 1.0f;
-    {
-        const unsigned mb = *dy_absmax;
-        int e = (int)((mb >> 23) & 0xffu) - 127;
-        if (mb != 0u && e > -100 && e < 100) {
-            scale = __uint_as_float((unsigned)(127 + 13 - e) << 23);
-            inv_scale = __uint_as_float((unsigned)(127 - 13 + e) << 23);
-        }
-    }
+    float scale, inv_scale;
+    pow2_scale(*dy_absmax, 13, &scale, &inv_scale);
 
     f32x16 acc[4][2];
 #pragma unroll
@@ -113,8 +106,8 @@ __global__ __launch_bounds__(512, 2) void PNY_DWG_KERNEL(const DwJob* __restrict
     auto fetch = [&](int h) {
         const int tv = it.tv_lo + (h >> 1), half = h & 1;
         const int tile = tv / jb.n_views, v = tv - tile * jb.n_views;
-        const float* rec = op == 0 ? dy_stash + (long long)tile * dy_tile + jb.a_off + (long long)v * jb.a_view
-                                   : x_stash + (long long)tile * x_tile + jb.x_off + (long long)v * jb.x_view;
+        const float* rec = op == 0 ? stash_record(dy_stash, dy_tile, tile) + jb.a_off + (long long)v * jb.a_view
+                                   : stash_record(x_stash, x_tile, tile) + jb.x_off + (long long)v * jb.x_view;
         const float4* g = reinterpret_cast<const float4*>(rec) + ((op == 0 ? row0 : col0) / 4 + fq) * 64 + 32 * half + c;
 #pragma unroll
         for (int i = 0; i < 8; ++i) r[i] = q_load ? g[4 * i] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -241,17 +234,8 @@ __global__ __launch_bounds__(512, 2) void PNY_DWG_KERNEL(const DwJob* __restrict
 void PNY_DWG_LAUNCH(const DwJob* jobs_dev, const DwItem* items_dev, int n_part, int n_full, const float* x_stash,
                     const float* dy_stash, long long x_tile, long long dy_tile, float* partial, float* bias_partial, hipStream_t st,
                     hipStream_t sp, const unsigned* dy_absmax) {
-    static bool attr_set[64] = {};
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
-    dev_ &= 63;
-    if (!attr_set[dev_]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(PNY_DWG_KERNEL<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)DWH_LDS_BYTES);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(PNY_DWG_KERNEL<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)DWH_LDS_BYTES);
-        attr_set[dev_] = true;
-    }
+    static LdsLimit lds;
+    (void)lds.raise(DWH_LDS_BYTES, PNY_DWG_KERNEL<true>, PNY_DWG_KERNEL<false>);
     if (n_part > 0)
         hipLaunchKernelGGL(PNY_DWG_KERNEL<false>, dim3(n_part), dim3(512), DWH_LDS_BYTES, sp, jobs_dev, items_dev, x_stash, dy_stash,
                            x_tile, dy_tile, partial, bias_partial, dy_absmax);

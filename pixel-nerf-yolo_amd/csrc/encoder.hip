@@ -14,6 +14,7 @@
 #include <cstring>
 
 #include "encoder.h"
+#include "pny_common.h"
 
 namespace pny {
 
@@ -698,15 +699,8 @@ bool run_conv_ex(const ConvLayer& L, const float* in, int n, int hin, int win, i
     const bool small = tiles64 < 2 * (long long)cus;
     const long long tiles = small ? tiles32 : tiles64;
     const bool split = L.J >= 32 && tiles <= 4 * (long long)cus;
-    static bool attr_set[64] = {};  // per device: function attributes are per device
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
-    dev_ &= 63;
-    if (!attr_set[dev_]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<8, 2, 2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 16 * 64 * (int)sizeof(float));
-        attr_set[dev_] = true;
-    }
+    static LdsLimit lds;
+    (void)lds.raise(8 * 4 * 16 * 64 * sizeof(float), conv_mfma_kernel<8, 2, 2>);
     if (split && small) {
         hipLaunchKernelGGL((conv_mfma_kernel<8, 1, 1>), dim3((unsigned)tiles), dim3(512), 8 * 1 * 16 * 64 * sizeof(float), st, a);
     } else if (split) {

@@ -50,11 +50,11 @@ __global__ __launch_bounds__(64 * LG_NW) void PNY_LG32_KERNEL(const MlpArgs a, c
             tap_w[tid][k] = live ? wgt[k] : 0.0f;
         }
     }
-    // B operand: chunk c = 32 features of block c / 16; the stash slot of dh_in(b) is (2 b + 1) slots into the view's part
-    const float* dyv = dy_stash + tile * lay.dy_tile + (size_t)v * lay.dy_view;
+    // B operand: chunk c = 32 features of block c / 16, from dh_in(b) = the dY of lin_z[b]
+    const float* dy_rec = lay.dy_record(dy_stash, tile);
     auto stage_load = [&](int c, float4 (&sv)[2]) {
         const int b = c / (HID / LG_KC), kg0 = (c % (HID / LG_KC)) * (LG_KC / 4);
-        const float4* src = reinterpret_cast<const float4*>(dyv + (size_t)(2 * b + 1) * STASH_SLOT) + (size_t)kg0 * 64;
+        const float4* src = reinterpret_cast<const float4*>(dy_rec + lay.dy_dh(v, b)) + (size_t)kg0 * 64;
         sv[0] = src[tid];
         sv[1] = src[tid + 256];
     };

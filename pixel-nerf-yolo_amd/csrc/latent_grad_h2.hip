@@ -11,7 +11,7 @@
 // float-atomic scatter are the same (reproducible to fp32 rounding, not bit for bit, like the other latent-gradient kernels).
 // -DPNY_LG_FIXED (latent_grad_h2_det.hip, latent_grad_h1_det.hip) is the deterministic mode's build: the epilogue adds 64-bit
 // fixed-point integers instead (latent_grad_fx.h).
-#include "mlp_core.h"
+#include "mlp_bwd_core.h"
 #include "latent_grad_fx.h"
 
 #ifndef PNY_H2_PLANES
@@ -76,15 +76,8 @@ __global__ __launch_bounds__(64 * LG_NW) void PNY_LG_KERNEL(const MlpArgs a, con
     const int v = (int)(tv % a.NS);
     const long long tile0 = (tv / a.NS) * TPW;
     const int K = nvb * HID, J = K / 8;
-    float scale = 1.0f, inv_scale = 1.0f;
-    {
-        const unsigned mb = *dy_absmax;
-        const int e = (int)((mb >> 23) & 0xffu) - 127;
-        if (mb != 0u && e > -100 && e < 100) {
-            scale = __uint_as_float((unsigned)(127 + 13 - e) << 23);
-            inv_scale = __uint_as_float((unsigned)(127 - 13 + e) << 23);
-        }
-    }
+    float scale, inv_scale;
+    pow2_scale(*dy_absmax, 13, &scale, &inv_scale);
     // tile t of the workgroup (the last workgroup of a view may hold a single live tile: the dead one re-reads the live
     // tile's stash and scatters with weight 0)
     long long tile_of[TPW];
@@ -108,14 +101,14 @@ __global__ __launch_bounds__(64 * LG_NW) void PNY_LG_KERNEL(const MlpArgs a, con
             tap_w[tid][k] = live ? wgt[k] * inv_scale : 0.0f;   // the inverse scale rides on the tap weight
         }
     }
-    const float* dyv[TPW];
+    const float* dy_rec[TPW];
 #pragma unroll
-    for (int t = 0; t < TPW; ++t) dyv[t] = dy_stash + tile_of[t] * lay.dy_tile + (size_t)v * lay.dy_view;
+    for (int t = 0; t < TPW; ++t) dy_rec[t] = lay.dy_record(dy_stash, tile_of[t]);
     auto stage_load = [&](int c, float4 (&sv)[TPW][2]) {
         const int b = c / (HID / LG_KC), kg0 = (c % (HID / LG_KC)) * (LG_KC / 4);
 #pragma unroll
         for (int t = 0; t < TPW; ++t) {
-            const float4* src = reinterpret_cast<const float4*>(dyv[t] + (size_t)(2 * b + 1) * STASH_SLOT) + (size_t)kg0 * 64;
+            const float4* src = reinterpret_cast<const float4*>(dy_rec[t] + lay.dy_dh(v, b)) + (size_t)kg0 * 64;
             sv[t][0] = src[tid];
             sv[t][1] = src[tid + 256];
         }

@@ -37,7 +37,7 @@
 namespace pny {
 
 // STASH (training, ZP = false only): every GEMM's B operand is also written to the activation stash of the tile
-// (pny_common.h StashLayout) for the backward pass; outputs and arithmetic are those of the plain instantiation.
+// (stash.h) for the backward pass; outputs and arithmetic are those of the plain instantiation.
 template <class C, bool ZP, bool STASH = false>
 __global__ __launch_bounds__(C::THREADS, C::WPS) void pny_mlp_kernel(const MlpArgs a) {
     static_assert(!(STASH && ZP), "the stash variant runs the reference operation order");
@@ -95,11 +95,10 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void pny_mlp_kernel(const MlpAr
     const int t_step = xcd_order ? (int)(gridDim.x >> 3) : (int)gridDim.x;
     for (long long tile = t_first; tile < t_last; tile += t_step) {
         f32x16 h[NT][MT];
-        float* const x_rec = STASH ? a.stash_x + tile * a.lay.x_tile : nullptr;
+        float* const x_rec = STASH ? a.lay.x_record(a.stash_x, tile) : nullptr;
+        auto slot = [&](unsigned off) { return reinterpret_cast<float4*>(x_rec + off); };   // off: a slot of a.lay (stash.h)
         const int vb = tile_view_base(a, tile * C::TM);   // grouped scene: the tile's object sees views vb .. vb + NS - 1
         for (int v = 0; v < a.NS; ++v) {
-            float* const x_view = STASH ? x_rec + (size_t)v * a.lay.x_view : nullptr;
-            auto act_slot = [&](int i) { return reinterpret_cast<float4*>(x_view + a.lay.x_act + (size_t)i * STASH_SLOT); };
             {
                 BiasRegs<NT> bias;
                 ST_BEGIN();
@@ -109,7 +108,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void pny_mlp_kernel(const MlpAr
                 prologue<C>(a, v, tile, act, tap_tab, tid);
                 __syncthreads();
                 if constexpr (STASH) {  // lin_in's B operand: act rows 0..15
-                    float4* g = reinterpret_cast<float4*>(x_view + a.lay.x_in);
+                    float4* g = slot(a.lay.x_in(v));
                     for (int i = tid; i < (D_IN_PAD / 4) * TMc; i += C::THREADS) g[i] = act[i];
                 }
                 bias_apply<NT, MT, false>(h, bias);
@@ -168,7 +167,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void pny_mlp_kernel(const MlpAr
                             __syncthreads();  // chunk visible to all waves
                             if constexpr (STASH) {  // lin_z's B operand (same for every view block): stash it once
                                 if (blk == 0) {
-                                    float4* g = reinterpret_cast<float4*>(x_view + a.lay.x_z) + (size_t)(c0 / 4) * TMc;
+                                    float4* g = slot(a.lay.x_z(v)) + (size_t)(c0 / 4) * TMc;
                                     for (int i = tid; i < (GCH / 4) * TMc; i += C::THREADS) g[i] = win[i];
                                 }
                             }
@@ -183,8 +182,8 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void pny_mlp_kernel(const MlpAr
                 // (reference util.py:489-499 combine_interleaved, mean over the NS views)
                 if constexpr (STASH)
                     res_block<C, false, true>(h, ring, ws, a.w, blk, last ? after_view(v) : zseg(blk + 1, 0), act, wave,
-                                              lane, (last && v > 0) ? slab : nullptr ST_PASS, act_slot(2 * blk),
-                                              act_slot(2 * blk + 1));
+                                              lane, (last && v > 0) ? slab : nullptr ST_PASS, slot(a.lay.x_h(v, blk)),
+                                              slot(a.lay.x_net(v, blk)));
                 else
                 res_block<C, false>(h, ring, ws, a.w, blk, last ? after_view(v) : zseg(blk + 1, 0), act, wave, lane,
                                     (last && v > 0) ? slab : nullptr ST_PASS);
@@ -216,12 +215,11 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void pny_mlp_kernel(const MlpAr
                 ST_END(ST_HSUM);
             }
         }
-        auto post_slot = [&](int i) { return reinterpret_cast<float4*>(x_rec + a.lay.x_post + (size_t)i * STASH_SLOT); };
         for (int blk = n_view_blocks; blk < a.n_blocks; ++blk) {
             if constexpr (STASH)
                 res_block<C, false, true>(h, ring, ws, a.w, blk, blk + 1 < a.n_blocks ? fc0seg(blk + 1) : s_in, act, wave,
-                                          lane, nullptr ST_PASS, post_slot(2 * (blk - n_view_blocks)),
-                                          post_slot(2 * (blk - n_view_blocks) + 1));
+                                          lane, nullptr ST_PASS, slot(a.lay.x_post_h(blk - n_view_blocks)),
+                                          slot(a.lay.x_post_net(blk - n_view_blocks)));
             else
             res_block<C, false>(h, ring, ws, a.w, blk, blk + 1 < a.n_blocks ? fc0seg(blk + 1) : s_in, act, wave, lane,
                                 nullptr ST_PASS);
@@ -230,7 +228,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void pny_mlp_kernel(const MlpAr
         // out = lin_out(relu(h)) (reference resnetfc.py:185) + output head (models.py:312-317)
         ST_BEGIN();
         __syncthreads();
-        store_relu<NT, MT, STASH>(h, act, wave, lane, STASH ? post_slot(2 * (a.n_blocks - n_view_blocks)) : nullptr);
+        store_relu<NT, MT, STASH>(h, act, wave, lane, STASH ? slot(a.lay.x_top()) : nullptr);
         __syncthreads();
         for (int idx = tid; idx < a.d_out * TMc; idx += C::THREADS) {
             const int o = idx / TMc, m = idx % TMc;
@@ -304,15 +302,8 @@ size_t mlp_scratch_floats() { return (size_t)mlp_cu_count() * 64 * HID; }  // sa
 
 template <class C, bool ZP>
 static void launch_mlp_t(const MlpArgs& a, int grid, hipStream_t st) {
-    static bool attr_set[64] = {};  // per device: function attributes are per device
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
-    dev_ &= 63;
-    if (!attr_set[dev_]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pny_mlp_kernel<C, ZP>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-        attr_set[dev_] = true;
-    }
+    static LdsLimit lds;
+    (void)lds.raise(C::LDS, pny_mlp_kernel<C, ZP>);
 #ifdef PNY_STAMP
     static unsigned long long* dbuf = nullptr;
     const size_t nst = (size_t)grid * C::NW * ST_N;
@@ -367,15 +358,8 @@ static void launch_mlp_c(const MlpArgs& a, int grid, hipStream_t st) {
 
 void launch_mlp_stash(const MlpArgs& a, int grid, hipStream_t st) {
     using C = Cfg<2, 2>;
-    static bool attr_set[64] = {};
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
-    dev_ &= 63;
-    if (!attr_set[dev_]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pny_mlp_kernel<C, false, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-        attr_set[dev_] = true;
-    }
+    static LdsLimit lds;
+    (void)lds.raise(C::LDS, pny_mlp_kernel<C, false, true>);
     hipLaunchKernelGGL((pny_mlp_kernel<C, false, true>), dim3(grid), dim3(C::THREADS), C::LDS, st, a);
 }
 

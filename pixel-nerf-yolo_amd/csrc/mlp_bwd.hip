@@ -2,10 +2,11 @@
 // loss.backward() through PixelNeRFNet.forward / ResnetFC.forward (reference src/model/resnetfc.py:134-186,
 // src/model/models.py:153-318) w.r.t. every MLP parameter.
 //
-// Three kernels, all exact-fp32 MFMA (v_mfma_f32_32x32x2_f32), all on 64-sample tiles:
+// The parameter gradients take three kernels, all exact-fp32 MFMA (v_mfma_f32_32x32x2_f32), all on 64-sample tiles (the file
+// also holds the split reduction and the render backward's small kernels: composite, depth-sample and YOLO aggregation):
 //   1. pny_mlp_kernel<.., STASH> (mlp.hip): the forward chain once more in the reference's operation order, writing
 //      every GEMM's B operand X_l (relu'd activations, gathered latent, positional code) to an HBM stash in the LDS
-//      operand layout [feature/4][sample] float4 (pny_common.h StashLayout).
+//      operand layout [feature/4][sample] float4 (stash.h).
 //   2. pny_mlp_bwd_kernel (here): the dX chain.  Same transposed formulation and weight-stream ring as the forward:
 //      dX^T[k][m] = W^T[k][n] dY^T[n][m] with the TRANSPOSED packed weights as the A operand and dY^T in the LDS
 //      activation buffer as the B operand; the gradient of the residual stream stays in the accumulators (dh), a second
@@ -110,17 +111,11 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void pny_mlp_bwd_kernel(const B
     float amax = 0.f;
 
     for (long long tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
-        float* dy_rec = a.dy_stash + tile * a.lay.dy_tile;
-        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x_stash + tile * a.lay.x_tile), 0,
-                                                                            (int)(a.lay.x_tile * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(dy_rec, 0, (int)(a.lay.dy_tile * 4), 0x00020000);
-        auto x_post = [&](int i) { return StashRef{xr, ((unsigned)a.lay.x_post + (unsigned)i * (unsigned)STASH_SLOT) * 4u}; };
-        auto x_act = [&](int v, int i) {
-            return StashRef{xr, ((unsigned)v * (unsigned)a.lay.x_view + (unsigned)a.lay.x_act + (unsigned)i * (unsigned)STASH_SLOT) * 4u};
-        };
-        float4* dy_draw = reinterpret_cast<float4*>(dy_rec + a.lay.dy_post);
-        auto dy_post = [&](int i) { return StashRef{yr, ((unsigned)a.lay.dy_post + (unsigned)STASH_SMALL + (unsigned)i * (unsigned)STASH_SLOT) * 4u}; };
-        auto dy_view = [&](int v, int i) { return StashRef{yr, ((unsigned)v * (unsigned)a.lay.dy_view + (unsigned)i * (unsigned)STASH_SLOT) * 4u}; };
+        float* dy_rec = a.lay.dy_record(a.dy_stash, tile);
+        const __amdgpu_buffer_rsrc_t xr = stash_rsrc(a.lay.x_record(a.x_stash, tile), a.lay.x_tile);
+        const __amdgpu_buffer_rsrc_t yr = stash_rsrc(dy_rec, a.lay.dy_tile);
+        const TileStash ts{xr, yr, a.lay};
+        float4* dy_draw = reinterpret_cast<float4*>(dy_rec + a.lay.dy_raw());
 
         // ---- head: gradient w.r.t. lin_out's output through sigmoid / relu (reference models.py:312-317), as the B
         // operand of lin_out^T (d_out rows padded to 64) and as the dY of lin_out for the weight-gradient GEMM
@@ -154,50 +149,34 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void pny_mlp_bwd_kernel(const B
         f32x16 dh[NT][MT];
         acc_zero<NT, MT>(dh);
         gemm_run<C>(dh, ring, ws, s_out, fc1t(nb - 1), act, lane);
-        mask_by<NT, MT>(dh, x_post(2 * npost), wave, lane);                 // relu(h_top) > 0
-        store_plain<NT, MT, false, true>(dh, nullptr, dy_post(0), wave, lane, amax);  // dh_top: dY of the last block's fc_1
+        mask_by<NT, MT>(dh, ts.x_post(2 * npost), wave, lane);                 // relu(h_top) > 0
+        store_plain<NT, MT, false, true>(dh, nullptr, ts.dy_post(0), wave, lane, amax);  // dh_top: dY of the last block's fc_1
 
         // ---- post-combine blocks, last to first; the first of them also applies the 1/NS of the cross-view mean
         for (int b = nb - 1; b >= nvb; --b) {
             const int i = b - nvb;
             const WSeg after = b > nvb ? fc1t(b - 1) : (nvb > 0 ? fc1t(nvb - 1) : s_out);
-            block_bwd<C>(dh, ring, ws, fc1t(b), fc0t(b), after, act, x_post(2 * i), x_post(2 * i + 1), dy_post(1 + 2 * i),
-                         dy_post(2 + 2 * i), b == nvb ? inv_ns : 1.0f, wave, lane, amax);
+            block_bwd<C>(dh, ring, ws, fc1t(b), fc0t(b), after, act, ts.x_post(2 * i), ts.x_post(2 * i + 1), ts.dy_post(1 + 2 * i),
+                         ts.dy_post(2 + 2 * i), b == nvb ? inv_ns : 1.0f, wave, lane, amax);
         }
         // dhm: what every view's last per-view block receives (dh_top itself when there is no post-combine block)
-        const StashRef dhm = npost > 0 ? dy_post(2) : dy_post(0);
+        const StashRef dhm = npost > 0 ? ts.dy_post(2) : ts.dy_post(0);
         for (int v = 0; v < a.NS && nvb > 0; ++v) {
             if (v > 0) acc_load<NT, MT>(dh, dhm, wave, lane);
             for (int b = nvb - 1; b >= 0; --b) {
                 const WSeg after = b > 0 ? fc1t(b - 1) : (v + 1 < a.NS ? fc1t(nvb - 1) : s_out);
-                block_bwd<C>(dh, ring, ws, fc1t(b), fc0t(b), after, act, x_act(v, 2 * b), x_act(v, 2 * b + 1),
-                             dy_view(v, 2 * b), dy_view(v, 2 * b + 1), 1.0f, wave, lane, amax);
+                block_bwd<C>(dh, ring, ws, fc1t(b), fc0t(b), after, act, ts.x_act(v, 2 * b), ts.x_act(v, 2 * b + 1),
+                             ts.dy_view(v, 2 * b), ts.dy_view(v, 2 * b + 1), 1.0f, wave, lane, amax);
             }
         }
     }
-    if (a.dy_absmax) {   // non-negative floats order like their bit patterns
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-        if (lane == 0) {
-            atomicMax(a.dy_absmax, __float_as_uint(amax));
-            // f16-range guard: a non-finite gradient was written to the dY stash (the split-f16 consumers -- this chain's
-            // scaled planes, the weight-gradient GEMM's scale -- cannot represent it): PNY_RANGE_GRADIENT
-            if (!(amax < 3.0e38f)) range_report(a.range_flag, 2u);
-        }
-    }
+    absmax_report(a, amax, lane);
 }
 
 void launch_mlp_bwd(const BwdArgs& a, int grid, hipStream_t st) {
     using C = Cfg<2, 2>;
-    static bool attr_set[64] = {};
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
-    dev_ &= 63;
-    if (!attr_set[dev_]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pny_mlp_bwd_kernel<C>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-        attr_set[dev_] = true;
-    }
+    static LdsLimit lds;
+    (void)lds.raise(C::LDS, pny_mlp_bwd_kernel<C>);
     hipLaunchKernelGGL((pny_mlp_bwd_kernel<C>), dim3(grid), dim3(C::THREADS), C::LDS, st, a);
 }
 
@@ -250,8 +229,8 @@ __global__ __launch_bounds__(512, 2) void pny_dw_gemm_kernel(const DwJob* __rest
     auto fetch = [&](int h) {
         const int tv = it.tv_lo + (h >> 1), half = h & 1;
         const int tile = tv / jb.n_views, v = tv - tile * jb.n_views;
-        const float4* ga = reinterpret_cast<const float4*>(dy_stash + (long long)tile * dy_tile + jb.a_off + (long long)v * jb.a_view) + (row0 / 4) * 64 + 32 * half + ms;
-        const float4* gx = reinterpret_cast<const float4*>(x_stash + (long long)tile * x_tile + jb.x_off + (long long)v * jb.x_view) + (col0 / 4) * 64 + 32 * half + ms;
+        const float4* ga = reinterpret_cast<const float4*>(stash_record(dy_stash, dy_tile, tile) + jb.a_off + (long long)v * jb.a_view) + (row0 / 4) * 64 + 32 * half + ms;
+        const float4* gx = reinterpret_cast<const float4*>(stash_record(x_stash, x_tile, tile) + jb.x_off + (long long)v * jb.x_view) + (col0 / 4) * 64 + 32 * half + ms;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int kg = kg_s + 16 * i;
@@ -362,17 +341,8 @@ void launch_dw_gemm(const DwJob* jobs_dev, const DwItem* items_dev, int n_part, 
         (planes == 1 ? launch_dw_gemm_h1 : launch_dw_gemm_h2)(jobs_dev, items_dev, n_part, n_full, x_stash, dy_stash, x_tile, dy_tile,
                                                               partial, bias_partial, st, sp, dy_absmax);
     } else {
-        static bool attr_set[64] = {};
-        int dev_ = 0;
-        (void)hipGetDevice(&dev_);
-        dev_ &= 63;
-        if (!attr_set[dev_]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pny_dw_gemm_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)DW_LDS_BYTES);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pny_dw_gemm_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)DW_LDS_BYTES);
-            attr_set[dev_] = true;
-        }
+        static LdsLimit lds;
+        (void)lds.raise(DW_LDS_BYTES, pny_dw_gemm_kernel<true>, pny_dw_gemm_kernel<false>);
         if (n_part > 0)
             hipLaunchKernelGGL(pny_dw_gemm_kernel<false>, dim3(n_part), dim3(512), DW_LDS_BYTES, sp, jobs_dev, items_dev, x_stash,
                                dy_stash, x_tile, dy_tile, partial, bias_partial);
@@ -557,7 +527,7 @@ __global__ __launch_bounds__(256) void mlp_dz_kernel(const DzArgs a) {
     const float zz = a.z[idx];
     const float d[3] = {r0.w, r1.x, r1.y};
     const float p[3] = {r0.x + zz * d[0], r0.y + zz * d[1], r0.z + zz * d[2]};
-    const float* dy_rec = a.dy_stash + tile * a.lay.dy_tile;
+    const float* dy_rec = a.lay.dy_record(a.dy_stash, tile);
     const int ncode = 3 + 6 * a.num_freqs;
     float acc = 0.f;
     // grouped scene (MlpArgs::obj_pts): the sample's object sees views vb .. vb + NS - 1 of the view list (wave-uniform)
@@ -571,8 +541,7 @@ __global__ __launch_bounds__(256) void mlp_dz_kernel(const DzArgs a) {
             xc[k] = xr[k] + cam.w2c[4 * k + 3];
         }
         // ---- positional code: g_in = lin_in^T dh_in(0), then d sin(phase + x f) / dx = cos(.) f
-        const float* dh0 = a.nvb > 0 ? dy_rec + (size_t)v * a.lay.dy_view + STASH_SLOT
-                                     : dy_rec + a.lay.dy_post + STASH_SMALL + (size_t)(a.npost > 0 ? 2 : 0) * STASH_SLOT;
+        const float* dh0 = dy_rec + a.lay.dy_lin_in(v);
         {
             const float4 h0 = *reinterpret_cast<const float4*>(dh0 + ((size_t)(2 * lane) * 64 + m) * 4);
             const float4 h1 = *reinterpret_cast<const float4*>(dh0 + ((size_t)(2 * lane + 1) * 64 + m) * 4);
@@ -605,7 +574,7 @@ __global__ __launch_bounds__(256) void mlp_dz_kernel(const DzArgs a) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) gx[k] = bwd_wave_sum(dim == k ? c : 0.f);
         // ---- projection + bilinear lookup of the projected maps
-        if (a.nvb > 0 && a.zp) {
+        if (a.lay.nvb() > 0 && a.zp) {
             const float sgn = a.yolo ? 1.0f : -1.0f;
             float ux = sgn * xc[0] / xc[2], uy = sgn * xc[1] / xc[2];
             ux = ux * cam.fx + cam.cx;
@@ -624,8 +593,8 @@ __global__ __launch_bounds__(256) void mlp_dz_kernel(const DzArgs a) {
             float six = 0.f, siy = 0.f;
             if (!cull) {
                 const float* zv = a.zp + (size_t)(vb + v) * a.Hl * a.Wl * a.zp_stride;
-                for (int b = 0; b < a.nvb; ++b) {
-                    const float* dhb = dy_rec + (size_t)v * a.lay.dy_view + (size_t)(2 * b + 1) * STASH_SLOT;
+                for (int b = 0; b < a.lay.nvb(); ++b) {
+                    const float* dhb = dy_rec + a.lay.dy_dh(v, b);
                     const float4 h0 = *reinterpret_cast<const float4*>(dhb + ((size_t)(2 * lane) * 64 + m) * 4);
                     const float4 h1 = *reinterpret_cast<const float4*>(dhb + ((size_t)(2 * lane + 1) * 64 + m) * 4);
 #pragma unroll

@@ -124,17 +124,11 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_BWD_KERNEL(const BwdArgs a
     float amax = 0.f;
 
     for (long long tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
-        float* dy_rec = a.dy_stash + tile * a.lay.dy_tile;
-        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x_stash + tile * a.lay.x_tile), 0,
-                                                                            (int)(a.lay.x_tile * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(dy_rec, 0, (int)(a.lay.dy_tile * 4), 0x00020000);
-        auto x_post = [&](int i) { return StashRef{xr, ((unsigned)a.lay.x_post + (unsigned)i * (unsigned)STASH_SLOT) * 4u}; };
-        auto x_act = [&](int v, int i) {
-            return StashRef{xr, ((unsigned)v * (unsigned)a.lay.x_view + (unsigned)a.lay.x_act + (unsigned)i * (unsigned)STASH_SLOT) * 4u};
-        };
-        float4* dy_draw = reinterpret_cast<float4*>(dy_rec + a.lay.dy_post);
-        auto dy_post = [&](int i) { return StashRef{yr, ((unsigned)a.lay.dy_post + (unsigned)STASH_SMALL + (unsigned)i * (unsigned)STASH_SLOT) * 4u}; };
-        auto dy_view = [&](int v, int i) { return StashRef{yr, ((unsigned)v * (unsigned)a.lay.dy_view + (unsigned)i * (unsigned)STASH_SLOT) * 4u}; };
+        float* dy_rec = a.lay.dy_record(a.dy_stash, tile);
+        const __amdgpu_buffer_rsrc_t xr = stash_rsrc(a.lay.x_record(a.x_stash, tile), a.lay.x_tile);
+        const __amdgpu_buffer_rsrc_t yr = stash_rsrc(dy_rec, a.lay.dy_tile);
+        const TileStash ts{xr, yr, a.lay};
+        float4* dy_draw = reinterpret_cast<float4*>(dy_rec + a.lay.dy_raw());
 
         // ---- head: gradient w.r.t. lin_out's output through sigmoid / relu (reference models.py:312-317): the dY of lin_out
         // (true values, to the stash) and, scaled by the tile's sigma, the B operand of lin_out^T (d_out rows padded to 64)
@@ -177,15 +171,8 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_BWD_KERNEL(const BwdArgs a
         float tmax = red[0];
 #pragma unroll
         for (int w = 1; w < THREADS / 64; ++w) tmax = fmaxf(tmax, red[w]);
-        float sigma = 1.0f, inv_sigma = 1.0f;
-        {
-            const unsigned mb = __float_as_uint(tmax);
-            const int e = (int)((mb >> 23) & 0xffu) - 127;
-            if (mb != 0u && e > -100 && e < 100) {
-                sigma = __uint_as_float((unsigned)(127 + 4 - e) << 23);
-                inv_sigma = __uint_as_float((unsigned)(127 - 4 + e) << 23);
-            }
-        }
+        float sigma, inv_sigma;
+        pow2_scale(__float_as_uint(tmax), 4, &sigma, &inv_sigma);
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
             const int idx = tid + i * THREADS;
@@ -206,7 +193,7 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_BWD_KERNEL(const BwdArgs a
             f32x16 t[NT][MT];
             h2zero<NT, MT>(t);
             h2gemm(t, ring, ws, s_out, fc1t(nb - 1), planes, lane);
-            mask_by<NT, MT>(t, x_post(2 * npost), wave, lane);                           // relu(h_top) > 0
+            mask_by<NT, MT>(t, ts.x_post(2 * npost), wave, lane);                           // relu(h_top) > 0
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -214,17 +201,17 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_BWD_KERNEL(const BwdArgs a
 #pragma unroll
                     for (int r = 0; r < 16; ++r) dh[nt][mt][r] = t[nt][mt][r];
         }
-        bh_store<false, true>(dh, nullptr, dy_post(0), inv_sigma, wave, lane, amax);     // dh_top: dY of the last block's fc_1
+        bh_store<false, true>(dh, nullptr, ts.dy_post(0), inv_sigma, wave, lane, amax);     // dh_top: dY of the last block's fc_1
 
         // ---- post-combine blocks, last to first; the first of them also applies the 1/NS of the cross-view mean
         for (int b = nb - 1; b >= nvb; --b) {
             const int i = b - nvb;
             const H2Seg after = b > nvb ? fc1t(b - 1) : (nvb > 0 ? fc1t(nvb - 1) : s_out);
-            bh_block(dh, ring, ws, fc1t(b), fc0t(b), after, planes, x_post(2 * i), x_post(2 * i + 1), dy_post(1 + 2 * i),
-                     dy_post(2 + 2 * i), b == nvb ? inv_ns : 1.0f, inv_sigma, wave, lane, amax);
+            bh_block(dh, ring, ws, fc1t(b), fc0t(b), after, planes, ts.x_post(2 * i), ts.x_post(2 * i + 1), ts.dy_post(1 + 2 * i),
+                     ts.dy_post(2 + 2 * i), b == nvb ? inv_ns : 1.0f, inv_sigma, wave, lane, amax);
         }
         // dhm: what every view's last per-view block receives (dh_top itself when there is no post-combine block)
-        const StashRef dhm = npost > 0 ? dy_post(2) : dy_post(0);
+        const StashRef dhm = npost > 0 ? ts.dy_post(2) : ts.dy_post(0);
         for (int v = 0; v < a.NS && nvb > 0; ++v) {
             if (v > 0) {   // the stash holds true values
                 acc_load<NT, MT>(dh, dhm, wave, lane);
@@ -237,21 +224,12 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_BWD_KERNEL(const BwdArgs a
             }
             for (int b = nvb - 1; b >= 0; --b) {
                 const H2Seg after = b > 0 ? fc1t(b - 1) : (v + 1 < a.NS ? fc1t(nvb - 1) : s_out);
-                bh_block(dh, ring, ws, fc1t(b), fc0t(b), after, planes, x_act(v, 2 * b), x_act(v, 2 * b + 1), dy_view(v, 2 * b),
-                         dy_view(v, 2 * b + 1), 1.0f, inv_sigma, wave, lane, amax);
+                bh_block(dh, ring, ws, fc1t(b), fc0t(b), after, planes, ts.x_act(v, 2 * b), ts.x_act(v, 2 * b + 1), ts.dy_view(v, 2 * b),
+                         ts.dy_view(v, 2 * b + 1), 1.0f, inv_sigma, wave, lane, amax);
             }
         }
     }
-    if (a.dy_absmax) {   // non-negative floats order like their bit patterns
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-        if (lane == 0) {
-            atomicMax(a.dy_absmax, __float_as_uint(amax));
-            // f16-range guard: a non-finite gradient was written to the dY stash (the split-f16 consumers -- this chain's
-            // scaled planes, the weight-gradient GEMM's scale -- cannot represent it): PNY_RANGE_GRADIENT
-            if (!(amax < 3.0e38f)) range_report(a.range_flag, 2u);
-        }
-    }
+    absmax_report(a, amax, lane);
 }
 
 #if PNY_H2_PLANES == 1
@@ -259,14 +237,8 @@ void launch_mlp_bwd_h1(const BwdArgs& a, int grid, hipStream_t st) {
 #else
 void launch_mlp_bwd_h2(const BwdArgs& a, int grid, hipStream_t st) {
 #endif
-    static bool attr_set[64] = {};
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
-    dev_ &= 63;
-    if (!attr_set[dev_]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(PNY_BWD_KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, BH_LDS);
-        attr_set[dev_] = true;
-    }
+    static LdsLimit lds;
+    (void)lds.raise(BH_LDS, PNY_BWD_KERNEL);
     hipLaunchKernelGGL(PNY_BWD_KERNEL, dim3(grid), dim3(h2::THREADS), BH_LDS, st, a);
 }
 

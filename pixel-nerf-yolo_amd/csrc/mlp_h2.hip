@@ -41,6 +41,7 @@
 #include <cstdio>
 #include <vector>
 
+#include "mlp_bwd_core.h"
 #include "mlp_h2_core.h"
 
 // The same source is the SPLIT shape's translation unit (mlp_h2s.hip: -DPNY_H2_SPLIT with PNY_H2_NT = 4, PNY_H2_MT = 1;
@@ -134,7 +135,7 @@ __device__ __forceinline__ void stash_store(__amdgpu_buffer_rsrc_t rsrc, unsigne
 }
 
 // STASH (training forward): relu(acc + ...) is also written in fp32 to `stash` in the [feature/4][sample] float4 tile layout of
-// the backward's operand stash (pny_common.h StashLayout; the same values the fp32 STASH kernel of mlp.hip writes).
+// the backward's operand stash (stash.h; the same values the fp32 STASH kernel of mlp.hip writes).
 template <bool ADDZ, bool STASH = false>
 __device__ __forceinline__ void h2epilogue(f32x16 (&acc)[h2::NT][h2::MT], const float* bias, char* planes, int wave, int lane, unsigned* range_flag,
                                            __amdgpu_buffer_rsrc_t stash = __amdgpu_buffer_rsrc_t(), unsigned stash_off = 0) {
@@ -424,10 +425,10 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
         // one residual block from "planes hold relu(h_in)" on: net = fc_0(.), h += fc_1(relu(net + b_fc0)).  `next_c0` >= 0:
         // the first chunk of the NEXT block's projection (channel offset next_c0) is fetched into gather buffer 0
         // underneath the fc_1 GEMM -- `net` is dead there, its registers hold the chunk.
-        // this tile's record of the X stash as a buffer resource; offsets below are bytes inside the record
+        // this tile's record of the X stash as a buffer resource; byte offsets spelled out in stash.h's order (its accessors cost scratch here)
         __amdgpu_buffer_rsrc_t xr = __amdgpu_buffer_rsrc_t();
         if constexpr (STASH)
-            xr = __builtin_amdgcn_make_buffer_rsrc(a.stash_x + tile * a.lay.x_tile, 0, (int)(a.lay.x_tile * 4), 0x00020000);
+            xr = stash_rsrc(a.lay.x_record(a.stash_x, tile), a.lay.x_tile);
         auto block_tail = [&](int blk, const H2Seg& after, bool slab_in, int next_c0, unsigned stash_net) {
             HS_T0();
             h2zero<NT, MT>(net);
@@ -472,18 +473,18 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
             // GEMM loops costs SGPR spills)
             const int vb = tile_view_base(a, tile * TM);
             const H2Seg after_view = v + 1 < a.NS ? s_in : (nvb < nb ? fc0seg(nvb) : s_in);
-            const unsigned x_view = STASH ? (unsigned)v * (unsigned)a.lay.x_view * 4u : 0u;
-            auto act_slot = [&](int i) { return x_view + ((unsigned)a.lay.x_act + (unsigned)i * (unsigned)STASH_SLOT) * 4u; };
+            const unsigned x_view = STASH ? stash_bytes((unsigned)v * (unsigned)a.lay.x_view) : 0u;
+            auto act_slot = [&](int i) { return x_view + stash_bytes((unsigned)a.lay.o_act + (unsigned)i * (unsigned)STASH_SLOT); };
             HS_T0();
             H2SYNC_P();
-            h2prologue<STASH>(a, v, tile, planes, tap_tab, tid, a.range_flag, xr, x_view + (unsigned)a.lay.x_in * 4u, tap_raw);
+            h2prologue<STASH>(a, v, tile, planes, tap_tab, tid, a.range_flag, xr, x_view + stash_bytes((unsigned)a.lay.o_in), tap_raw);
             h2zero<NT, MT>(h);
             H2SYNC_P();
             if constexpr (STASH) {
                 // z = the interpolated latent of this view (reference encoder.py:101), the B operand of lin_z's weight
                 // gradient: gathered from the latent itself, 128 channels at a time, two chunks in flight, written straight
                 // to the stash (a lane holds 4 channels of one sample = one float4 of the [channel/4][sample] tile)
-                const unsigned xz = x_view + (unsigned)a.lay.x_z * 4u;
+                const unsigned xz = x_view + stash_bytes((unsigned)a.lay.o_z);
                 gather_setup<C>(g, a.latent + (size_t)(vb + v) * a.Hl * a.Wl * a.L, tap_raw, wave, lane);
                 const int nch = a.L / GCH;
                 const unsigned zlane = (unsigned)(((lane >> 3) * TM + (wave % 8) * 8 + (lane & 7)) * 16);
@@ -573,7 +574,7 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
                 HS_LAP(HS_SLAB);
             }
         }
-        auto post_slot = [&](int i) { return ((unsigned)a.lay.x_post + (unsigned)i * (unsigned)STASH_SLOT) * 4u; };
+        auto post_slot = [&](int i) { return stash_bytes((unsigned)a.lay.x_post + (unsigned)i * (unsigned)STASH_SLOT); };
         for (int blk = nvb; blk < nb; ++blk) {
             HS_T0();
             H2SYNC();
@@ -646,20 +647,13 @@ bool mlp_h2_supports(int n_blocks, int combine_layer) { return n_blocks <= h2::M
 
 template <bool STASH>
 static void launch_mlp_h2_t(const MlpArgs& a, int grid, hipStream_t st) {
-    static bool attr_set[64] = {};
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
-    dev_ &= 63;
 #ifdef PNY_H2_EXP_STAGGER
     const int extra = h2::TAP_BYTES + 64;
 #else
     const int extra = STASH ? h2::TAP_BYTES : 0;   // second tap table
 #endif
-    if (!attr_set[dev_]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(PNY_H2_KERNEL<STASH>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  h2::lds_bytes(h2::MAX_NB) + extra);
-        attr_set[dev_] = true;
-    }
+    static LdsLimit lds;
+    (void)lds.raise(h2::lds_bytes(h2::MAX_NB) + extra, PNY_H2_KERNEL<STASH>);
 #ifdef PNY_H2_STAMP
     static unsigned long long* dbuf = nullptr;
     constexpr int NWV = h2::THREADS / 64;

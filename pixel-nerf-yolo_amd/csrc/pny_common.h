@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../include/pnyolo.h"
+#include "stash.h"
 
 namespace pny {
 
@@ -15,6 +16,7 @@ constexpr int MAX_BLOCKS = 8;
 constexpr int MAX_VIEWS = 16;
 constexpr int D_IN_PAD = 64;    // 42 inputs padded to 8 k-iterations (a multiple of the weight-ring depth)
 constexpr int ACT_KG = 128;     // k-groups (4 features each) held by the LDS activation buffer
+static_assert(STASH_ROWS == HID && STASH_SMALL_ROWS == D_IN_PAD, "stash.h slot sizes");
 
 // World->camera pose and intrinsics of one source view (reference models.py:74-87 buffers).
 struct Cam {
@@ -36,24 +38,6 @@ struct MlpWeights {
     const float* w_out;
     const float* b_out;
 };
-
-// Training stash (64-sample tiles; every tensor slot is [feature/4][64 samples] float4, i.e. the LDS B-operand layout):
-//   X record of a tile  = NS views x { x_in (16 rows), z (L/4 rows), per view block b: relu(h_in(b)), relu(net(b)) }
-//                         + post part { per post block: relu(h_in(b)), relu(net(b)) ; relu(h_top) }
-//   dY record of a tile = NS views x { per view block b: dnet(b), dh_in(b) }
-//                         + post part { d_raw (16 rows), dh_top, per post block b: dnet(b), dh_in(b) }
-//     (dh_in of the first post-combine block holds dhm = dh / NS, the gradient every view's last block receives; when
-//      there is no post-combine block dhm IS dh_top)
-// Offsets are in floats.  SLOT = 64 * 512 floats.
-struct StashLayout {
-    long long x_tile, dy_tile;       // record strides
-    int x_view, x_in, x_z, x_act;    // view stride; offsets inside a view
-    int x_post;                      // offset of the post part inside a record
-    int dy_view;                     // view stride (offset of a view's first slot is v * dy_view)
-    int dy_post;                     // offset of the post part: d_raw, dh_top, then the post blocks
-};
-constexpr int STASH_SLOT = 64 * HID;
-constexpr int STASH_SMALL = 64 * D_IN_PAD;  // 16-row slots: x_in, d_raw
 
 struct MlpArgs {
     MlpWeights w;
@@ -191,7 +175,7 @@ struct DzArgs {
     int d_in;
     const float* zp;      // projected maps of this MLP (api.hip ensure_projection) or null
     int zp_stride;
-    int NS, Hl, Wl, nvb, npost, yolo, num_freqs;
+    int NS, Hl, Wl, yolo, num_freqs;
     long long obj_pts;    // grouped scene (MlpArgs::obj_pts): samples per object, 0 = one object
     float freq_factor, sx, sy;
     float* dz;            // (n_points of the pass) accumulated
@@ -301,6 +285,26 @@ void launch_nhwc_to_nchw(const float* in, float* out, int n, int c, int hw, hipS
 __device__ __forceinline__ void range_report(unsigned* flag, unsigned bit) {
     if (flag) __hip_atomic_fetch_or(flag, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+
+// Dynamic-LDS limit of the kernels of one launch site, raised at most once per device and size.  One `static` instance per
+// site; the call names every kernel the site launches (two instantiations of a template share a type, not a limit).
+struct LdsLimit {
+    size_t set[64] = {};
+    template <class... K>
+    hipError_t raise(size_t bytes, K... kernels) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        dev &= 63;
+        if (bytes <= set[dev]) return hipSuccess;
+        hipError_t e = hipSuccess;
+        for (const void* k : {reinterpret_cast<const void*>(kernels)...}) {
+            const hipError_t ek = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+            if (ek != hipSuccess) e = ek;
+        }
+        if (e == hipSuccess) set[dev] = bytes;
+        return e;
+    }
+};
 
 // error plumbing
 void set_error(const std::string& msg);

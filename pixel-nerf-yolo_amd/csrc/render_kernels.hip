@@ -240,15 +240,8 @@ void launch_sample_fine(const float* rays, const float* zc, const float* w, cons
                         const float* g, uint64_t seed, float* zout, hipStream_t st) {
     if (n == 0) return;
     const size_t lds = (size_t)FINE_WAVES * (3 * kc + 1 + kf + kc + kf) * sizeof(float);
-    static size_t max_set[64] = {};  // per device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev &= 63;
-    if (lds > 48 * 1024 && lds > max_set[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sample_fine_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        max_set[dev] = lds;
-    }
+    static LdsLimit limit;
+    if (lds > 48 * 1024) (void)limit.raise(lds, sample_fine_kernel);
     hipLaunchKernelGGL(sample_fine_kernel, dim3((unsigned)((n + FINE_WAVES - 1) / FINE_WAVES)), dim3(64 * FINE_WAVES), lds,
                        st, rays, zc, w, depth, n, kc, kf, kfd, depth_std, lindisp, u, u2, g, seed, zout);
 }

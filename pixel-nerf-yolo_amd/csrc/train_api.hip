@@ -11,23 +11,6 @@
 
 using namespace pny;
 
-namespace pny {
-StashLayout stash_layout(const pny_model_desc& d, int ns, int L) {
-    const int nb = d.n_blocks, nvb = view_blocks(d), npost = nb - nvb;
-    StashLayout l;
-    l.x_in = 0;
-    l.x_z = STASH_SMALL;
-    l.x_act = STASH_SMALL + L * 64;
-    l.x_view = l.x_act + 2 * nvb * STASH_SLOT;
-    l.x_post = ns * l.x_view;
-    l.x_tile = (long long)l.x_post + (long long)(2 * npost + 1) * STASH_SLOT;
-    l.dy_view = 2 * nvb * STASH_SLOT;
-    l.dy_post = ns * l.dy_view;
-    l.dy_tile = (long long)l.dy_post + STASH_SMALL + (long long)(1 + 2 * npost) * STASH_SLOT;
-    return l;
-}
-}  // namespace pny
-
 namespace {
 
 struct TrainPlan {
@@ -41,28 +24,21 @@ float* grad_of(const pny_model* m, const std::string& name) {
     return it == m->grads.end() ? nullptr : it->second;
 }
 
-// Stash layout and the list of weight-gradient GEMMs of one MLP (pny_common.h StashLayout for the slot order).
+// Stash layout and the list of weight-gradient GEMMs of one MLP: each job is (dY slot and its per-view stride, rows, X slot and
+// stride, columns, views reduced over, target tensors), the slots named by stash.h for view 0; stride 0 = one slot per tile.
 TrainPlan build_plan(const pny_model* m, int ns, int L, const std::string& pre) {
     const pny_model_desc& d = m->desc;
-    const int nb = d.n_blocks, nvb = view_blocks(d), npost = nb - nvb;
-    const int d_in = pny::d_in(d);
     TrainPlan p;
     p.lay = stash_layout(d, ns, L);
-    StashLayout& l = p.lay;
-    auto xact = [&](int i) { return (long long)l.x_act + (long long)i * STASH_SLOT; };
-    auto xpost = [&](int i) { return (long long)l.x_post + (long long)i * STASH_SLOT; };
-    auto dyv = [&](int i) { return (long long)i * STASH_SLOT; };
-    const long long draw = l.dy_post;
-    auto dypost = [&](int i) { return (long long)l.dy_post + STASH_SMALL + (long long)i * STASH_SLOT; };
-    const long long dhm = npost > 0 ? dypost(2) : dypost(0);
-    auto add = [&](long long a_off, int a_view, int a_rows, long long x_off, int x_view, int x_cols, int n_views,
+    const StashLayout& l = p.lay;
+    auto add = [&](unsigned dy_slot, int dy_stride, int a_rows, unsigned x_slot, int x_stride, int x_cols, int n_views,
                    const std::string& wname, int rows_valid, int cols_valid, const std::string& b0, const std::string& b1) {
         DwJob j;
-        j.a_off = a_off;
-        j.a_view = a_view;
+        j.a_off = dy_slot;
+        j.a_view = dy_stride;
         j.a_rows = a_rows;
-        j.x_off = x_off;
-        j.x_view = x_view;
+        j.x_off = x_slot;
+        j.x_view = x_stride;
         j.x_cols = x_cols;
         j.n_views = n_views;
         DwTarget t;
@@ -79,24 +55,21 @@ TrainPlan build_plan(const pny_model* m, int ns, int L, const std::string& pre) 
     };
     auto blk = [&](int b) { return pre + "blocks." + std::to_string(b); };
     auto lz = [&](int b) { return pre + "lin_z." + std::to_string(b); };
-    // lin_out: dY = d_raw (16-row slot, d_out rows valid), X = relu(h_top)
-    add(draw, 0, D_IN_PAD, xpost(2 * npost), 0, HID, 1, pre + "lin_out.weight", d.d_out, HID, pre + "lin_out.bias", "");
-    for (int b = nvb; b < nb; ++b) {  // post-combine blocks
-        const int i = b - nvb;
-        add(dypost(1 + 2 * i), 0, HID, xpost(2 * i), 0, HID, 1, blk(b) + ".fc_0.weight", HID, HID, blk(b) + ".fc_0.bias", "");
-        add(b == nb - 1 ? dypost(0) : dypost(2 + 2 * (i + 1)), 0, HID, xpost(2 * i + 1), 0, HID, 1, blk(b) + ".fc_1.weight", HID, HID,
-            blk(b) + ".fc_1.bias", "");
+    // lin_out: d_out of the 64 rows of d_raw are valid
+    add(l.dy_raw(), 0, D_IN_PAD, l.x_top(), 0, HID, 1, pre + "lin_out.weight", d.d_out, HID, pre + "lin_out.bias", "");
+    for (int i = 0; i < l.npost(); ++i) {  // post-combine blocks
+        const std::string b = blk(l.nvb() + i);
+        add(l.dy_post_dnet(i), 0, HID, l.x_post_h(i), 0, HID, 1, b + ".fc_0.weight", HID, HID, b + ".fc_0.bias", "");
+        add(l.dy_post_fc1(i), 0, HID, l.x_post_net(i), 0, HID, 1, b + ".fc_1.weight", HID, HID, b + ".fc_1.bias", "");
     }
-    for (int b = 0; b < nvb; ++b) {  // per-view blocks: reduce over the views too
-        add(dyv(2 * b), l.dy_view, HID, xact(2 * b), l.x_view, HID, ns, blk(b) + ".fc_0.weight", HID, HID, blk(b) + ".fc_0.bias", "");
-        const bool last = b == nvb - 1;
-        add(last ? dhm : dyv(2 * (b + 1) + 1), last ? 0 : l.dy_view, HID, xact(2 * b + 1), l.x_view, HID, ns,
-            blk(b) + ".fc_1.weight", HID, HID, blk(b) + ".fc_1.bias", last ? std::string() : lz(b + 1) + ".bias");
-        add(dyv(2 * b + 1), l.dy_view, HID, l.x_z, l.x_view, L, ns, lz(b) + ".weight", HID, L, "", "");
+    for (int b = 0; b < l.nvb(); ++b) {  // per-view blocks; lin_z[b + 1]'s bias shares fc_1's column sum
+        add(l.dy_dnet(0, b), l.dy_view, HID, l.x_h(0, b), l.x_view, HID, ns, blk(b) + ".fc_0.weight", HID, HID, blk(b) + ".fc_0.bias", "");
+        add(l.dy_fc1(0, b), l.dy_fc1_stride(b), HID, l.x_net(0, b), l.x_view, HID, ns, blk(b) + ".fc_1.weight", HID, HID, blk(b) + ".fc_1.bias",
+            b + 1 < l.nvb() ? lz(b + 1) + ".bias" : std::string());
+        add(l.dy_dh(0, b), l.dy_view, HID, l.x_z(0), l.x_view, L, ns, lz(b) + ".weight", HID, L, "", "");
     }
-    // lin_in: dY = the gradient at the first block's entry (dhm when the mean follows lin_in directly)
-    add(nvb > 0 ? dyv(1) : dhm, nvb > 0 ? l.dy_view : 0, HID, l.x_in, l.x_view, D_IN_PAD, ns, pre + "lin_in.weight", HID, d_in,
-        pre + "lin_in.bias", nvb > 0 ? lz(0) + ".bias" : std::string());
+    add(l.dy_lin_in(0), l.dy_view, HID, l.x_in(0), l.x_view, D_IN_PAD, ns, pre + "lin_in.weight", HID, d_in(d), pre + "lin_in.bias",
+        l.nvb() > 0 ? lz(0) + ".bias" : std::string());
     return p;
 }
 
@@ -315,16 +288,16 @@ int mlp_backward(pny_scene* s, int mode, const float* xyz, const float* dirs, co
     float* dy_base = nullptr;
     if (have_x) {
         chunk_pts = n_points;
-        x_base = m->dx_stash[stashed->which].f() + stashed->tile0 * plan.lay.x_tile;
-        dy_base = m->ddy_stash[stashed->which].f() + stashed->tile0 * plan.lay.dy_tile;
+        x_base = plan.lay.x_record(m->dx_stash[stashed->which].f(), stashed->tile0);
+        dy_base = plan.lay.dy_record(m->ddy_stash[stashed->which].f(), stashed->tile0);
     } else if (defer) {
         const long long tiles = (n_points + 63) / 64;
         if (obj_views(s) != m->defer_ns) return fail(PNY_ERR_STATE, "deferred weight gradients: scene view count differs from the reservation");
         if (m->defer_used[which] + tiles > m->defer_cap[which])
             return fail(PNY_ERR_STATE, "deferred weight gradients: more tiles than pny_model_defer_weight_grads reserved");
         chunk_pts = n_points;   // one chunk: the reservation was made against the budget
-        x_base = m->dx_stash[which].f() + m->defer_used[which] * plan.lay.x_tile;
-        dy_base = m->ddy_stash[which].f() + m->defer_used[which] * plan.lay.dy_tile;
+        x_base = plan.lay.x_record(m->dx_stash[which].f(), m->defer_used[which]);
+        dy_base = plan.lay.dy_record(m->ddy_stash[which].f(), m->defer_used[which]);
         m->defer_used[which] += tiles;
     } else {
         if ((rc = s->x_stash.reserve((size_t)chunk_tiles_max * plan.lay.x_tile * sizeof(float)))) return rc;
@@ -452,8 +425,6 @@ int mlp_backward(pny_scene* s, int mode, const float* xyz, const float* dirs, co
             dz.obj_pts = a.obj_pts;
             dz.Hl = s->hl;
             dz.Wl = s->wl;
-            dz.nvb = view_blocks(d);
-            dz.npost = d.n_blocks - view_blocks(d);
             dz.yolo = d.yolo;
             dz.num_freqs = d.num_freqs;
             dz.freq_factor = d.freq_factor;
@@ -674,10 +645,10 @@ int pny_render_backward(pny_scene* s, const float* rays_dev, int64_t n, const pn
     const bool depth_path = any_f && kfd > 0 && sv->depth_coarse;
     {   // a pass that was stashed by the forward but receives no gradient must not leave stale dY tiles for the flush
         pny_model* m = s->m;
-        const long long dy_tile = stash_layout(m->desc, obj_views(s), s->L).dy_tile;
+        const StashLayout lay = stash_layout(m->desc, obj_views(s), s->L);
         auto zero_pass = [&](const pny_scene::StashedPass& sp) -> int {
             if (sp.valid && m->defer && !immediate && sp.epoch == m->defer_epoch)
-                PNY_HIP(hipMemsetAsync(m->ddy_stash[sp.which].f() + sp.tile0 * dy_tile, 0, (size_t)sp.tiles * dy_tile * sizeof(float), st));
+                PNY_HIP(hipMemsetAsync(lay.dy_record(m->ddy_stash[sp.which].f(), sp.tile0), 0, (size_t)sp.tiles * lay.dy_tile * sizeof(float), st));
             return 0;
         };
         if (do_fine && !any_f && (rc = zero_pass(s->stashed[1]))) return rc;

@@ -167,14 +167,16 @@ def test_query_backward_yolo_mode():
 
 
 # --------------------------------------------------------------------------- render backward
-@pytest.mark.parametrize("with_depth,detach", [(False, True), (True, True), (False, False), (True, False)])
-def test_render_backward_vs_oracle(with_depth, detach):
+@pytest.mark.parametrize("with_depth,detach,n_blocks,combine_layer",
+                         [(False, True, 5, 3), (True, True, 5, 3), (False, False, 5, 3), (True, False, 5, 3), (True, False, 2, 0)],
+                         ids=["False-True", "True-True", "False-False", "True-False", "True-False-combine0"])
+def test_render_backward_vs_oracle(with_depth, detach, n_blocks, combine_layer):
     """The trainer's loss (MSE on coarse.rgb + MSE on fine.rgb, PixelNerfTrainer.py:133-156) through the renderer.
     detach = False is the reference's graph: the fine pass's depth samples are centred on the ATTACHED coarse depth
     (nerf.py:156-167, 296-298), so the fine loss reaches mlp_coarse through the sample positions (positional code,
     projection, bilinear latent lookup).  detach = True cuts that path on both sides (isolates the parameter path)."""
     ns, H, W, kc, kf, kfd, n = 2, 32, 32, 16, 8, 4, 40
-    net, sc = scene_pair(ns, H, W, 512, 4, 5, 3, 700)
+    net, sc = scene_pair(ns, H, W, 512, 4, n_blocks, combine_layer, 700)
     _, tgt = synth.scene_cameras(ns)
     rs = np.random.RandomState(9)
     nc = H * W
