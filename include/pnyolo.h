@@ -12,7 +12,8 @@
  *   - every function returns 0 on success or a negative pny_status; it never throws.
  *     pny_last_error() returns a thread-local message for the last failure.
  *   - *_dev pointers are device (HIP) pointers owned by the caller and borrowed for the call;
- *     *_host pointers are host memory.  All floating point data is fp32, row-major.
+ *     *_host pointers are host memory.  All floating point data is fp32, row-major (one exception:
+ *     the fp64 results of pny_view_metrics).
  *   - work is enqueued on the caller's stream (hipStream_t passed as void*); the library does
  *     not synchronise except where a function says so.
  *   - a pny_model owns packed weights; a pny_scene owns the per-scene state the reference keeps
@@ -656,6 +657,42 @@ int pny_finite_check(pny_finite* f, int first, int n, int32_t* flags_dev, pny_st
 int pny_finite_check_tensors(const float* const* ptrs, const int64_t* counts, const int32_t* groups, int n, int32_t* flags_dev,
                              pny_stream stream);
 int pny_finite_reset(int32_t* flags_dev, int n_groups, pny_stream stream);
+
+/* ---- view metrics: the clamped 8-bit image, PSNR and SSIM of every rendered view in ONE launch (csrc/metrics.hip).
+ * Replaces the scoring tail of the reference's eval scripts (eval/eval.py:288-345, eval/calc_metrics.py:189-191), which bring
+ * every render to the host and call skimage there, and util.psnr (src/util/util.py:502).  Model-free, raw device pointers,
+ * enqueued on `stream`; nothing waits for the device and the results stay on the device.  Sums are accumulated in fp64 in a
+ * fixed order without float atomics: the same inputs give the same bits on every run.  The first call on a stream allocates
+ * that stream's reduction workspace (1 MiB, kept; a launch of more than 65 536 tiles replaces it, and that alone waits for the
+ * device); not for graph capture.
+ *
+ * rgb_dev (NV, H, W, 3): the renders.  x = clamp(rgb, 0, 1) in fp32 (eval.py:288).
+ * gt_dev: PNY_GT_NHWC_01   (NV, H, W, 3) in [0, 1], taken as given (calc_metrics.py);
+ *         PNY_GT_NCHW_PM1  (NV, 3, H, W) in [-1, 1], the dataset's `images`: y = fl32(g * 0.5 + 0.5) (eval.py:315).
+ * rgb8_dev (NV, H, W, 3) (or NULL) = (uint8) trunc(fl32(x * 255)), numpy's (all_rgb * 255).astype(np.uint8) (eval.py:291).
+ * metrics_dev (NV, 2) (or NULL: the launch only converts) = per view {psnr, ssim}, fp64 because the reference reports Python
+ * floats (the one exception to "all floating point data is fp32"):
+ *   psnr = 10 log10(1 / mean((x - y)^2)) over the view's H * W * 3 elements, difference, squares and mean in fp64
+ *          (skimage compare_psnr, data_range = 1); identical images give +inf;
+ *   ssim = skimage compare_ssim(multichannel=True, data_range=1): win_size 7, uniform window, sample covariance, K1 = 0.01,
+ *          K2 = 0.03; the mean of S over the (H - 6) (W - 6) windows inside the image, per channel, then over the 3 channels;
+ *          the five moments of a window are fp64 sums.
+ * A NaN prediction makes both metrics of ITS view NaN and writes byte 0.
+ * PNY_GT_FLAT: util.psnr's form.  rgb_dev and gt_dev are (NV, height * width) plain elements, compared as given (no clamp, no
+ * channels, any height and width >= 1): psnr = -10 log10(mean((p - t)^2)), ssim = NaN; rgb8_dev must be NULL.
+ * PNY_ERR_ARG: a NULL desc, rgb_dev or gt_dev, both outputs NULL, a non-positive size, height or width below 7 (except
+ * PNY_GT_FLAT), an unknown gt_layout, win_size other than 7, or 2^31 or more elements (NV * H * W * 3). */
+#define PNY_GT_NHWC_01 0
+#define PNY_GT_NCHW_PM1 1
+#define PNY_GT_FLAT 2
+typedef struct pny_view_metrics_desc {
+    int32_t n_views, height, width; /* channels = 3 */
+    int32_t gt_layout;              /* PNY_GT_NHWC_01 | PNY_GT_NCHW_PM1 | PNY_GT_FLAT */
+    int32_t win_size;               /* 7; anything else is PNY_ERR_ARG in this build */
+} pny_view_metrics_desc;
+int pny_view_metrics(const pny_view_metrics_desc* desc, const float* rgb_dev, const float* gt_dev,
+                     double* metrics_dev /* (NV, 2) {psnr, ssim}, or NULL */,
+                     uint8_t* rgb8_dev /* (NV, H, W, 3), or NULL */, pny_stream stream);
 
 #ifdef __cplusplus
 }

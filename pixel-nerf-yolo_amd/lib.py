@@ -81,6 +81,11 @@ class YoloLossDesc(C.Structure):
                 ("no_object_loss", C.c_float), ("class_loss", C.c_float)]
 
 
+class ViewMetricsDesc(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("gt_layout", C.c_int32),
+                ("win_size", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/pnyolo.h declares
 SIGNATURES = {
     "pny_version": (C.c_int, []),
@@ -173,6 +178,7 @@ SIGNATURES = {
     "pny_finite_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pny_finite_check_tensors": (C.c_int, [C.POINTER(C.c_void_p), c_i64_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p]),
     "pny_finite_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "pny_view_metrics": (C.c_int, [C.POINTER(ViewMetricsDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -186,6 +192,8 @@ LAST_PRECISION = {0: "f32", 1: "f16x2", 2: "f16"}   # pny_scene_last_precision, 
 RANGE_BITS = {1: "activation", 2: "gradient", 4: "weight"}   # include/pnyolo.h PNY_RANGE_*
 YOLO_BATCH_MAX_VIEWS, YOLO_BATCH_MAX_SCALES = 16, 4           # PNY_YOLO_BATCH_MAX_*
 FINITE_NAN, FINITE_INF, FINITE_MAX_IMMEDIATE = 1, 2, 8        # PNY_FINITE_*
+GT_LAYOUT = {"nhwc01": 0, "nchw_pm1": 1}                      # PNY_GT_NHWC_01, PNY_GT_NCHW_PM1
+GT_FLAT, METRICS_WIN = 2, 7                                   # PNY_GT_FLAT (util.psnr's form); the SSIM window of this build
 
 
 class PnyError(RuntimeError):

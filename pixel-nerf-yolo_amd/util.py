@@ -5,7 +5,8 @@ device (that of ``poses``, or the current one when ``poses`` is a CPU tensor as 
 ``sample_train_batch`` is the trainer's ray batch and ground truth in one launch (no counterpart function in the reference:
 it replaces the per-object loop of train/trainlib/PixelNerfTrainer.py:76-123).  ``yolo_train_batch`` /
 ``stage_yolo_targets`` and ``FiniteMonitor`` are the same for the YOLO trainer: the batch of train/trainlib/YoloTrainer.py:93-129
-in one launch, and its NaN / Inf tests (:163-194) without a host wait.
+in one launch, and its NaN / Inf tests (:163-194) without a host wait.  ``psnr`` is the reference's util.psnr (:502-509) on
+device tensors (metrics.py).
 """
 import ctypes as C
 
@@ -13,6 +14,7 @@ import torch
 
 from . import lib as _lib
 from .lib import check, ptr, stream_of
+from .metrics import psnr  # noqa: F401  (the reference's util.psnr)
 
 
 def _pair(v, name):
