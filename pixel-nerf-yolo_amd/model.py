@@ -409,10 +409,16 @@ class PixelNeRFNet(nn.Module):
     def _handles(self):
         return list(self._h_scenes) + ([self._h_group] if self._h_group is not None else [])
 
+    def _last_grouped(self):
+        """True when the last render call was one launch on the grouped scene, which then holds the call's records."""
+        return self._last_call_group and self._group is not None
+
+    def _last_handle(self, scene):
+        """The handle that holds the last call's records of object `scene`."""
+        return self._h_group if self._last_grouped() else self._scene(scene)
+
     def _stat_handles(self):
-        if self._last_call_group and self._group is not None:
-            return [self._h_group]
-        return self._h_scenes[: max(self.num_objs, 1)]
+        return [self._h_group] if self._last_grouped() else self._h_scenes[: max(self.num_objs, 1)]
 
     @staticmethod
     def _cam_rows(t, sb, SB, NS):
@@ -506,8 +512,7 @@ class PixelNeRFNet(nn.Module):
         """True when the last backward of scene `scene` (or of the grouped scene, when the last call was grouped) that
         computed a latent gradient took the deterministic path (include/pnyolo.h pny_scene_last_latent_grad_mode)."""
         v = C.c_int(0)
-        h = self._h_group if (self._last_call_group and self._group is not None) else self._scene(scene)
-        check(_lib.load().pny_scene_last_latent_grad_mode(h, C.byref(v)))
+        check(_lib.load().pny_scene_last_latent_grad_mode(self._last_handle(scene), C.byref(v)))
         return bool(v.value)
 
     def range_status(self, clear=False):
@@ -571,14 +576,12 @@ class PixelNeRFNet(nn.Module):
         """The arithmetic of the dX chain of the last backward of scene `scene` (or of the grouped scene, when the last
         call was grouped): 'f32' | 'f16x2' | 'f16' (include/pnyolo.h pny_scene_last_backward_precision)."""
         v = C.c_int(0)
-        h = self._h_group if (self._last_call_group and self._group is not None) else self._scene(scene)
-        check(_lib.load().pny_scene_last_backward_precision(h, C.byref(v)))
+        check(_lib.load().pny_scene_last_backward_precision(self._last_handle(scene), C.byref(v)))
         return _lib.LAST_PRECISION[int(v.value)]
 
     def _last_precision_code(self, scene):
         v = C.c_int(0)
-        h = self._h_group if (self._last_call_group and self._group is not None) else self._scene(scene)
-        check(_lib.load().pny_scene_last_precision(h, C.byref(v)))
+        check(_lib.load().pny_scene_last_precision(self._last_handle(scene), C.byref(v)))
         return int(v.value)
 
     def project_latent(self):
@@ -648,26 +651,21 @@ class PixelNeRFNet(nn.Module):
             return getattr(self, "_latent_src", None)
         return None
 
-    def begin_latent_grad(self, meta, n_scenes, group=False):
-        """Zeroed (SB * NS, Hl, Wl, L) accumulator bound slice by slice to the scenes (pny_scene_bind_latent_grad), or whole to
-        the grouped scene."""
+    def begin_latent_grad(self, meta, handles):
+        """Zeroed (SB * NS, Hl, Wl, L) accumulator bound in equal slices to the scene handles (pny_scene_bind_latent_grad):
+        the per-object scenes take their own views each, the grouped scene takes it whole."""
         n_lat, l_ch, hl, wl = meta[0]
         self._latent_grad_deterministic()
         buf = torch.zeros(n_lat, hl, wl, l_ch, device=self._device(), dtype=torch.float32)
-        if group:
-            check(_lib.load().pny_scene_bind_latent_grad(self._h_group, ptr(buf)))
-            return buf
-        nsv = n_lat // n_scenes
-        for sb in range(n_scenes):
-            check(_lib.load().pny_scene_bind_latent_grad(self._scene(sb), ptr(buf[sb * nsv:(sb + 1) * nsv])))
+        nsv = n_lat // len(handles)
+        for i, h in enumerate(handles):
+            check(_lib.load().pny_scene_bind_latent_grad(h, ptr(buf[i * nsv:(i + 1) * nsv])))
         return buf
 
-    def end_latent_grad(self, buf, meta, n_scenes, group=False):
+    def end_latent_grad(self, buf, meta, handles):
         """Unbind and return the gradient in the latent's own layout (SB * NS, L, Hl, Wl), device and dtype."""
-        if group:
-            check(_lib.load().pny_scene_bind_latent_grad(self._h_group, None))
-        for sb in range(0 if group else n_scenes):
-            check(_lib.load().pny_scene_bind_latent_grad(self._scene(sb), None))
+        for h in handles:
+            check(_lib.load().pny_scene_bind_latent_grad(h, None))
         return buf.permute(0, 3, 1, 2).contiguous().to(meta[1], meta[2])   # packed NCHW, like the latent it belongs to
 
     def bind_mlp_grads(self):
@@ -1067,11 +1065,12 @@ class _QueryFunction(torch.autograd.Function):
         use_coarse = bool(ctx.coarse) or net.mlp_fine is None
         st = stream_of(dev)
         SB = ctx.xyz.shape[0]
-        lat_grad = net.begin_latent_grad(ctx.lat_meta, SB) if ctx.lat_meta is not None else None
+        scenes = [net._scene(sb) for sb in range(SB)]
+        lat_grad = net.begin_latent_grad(ctx.lat_meta, scenes) if ctx.lat_meta is not None else None
         for sb in range(SB):
-            check(L.pny_query_backward(net._scene(sb), ptr(ctx.xyz[sb]), ptr(ctx.dirs[sb]), ctx.xyz.shape[1], int(use_coarse),
+            check(L.pny_query_backward(scenes[sb], ptr(ctx.xyz[sb]), ptr(ctx.dirs[sb]), ctx.xyz.shape[1], int(use_coarse),
                                        ptr(g_out[sb]), 1, st))
-        extra = () if lat_grad is None else (net.end_latent_grad(lat_grad, ctx.lat_meta, SB),)
+        extra = () if lat_grad is None else (net.end_latent_grad(lat_grad, ctx.lat_meta, scenes),)
         net._lat_grad_event = None      # (unmarked: a trunk backward behind this one waits for the whole stream)
         return (None, None, None, None, None) + tuple(grads) + extra
 

@@ -5,6 +5,10 @@ signatures and return conventions, executing on libpnyolo.so.
 
 A render call is ONE C-ABI call per scene (pny_render / pny_yolo_render): sampling, point
 generation, the fused MLP, compositing, importance sampling and the sort all stay on the device.
+A training super-batch that one grouped scene holds (model.encode, pny_scene_set_groups) is ONE
+call for all its objects.  Both are the same code: G launches of R rays each (``_launches``), on
+row g of every tensor's (G, R, ...) view, forward (``NeRFRenderer._render``) and backward
+(``_RenderFunction.backward``) alike.
 The reference's ``eval_batch_size`` point-chunking exists only to bound its (rows x 554)
 intermediates; fusion removes them, so the attribute is kept for interface compatibility and
 ignored.
@@ -12,7 +16,8 @@ ignored.
 Random draws: the reference jitters unconditionally (nerf.py:117) and draws three more tensors
 in the fine pass -- they are inputs of the path.  By default a per-call Philox seed is used
 (in-kernel generation); ``renderer.draws = dict(u_coarse=, u_fine=, u_fine2=, g_depth=)`` replays
-explicit tensors instead (parity mode, consumed by the next call).
+explicit tensors instead (parity mode, consumed by the next call; ``noise_coarse=, noise_fine=``
+replay the training sigma noise).  The library takes them for every stage or for none.
 """
 import ctypes as C
 import os
@@ -55,8 +60,11 @@ class _MultiDeviceRenderWrapper(torch.nn.Module):
         without waiting, and gathers the tiles on ``gpus[0]`` with peer copies.
     Results: a ray renders to the same bits whatever range it is in (slice invariance), so with explicit draws
     the assembled output equals the single-device call bit for bit; with Philox draws each range has its own seed.
+    Every split call goes through ``_split`` (ranges from ``_ray_ranges``, per-range seed, draws and replica, the renderer's
+    state restored afterwards); on its device a range is an ordinary renderer call: one library call per scene, or one on the
+    replica's grouped scene in training.
     Training calls (grad mode) split the same way (_train_split): every device runs the training forward and backward of its ray
-    range on its replica, the replica's parameters enter the graph as device copies of the master's (``p.to(device)``: autograd
+    range on its replica, the replica's parameters enter the graph as device copies of the master's (``_leaves``, ``p.to(device)``: autograd
     carries each device's gradients back and sums them into the master's ``.grad``, as DataParallel's replicate / gather do), and
     the replicas pick the stepped weights up at the next call.  A latent that takes a gradient (trainable encoder: the trunk runs
     once, on the master) is a leaf of every device's graph in the same way: each device returns its share of d loss / d latent.
@@ -127,99 +135,97 @@ class _MultiDeviceRenderWrapper(torch.nn.Module):
             return part["rgb"], part["depth"]
         return outputs
 
-    def _train_split(self, rays, want_weights):
-        """Training call over several devices (see the class docstring): _RenderFunction per device on its replica, with
-        differentiable device copies of the master's parameters as the graph's leaves."""
-        net, ren = self.net, self.renderer
-        SB, B = rays.shape[0], rays.shape[1]
-        n_dev = len(self.gpus)
-        per = -(-B // n_dev)
-        per = -(-per // 64) * 64
-        bounds = [(min(B, i * per), min(B, (i + 1) * per)) for i in range(n_dev)]
-        named = net.trainable_mlp_parameters()
+    def _split(self, SB, B, body, train=False, prefetch=False, guard=None):
+        """One call over (SB, B) rays split on B across the devices.  For every non-empty range of _ray_ranges, in order:
+        fetch the replica, make its device current, give the renderer the range's own seed (``_calls + i``), its rows of the
+        explicit draws and (YOLO) the replica as its net, and run ``body(replica, device, lo, hi)``.  Once every device has
+        its work, ``guard(i, replica, again)`` looks at each range; ``again()`` repeats it, and a result it returns replaces
+        the range's.  The renderer's state is restored whatever happens.  Returns the results in range order."""
+        net, ren, n_dev = self.net, self.renderer, len(self.gpus)
+        yolo = isinstance(ren, YoloRenderer)
+        draws, calls, ren.draws = ren.draws, ren._calls, None
+        ranges = [(i, lo, hi) for i, (lo, hi) in enumerate(_ray_ranges(B, n_dev)) if hi > lo]
+
+        def visit(i, lo, hi, r):
+            dev = torch.device("cuda", self.gpus[i])
+            with torch.cuda.device(dev):
+                ren._calls = calls + i
+                if yolo:
+                    ren.net = r
+                if draws is not None:
+                    ren.draws = {k: torch.as_tensor(v).reshape(SB, B, -1)[:, lo:hi].reshape(SB * (hi - lo), -1) for k, v in draws.items()}
+                return body(r, dev, lo, hi)
+
+        try:
+            reps = {i: self._replica(i) for i, _, _ in ranges} if prefetch else {}
+            outs = []
+            for i, lo, hi in ranges:
+                if i not in reps:
+                    reps[i] = self._replica(i)
+                if train:
+                    reps[i].train()
+                outs.append(visit(i, lo, hi, reps[i]))
+            for j, (i, lo, hi) in enumerate(ranges if guard is not None else ()):
+                again = guard(i, reps[i], lambda: visit(i, lo, hi, reps[i]))
+                if again is not None:
+                    outs[j] = again
+        finally:
+            ren._calls, ren.draws = calls + n_dev, None
+            if yolo:
+                ren.net = net
+        return outs
+
+    def _leaves(self):
+        """The leaves of the per-device training graphs: -> (number of MLP parameters, leaves(device)).  ``leaves(device)``
+        are the master's trainable MLP parameters, then its latent if that takes a gradient (trainable encoder: each device
+        returns its share), as differentiable copies on that device."""
+        net = self.net
+        src = [p for _, p in net.trainable_mlp_parameters()]
+        n_params = len(src)
         lat_src = net.differentiable_latent()
         if lat_src is None:
             net.check_differentiable()
+        else:
+            src.append(lat_src)
+        return n_params, lambda dev: [p if p.device == dev else p.to(dev) for p in src]
+
+    def _train_split(self, rays, want_weights):
+        """Training call over several devices (see the class docstring): _RenderFunction per device on its replica, with
+        differentiable device copies of the master's parameters as the graph's leaves."""
+        ren = self.renderer
+        n_params, leaves = self._leaves()
         kf = int(ren.n_fine) if (ren.using_fine and ren.n_fine > 0) else 0
-        draws, calls = ren.draws, ren._calls
-        ren.draws = None
         dev0 = torch.device("cuda", self.gpus[0])
-        parts = []
-        try:
-            for i, (lo, hi) in enumerate(bounds):
-                if hi <= lo:
-                    continue
-                r = self._replica(i)
-                r.train()
-                dev = torch.device("cuda", self.gpus[i])
-                with torch.cuda.device(dev):
-                    ren._calls = calls + i
-                    if draws is not None:
-                        ren.draws = {k: torch.as_tensor(v).reshape(SB, B, -1)[:, lo:hi].reshape(SB * (hi - lo), -1) for k, v in draws.items()}
-                    leaves = [p if p.device == dev else p.to(dev) for _, p in named]
-                    n_params = len(leaves)
-                    if lat_src is not None:   # a latent that takes a gradient (trainable encoder): each device returns its share
-                        leaves.append(lat_src if lat_src.device == dev else lat_src.to(dev))
-                    outs = _RenderFunction.apply(ren, r, rays[:, lo:hi].to(dev), kf > 0, n_params, *leaves)
-                parts.append([o.to(dev0) for o in outs])
-        finally:
-            ren._calls, ren.draws = calls + n_dev, None
+
+        def body(r, dev, lo, hi):
+            outs = _RenderFunction.apply(ren, r, rays[:, lo:hi].to(dev), kf > 0, n_params, *leaves(dev))
+            return [o.to(dev0) for o in outs]
+        parts = self._split(rays.shape[0], rays.shape[1], body, train=True)
         cat = [torch.cat([p[j] for p in parts], dim=1) if parts[0][j].numel() else parts[0][j] for j in range(6)]
-        res = {"coarse": {"rgb": cat[0], "depth": cat[1]}}
-        if want_weights:
-            res["coarse"]["weights"] = cat[2]
-        if kf > 0:
-            res["fine"] = {"rgb": cat[3], "depth": cat[4]}
-            if want_weights:
-                res["fine"]["weights"] = cat[5]
-        return res
+        return _result(cat, kf > 0, want_weights)
 
     def _render_split(self, rays, want_weights):
-        net, ren = self.net, self.renderer
-        SB, B = rays.shape[0], rays.shape[1]
-        n_dev = len(self.gpus)
-        per = -(-B // n_dev)
-        per = -(-per // 64) * 64                   # whole 64-ray groups per device
-        bounds = [(min(B, i * per), min(B, (i + 1) * per)) for i in range(n_dev)]
-        draws, calls = ren.draws, ren._calls
-        ren.draws = None
-        reps = [self._replica(i) if hi > lo else None for i, (lo, hi) in enumerate(bounds)]
-        master_policy = net.f16_range_policy
+        ren = self.renderer
+        master_policy = self.net.f16_range_policy
 
-        def part(i, only_f32=False):
-            lo, hi = bounds[i]
-            r = reps[i]
-            dev = torch.device("cuda", self.gpus[i])
-            if only_f32:
-                r.set_matrix_precision("f32")
-            with torch.cuda.device(dev):
-                ren._calls = calls + i
-                if draws is not None:
-                    ren.draws = {k: torch.as_tensor(v).reshape(SB, B, -1)[:, lo:hi].reshape(SB * (hi - lo), -1) for k, v in draws.items()}
-                return ren._render(r, rays[:, lo:hi].to(dev), want_weights, save=False)[0]
-
-        try:
-            outs = [part(i) if reps[i] is not None else None for i in range(n_dev)]
-            # f16-range guard (model.guard_f16_range), after every device has its work: wait per device, repeat a range on fp32
-            for i, r in enumerate(reps):
-                if r is None or master_policy == "lazy" or not any(r.last_launch_f16x2(s) for s in range(len(r._h_scenes))):
-                    continue
-                torch.cuda.current_stream(torch.device("cuda", self.gpus[i])).synchronize()
-                bits = r.range_status(clear=False)
-                if bits:
-                    r.range_status(clear=True)
-                    if master_policy == "raise":
-                        raise _lib.PnyRangeError(r._range_message(bits))
-                    import warnings
-                    warnings.warn("libpnyolo: " + r._range_message(bits) + " -- repeating the rays of cuda:%d on the fp32 kernels" % self.gpus[i])
-                    outs[i] = part(i, only_f32=True)
-        finally:
-            ren._calls = calls + n_dev
+        def guard(i, r, again):   # f16-range guard (model.guard_f16_range): wait per device, repeat a range on fp32
+            if master_policy == "lazy" or not any(r.last_launch_f16x2(s) for s in range(len(r._h_scenes))):
+                return None
+            torch.cuda.current_stream(torch.device("cuda", self.gpus[i])).synchronize()
+            bits = r.range_status(clear=False)
+            if not bits:
+                return None
+            r.range_status(clear=True)
+            if master_policy == "raise":
+                raise _lib.PnyRangeError(r._range_message(bits))
+            import warnings
+            warnings.warn("libpnyolo: " + r._range_message(bits) + " -- repeating the rays of cuda:%d on the fp32 kernels" % self.gpus[i])
+            r.set_matrix_precision("f32")
+            return again()
+        outs = self._split(rays.shape[0], rays.shape[1], prefetch=True, guard=guard,   # (every replica first, then the launches)
+                           body=lambda r, dev, lo, hi: ren._render(r, rays[:, lo:hi].to(dev), want_weights, save=False)[0])
         dev0 = torch.device("cuda", self.gpus[0])
-        res = {}
-        for p in outs[[o is not None for o in outs].index(True)]:
-            res[p] = {k: torch.cat([o[p][k].to(dev0) for o in outs if o is not None], dim=1) for k in outs[0][p]}
-        return res
+        return {p: {k: torch.cat([o[p][k].to(dev0) for o in outs], dim=1) for k in outs[0][p]} for p in outs[0]}
 
 
 class _MultiDeviceYoloWrapper(_MultiDeviceRenderWrapper):
@@ -234,59 +240,41 @@ class _MultiDeviceYoloWrapper(_MultiDeviceRenderWrapper):
         net, ren = self.net, self.renderer
         training = torch.is_grad_enabled() and net.training and (net.trainable_mlp_parameters() or net.differentiable_latent() is not None)
         flat = rays.reshape(-1, 8)
-        N, n_dev = flat.shape[0], len(self.gpus)
-        if N < 64 * n_dev:
+        N = flat.shape[0]
+        if N < 64 * len(self.gpus):
             ren.net = net
             return ren(rays)
-        per = -(-(-(-N // n_dev)) // 64) * 64
-        bounds = [(min(N, i * per), min(N, (i + 1) * per)) for i in range(n_dev)]
-        draws, calls = ren.draws, ren._calls
-        if training:   # as _MultiDeviceRenderWrapper._train_split: per-device graphs whose leaves are device copies of the master's
-            named, lat_src = net.trainable_mlp_parameters(), net.differentiable_latent()
-            if lat_src is None:
-                net.check_differentiable()
-            dev0 = torch.device("cuda", self.gpus[0])
-            parts = []
-            try:
-                for i, (lo, hi) in enumerate(bounds):
-                    if hi <= lo:
-                        continue
-                    r = self._replica(i)
-                    r.train()
-                    dev = torch.device("cuda", self.gpus[i])
-                    with torch.cuda.device(dev):
-                        ren.net, ren._calls = r, calls + i
-                        ren.draws = None if draws is None else {"u_coarse": torch.as_tensor(draws["u_coarse"]).reshape(N, -1)[lo:hi]}
-                        leaves = [p if p.device == dev else p.to(dev) for _, p in named]
-                        n_params = len(leaves)
-                        if lat_src is not None:
-                            leaves.append(lat_src if lat_src.device == dev else lat_src.to(dev))
-                        parts.append(_YoloRenderFunction.apply(ren, flat[lo:hi].to(dev), n_params, *leaves).to(dev0))
-            finally:
-                ren.net, ren._calls, ren.draws = net, calls + n_dev, None
-            return torch.cat(parts, dim=0)
-        outs = []
-        try:
-            for i, (lo, hi) in enumerate(bounds):
-                if hi <= lo:
-                    continue
-                r = self._replica(i)
-                dev = torch.device("cuda", self.gpus[i])
-                with torch.cuda.device(dev):
-                    ren.net, ren._calls = r, calls + i
-                    ren.draws = None if draws is None else {"u_coarse": torch.as_tensor(draws["u_coarse"]).reshape(N, -1)[lo:hi]}
-                    outs.append((i, r, ren._render(flat[lo:hi].to(dev))[0]))
-            for i, r, _ in outs:   # f16-range guard, after every device has its work
-                if net.f16_range_policy == "lazy" or not r.last_launch_f16x2():
-                    continue
-                torch.cuda.current_stream(torch.device("cuda", self.gpus[i])).synchronize()
-                bits = r.range_status(clear=True)
-                if bits:
-                    raise _lib.PnyRangeError(r._range_message(bits))
-        finally:
-            ren.net, ren._calls, ren.draws = net, calls + n_dev, None
         dev0 = torch.device("cuda", self.gpus[0])
-        return torch.cat([o.to(dev0) for _, _, o in outs], dim=0)
+        if training:   # as _train_split: per-device graphs whose leaves are device copies of the master's
+            n_params, leaves = self._leaves()
+            return torch.cat(self._split(1, N, train=True, body=lambda r, dev, lo, hi: _YoloRenderFunction.apply(
+                ren, flat[lo:hi].to(dev), n_params, *leaves(dev)).to(dev0)), dim=0)
+
+        def guard(i, r, again):
+            if net.f16_range_policy == "lazy" or not r.last_launch_f16x2():
+                return
+            torch.cuda.current_stream(torch.device("cuda", self.gpus[i])).synchronize()
+            bits = r.range_status(clear=True)
+            if bits:
+                raise _lib.PnyRangeError(r._range_message(bits))
+        outs = self._split(1, N, guard=guard, body=lambda r, dev, lo, hi: ren._render(flat[lo:hi].to(dev))[0])
+        return torch.cat([o.to(dev0) for o in outs], dim=0)
+
+
+def _ray_ranges(n, n_dev):
+    """(lo, hi) of the contiguous range of n rays that each of n_dev devices takes: whole 64-ray groups per device, so the
+    trailing ranges may be empty."""
+    per = -(-(-(-n // n_dev)) // 64) * 64
+    return [(min(n, i * per), min(n, (i + 1) * per)) for i in range(n_dev)]
+
+
+def _result(outs, has_fine, want_weights):
+    """The renderer's nested result from (rgb, depth, weights) of the coarse and of the fine pass."""
+    keys = ("rgb", "depth", "weights") if want_weights else ("rgb", "depth")
+    res = {"coarse": dict(zip(keys, outs[:3]))}
+    if has_fine:
+        res["fine"] = dict(zip(keys, outs[3:6]))
+    return res
 
 
 def _mark_latent_grad(model, extra, dev):
@@ -304,7 +292,7 @@ def _mark_latent_grad(model, extra, dev):
 
 class _RenderFunction(torch.autograd.Function):
     """NeRFRenderer.forward under autograd: forward = the ordinary pny_render (with its z / per-sample outputs kept),
-    backward = pny_render_backward per scene, which accumulates into gradient buffers bound to the MLP parameters."""
+    backward = pny_render_backward per launch of the forward, which accumulates into gradient buffers bound to the MLP parameters."""
 
     @staticmethod
     def forward(ctx, renderer, model, rays, has_fine, n_params, *params):
@@ -346,8 +334,6 @@ class _RenderFunction(torch.autograd.Function):
         dev = model._device()
         grads = model.bind_mlp_grads()            # zeroed fp32 buffers, one per trainable MLP parameter, bound by name
         SB, B = sv["rays"].shape[0], sv["rays"].shape[1]
-        kc = sv["z_coarse"].shape[-1]
-        kt = sv["z_fine"].shape[-1] if ctx.has_fine else 0
 
         def prep(t):
             if t is None or t.numel() == 0:
@@ -359,53 +345,41 @@ class _RenderFunction(torch.autograd.Function):
         # call computes its weight gradients immediately (accumulate bit 1), scene after scene, with recompute.
         deferred = ctx.deferred and getattr(model, "_defer_token", None) == ctx.token
         acc = 1 if deferred else 3
-        # d loss / d latent, accumulated by every scene's call into its own slice (channel-last).  Its zero fill runs on the
-        # current stream, so it is enqueued BEFORE the side streams fork from that stream: scenes 1.. add into the buffer
-        # with atomics from their own streams, and nothing else would order those behind the fill.
         group = bool(sv.get("group"))
         if group and not deferred:
             raise RuntimeError("the grouped training forward lost its stash reservation (another training forward ran before "
                                "this backward): call backward() before the next forward, or set PNYOLO_GROUP=0")
-        lat_grad = model.begin_latent_grad(ctx.lat_meta, SB, group=group) if ctx.lat_meta is not None else None
-        if group:   # one call over the SB * B rays on the grouped scene (see NeRFRenderer._render)
-            s_ = _lib.RenderSaved(z_coarse=sv["z_coarse"].data_ptr(), sample_coarse=sv["sample_coarse"].data_ptr())
-            if not getattr(ren, "_detach_fine_depth", False):
-                s_.depth_coarse = sv["depth_coarse"].data_ptr()
-            if ctx.has_fine:
-                s_.z_fine = sv["z_fine"].data_ptr()
-                s_.sample_fine = sv["sample_fine"].data_ptr()
-            g_ = _lib.RenderGrads(*[None if p is None else p.data_ptr() for p in ups])
-            check(L.pny_render_backward(model._h_group, ptr(sv["rays"]), SB * B, C.byref(sv["opts"][0]), C.byref(s_), C.byref(g_),
-                                        acc, stream_of(dev)))
-            extra = () if lat_grad is None else (model.end_latent_grad(lat_grad, ctx.lat_meta, SB, group=True),)
-            _mark_latent_grad(model, extra, dev)
-            check(L.pny_model_flush_weight_grads(model._h_model, 1, stream_of(dev)))
-            check(L.pny_model_defer_weight_grads(model._h_model, 0, 0, 0, 0))
-            return (None, None, None, None, None) + tuple(grads) + extra
-        streams = model.fork_streams(SB) if deferred else [None] * SB
-        calls = []
-        for sb in range(SB):
-            s_ = _lib.RenderSaved(z_coarse=sv["z_coarse"][sb].data_ptr(), sample_coarse=sv["sample_coarse"][sb].data_ptr())
-            if not getattr(ren, "_detach_fine_depth", False):   # test aid: treat the depth samples as constants
-                s_.depth_coarse = sv["depth_coarse"][sb].data_ptr()
-            if ctx.has_fine:
-                s_.z_fine = sv["z_fine"][sb].data_ptr()
-                s_.sample_fine = sv["sample_fine"][sb].data_ptr()
-            calls.append((s_, _lib.RenderGrads(*[None if p is None else p[sb].data_ptr() for p in ups])))
+        handles, G, R = _launches(model, group, SB, B)    # the forward's launches (NeRFRenderer._render)
+        # d loss / d latent, accumulated by every scene's call into its own slice (channel-last).  Its zero fill runs on the
+        # current stream, so it is enqueued BEFORE the side streams fork from that stream: scenes 1.. add into the buffer
+        # with atomics from their own streams, and nothing else would order those behind the fill.
+        lat_grad = model.begin_latent_grad(ctx.lat_meta, handles) if ctx.lat_meta is not None else None
+        streams = model.fork_streams(G) if deferred else [None] * G
+        rows = lambda t: None if t is None else t.view(G, R, *t.shape[2:])
+        names = [k for k in _SAVED_BUFFERS if k in sv]
+        if not getattr(ren, "_detach_fine_depth", False):   # test aid: treat the depth samples as constants
+            names.append("depth_coarse")
+        rays, sv_rows, up_rows = rows(sv["rays"]), {k: rows(sv[k]) for k in names}, [rows(p) for p in ups]
 
-        def run(sb, bits):
-            with torch.cuda.stream(streams[sb]):
-                check(L.pny_render_backward(model._scene(sb), ptr(sv["rays"][sb]), B, C.byref(sv["opts"][sb]), C.byref(calls[sb][0]),
-                                            C.byref(calls[sb][1]), acc | bits, stream_of(dev)))
-        # Optional (PNYOLO_SPLIT_FLUSH=1): every scene's FINE pass first, then mlp_fine's weight-gradient flush on a stream of its own
-        # BESIDE the coarse passes instead of behind them.  Measured (round 3): no gain -- 12.5-13.5 ms per step against 12.3-12.5:
-        # the chain kernels hold 152 KiB of a CU's LDS and the weight-gradient GEMM 128 KiB, so the two never share a CU and the
-        # "quarter-busy" coarse chains cannot be filled in.  Off by default; kept because it is tested (bits 4 / 8 of accumulate).
-        split = deferred and ctx.has_fine and model.mlp_fine is not None and os.environ.get("PNYOLO_SPLIT_FLUSH", "0") == "1"
+        def structs(g):
+            return (_lib.RenderSaved(**{k: t[g].data_ptr() for k, t in sv_rows.items()}),
+                    _lib.RenderGrads(*[None if t is None else t[g].data_ptr() for t in up_rows]))
+        calls = [structs(g) for g in range(G)]
+
+        def run(g, bits):
+            with torch.cuda.stream(streams[g]):
+                check(L.pny_render_backward(handles[g], ptr(rays[g]), R, C.byref(sv["opts"][g]), C.byref(calls[g][0]),
+                                            C.byref(calls[g][1]), acc | bits, stream_of(dev)))
+        # Optional (PNYOLO_SPLIT_FLUSH=1, per-object scenes): every scene's FINE pass first, then mlp_fine's weight-gradient flush on a
+        # stream of its own BESIDE the coarse passes instead of behind them.  Measured: no gain -- 12.5-13.5 ms per step against
+        # 12.3-12.5: the chain kernels hold 152 KiB of a CU's LDS and the weight-gradient GEMM 128 KiB, so the two never share a CU and
+        # the "quarter-busy" coarse chains cannot be filled in.  Off by default; kept because it is tested (bits 4 / 8 of accumulate).
+        split = (deferred and not group and ctx.has_fine and model.mlp_fine is not None
+                 and os.environ.get("PNYOLO_SPLIT_FLUSH", "0") == "1")
         fstream = None
         if split:
-            for sb in range(SB):
-                run(sb, 4)     # (bit 4: the fine pass only; bit 8: the coarse pass only -- include/pnyolo.h pny_render_backward)
+            for g in range(G):
+                run(g, 4)      # (bit 4: the fine pass only; bit 8: the coarse pass only -- include/pnyolo.h pny_render_backward)
             main = torch.cuda.current_stream(dev)
             fstream = getattr(model, "_flush_stream", None)
             if fstream is None or fstream.device != dev:
@@ -416,16 +390,13 @@ class _RenderFunction(torch.autograd.Function):
                     fstream.wait_stream(st_)
             with torch.cuda.stream(fstream):
                 check(L.pny_model_flush_weight_grads(model._h_model, 1 | 32, stream_of(dev)))
-            for sb in range(SB):
-                run(sb, 8)
-        else:
-            for sb in range(SB):
-                run(sb, 0)
+        for g in range(G):
+            run(g, 8 if split else 0)
         if deferred:
             model.join_streams(streams)
         # d loss / d latent is complete here, BEFORE the weight-gradient flush is enqueued: the encoder's backward (the trunk's
         # kernels, model._TrunkFunction) starts behind this point on its own stream and runs beside the flush
-        extra = () if lat_grad is None else (model.end_latent_grad(lat_grad, ctx.lat_meta, SB),)
+        extra = () if lat_grad is None else (model.end_latent_grad(lat_grad, ctx.lat_meta, handles),)
         _mark_latent_grad(model, extra, dev)
         if deferred:
             check(L.pny_model_flush_weight_grads(model._h_model, 1 | (16 if split else 0), stream_of(dev)))
@@ -433,6 +404,19 @@ class _RenderFunction(torch.autograd.Function):
                 torch.cuda.current_stream(dev).wait_stream(fstream)
             check(L.pny_model_defer_weight_grads(model._h_model, 0, 0, 0, 0))
         return (None, None, None, None, None) + tuple(grads) + extra
+
+
+_SAVED_BUFFERS = ("z_coarse", "sample_coarse", "z_fine", "sample_fine")   # per-sample outputs of the forward that the backward reads
+
+
+def _launches(model, group, SB, B):
+    """The library launches of one render call or of its backward: -> (scene handles, G, R) for G launches of R rays each.
+    Grouped, it is one launch over the SB * B rays on the handle that holds the whole super-batch; otherwise one launch of B
+    rays per object's scene.  Every tensor of the call -- rays, draws, results, saved buffers, upstream gradients -- is
+    (SB, B, ...) in memory, so launch g takes row g of its (G, R, ...) view either way."""
+    if group:
+        return [model._h_group], 1, SB * B
+    return [model._scene(sb) for sb in range(SB)], SB, B
 
 
 class NeRFRenderer(torch.nn.Module):
@@ -489,18 +473,12 @@ class NeRFRenderer(torch.nn.Module):
         kf = int(self.n_fine) if (self.using_fine and self.n_fine > 0) else 0
         outs = _RenderFunction.apply(self, model, rays, kf > 0, len(params), *[p for _, p in params],
                                      *([lat_src] if lat_src is not None else []))
-        res = {"coarse": {"rgb": outs[0], "depth": outs[1]}}
-        if want_weights:
-            res["coarse"]["weights"] = outs[2]
-        if kf > 0:
-            res["fine"] = {"rgb": outs[3], "depth": outs[4]}
-            if want_weights:
-                res["fine"]["weights"] = outs[5]
-        return res
+        return _result(outs, kf > 0, want_weights)
 
     def _render(self, model, rays, want_weights, save, stash=False):
-        """One pny_render call per scene.  save=True also returns what the backward needs: the detached device rays,
-        the sample depths and the per-sample MLP outputs of both passes, and the options of every scene's call."""
+        """The pny_render launches of one call (_launches): one per scene, or one on the grouped scene.  save=True also returns
+        what the backward needs: the detached device rays, the sample depths and the per-sample MLP outputs of both passes, and
+        the options of every launch."""
         model._sync()
         L = _lib.load()
         dev = model._device()
@@ -529,113 +507,70 @@ class NeRFRenderer(torch.nn.Module):
             if use_fine:
                 saved["z_fine"] = torch.empty(SB, B, kc + kf, **f32)
                 saved["sample_fine"] = torch.empty(SB, B, kc + kf, 4, **f32)
-            for k in ("z_coarse", "sample_coarse", "z_fine", "sample_fine"):
+            for k in _SAVED_BUFFERS:
                 if k in saved:
                     saved[k] = extra.pop(k, saved[k])   # a debug capture of the same buffer: share it
         draws, self.draws = self.draws, None
         self._calls += 1
-        keep = []
+        keep = []       # the uploaded draws: read again by the backward (depth samples)
         # Training on a super-batch held by ONE grouped scene (model.encode, pny_scene_set_groups): a single pny_render over
         # the SB * B rays -- one MLP launch per pass over every object's tiles instead of SB launches on side streams.  Needs
-        # whole 64-sample tiles per object in both passes; otherwise the per-object path below (model._scene fills its handles).
+        # whole 64-sample tiles per object in both passes; otherwise one launch per object (model._scene fills its handles).
         model._last_call_group = False
-        g = model._group_scene() if stash else None
-        if (g is not None and SB == model._group["SB"] and (B * kc) % 64 == 0 and (not use_fine or (B * (kc + kf)) % 64 == 0)
-                and not extra):
+        group = (stash and model._group_scene() is not None and SB == model._group["SB"] and (B * kc) % 64 == 0
+                 and (not use_fine or (B * (kc + kf)) % 64 == 0) and not extra)
+        handles, G, R = _launches(model, group, SB, B)
+        streams = model.fork_streams(G)       # scenes are independent: one side stream each (None = current stream)
+        rows = lambda t: t.view(G, R, *t.shape[2:])
+        bufs = {k + "_" + p: t for p in res for k, t in res[p].items()}     # RenderOut's fields: results, debug captures, saved
+        bufs.update(extra)
+        if save:
+            bufs.update({k: saved[k] for k in _SAVED_BUFFERS if k in saved})
+        bufs, rays_g = {k: rows(t) for k, t in bufs.items()}, rows(rays)
+
+        def draw(g, name, cols, scale=None):
+            """Device pointer of launch g's rows of the explicit draw `name` (None when it is not supplied: the library then
+            draws in the kernel), kept alive.  With `scale` it is sigma noise: drawn here unless supplied, and scaled."""
+            if cols == 0:
+                return None
+            if draws is not None and name in draws:
+                t = torch.as_tensor(draws[name], dtype=torch.float32).reshape(G, R, cols)[g].to(dev)
+            elif scale is not None:
+                t = torch.randn(R, cols, device=dev, dtype=torch.float32)
+            else:
+                return None
+            t = (t * scale if scale is not None else t).contiguous()
+            keep.append(t)
+            return t.data_ptr()
+
+        def opts(g):
             o = RenderOpts(n_coarse=kc, n_fine=kf, n_fine_depth=kfd, depth_std=float(self.depth_std),
                            white_bkgd=int(bool(self.white_bkgd)), lindisp=int(bool(self.lindisp)),
-                           seed=(self.base_seed + 7919 * self._calls) & 0xFFFFFFFFFFFFFFFF)
-
-            def flat(name, cols, scale=None):
-                if cols == 0:
-                    return None
-                if draws is not None and name in draws:
-                    t = torch.as_tensor(draws[name], dtype=torch.float32).reshape(SB * B, cols).to(dev)
-                elif scale is not None:
-                    t = torch.randn(SB * B, cols, device=dev, dtype=torch.float32)
-                else:
-                    return None
-                t = (t * scale if scale is not None else t).contiguous()
-                keep.append(t)
-                return t.data_ptr()
-            if draws is not None:
-                o.u_coarse_dev = flat("u_coarse", kc)
-                o.u_fine_dev = flat("u_fine", kf - kfd)
-                o.u_fine2_dev = flat("u_fine2", kf - kfd)
-                o.g_depth_dev = flat("g_depth", kfd)
+                           seed=(self.base_seed + 7919 * self._calls + g) & 0xFFFFFFFFFFFFFFFF)
+            o.u_coarse_dev = draw(g, "u_coarse", kc)
+            o.u_fine_dev = draw(g, "u_fine", kf - kfd)
+            o.u_fine2_dev = draw(g, "u_fine2", kf - kfd)
+            o.g_depth_dev = draw(g, "g_depth", kfd)
             if self.training and self.noise_std > 0.0:
-                o.sigma_noise_coarse_dev = flat("noise_coarse", kc, float(self.noise_std))
+                # sigma noise (nerf.py:231-232), training only: drawn here (or replayed from draws["noise_coarse" /
+                # "noise_fine"], unit normals) and handed to the composite kernels already scaled
+                o.sigma_noise_coarse_dev = draw(g, "noise_coarse", kc, float(self.noise_std))
                 if use_fine:
-                    o.sigma_noise_fine_dev = flat("noise_fine", kc + kf, float(self.noise_std))
-            out = RenderOut()
-            out.rgb_coarse, out.depth_coarse = res["coarse"]["rgb"].data_ptr(), res["coarse"]["depth"].data_ptr()
-            if want_weights:
-                out.weights_coarse = res["coarse"]["weights"].data_ptr()
-            if use_fine:
-                out.rgb_fine, out.depth_fine = res["fine"]["rgb"].data_ptr(), res["fine"]["depth"].data_ptr()
-                if want_weights:
-                    out.weights_fine = res["fine"]["weights"].data_ptr()
-            for name in ("z_coarse", "sample_coarse", "z_fine", "sample_fine"):
-                if name in saved:
-                    setattr(out, name, saved[name].data_ptr())
-            saved["opts"], saved["keep"], saved["group"] = [o], keep, True
-            check(L.pny_scene_stash_next_render(g, 1))
-            check(L.pny_render(g, ptr(rays), SB * B, C.byref(o), C.byref(out), stream_of(dev)))
-            model._last_call_group = True
-            return res, saved
-        streams = model.fork_streams(SB)      # scenes are independent: one side stream each (None = current stream)
-        for sb in range(SB):
-            with torch.cuda.stream(streams[sb]):
-                o = RenderOpts(n_coarse=kc, n_fine=kf, n_fine_depth=kfd, depth_std=float(self.depth_std),
-                               white_bkgd=int(bool(self.white_bkgd)), lindisp=int(bool(self.lindisp)),
-                               seed=(self.base_seed + 7919 * self._calls + sb) & 0xFFFFFFFFFFFFFFFF)
-                if draws is not None:
-                    def dev_draw(name, cols):
-                        if cols == 0:
-                            return None
-                        t = torch.as_tensor(draws[name], dtype=torch.float32).reshape(SB, B, cols)[sb].to(dev).contiguous()
-                        keep.append(t)
-                        return t.data_ptr()
-                    o.u_coarse_dev = dev_draw("u_coarse", kc)
-                    o.u_fine_dev = dev_draw("u_fine", kf - kfd)
-                    o.u_fine2_dev = dev_draw("u_fine2", kf - kfd)
-                    o.g_depth_dev = dev_draw("g_depth", kfd)
-                if self.training and self.noise_std > 0.0:
-                    # sigma noise (nerf.py:231-232), training only: drawn here (or replayed from draws["noise_coarse" /
-                    # "noise_fine"], unit normals) and handed to the composite kernels already scaled
-                    def noise(name, cols):
-                        if draws is not None and name in draws:
-                            t = torch.as_tensor(draws[name], dtype=torch.float32).reshape(SB, B, cols)[sb].to(dev)
-                        else:
-                            t = torch.randn(B, cols, device=dev, dtype=torch.float32)
-                        t = (t * float(self.noise_std)).contiguous()
-                        keep.append(t)
-                        return t.data_ptr()
-                    o.sigma_noise_coarse_dev = noise("noise_coarse", kc)
-                    if use_fine:
-                        o.sigma_noise_fine_dev = noise("noise_fine", kc + kf)
-                out = RenderOut()
-                out.rgb_coarse = res["coarse"]["rgb"][sb].data_ptr()
-                out.depth_coarse = res["coarse"]["depth"][sb].data_ptr()
-                if want_weights:
-                    out.weights_coarse = res["coarse"]["weights"][sb].data_ptr()
-                if use_fine:
-                    out.rgb_fine = res["fine"]["rgb"][sb].data_ptr()
-                    out.depth_fine = res["fine"]["depth"][sb].data_ptr()
-                    if want_weights:
-                        out.weights_fine = res["fine"]["weights"][sb].data_ptr()
-                for name, buf in extra.items():
-                    setattr(out, name, buf[sb].data_ptr())
+                    o.sigma_noise_fine_dev = draw(g, "noise_fine", kc + kf, float(self.noise_std))
+            return o
+
+        for g, h in enumerate(handles):
+            with torch.cuda.stream(streams[g]):
+                o, out = opts(g), RenderOut(**{k: t[g].data_ptr() for k, t in bufs.items()})
                 if save:
-                    for name in ("z_coarse", "sample_coarse", "z_fine", "sample_fine"):
-                        if name in saved:
-                            setattr(out, name, saved[name][sb].data_ptr())
                     saved["opts"].append(o)
-                    saved["keep"] = keep   # the explicit draws are read again by the backward (depth samples)
                 if stash:   # training forward into the reserved stash (pny_scene_stash_next_render)
-                    check(L.pny_scene_stash_next_render(model._scene(sb), 1))
-                check(L.pny_render(model._scene(sb), ptr(rays[sb]), B, C.byref(o), C.byref(out), stream_of(dev)))
+                    check(L.pny_scene_stash_next_render(h, 1))
+                check(L.pny_render(h, ptr(rays_g[g]), R, C.byref(o), C.byref(out), stream_of(dev)))
         model.join_streams(streams)
+        model._last_call_group = group
+        if save:
+            saved["keep"], saved["group"] = keep, group
         return res, saved
 
     def sched_step(self, steps=1):
@@ -763,10 +698,11 @@ class _YoloRenderFunction(torch.autograd.Function):
         dev = net._device()
         grads = net.bind_mlp_grads()
         g_out = g_out.detach().to(dev, torch.float32).contiguous()
-        lat_grad = net.begin_latent_grad(ctx.lat_meta, 1) if ctx.lat_meta is not None else None
-        check(L.pny_yolo_render_backward(net._scene(0), ptr(sv["rays"]), sv["rays"].shape[0], sv["n_coarse"], ptr(sv["u"]),
+        scene = net._scene(0)
+        lat_grad = net.begin_latent_grad(ctx.lat_meta, [scene]) if ctx.lat_meta is not None else None
+        check(L.pny_yolo_render_backward(scene, ptr(sv["rays"]), sv["rays"].shape[0], sv["n_coarse"], ptr(sv["u"]),
                                          sv["seed"], ptr(sv["raw"]), ptr(g_out), 1, stream_of(dev)))
-        extra = () if lat_grad is None else (net.end_latent_grad(lat_grad, ctx.lat_meta, 1),)
+        extra = () if lat_grad is None else (net.end_latent_grad(lat_grad, ctx.lat_meta, [scene]),)
         net._lat_grad_event = None      # (unmarked: a trunk backward behind this one waits for the whole stream)
         return (None, None, None) + tuple(grads) + extra
 

@@ -350,3 +350,21 @@ def test_checkpoint_contract_matches_reference(tmp_path):
         files = {fn: marker_of(torch.load(str(root / fn), map_location="cpu", weights_only=True))
                  for fn in sorted(os.listdir(root))}
         assert files == step["files"], (step, files)
+
+
+@pytest.mark.parametrize("n_dev", [1, 2, 3, 8])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 127, 128, 129, 1000])
+def test_ray_ranges_split_a_call_into_whole_64_ray_groups(n, n_dev):
+    """render._ray_ranges, the one place that splits a call's rays over the devices of bind_parallel: one (lo, hi) per device,
+    contiguous from 0 to n, every start and every length but the last non-empty one a multiple of 64 (the kernels' ray
+    group), empty ranges only at the end."""
+    from pixel_nerf_yolo_amd.render import _ray_ranges
+    ranges = _ray_ranges(n, n_dev)
+    assert len(ranges) == n_dev
+    assert ranges[0][0] == 0 and ranges[-1][1] == n
+    assert all(a[1] == b[0] for a, b in zip(ranges, ranges[1:]))
+    assert all(lo % 64 == 0 or lo == hi == n for lo, hi in ranges)
+    full = [(lo, hi) for lo, hi in ranges if hi > lo]
+    assert full == ranges[:len(full)] and len(full) >= 1
+    assert all(lo % 64 == 0 for lo, _ in full) and all((hi - lo) % 64 == 0 for lo, hi in full[:-1])
+    assert sum(hi - lo for lo, hi in full) == n

@@ -547,6 +547,54 @@ def test_grouped_super_batch_equals_per_object(lat_grad, monkeypatch):
         assert torch.equal(out_r[k], out_r0[k]), k
 
 
+def test_grouped_super_batch_with_sigma_noise_equals_per_object(monkeypatch):
+    """Sigma noise (noise_std > 0 in train() mode, replayed from draws["noise_coarse" / "noise_fine"]) on the grouped scene:
+    launch 0 of 1 takes the (SB * n, cols) draws whole where the per-object launches take a row of their (SB, n, cols) view
+    each -- rendered outputs bit-equal, parameter gradients equal to fp32 summation order (the bound of
+    test_grouped_super_batch_equals_per_object), and the noise reaches the kernels: noise_std = 0 renders another image."""
+    SB, ns, H, W, kc, kf, kfd, n = 2, 2, 32, 32, 16, 8, 4, 16        # 256 and 384 samples per object: whole 64-sample tiles
+    c = pconf.default_mv()
+    rs = np.random.RandomState(6)
+    lat = np.concatenate([synth.latent(1710 + i, ns, 512, H // 2, W // 2) for i in range(SB)])
+    poses = np.stack([synth.scene_cameras(ns, radius=1.3 + 0.05 * i)[0] for i in range(SB)])
+    rays = torch.stack([orc.gen_rays(synth.pose_spherical(100.0 + 25 * i, -20.0, 1.3)[None], W, H, 29.0, 0.3, 1.8)[0]
+                        .reshape(-1, 8)[torch.from_numpy(rs.choice(H * W, n, replace=False))] for i in range(SB)])
+    dr = dict(u_coarse=rs.rand(SB * n, kc).astype(np.float32), u_fine=rs.rand(SB * n, kf - kfd).astype(np.float32),
+              u_fine2=rs.rand(SB * n, kf - kfd).astype(np.float32), g_depth=rs.randn(SB * n, kfd).astype(np.float32),
+              noise_coarse=rs.randn(SB * n, kc).astype(np.float32), noise_fine=rs.randn(SB * n, kc + kf).astype(np.float32))
+    gt = torch.from_numpy(rs.uniform(0, 1, size=(SB, n, 3)).astype(np.float32)).to(DEV)
+
+    def run(group, noise_std=0.5):
+        monkeypatch.setenv("PNYOLO_GROUP", "1" if group else "0")
+        net = make_model(c["model"], stop_encoder_grad=True)
+        load_mlp(net.mlp_coarse, 1701, 512, 4)
+        load_mlp(net.mlp_fine, 1702, 512, 4)
+        net = net.to(DEV).train()
+        net.encode(torch.zeros(SB, ns, 3, H, W), torch.from_numpy(poses), torch.tensor(29.0), latent=torch.from_numpy(lat).to(DEV))
+        ren = NeRFRenderer(n_coarse=kc, n_fine=kf, n_fine_depth=kfd, noise_std=noise_std, white_bkgd=True).train()
+        ren.draws = dict(dr)
+        out = ren(net, rays.to(DEV), want_weights=True)
+        (torch.nn.functional.mse_loss(out["coarse"]["rgb"], gt) + torch.nn.functional.mse_loss(out["fine"]["rgb"], gt)
+         + 0.1 * out["fine"]["depth"].mean()).backward()
+        torch.cuda.synchronize()
+        assert net._last_call_group == group
+        grads = {k: p.grad.clone() for k, p in net.named_parameters() if p.grad is not None}
+        return {q + "." + k: v.detach().clone() for q in ("coarse", "fine") for k, v in out[q].items()}, grads
+
+    out_g, grad_g = run(True)
+    out_s, grad_s = run(False)
+    assert sorted(out_g) == sorted(out_s) and len(out_s) == 6
+    for k in out_s:
+        assert torch.equal(out_g[k], out_s[k]), k
+    assert len(grad_g) == len(grad_s) >= 60
+    for k in grad_s:
+        scale = float(grad_s[k].abs().max())
+        err = float((grad_g[k] - grad_s[k]).abs().max())
+        assert err <= 2e-6 * max(scale, 1e-20), (k, err, scale)
+    out_0, _ = run(True, noise_std=0.0)
+    assert not torch.equal(out_0["fine.rgb"], out_g["fine.rgb"])
+
+
 @pytest.mark.one_backward_leg
 def test_grouped_scene_through_the_abi(monkeypatch):
     """pny_scene_set_groups at the C ABI, without the Python render path: pny_query on a grouped scene (points in n_objs equal
