@@ -519,12 +519,31 @@ int pny_render_backward(pny_scene* s, const float* rays_dev, int64_t n, const pn
  * sorted fine depths, or -1 for a sample that the forward clamped to [near, far] (no gradient passes the clamp).  A sample
  * strictly inside (near, far) always has a position.  PNY_ERR_STATE when count is not that backward's n * n_fine_depth. */
 int pny_scene_last_depth_sel(pny_scene* s, int32_t* sel_dev, int64_t count, pny_stream stream);
+/* Stage entry points of that depth-sample path (used by pny_render_backward; exported for stage-wise tests, as
+ * pny_composite_backward is).  The fine pass centres its n_fine_depth depth samples on the coarse depth without detaching it
+ * (src/render/nerf.py:156-167, 296-298), so dL/dz of those samples is an extra dL/d(depth_coarse).
+ * pny_locate_depth_samples: re-creates the forward's draw zz = depth_coarse + g * depth_std (g_dev (n,kfd), or NULL: the
+ * seeded normals of pny_sample_fine under the same seed) and finds it in z_fine_dev (n,kt), the sorted output of
+ * pny_sample_fine.  sel_dev (n*kfd int32) = ray * kt + the FIRST position holding the sample's depth, or -1 for a sample that
+ * the clamp of nerf.py:166 caught (zz <= near or zz >= far).  n * kt must fit an int32.
+ * pny_depth_grad_gather: g_out_dev (n) = g_in_dev (n) (NULL = 0) + the sum of dz_dev[sel] over the ray's entries with
+ * sel >= 0, added in sample order in fp32 (a fixed order: bit-reproducible).  Every sel >= 0 must index dz_dev. */
+int pny_locate_depth_samples(const float* rays_dev, const float* depth_coarse_dev, const float* g_dev, uint64_t seed,
+                             const float* z_fine_dev, int64_t n, int kt, int kfd, float depth_std, int32_t* sel_dev,
+                             pny_stream stream);
+int pny_depth_grad_gather(const int32_t* sel_dev, const float* dz_dev, const float* g_in_dev, int64_t n, int kfd,
+                          float* g_out_dev, pny_stream stream);
 
 /* Backward of pny_yolo_render (src/render/yolo.py:96-114 aggregation + the MLP; caller: train/trainlib/YoloTrainer.py:160-186):
  * raw_dev (n, K, A*7) = the forward's raw_dev output, g_out_dev (n, A, 7) = dL/d(out); the sample depths are re-created
  * from u_coarse_dev / seed as the forward made them.  Gradients go to the bound targets of mlp_coarse. */
 int pny_yolo_render_backward(pny_scene* s, const float* rays_dev, int64_t n, int n_coarse, const float* u_coarse_dev,
                              uint64_t seed, const float* raw_dev, const float* g_out_dev, int accumulate, pny_stream stream);
+/* Backward of pny_yolo_aggregate alone (src/render/yolo.py:96-114; the stage pny_yolo_render_backward runs before the MLP,
+ * exported for stage-wise tests): raw_dev (n,K,A*7), g_out_dev (n,A,7) = dL/d(out) -> d_raw_dev (n,K,A*7) = dL/d(raw), every
+ * element written.  The gradient of max_k p goes to the first index that attains it, as torch.max(dim) sends it. */
+int pny_yolo_aggregate_backward(const float* raw_dev, const float* g_out_dev, int64_t n, int k, int n_anchors,
+                                float* d_raw_dev, pny_stream stream);
 
 /* Deferred weight gradients.  A training batch holds several scenes (the reference's super-batch, SB objects x B rays,
  * train/train.py:23) whose backward calls are independent until the weight gradients are summed.  With deferral enabled

@@ -444,7 +444,12 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restr
             const float dn = __shfl_down(incl, o, 64);
             if (lane + o < 64) incl += dn;
         }
-        const float excl = incl - G * w + suffix;   // sum_{j > k} G_j w_j
+        // sum_{j > k} G_j w_j = the next lane's inclusive sum, NOT incl - G_k w_k: behind a nearly opaque sample the tail is
+        // orders of magnitude below the sample's own term, the difference keeps only that term's rounding error, and
+        // 1 / A_k and sigma_k then multiply it (1e-4 of a ray's largest gradient at sigma delta = 4)
+        float excl = __shfl_down(incl, 1, 64);
+        if (lane == 63) excl = 0.f;
+        excl += suffix;
         suffix += __shfl(incl, 0, 64);
         if (on) {
             const float A = 1.0f - alpha + 1e-10f;

@@ -8,7 +8,8 @@
 // wherever the chunk's four base pointers share their misalignment to 16 bytes (a scalar head of up to 3 elements brings all
 // four to a boundary, a scalar tail takes count % 4); pointers that disagree take the scalar path for the whole chunk.
 // No LDS, no atomics: every element is read and written by exactly one lane, so a step is bit-reproducible; the file is
-// compiled with -ffp-contract=off (csrc/Makefile) and the operation order below is fixed, so every build gives the same bits.
+// compiled with -ffp-contract=off (csrc/Makefile) and the operation order below is fixed (the two fmaf are explicit), so every build
+// gives the same bits.
 // Parameters and moments are fixed for the optimizer's life (AdamTensor); the gradient pointers change with every backward
 // and are read from a host-pinned table that the launch owns until it has executed (optim_api.hip: ring of tables).
 #include "pny_common.h"
@@ -17,8 +18,10 @@ namespace pny {
 
 __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, const AdamScalars& sc) {
     if (sc.weight_decay != 0.f) g = g + sc.weight_decay * p;
-    m = m + (g - m) * sc.one_minus_beta1;
-    v = v * sc.beta2 + g * g * sc.one_minus_beta2;
+    // both moments with the product fused into the sum: one rounding fewer each.  exp_avg is then ATen's lerp_ bit for bit
+    // (start + weight * (end - start), which the device compiler fuses), so its error against fp64 IS torch.optim.Adam's
+    m = fmaf(g - m, sc.one_minus_beta1, m);
+    v = fmaf(sc.one_minus_beta2 * g, g, v * sc.beta2);
     p = p - sc.step_size * m / (sqrtf(v) / sc.bc2_sqrt + sc.eps);
 }
 

@@ -706,6 +706,36 @@ int pny_scene_last_depth_sel(pny_scene* s, int32_t* sel_dev, int64_t count, pny_
     return PNY_OK;
 }
 
+int pny_locate_depth_samples(const float* rays_dev, const float* depth_coarse_dev, const float* g_dev, uint64_t seed,
+                             const float* z_fine_dev, int64_t n, int kt, int kfd, float depth_std, int32_t* sel_dev,
+                             pny_stream stream) {
+    if (n < 0 || kt < 1 || kfd < 0 || kfd > kt) return fail(PNY_ERR_ARG, "pny_locate_depth_samples: bad sample counts");
+    if (n > 0 && kfd > 0 && (!rays_dev || !depth_coarse_dev || !z_fine_dev || !sel_dev))
+        return fail(PNY_ERR_ARG, "pny_locate_depth_samples: null argument");
+    if (n > (int64_t)0x7fffffff / kt) return fail(PNY_ERR_ARG, "pny_locate_depth_samples: n * kt does not fit the int32 positions");
+    launch_locate_depth_samples(rays_dev, depth_coarse_dev, g_dev, seed, z_fine_dev, n, kt, kfd, depth_std, sel_dev, (hipStream_t)stream);
+    PNY_HIP(hipGetLastError());
+    return PNY_OK;
+}
+
+int pny_depth_grad_gather(const int32_t* sel_dev, const float* dz_dev, const float* g_in_dev, int64_t n, int kfd, float* g_out_dev,
+                          pny_stream stream) {
+    if (n < 0 || kfd < 0 || (n > 0 && (!g_out_dev || (kfd > 0 && (!sel_dev || !dz_dev)))))
+        return fail(PNY_ERR_ARG, "pny_depth_grad_gather: bad argument");
+    launch_depth_grad_gather(sel_dev, dz_dev, g_in_dev, n, kfd, g_out_dev, (hipStream_t)stream);
+    PNY_HIP(hipGetLastError());
+    return PNY_OK;
+}
+
+int pny_yolo_aggregate_backward(const float* raw_dev, const float* g_out_dev, int64_t n, int k, int n_anchors, float* d_raw_dev,
+                                pny_stream stream) {
+    if (n < 0 || k < 1 || n_anchors < 1 || (n > 0 && (!raw_dev || !g_out_dev || !d_raw_dev)))
+        return fail(PNY_ERR_ARG, "pny_yolo_aggregate_backward: bad argument");
+    launch_yolo_aggregate_bwd(raw_dev, g_out_dev, n, k, n_anchors, d_raw_dev, (hipStream_t)stream);
+    PNY_HIP(hipGetLastError());
+    return PNY_OK;
+}
+
 int pny_yolo_render_backward(pny_scene* s, const float* rays_dev, int64_t n, int n_coarse, const float* u_coarse_dev, uint64_t seed,
                              const float* raw_dev, const float* g_out_dev, int accumulate, pny_stream stream) {
     int rc;

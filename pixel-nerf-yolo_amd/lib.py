@@ -163,6 +163,10 @@ SIGNATURES = {
     "pny_render_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(RenderOpts), C.POINTER(RenderSaved),
                                       C.POINTER(RenderGrads), C.c_int, C.c_void_p]),
     "pny_scene_last_depth_sel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "pny_locate_depth_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                           C.c_float, C.c_void_p, C.c_void_p]),
+    "pny_depth_grad_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "pny_yolo_aggregate_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pny_optim_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
     "pny_optim_destroy": (None, [C.c_void_p]),
     "pny_optim_add_tensor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),

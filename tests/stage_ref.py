@@ -278,16 +278,17 @@ def fine_ref(c, kc, kf, kfd, lindisp, dtype=F64, depth_std=DEPTH_STD):
     return torch.sort(torch.cat(parts, -1), -1)[0]
 
 
-def hip_fine(c, kc, kf, kfd, lindisp, depth_std=DEPTH_STD, device="cuda:0"):
+def hip_fine(c, kc, kf, kfd, lindisp, depth_std=DEPTH_STD, device="cuda:0", seed=0):
     """pny_sample_fine on a case of fine_case / dyadic_case / depth_tie_case (GPU; the one place that marshals its arguments,
-    for the sweep and for its two-device child process).  Returns the merged depths (n, kc + kf) on the CPU."""
+    for the sweep and for its two-device child process).  An absent draw array is drawn from `seed`.  Returns the merged depths (n, kc + kf) on
+    the CPU."""
     from pixel_nerf_yolo_amd import lib as plib
     t = {k: torch.as_tensor(c[k], dtype=F32, device=device).contiguous() for k in ("rays", "zc", "w", "depth", "u", "u2", "g")}
     opt = lambda v: plib.ptr(v) if v.numel() else None          # noqa: E731  (NULL for an absent draw array)
     n = t["rays"].shape[0]
     zo = torch.full((n, kc + kf), float("nan"), device=device)
     plib.check(plib.load().pny_sample_fine(plib.ptr(t["rays"]), plib.ptr(t["zc"]), plib.ptr(t["w"]), plib.ptr(t["depth"]), n, kc,
-                                           kf, kfd, depth_std, lindisp, opt(t["u"]), opt(t["u2"]), opt(t["g"]), 0,
+                                           kf, kfd, depth_std, lindisp, opt(t["u"]), opt(t["u2"]), opt(t["g"]), seed,
                                            plib.ptr(zo), plib.stream_of(torch.device(device))))
     torch.cuda.synchronize(device)
     return zo.cpu()
@@ -591,3 +592,315 @@ def match_cases():
     b, v, _ = iou_pair_case()
     cases["iou_equals_match"] = (b[:1], b[1:], 0.5, 0.1, v)     # best IoU == match_iou: no true positive, no false negative
     return cases
+
+
+# =========================================================================== backward stages (csrc/mlp_bwd.hip)
+# The MLP-free reverses of the stages above, through their own entry points: pny_composite_backward,
+# pny_yolo_aggregate_backward (float: the oracle under autograd in float64 on the float32 inputs), pny_depth_grad_gather and
+# pny_locate_depth_samples (exact: a host restatement).
+#
+# Error measure of the two float stages, PER ROW -- a ray for the composite, a (ray, anchor) for the aggregation:
+# max |got - ref| over the row / max |ref| over the row.  One row's error is not hidden behind another row's larger gradient,
+# which the whole-tensor measure of test_composite_backward_vs_autograd allows.  A row whose reference maximum is below TINY
+# (sigma == 0, all_low: gradients <= 5e-38, subnormal, which a GPU may flush) is checked absolutely: finite and <= TINY.
+TINY = 1e-30
+
+
+def row_err(got, ref, n):
+    """Largest per-row relative error of got against ref, rows = the leading n entries (see above).  Asserts that got is
+    finite, and that the rows whose reference stays below TINY stay below TINY."""
+    g = torch.as_tensor(np.asarray(got), dtype=F64).reshape(n, -1)
+    r = torch.as_tensor(np.asarray(ref), dtype=F64).reshape(n, -1)
+    assert g.shape == r.shape and bool(torch.isfinite(g).all()), "non-finite gradient"
+    if g.shape[1] == 0:
+        return 0.0
+    top = r.abs().max(1)[0]
+    small = top < TINY
+    if bool(small.any()):
+        assert float(g[small].abs().max()) <= TINY, "a row whose reference is below %g holds %.3e" % (TINY, float(g[small].abs().max()))
+    if bool(small.all()):
+        return 0.0
+    return float(((g - r).abs().max(1)[0][~small] / top[~small]).max())
+
+
+def _seed_of(*key):
+    import zlib
+    return zlib.crc32(repr(key).encode())
+
+
+# --------------------------------------------------------------------------- composite backward
+# Inputs: composite_bwd_case = composite_case, every family, with sigma x delta either SMALL (at most X_CAP) or 1e6 (the planted
+# opaque samples: alpha == 1 and A == 1e-10 in both precisions).  The opacities in between are EXCLUDED on purpose, and
+# composite_case's exponential draws do reach them (sigma x delta to 28 at n = 257).  alpha = 1 - exp(-x) is rounded to float32
+# with an absolute error of 6e-8, so A = 1 - alpha + 1e-10 = exp(-x) carries a RELATIVE error of 6e-8 exp(x): 3e-6 at x = 4,
+# 2e-4 at x = 8, 1e-2 at x = 12, and from x = 15 to 25 A is one of 1e-10, 6e-8, 1.2e-7 whatever x is.  excl / A inherits that
+# factor in every float32 evaluation, the oracle's included.  Under the whole-tensor measure a small T hides it; per ray it
+# does not where such a sample comes FIRST on its ray (T = 1) and makes every gradient of the row tiny: the float32 oracle is
+# then 1.7e-3 off the float64 one (x = 12.3 at sample 0, row maximum 1e-7; K = 64, n = 4).  No float32 implementation can be
+# held to float64 there, so the sweep does not ask it.
+X_CAP = 4.0
+
+
+def composite_bwd_case(family, n, K, seed=0):
+    """composite_case with every sigma x delta above X_CAP brought down to X_CAP, the planted 1e6 excepted."""
+    rays, z, samp = composite_case(family, n, K, seed)
+    delta = np.diff(np.concatenate([z, rays[:, 7:8]], 1).astype(np.float64), axis=1)
+    sigma = samp[..., 3].astype(np.float64)
+    high = (sigma < 1e5) & (sigma * delta > X_CAP)
+    samp[..., 3] = np.where(high, X_CAP / np.where(high, delta, 1.0), sigma).astype(np.float32)
+    return rays, z, samp
+
+
+COMPOSITE_BWD_KMAX = 2048                                  # 4 rays x 2 arrays x K floats of LDS = 64 KB: the largest K accepted
+COMPOSITE_BWD_K = COMPOSITE_K + (COMPOSITE_BWD_KMAX,)
+COMPOSITE_BWD_FLOOR = 2e-5                                 # test_composite_backward_vs_autograd (there: of the whole tensor's max)
+# float32 oracle under autograd against the float64 one, per ray, over every case of the sweep (n to 257, white 0 and 1, the
+# gradient subsets included).  d_z of a ray with one or two samples is one or two numbers, each a difference of two terms
+# (g_depth w_k - dL/ddelta_k [+ dL/ddelta_k-1]) that nearly cancel on a few of 257 rays: the float32 oracle itself is 3.7e-4
+# off there, and those K get the bar that belongs to them instead of lending it to every K.
+COMPOSITE_BWD_ERR32_DSAMPLE = 8.1e-6                       # every K (worst: K = 64, depth gradient only)
+COMPOSITE_BWD_ERR32_DZ = {1: 3.7e-4, 2: 3.8e-5}            # K = 1, K = 2
+COMPOSITE_BWD_ERR32_DZ_LONG = 1.6e-5                       # K >= 63 (worst: K = 256, underflow)
+# the slice behind an opaque sample x 1e10 (d_sample's rgb columns, d_z).  Behind opaque@K-2 it is ONE sample: the same
+# near-cancellation of a single d_z, on one of 257 rays (K = 1000; 5.1e-5 at K = 96)
+COMPOSITE_BWD_ERR32_BEHIND = 7.2e-5
+COMPOSITE_BWD_BAR_DSAMPLE = _bar(COMPOSITE_BWD_FLOOR, COMPOSITE_BWD_ERR32_DSAMPLE)      # = the floor
+COMPOSITE_BWD_BAR_BEHIND = _bar(COMPOSITE_BWD_FLOOR, COMPOSITE_BWD_ERR32_BEHIND)
+
+
+def composite_bwd_dz_err32(K):
+    return COMPOSITE_BWD_ERR32_DZ.get(K, COMPOSITE_BWD_ERR32_DZ_LONG)
+
+
+def composite_bwd_dz_bar(K):
+    return _bar(COMPOSITE_BWD_FLOOR, composite_bwd_dz_err32(K))
+
+
+GRAD_SUBSETS = ((0, 1, 0), (0, 0, 1), (0, 0, 0))           # (g_rgb, g_depth, g_weights) given: what the existing test does not run
+
+
+def composite_bwd_n(K):
+    return (1, 5) if K == COMPOSITE_BWD_KMAX else N_LIST
+
+
+def subset_family(K):
+    """The one family per K that also runs GRAD_SUBSETS and d_z_dev = NULL: an opaque sample next to the first chunk boundary
+    where K reaches it, else `random`."""
+    return "opaque@63" if K > 64 else "random"
+
+
+def composite_grads(family, n, K):
+    """Upstream gradients (g_rgb (n, 3), g_depth (n), g_weights (n, K)), standard normal, seeded from (K, family)."""
+    rs = np.random.RandomState(_seed_of("composite_bwd", K, family))
+    return tuple(rs.standard_normal(s).astype(np.float32) for s in ((n, 3), (n,), (n, K)))
+
+
+def composite_bwd_ref(rays, z, samp, white, g_rgb, g_depth, g_w, dtype=F64):
+    """(dL/d(sample) (n, K, 4), dL/dz (n, K)) of L = <g_rgb, rgb> + <g_depth, depth> + <g_w, weights> through orc.composite
+    under autograd in `dtype` on the float32 inputs; a g that is None is absent (all None: zeros)."""
+    zt, st = as_dt(z, dtype).requires_grad_(), as_dt(samp, dtype).requires_grad_()
+    outs = orc.composite(as_dt(rays, dtype), zt, st, bool(white))                  # weights, rgb, depth
+    terms = [(o * as_dt(g, dtype)).sum() for o, g in zip(outs, (g_w, g_rgb, g_depth)) if g is not None]
+    if not terms:
+        return torch.zeros_like(st), torch.zeros_like(zt)
+    sum(terms).backward()
+    return st.grad, zt.grad
+
+
+def check_composite_bwd(fam, n, K, d_samp, d_z, ref, g_rgb_given=True):
+    """One case against its reference ref = (d_sample, d_z) in float64.  d_z may be None (not asked for).
+    Returns the per-row errors (d_sample, d_z, behind the opaque sample x 1e10); asserts the bars and the exact zeros."""
+    e_s = row_err(d_samp, ref[0], n)
+    assert e_s <= COMPOSITE_BWD_BAR_DSAMPLE, (fam, n, K, "d_sample", e_s)
+    e_z = e_b = 0.0
+    if d_z is not None:
+        e_z = row_err(d_z, ref[1], n)
+        assert e_z <= composite_bwd_dz_bar(K), (fam, n, K, "d_z", e_z)
+    if fam == "zero_sigma":                                      # relu'(0) = 0, alpha = 0, w = 0: exact zeros
+        assert float(torch.as_tensor(d_samp)[..., 3].abs().max()) == 0.0, (fam, n, K, "d_sigma not exactly 0")
+        assert d_z is None or float(torch.as_tensor(d_z).abs().max()) == 0.0, (fam, n, K, "d_z not exactly 0")
+    sl = behind(fam, K)
+    if sl is not None:      # behind an opaque sample every gradient carries T = 1e-10 x ...: order-one numbers again after x 1e10
+        e_b = row_err(torch.as_tensor(d_samp)[:, sl, :3].to(F64) * 1e10, ref[0][:, sl, :3] * 1e10, n)
+        if d_z is not None:
+            e_b = max(e_b, row_err(torch.as_tensor(d_z)[:, sl].to(F64) * 1e10, ref[1][:, sl] * 1e10, n))
+        assert e_b <= COMPOSITE_BWD_BAR_BEHIND, (fam, n, K, "behind the opaque sample", e_b)
+    return e_s, e_z, e_b
+
+
+# --------------------------------------------------------------------------- yolo_aggregate backward
+# float32 oracle under autograd against the float64 one, per (ray, anchor).  The figure comes from the maximum's own term
+# g_0 p (1 - p) where the winning logit is 8 to 10: 1 - p = 2.5e-4 is formed from a float32 p, one ulp of which is 2.4e-4 of it
+# (`random`, K = 200; 1.5e-5 at K = 128, below 1e-6 in every other family)
+AGG_BWD_ERR32 = 3.2e-5
+AGG_BWD_BAR = _bar(0.0, AGG_BWD_ERR32)                     # no earlier stage bar: twice the float32 oracle's error
+
+
+def agg_bwd_families(K):
+    return agg_families(K) + ["tie"]
+
+
+def tie_pairs(K):
+    """(first, second) positions of the exact maxima of the `tie` family: (K // 2, K - 1), and from K = 66 on (1, 65) -- the
+    same lane in two successive `k += 64` iterations.  The first of ALL tied positions takes the maximum's gradient."""
+    pairs = [(K // 2, K - 1)]
+    if K >= 66:
+        pairs.append((1, 65))
+    return pairs
+
+
+def agg_bwd_case(family, n, K, na, seed=0):
+    """raw (n, K, na * 7) and the upstream gradient g (n, na, 7), standard normal."""
+    if family == "tie":
+        raw = agg_case("random", n, K, na, seed).reshape(n, K, na, 7)
+        raw[..., 0] = np.minimum(raw[..., 0], 1.0)
+        for pair in tie_pairs(K):
+            raw[:, list(pair), :, 0] = 2.0
+        raw = raw.reshape(n, K, na * 7)
+    else:
+        raw = agg_case(family, n, K, na, seed)
+    g = np.random.RandomState(_seed_of("agg_bwd", K, na, family)).standard_normal((n, na, 7)).astype(np.float32)
+    return raw, g
+
+
+def agg_bwd_ref(raw, g, na, dtype=F64):
+    """dL/d(raw) (n, K, na * 7) of L = <g, orc.yolo_aggregate(raw)> under autograd in `dtype` on the float32 inputs."""
+    rt = as_dt(raw, dtype).requires_grad_()
+    (orc.yolo_aggregate(rt, na) * as_dt(g, dtype)).sum().backward()
+    return rt.grad
+
+
+def agg_rows(d, na):
+    """(n, K, na * 7) -> (n * na, K * 7): one row per (ray, anchor), as the kernel's wavefronts take them."""
+    d = torch.as_tensor(np.asarray(d))
+    n, K = d.shape[0], d.shape[1]
+    return d.reshape(n, K, na, 7).permute(0, 2, 1, 3).reshape(n * na, K * 7)
+
+
+def agg_row_err(got, ref, na):
+    r = agg_rows(ref, na)
+    return row_err(agg_rows(got, na), r, r.shape[0])
+
+
+def max_term(raw, g, na):
+    """The g_0 term of dL/d(raw[.., 0]) in float64 where it belongs: g_0 p (1 - p) at the FIRST index of the maximum, (n, K, na)."""
+    o = as_dt(raw, F64).reshape(raw.shape[0], raw.shape[1], na, 7)[..., 0]
+    p = torch.sigmoid(o)
+    first = torch.zeros_like(p)
+    first.scatter_(1, torch.argmax((o == o.max(1, keepdim=True)[0]).to(torch.int8), dim=1, keepdim=True), 1.0)   # first True
+    return first * (as_dt(g, F64)[:, None, :, 0] * p * (1 - p))
+
+
+def check_tie(got, ref, raw, g, K, na):
+    """The semantics of the tie: the maximum's gradient reaches the first tied index and no other.  got, ref (n, K, na * 7);
+    at each tied position got's column 0 is within the bar (x the row's maximum) of the reference -- which has the term at the
+    first and not at the others -- and the term is at least 100 bars there, so that a kernel that puts it elsewhere, twice or
+    nowhere fails.  Returns the number of (ray, anchor) rows on which the check discriminates."""
+    n = raw.shape[0]
+    G = torch.as_tensor(np.asarray(got), dtype=F64).reshape(n, K, na, 7)
+    R = torch.as_tensor(np.asarray(ref), dtype=F64).reshape(n, K, na, 7)
+    term = max_term(raw, g, na)
+    tied = sorted({i for pair in tie_pairs(K) for i in pair})
+    assert bool((term[:, tied[0]] != 0).any()) and float(term[:, tied[1:]].abs().max() if len(tied) > 1 else 0.0) == 0.0
+    top = R.abs().amax(dim=(1, 3))                                          # (n, na): the row's maximum
+    slack = AGG_BWD_BAR * top
+    for i in tied:
+        assert bool(((G[:, i, :, 0] - R[:, i, :, 0]).abs() <= slack).all()), ("tie", K, na, "position %d" % i)
+    return int((term[:, tied[0]].abs() > 100 * slack).sum())
+
+
+# --------------------------------------------------------------------------- depth-gradient gather (exact)
+GATHER_KFD = (1, 4, 63, 64, 65, 130)
+GATHER_PATTERNS = ("live", "dead", "alternating", "last_only", "random")
+
+
+def gather_case(pattern, n, kfd, seed=0):
+    """sel (n, kfd) int32: ray * kt + a random position of the ray's own row of dz, or -1; dz (n, kt); g_in (n)."""
+    rs = np.random.RandomState(_seed_of("gather", pattern, n, kfd, seed) % (2 ** 31))
+    kt = kfd + 7
+    dz = rs.standard_normal((n, kt)).astype(np.float32)
+    sel = (np.arange(n)[:, None] * kt + rs.randint(0, kt, (n, kfd))).astype(np.int32)
+    if pattern == "dead":
+        sel[:] = -1
+    elif pattern == "alternating":
+        sel[:, 1::2] = -1
+    elif pattern == "last_only":
+        sel[:, :-1] = -1
+    elif pattern == "random":
+        sel[rs.rand(n, kfd) < 0.3] = -1
+    else:
+        assert pattern == "live", pattern
+    assert bool(((sel < 0) | (sel // kt == np.arange(n)[:, None])).all())
+    return sel, dz, rs.standard_normal(n).astype(np.float32)
+
+
+def gather_ref(sel, dz, g_in=None):
+    """g_in[ray] (or 0) + the live samples' dz added one after the other in sample order, every sum rounded to float32: the
+    order depth_grad_gather_kernel promises."""
+    n, kfd = sel.shape
+    flat = np.asarray(dz, np.float32).reshape(-1)
+    s = np.zeros(n, np.float32) if g_in is None else np.array(g_in, np.float32)
+    for j in range(kfd):
+        live = sel[:, j] >= 0
+        v = np.where(live, flat[np.where(live, sel[:, j], 0)], np.float32(0)).astype(np.float32)
+        s = np.where(live, s + v, s).astype(np.float32)        # a dead sample adds nothing (not even + 0: -0 stays -0)
+    assert s.dtype == np.float32
+    return s
+
+
+# --------------------------------------------------------------------------- locate depth samples (exact)
+LOCATE_SHAPES = tuple(s for s in FINE_SHAPES if s[2] > 0)
+LOCATE_N = (5, 257)
+LOCATE_STD = (0.01, 0.05)
+ROBUST = 1e-6
+LOCATE_SEED = 0x5EED0000BEEF            # a non-zero high word
+
+
+def locate_case(n, kc, kf, kfd, seed=0):
+    """fine_case (lindisp off) with the coarse depth of a fifth of the rays exactly `near` and of a fifth exactly `far` -- about
+    half of their draws clamp -- and g = 0 on ray 0, whose depth is `near`: zz == near exactly, which is NOT inside."""
+    c = fine_case(n, kc, kf, kfd, 0, "random", seed)
+    near, far = near_far(0)
+    c["depth"] = c["depth"].copy()
+    c["depth"][0::5] = near
+    c["depth"][1::5] = far
+    c["g"] = c["g"].copy()
+    c["g"][0] = 0.0
+    return c
+
+
+def locate_expect(c, depth_std, g=None):
+    """Float64 on the float32 inputs: zz = depth + g * std (n, kfd); inside = strictly within (near, far); checked = robust
+    (further than ROBUST from both bounds) or exactly ON a bound through g == 0 (zz == depth == bound in every arithmetic)."""
+    g = np.asarray(c["g"] if g is None else g, np.float32)
+    depth = np.asarray(c["depth"], np.float32).astype(np.float64)[:, None]
+    std = float(np.float32(depth_std))
+    zz = depth + g.astype(np.float64) * std
+    near = c["rays"][:, 6:7].astype(np.float64)
+    far = c["rays"][:, 7:8].astype(np.float64)
+    inside = (zz > near) & (zz < far)
+    on_bound = (g == 0) & ((depth == near) | (depth == far))
+    checked = (np.minimum(np.abs(zz - near), np.abs(zz - far)) > ROBUST) | on_bound
+    return zz, inside, checked
+
+
+def check_located(sel, z_fine, c, depth_std, kt, g=None):
+    """sel (n, kfd) int32 and z_fine (n, kt) of one case against locate_expect.  Returns the number of samples left out."""
+    sel, z_fine = np.asarray(sel), np.asarray(z_fine, np.float32)
+    zz, inside, checked = locate_expect(c, depth_std, g)
+    n, kfd = zz.shape
+    assert sel.shape == (n, kfd) and 100 * int((~checked).sum()) < checked.size
+    assert bool((sel[checked & ~inside] == -1).all()), "a clamped sample was located"
+    ok = checked & inside
+    assert bool((sel[ok] >= 0).all()), "%d samples strictly inside (near, far) were not located" % int((sel[ok] < 0).sum())
+    ray = np.broadcast_to(np.arange(n)[:, None], (n, kfd))
+    assert bool((sel[ok] // kt == ray[ok]).all()), "a sample was located on another ray"
+    pos = sel[ok] % kt
+    val = z_fine[ray[ok], pos]
+    assert float(np.abs(val.astype(np.float64) - zz[ok]).max(initial=0.0)) <= ROBUST
+    before = z_fine[ray[ok], np.maximum(pos - 1, 0)]
+    assert bool(((pos == 0) | (before < val)).all()), "not the first position of its value"
+    rest = sel[~checked]
+    assert bool(((rest == -1) | ((rest >= 0) & (rest // kt == ray[~checked]))).all())      # left out, but never out of bounds
+    return int((~checked).sum())
+LOCATE_SEEDED_SHAPE = (64, 32, 16)

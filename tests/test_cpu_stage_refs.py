@@ -269,3 +269,212 @@ def test_duplicates_case_needs_the_first_equal_rule():
                 del lst[i]
             i += 1
     assert [tuple(r) for r in boxes[kept]] != rows
+
+
+# =========================================================================== backward stages
+def composite_bwd_cases():
+    """Every case of the composite backward sweep: (K, family, n, white, (g_rgb, g_depth, g_weights given))."""
+    for K in sr.COMPOSITE_BWD_K:
+        for fam in sr.composite_families(K):
+            for n in sr.composite_bwd_n(K):
+                for white in (0, 1):
+                    yield K, fam, n, white, (1, 1, 1)
+                    if fam == sr.subset_family(K):
+                        for sub in sr.GRAD_SUBSETS:
+                            yield K, fam, n, white, sub
+
+
+def measure_composite_bwd():
+    """The float32 oracle under autograd against the float64 one on every case, per row: d_sample, d_z by K, behind x 1e10.
+    check_composite_bwd also asserts the bars and the exact zeros on the float32 oracle."""
+    ds = beh = 0.0
+    dz = {}
+    for K, fam, n, white, sub in composite_bwd_cases():
+        rays, z, samp = sr.composite_bwd_case(fam, n, K)
+        g = [v if on else None for v, on in zip(sr.composite_grads(fam, n, K), sub)]
+        r64 = sr.composite_bwd_ref(rays, z, samp, white, *g, dtype=F64)
+        r32 = sr.composite_bwd_ref(rays, z, samp, white, *g, dtype=F32)
+        e = sr.check_composite_bwd(fam, n, K, r32[0], r32[1], r64)
+        ds, beh = max(ds, e[0]), max(beh, e[2])
+        key = K if K in sr.COMPOSITE_BWD_ERR32_DZ else "long"
+        dz[key] = max(dz.get(key, 0.0), e[1])
+        if sub == (0, 0, 0):
+            assert float(r64[0].abs().max()) == 0.0 and float(r64[1].abs().max()) == 0.0
+    return ds, dz, beh
+
+
+def test_composite_backward_fp32_oracle_error():
+    ds, dz, beh = measure_composite_bwd()
+    held("composite backward, d_sample per ray", ds, sr.COMPOSITE_BWD_ERR32_DSAMPLE)
+    for K in sr.COMPOSITE_BWD_ERR32_DZ:
+        held("composite backward, d_z per ray, K = %d" % K, dz[K], sr.composite_bwd_dz_err32(K))
+    held("composite backward, d_z per ray, K >= 63", dz["long"], sr.COMPOSITE_BWD_ERR32_DZ_LONG)
+    held("composite backward, behind an opaque sample x 1e10", beh, sr.COMPOSITE_BWD_ERR32_BEHIND)
+    assert sr.COMPOSITE_BWD_BAR_DSAMPLE == 2e-5 and all(sr.composite_bwd_dz_bar(K) >= 2e-5 for K in sr.COMPOSITE_BWD_K)   # the floor
+
+
+def test_composite_backward_inputs_avoid_the_intermediate_opacity_regime():
+    """sigma x delta is at most X_CAP or is the planted 1e6 (stage_ref.py says why), and the cap leaves the families what they
+    are: it moves a sample of the ordinary families only, and few of those."""
+    moved = total = 0
+    for K in sr.COMPOSITE_BWD_K:
+        for fam in sr.composite_families(K):
+            for n in sr.composite_bwd_n(K):
+                rays, z, samp = sr.composite_bwd_case(fam, n, K)
+                raw = sr.composite_case(fam, n, K)[2]
+                zz = np.concatenate([z, rays[:, 7:8]], 1).astype(np.float64)
+                x = np.diff(zz, axis=1) * np.maximum(samp[..., 3].astype(np.float64), 0.0)
+                assert bool(((x <= sr.X_CAP * (1 + 1e-6)) | (samp[..., 3] == np.float32(1e6))).all()), (K, fam, n)
+                assert np.array_equal(samp[..., :3], raw[..., :3]) and bool((samp[..., 3] <= raw[..., 3]).all())
+                assert np.array_equal(samp[..., 3] == np.float32(1e6), raw[..., 3] == np.float32(1e6))
+                moved += int((samp[..., 3] != raw[..., 3]).sum())
+                total += x.size
+                if fam == "z_last_far":
+                    assert bool((x[:, -1] == 0).all()) and bool((samp[:, -1, 3] > 0).all())       # a zero last delta under a live sigma
+    print("composite backward inputs: %d of %d samples brought down to sigma x delta = %g" % (moved, total, sr.X_CAP))
+    assert 0 < moved < 0.05 * total
+
+
+def aggregate_bwd_cases():
+    for K in sr.AGG_K:
+        for na in sr.AGG_ANCHORS:
+            for fam in sr.agg_bwd_families(K):
+                for n in sr.N_LIST:
+                    yield K, na, fam, n
+
+
+def measure_aggregate_bwd():
+    worst, rows = 0.0, 0
+    for K, na, fam, n in aggregate_bwd_cases():
+        raw, g = sr.agg_bwd_case(fam, n, K, na)
+        r32, r64 = sr.agg_bwd_ref(raw, g, na, F32), sr.agg_bwd_ref(raw, g, na, F64)
+        worst = max(worst, sr.agg_row_err(r32, r64, na))
+        if fam == "all_low":
+            assert float(r64.abs().max()) < 1e-36 < sr.TINY             # at float32's smallest normal and below: the absolute check
+        if fam == "tie" and K > 1:
+            rows += sr.check_tie(r32, r64, raw, g, K, na)
+    return worst, rows
+
+
+def test_aggregate_backward_fp32_oracle_error():
+    worst, rows = measure_aggregate_bwd()
+    held("yolo_aggregate backward, per (ray, anchor)", worst, sr.AGG_BWD_ERR32)
+    assert rows > 1000, rows          # the tie check discriminates (the maximum's term is 100 bars and more) on this many rows
+
+
+@pytest.mark.parametrize("dtype", [F32, F64], ids=["float32", "float64"])
+def test_max_backward_sends_a_tie_to_the_first_index(dtype):
+    """torch's max(dim) backward on the CPU, which the references of the `tie` family rest on: the gradient of out[..., 0]
+    alone reaches raw[.., 0] at the FIRST tied position of each (ray, anchor) and nowhere else."""
+    for K in sr.AGG_K:
+        for na in (1, 3):
+            raw, g = sr.agg_bwd_case("tie", 5, K, na)
+            tied = sorted({i for pair in sr.tie_pairs(K) for i in pair})
+            o = raw.reshape(5, K, na, 7)[..., 0]
+            assert bool((o[:, tied] == 2.0).all()) and float(np.delete(o, tied, axis=1).max(initial=-9.0)) <= 1.0
+            rt = sr.as_dt(raw, dtype).requires_grad_()
+            orc.yolo_aggregate(rt, na)[..., 0].sum().backward()
+            d = rt.grad.reshape(5, K, na, 7)
+            assert float(d[..., 1:].abs().max()) == 0.0
+            hit = d[..., 0] != 0
+            assert bool(hit[:, tied[0]].all()) and int(hit.sum()) == 5 * na, (K, na, hit.sum(1))
+            p = 1 / (1 + np.exp(-2.0))
+            assert abs(float(d[0, tied[0], 0, 0]) - p * (1 - p)) < 1e-6
+            assert sr.err(sr.max_term(raw, np.ones_like(g), na), d[..., 0]) < 1e-6      # the restatement check_tie uses
+
+
+def test_gather_reference_is_a_sequential_float32_sum():
+    for kfd in sr.GATHER_KFD:
+        for pat in sr.GATHER_PATTERNS:
+            for n in sr.N_LIST:
+                sel, dz, g_in = sr.gather_case(pat, n, kfd)
+                assert sel.dtype == np.int32 and sel.shape == (n, kfd) and int(sel.max()) < dz.size
+                live = sel >= 0
+                assert {"live": live.all(), "dead": not live.any(), "alternating": live[:, 0::2].all() and not live[:, 1::2].any(),
+                        "last_only": live[:, -1].all() and not live[:, :-1].any(),
+                        "random": kfd * n < 50 or 0.15 < 1 - live.mean() < 0.45}[pat], (pat, n, kfd)
+                for gi in (None, g_in):
+                    ref = sr.gather_ref(sel, dz, gi)
+                    v = np.where(live, dz.reshape(-1)[np.maximum(sel, 0)].astype(np.float64), 0.0)
+                    exact = v.sum(1) + (0.0 if gi is None else gi.astype(np.float64))
+                    mag = np.abs(v).sum(1) + (0.0 if gi is None else np.abs(gi))
+                    assert ref.dtype == np.float32 and bool((np.abs(ref - exact) <= (kfd + 1) * 2.0 ** -24 * mag).all())
+                    if pat == "dead":
+                        assert np.array_equal(ref, np.zeros(n, np.float32) if gi is None else gi)
+    # the order matters at float32: summing the same samples backwards gives other bits somewhere
+    sel, dz, _ = sr.gather_case("live", 257, 130)
+    back = sr.gather_ref(sel[:, ::-1], dz)
+    assert not np.array_equal(back, sr.gather_ref(sel, dz))
+
+
+def host_locate(c, z_fine, depth_std, g=None):
+    """locate_depth_samples_kernel restated in numpy float32 on a float32 z_fine: first position of clamp(zz), -1 if clamped."""
+    g = np.asarray(c["g"] if g is None else g, np.float32)
+    zz = (c["depth"][:, None] + g * np.float32(depth_std)).astype(np.float32)
+    near, far = c["rays"][:, 6:7], c["rays"][:, 7:8]
+    n, kt = z_fine.shape
+    sel = np.full(zz.shape, -1, np.int32)
+    for r in range(n):
+        lo = np.searchsorted(z_fine[r], np.clip(zz[r], near[r], far[r]), side="left")
+        found = (lo < kt) & (z_fine[r][np.minimum(lo, kt - 1)] == zz[r]) & (zz[r] > near[r]) & (zz[r] < far[r])
+        sel[r] = np.where(found, r * kt + lo, -1)
+    return sel
+
+
+def test_locate_cases_are_robust_and_their_check_holds_on_the_float32_oracle():
+    for kc, kf, kfd in sr.LOCATE_SHAPES:
+        for n in sr.LOCATE_N:
+            c = sr.locate_case(n, kc, kf, kfd)
+            assert float(c["depth"][0]) == np.float32(0.8) and not c["g"][0].any()
+            for std in sr.LOCATE_STD:
+                zz, inside, checked = sr.locate_expect(c, std)
+                assert 100 * int((~checked).sum()) < checked.size, (kc, kf, kfd, n, std)     # under 1 % left out
+                assert not inside[0].any() and checked[0].all()                              # zz == near exactly: not inside, and checked
+                if n * kfd >= 100:
+                    assert 0.2 * inside.size < int(inside.sum()) < 0.95 * inside.size       # both kinds are present
+                z32 = sr.fine_ref(c, kc, kf, kfd, 0, F32, depth_std=std).numpy()
+                sel = host_locate(c, z32, std)
+                sr.check_located(sel, z32, c, std, kc + kf)
+                wrong = sel.copy()
+                wrong[wrong >= 0] += 1                                                     # one position further: caught
+                if (sel >= 0).any():
+                    with pytest.raises(AssertionError):
+                        sr.check_located(wrong, z32, c, std, kc + kf)
+    # the seeded case: the draws of the renderer's generator instead of the explicit ones
+    kc, kf, kfd = sr.LOCATE_SEEDED_SHAPE
+    c = sr.locate_case(257, kc, kf, kfd)
+    g = orc.seeded_draws(sr.LOCATE_SEED, 257, kc, kf, kfd)["g_depth"]
+    zz, inside, checked = sr.locate_expect(c, 0.05, g)
+    assert 100 * int((~checked).sum()) < checked.size and 0.2 * inside.size < int(inside.sum()) < 0.95 * inside.size
+
+
+def test_backward_stage_entry_points_are_declared_and_refuse_on_the_host():
+    """The three stage entry points: declared with the reference lines they restate, bound with the header's argument counts,
+    and every bad argument refused before anything touches a device (so this runs without one)."""
+    import re
+    from pixel_nerf_yolo_amd import lib as plib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hdr = open(os.path.join(root, "include", "pnyolo.h")).read()
+    assert re.search(r"#define\s+PNY_ABI_VERSION\s+11\b", hdr)                     # additions: the ABI number stays
+    for name, n_args, cites in (("pny_yolo_aggregate_backward", 7, "yolo.py:96-114"), ("pny_locate_depth_samples", 11, "nerf.py:156-167"),
+                                ("pny_depth_grad_gather", 7, "nerf.py:156-167")):
+        decl = re.search(r"\bint\s+%s\s*\(([^;]*)\)\s*;" % name, hdr)
+        assert decl and decl.group(1).count(",") + 1 == n_args == len(plib.SIGNATURES[name][1]), name
+        assert cites in hdr[hdr.rindex("/*", 0, decl.start()):decl.start()], name
+    if not os.path.exists(plib.LIB_PATH):
+        plib.build()
+    L = plib.load()
+    buf = np.zeros(64, np.float32)
+    p = plib.C.c_void_p(buf.ctypes.data)          # never dereferenced: every call below is refused first
+    assert L.pny_composite_backward(p, p, p, 1, sr.COMPOSITE_BWD_KMAX + 1, 1, p, p, p, p, p, None) == -1
+    assert b"too many samples" in L.pny_last_error()
+    for bad in ((p, p, -1, 4, 3, p), (p, p, 1, 0, 3, p), (p, p, 1, 4, 0, p), (None, p, 1, 4, 1, p), (p, None, 1, 4, 1, p), (p, p, 1, 4, 1, None)):
+        assert L.pny_yolo_aggregate_backward(*bad, None) == -1 and b"pny_yolo_aggregate_backward" in L.pny_last_error(), bad
+    for bad in ((p, p, p, -1, 4, p), (p, p, p, 1, -1, p), (None, p, p, 1, 4, p), (p, None, p, 1, 4, p), (p, p, p, 1, 4, None)):
+        assert L.pny_depth_grad_gather(*bad, None) == -1 and b"pny_depth_grad_gather" in L.pny_last_error(), bad
+    ok = [p, p, p, 0, p, 1, 8, 4, 0.01, p]
+    for i, v in ((5, -1), (6, 0), (7, -1), (7, 9), (0, None), (1, None), (4, None), (9, None), (5, 2 ** 31 // 8 + 1)):
+        bad = list(ok)
+        bad[i] = v
+        assert L.pny_locate_depth_samples(*bad, None) == -1 and b"pny_locate_depth_samples" in L.pny_last_error(), (i, v)
+    assert not buf.any()

@@ -3,6 +3,10 @@ The renderer's stage kernels (csrc/render_kernels.hip: sample_coarse, composite,
 and the detection tail (csrc/detect.hip: cells_to_bboxes, nms, tp / fp / fn) through pixel_nerf_yolo_amd.util, swept over the
 shapes, edges and ties where such kernels go wrong (-m gpu, real MI355X).
 
+The MLP-free backward stages (csrc/mlp_bwd.hip: composite_bwd, yolo_aggregate_bwd, depth_grad_gather, locate_depth_samples)
+follow, through their own entry points: the two float ones against the oracle under autograd, the two exact ones against a host
+restatement, bit for bit.
+
 Every float result is held to oracle/pnyolo_oracle.py evaluated in float64 on the float32 inputs, every index / integer result
 of the detection tail to the oracle's list semantics (tests/stage_ref.py nms_fast, proven equal to orc.nms and to the
 reference's captures in tests/test_cpu_stage_refs.py), exactly.  The inputs, the bars and where each bar comes from are in
@@ -307,6 +311,188 @@ def test_tp_fp_fn_sweep(name):
     ref = sr.tp_fp_fn_fast(t, p, nms_iou, nms_t, m)
     assert putil.calculate_tp_fp_fn(dev(t), dev(p), nms_iou, nms_t, m) == ref, name
     assert putil.calculate_tp_fp_fn(t.tolist(), p.tolist(), nms_iou, nms_t, m, device=DEV) == ref, name
+
+
+# =========================================================================== backward stages (csrc/mlp_bwd.hip)
+def opt_dev(x):
+    return None if x is None else dev(x)
+
+
+def hip_composite_bwd(rays, z, samp, K, white, g_rgb, g_depth, g_w, want_dz=True):
+    r, zz, s = dev(rays), dev(z), dev(samp)
+    n = r.shape[0]
+    a, b, c = opt_dev(g_rgb), opt_dev(g_depth), opt_dev(g_w)
+    d_samp = torch.full((n, K, 4), float("nan"), device=DEV)
+    d_z = torch.full((n, K), float("nan"), device=DEV) if want_dz else None
+    plib.check(plib.load().pny_composite_backward(plib.ptr(r), plib.ptr(zz), plib.ptr(s), n, K, white, plib.ptr(a), plib.ptr(b),
+                                                  plib.ptr(c), plib.ptr(d_samp), plib.ptr(d_z), stream()))
+    torch.cuda.synchronize()
+    return d_samp.cpu(), None if d_z is None else d_z.cpu()
+
+
+@pytest.mark.parametrize("white", [0, 1])
+@pytest.mark.parametrize("K", sr.COMPOSITE_BWD_K)
+def test_composite_backward_sweep(K, white):
+    """composite_bwd_kernel per ray against autograd through the oracle in float64: every family of the forward sweep, every n
+    tail, K to the accepted maximum; for one family per K also each subset of upstream gradients that
+    test_composite_backward_vs_autograd leaves out (all NULL: exactly zero) and d_z_dev = NULL."""
+    worst = [0.0, 0.0, 0.0]
+    for fam in sr.composite_families(K):
+        for n in sr.composite_bwd_n(K):
+            rays, z, samp = sr.composite_bwd_case(fam, n, K)
+            grads = sr.composite_grads(fam, n, K)
+            subsets = ((1, 1, 1),) + (sr.GRAD_SUBSETS if fam == sr.subset_family(K) else ())
+            for sub in subsets:
+                g = [v if on else None for v, on in zip(grads, sub)]
+                ref = sr.composite_bwd_ref(rays, z, samp, white, *g, dtype=F64)
+                d_samp, d_z = hip_composite_bwd(rays, z, samp, K, white, *g)
+                e = sr.check_composite_bwd(fam, n, K, d_samp, d_z, ref)
+                worst = [max(a, b) for a, b in zip(worst, e)]
+                if sub == (0, 0, 0):
+                    assert float(d_samp.abs().max()) == 0.0 and float(d_z.abs().max()) == 0.0, (fam, n, K)
+                if sub == (1, 1, 1) and fam == sr.subset_family(K):          # d_z not asked for: d_sample is the same, bit for bit
+                    only = hip_composite_bwd(rays, z, samp, K, white, *g, want_dz=False)[0]
+                    assert np.array_equal(bits(only), bits(d_samp)), (fam, n, K, "d_z_dev = NULL")
+    print("composite backward K=%d white=%d: worst per-ray error vs float64 d_sample %.3e (bar %.1e), d_z %.3e (bar %.1e), "
+          "behind an opaque sample x 1e10 %.3e (bar %.1e)" % (K, white, worst[0], sr.COMPOSITE_BWD_BAR_DSAMPLE, worst[1],
+                                                               sr.composite_bwd_dz_bar(K), worst[2], sr.COMPOSITE_BWD_BAR_BEHIND))
+
+
+def hip_agg_bwd(raw, g, K, na):
+    r, gg = dev(raw), dev(g)
+    d = torch.full((r.shape[0], K, na * 7), float("nan"), device=DEV)
+    plib.check(plib.load().pny_yolo_aggregate_backward(plib.ptr(r), plib.ptr(gg), r.shape[0], K, na, plib.ptr(d), stream()))
+    torch.cuda.synchronize()
+    return d.cpu()
+
+
+@pytest.mark.parametrize("na", sr.AGG_ANCHORS)
+@pytest.mark.parametrize("K", sr.AGG_K)
+def test_yolo_aggregate_backward_sweep(K, na):
+    """yolo_aggregate_bwd_kernel per (ray, anchor) against autograd through the oracle in float64; in the `tie` family the
+    maximum's gradient reaches the first tied index and no other."""
+    worst = 0.0
+    for fam in sr.agg_bwd_families(K):
+        for n in sr.N_LIST:
+            raw, g = sr.agg_bwd_case(fam, n, K, na)
+            ref = sr.agg_bwd_ref(raw, g, na, F64)
+            got = hip_agg_bwd(raw, g, K, na)
+            e = sr.agg_row_err(got, ref, na)
+            worst = max(worst, e)
+            assert e <= sr.AGG_BWD_BAR, (fam, n, K, na, e)
+            if fam == "tie" and K > 1:
+                rows = sr.check_tie(got, ref, raw, g, K, na)
+                assert n < 257 or rows > n * na // 2, (K, na, n, rows)
+    print("yolo_aggregate backward K=%d A=%d: worst per-(ray, anchor) error vs float64 %.3e (bar %.1e)" % (K, na, worst, sr.AGG_BWD_BAR))
+
+
+def hip_gather(sel, dz, g_in):
+    s = torch.as_tensor(sel, dtype=torch.int32, device=DEV).contiguous()
+    d, gi = dev(dz), opt_dev(g_in)
+    n, kfd = sel.shape
+    out = torch.full((n,), float("nan"), device=DEV)
+    plib.check(plib.load().pny_depth_grad_gather(C.c_void_p(s.data_ptr()), plib.ptr(d), plib.ptr(gi), n, kfd, plib.ptr(out), stream()))
+    torch.cuda.synchronize()
+    return out.cpu()
+
+
+@pytest.mark.parametrize("kfd", sr.GATHER_KFD)
+def test_depth_grad_gather_sweep(kfd):
+    """depth_grad_gather_kernel: the sum over a ray's located depth samples in sample order, bit for bit the sequential float32
+    sum -- across the `j0 += 64` chunks, with a partial last chunk, with wholly clamped rays, with and without g_in."""
+    cases = 0
+    for pat in sr.GATHER_PATTERNS:
+        for n in sr.N_LIST:
+            sel, dz, g_in = sr.gather_case(pat, n, kfd)
+            for gi in (None, g_in):
+                got = hip_gather(sel, dz, gi)
+                ref = sr.gather_ref(sel, dz, gi)
+                assert np.array_equal(bits(got), bits(ref)), (pat, n, kfd, gi is not None, float(np.abs(got.numpy() - ref).max()))
+                cases += 1
+    print("depth_grad_gather kfd=%d: %d cases bit-identical to the sequential float32 sum" % (kfd, cases))
+
+
+def hip_locate(c, z_fine, kt, kfd, depth_std, g=None, seed=0):
+    r, d, zf = dev(c["rays"]), dev(c["depth"]), dev(z_fine)
+    gg = opt_dev(g)
+    n = r.shape[0]
+    sel = torch.full((n, kfd), -7, dtype=torch.int32, device=DEV)
+    plib.check(plib.load().pny_locate_depth_samples(plib.ptr(r), plib.ptr(d), plib.ptr(gg), seed, plib.ptr(zf), n, kt, kfd, depth_std,
+                                                    C.c_void_p(sel.data_ptr()), stream()))
+    torch.cuda.synchronize()
+    return sel.cpu().numpy()
+
+
+@pytest.mark.parametrize("shape", sr.LOCATE_SHAPES, ids=lambda s: "%d-%d-%d" % s)
+def test_locate_depth_samples_sweep(shape):
+    """locate_depth_samples_kernel on the real sorted output of pny_sample_fine: every robust sample strictly inside (near, far)
+    is found on its own ray at the first position of its value, every clamped one -- zz == near exactly included -- gives -1."""
+    kc, kf, kfd = shape
+    left_out = total = 0
+    for n in sr.LOCATE_N:
+        c = sr.locate_case(n, kc, kf, kfd)
+        for std in sr.LOCATE_STD:
+            z_fine = hip_fine(c, kc, kf, kfd, 0, depth_std=std)
+            sel = hip_locate(c, z_fine, kc + kf, kfd, std, g=c["g"])
+            assert bool((sel[0] == -1).all()), "zz == near exactly was located"
+            left_out += sr.check_located(sel, z_fine.numpy(), c, std, kc + kf)
+            total += sel.size
+    print("locate_depth_samples %s: %d samples exact, %d within %.0e of a bound left out" % (shape, total - left_out, left_out, sr.ROBUST))
+
+
+def test_locate_depth_samples_seeded():
+    """g_dev = NULL: the kernel re-creates the forward's seeded normals (normal_at is compiled into render_kernels.hip and into
+    mlp_bwd.hip).  Every located position holds a depth strictly inside (near, far), and a ray has as many located samples as the
+    oracle's generator puts strictly inside."""
+    kc, kf, kfd = sr.LOCATE_SEEDED_SHAPE
+    n, std, kt = 257, 0.05, kc + kf
+    c = sr.locate_case(n, kc, kf, kfd)
+    seeded = dict(c, g=np.zeros((n, 0), np.float32))                     # no explicit normals: pny_sample_fine draws them from the seed
+    z_fine = sr.hip_fine(seeded, kc, kf, kfd, 0, depth_std=std, seed=sr.LOCATE_SEED)
+    sel = hip_locate(c, z_fine, kt, kfd, std, g=None, seed=sr.LOCATE_SEED)
+    g = orc.seeded_draws(sr.LOCATE_SEED, n, kc, kf, kfd)["g_depth"]
+    sr.check_located(sel, z_fine.numpy(), c, std, kt, g=g)
+    zz, inside, checked = sr.locate_expect(c, std, g)
+    val = z_fine.numpy().reshape(-1)[sel[sel >= 0]]
+    near, far = (np.float32(v) for v in sr.near_far(0))
+    assert bool(((val > near) & (val < far)).all())
+    rows = checked.all(1)
+    assert int(rows.sum()) > 0.9 * n and np.array_equal((sel >= 0).sum(1)[rows], inside.sum(1)[rows])
+    other = hip_locate(c, z_fine, kt, kfd, std, g=None, seed=sr.LOCATE_SEED + 1)        # another seed finds next to nothing
+    assert int((other >= 0).sum()) < 0.02 * int((sel >= 0).sum())
+
+
+def test_backward_stages_refuse_bad_arguments():
+    L = plib.load()
+    one = torch.zeros(64, device=DEV)
+    p, st = plib.ptr(one), stream()
+    isel = C.c_void_p(torch.zeros(64, dtype=torch.int32, device=DEV).data_ptr())
+    K = sr.COMPOSITE_BWD_KMAX + 1
+    assert L.pny_composite_backward(p, p, p, 1, K, 1, p, p, p, p, p, st) == -1 and b"too many samples" in L.pny_last_error()
+    assert L.pny_composite_backward(p, p, p, -1, 4, 1, p, p, p, p, p, st) == -1
+    assert L.pny_composite_backward(p, p, p, 1, 0, 1, p, p, p, p, p, st) == -1
+    for miss in range(3):
+        a = [p, p, p]
+        a[miss] = None
+        assert L.pny_composite_backward(a[0], a[1], a[2], 1, 4, 1, p, p, p, p, p, st) == -1
+    assert L.pny_composite_backward(p, p, p, 1, 4, 1, p, p, p, None, p, st) == -1
+    assert L.pny_composite_backward(None, None, None, 0, 4, 1, None, None, None, None, None, st) == 0          # n = 0: no launch
+    for bad in ((p, p, -1, 4, 3, p), (p, p, 1, 0, 3, p), (p, p, 1, 4, 0, p), (None, p, 1, 4, 1, p), (p, None, 1, 4, 1, p), (p, p, 1, 4, 1, None)):
+        assert L.pny_yolo_aggregate_backward(*bad, st) == -1 and b"pny_yolo_aggregate_backward" in L.pny_last_error(), bad
+    assert L.pny_yolo_aggregate_backward(None, None, 0, 4, 3, None, st) == 0
+    for bad in ((isel, p, p, -1, 4, p), (isel, p, p, 1, -1, p), (None, p, p, 1, 4, p), (isel, None, p, 1, 4, p), (isel, p, p, 1, 4, None)):
+        assert L.pny_depth_grad_gather(*bad, st) == -1 and b"pny_depth_grad_gather" in L.pny_last_error(), bad
+    assert L.pny_depth_grad_gather(None, None, None, 0, 4, None, st) == 0
+    ok = [p, p, p, 0, p, 1, 8, 4, 0.01, isel]
+    for i, v in ((5, -1), (6, 0), (7, -1), (7, 9), (0, None), (1, None), (4, None), (9, None), (5, 2 ** 31 // 8 + 1)):
+        bad = list(ok)
+        bad[i] = v
+        assert L.pny_locate_depth_samples(*bad, st) == -1 and b"pny_locate_depth_samples" in L.pny_last_error(), (i, v)
+    assert L.pny_locate_depth_samples(None, None, None, 0, None, 0, 8, 4, 0.01, None, st) == 0
+    with pytest.raises(plib.PnyError):
+        plib.check(L.pny_locate_depth_samples(*ok[:5], -1, *ok[6:], st))
+    torch.cuda.synchronize()
+    assert float(one.abs().max()) == 0.0                                  # nothing was launched on the refused calls
 
 
 # --------------------------------------------------------------------------- a second device in the same process
