@@ -713,6 +713,36 @@ int pny_view_metrics(const pny_view_metrics_desc* desc, const float* rgb_dev, co
                      double* metrics_dev /* (NV, 2) {psnr, ssim}, or NULL */,
                      uint8_t* rgb8_dev /* (NV, H, W, 3), or NULL */, pny_stream stream);
 
+/* ---- colour jitter: the training-time augmentation of all views of all objects in ONE launch (csrc/augment.hip).
+ * Replaces the four passes per view that the reference's ColorJitterDataset runs on CPU tensors in every __getitem__
+ * (src/data/data_util.py:34-47; get_split_dataset wraps the training split of `yolo` and `dvr_dtu` in it,
+ * src/data/__init__.py:12-76).  Model-free, raw device pointers, enqueued on `stream`: no workspace, no allocation, no
+ * synchronisation, and the same input gives the same bits on every run (no atomics; one workgroup owns one image).
+ *
+ * images_dev: PNY_IMG_F32_NCHW_PM1  (n_objs, n_views, 3, H, W) fp32 in [-1, 1], the datasets' `images`: t = (x + 1) * 0.5;
+ *             PNY_IMG_U8_NHWC       (n_objs, n_views, H, W, 3) bytes as decoded: t = x / 255.  Any byte alignment.
+ * factors_host (n_objs, 4) = per object {hue, saturation, brightness, contrast}, the four draws of data_util.py:35-38 in
+ * that order; read before the call returns.
+ * out_dev (n_objs, n_views, 3, H, W) fp32 in [-1, 1]; for PNY_IMG_F32_NCHW_PM1 it may be images_dev (in place).
+ * Per image, all in fp32, in this order (data_util.py:41-45):
+ *   saturation  blend(t, grey(t), saturation), grey = 0.2989 r + 0.587 g + 0.114 b, blend(a, b, f) = clamp(f a + (1 - f) b, 0, 1)
+ *   hue         RGB -> HSV, h <- (h + hue) mod 1, HSV -> RGB
+ *   contrast    blend(t, mean, contrast), mean = the image's mean grey level after the two steps above (an fp64 sum in a fixed
+ *               order, rounded to fp32)
+ *   brightness  blend(t, 0, brightness)
+ * and out = t * 2 - 1.
+ * PNY_ERR_ARG, before any launch: a NULL pointer, a non-positive size, an unknown in_format, n_objs > PNY_JITTER_MAX_OBJS (the
+ * caller splits), 2^31 or more elements (n_objs * n_views * H * W * 3), |hue| > 0.5, a negative or non-finite saturation,
+ * brightness or contrast, out_dev == images_dev with PNY_IMG_U8_NHWC. */
+enum { PNY_IMG_F32_NCHW_PM1 = 0, PNY_IMG_U8_NHWC = 1 };
+#define PNY_JITTER_MAX_OBJS 64
+typedef struct pny_color_jitter_desc {
+    int32_t n_objs, n_views, height, width; /* channels = 3 */
+    int32_t in_format;                      /* PNY_IMG_F32_NCHW_PM1 | PNY_IMG_U8_NHWC */
+} pny_color_jitter_desc;
+int pny_color_jitter(const pny_color_jitter_desc* desc, const void* images_dev, const float* factors_host, float* out_dev,
+                     pny_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

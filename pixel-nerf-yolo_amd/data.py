@@ -7,7 +7,8 @@ Host-side Python mirroring the reference's interface (same class names, construc
   YOLODataset  reference src/data/YOLODataset.py:10-225 (incl. the anchor / cell target assignment)
   DVRDataset   reference src/data/DVRDataset.py:11-275 (ShapeNet / NMR renderings and the DTU sub-format)
   MultiObjectDataset  reference src/data/MultiObjectDataset.py:14-117 (scenes of several ShapeNet objects, NeRF-style transforms.json)
-  ColorJitterDataset  reference src/data/data_util.py:13-55 (training-time augmentation of ``dvr_dtu`` and ``yolo``)
+  ColorJitterDataset  reference src/data/data_util.py:13-55 (training-time augmentation of ``dvr_dtu`` and ``yolo``;
+                      ``defer=True`` only draws the factors, for ``augment.color_jitter`` to apply on the device)
   get_split_dataset  reference src/data/__init__.py:12-76 (types ``srn``, ``multi_obj``, ``dvr``, ``dvr_gen``, ``dvr_dtu`` and ``yolo``)
   psnr / ssim / write_views  what eval/eval.py:291-359 does with skimage / imageio
 
@@ -226,9 +227,10 @@ class YOLODataset(torch.utils.data.Dataset):
         return tuple(targets)
 
 
-def get_split_dataset(dataset_type, datadir, want_split="all", training=True, **kwargs):
+def get_split_dataset(dataset_type, datadir, want_split="all", training=True, jitter_on_device=False, **kwargs):
     """reference src/data/__init__.py:12-76: dataset class + flags per type name; the training split of ``dvr_dtu`` and
-    ``yolo`` is wrapped in the colour-jitter augmentation."""
+    ``yolo`` is wrapped in the colour-jitter augmentation.  ``jitter_on_device=True`` defers that augmentation: the items
+    carry their factors (``ColorJitterDataset(defer=True)``) and the trainer applies them with ``augment.color_jitter``."""
     flags, aug, aug_flags = {}, None, {}
     if dataset_type == "srn":
         dset_class = SRNDataset
@@ -255,7 +257,7 @@ def get_split_dataset(dataset_type, datadir, want_split="all", training=True, **
     sets = [dset_class(datadir, stage=st, **flags, **kwargs) if want else None
             for st, want in (("train", want_train), ("val", want_val), ("test", want_test))]
     if sets[0] is not None and aug is not None:
-        sets[0] = aug(sets[0], **aug_flags)
+        sets[0] = aug(sets[0], defer=jitter_on_device, **aug_flags)
     if want_split in ("train", "val", "test"):
         return sets[("train", "val", "test").index(want_split)]
     return tuple(sets)
@@ -496,10 +498,13 @@ def adjust_hue(img, factor):
 
 class ColorJitterDataset(torch.utils.data.Dataset):
     """Wraps a dataset: ONE random (hue, saturation, brightness, contrast) draw per item, applied to all of its views
-    (images are mapped from [-1, 1] to [0, 1] and back; order saturation, hue, contrast, brightness)."""
+    (images are mapped from [-1, 1] to [0, 1] and back; order saturation, hue, contrast, brightness).
+    ``defer=True`` makes the same draw but leaves ``images`` as they are and adds ``data["jitter"]``, the (4,) fp32 factors
+    {hue, saturation, brightness, contrast} (collated to (SB, 4)), for ``augment.color_jitter`` to apply on the device."""
 
     def __init__(self, base_dset, hue_range=0.1, saturation_range=0.1, brightness_range=0.1, contrast_range=0.1,
-                 extra_inherit_attrs=()):
+                 extra_inherit_attrs=(), defer=False):
+        self.defer = defer
         self.hue_range = [-hue_range, hue_range]
         self.saturation_range = [1 - saturation_range, 1 + saturation_range]
         self.brightness_range = [1 - brightness_range, 1 + brightness_range]
@@ -508,9 +513,14 @@ class ColorJitterDataset(torch.utils.data.Dataset):
         for attr in ["z_near", "z_far", "base_path", "image_to_tensor", *extra_inherit_attrs]:
             setattr(self, attr, getattr(base_dset, attr))
 
-    def apply_color_jitter(self, images):
+    def draw_factors(self):
+        """The item's four draws, in the order the reference makes them."""
         hue, sat = np.random.uniform(*self.hue_range), np.random.uniform(*self.saturation_range)
         bri, con = np.random.uniform(*self.brightness_range), np.random.uniform(*self.contrast_range)
+        return hue, sat, bri, con
+
+    def apply_color_jitter(self, images):
+        hue, sat, bri, con = self.draw_factors()
         for i in range(len(images)):
             t = (images[i] + 1.0) * 0.5
             t = adjust_brightness(adjust_contrast(adjust_hue(adjust_saturation(t, sat), hue), con), bri)
@@ -522,7 +532,10 @@ class ColorJitterDataset(torch.utils.data.Dataset):
 
     def __getitem__(self, idx):
         data = self.base_dset[idx]
-        data["images"] = self.apply_color_jitter(data["images"])
+        if self.defer:
+            data["jitter"] = torch.tensor(self.draw_factors(), dtype=torch.float32)
+        else:
+            data["images"] = self.apply_color_jitter(data["images"])
         return data
 
 

@@ -86,6 +86,11 @@ class ViewMetricsDesc(C.Structure):
                 ("win_size", C.c_int32)]
 
 
+class ColorJitterDesc(C.Structure):
+    _fields_ = [("n_objs", C.c_int32), ("n_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("in_format", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/pnyolo.h declares
 SIGNATURES = {
     "pny_version": (C.c_int, []),
@@ -183,6 +188,7 @@ SIGNATURES = {
     "pny_finite_check_tensors": (C.c_int, [C.POINTER(C.c_void_p), c_i64_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p]),
     "pny_finite_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "pny_view_metrics": (C.c_int, [C.POINTER(ViewMetricsDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pny_color_jitter": (C.c_int, [C.POINTER(ColorJitterDesc), C.c_void_p, c_float_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -198,6 +204,7 @@ YOLO_BATCH_MAX_VIEWS, YOLO_BATCH_MAX_SCALES = 16, 4           # PNY_YOLO_BATCH_M
 FINITE_NAN, FINITE_INF, FINITE_MAX_IMMEDIATE = 1, 2, 8        # PNY_FINITE_*
 GT_LAYOUT = {"nhwc01": 0, "nchw_pm1": 1}                      # PNY_GT_NHWC_01, PNY_GT_NCHW_PM1
 GT_FLAT, METRICS_WIN = 2, 7                                   # PNY_GT_FLAT (util.psnr's form); the SSIM window of this build
+IMG_F32_NCHW_PM1, IMG_U8_NHWC, JITTER_MAX_OBJS = 0, 1, 64     # PNY_IMG_*, PNY_JITTER_MAX_OBJS
 
 
 class PnyError(RuntimeError):
