@@ -743,6 +743,75 @@ typedef struct pny_color_jitter_desc {
 int pny_color_jitter(const pny_color_jitter_desc* desc, const void* images_dev, const float* factors_host, float* out_dev,
                      pny_stream stream);
 
+/* ---- ingest: from decoded bytes to the tensors the trainer uses, on the device (csrc/ingest.hip; arithmetic in
+ * csrc/pny_ingest.h).  Replaces what the reference's datasets do per view on CPU tensors between imread and the item: the
+ * resize and normalisation of src/data/YOLODataset.py:79-225 (1920 x 1080 views scaled by image_scale) and the white-background
+ * mask, bounding box, normalisation and area resize of src/data/SRNDataset.py:61-136.  File reading and PNG decoding stay on
+ * the host.  Model-free, raw device pointers, enqueued on `stream`: no workspace, no allocation, no synchronisation, no
+ * atomics; the same input gives the same bits on every run, for a view alone as for the same view inside a batch.
+ * ONE launch; TWO with white_mask (the box is a second launch with one workgroup per view).  All arithmetic is fp32.
+ *
+ * images_dev (n_views, height, width, channels) bytes as decoded, any byte alignment; of a pixel's `channels` bytes the first
+ *            three are used.
+ * out_dev    (n_views, 3, out_height, out_width) fp32 in [-1, 1]: the byte map t = b / 255, out = (t - 0.5) / 0.5, bit-equal to
+ *            ToTensor + Normalize(0.5, 0.5) for all 256 bytes, applied after
+ *   PNY_RESIZE_NONE         nothing;
+ *   PNY_RESIZE_BILINEAR_U8  cv2.resize(INTER_LINEAR) as this project's data.resize_bilinear_u8 restates it: half-pixel centres,
+ *                           src = max(fma(scale, dst + 0.5, -0.5), 0), scale = in / out; i0 = min(floor(src), in - 1),
+ *                           i1 = min(i0 + 1, in - 1), lambda = src - i0; four taps, rounded half to even back to a byte and
+ *                           clamped to 0 .. 255.  Any ratio, enlarging included;
+ *   or before
+ *   PNY_RESIZE_AREA         F.interpolate(mode="area") of the mapped values: window [floor(i in / out), ceil((i + 1) in / out))
+ *                           per axis, an fp32 sum in row-major order, one division by the element count.
+ * white_mask = 1 (SRN): mask_dev (n_views, 1, out_height, out_width) = m after the same resize, m = 1 where none of the pixel's
+ *            three bytes is 255 (`(img != 255).all(axis=-1)`, SRNDataset.py:81), else 0; bbox_dev (n_views, 4) =
+ *            [cmin, rmin, cmax, rmax] of m at decoded resolution, each multiplied by (float)(out_height / (double)height) when
+ *            resizing.  A view with an empty mask gets [width, height, -1, -1], unscaled: the host path raises there, the device
+ *            path does not wait, so the caller tests bbox[:, 2] < 0.
+ * PNY_ERR_ARG, before any launch: a NULL desc, images_dev or out_dev; a non-positive size; channels not 3 or 4; an unknown
+ * resize; out size != size under PNY_RESIZE_NONE; 2^31 or more input or output elements; mask_dev or bbox_dev without
+ * white_mask, or white_mask without both; white_mask with PNY_RESIZE_BILINEAR_U8 (no dataset does that). */
+enum { PNY_RESIZE_NONE = 0, PNY_RESIZE_BILINEAR_U8 = 1, PNY_RESIZE_AREA = 2 };
+typedef struct pny_ingest_desc {
+    int32_t n_views, height, width; /* decoded size */
+    int32_t channels;               /* 3 or 4: byte stride of a pixel; the first three are used */
+    int32_t out_height, out_width;  /* == height, width for PNY_RESIZE_NONE */
+    int32_t resize;                 /* PNY_RESIZE_* */
+    int32_t white_mask;             /* 1: also the white-background mask and box (SRN) */
+} pny_ingest_desc;
+int pny_ingest_views(const pny_ingest_desc* desc, const uint8_t* images_dev /* (NV, H, W, C) */,
+                     float* out_dev /* (NV, 3, OH, OW) in [-1, 1] */, float* mask_dev /* (NV, 1, OH, OW) or NULL */,
+                     float* bbox_dev /* (NV, 4) or NULL */, pny_stream stream);
+
+/* The YOLO target grids of all views in ONE launch: YOLODataset._get_all_bboxes (src/data/YOLODataset.py:156-225) for every
+ * view, complete grids (zero fill included), exactly what the trainer stacks per scale (YoloTrainer.py:97-101) and
+ * pny_yolo_train_batch takes.  One workgroup per view: all threads zero the view's grids, then one thread walks the view's
+ * boxes in file order.
+ * boxes_dev (n_views, max_boxes, 5) fp64 {cx, cy, w, h, cls}, normalised to the image; view v uses its first n_boxes_dev[v]
+ * rows (clamped to 0 .. max_boxes).  anchors_host (n_scales * n_anchors, 2) {w, h}, read before the call returns.
+ * targets_dev: n_scales device pointers (a host array), scale s being (n_views, Hs, Ws, n_anchors, 6) fp32 with
+ * Hs = height / cell_sizes[s], Ws = width / cell_sizes[s] (integer division).
+ * Per box: the IoU of (w, h), rounded to fp32, against every anchor in fp32 (min * min, (w h + aw ah) - inter, a division);
+ * anchors are visited by descending IoU, ties by ascending index; cell i = (int)(Hs cy), j = (int)(Ws cx) in fp64; on each
+ * scale the first visited anchor whose slot (i, j, anchor) is free gets [1, Ws cx - j, Hs cy - i, w Ws, h Hs, (int)cls]
+ * (fp64, rounded once); a free slot visited later on that scale is set to -1 when its IoU > ignore_iou_thresh (fp32).  A box
+ * whose cell lies outside a grid (cx or cy outside [0, 1)) is left out of that grid.
+ * PNY_ERR_ARG, before any launch: a NULL pointer (a grid pointer included), a non-positive n_views, max_boxes, height or width,
+ * n_scales outside 1 .. PNY_YOLO_BATCH_MAX_SCALES, n_anchors outside 1 .. 64 or n_scales * n_anchors above 64, a cell size below
+ * 1 or above the image, a negative or non-finite ignore_iou_thresh, 2^31 or more elements in the boxes or in a grid. */
+#define PNY_YOLO_TARGETS_MAX_ANCHORS 64
+typedef struct pny_yolo_targets_desc {
+    int32_t n_views, max_boxes;     /* rows per view in boxes_dev */
+    int32_t height, width;          /* the resized image the grids refer to */
+    int32_t n_scales;               /* 1 .. PNY_YOLO_BATCH_MAX_SCALES */
+    int32_t cell_sizes[PNY_YOLO_BATCH_MAX_SCALES];
+    int32_t n_anchors;              /* A per scale, 1 .. 64; n_scales * A <= 64 */
+    float ignore_iou_thresh;
+} pny_yolo_targets_desc;
+int pny_yolo_build_targets(const pny_yolo_targets_desc* desc, const double* boxes_dev /* (NV, max_boxes, 5) cx cy w h cls */,
+                           const int32_t* n_boxes_dev /* (NV) */, const float* anchors_host /* (n_scales * A, 2) */,
+                           float* const* targets_dev /* n_scales pointers, (NV, Hs, Ws, A, 6) */, pny_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

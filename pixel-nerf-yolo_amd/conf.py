@@ -80,6 +80,11 @@ def yolo():
     d["model"]["mlp_coarse"].update({"d_out": 7, "num_scales": 1, "num_anchors_per_scale": 3, "yolo": True})
     d["model"]["mlp_fine"] = {"type": "empty"}
     d["model"]["encoder"]["backbone"] = "custom"
+    # the `yolo { ... }` block of the same file, as far as the dataset reads it (data.YOLODataset)
+    d["yolo"] = {"image_scale": [0.5, 0.47407], "cell_sizes": [32],
+                 "anchors": [[[0.02, 0.03], [0.04, 0.07], [0.08, 0.06]], [[0.07, 0.15], [0.15, 0.11], [0.14, 0.29]],
+                             [[0.28, 0.22], [0.38, 0.48], [0.9, 0.78]]],
+                 "ignore_iou_thresh": 0.5}
     return Conf(d)
 
 

@@ -71,8 +71,9 @@ def resize_bilinear_u8(img, fx, fy):
 class SRNDataset(torch.utils.data.Dataset):
     """reference src/data/SRNDataset.py: <path>_<stage>/<object>/{intrinsics.txt, rgb/*, pose/*}."""
 
-    def __init__(self, path, stage="train", image_size=(128, 128), world_scale=1.0):
+    def __init__(self, path, stage="train", image_size=(128, 128), world_scale=1.0, ingest_on_device=False):
         super().__init__()
+        self.ingest_on_device = ingest_on_device
         self.base_path = path + "_" + stage
         self.dataset_name = os.path.basename(path)
         print("Loading SRN dataset", self.base_path, "name:", self.dataset_name)
@@ -105,6 +106,8 @@ class SRNDataset(torch.utils.data.Dataset):
             lines = fh.readlines()
             focal, cx, cy, _ = map(float, lines[0].split())
             height, width = map(int, lines[-1].split())
+        if self.ingest_on_device:
+            return self._item_u8(index, dir_path, rgb_paths, pose_paths, focal, cx, cy)
         all_imgs, all_poses, all_masks, all_bboxes = [], [], [], []
         for rgb_path, pose_path in zip(rgb_paths, pose_paths):
             img = imread(rgb_path)[..., :3]
@@ -142,6 +145,25 @@ class SRNDataset(torch.utils.data.Dataset):
             "poses": all_poses,
         }
 
+    def _item_u8(self, index, dir_path, rgb_paths, pose_paths, focal, cx, cy):
+        """ingest_on_device: the decoded bytes in place of images / masks / bbox, for
+        ``augment.ingest_views(images_u8, size=image_size, resize="area", white_mask=True)``; focal and c already scaled."""
+        imgs = np.stack([imread(p)[..., :3] for p in rgb_paths])
+        poses = torch.stack([torch.from_numpy(np.loadtxt(p, dtype=np.float32).reshape(4, 4)) @ self._coord_trans for p in pose_paths])
+        if tuple(imgs.shape[1:3]) != tuple(self.image_size):
+            scale = self.image_size[0] / imgs.shape[1]
+            focal *= scale
+            cx *= scale
+            cy *= scale
+        if self.world_scale != 1.0:
+            focal *= self.world_scale
+            poses[:, :3, 3] *= self.world_scale
+        return {
+            "path": dir_path, "img_id": index, "focal": torch.tensor(focal, dtype=torch.float32),
+            "c": torch.tensor([cx, cy], dtype=torch.float32), "images_u8": torch.from_numpy(np.ascontiguousarray(imgs)),
+            "image_size": torch.tensor(self.image_size, dtype=torch.int64), "poses": poses,
+        }
+
 
 # ------------------------------------------------------------------ YOLO
 def iou_wh(box_wh, anchors_wh):
@@ -155,8 +177,9 @@ class YOLODataset(torch.utils.data.Dataset):
     """reference src/data/YOLODataset.py: <path>/{train,val,test}.lst of scene directories holding image_XXXX.png,
     extrinsic_XXXX.npy, intrinsic_0000.npy and projected_bboxes_XXXX.txt (cls cx cy w h, normalised)."""
 
-    def __init__(self, path, stage="train", z_near=1.2, z_far=4.0, conf=None):
+    def __init__(self, path, stage="train", z_near=1.2, z_far=4.0, conf=None, ingest_on_device=False):
         super().__init__()
+        self.ingest_on_device = ingest_on_device
         self.base_path = path
         assert os.path.exists(self.base_path)
         with open(os.path.join(self.base_path, {"train": "train.lst", "val": "val.lst", "test": "test.lst"}[stage]), "r") as fh:
@@ -183,8 +206,11 @@ class YOLODataset(torch.utils.data.Dataset):
         n = 0
         while os.path.exists(os.path.join(root_dir, "image_{:04d}.png".format(n))):   # the reference stops at the first failing read
             img = imread(os.path.join(root_dir, "image_{:04d}.png".format(n)))[..., :3]
-            img = resize_bilinear_u8(img, self.image_scale[0], self.image_scale[1])
-            all_imgs.append(self.image_to_tensor(img))
+            if self.ingest_on_device:
+                all_imgs.append(img)
+            else:
+                img = resize_bilinear_u8(img, self.image_scale[0], self.image_scale[1])
+                all_imgs.append(self.image_to_tensor(img))
             n += 1
         for i in range(n):
             pose = np.load(os.path.join(root_dir, "extrinsic_{:04d}.npy".format(i))).copy()
@@ -193,10 +219,20 @@ class YOLODataset(torch.utils.data.Dataset):
         for i in range(n):
             bb = np.roll(np.loadtxt(os.path.join(root_dir, "projected_bboxes_{:04d}.txt".format(i)), delimiter=" ", ndmin=2),
                          4, axis=1).tolist()                                           # -> cx, cy, w, h, cls
-            all_bboxes.append(self._get_all_bboxes(bb, all_imgs[i].shape[1], all_imgs[i].shape[2]))
+            all_bboxes.append(bb if self.ingest_on_device else self._get_all_bboxes(bb, all_imgs[i].shape[1], all_imgs[i].shape[2]))
         intrinsic = np.load(os.path.join(root_dir, "intrinsic_0000.npy"))
         focal = torch.tensor(intrinsic[0, 0] * np.array(self.image_scale), dtype=torch.float32)
         c = torch.tensor(intrinsic[:2, 2] * self.image_scale, dtype=torch.float32)
+        if self.ingest_on_device:
+            # the decoded bytes and the label rows in place of images / bboxes, for ``augment.ingest_views(images_u8,
+            # scale=image_scale)`` and ``util.build_yolo_targets(labels, n_labels, ...)``
+            labels = np.zeros((n, max([len(bb) for bb in all_bboxes] + [1]), 5), np.float64)
+            for i, bb in enumerate(all_bboxes):
+                if len(bb):
+                    labels[i, :len(bb)] = np.asarray(bb, np.float64)
+            return {"path": root_dir, "img_id": index, "focal": focal, "images_u8": torch.from_numpy(np.stack(all_imgs)),
+                    "labels": torch.from_numpy(labels), "n_labels": torch.tensor([len(bb) for bb in all_bboxes], dtype=torch.int32),
+                    "image_scale": torch.tensor(self.image_scale, dtype=torch.float64), "poses": torch.stack(all_poses), "c": c}
         return {"path": root_dir, "img_id": index, "focal": focal, "images": torch.stack(all_imgs), "bboxes": all_bboxes,
                 "poses": torch.stack(all_poses), "c": c}
 
@@ -227,11 +263,22 @@ class YOLODataset(torch.utils.data.Dataset):
         return tuple(targets)
 
 
-def get_split_dataset(dataset_type, datadir, want_split="all", training=True, jitter_on_device=False, **kwargs):
+def get_split_dataset(dataset_type, datadir, want_split="all", training=True, jitter_on_device=False, ingest_on_device=False,
+                      **kwargs):
     """reference src/data/__init__.py:12-76: dataset class + flags per type name; the training split of ``dvr_dtu`` and
     ``yolo`` is wrapped in the colour-jitter augmentation.  ``jitter_on_device=True`` defers that augmentation: the items
-    carry their factors (``ColorJitterDataset(defer=True)``) and the trainer applies them with ``augment.color_jitter``."""
+    carry their factors (``ColorJitterDataset(defer=True)``) and the trainer applies them with ``augment.color_jitter``.
+    ``ingest_on_device=True`` (``srn`` and ``yolo``) makes the items carry the decoded bytes (and, for ``yolo``, the label rows)
+    for ``augment.ingest_views`` / ``util.build_yolo_targets`` instead of resized, normalised tensors and target grids; with
+    ``yolo`` it needs ``jitter_on_device=True`` for the training split, since the host jitter has no images to work on."""
     flags, aug, aug_flags = {}, None, {}
+    if ingest_on_device:
+        if dataset_type.startswith("dvr") or dataset_type == "multi_obj":
+            raise NotImplementedError(
+                "ingest_on_device is not implemented for dataset type %r (%s): its masks come from files and it needs no resize "
+                "kernel; augment.color_jitter already takes its decoded bytes"
+                % (dataset_type, "MultiObjectDataset" if dataset_type == "multi_obj" else "DVRDataset"))
+        flags["ingest_on_device"] = True
     if dataset_type == "srn":
         dset_class = SRNDataset
     elif dataset_type == "multi_obj":
@@ -257,6 +304,9 @@ def get_split_dataset(dataset_type, datadir, want_split="all", training=True, ji
     sets = [dset_class(datadir, stage=st, **flags, **kwargs) if want else None
             for st, want in (("train", want_train), ("val", want_val), ("test", want_test))]
     if sets[0] is not None and aug is not None:
+        if ingest_on_device and not jitter_on_device:
+            raise ValueError("ingest_on_device=True with the training split of %r needs jitter_on_device=True: the items carry "
+                             "bytes, which the host jitter cannot work on" % dataset_type)
         sets[0] = aug(sets[0], defer=jitter_on_device, **aug_flags)
     if want_split in ("train", "val", "test"):
         return sets[("train", "val", "test").index(want_split)]

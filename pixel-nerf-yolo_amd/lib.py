@@ -91,6 +91,16 @@ class ColorJitterDesc(C.Structure):
                 ("in_format", C.c_int32)]
 
 
+class IngestDesc(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("out_height", C.c_int32), ("out_width", C.c_int32), ("resize", C.c_int32), ("white_mask", C.c_int32)]
+
+
+class YoloTargetsDesc(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("max_boxes", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("n_scales", C.c_int32), ("cell_sizes", C.c_int32 * 4), ("n_anchors", C.c_int32), ("ignore_iou_thresh", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/pnyolo.h declares
 SIGNATURES = {
     "pny_version": (C.c_int, []),
@@ -189,6 +199,9 @@ SIGNATURES = {
     "pny_finite_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "pny_view_metrics": (C.c_int, [C.POINTER(ViewMetricsDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pny_color_jitter": (C.c_int, [C.POINTER(ColorJitterDesc), C.c_void_p, c_float_p, C.c_void_p, C.c_void_p]),
+    "pny_ingest_views": (C.c_int, [C.POINTER(IngestDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pny_yolo_build_targets": (C.c_int, [C.POINTER(YoloTargetsDesc), C.c_void_p, C.c_void_p, c_float_p, C.POINTER(C.c_void_p),
+                                         C.c_void_p]),
 }
 
 _lib = None
@@ -205,6 +218,8 @@ FINITE_NAN, FINITE_INF, FINITE_MAX_IMMEDIATE = 1, 2, 8        # PNY_FINITE_*
 GT_LAYOUT = {"nhwc01": 0, "nchw_pm1": 1}                      # PNY_GT_NHWC_01, PNY_GT_NCHW_PM1
 GT_FLAT, METRICS_WIN = 2, 7                                   # PNY_GT_FLAT (util.psnr's form); the SSIM window of this build
 IMG_F32_NCHW_PM1, IMG_U8_NHWC, JITTER_MAX_OBJS = 0, 1, 64     # PNY_IMG_*, PNY_JITTER_MAX_OBJS
+RESIZE = {"none": 0, "bilinear_u8": 1, "area": 2}             # PNY_RESIZE_*
+YOLO_TARGETS_MAX_ANCHORS = 64                                 # PNY_YOLO_TARGETS_MAX_ANCHORS
 
 
 class PnyError(RuntimeError):

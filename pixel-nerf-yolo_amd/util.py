@@ -4,7 +4,7 @@ Ray generation and the YOLO detection tail with the reference's signatures (src/
 device (that of ``poses``, or the current one when ``poses`` is a CPU tensor as at the reference's call sites).
 ``sample_train_batch`` is the trainer's ray batch and ground truth in one launch (no counterpart function in the reference:
 it replaces the per-object loop of train/trainlib/PixelNerfTrainer.py:76-123).  ``yolo_train_batch`` /
-``stage_yolo_targets`` and ``FiniteMonitor`` are the same for the YOLO trainer: the batch of train/trainlib/YoloTrainer.py:93-129
+``stage_yolo_targets`` (``build_yolo_targets``: the grids built on the device from the label rows) and ``FiniteMonitor`` are the same for the YOLO trainer: the batch of train/trainlib/YoloTrainer.py:93-129
 in one launch, and its NaN / Inf tests (:163-194) without a host wait.  ``psnr`` is the reference's util.psnr (:502-509) on
 device tensors (metrics.py).
 """
@@ -176,6 +176,66 @@ def stage_yolo_targets(all_bboxes, device):
         grid = torch.stack([torch.as_tensor(view[s]) for view in all_bboxes]).squeeze(1)
         out.append(grid.to(dev, torch.float32, non_blocking=True).contiguous())
     return out
+
+
+def build_yolo_targets(labels, n_labels, height, width, cell_sizes, anchors, ignore_iou_thresh, device):
+    """
+    The target grids of all views of an item, built on the device in one launch (include/pnyolo.h pny_yolo_build_targets): what
+    ``data.YOLODataset._get_all_bboxes`` computes per view in Python and ``stage_yolo_targets`` stacks and copies.
+
+    :param labels (NV, MAXB, 5) host float64 {cx, cy, w, h, cls}, normalised to the image; n_labels (NV,) rows used per view
+    :param height, width the resized image the grids refer to; cell_sizes one per scale
+    :param anchors (num_scales * A, 2) or (num_scales, A, 2) {w, h}; ignore_iou_thresh as ``yolo.ignore_iou_thresh``
+    :return num_scales-long list of (NV, height // cell, width // cell, A, 6) fp32 device tensors: ``stage_yolo_targets``' result
+    Raises ValueError naming the view and row of a label with cx or cy outside [0, 1) or a non-finite or non-positive w or h
+    (the reference's IndexError); checked on the host, so nothing waits for the device.
+    """
+    import numpy as np
+    who = "pixel_nerf_yolo_amd.util.build_yolo_targets: "
+    dev = torch.device(device)
+    lab = np.ascontiguousarray(np.asarray(labels.numpy() if isinstance(labels, torch.Tensor) else labels, dtype=np.float64))
+    if lab.ndim != 3 or lab.shape[2] != 5 or lab.shape[0] < 1:
+        raise ValueError(who + "labels must be (NV, MAXB, 5) {cx, cy, w, h, cls}, got %s" % (tuple(lab.shape),))
+    nv, maxb = int(lab.shape[0]), int(lab.shape[1])
+    cnt = np.asarray(n_labels.numpy() if isinstance(n_labels, torch.Tensor) else n_labels)
+    if cnt.shape != (nv,) or not np.issubdtype(cnt.dtype, np.integer) or (cnt < 0).any() or (cnt > maxb).any():
+        raise ValueError(who + "n_labels must be (%d,) integers in 0 .. %d, got %s %s" % (nv, maxb, tuple(cnt.shape), cnt.tolist()
+                                                                                         if cnt.size <= 64 else cnt.dtype))
+    cnt = np.ascontiguousarray(cnt.astype(np.int32))
+    cells = [int(v) for v in cell_sizes]
+    anc = np.ascontiguousarray(np.asarray(anchors.numpy() if isinstance(anchors, torch.Tensor) else anchors, dtype=np.float32))
+    if not 1 <= len(cells) <= _lib.YOLO_BATCH_MAX_SCALES:
+        raise ValueError(who + "cell_sizes must hold 1 .. %d scales, got %d" % (_lib.YOLO_BATCH_MAX_SCALES, len(cells)))
+    anc = anc.reshape(-1, 2) if anc.ndim == 3 and anc.shape[0] == len(cells) and anc.shape[2] == 2 else anc
+    if anc.ndim != 2 or anc.shape[1] != 2 or anc.shape[0] == 0 or anc.shape[0] % len(cells) or anc.shape[0] > _lib.YOLO_TARGETS_MAX_ANCHORS:
+        raise ValueError(who + "anchors must be (num_scales * A, 2) with %d scale%s and at most %d rows, got %s"
+                         % (len(cells), "" if len(cells) == 1 else "s", _lib.YOLO_TARGETS_MAX_ANCHORS, tuple(anc.shape)))
+    A = anc.shape[0] // len(cells)
+    used = np.arange(maxb)[None, :] < cnt[:, None]
+    cx, cy, bw, bh = lab[..., 0], lab[..., 1], lab[..., 2], lab[..., 3]
+    with np.errstate(invalid="ignore"):
+        bad = used & ~((cx >= 0) & (cx < 1) & (cy >= 0) & (cy < 1) & np.isfinite(bw) & (bw > 0) & np.isfinite(bh) & (bh > 0)
+                       & np.isfinite(lab[..., 4]))
+    if bad.any():
+        v, r = (int(i) for i in np.argwhere(bad)[0])
+        raise ValueError(who + "labels[%d, %d] = %s (view %d, row %d): cx and cy must lie in [0, 1), w and h be finite and positive"
+                         % (v, r, lab[v, r].tolist(), v, r))
+    if dev.type != "cuda":
+        raise _lib.PnyError(who + "device is %s; the targets are built on an MI355X only (the host path is "
+                            "data.YOLODataset._get_all_bboxes)" % dev)
+    if maxb == 0:                                              # no label in any view: one unused row
+        lab, maxb = np.zeros((nv, 1, 5)), 1
+    boxes = torch.from_numpy(lab).to(dev, non_blocking=True)
+    counts = torch.from_numpy(cnt).to(dev, non_blocking=True)
+    height, width = int(height), int(width)
+    grids = [torch.empty(nv, height // max(c, 1), width // max(c, 1), A, 6, device=dev, dtype=torch.float32) for c in cells]
+    desc = _lib.YoloTargetsDesc(n_views=nv, max_boxes=maxb, height=height, width=width, n_scales=len(cells),
+                                cell_sizes=(C.c_int32 * 4)(*cells), n_anchors=A, ignore_iou_thresh=float(ignore_iou_thresh))
+    with torch.cuda.device(dev):
+        check(_lib.load().pny_yolo_build_targets(C.byref(desc), C.c_void_p(boxes.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                                 anc.ctypes.data_as(_lib.c_float_p),
+                                                 (C.c_void_p * len(grids))(*[g.data_ptr() for g in grids]), stream_of(dev)))
+    return grids
 
 
 def yolo_train_batch(poses, view_ids, focal, c, targets, height, width, cell_sizes, z_near, z_far, device=None):
