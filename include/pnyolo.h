@@ -424,6 +424,50 @@ int pny_trunk_train_forward(pny_model* m, const float* images_dev, int n_images,
                             float* latent_nchw_dev, pny_stream stream);
 int pny_trunk_train_backward(pny_model* m, const float* d_latent_nchw_dev, pny_stream stream);
 
+/* Stage entry points of the trunk (exported for stage-wise tests; nothing in the library calls them).  Each runs ONE stage on
+ * caller-chosen device tensors through the host launcher that the two calls above and the inference encoder use for that stage, needs no model handle, allocates its scratch per call, and -- the convolution, weight-gradient and batch-norm entries --
+ * returns once `stream` has drained.  Activations are channel-last, (n, h, w, c) or (P, C) with P = n h w; weights and weight
+ * gradients are (cout, cin, k, k) as PyTorch keeps them.  A convolution is named by its index in the trunk's table of
+ * convolution + batch-norm units (stem, then per BasicBlock [downsample,] conv1, conv2): pny_trunk_unit gives a unit's
+ * geometry and is PNY_ERR_ARG past the end of the table.  PNY_ERR_ARG, before any launch, with the function's name in
+ * pny_last_error(): a NULL required pointer, a unit or level out of range, C not 64 / 128 / 256, a count below 1, sizes that
+ * are not the unit's.
+ * pny_trunk_conv: out = relu?(conv(in) * scale + shift + resid) per output channel.  transposed = 0: the unit's convolution,
+ * in (n, hin, win, cin rounded up to 4) -> out (n, hout, wout, cout).  transposed = 1: the gradient of its input, in = the
+ * gradient of its output (n, hin, win, cout) -> out (n, hout, wout, cin), (hout, wout) being the forward input's size (a
+ * stride-2 unit maps two input sizes to one output size); scale / shift / resid then have cin channels; not for the stem.
+ * variant (optional): the kernel instantiation launched, 100 SPLIT + 10 NT + MT (csrc/encoder.hip conv_mfma_kernel).
+ * pny_trunk_conv_dw: dw = d loss / d weight from dy (n, hout, wout, cout) and the input x (n, hin, win, cin rounded up to 4);
+ * splits / chunk (optional): the pixel slices the contraction was cut into, slice i = pixels [i chunk, (i + 1) chunk).
+ * pny_trunk_bn_forward: out = relu?((y - mean) invstd gamma + beta + resid) on batch statistics (eps 1e-5), mean / invstd (C)
+ * as the backward takes them; running_mean / running_var (both or neither) are stepped with `momentum` (0: left alone);
+ * use_running != 0 normalises with them instead and leaves them alone.
+ * pny_trunk_bn_backward: d_out -> dy; out = the forward's result as relu mask (out > 0), or NULL for no relu; g_out (the
+ * masked d_out), d_gamma, d_beta optional.
+ * pny_trunk_maxpool(_backward): max_pool2d(3, stride 2, pad 1), (n, hin, win, C) <-> (n, (hin - 1) / 2 + 1, (win - 1) / 2 + 1, C);
+ * the gradient goes to the first maximum in scan order; d_in = result + add (add optional).
+ * pny_trunk_upsample(_backward): pyramid level `level` (0 .. 3; 64, 64, 128, 256 channels at latent offsets 0, 64, 128, 256)
+ * resampled (bilinear, align_corners = True) from (hin, win) to (h0, w0) into its channels of the (n, h0, w0, 512) latent,
+ * whose other channels are left alone; the backward reads those channels of d_latent, d_in = result + add (add optional). */
+int pny_trunk_unit(int unit, int* cin, int* cout, int* k, int* stride, int* pad);
+int pny_trunk_conv(int unit, int transposed, const float* weight_dev, const float* in_dev, int n, int hin, int win, int hout, int wout,
+                   const float* scale_dev, const float* shift_dev, const float* resid_dev, int relu, float* out_dev, int* variant,
+                   pny_stream stream);
+int pny_trunk_conv_dw(int unit, const float* dy_dev, const float* x_dev, int n, int hin, int win, float* dw_dev, int* splits, int64_t* chunk,
+                      pny_stream stream);
+int pny_trunk_bn_forward(const float* y_dev, int64_t P, int C, const float* gamma_dev, const float* beta_dev, const float* resid_dev, int relu,
+                         float* running_mean_dev, float* running_var_dev, float momentum, int use_running, float* out_dev, float* mean_dev,
+                         float* invstd_dev, pny_stream stream);
+int pny_trunk_bn_backward(const float* d_out_dev, const float* out_dev, const float* y_dev, const float* mean_dev, const float* invstd_dev,
+                          const float* gamma_dev, int64_t P, int C, int use_running, float* dy_dev, float* g_out_dev, float* d_gamma_dev,
+                          float* d_beta_dev, pny_stream stream);
+int pny_trunk_maxpool(const float* in_dev, int n, int hin, int win, int C, float* out_dev, pny_stream stream);
+int pny_trunk_maxpool_backward(const float* in_dev, const float* g_dev, const float* add_dev, int n, int hin, int win, int C, float* d_in_dev,
+                               pny_stream stream);
+int pny_trunk_upsample(const float* in_dev, int n, int hin, int win, int level, int h0, int w0, float* latent_dev, pny_stream stream);
+int pny_trunk_upsample_backward(const float* d_latent_dev, const float* add_dev, int n, int hin, int win, int level, int h0, int w0,
+                                float* d_in_dev, pny_stream stream);
+
 /* Introspection for bench.py: GEMM FLOPs (2/MAC, unpadded, MLP only) of the last pny_render /
  * pny_query on this scene -- `flops` as executed by the fused kernel, `flops_reference` as the
  * reference's operation order would execute them (equal when the projection is off) --, the HIP-event

@@ -86,15 +86,20 @@ bool run_pixel_linear(const ConvLayer& L, const float* in, long long npix, float
 
 // One convolution through conv_mfma_kernel (encoder.hip): out = relu?(conv(in) * L.scale + L.shift + resid), channel-last.
 // hout / wout explicit; dil_shift > 0 reads the input as if 2^dil_shift - 1 zeros stood between its samples.
+// variant (optional): the conv_mfma_kernel<SPLIT, NT, MT> instantiation that was launched, as 100 SPLIT + 10 NT + MT.
 bool run_conv_ex(const ConvLayer& L, const float* in, int n, int hin, int win, int hout, int wout, int dil_shift, const float* resid,
-                 int relu, float* out, hipStream_t st);
+                 int relu, float* out, hipStream_t st, int* variant = nullptr);
 // The trunk's other forward kernels (encoder.hip), shared by inference and training:
 // images (n,3,H,W) NCHW -> (n,H,W,4) channel-last with a zero 4th channel
 void launch_image_to_nhwc4(const float* images, float* out, int n, int height, int width, hipStream_t st);
 // max_pool2d(3, stride 2, pad 1) in front of layer1: level 0 of the pyramid -> level 1's size
 void launch_first_pool(const float* l0, float* out, int n, const Pyramid& d, hipStream_t st);
+// ... which is this on level 0: max_pool2d(3, stride 2, pad 1) of a channel-last (n, hin, win, c) tensor
+void launch_maxpool(const float* in, float* out, int n, int hin, int win, int c, hipStream_t st);
 // every pyramid level resampled (bilinear, align_corners=True) to level 0's size into the channel-last latent
 void launch_pyramid_to_latent(const float* const level_out[4], float* latent_nhwc, int n, const Pyramid& d, hipStream_t st);
+// ... one level of it: (n, hin, win, TRUNK_CH[lv]) -> channels [TRUNK_COFF[lv], + TRUNK_CH[lv]) of the (n, h0, w0, 512) latent
+void launch_upsample_level(const float* in, float* latent_nhwc, int n, int hin, int win, int lv, int h0, int w0, hipStream_t st);
 
 size_t encoder_workspace_bytes(int ns, int height, int width, bool use_first_pool);
 // images (ns,3,H,W) NCHW -> latent (ns, H0, W0, 512) channel-last

@@ -664,7 +664,7 @@ static bool run_conv(const ConvLayer& L, const float* in, int n, int hin, int wi
 
 // The general form: explicit output size and an input dilation (transposed convolutions of the trunk's backward).
 bool run_conv_ex(const ConvLayer& L, const float* in, int n, int hin, int win, int hout, int wout, int dil_shift, const float* resid,
-                 int relu, float* out, hipStream_t st) {
+                 int relu, float* out, hipStream_t st, int* variant) {
     ConvArgs a;
     a.in = in;
     a.w = L.w;
@@ -701,15 +701,21 @@ bool run_conv_ex(const ConvLayer& L, const float* in, int n, int hin, int win, i
     const bool split = L.J >= 32 && tiles <= 4 * (long long)cus;
     static LdsLimit lds;
     (void)lds.raise(8 * 4 * 16 * 64 * sizeof(float), conv_mfma_kernel<8, 2, 2>);
+    int launched;   // 100 SPLIT + 10 NT + MT of the instantiation below
     if (split && small) {
         hipLaunchKernelGGL((conv_mfma_kernel<8, 1, 1>), dim3((unsigned)tiles), dim3(512), 8 * 1 * 16 * 64 * sizeof(float), st, a);
+        launched = 811;
     } else if (split) {
         hipLaunchKernelGGL((conv_mfma_kernel<8, 2, 2>), dim3((unsigned)tiles), dim3(512), 8 * 4 * 16 * 64 * sizeof(float), st, a);
+        launched = 822;
     } else if (small) {
         hipLaunchKernelGGL((conv_mfma_kernel<1, 1, 1>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, a);
+        launched = 111;
     } else {
         hipLaunchKernelGGL((conv_mfma_kernel<1, 2, 2>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, a);
+        launched = 122;
     }
+    if (variant) *variant = launched;
     return hipGetLastError() == hipSuccess;
 }
 
@@ -738,18 +744,25 @@ void launch_image_to_nhwc4(const float* images, float* out, int n, int height, i
     hipLaunchKernelGGL(image_to_nhwc4_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, st, images, out, n, height * width);
 }
 
+void launch_maxpool(const float* in, float* out, int n, int hin, int win, int c, hipStream_t st) {
+    const int hout = conv_out(hin, 3, 2, 1), wout = conv_out(win, 3, 2, 1);
+    const long long npool = (long long)n * hout * wout * (c / 4);
+    hipLaunchKernelGGL(maxpool_kernel, dim3((unsigned)((npool + 255) / 256)), dim3(256), 0, st, in, out, n, hin, win, c, hout, wout);
+}
+
 void launch_first_pool(const float* l0, float* out, int n, const Pyramid& d, hipStream_t st) {
-    const long long npool = (long long)n * d.h[1] * d.w[1] * (TRUNK_CH[0] / 4);
-    hipLaunchKernelGGL(maxpool_kernel, dim3((unsigned)((npool + 255) / 256)), dim3(256), 0, st, l0, out, n, d.h[0], d.w[0], TRUNK_CH[0],
-                       d.h[1], d.w[1]);
+    launch_maxpool(l0, out, n, d.h[0], d.w[0], TRUNK_CH[0], st);   // d.h[1], d.w[1] are conv_out(., 3, 2, 1) of level 0 (pyramid())
+}
+
+void launch_upsample_level(const float* in, float* lat, int n, int hin, int win, int lv, int h0, int w0, hipStream_t st) {
+    const long long np = (long long)n * h0 * w0 * (TRUNK_CH[lv] / 4);
+    hipLaunchKernelGGL(upsample_concat_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, in, lat, n, hin, win, TRUNK_CH[lv], h0, w0,
+                       TRUNK_LATENT, TRUNK_COFF[lv]);
 }
 
 void launch_pyramid_to_latent(const float* const level_out[4], float* lat, int n, const Pyramid& d, hipStream_t st) {
-    for (int lv = 0; lv < 4; ++lv) {   // identity for level 0
-        const long long np = (long long)n * d.h[0] * d.w[0] * (TRUNK_CH[lv] / 4);
-        hipLaunchKernelGGL(upsample_concat_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, level_out[lv], lat, n, d.h[lv],
-                           d.w[lv], TRUNK_CH[lv], d.h[0], d.w[0], TRUNK_LATENT, TRUNK_COFF[lv]);
-    }
+    for (int lv = 0; lv < 4; ++lv)   // identity for level 0
+        launch_upsample_level(level_out[lv], lat, n, d.h[lv], d.w[lv], lv, d.h[0], d.w[0], st);
 }
 
 bool encoder_forward(const EncoderWeights& W, const float* images, int ns, int height, int width, bool use_first_pool,

@@ -61,6 +61,7 @@ __global__ __launch_bounds__(256) void trunk_pack_kernel(const TrunkPackJob* __r
 // channel's value at pixel 0 (s1 = sum (y - K), s2 = sum (y - K)^2: var = s2 / P - (s1 / P)^2 without the cancellation of the
 // plain sum of squares).  part[b][0 | 1][C].
 constexpr int BN_THREADS = 256, BN_MAXB = 64;
+constexpr size_t BN_PART_FLOATS = (size_t)BN_MAXB * 2 * 256;   // the partial-sum scratch of a batch-norm launch pair, C <= 256
 
 __global__ __launch_bounds__(BN_THREADS) void bn_stats_kernel(const float* __restrict__ y, long long P, int C, long long chunk,
                                                               float* __restrict__ part) {
@@ -489,6 +490,30 @@ struct TrunkUnit {
 // a packed operand's size in 16-byte elements
 static int pack_count(const ConvLayer& L) { return (L.cout / 32) * L.J * 64; }
 
+// every job of a device-side table in one launch; max_count = the largest job's count
+static void launch_trunk_pack(const TrunkPackJob* jobs_dev, int n_jobs, int max_count, hipStream_t st) {
+    int bx = (max_count + 255) / 256;
+    if (bx > 128) bx = 128;
+    hipLaunchKernelGGL(trunk_pack_kernel, dim3(bx, n_jobs), dim3(256), 0, st, jobs_dev);
+}
+
+// the transposed convolution of a unit's input gradient (conv_pack_src_t images): stride 1 over the (dilated) output gradient
+static ConvLayer transposed_geometry(const TrunkConv& c) {
+    ConvLayer L;
+    L.cin = L.cin_p = c.cout;
+    L.cout = c.cin;
+    L.k = c.k;
+    L.stride = 1;
+    L.pad = c.k - 1 - c.pad;
+    L.J = c.k * c.k * c.cout / 8;
+    return L;
+}
+// a stride-2 convolution's gradient is read as a dilated input
+static int transposed_dil_shift(const ConvLayer& fwd) { return fwd.stride == 2 ? 1 : 0; }
+static TrunkPackJob pack_job(const ConvLayer& fwd, const ConvLayer& L, int kind, const float* src, float* dst) {
+    return {src, dst, kind, fwd.cout, fwd.cin, fwd.cin_p, fwd.k, L.J, pack_count(L)};
+}
+
 struct TrunkTrain {
     DevBuf work, packs, jobs, part, dwpart, ones;
     std::vector<TrunkUnit> units;
@@ -534,7 +559,8 @@ void trunk_release(TrunkTrain* t) {
     delete t;
 }
 
-static void dw_split(const TrunkUnit& u, int n, int* splits, long long* chunk);
+static void dw_split(const ConvLayer& L, long long npix, int* splits, long long* chunk);
+static size_t dw_partial_floats(const ConvLayer& L, long long npix);
 
 static int find_param(pny_model* m, const std::string& name, const float** out) {
     auto it = m->params_dev.find(name);
@@ -589,12 +615,7 @@ static int trunk_plan(pny_model* m, TrunkTrain& T, int n, int height, int width)
         u.conv = "encoder.model." + c.conv;
         u.bn = "encoder.model." + c.bn;
         u.fwd = conv_geometry(c);
-        u.bwd.cin = u.bwd.cin_p = c.cout;
-        u.bwd.cout = c.cin;
-        u.bwd.k = c.k;
-        u.bwd.stride = 1;
-        u.bwd.pad = c.k - 1 - c.pad;
-        u.bwd.J = c.k * c.k * c.cout / 8;
+        u.bwd = transposed_geometry(c);
         u.hin = hin;
         u.win = win;
         u.hout = conv_out(hin, c.k, c.stride, c.pad);
@@ -620,14 +641,11 @@ static int trunk_plan(pny_model* m, TrunkTrain& T, int n, int height, int width)
             u.fwd.shift = u.bwd.shift = T.ones.f() + 256;
         }
     }
-    if ((rc = T.part.reserve((size_t)BN_MAXB * 2 * 256 * sizeof(float)))) return rc;
+    if ((rc = T.part.reserve(BN_PART_FLOATS * sizeof(float)))) return rc;
     {   // the largest weight-gradient partial buffer of any unit (never reallocated while a side-stream launch may read it)
         size_t mx = 0;
         for (const TrunkUnit& u : T.units) {
-            int sp;
-            long long ch_;
-            dw_split(u, n, &sp, &ch_);
-            mx = std::max(mx, (size_t)sp * u.fwd.cout * u.fwd.k * u.fwd.k * u.fwd.cin_p);
+            mx = std::max(mx, dw_partial_floats(u.fwd, (long long)n * u.hout * u.wout));
         }
         if ((rc = T.dwpart.reserve(mx * sizeof(float)))) return rc;
     }
@@ -657,15 +675,8 @@ static int trunk_upload_jobs(pny_model* m, TrunkTrain& T, hipStream_t st) {
     for (TrunkUnit& u : T.units) {
         const float* w = nullptr;
         if ((rc = find_param(m, u.conv + ".weight", &w))) return rc;
-        TrunkPackJob j = {w, u.fwd.w, 0, u.fwd.cout, u.fwd.cin, u.fwd.cin_p, u.fwd.k, u.fwd.J, pack_count(u.fwd)};
-        jobs.push_back(j);
-        if (u.bwd.w) {
-            j.dst = u.bwd.w;
-            j.kind = 1;
-            j.J = u.bwd.J;
-            j.count = pack_count(u.bwd);
-            jobs.push_back(j);
-        }
+        jobs.push_back(pack_job(u.fwd, u.fwd, 0, w, u.fwd.w));
+        if (u.bwd.w) jobs.push_back(pack_job(u.fwd, u.bwd, 1, w, u.bwd.w));
     }
     if ((rc = T.jobs.reserve(jobs.size() * sizeof(TrunkPackJob)))) return rc;
     T.host_jobs = jobs;
@@ -683,25 +694,46 @@ static void bn_grid(long long P, int* B, long long* chunk) {
     *B = (int)((P + *chunk - 1) / *chunk);
 }
 
-static int unit_forward(pny_model* m, TrunkTrain& T, TrunkUnit& u, float momentum, hipStream_t st) {
-    if (!run_conv_ex(u.fwd, u.x, T.n, u.hin, u.win, u.hout, u.wout, 0, nullptr, 0, u.y, st)) return fail(PNY_ERR_HIP, "trunk training: convolution launch failed");
-    const long long P = (long long)T.n * u.hout * u.wout;
+// Batch norm over the P pixels of a channel-last (P, C) tensor, C in {64, 128, 256}: the statistics launch and the apply launch
+static void launch_bn_forward(const float* y, long long P, int C, const float* gamma, const float* beta, const float* resid, int relu,
+                              float* out, float* mean, float* invstd, float* run_mean, float* run_var, float momentum, int use_running,
+                              float* part, hipStream_t st) {
     int B;
     long long chunk;
     bn_grid(P, &B, &chunk);
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(B), dim3(BN_THREADS), 0, st, y, P, C, chunk, part);
+    const long long total = P * (C / 4);
+    long long grid = (total + BN_THREADS - 1) / BN_THREADS;
+    if (grid > 1024) grid = 1024;
+    hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)grid), dim3(BN_THREADS), 0, st, y, part, B, P, C, gamma, beta, resid, relu, out, mean,
+                       invstd, run_mean, run_var, momentum, 1e-5f, use_running);
+}
+
+// ... and its backward: d_out (through the relu mask `mask`, or null) -> dy, optional g_out / d_gamma / d_beta
+static void launch_bn_backward(const float* d_out, const float* mask, const float* y, const float* mean, const float* invstd,
+                               const float* gamma, long long P, int C, float* dy, float* g_out, float* d_gamma, float* d_beta,
+                               int use_running, float* part, hipStream_t st) {
+    int B;
+    long long chunk;
+    bn_grid(P, &B, &chunk);
+    hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(B), dim3(BN_THREADS), 0, st, d_out, mask, y, mean, invstd, P, C, chunk, part);
+    const long long total = P * (C / 4);
+    long long grid = (total + BN_THREADS - 1) / BN_THREADS;
+    if (grid > 1024) grid = 1024;
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)grid), dim3(BN_THREADS), 0, st, d_out, mask, y, mean, invstd, gamma, part, B, P, C, dy,
+                       g_out, d_gamma, d_beta, use_running);
+}
+
+static int unit_forward(pny_model* m, TrunkTrain& T, TrunkUnit& u, float momentum, hipStream_t st) {
+    if (!run_conv_ex(u.fwd, u.x, T.n, u.hin, u.win, u.hout, u.wout, 0, nullptr, 0, u.y, st)) return fail(PNY_ERR_HIP, "trunk training: convolution launch failed");
+    const long long P = (long long)T.n * u.hout * u.wout;
     const float *gamma, *beta, *rm, *rv;
     int rc;
     if ((rc = find_param(m, u.bn + ".weight", &gamma)) || (rc = find_param(m, u.bn + ".bias", &beta)) ||
         (rc = find_param(m, u.bn + ".running_mean", &rm)) || (rc = find_param(m, u.bn + ".running_var", &rv)))
         return rc;
-    const int C = u.fwd.cout;
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(B), dim3(BN_THREADS), 0, st, u.y, P, C, chunk, T.part.f());
-    const long long total = P * (C / 4);
-    long long grid = (total + BN_THREADS - 1) / BN_THREADS;
-    if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)grid), dim3(BN_THREADS), 0, st, u.y, T.part.f(), B, P, C, gamma, beta, u.resid,
-                       u.relu ? 1 : 0, u.out, u.mean, u.invstd, const_cast<float*>(rm), const_cast<float*>(rv), momentum, 1e-5f,
-                       T.bn_eval ? 1 : 0);
+    launch_bn_forward(u.y, P, u.fwd.cout, gamma, beta, u.resid, u.relu ? 1 : 0, u.out, u.mean, u.invstd, const_cast<float*>(rm),
+                      const_cast<float*>(rv), momentum, T.bn_eval ? 1 : 0, T.part.f(), st);
     PNY_HIP(hipGetLastError());
     return 0;
 }
@@ -720,9 +752,7 @@ int trunk_train_forward(pny_model* m, const float* images, int n, int height, in
     {
         int mx = 0;
         for (const TrunkUnit& u : T.units) mx = std::max(mx, std::max(pack_count(u.fwd), u.bwd.w ? pack_count(u.bwd) : 0));
-        int bx = (mx + 255) / 256;
-        if (bx > 128) bx = 128;
-        hipLaunchKernelGGL(trunk_pack_kernel, dim3(bx, T.n_jobs), dim3(256), 0, st, reinterpret_cast<const TrunkPackJob*>(T.jobs.p));
+        launch_trunk_pack(reinterpret_cast<const TrunkPackJob*>(T.jobs.p), T.n_jobs, mx, st);
         PNY_HIP(hipEventRecord(T.ev_pack, st));
     }
     launch_image_to_nhwc4(images, T.img4, n, height, width, st);
@@ -756,16 +786,56 @@ int trunk_train_forward(pny_model* m, const float* images, int n, int height, in
 }
 
 // pixel slices of a unit's weight-gradient GEMM: ~4 waves per CU in all, at least 128 pixels per slice
-static void dw_split(const TrunkUnit& u, int n, int* splits, long long* chunk) {
-    const long long npix = (long long)n * u.hout * u.wout;
-    const int Kp = u.fwd.k * u.fwd.k * u.fwd.cin_p;
-    const long long base = (long long)(u.fwd.cout / 64) * ((Kp + 127) / 128);
+static void dw_split(const ConvLayer& L, long long npix, int* splits, long long* chunk) {
+    const int Kp = L.k * L.k * L.cin_p;
+    const long long base = (long long)(L.cout / 64) * ((Kp + 127) / 128);
     long long sp = (1024 + base - 1) / base;
     const long long max_splits = std::max(1ll, npix / 128);
     if (sp > max_splits) sp = max_splits;
     if (sp < 1) sp = 1;
     *chunk = ((npix + sp - 1) / sp + 3) / 4 * 4;   // the pixel loop walks 4 pixels per iteration
     *splits = (int)((npix + *chunk - 1) / *chunk);
+}
+
+// floats of the partials buffer of a unit's weight gradient over npix output pixels
+static size_t dw_partial_floats(const ConvLayer& L, long long npix) {
+    int sp;
+    long long ch;
+    dw_split(L, npix, &sp, &ch);
+    return (size_t)sp * L.cout * L.k * L.k * L.cin_p;
+}
+
+// dw (cout, cin, k, k) of convolution L from dy (n, hout, wout, cout) and its input x (n, hin, win, cin_p): the split-K GEMM
+// and the reduction of its partials.  False (nothing launched) when `partial` is too small.  Reports the pixel slicing.
+static bool launch_conv_dw(const ConvLayer& L, const float* dy, const float* x, int n, int hin, int win, int hout, int wout, float* partial,
+                           size_t partial_bytes, float* dw, hipStream_t st, int* splits, long long* chunk) {
+    DwcArgs a;
+    a.dy = dy;
+    a.x = x;
+    a.n = n;
+    a.hin = hin;
+    a.win = win;
+    a.cin_p = L.cin_p;
+    a.hout = hout;
+    a.wout = wout;
+    a.cout = L.cout;
+    a.k = L.k;
+    a.stride = L.stride;
+    a.pad = L.pad;
+    a.Kp = L.k * L.k * L.cin_p;
+    a.ntiles = (a.Kp + 127) / 128;
+    a.npix = (long long)n * hout * wout;
+    const long long base = (long long)(L.cout / 64) * a.ntiles;
+    dw_split(L, a.npix, &a.splits, &a.chunk);
+    if (splits) *splits = a.splits;
+    if (chunk) *chunk = a.chunk;
+    if ((size_t)a.splits * L.cout * a.Kp * sizeof(float) > partial_bytes) return false;
+    a.partial = partial;
+    const long long items = base * a.splits;
+    hipLaunchKernelGGL(conv_dw_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, a);
+    const int tot = L.cout * L.cin * L.k * L.k;
+    hipLaunchKernelGGL(conv_dw_reduce_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, partial, a.splits, L.cout, L.cin, L.cin_p, L.k, a.Kp, dw);
+    return true;
 }
 
 static int unit_weight_grad(pny_model* m, TrunkTrain& T, const TrunkUnit& u, const float* dy, hipStream_t main_st) {
@@ -778,32 +848,8 @@ static int unit_weight_grad(pny_model* m, TrunkTrain& T, const TrunkUnit& u, con
         PNY_HIP(hipStreamWaitEvent(T.side, T.ev_ready, 0));
         st = T.side;
     }
-    const ConvLayer& L = u.fwd;
-    DwcArgs a;
-    a.dy = dy;
-    a.x = u.x;
-    a.n = T.n;
-    a.hin = u.hin;
-    a.win = u.win;
-    a.cin_p = L.cin_p;
-    a.hout = u.hout;
-    a.wout = u.wout;
-    a.cout = L.cout;
-    a.k = L.k;
-    a.stride = L.stride;
-    a.pad = L.pad;
-    a.Kp = L.k * L.k * L.cin_p;
-    a.ntiles = (a.Kp + 127) / 128;
-    a.npix = (long long)T.n * u.hout * u.wout;
-    const long long base = (long long)(L.cout / 64) * a.ntiles;
-    dw_split(u, T.n, &a.splits, &a.chunk);
-    if ((size_t)a.splits * L.cout * a.Kp * sizeof(float) > T.dwpart.bytes) return fail(PNY_ERR_STATE, "trunk backward: weight-gradient partials larger than planned");
-    a.partial = T.dwpart.f();
-    const long long items = base * a.splits;
-    hipLaunchKernelGGL(conv_dw_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, a);
-    const int tot = L.cout * L.cin * L.k * L.k;
-    hipLaunchKernelGGL(conv_dw_reduce_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, T.dwpart.f(), a.splits, L.cout, L.cin, L.cin_p, L.k,
-                       a.Kp, dw);
+    if (!launch_conv_dw(u.fwd, dy, u.x, T.n, u.hin, u.win, u.hout, u.wout, T.dwpart.f(), T.dwpart.bytes, dw, st, nullptr, nullptr))
+        return fail(PNY_ERR_STATE, "trunk backward: weight-gradient partials larger than planned");
     PNY_HIP(hipGetLastError());
     if (T.side)
         for (int i = 0; i < TrunkTrain::NSCR; ++i)
@@ -819,26 +865,31 @@ static int unit_weight_grad(pny_model* m, TrunkTrain& T, const TrunkUnit& u, con
 static int unit_backward(pny_model* m, TrunkTrain& T, TrunkUnit& u, const float* d_out, float* dy_buf, float* g_buf, float* dx_buf,
                          const float* dx_add, hipStream_t st) {
     const long long P = (long long)T.n * u.hout * u.wout;
-    const int C = u.fwd.cout;
-    int B;
-    long long chunk;
-    bn_grid(P, &B, &chunk);
     const float* gamma;
     int rc;
     if ((rc = find_param(m, u.bn + ".weight", &gamma))) return rc;
-    const float* mask = u.relu ? u.out : nullptr;
-    hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(B), dim3(BN_THREADS), 0, st, d_out, mask, u.y, u.mean, u.invstd, P, C, chunk, T.part.f());
-    const long long total = P * (C / 4);
-    long long grid = (total + BN_THREADS - 1) / BN_THREADS;
-    if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)grid), dim3(BN_THREADS), 0, st, d_out, mask, u.y, u.mean, u.invstd, gamma, T.part.f(), B,
-                       P, C, dy_buf, g_buf, find_grad(m, u.bn + ".weight"), find_grad(m, u.bn + ".bias"), T.bn_eval ? 1 : 0);
+    launch_bn_backward(d_out, u.relu ? u.out : nullptr, u.y, u.mean, u.invstd, gamma, P, u.fwd.cout, dy_buf, g_buf, find_grad(m, u.bn + ".weight"),
+                       find_grad(m, u.bn + ".bias"), T.bn_eval ? 1 : 0, T.part.f(), st);
     PNY_HIP(hipGetLastError());
     if ((rc = unit_weight_grad(m, T, u, dy_buf, st))) return rc;
-    // a stride-2 convolution's gradient is read as a dilated input
-    if (dx_buf && !run_conv_ex(u.bwd, dy_buf, T.n, u.hout, u.wout, u.hin, u.win, u.fwd.stride == 2 ? 1 : 0, dx_add, 0, dx_buf, st))
+    if (dx_buf && !run_conv_ex(u.bwd, dy_buf, T.n, u.hout, u.wout, u.hin, u.win, transposed_dil_shift(u.fwd), dx_add, 0, dx_buf, st))
         return fail(PNY_ERR_HIP, "trunk training: transposed convolution launch failed");
     return 0;
+}
+
+// gradient of max_pool2d(3, stride 2, pad 1): g (n, hout, wout, c) -> d_in (n, hin, win, c) (+ add, optional)
+static void launch_maxpool_bwd(const float* in, const float* g, const float* add, float* d_in, int n, int hin, int win, int c, hipStream_t st) {
+    const long long np = (long long)n * hin * win * (c / 4);
+    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, in, g, add, d_in, n, hin, win, c,
+                       conv_out(hin, 3, 2, 1), conv_out(win, 3, 2, 1));
+}
+
+// gradient of launch_upsample_level: channels of level lv in d_lat (n, h0, w0, 512) -> d_in (n, hin, win, TRUNK_CH[lv]) (+ add)
+static void launch_upsample_bwd(const float* d_lat, const float* add, float* d_in, int n, int hin, int win, int lv, int h0, int w0,
+                                hipStream_t st) {
+    const long long np = (long long)n * hin * win * (TRUNK_CH[lv] / 4);
+    hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, d_lat, add, d_in, n, hin, win, TRUNK_CH[lv], h0, w0,
+                       TRUNK_LATENT, TRUNK_COFF[lv]);
 }
 
 // d loss / d latent (n, 512, hl, wl) NCHW -> gradients of every bound encoder parameter
@@ -851,11 +902,7 @@ int trunk_train_backward(pny_model* m, const float* d_latent_nchw, hipStream_t s
     float* d_lat = T.lat_nhwc;   // (the forward's channel-last latent is no longer needed)
     const Pyramid& d = T.d;
     launch_nchw_to_nhwc(d_latent_nchw, d_lat, n, TRUNK_LATENT, d.h[0] * d.w[0], st);
-    for (int lv = 0; lv < 4; ++lv) {
-        const long long np = (long long)n * d.h[lv] * d.w[lv] * (TRUNK_CH[lv] / 4);
-        hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, d_lat, (const float*)nullptr, T.d_level[lv], n,
-                           d.h[lv], d.w[lv], TRUNK_CH[lv], d.h[0], d.w[0], TRUNK_LATENT, TRUNK_COFF[lv]);
-    }
+    for (int lv = 0; lv < 4; ++lv) launch_upsample_bwd(d_lat, nullptr, T.d_level[lv], n, d.h[lv], d.w[lv], lv, d.h[0], d.w[0], st);
     // residual layers, last to first.  g_x = gradient w.r.t. the current block's output.  Scratch: a pool of NSCR buffers of
     // the largest activation; at most four are live at any point.
     if (!T.side && !getenv("PNYOLO_TRUNK_NO_SIDE_STREAM")) {
@@ -927,9 +974,7 @@ int trunk_train_backward(pny_model* m, const float* d_latent_nchw, hipStream_t s
     float* d_l0 = grab();
     TrunkUnit& u0 = T.units[0];
     if (T.pool) {
-        const long long np = (long long)n * d.h[0] * d.w[0] * 16;
-        hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, u0.out, g_x, (const float*)T.d_level[0], d_l0, n,
-                           d.h[0], d.w[0], 64, d.h[1], d.w[1]);
+        launch_maxpool_bwd(u0.out, g_x, T.d_level[0], d_l0, n, d.h[0], d.w[0], TRUNK_CH[0], st);   // d.h[1], d.w[1]: conv_out(., 3, 2, 1)
     } else {
         const long long n4 = (long long)n * d.h[0] * d.w[0] * 16;
         hipLaunchKernelGGL(add2_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, g_x, (const float*)T.d_level[0], d_l0, n4);
@@ -964,6 +1009,164 @@ int pny_trunk_train_backward(pny_model* m, const float* d_latent_nchw_dev, pny_s
     if (!m || !d_latent_nchw_dev) return fail(PNY_ERR_ARG, "pny_trunk_train_backward: null argument");
     PNY_HIP(hipSetDevice(m->desc.device));
     return trunk_train_backward(m, d_latent_nchw_dev, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------ stage entry points
+// One trunk stage per call on caller-chosen inputs (tests/test_gpu_trunk_stages.py), through the launchers the trunk itself
+// uses.  No model handle: scratch is allocated per call and the call returns once the stream has drained.
+namespace {
+struct StageScratch {
+    void* p = nullptr;
+    ~StageScratch() {
+        if (p) (void)hipFree(p);
+    }
+};
+bool bn_channels(int C) { return C == 64 || C == 128 || C == 256; }
+bool fits_int(long long a, long long b, long long c) { return a * b <= 0x7fffffffll && a * b * c <= 0x7fffffffll; }
+const TrunkConv* stage_unit(int unit) {
+    const std::vector<TrunkConv>& t = trunk_table();
+    return unit >= 0 && unit < (int)t.size() ? &t[unit] : nullptr;
+}
+}  // namespace
+
+int pny_trunk_unit(int unit, int* cin, int* cout, int* k, int* stride, int* pad) {
+    const TrunkConv* c = stage_unit(unit);
+    if (!c) return fail(PNY_ERR_ARG, "pny_trunk_unit: unit index out of range");
+    if (cin) *cin = c->cin;
+    if (cout) *cout = c->cout;
+    if (k) *k = c->k;
+    if (stride) *stride = c->stride;
+    if (pad) *pad = c->pad;
+    return PNY_OK;
+}
+
+int pny_trunk_conv(int unit, int transposed, const float* weight_dev, const float* in_dev, int n, int hin, int win, int hout, int wout,
+                   const float* scale_dev, const float* shift_dev, const float* resid_dev, int relu, float* out_dev, int* variant,
+                   pny_stream stream) {
+    const TrunkConv* c = stage_unit(unit);
+    if (!c) return fail(PNY_ERR_ARG, "pny_trunk_conv: unit index out of range");
+    if (!weight_dev || !in_dev || !scale_dev || !shift_dev || !out_dev) return fail(PNY_ERR_ARG, "pny_trunk_conv: null argument");
+    if (n < 1 || hin < 1 || win < 1 || hout < 1 || wout < 1 || !fits_int(n, hin, win) || !fits_int(n, hout, wout))
+        return fail(PNY_ERR_ARG, "pny_trunk_conv: bad shape");
+    if (transposed && c->cin < 32) return fail(PNY_ERR_ARG, "pny_trunk_conv: the stem has no transposed form (its input gradient is never computed)");
+    // the convolution's own input and output sizes: (hin, win) -> (hout, wout) forward, the other way round transposed
+    const int fh = transposed ? hout : hin, fw = transposed ? wout : win, oh = transposed ? hin : hout, ow = transposed ? win : wout;
+    if (fh + 2 * c->pad < c->k || fw + 2 * c->pad < c->k || conv_out(fh, c->k, c->stride, c->pad) != oh || conv_out(fw, c->k, c->stride, c->pad) != ow)
+        return fail(PNY_ERR_ARG, "pny_trunk_conv: sizes do not belong to this unit's convolution");
+    hipStream_t st = (hipStream_t)stream;
+    const ConvLayer fwd = conv_geometry(*c);
+    ConvLayer L = transposed ? transposed_geometry(*c) : fwd;
+    StageScratch scr;
+    const size_t job_fl = 64;   // the one-job table in front of the packed operand
+    static_assert(sizeof(TrunkPackJob) <= job_fl * sizeof(float), "job table slot");
+    PNY_HIP(hipMalloc(&scr.p, (job_fl + (size_t)pack_count(L) * 4) * sizeof(float)));
+    L.w = reinterpret_cast<float*>(scr.p) + job_fl;
+    L.scale = const_cast<float*>(scale_dev);
+    L.shift = const_cast<float*>(shift_dev);
+    const TrunkPackJob job = pack_job(fwd, L, transposed ? 1 : 0, weight_dev, L.w);
+    PNY_HIP(hipMemcpy(scr.p, &job, sizeof(job), hipMemcpyHostToDevice));
+    launch_trunk_pack(reinterpret_cast<const TrunkPackJob*>(scr.p), 1, job.count, st);
+    PNY_HIP(hipGetLastError());
+    if (!run_conv_ex(L, in_dev, n, hin, win, hout, wout, transposed ? transposed_dil_shift(fwd) : 0, resid_dev, relu ? 1 : 0, out_dev, st, variant))
+        return fail(PNY_ERR_HIP, "pny_trunk_conv: convolution launch failed");
+    PNY_HIP(hipStreamSynchronize(st));
+    return PNY_OK;
+}
+
+int pny_trunk_conv_dw(int unit, const float* dy_dev, const float* x_dev, int n, int hin, int win, float* dw_dev, int* splits, int64_t* chunk,
+                      pny_stream stream) {
+    const TrunkConv* c = stage_unit(unit);
+    if (!c) return fail(PNY_ERR_ARG, "pny_trunk_conv_dw: unit index out of range");
+    if (!dy_dev || !x_dev || !dw_dev) return fail(PNY_ERR_ARG, "pny_trunk_conv_dw: null argument");
+    if (n < 1 || hin < 1 || win < 1 || !fits_int(n, hin, win) || hin + 2 * c->pad < c->k || win + 2 * c->pad < c->k)
+        return fail(PNY_ERR_ARG, "pny_trunk_conv_dw: bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    const ConvLayer L = conv_geometry(*c);
+    const int hout = conv_out(hin, c->k, c->stride, c->pad), wout = conv_out(win, c->k, c->stride, c->pad);
+    StageScratch scr;
+    const size_t bytes = dw_partial_floats(L, (long long)n * hout * wout) * sizeof(float);
+    PNY_HIP(hipMalloc(&scr.p, bytes));
+    int sp = 0;
+    long long ch = 0;
+    if (!launch_conv_dw(L, dy_dev, x_dev, n, hin, win, hout, wout, reinterpret_cast<float*>(scr.p), bytes, dw_dev, st, &sp, &ch))
+        return fail(PNY_ERR_STATE, "pny_trunk_conv_dw: weight-gradient partials larger than planned");
+    PNY_HIP(hipGetLastError());
+    PNY_HIP(hipStreamSynchronize(st));
+    if (splits) *splits = sp;
+    if (chunk) *chunk = ch;
+    return PNY_OK;
+}
+
+int pny_trunk_bn_forward(const float* y_dev, int64_t P, int C, const float* gamma_dev, const float* beta_dev, const float* resid_dev, int relu,
+                         float* running_mean_dev, float* running_var_dev, float momentum, int use_running, float* out_dev, float* mean_dev,
+                         float* invstd_dev, pny_stream stream) {
+    if (!y_dev || !gamma_dev || !beta_dev || !out_dev || !mean_dev || !invstd_dev) return fail(PNY_ERR_ARG, "pny_trunk_bn_forward: null argument");
+    if (!running_mean_dev != !running_var_dev || (use_running && !running_mean_dev))
+        return fail(PNY_ERR_ARG, "pny_trunk_bn_forward: running_mean and running_var go together, and use_running needs them");
+    if (!bn_channels(C) || P < 1 || P > 0x7fffffffll / C) return fail(PNY_ERR_ARG, "pny_trunk_bn_forward: C must be 64, 128 or 256 and P >= 1");
+    hipStream_t st = (hipStream_t)stream;
+    StageScratch scr;
+    PNY_HIP(hipMalloc(&scr.p, BN_PART_FLOATS * sizeof(float)));
+    launch_bn_forward(y_dev, P, C, gamma_dev, beta_dev, resid_dev, relu ? 1 : 0, out_dev, mean_dev, invstd_dev, running_mean_dev, running_var_dev,
+                      momentum, use_running ? 1 : 0, reinterpret_cast<float*>(scr.p), st);
+    PNY_HIP(hipGetLastError());
+    PNY_HIP(hipStreamSynchronize(st));
+    return PNY_OK;
+}
+
+int pny_trunk_bn_backward(const float* d_out_dev, const float* out_dev, const float* y_dev, const float* mean_dev, const float* invstd_dev,
+                          const float* gamma_dev, int64_t P, int C, int use_running, float* dy_dev, float* g_out_dev, float* d_gamma_dev,
+                          float* d_beta_dev, pny_stream stream) {
+    if (!d_out_dev || !y_dev || !mean_dev || !invstd_dev || !gamma_dev || !dy_dev) return fail(PNY_ERR_ARG, "pny_trunk_bn_backward: null argument");
+    if (!bn_channels(C) || P < 1 || P > 0x7fffffffll / C) return fail(PNY_ERR_ARG, "pny_trunk_bn_backward: C must be 64, 128 or 256 and P >= 1");
+    hipStream_t st = (hipStream_t)stream;
+    StageScratch scr;
+    PNY_HIP(hipMalloc(&scr.p, BN_PART_FLOATS * sizeof(float)));
+    launch_bn_backward(d_out_dev, out_dev, y_dev, mean_dev, invstd_dev, gamma_dev, P, C, dy_dev, g_out_dev, d_gamma_dev, d_beta_dev,
+                       use_running ? 1 : 0, reinterpret_cast<float*>(scr.p), st);
+    PNY_HIP(hipGetLastError());
+    PNY_HIP(hipStreamSynchronize(st));
+    return PNY_OK;
+}
+
+int pny_trunk_maxpool(const float* in_dev, int n, int hin, int win, int C, float* out_dev, pny_stream stream) {
+    if (!in_dev || !out_dev) return fail(PNY_ERR_ARG, "pny_trunk_maxpool: null argument");
+    if (!bn_channels(C) || n < 1 || hin < 1 || win < 1 || !fits_int(n, hin, (long long)win * C))
+        return fail(PNY_ERR_ARG, "pny_trunk_maxpool: C must be 64, 128 or 256 and the sizes >= 1");
+    launch_maxpool(in_dev, out_dev, n, hin, win, C, (hipStream_t)stream);
+    PNY_HIP(hipGetLastError());
+    return PNY_OK;
+}
+
+int pny_trunk_maxpool_backward(const float* in_dev, const float* g_dev, const float* add_dev, int n, int hin, int win, int C, float* d_in_dev,
+                               pny_stream stream) {
+    if (!in_dev || !g_dev || !d_in_dev) return fail(PNY_ERR_ARG, "pny_trunk_maxpool_backward: null argument");
+    if (!bn_channels(C) || n < 1 || hin < 1 || win < 1 || !fits_int(n, hin, (long long)win * C))
+        return fail(PNY_ERR_ARG, "pny_trunk_maxpool_backward: C must be 64, 128 or 256 and the sizes >= 1");
+    launch_maxpool_bwd(in_dev, g_dev, add_dev, d_in_dev, n, hin, win, C, (hipStream_t)stream);
+    PNY_HIP(hipGetLastError());
+    return PNY_OK;
+}
+
+int pny_trunk_upsample(const float* in_dev, int n, int hin, int win, int level, int h0, int w0, float* latent_dev, pny_stream stream) {
+    if (!in_dev || !latent_dev) return fail(PNY_ERR_ARG, "pny_trunk_upsample: null argument");
+    if (level < 0 || level > 3 || n < 1 || hin < 1 || win < 1 || h0 < 1 || w0 < 1 || !fits_int(n, hin, (long long)win * TRUNK_LATENT) ||
+        !fits_int(n, h0, (long long)w0 * TRUNK_LATENT))
+        return fail(PNY_ERR_ARG, "pny_trunk_upsample: level must be 0 .. 3 and the sizes >= 1");
+    launch_upsample_level(in_dev, latent_dev, n, hin, win, level, h0, w0, (hipStream_t)stream);
+    PNY_HIP(hipGetLastError());
+    return PNY_OK;
+}
+
+int pny_trunk_upsample_backward(const float* d_latent_dev, const float* add_dev, int n, int hin, int win, int level, int h0, int w0,
+                                float* d_in_dev, pny_stream stream) {
+    if (!d_latent_dev || !d_in_dev) return fail(PNY_ERR_ARG, "pny_trunk_upsample_backward: null argument");
+    if (level < 0 || level > 3 || n < 1 || hin < 1 || win < 1 || h0 < 1 || w0 < 1 || !fits_int(n, hin, (long long)win * TRUNK_LATENT) ||
+        !fits_int(n, h0, (long long)w0 * TRUNK_LATENT))
+        return fail(PNY_ERR_ARG, "pny_trunk_upsample_backward: level must be 0 .. 3 and the sizes >= 1");
+    launch_upsample_bwd(d_latent_dev, add_dev, d_in_dev, n, hin, win, level, h0, w0, (hipStream_t)stream);
+    PNY_HIP(hipGetLastError());
+    return PNY_OK;
 }
 
 }  // extern "C"
