@@ -856,6 +856,45 @@ int pny_yolo_build_targets(const pny_yolo_targets_desc* desc, const double* boxe
                            const int32_t* n_boxes_dev /* (NV) */, const float* anchors_host /* (n_scales * A, 2) */,
                            float* const* targets_dev /* n_scales pointers, (NV, Hs, Ws, A, 6) */, pny_stream stream);
 
+/* ---- mesh extraction: the sigma grid and marching cubes of the reference's src/util/recon.py on the device (csrc/recon.hip;
+ * conventions and arithmetic in csrc/pny_recon.h, the case table in csrc/mc_table.h, generated by tools/gen_mc_table.py).
+ * Model-free, raw device pointers, enqueued on `stream`: no allocation, no copy, no synchronisation, no atomics; the same
+ * input gives the same bits on every run.  Arrays named *_host are read before the call returns.
+ *
+ * pny_grid_points: ONE launch writes the flat indices [i0, i1) of the grid of util.gen_grid(*zip(c1, c2, reso),
+ * ij_indexing=True) (x slowest, z fastest) to xyz_dev (i1 - i0, 3), and to dirs_dev (i1 - i0, 3) the fake view directions of
+ * recon.py:54.  A coordinate is np.linspace(lo, hi, sz, dtype=float32): lo + i * ((hi - lo) / (sz - 1)) in double, the last
+ * point exactly hi, rounded to fp32 (bit-equal to numpy's).  A direction is -p / |p| in fp32 from the rounded coordinates,
+ * |p| = sqrt((x x + y y) + z z); a grid point exactly at the origin gets (0, 0, 0), where the reference's 0 / 0 gives NaN.
+ * PNY_ERR_ARG, before any launch: a NULL pointer, a reso below 2, non-finite bounds, c2 <= c1 on an axis, 3 X Y Z >= 2^31,
+ * i0 < 0, i1 > X Y Z or i0 >= i1. */
+int pny_grid_points(const double* c1_host /* 3 */, const double* c2_host /* 3 */, const int32_t* reso_host /* 3: X Y Z */,
+                    int64_t i0, int64_t i1, float* xyz_dev /* (i1 - i0, 3) */, float* dirs_dev /* (i1 - i0, 3) */,
+                    pny_stream stream);
+
+/* Marching cubes over sigma_dev, a (X, Y, Z) fp32 volume (dims_host = {X, Y, Z}), giving an indexed mesh in index coordinates:
+ *   corner c of a cell sits at offset (c & 1, (c >> 1) & 1, (c >> 2) & 1) and is inside when sigma > iso, strictly (a NaN is
+ *   outside); a grid edge whose ends differ is cut, and the grid point at its lower end owns the vertex: with a the owner's
+ *   sigma and b the neighbour's, t = (iso - a) / (b - a), coordinate (float)i + t along the edge, both fp32;
+ *   vertices in ascending owner flat index, then axis x, y, z; triangles in ascending cell flat index (the cell's low corner),
+ *   then table order; int32 indices; by the right-hand rule the normals point from sigma > iso to sigma < iso.
+ * Every cut edge has exactly one vertex (the mesh is welded).  A sigma equal to iso gives zero-area triangles, which are kept.
+ * pny_mc_workspace_bytes: the workspace pny_mc_count fills and pny_mc_emit reads, 8 bytes per grid point and 8 per 1024.
+ * pny_mc_count: the per-point counts and their exclusive scan (2 launches up to 1024 * 1024 points, 4 above), and
+ *   counts_dev = int32[2] {vertices, triangles}.  Reading them is the one host read between the two calls.  (More than 2^31 - 1
+ *   triangles, which needs over 429 million grid points, read back negative and pny_mc_emit refuses them.)
+ * pny_mc_emit: with the same sigma_dev, dims_host, iso and workspace, writes vertices_dev (n_vertices, 3) fp32 and
+ *   triangles_dev (n_triangles, 3) int32, one launch each; a count of 0 launches nothing for that half (its pointer may be
+ *   NULL).  Nothing is written past the counts given.
+ * PNY_ERR_ARG, before any launch: a NULL pointer, a dimension below 2, 3 X Y Z >= 2^31, a non-finite iso; for pny_mc_emit a
+ * negative count or one above what the volume can have. */
+int pny_mc_workspace_bytes(const int32_t* dims_host /* 3: X Y Z */, int64_t* bytes);
+int pny_mc_count(const float* sigma_dev /* (X, Y, Z) */, const int32_t* dims_host, float iso, void* workspace_dev,
+                 int32_t* counts_dev /* int32[2]: vertices, triangles */, pny_stream stream);
+int pny_mc_emit(const float* sigma_dev, const int32_t* dims_host, float iso, const void* workspace_dev, int64_t n_vertices,
+                int64_t n_triangles, float* vertices_dev /* (V, 3) index coordinates */, int32_t* triangles_dev /* (T, 3) */,
+                pny_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

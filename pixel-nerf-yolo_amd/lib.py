@@ -214,6 +214,12 @@ SIGNATURES = {
     "pny_ingest_views": (C.c_int, [C.POINTER(IngestDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pny_yolo_build_targets": (C.c_int, [C.POINTER(YoloTargetsDesc), C.c_void_p, C.c_void_p, c_float_p, C.POINTER(C.c_void_p),
                                          C.c_void_p]),
+    "pny_grid_points": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int64, C.c_int64, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    "pny_mc_workspace_bytes": (C.c_int, [C.POINTER(C.c_int32), c_i64_p]),
+    "pny_mc_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pny_mc_emit": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_float, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                              C.c_void_p]),
 }
 
 _lib = None
@@ -232,6 +238,7 @@ GT_FLAT, METRICS_WIN = 2, 7                                   # PNY_GT_FLAT (uti
 IMG_F32_NCHW_PM1, IMG_U8_NHWC, JITTER_MAX_OBJS = 0, 1, 64     # PNY_IMG_*, PNY_JITTER_MAX_OBJS
 RESIZE = {"none": 0, "bilinear_u8": 1, "area": 2}             # PNY_RESIZE_*
 YOLO_TARGETS_MAX_ANCHORS = 64                                 # PNY_YOLO_TARGETS_MAX_ANCHORS
+MC_SCAN_TILE, MC_MAX_POINTS = 1024, (2 ** 31 - 1) // 3        # csrc/pny_recon.h: points per scan tile; 3 X Y Z < 2^31
 
 
 class PnyError(RuntimeError):
