@@ -330,13 +330,32 @@ int pny_scene_set_projection(pny_scene* s, int mode);
 /* Compute the projected maps now (coarse, and fine when the model has one) instead of lazily inside
  * the first large launch; a no-op when they are current.  Error when the mode is OFF. */
 int pny_scene_project(pny_scene* s, pny_stream stream);
+/* Read-out of the projection (exported for stage-wise tests; nothing in the library calls it).  Projects the scene's latent
+ * with the coarse (fine = 0) or fine (fine != 0; the coarse one on a model without a fine MLP) MLP's stacked lin_z weights
+ * into out_dev, (ns * hl * wl, view blocks * 512) row-major: out[p][512 b + n] = sum_k lin_z[b].weight[n][k] latent[v][k][y][x],
+ * p = (v * hl + y) * wl + x, no bias.  It runs the function the cached maps are computed by, in the arithmetic they would
+ * have on this scene now (pny_scene_set_precision), but neither reads nor fills nor invalidates the cache, whatever the
+ * projection mode.  route (optional): the kernel that ran, PNY_PROJECTION_ROUTE_TILED_F32 / _TILED_F16X2 for the tiled GEMM
+ * (maps of at least 256 pixels), else the 1x1-convolution path's instantiation, 100 SPLIT + 10 NT + MT as pny_trunk_conv
+ * reports it (>= 111).  PNY_ERR_ARG: out_floats below the size above, a model without per-view blocks; PNY_ERR_STATE: no
+ * finalized weights, no latent.  Asynchronous on `stream`. */
+#define PNY_PROJECTION_ROUTE_TILED_F32 1
+#define PNY_PROJECTION_ROUTE_TILED_F16X2 2
+int pny_scene_projection(pny_scene* s, int fine, float* out_dev, int64_t out_floats, int* route, pny_stream stream);
 
 /* Matrix arithmetic of PROJECTED launches.  F32: v_mfma_f32_32x32x2_f32 on fp32 operands.  F16X2: every fp32 operand
  * is split into two f16 planes, x = f16(x) + f16(x - f16(x)) (22 significant bits; the second plane may be denormal,
  * which the matrix cores honour), and a product is x1 w1 + x2 w1 + x1 w2 on v_mfma_f32_32x32x16_f16 with fp32
  * accumulation: the same measured error against fp64 as the fp32 matrix path (tools/ubench/split_f16_check.hip,
  * 1.7e-6 vs 1.8e-6 at K = 512 on the network's magnitudes) at 5.3x its matrix rate; held to the same 1e-4 bar by the
- * same golden vectors.  Values beyond the f16 range (|x| > 65504 in an activation or weight) are NOT representable: use
+ * same golden vectors.  The 22 bits hold for operands of ordinary magnitude only: an f16 denormal has the fixed spacing 2^-24, so the
+ * second plane of a value below 2^-14 * 2^11 = 0.125 already keeps fewer than its 11 bits, and what two planes leave behind is up to
+ * 2^-25 ABSOLUTE whatever the value.  Measured on the latent projection (K = 128 .. 1792, error over the map's max against
+ * fp64, tests/projection_ref.py): with both operands -- latent and lin_z weights -- of standard deviation 0.05 or
+ * more (up to 1e3, the largest tried) the split product stays within 2 x the error of an fp32 matmul (it is within 1.5 x); it
+ * leaves that band between 0.02 (K = 128) and 0.005 (K = 1792), and below it the error is 1.7e-8 / s of the map's max for an
+ * operand of standard deviation s: 1.7e-5 at 1e-3, 1.6e-4 at 1e-4, where fp32 stays at 5e-7 .. 2e-6.  A flush of f16 denormals
+ * would cost 2e-4 .. 3e-4 at every magnitude; tests/test_gpu_projection.py holds the kernels a factor 50 or more below that.  Values beyond the f16 range (|x| > 65504 in an activation or weight) are NOT representable: use
  * F32 for such models (AUTO does so by itself when a WEIGHT loaded at pny_model_finalize is outside the range; weights changed
  * through pny_model_refresh and activations are not checked).  AUTO (default; env PNYOLO_MLP_PRECISION=f32|f16x2|f16 overrides at scene creation) otherwise
  * equals F16X2: every projected launch, whatever its size, so that a ray's result does not depend on the batch it is rendered

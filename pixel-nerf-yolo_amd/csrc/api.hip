@@ -1016,6 +1016,18 @@ static MlpRoute route_mlp(const pny_scene* s, long long n_points, bool stash) {
 // has at least twice as many points as the latent has pixels per view (the projection costs one lin_z per PIXEL instead of
 // one per (sample, view); tiny training-size batches on large maps stay direct).
 namespace pny {
+// The projection itself, for the cache below and for the read-out (pny_scene_projection): MLP `which`'s stacked lin_z applied
+// to every pixel of the scene's latent, into out (ns hl wl, view blocks x 512).  Scenes whose projected launches run the f16x2
+// kernel project on the split-f16 matrix path too.  route: see run_pixel_linear.
+static int project_latent(const pny_scene* s, int which, float* out, hipStream_t st, int* route) {
+    const pny_model* m = s->m;
+    if (!m->desc.has_fine) which = 0;
+    const long long npix = (long long)s->ns * s->hl * s->wl;
+    if (!run_pixel_linear(m->zproj[which], s->latent.f(), npix, out, st, f16_default(s), route))
+        return fail(PNY_ERR_HIP, "latent projection launch failed");
+    return 0;
+}
+
 int ensure_projection(pny_scene* s, int which, long long n_points, hipStream_t st, const float** zp, bool force) {
     *zp = nullptr;
     const pny_model* m = s->m;
@@ -1030,9 +1042,7 @@ int ensure_projection(pny_scene* s, int which, long long n_points, hipStream_t s
         const long long npix = (long long)s->ns * s->hl * s->wl;
         int rc;
         if ((rc = s->zp[which].reserve((size_t)npix * nvb * HID * sizeof(float)))) return rc;
-        // scenes whose projected launches run the f16x2 kernel project on the split-f16 matrix path too
-        if (!run_pixel_linear(m->zproj[which], s->latent.f(), npix, s->zp[which].f(), st, f16_default(s)))
-            return fail(PNY_ERR_HIP, "latent projection launch failed");
+        if ((rc = project_latent(s, which, s->zp[which].f(), st, nullptr))) return rc;
         s->zp_valid[which] = true;
     }
     *zp = s->zp[which].f();
@@ -1367,6 +1377,25 @@ int pny_scene_project(pny_scene* s, pny_stream stream) {
     s->zp_mode = keep;
     if (rc) return rc;
     PNY_HIP(hipGetLastError());
+    return PNY_OK;
+}
+
+int pny_scene_projection(pny_scene* s, int fine, float* out_dev, int64_t out_floats, int* route, pny_stream stream) {
+    if (!s || !out_dev) return fail(PNY_ERR_ARG, "pny_scene_projection: null argument");
+    const pny_model* m = s->m;
+    if (!m->finalized) return fail(PNY_ERR_STATE, "pny_scene_projection: weights not finalized (pny_model_finalize)");
+    if (!m->has_zproj) return fail(PNY_ERR_ARG, "pny_scene_projection: the model has no per-view blocks, nothing is projected");
+    if (!s->have_latent) return fail(PNY_ERR_STATE, "pny_scene_projection: scene has no latent (pny_scene_encode / pny_scene_set_latent)");
+    const long long need = (long long)s->ns * s->hl * s->wl * view_blocks(m->desc) * HID;
+    if (out_floats < need)
+        return fail(PNY_ERR_ARG, "pny_scene_projection: out_dev holds " + std::to_string((long long)out_floats) + " floats, the maps need " +
+                                     std::to_string(need));
+    PNY_HIP(hipSetDevice(m->desc.device));
+    int rc;
+    if ((rc = enter_stream(s, (hipStream_t)stream))) return rc;
+    int launched = 0;
+    if ((rc = project_latent(s, fine ? 1 : 0, out_dev, (hipStream_t)stream, &launched))) return rc;
+    if (route) *route = launched;
     return PNY_OK;
 }
 

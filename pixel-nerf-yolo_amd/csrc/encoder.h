@@ -82,7 +82,11 @@ struct EncoderWeights {
 // stacked along n; rows*nmat must be a multiple of 64, k of 8.  Allocates the layer; the caller fills `w` (pack.hip PACK_NT).
 bool build_pixel_linear(int nmat, int rows, int k, ConvLayer* out, std::vector<float*>* allocs, std::string* err);
 // f16x2: split-f16 matrix products (pixel_linear_h2_kernel) instead of the fp32 MFMA
-bool run_pixel_linear(const ConvLayer& L, const float* in, long long npix, float* out, hipStream_t st, bool f16x2 = false);
+// route (optional): the kernel that was launched -- PL_ROUTE_TILED_F32 / PL_ROUTE_TILED_H2 for the tiled GEMM, else the
+// 1x1-convolution path's conv_mfma_kernel instantiation as run_conv_ex reports it (100 SPLIT + 10 NT + MT, >= 111).
+constexpr int PL_ROUTE_TILED_F32 = 1, PL_ROUTE_TILED_H2 = 2;
+bool run_pixel_linear(const ConvLayer& L, const float* in, long long npix, float* out, hipStream_t st, bool f16x2 = false,
+                      int* route = nullptr);
 
 // One convolution through conv_mfma_kernel (encoder.hip): out = relu?(conv(in) * L.scale + L.shift + resid), channel-last.
 // hout / wout explicit; dil_shift > 0 reads the input as if 2^dil_shift - 1 zeros stood between its samples.

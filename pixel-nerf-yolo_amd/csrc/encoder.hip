@@ -719,7 +719,7 @@ bool run_conv_ex(const ConvLayer& L, const float* in, int n, int hin, int win, i
     return hipGetLastError() == hipSuccess;
 }
 
-bool run_pixel_linear(const ConvLayer& L, const float* in, long long npix, float* out, hipStream_t st, bool f16x2) {
+bool run_pixel_linear(const ConvLayer& L, const float* in, long long npix, float* out, hipStream_t st, bool f16x2, int* route) {
     if (npix <= 0 || npix > 0x7fffffffll) return false;
     // the tiled GEMM wants K in 32-channel chunks and 256-output blocks (the latent projection: K = 512 | 1792,
     // cout = 512 * view blocks when that is a multiple of 256) and enough pixels to fill tiles; otherwise the generic
@@ -733,10 +733,11 @@ bool run_pixel_linear(const ConvLayer& L, const float* in, long long npix, float
             else
                 hipLaunchKernelGGL(pixel_linear_kernel, dim3((unsigned)blocks), dim3(64 * PL_NW), 0, st, in, L.w, out, npix,
                                    L.cin_p, L.cout);
+            if (route) *route = f16x2 ? PL_ROUTE_TILED_H2 : PL_ROUTE_TILED_F32;
             return hipGetLastError() == hipSuccess;
         }
     }
-    return run_conv(L, in, 1, 1, (int)npix, nullptr, 0, out, st);
+    return run_conv_ex(L, in, 1, 1, (int)npix, 1, (int)npix, 0, nullptr, 0, out, st, route);
 }
 
 void launch_image_to_nhwc4(const float* images, float* out, int n, int height, int width, hipStream_t st) {

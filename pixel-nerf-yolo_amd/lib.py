@@ -172,6 +172,7 @@ SIGNATURES = {
     "pny_trunk_upsample": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p]),
     "pny_trunk_upsample_backward": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p]),
     "pny_scene_project": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pny_scene_projection": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int), C.c_void_p]),
     "pny_scene_last_mlp_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                            C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pny_scene_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),
@@ -228,6 +229,7 @@ PROJECTION = {"off": 0, "on": 1, "auto": 2}
 # f16: opt-in single-plane mode for no-grad launches, f16_train: the same for training too; both outside the 1e-4 parity bar
 PRECISION = {"f32": 0, "f16x2": 1, "auto": 2, "f16": 3, "f16_train": 5}
 LAST_PRECISION = {0: "f32", 1: "f16x2", 2: "f16"}   # pny_scene_last_precision, pny_scene_last_backward_precision
+PROJECTION_ROUTE_TILED = {1: "f32", 2: "f16x2"}     # pny_scene_projection: PNY_PROJECTION_ROUTE_TILED_*; >= 111: the 1x1 convolution
 
 
 RANGE_BITS = {1: "activation", 2: "gradient", 4: "weight"}   # include/pnyolo.h PNY_RANGE_*
