@@ -122,6 +122,32 @@ int pny_scene_set_groups(pny_scene* s, int n_objs);
  * it in self.latent (src/model/encoder.py:169-172); repacked to NHWC on device. */
 int pny_scene_set_latent(pny_scene* s, const float* latent_dev, int ns, int channels, int hl, int wl,
                          pny_stream stream);
+/* The latent of a backbone that hands back a LIST of feature maps (SpatialEncoder.forward with backbone = "custom",
+ * src/model/encoder.py:126-137: every map resized to the first map's size by F.interpolate(bilinear, align_corners = True),
+ * then torch.cat along the channels).  Level i is fp32 NCHW (n, channels[i], h[i], w[i]) on the device; maps_dev, channels, h
+ * and w are HOST arrays of n_levels entries (1 .. PNY_MAX_LATENT_LEVELS).  A level may be smaller than level 0, of its size
+ * (then copied bit for bit) or larger; a channel count is any positive number (levels whose count and channel offset are
+ * multiples of 4 move as 16-byte words).  Resampling restates ATen's upsample_bilinear2d in float32: scale = (h_i - 1) /
+ * (h_0 - 1), 0 when h_0 == 1; src = scale * dst; i0 = (int)src; i1 = i0 + (i0 < h_i - 1); l1 = src - i0; l0 = 1 - l1;
+ * l0y (l0x v00 + l1x v01) + l1y (l0x v10 + l1x v11).
+ * pny_latent_levels: ONE launch writes the channel-last latent (n, h[0], w[0], sum channels), level i at channel offset
+ *   channels[0] + .. + channels[i - 1], into the caller's buffer; every element is written.  Needs no model.
+ * pny_latent_levels_backward: the adjoint, ONE launch: d_latent (n, h[0], w[0], sum channels) channel-last -> per level its
+ *   NCHW gradient (n, channels[i], h[i], w[i]), WRITTEN (not added); a NULL entry of d_maps_dev skips that level.  A gather in a
+ *   fixed order of summation, no atomics: the same bits on every run.
+ * pny_scene_set_latent_levels: assembles straight into the scene's latent (ns = n views) and leaves the scene as
+ *   pny_scene_set_latent does -- same checks (sum channels == d_latent, ns <= 16, Hl Wl L < 2^31), projected maps marked stale --
+ *   without an NCHW copy of the latent and without a transpose.
+ * None allocates (the scene entry: the scene's latent, as pny_scene_set_latent), copies or waits.  PNY_ERR_ARG, before any
+ * launch, with the function's name in pny_last_error(): a NULL pointer (a map included), n_levels outside 1 .. 8, a size, a
+ * channel count or n below 1, a level of 2^31 pixels or more. */
+#define PNY_MAX_LATENT_LEVELS 8
+int pny_latent_levels(const float* const* maps_dev, const int* channels, const int* h, const int* w, int n_levels, int n,
+                      float* latent_nhwc_dev, pny_stream stream);
+int pny_latent_levels_backward(const float* d_latent_nhwc_dev, float* const* d_maps_dev /* entries may be NULL */, const int* channels,
+                               const int* h, const int* w, int n_levels, int n, pny_stream stream);
+int pny_scene_set_latent_levels(pny_scene* s, const float* const* maps_dev, const int* channels, const int* h, const int* w,
+                                int n_levels, int ns, pny_stream stream);
 /* SpatialEncoder.forward, ResNet-34 trunk, eval-mode batch norm (src/model/encoder.py:139-173).
  * images_dev (ns,3,H,W) in [-1,1].  Leaves the 512-channel latent (H/2 x W/2) in the scene. */
 int pny_scene_encode(pny_scene* s, const float* images_dev, int ns, int height, int width, pny_stream stream);

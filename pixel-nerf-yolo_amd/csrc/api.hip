@@ -652,6 +652,24 @@ int pny_scene_set_latent(pny_scene* s, const float* latent_dev, int ns, int chan
     return PNY_OK;
 }
 
+int pny_scene_set_latent_levels(pny_scene* s, const float* const* maps_dev, const int* channels, const int* h, const int* w, int n_levels,
+                                int ns, pny_stream stream) {
+    const char* who = "pny_scene_set_latent_levels";
+    if (!s) return fail(PNY_ERR_ARG, std::string(who) + ": null argument");
+    long long L = 0;
+    int rc;
+    if ((rc = latent_levels_check(who, maps_dev, channels, h, w, n_levels, ns, &L))) return rc;
+    if (L != s->m->desc.d_latent) return fail(PNY_ERR_ARG, std::string(who) + ": channel count != model d_latent");
+    if (ns > MAX_VIEWS) return fail(PNY_ERR_ARG, std::string(who) + ": bad shape");
+    if ((long long)h[0] * w[0] * L >= (1ll << 31)) return fail(PNY_ERR_ARG, std::string(who) + ": latent too large for 32-bit tap offsets");
+    PNY_HIP(hipSetDevice(s->m->desc.device));
+    if ((rc = enter_stream(s, (hipStream_t)stream))) return rc;
+    if ((rc = s->latent.reserve((size_t)ns * L * h[0] * w[0] * sizeof(float)))) return rc;
+    if ((rc = latent_levels_assemble(who, maps_dev, channels, h, w, n_levels, ns, s->latent.f(), (hipStream_t)stream))) return rc;
+    set_latent_shape(s, ns, (int)L, h[0], w[0]);
+    return PNY_OK;
+}
+
 int pny_scene_encode(pny_scene* s, const float* images_dev, int ns, int height, int width, pny_stream stream) {
     if (!s || !images_dev) return fail(PNY_ERR_ARG, "pny_scene_encode: null argument");
     int hl = 0, wl = 0, rc;

@@ -305,4 +305,10 @@ int ensure_projection(pny_scene* s, int which, long long n_points, hipStream_t s
 // MlpArgs of a launch on this scene in the reference's operation order (no projected latent); tiles of 64 samples
 int fill_mlp_args(pny_scene* s, int mode, const float* xyz, const float* dirs, const float* rays, const float* z, int K,
                   long long n_points, int coarse, float* out, MlpArgs* a);
+// latent of a list of feature maps (latent_levels.hip): the shape checks of the pny_latent_levels* entries (`who` names the
+// caller in the message), then the one launch that assembles the maps into a channel-last latent
+int latent_levels_check(const char* who, const float* const* maps, const int* channels, const int* h, const int* w, int n_levels, int n,
+                        long long* total_channels);
+int latent_levels_assemble(const char* who, const float* const* maps, const int* channels, const int* h, const int* w, int n_levels, int n,
+                           float* latent_nhwc, hipStream_t st);
 }  // namespace pny

@@ -16,6 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 
 c_float_p = C.POINTER(C.c_float)
 c_i64_p = C.POINTER(C.c_int64)
+c_int_p = C.POINTER(C.c_int)
 
 
 class ModelDesc(C.Structure):
@@ -118,6 +119,10 @@ SIGNATURES = {
     "pny_scene_set_cameras": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                         C.c_int, C.c_int]),
     "pny_scene_set_latent": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "pny_latent_levels": (C.c_int, [C.POINTER(C.c_void_p), c_int_p, c_int_p, c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pny_latent_levels_backward": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_int_p, c_int_p, c_int_p, C.c_int, C.c_int, C.c_void_p]),
+    "pny_scene_set_latent_levels": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_int_p, c_int_p, c_int_p, C.c_int, C.c_int,
+                                              C.c_void_p]),
     "pny_scene_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pny_scenes_encode": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pny_scene_get_latent": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -241,6 +246,7 @@ IMG_F32_NCHW_PM1, IMG_U8_NHWC, JITTER_MAX_OBJS = 0, 1, 64     # PNY_IMG_*, PNY_J
 RESIZE = {"none": 0, "bilinear_u8": 1, "area": 2}             # PNY_RESIZE_*
 YOLO_TARGETS_MAX_ANCHORS = 64                                 # PNY_YOLO_TARGETS_MAX_ANCHORS
 MC_SCAN_TILE, MC_MAX_POINTS = 1024, (2 ** 31 - 1) // 3        # csrc/pny_recon.h: points per scan tile; 3 X Y Z < 2^31
+MAX_LATENT_LEVELS = 8                                         # PNY_MAX_LATENT_LEVELS
 
 
 class PnyError(RuntimeError):

@@ -651,6 +651,15 @@ class PixelNeRFNet(nn.Module):
             return getattr(self, "_latent_src", None)
         return None
 
+    def latent_meta(self, lat):
+        """What a render / query backward needs of the differentiable latent `lat`: ((SB * NS, L, Hl, Wl), device, dtype,
+        channel-last).  A tensor latent is NCHW and takes its gradient in that layout; the stand-in of a list of feature maps
+        (_LevelsFunction) is shaped like the library's own (SB * NS, Hl, Wl, L) buffer and takes that buffer as it is."""
+        if getattr(self, "_latent_channel_last", False):
+            n, hl, wl, l_ch = lat.shape
+            return (n, l_ch, hl, wl), lat.device, lat.dtype, True
+        return tuple(lat.shape), lat.device, lat.dtype, False
+
     def begin_latent_grad(self, meta, handles):
         """Zeroed (SB * NS, Hl, Wl, L) accumulator bound in equal slices to the scene handles (pny_scene_bind_latent_grad):
         the per-object scenes take their own views each, the grouped scene takes it whole."""
@@ -663,9 +672,12 @@ class PixelNeRFNet(nn.Module):
         return buf
 
     def end_latent_grad(self, buf, meta, handles):
-        """Unbind and return the gradient in the latent's own layout (SB * NS, L, Hl, Wl), device and dtype."""
+        """Unbind and return the gradient in the latent's own layout (SB * NS, L, Hl, Wl), device and dtype; for a list of
+        feature maps the channel-last buffer itself, which pny_latent_levels_backward reads (_LevelsFunction)."""
         for h in handles:
             check(_lib.load().pny_scene_bind_latent_grad(h, None))
+        if len(meta) > 3 and meta[3]:
+            return buf
         return buf.permute(0, 3, 1, 2).contiguous().to(meta[1], meta[2])   # packed NCHW, like the latent it belongs to
 
     def bind_mlp_grads(self):
@@ -738,8 +750,16 @@ class PixelNeRFNet(nn.Module):
         :param images (NS, 3, H, W) or (SB, NS, 3, H, W), in [-1, 1]
         :param poses (NS, 4, 4) or (SB, NS, 4, 4) cam->world (YOLO mode: world->cam extrinsics)
         :param focal () or (N) or (N, 2);  :param c None or () or (N) or (N, 2)
-        :param latent optional (SB*NS, L, Hl, Wl): encoder bypass (required for backbone=custom)
+        :param latent optional (SB*NS, L, Hl, Wl): encoder bypass (required for backbone=custom); or the list / tuple of
+            feature maps (SB*NS, C_i, h_i, w_i) as a pyramid backbone returns it: every map is resized to the first map's size
+            (bilinear, align_corners=True) and the channels are concatenated, as the reference's SpatialEncoder.forward does
+            for backbone=custom (src/model/encoder.py:126-137) -- in one launch, straight into the scene's channel-last latent
+            (pny_scene_set_latent_levels).  Maps that require grad receive d loss / d map from the render / query backward.
         """
+        levels = None
+        if isinstance(latent, (list, tuple)):
+            n_views = int(images.shape[0] * images.shape[1]) if images.dim() == 5 else int(images.shape[0])
+            levels = check_latent_levels(latent, n_views, self.d_latent)
         self._sync()
         L = _lib.load()
         dev = self._device()
@@ -797,10 +817,18 @@ class PixelNeRFNet(nn.Module):
         # a latent that requires grad (this trunk's, or a trainable encoder outside the library): the render backward returns
         # d loss / d latent for it (render._RenderFunction, pny_scene_bind_latent_grad)
         self._latent_src = latent if (torch.is_tensor(latent) and latent.requires_grad) else None
-        if latent is not None:
+        self._latent_channel_last = levels is not None
+        if levels is not None:
+            # the maps as the library reads them (fp32, packed NCHW, on the device); the tensor that stands for the assembled
+            # latent in the render's graph carries the maps' graph (_LevelsFunction)
+            maps = [m.detach().to(dev, torch.float32).contiguous() for m in latent]
+            token = _LevelsFunction.apply(self, levels, *latent)
+            self._latent_src = token if token.requires_grad else None
+            latent = None
+        elif latent is not None:
             latent = latent.detach().to(dev, torch.float32).contiguous()
             assert latent.dim() == 4 and latent.shape[0] == SB * NS, "latent must be (SB*NS, L, Hl, Wl)"
-        else:
+        elif levels is None:
             if getattr(self, "_enc_stale", False):   # the trunk's weights were trained since their last upload
                 self._synced_key = None
                 self._sync()
@@ -820,7 +848,9 @@ class PixelNeRFNet(nn.Module):
             f_all, c_all = all_rows(focal), all_rows(c)
             check(L.pny_scene_set_cameras(g, ptr(poses_h), SB * NS, ptr(f_all), SB * NS, ptr(c_all), SB * NS, W, H))
             check(L.pny_scene_set_groups(g, SB))
-            if latent is not None:
+            if levels is not None:
+                set_latent_levels(g, maps, levels, 0, SB * NS, st)
+            elif latent is not None:
                 check(L.pny_scene_set_latent(g, ptr(latent), SB * NS, latent.shape[1], latent.shape[2], latent.shape[3], st))
             else:
                 check(L.pny_scene_encode(g, ptr(images), SB * NS, H, W, st))
@@ -830,7 +860,7 @@ class PixelNeRFNet(nn.Module):
         scenes = [self._scene(sb) for sb in range(SB)]
         # the library's trunk over a super-batch: ONE pass over all SB * NS images (as the reference's encode flattens them),
         # cameras per scene below
-        batch_encode = latent is None and SB > 1
+        batch_encode = latent is None and levels is None and SB > 1
         if batch_encode:
             arr = (C.c_void_p * SB)(*[s_ for s_ in scenes])
             check(L.pny_scenes_encode(arr, SB, ptr(images), NS, H, W, stream_of(dev)))
@@ -842,7 +872,9 @@ class PixelNeRFNet(nn.Module):
             f_s, c_s = self._cam_rows(focal, sb, SB, NS).contiguous(), self._cam_rows(c, sb, SB, NS).contiguous()
             p_s = poses_h[sb * NS:(sb + 1) * NS].contiguous()
             check(L.pny_scene_set_cameras(s, ptr(p_s), NS, ptr(f_s), f_s.shape[0], ptr(c_s), c_s.shape[0], W, H))
-            if latent is not None:
+            if levels is not None:
+                set_latent_levels(s, maps, levels, sb * NS, NS, st)
+            elif latent is not None:
                 lat = latent[sb * NS:(sb + 1) * NS]
                 check(L.pny_scene_set_latent(s, ptr(lat), NS, lat.shape[1], lat.shape[2], lat.shape[3], st))
             elif not batch_encode:
@@ -960,6 +992,69 @@ class PixelNeRFNet(nn.Module):
         return self
 
 
+def check_latent_levels(maps, n_views, d_latent):
+    """encode(latent=[m0, m1, ...]): the list's shapes, or ValueError -> ((C_i, h_i, w_i) per level)."""
+    if len(maps) == 0:
+        raise ValueError("encode(latent=[...]): empty list of feature maps")
+    if len(maps) > _lib.MAX_LATENT_LEVELS:
+        raise ValueError("encode(latent=[...]): %d feature maps, more than %d levels" % (len(maps), _lib.MAX_LATENT_LEVELS))
+    for i, m in enumerate(maps):
+        if not torch.is_tensor(m) or m.dim() != 4 or not m.is_floating_point():
+            raise ValueError("encode(latent=[...]): map %d is not a 4-D float tensor (SB*NS, C, h, w)" % i)
+    for i, m in enumerate(maps):
+        if m.shape[0] != n_views:
+            raise ValueError("encode(latent=[...]): leading sizes differ: map %d has %d, the images have SB*NS = %d"
+                             % (i, m.shape[0], n_views))
+        if min(m.shape[1:]) < 1:
+            raise ValueError("encode(latent=[...]): map %d is empty" % i)
+    total = sum(int(m.shape[1]) for m in maps)
+    if total != d_latent:
+        raise ValueError("encode(latent=[...]): the maps' channels sum to %d, d_latent is %d" % (total, d_latent))
+    return tuple((int(m.shape[1]), int(m.shape[2]), int(m.shape[3])) for m in maps)
+
+
+def _levels_arrays(levels):
+    n = len(levels)
+    return [(C.c_int * n)(*[lv[k] for lv in levels]) for k in range(3)]
+
+
+def set_latent_levels(scene, maps, levels, first, count, stream):
+    """pny_scene_set_latent_levels on views [first, first + count) of fp32 packed NCHW device maps."""
+    ptrs = (C.c_void_p * len(maps))(*[m[first:first + count].data_ptr() for m in maps])
+    ch, hs, ws = _levels_arrays(levels)
+    check(_lib.load().pny_scene_set_latent_levels(scene, ptrs, ch, hs, ws, len(maps), count, stream))
+
+
+class _LevelsFunction(torch.autograd.Function):
+    """The feature maps of encode(latent=[...]) under autograd.  The output STANDS FOR the scene latent in the graphs of the
+    render / query calls: it has the shape of the library's channel-last latent, (SB * NS, Hl, Wl, L), and no storage of that
+    size (one element, expanded) -- the latent itself lives in the scene handles, where encode() assembles it
+    (pny_scene_set_latent_levels).  Backward: the channel-last d loss / d latent buffer of the render backward
+    (begin_latent_grad / end_latent_grad) goes to pny_latent_levels_backward, one launch, which writes the gradient of every map
+    that requires grad in the map's own NCHW shape.  No (n, L, Hl, Wl) tensor and no transpose on the way there or back."""
+
+    @staticmethod
+    def forward(ctx, net, levels, *maps):
+        ctx.net, ctx.levels = net, levels
+        ctx.metas = [(m.device, m.dtype) for m in maps]
+        n, (_, hl, wl) = maps[0].shape[0], levels[0]
+        return torch.empty(1, device=net._device(), dtype=torch.float32).expand(n, hl, wl, sum(lv[0] for lv in levels))
+
+    @staticmethod
+    def backward(ctx, g):
+        net, levels = ctx.net, ctx.levels
+        dev = net._device()
+        g = g.detach().to(dev, torch.float32).contiguous()
+        n = g.shape[0]
+        outs = [torch.empty(n, *lv, device=dev, dtype=torch.float32) if need else None
+                for lv, need in zip(levels, ctx.needs_input_grad[2:])]
+        ptrs = (C.c_void_p * len(levels))(*[None if o is None else o.data_ptr() for o in outs])
+        ch, hs, ws = _levels_arrays(levels)
+        with torch.cuda.device(dev):
+            check(_lib.load().pny_latent_levels_backward(ptr(g), ptrs, ch, hs, ws, len(levels), n, stream_of(dev)))
+        return (None, None) + tuple(None if o is None else o.to(d, t) for o, (d, t) in zip(outs, ctx.metas))
+
+
 class _TrunkFunction(torch.autograd.Function):
     """The ResNet-34 trunk in training mode on the library's kernels (pny_trunk_train_forward / _backward, reference
     src/model/encoder.py:139-173 under autograd): images (n, 3, H, W) -> latent (n, 512, H/2, W/2); backward fills the
@@ -1047,7 +1142,7 @@ class _QueryFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, xyz, coarse, viewdirs, n_params, *params):
         lat = params[n_params] if len(params) > n_params else None
-        ctx.lat_meta = None if lat is None else (tuple(lat.shape), lat.device, lat.dtype)
+        ctx.lat_meta = None if lat is None else net.latent_meta(lat)
         out = net._query(xyz, coarse, viewdirs)
         dev = net._device()
         ctx.net, ctx.coarse = net, coarse

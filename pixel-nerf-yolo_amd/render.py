@@ -114,6 +114,7 @@ class _MultiDeviceRenderWrapper(torch.nn.Module):
                 images = torch.zeros(le["SB"], le["NS"], 3, le["H"], le["W"])
                 r.encode(images, le["poses"], le["focal"], c=le["c"], latent=lat)
             self._seen[i] = key
+        r._latent_channel_last = getattr(net, "_latent_channel_last", False)   # (the layout of the master's latent leaf: latent_meta)
         return r
 
     def forward(self, rays, want_weights=False):
@@ -298,7 +299,7 @@ class _RenderFunction(torch.autograd.Function):
     def forward(ctx, renderer, model, rays, has_fine, n_params, *params):
         # params = the trainable MLP parameters, optionally followed by the differentiable latent of encode(latent=...)
         lat = params[n_params] if len(params) > n_params else None
-        ctx.lat_meta = None if lat is None else (tuple(lat.shape), lat.device, lat.dtype)
+        ctx.lat_meta = None if lat is None else model.latent_meta(lat)
         # Reserve the model-level stash for every scene's tiles (pny_model_defer_weight_grads): the forward then writes the
         # GEMM operands the backward needs while it evaluates the MLPs (no recompute), the scenes' backward calls run on
         # side streams and ONE weight-gradient GEMM per MLP follows.  If the reservation exceeds the stash budget: plain
@@ -686,7 +687,7 @@ class _YoloRenderFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, renderer, rays, n_params, *params):
         lat = params[n_params] if len(params) > n_params else None
-        ctx.lat_meta = None if lat is None else (tuple(lat.shape), lat.device, lat.dtype)
+        ctx.lat_meta = None if lat is None else renderer.net.latent_meta(lat)
         out, saved = renderer._render(rays, keep_raw=True)
         ctx.renderer, ctx.saved, ctx.net = renderer, saved, renderer.net   # (the net of THIS call: a per-device replica under bind_parallel)
         return out

@@ -891,6 +891,42 @@ def fixture_ckpt(name, seed=29):
     print("wrote", name, len(rec["load"]), "load cases,", len(rec["save"]), "save steps")
 
 
+def fixture_latent_levels(name):
+    """SpatialEncoder.forward with backbone = "custom" (reference encoder.py:126-137): a stub YOLOEncoder hands back a seeded
+    LIST of feature maps, the reference resizes each to the first map's size and concatenates them into self.latent.  Cases
+    and inputs are those of the sweep (tests/latent_levels_ref.py): of every list of level sizes the first case (channels a
+    multiple of 4, one image) and the last plain one (odd channel counts, two images)."""
+    import model.encoder as enc_mod
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import latent_levels_ref as lr
+
+    d = {}
+    for size_name in sorted(lr.SIZES):
+        plain = [c for c in lr.cases(size_name) if c["tag"] == "plain"]
+        for case in (plain[0], plain[-1]):
+            maps, _ = lr.inputs(case)
+
+            class StubYolo(nn.Module):
+                def __init__(self):
+                    super().__init__()
+                    self.dims = [sum(case["channels"])]
+
+                def forward(self, x):
+                    return [m.clone() for m in maps]
+
+            enc_mod.YOLOEncoder = StubYolo
+            enc = enc_mod.SpatialEncoder(backbone="custom", pretrained=False).eval()
+            with torch.no_grad():
+                lat = enc(torch.zeros(case["n"], 3, 8, 8))
+            assert enc.latent is lat and lat.shape[1] == enc.latent_size
+            key = lr.case_id(case)
+            for i, m in enumerate(maps):
+                d["%s/map%d" % (key, i)] = np_(m)
+            d[key + "/latent"] = np_(lat)
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **d)
+    print("wrote", name, len(d), "arrays,", os.path.getsize(os.path.join(OUT, name + ".npz")), "bytes")
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     install_shims()
@@ -927,6 +963,7 @@ def main():
     fixture_encoder("encoder_unit", seed=43, NS=1, H=64, W=48, residual_gain=0.25)
     fixture_enc_render("enc_render")
     fixture_ckpt("ckpt")
+    fixture_latent_levels("latent_levels")
 
 
 if __name__ == "__main__":
