@@ -951,7 +951,8 @@ double mlp_flops_per_point(const pny_model_desc& d, int ns, MlpPass pass) {
     const double per_view = (pass == PASS_CHAIN ? 0.0 : (double)d_in(d) * HID) +
                             (pass == PASS_FORWARD ? (double)nvb * d.d_latent * HID : 0.0) + 2.0 * nvb * HID * HID;
     const double post = 2.0 * (d.n_blocks - nvb) * HID * HID + (double)HID * d.d_out;
-    return 2.0 * (ns * per_view + post);
+    const double once = pass == PASS_FORWARD_VIEW_MEAN ? (double)(ns - 1) * HID * HID : 0.0;   // fc_1 GEMMs that do not run
+    return 2.0 * (ns * per_view + post - once);
 }
 }  // namespace pny
 
@@ -1186,7 +1187,10 @@ static int run_mlp(pny_scene* s, int mode, const float* xyz, const float* dirs, 
     if ((rc = stamp_event(s->timing, s->ev, s->ev_used, st))) return rc;
     s->last_prec = r.prec;
     s->last_projected = r.projected;
-    s->last_flops += mlp_flops_per_point(d, obj_views(s), r.projected ? PASS_FORWARD_PROJECTED : PASS_FORWARD) * (double)n_points;
+    // executed FLOPs: the non-stashing split-f16 kernels run the last per-view fc_1 once, on the mean over views (mlp_h2.hip)
+    const bool view_mean = !r.stash && (r.kernel == K_H2 || r.kernel == K_H2S);
+    s->last_flops += mlp_flops_per_point(d, obj_views(s), view_mean ? PASS_FORWARD_VIEW_MEAN : r.projected ? PASS_FORWARD_PROJECTED : PASS_FORWARD) *
+                     (double)n_points;
     s->last_flops_ref += mlp_flops_per_point(d, obj_views(s), PASS_FORWARD) * (double)n_points;
     s->last_launches += 1;
     return 0;

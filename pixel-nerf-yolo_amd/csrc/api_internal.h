@@ -290,7 +290,9 @@ inline int d_in(const pny_model_desc& d) { return 3 + 6 * d.num_freqs + 3; }   /
 // GEMM FLOPs (2 per MAC, unpadded) per query point over ns views: the forward as the reference computes it, the forward as the
 // projected-latent variant executes it (lin_z moved to the per-scene projection), the backward's dX chain.  Every forward
 // GEMM has one weight-gradient GEMM of the same size.
-enum MlpPass { PASS_FORWARD, PASS_FORWARD_PROJECTED, PASS_CHAIN };
+// PASS_FORWARD_VIEW_MEAN: a projected forward in the view-mean order of the non-stashing split-f16 kernels (mlp_h2.hip): the last
+// per-view fc_1 runs once per sample instead of once per view
+enum MlpPass { PASS_FORWARD, PASS_FORWARD_PROJECTED, PASS_CHAIN, PASS_FORWARD_VIEW_MEAN };
 double mlp_flops_per_point(const pny_model_desc& d, int ns, MlpPass pass);
 // single-plane f16 images (PNY_PRECISION_F16): marks the model as using them and builds them if it is finalized
 int want_h1_images(pny_model* m, bool transposed = false);   // transposed: also the chain's images (PNY_PRECISION_F16_TRAIN)

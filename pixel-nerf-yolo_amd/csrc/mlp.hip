@@ -298,7 +298,9 @@ int mlp_pick_variant(long long n_points) {
 }
 int mlp_tile_samples(int variant) { return variant == MLP_8x32 ? 32 : 64; }
 int mlp_max_grid(int variant) { return mlp_cu_count() * (variant == MLP_8x32 ? 2 : 1); }
-size_t mlp_scratch_floats() { return (size_t)mlp_cu_count() * 64 * HID; }  // same for every shape
+// Same for every shape.  Two slabs per resident workgroup: the running sum of h and, behind the h slabs of the whole grid, the
+// split-f16 kernels' running sum of relu(net) of the last per-view block (mlp_h2.hip); the fp32 kernels address the first half only.
+size_t mlp_scratch_floats() { return (size_t)mlp_cu_count() * 64 * HID * 2; }
 
 template <class C, bool ZP>
 static void launch_mlp_t(const MlpArgs& a, int grid, hipStream_t st) {

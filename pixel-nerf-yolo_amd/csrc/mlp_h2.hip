@@ -25,8 +25,25 @@
 //     of (h_v + b) = mean(h_v) + b, so the last per-view bias may follow the mean.)
 //   * the projected channels of a block arrive in 4 chunks of 128 through two register buffers, the first chunk of the next
 //     block fetched underneath the fc_1 GEMM (in the registers of the then-dead `net` accumulators);
-//   * stash / slab traffic goes through raw buffer resources (one VGPR of lane offset instead of per-quad 64-bit pointers).
-// STASH = true is the training forward (the backward's operand stash written from prologue and epilogues).
+//   * stash / slab traffic goes through raw buffer resources (one VGPR of lane offset instead of per-quad 64-bit pointers);
+//   * the VIEW-MEAN order (the non-stashing two-plane instantiations, pny_mlp_h2_kernel<false> and pny_mlp_h2s_kernel): the
+//     last per-view block ends `h_v += fc_1(R_v)`, R_v =
+//     relu(net_v + b_fc0), directly followed by the mean over views, and fc_1 is linear, so
+//         mean_v(h_v + fc_1(R_v)) = mean_v(h_v) + fc_1(mean_v R_v):
+//     that block's fc_1 GEMM runs ONCE per sample instead of once per view (20 instead of 22 full GEMMs per 3-view tile).
+//     Every view but the last stops behind the block's fc_0 GEMM: in registers net = relu(net + b_fc0), the running sums of
+//     the earlier views are added to net and to h from two lane-private slabs (the h slab and, behind the h slabs of the
+//     whole grid, a second one of the same layout for R) and stored back; nothing goes to the planes, no barrier, and the
+//     fc_0 GEMM leaves the weight ring primed for the next view's lin_in.  The last view writes the planes of net / NS (the
+//     epilogues' split and f16-range guard), scales h by 1 / NS and runs the one fc_1 GEMM.  One path: a single view takes
+//     it with 1 / NS = 1, which is exact.  One fp32 sum per sample is reordered (the sqrt(NS) averaging of that one layer's
+//     rounding error is lost); a result still does not depend on the batch a point is rendered in.
+//     -DPNY_H2_PER_VIEW_FC1 (diagnostic builds only, tools/h2_variant_build.sh) keeps the per-view order for an A/B.
+// STASH = true is the training forward (the backward's operand stash written from prologue and epilogues); it keeps the
+// per-view order: the backward and the stash layout consume relu(net_v) of every view.  The single-plane kernel below keeps
+// it too: its no-grad kernel is also the training forward of an F16_TRAIN scene whose stash has no room, and with the view-mean
+// order there tests/test_gpu_f16_train.py test_recompute_in_chunks_deterministic measures 2.94e-3 against its 2.6e-3 bar
+// (1.28e-3 in the per-view order).
 // This file is compiled with -fno-slp-vectorize (csrc/Makefile).  Phase timing: -DPNY_H2_STAMP
 // (tools/h2_variant_build.sh).
 //
@@ -241,6 +258,106 @@ __device__ __forceinline__ void h2slab_load(f32x16 (&t)[h2::NT][h2::MT], const S
             }
 }
 
+// The last per-view block in the view-mean order (header comment): behind its fc_0 GEMM, in registers,
+//     net = relu(net + b_fc0) (+ the running sum of the earlier views' relu: `add`),   h += the earlier views' h (`add`),
+// and both running sums go back to the lane's slabs for the next view (`store`).  Nothing touches the planes, so no barrier.
+// The slabs arrive an accumulator tile at a time through a few buffers of 16 registers (SlabPipe), never the 64 registers of a
+// whole slab.
+// `add` and `store` are run-time flags of ONE body on purpose: as four instantiations that join in front of the next phase
+// the kernel spilled 126 VGPRs instead of 33.
+// piece 2 t = tile t of the relu slab, piece 2 t + 1 = tile t of the h slab; SD buffers of 16 registers: SD - 1 pieces are in
+// flight while one is summed.  Measured on the C2 frame (profiles/view_mean_fc1.md): depth 2 38.16, 3 37.98, 4 37.89 ms per
+// launch at the same spill count, 5 spills more; issuing the first pieces underneath the fc_0 GEMM (h2gemm's `side` hook)
+// returned nothing on top (37.83 with two pieces, 38.6 with three).
+#ifndef PNY_H2_SLAB_DEPTH
+#define PNY_H2_SLAB_DEPTH 4
+#endif
+struct SlabPipe {
+    static constexpr int SD = PNY_H2_SLAB_DEPTH;
+    static_assert(SD >= 2, "slab pipeline");
+    f32x4 buf[SD][4];
+};
+__device__ __forceinline__ void h2slab_issue(SlabPipe& sp, int p, const SlabRef& sh, const SlabRef& sr) {
+    const SlabRef& s = (p & 1) ? sh : sr;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        sp.buf[p % SlabPipe::SD][q] =
+            __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(s.rsrc, s.lane_off, (unsigned)(((p >> 1) * 4 + q) * 64 * 16), 2));
+}
+__device__ __forceinline__ void h2view_sum(f32x16 (&net)[h2::NT][h2::MT], f32x16 (&h)[h2::NT][h2::MT], const float* bias, const SlabRef& sh,
+                                           const SlabRef& sr, bool add, bool store, int wave, int lane) {
+    using namespace h2;
+    SlabPipe sp;
+    const float* bl = bias + 32 * NT * wave + 4 * (lane >> 5);
+    constexpr int NP = 2 * NT * MT, SD = SlabPipe::SD;
+    if (add) {
+#pragma unroll
+        for (int p = 0; p + 1 < SD; ++p) h2slab_issue(sp, p, sh, sr);
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const int nt = (p >> 1) / MT, mt = (p >> 1) % MT;
+        if (add) {
+            if (p + SD - 1 < NP) h2slab_issue(sp, p + SD - 1, sh, sr);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        f32x16& t = (p & 1) ? h[nt][mt] : net[nt][mt];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (!(p & 1)) {
+                const float4 b = *reinterpret_cast<const float4*>(bl + 32 * nt + 8 * q);
+                t[4 * q + 0] = relu1(t[4 * q + 0] + b.x);
+                t[4 * q + 1] = relu1(t[4 * q + 1] + b.y);
+                t[4 * q + 2] = relu1(t[4 * q + 2] + b.z);
+                t[4 * q + 3] = relu1(t[4 * q + 3] + b.w);
+            }
+            if (add) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) t[4 * q + i] = t[4 * q + i] + sp.buf[p % SD][q][i];
+            }
+            if (store) {
+                const SlabRef& s = (p & 1) ? sh : sr;
+                const f32x4 v = {t[4 * q + 0], t[4 * q + 1], t[4 * q + 2], t[4 * q + 3]};
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), s.rsrc, s.lane_off + (unsigned)(((p >> 1) * 4 + q) * 64 * 16), 0, 2);
+            }
+        }
+        if (add) __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// ... and on the last view the planes of the mean, net * rns (rns = 1 / NS; 1 for a single view: today's bits), go to the
+// lane's own feature-quad slots like an epilogue's, with the same f16-range guard; then h becomes the mean as well.
+__device__ __forceinline__ void h2mean_planes(const f32x16 (&net)[h2::NT][h2::MT], f32x16 (&h)[h2::NT][h2::MT], float rns, char* planes, int wave,
+                                              int lane, unsigned* range_flag) {
+    using namespace h2;
+    float rmax = 0.f;
+    char* base = planes + (4 * NT * wave) * (2 * ROW_BYTES) + (lane & 31) * 16 + 8 * (lane >> 5);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                char* s0 = base + (4 * nt + q) * (2 * ROW_BYTES) + 32 * mt * 16;
+                const float r0 = net[nt][mt][4 * q + 0] * rns, r1 = net[nt][mt][4 * q + 1] * rns;
+                const float r2 = net[nt][mt][4 * q + 2] * rns, r3 = net[nt][mt][4 * q + 3] * rns;
+                rmax = fmaxf(fmaxf(rmax, fmaxf(r0, r1)), fmaxf(r2, r3));
+#if PNY_H2_PLANES == 1
+                *reinterpret_cast<h4*>(s0) = cvt4(r0, r1, r2, r3);
+#else
+                h4 p0, p1;
+                split4(r0, r1, r2, r3, p0, p1);
+                *reinterpret_cast<h4*>(s0) = p0;
+                *reinterpret_cast<h4*>(s0 + ROW_BYTES) = p1;
+#endif
+#pragma unroll
+                for (int i = 0; i < 4; ++i) h[nt][mt][4 * q + i] = h[nt][mt][4 * q + i] * rns;
+            }
+#ifndef PNY_H2_EXP_NOSYNC
+    if (__builtin_expect(!(rmax < 65520.0f), 0)) range_report(range_flag, 1u);
+#endif
+}
+
 // gather_commit (mlp_core.h) for the staging layout above: chunk c covers feature quads [32 c, 32 c + 32)
 template <int B>
 __device__ __forceinline__ void h2gather_commit(const GatherTaps<h2::C, 2>& g, char* planes, int chunk, int wave, int lane) {
@@ -374,6 +491,16 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
 #endif
     const SlabRef slab = {__builtin_amdgcn_make_buffer_rsrc(a.scratch + (size_t)blockIdx.x * (TM * HID), 0, TM * HID * 4, 0x00020000),
                           (unsigned)((wave * (NT * MT * 16 * 64) + 4 * lane) * 4)};
+    // The view-mean order (header comment) of the non-stashing two-plane instantiations; -DPNY_H2_PER_VIEW_FC1 (diagnostic
+    // builds only, tools/h2_variant_build.sh) keeps the per-view order for an A/B.  Its second slab, the running sum of
+    // relu(net), lies behind the h slabs of the whole grid.
+#if defined(PNY_H2_PER_VIEW_FC1) || PNY_H2_PLANES == 1
+    constexpr bool VIEW_MEAN = false;
+#else
+    constexpr bool VIEW_MEAN = !STASH;
+#endif
+    const SlabRef slab_r = {__builtin_amdgcn_make_buffer_rsrc(a.scratch + ((size_t)gridDim.x + blockIdx.x) * (TM * HID), 0, TM * HID * 4, 0x00020000),
+                            slab.lane_off};
     const int nb = a.n_blocks;
     const int nvb = a.combine_layer < nb ? a.combine_layer : nb;   // >= 1 (the host only selects this kernel with a projection)
     const WStream ws = wstream(a, lane);
@@ -441,7 +568,7 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
             h2epilogue<false, STASH>(net, fc0_bias(blk), planes, wave, lane, a.range_flag, xr, stash_net);
             // three exclusive continuations (the running sum of the other views and the prefetched chunk both want the
             // registers of `net`: written as one if / else chain so that the allocator never has to provide for both)
-            if (slab_in) {
+            if (!VIEW_MEAN && slab_in) {   // (per-view order only: the view-mean order sums in mean_tail)
                 h2slab_load(net, slab);
                 HS_LAP(HS_EPI);
                 H2SYNC();
@@ -516,7 +643,7 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
             HS_LAP(HS_GEMM);
             // one per-view block; the last one of a view is a call site of its own so that the compiler sees that the
             // gather buffers are dead across its fc_1 GEMM (where the other views' running sum takes those registers)
-            auto view_block = [&](int blk, const H2Seg& after, bool slab_in, int next_c0) {
+            auto block_entry = [&](int blk) {
                 // h += interp(lin_z[blk](latent map)): the block's 512 projected channels in 4 chunks of 128, staged in
                 // fp32 (see h2epilogue).  Chunk 0 is in buffer 0 already (issued before / underneath the previous GEMM);
                 // from here two chunks are in flight: the loads of chunk c + 1 are issued before chunk c is blended.
@@ -547,7 +674,36 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
                 HS_LAP(HS_GATHER_WAIT);
                 h2epilogue<true, STASH>(h, entry_bias(blk), planes, wave, lane, a.range_flag, xr, act_slot(2 * blk));
                 HS_LAP(HS_EPI);
+            };
+            auto view_block = [&](int blk, const H2Seg& after, bool slab_in, int next_c0) {
+                block_entry(blk);
                 block_tail(blk, after, slab_in, next_c0, act_slot(2 * blk + 1));
+            };
+            // The last per-view block in the view-mean order: fc_1 is linear, so mean_v(h_v + fc_1(R_v)) = mean_v(h_v) +
+            // fc_1(mean_v R_v) with R_v = relu(net_v + b_fc0) -- every view but the last ends behind its fc_0 GEMM, with both
+            // running sums in the slabs and the ring primed for the next view's lin_in; the last view runs the one fc_1 GEMM.
+            auto mean_tail = [&](int blk) {
+                const bool last = v + 1 == a.NS;
+                HS_T0();
+                h2zero<NT, MT>(net);
+                H2SYNC();
+                HS_LAP(HS_EPI_WAIT);
+                h2gemm(net, ring, ws, fc0seg(blk), last ? fc1seg(blk) : s_in, planes, lane);
+                HS_LAP(HS_GEMM);
+                h2view_sum(net, h, fc0_bias(blk), slab, slab_r, v > 0, !last, wave, lane);
+                if (!last) {
+                    HS_LAP(HS_SLAB);
+                    return;
+                }
+                HS_LAP(v > 0 ? HS_SLAB : HS_EPI);
+                H2SYNC();   // every wave is done reading the planes (fc_0 GEMM)
+                HS_LAP(HS_EPI_WAIT);
+                h2mean_planes(net, h, 1.0f / (float)a.NS, planes, wave, lane, a.range_flag);
+                HS_LAP(HS_EPI);
+                H2SYNC();
+                HS_LAP(HS_EPI_WAIT);
+                h2gemm(h, ring, ws, fc1seg(blk), after_view, planes, lane);
+                HS_LAP(HS_GEMM);
             };
 #if defined(PNY_H2_NOPREFETCH)
             for (int blk = 0; blk + 1 < nvb; ++blk) {
@@ -557,8 +713,13 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
 #else
             for (int blk = 0; blk + 1 < nvb; ++blk) view_block(blk, fc0seg(blk + 1), false, (blk + 1) * HID);
 #endif
-            view_block(nvb - 1, after_view, v > 0, -1);
-            if (a.NS > 1) {
+            if constexpr (VIEW_MEAN) {
+                block_entry(nvb - 1);
+                mean_tail(nvb - 1);
+            } else {
+                view_block(nvb - 1, after_view, v > 0, -1);
+            }
+            if (!VIEW_MEAN && a.NS > 1) {
                 HS_T0();
                 if (v + 1 < a.NS) {
                     h2slab_store(h, slab);

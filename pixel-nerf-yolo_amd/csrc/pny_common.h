@@ -56,7 +56,8 @@ struct MlpArgs {
     const float* rays;
     const float* z;
     float* out;       // (n_points, d_out)
-    float* scratch;   // gridDim.x * tile * HID floats: cross-view running sum
+    float* scratch;   // cross-view running sums (mlp_scratch_floats): gridDim.x * tile * HID floats of h, and behind them as many
+                      // of relu(net) of the last per-view block (the f16 kernels' view-mean order, mlp_h2.hip)
     long long n_points;
     int K;            // samples per ray (mode 1)
     int mode;
