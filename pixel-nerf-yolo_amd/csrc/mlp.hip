@@ -73,27 +73,9 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void pny_mlp_kernel(const MlpAr
     };
     WRing<C::WDEPTH, NT> ring;
     ring_fill(ring, ws, s_in);
-#ifdef PNY_EXP_FOOT
-    ring.exp_base = s_in.off;
-    ring.exp_ctr = 0;
-#endif
 
-    // XCD-aware tile order: workgroups are dispatched round-robin over the 8 XCDs (XCD = blockIdx % 8), each with
-    // its own L2.  XCD x walks the contiguous tile range [x*chunk, (x+1)*chunk): the 32 workgroups of an XCD then
-    // work on neighbouring rays at any moment, whose samples project onto overlapping pixels of the (projected)
-    // latent, instead of on every 8th ray.
-#ifndef PNY_NO_XCD_ORDER
-    const bool xcd_order = (gridDim.x & 7) == 0;
-#else
-    const bool xcd_order = false;
-#endif
-    const long long t_chunk = xcd_order ? (a.n_tiles + 7) / 8 : a.n_tiles;
-    const long long t_first = xcd_order ? (long long)(blockIdx.x & 7) * t_chunk + (blockIdx.x >> 3) : blockIdx.x;
-    const long long t_last = xcd_order ? ((long long)((blockIdx.x & 7) + 1) * t_chunk < a.n_tiles
-                                              ? (long long)((blockIdx.x & 7) + 1) * t_chunk : (long long)a.n_tiles)
-                                       : (long long)a.n_tiles;
-    const int t_step = xcd_order ? (int)(gridDim.x >> 3) : (int)gridDim.x;
-    for (long long tile = t_first; tile < t_last; tile += t_step) {
+    const TileWalk tw = tile_walk(a.n_tiles);   // XCD-aware order (mlp_core.h)
+    for (long long tile = tw.first; tile < tw.last; tile += tw.step) {
         f32x16 h[NT][MT];
         float* const x_rec = STASH ? a.lay.x_record(a.stash_x, tile) : nullptr;
         auto slot = [&](unsigned off) { return reinterpret_cast<float4*>(x_rec + off); };   // off: a slot of a.lay (stash.h)
@@ -243,13 +225,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void pny_mlp_kernel(const MlpAr
                 sum += x.z * ww.z;
                 sum += x.w * ww.w;
             }
-            sum += a.w.b_out[o];
-            if (!a.yolo) {
-                if (o < 3)
-                    sum = 1.0f / (1.0f + expf(-sum));
-                else if (o == 3)
-                    sum = fmaxf(sum, 0.f);
-            }
+            sum = output_head(sum + a.w.b_out[o], o, a.yolo);
             const long long s = tile * TMc + m;
             if (s < a.n_points) a.out[s * a.d_out + o] = sum;
         }

@@ -539,12 +539,8 @@ __global__ __launch_bounds__(256) void mlp_dz_kernel(const DzArgs a) {
     const int vb = a.obj_pts ? __builtin_amdgcn_readfirstlane((int)((long long)idx / a.obj_pts) * a.NS) : 0;
     for (int v = 0; v < a.NS; ++v) {
         const Cam cam = a.cams[vb + v];
-        float xr[3], xc[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            xr[k] = cam.w2c[4 * k + 0] * p[0] + cam.w2c[4 * k + 1] * p[1] + cam.w2c[4 * k + 2] * p[2];
-            xc[k] = xr[k] + cam.w2c[4 * k + 3];
-        }
+        float xr[3], xc[3], vd[3];
+        camera_point(cam, p, d, xr, xc, vd);
         // ---- positional code: g_in = lin_in^T dh_in(0), then d sin(phase + x f) / dx = cos(.) f
         const float* dh0 = dy_rec + a.lay.dy_lin_in(v);
         {
@@ -580,17 +576,12 @@ __global__ __launch_bounds__(256) void mlp_dz_kernel(const DzArgs a) {
         for (int k = 0; k < 3; ++k) gx[k] = bwd_wave_sum(dim == k ? c : 0.f);
         // ---- projection + bilinear lookup of the projected maps
         if (a.lay.nvb() > 0 && a.zp) {
+            // the forward's pixel coordinates and corners (mlp_core.h); sgn: d(ux, uy)/d xc of pixel_coords' two modes
             const float sgn = a.yolo ? 1.0f : -1.0f;
-            float ux = sgn * xc[0] / xc[2], uy = sgn * xc[1] / xc[2];
-            ux = ux * cam.fx + cam.cx;
-            uy = uy * cam.fy + cam.cy;
-            const float gxn = ux * a.sx - 1.0f, gyn = uy * a.sy - 1.0f;
-            const float ix = ((gxn + 1.0f) / 2.0f) * (float)(a.Wl - 1);
-            const float iy = ((gyn + 1.0f) / 2.0f) * (float)(a.Hl - 1);
-            const float x0 = floorf(ix), y0 = floorf(iy);
-            const float x1 = x0 + 1.0f, y1 = y0 + 1.0f;
-            const float xs[4] = {x0, x1, x0, x1};
-            const float ys[4] = {y0, y0, y1, y1};
+            float ix, iy, xs[4], ys[4];
+            pixel_coords(a, cam, xc, ix, iy);
+            tap_corners(ix, iy, xs, ys);
+            const float x0 = xs[0], x1 = xs[1], y0 = ys[0], y1 = ys[2];
             // d(bilinear weight of tap k)/d ix and /d iy: nw = (x1-ix)(y1-iy), ne = (ix-x0)(y1-iy), sw, se
             const float wx[4] = {-(y1 - iy), (y1 - iy), -(iy - y0), (iy - y0)};
             const float wy[4] = {-(x1 - ix), -(ix - x0), (x1 - ix), (ix - x0)};
@@ -604,8 +595,7 @@ __global__ __launch_bounds__(256) void mlp_dz_kernel(const DzArgs a) {
                     const float4 h1 = *reinterpret_cast<const float4*>(dhb + ((size_t)(2 * lane + 1) * 64 + m) * 4);
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const bool ok = (xs[k] >= 0.f) && (xs[k] <= (float)(a.Wl - 1)) && (ys[k] >= 0.f) && (ys[k] <= (float)(a.Hl - 1));
-                        if (!ok) continue;
+                        if (!tap_inside(a, xs[k], ys[k])) continue;
                         const float* tp = zv + ((size_t)((int)ys[k] * a.Wl + (int)xs[k])) * a.zp_stride + b * HID + 8 * lane;
                         const float4 t0 = *reinterpret_cast<const float4*>(tp);
                         const float4 t1 = *reinterpret_cast<const float4*>(tp + 4);

@@ -53,15 +53,7 @@ __device__ __forceinline__ void bh_store(const Acc (&acc)[h2::NT][h2::MT], char*
             for (int q = 0; q < 4; ++q) {
                 const float x0 = acc[nt][mt][4 * q + 0], x1 = acc[nt][mt][4 * q + 1], x2 = acc[nt][mt][4 * q + 2], x3 = acc[nt][mt][4 * q + 3];
                 if (TO_LDS) {
-                    char* s0 = base + (4 * nt + q) * (2 * ROW_BYTES) + 32 * mt * 16;
-#if PNY_H2_PLANES == 1
-                    *reinterpret_cast<h4*>(s0) = cvt4(x0, x1, x2, x3);
-#else
-                    h4 p0, p1;
-                    split4(x0, x1, x2, x3, p0, p1);
-                    *reinterpret_cast<h4*>(s0) = p0;
-                    *reinterpret_cast<h4*>(s0 + ROW_BYTES) = p1;
-#endif
+                    put_planes(base + (4 * nt + q) * (2 * ROW_BYTES) + 32 * mt * 16, x0, x1, x2, x3);
                 }
                 if (TO_GLOBAL) {
                     const float4 v = make_float4(x0 * inv_sigma, x1 * inv_sigma, x2 * inv_sigma, x3 * inv_sigma);
@@ -177,15 +169,8 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_BWD_KERNEL(const BwdArgs a
         for (int i = 0; i < NQ; ++i) {
             const int idx = tid + i * THREADS;
             const int kg = idx / TM, m = idx % TM;
-            char* s0 = planes + (kg >> 1) * (2 * ROW_BYTES) + m * 16 + 8 * (kg & 1);
-#if PNY_H2_PLANES == 1
-            *reinterpret_cast<h4*>(s0) = cvt4(hv[i].x * sigma, hv[i].y * sigma, hv[i].z * sigma, hv[i].w * sigma);
-#else
-            h4 p0, p1;
-            split4(hv[i].x * sigma, hv[i].y * sigma, hv[i].z * sigma, hv[i].w * sigma, p0, p1);
-            *reinterpret_cast<h4*>(s0) = p0;
-            *reinterpret_cast<h4*>(s0 + ROW_BYTES) = p1;
-#endif
+            put_planes(planes + (kg >> 1) * (2 * ROW_BYTES) + m * 16 + 8 * (kg & 1), hv[i].x * sigma, hv[i].y * sigma, hv[i].z * sigma,
+                       hv[i].w * sigma);
         }
         __syncthreads();
         bh_acc dh[NT][MT];

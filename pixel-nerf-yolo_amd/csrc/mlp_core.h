@@ -151,10 +151,6 @@ __device__ __forceinline__ f32x4 wload(const WStream& ws, unsigned seg_off, int 
 template <int D, int NT>
 struct WRing {
     f32x4 f[D][NT];
-#ifdef PNY_EXP_FOOT  // timing-only experiment: stream cyclically through the first PNY_EXP_FOOT k-iterations
-    unsigned exp_base;  // (16 KiB each) of the packed blob instead of the real layers (wrong results)
-    int exp_ctr;
-#endif
 };
 
 template <int D, int NT>
@@ -204,19 +200,8 @@ __device__ __forceinline__ void gemm_run(f32x16 (&acc)[C::NT][C::MT], WRing<C::W
             const unsigned src = in_cur ? cur.off : next.off;
             // (at jd == 0 this loads fragment WDEPTH-1 of this very segment: on entry the ring holds
             //  fragments 0 .. WDEPTH-2 only, so there is no special case at segment boundaries)
-#ifdef PNY_EXP_FOOT
-            {
-                (void)src;
-                (void)jx;
-                const int it = r.exp_ctr;
-                r.exp_ctr = (it + 1 == PNY_EXP_FOOT) ? 0 : it + 1;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) r.f[dp][nt] = wload(ws, r.exp_base, nt, it);
-            }
-#else
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) r.f[dp][nt] = wload(ws, src, nt, jx);
-#endif
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) B[(d + 1) & 1][mt] = bp[(2 * j1) * TMc + 32 * mt];
             mfma_iter<NT, MT>(acc, r.f[d], B[d & 1]);
@@ -517,6 +502,87 @@ __device__ __forceinline__ float input_entry(int e, const float (&xr)[3], const 
     return 0.f;
 }
 
+// ---- sample geometry: world point -> camera -> latent pixel -> four bilinear taps ----------------------------------
+// The ONE definition for every kernel that looks a sample up in a source view: the forward prologues (prologue<C>
+// below, h2prologue in mlp_h2.hip), sample_taps (latent_grad*.hip) and the depth gradient (mlp_bwd.hip mlp_dz_kernel).
+// `A` is MlpArgs or DzArgs (yolo, sx, sy, Wl, Hl).  The operation order is part of the contract: the fp32 kernel's parity
+// with the reference and the bit-equality of forward and backward taps rest on it (the build uses -ffp-contract=off).
+
+// xr = R p (the positional code's input), xc = xr + t (camera coordinates), vd = R d (view direction)
+__device__ __forceinline__ void camera_point(const Cam& cam, const float (&p)[3], const float (&d)[3], float (&xr)[3],
+                                             float (&xc)[3], float (&vd)[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        xr[i] = cam.w2c[4 * i + 0] * p[0] + cam.w2c[4 * i + 1] * p[1] + cam.w2c[4 * i + 2] * p[2];
+        xc[i] = xr[i] + cam.w2c[4 * i + 3];
+        vd[i] = cam.w2c[4 * i + 0] * d[0] + cam.w2c[4 * i + 1] * d[1] + cam.w2c[4 * i + 2] * d[2];
+    }
+}
+
+// projection (reference models.py:219-230; NeRF mode looks down -z, YOLO mode down +z) and grid_sample's pixel
+// coordinates (encoder.py:97-98, align_corners=True)
+template <class A>
+__device__ __forceinline__ void pixel_coords(const A& a, const Cam& cam, const float (&xc)[3], float& ix, float& iy) {
+    float ux, uy;
+    if (!a.yolo) {
+        ux = -xc[0] / xc[2];
+        uy = -xc[1] / xc[2];
+    } else {
+        ux = xc[0] / xc[2];
+        uy = xc[1] / xc[2];
+    }
+    ux = ux * cam.fx + cam.cx;
+    uy = uy * cam.fy + cam.cy;
+    const float gx = ux * a.sx - 1.0f, gy = uy * a.sy - 1.0f;
+    ix = ((gx + 1.0f) / 2.0f) * (float)(a.Wl - 1);
+    iy = ((gy + 1.0f) / 2.0f) * (float)(a.Hl - 1);
+}
+
+// the four corners around (ix, iy) in the order nw, ne, sw, se, and whether one lies inside the map (zeros padding)
+__device__ __forceinline__ void tap_corners(float ix, float iy, float (&xs)[4], float (&ys)[4]) {
+    const float x0 = floorf(ix), y0 = floorf(iy);
+    const float x1 = x0 + 1.0f, y1 = y0 + 1.0f;
+    xs[0] = x0, xs[1] = x1, xs[2] = x0, xs[3] = x1;
+    ys[0] = y0, ys[1] = y0, ys[2] = y1, ys[3] = y1;
+}
+template <class A>
+__device__ __forceinline__ bool tap_inside(const A& a, float x, float y) {
+    return (x >= 0.f) && (x <= (float)(a.Wl - 1)) && (y >= 0.f) && (y <= (float)(a.Hl - 1));
+}
+
+// The four bilinear taps of camera point xc: element offset (y * Wl + x) * stride (stride = the map's floats per pixel,
+// or 1 for the pixel index itself; 0 for a tap outside the map) and weight.  (The results are built in local arrays and
+// copied out: written straight to the caller's arrays the 16 x 64 fp32 kernel spilled two more VGPRs.)  An outside tap contributes 0 (its weight times 0: NaN coordinates stay
+// NaN in NeRF mode, as in ATen); YOLO mode zeroes the latent of a point with z >= 0 or NaN (models.py:224,254-264).
+template <class A>
+__device__ __forceinline__ void pixel_taps(const A& a, const Cam& cam, const float (&xc)[3], int stride, int (&offs)[4],
+                                           float (&wgt)[4]) {
+    float ix, iy, xs[4], ys[4];
+    pixel_coords(a, cam, xc, ix, iy);
+    tap_corners(ix, iy, xs, ys);
+    const float x0 = xs[0], x1 = xs[1], y0 = ys[0], y1 = ys[2];
+    float w[4] = {(x1 - ix) * (y1 - iy), (ix - x0) * (y1 - iy), (x1 - ix) * (iy - y0), (ix - x0) * (iy - y0)};
+    const bool cull = a.yolo && !(xc[2] < 0.0f);
+    int o[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        o[k] = 0;
+        if (tap_inside(a, xs[k], ys[k]))
+            o[k] = ((int)ys[k] * a.Wl + (int)xs[k]) * stride;
+        else
+            w[k] = w[k] * 0.0f;
+        if (cull || (a.yolo && (w[k] != w[k]))) w[k] = 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) offs[k] = o[k], wgt[k] = w[k];
+}
+
+// one 32-byte tap-table record per sample: {element offset[4] (int bits), weight[4]}
+__device__ __forceinline__ void tap_record(float4* tab, int m, const int (&offs)[4], const float (&wgt)[4]) {
+    tab[2 * m] = make_float4(__int_as_float(offs[0]), __int_as_float(offs[1]), __int_as_float(offs[2]), __int_as_float(offs[3]));
+    tab[2 * m + 1] = make_float4(wgt[0], wgt[1], wgt[2], wgt[3]);
+}
+
 // Per (view, tile) prologue: B operand of lin_in into act k-groups 0..15, and the four bilinear
 // taps of every sample into the tap table.
 template <class C>
@@ -530,12 +596,7 @@ __device__ __forceinline__ void prologue(const MlpArgs& a, int v, long long tile
     load_point(a, s, p, d);
     const Cam cam = a.cams[tile_view_base(a, tile * TMc) + v];
     float xr[3], xc[3], vd[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        xr[i] = cam.w2c[4 * i + 0] * p[0] + cam.w2c[4 * i + 1] * p[1] + cam.w2c[4 * i + 2] * p[2];
-        xc[i] = xr[i] + cam.w2c[4 * i + 3];
-        vd[i] = cam.w2c[4 * i + 0] * d[0] + cam.w2c[4 * i + 1] * d[1] + cam.w2c[4 * i + 2] * d[2];
-    }
+    camera_point(cam, p, d, xr, xc, vd);
     for (int g = part; g < D_IN_PAD / 4; g += NPART) {
         float4 x4;
         x4.x = input_entry(4 * g + 0, xr, vd, a.freq_factor, a.num_freqs);
@@ -545,85 +606,38 @@ __device__ __forceinline__ void prologue(const MlpArgs& a, int v, long long tile
         act[g * TMc + m] = x4;
     }
     if (part == NPART - 1) {
-        // projection (reference models.py:219-230) and grid_sample coordinates
-        // (encoder.py:97-98, align_corners=True, zeros padding)
-        float ux, uy;
-        if (!a.yolo) {
-            ux = -xc[0] / xc[2];
-            uy = -xc[1] / xc[2];
-        } else {
-            ux = xc[0] / xc[2];
-            uy = xc[1] / xc[2];
-        }
-        ux = ux * cam.fx + cam.cx;
-        uy = uy * cam.fy + cam.cy;
-        const float gx = ux * a.sx - 1.0f, gy = uy * a.sy - 1.0f;
-        const float ix = ((gx + 1.0f) / 2.0f) * (float)(a.Wl - 1);
-        const float iy = ((gy + 1.0f) / 2.0f) * (float)(a.Hl - 1);
-        const float x0 = floorf(ix), y0 = floorf(iy);
-        const float x1 = x0 + 1.0f, y1 = y0 + 1.0f;
-        float wgt[4] = {(x1 - ix) * (y1 - iy), (ix - x0) * (y1 - iy), (x1 - ix) * (iy - y0), (ix - x0) * (iy - y0)};
-        const float xs[4] = {x0, x1, x0, x1};
-        const float ys[4] = {y0, y0, y1, y1};
-        const bool cull = a.yolo && !(xc[2] < 0.0f);  // models.py:224,254-264: z >= 0 (or NaN) -> zero latent
         int offs[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const bool ok = (xs[k] >= 0.f) && (xs[k] <= (float)(a.Wl - 1)) && (ys[k] >= 0.f) && (ys[k] <= (float)(a.Hl - 1));
-            offs[k] = 0;
-            if (ok) {
-                offs[k] = ((int)ys[k] * a.Wl + (int)xs[k]) * a.tap_stride;
-            } else {
-                wgt[k] = wgt[k] * 0.0f;  // out-of-range tap contributes 0 (NaN coordinates stay NaN, as in ATen)
-            }
-            if (cull || (a.yolo && (wgt[k] != wgt[k]))) wgt[k] = 0.0f;
-        }
-        // one 32-byte record per sample: {offset[4] (int bits), weight[4]}
-        tap_tab[2 * m] = make_float4(__int_as_float(offs[0]), __int_as_float(offs[1]), __int_as_float(offs[2]),
-                                     __int_as_float(offs[3]));
-        tap_tab[2 * m + 1] = make_float4(wgt[0], wgt[1], wgt[2], wgt[3]);
+        float wgt[4];
+        pixel_taps(a, cam, xc, a.tap_stride, offs, wgt);
+        tap_record(tap_tab, m, offs, wgt);
     }
 }
 
-// The four bilinear taps of sample s in source view v: element offsets (pixel index x tap_stride) and weights, exactly as
-// the prologue above computes them (projection models.py:219-230; grid_sample coordinates encoder.py:97-98,
-// align_corners=True, zeros padding; YOLO-mode culling).  Used by kernels outside the forward chain (latent_grad.hip).
+// The four bilinear taps of sample s in source view v: element offsets (pixel index x tap_stride) and weights, the
+// forward prologues' own.  Used by kernels outside the forward chain (latent_grad.hip).
 // v: index into the scene's view list (a grouped scene: tile_view_base + the object's view).
+// The tap loop is pixel_taps' own, written out on the caller's arrays: through pixel_taps the SLP vectoriser packs the
+// weights into v_pk_mul_f32 / v_pk_add_f32 here (42 instead of 10 packed instructions per latent-gradient kernel), and with
+// those the deterministic latent gradient of a training step came out different between runs on the MI355X (13 pixels,
+// 5 % of the gradient's maximum; the anomaly of packed fp32 beside the f16 GEMMs, csrc/Makefile and DESIGN.md 4.0).
 __device__ __forceinline__ void sample_taps(const MlpArgs& a, int v, long long s, int (&offs)[4], float (&wgt)[4]) {
-    float p[3], d[3];
+    float p[3], d[3], xr[3], xc[3], vd[3];
     load_point(a, s, p, d);
     const Cam cam = a.cams[v];
-    float xc[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        xc[i] = (cam.w2c[4 * i + 0] * p[0] + cam.w2c[4 * i + 1] * p[1] + cam.w2c[4 * i + 2] * p[2]) + cam.w2c[4 * i + 3];
-    float ux, uy;
-    if (!a.yolo) {
-        ux = -xc[0] / xc[2];
-        uy = -xc[1] / xc[2];
-    } else {
-        ux = xc[0] / xc[2];
-        uy = xc[1] / xc[2];
-    }
-    ux = ux * cam.fx + cam.cx;
-    uy = uy * cam.fy + cam.cy;
-    const float gx = ux * a.sx - 1.0f, gy = uy * a.sy - 1.0f;
-    const float ix = ((gx + 1.0f) / 2.0f) * (float)(a.Wl - 1);
-    const float iy = ((gy + 1.0f) / 2.0f) * (float)(a.Hl - 1);
-    const float x0 = floorf(ix), y0 = floorf(iy);
-    const float x1 = x0 + 1.0f, y1 = y0 + 1.0f;
+    camera_point(cam, p, d, xr, xc, vd);
+    float ix, iy, xs[4], ys[4];
+    pixel_coords(a, cam, xc, ix, iy);
+    tap_corners(ix, iy, xs, ys);
+    const float x0 = xs[0], x1 = xs[1], y0 = ys[0], y1 = ys[2];
     wgt[0] = (x1 - ix) * (y1 - iy);
     wgt[1] = (ix - x0) * (y1 - iy);
     wgt[2] = (x1 - ix) * (iy - y0);
     wgt[3] = (ix - x0) * (iy - y0);
-    const float xs[4] = {x0, x1, x0, x1};
-    const float ys[4] = {y0, y0, y1, y1};
     const bool cull = a.yolo && !(xc[2] < 0.0f);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const bool ok = (xs[k] >= 0.f) && (xs[k] <= (float)(a.Wl - 1)) && (ys[k] >= 0.f) && (ys[k] <= (float)(a.Hl - 1));
         offs[k] = 0;
-        if (ok)
+        if (tap_inside(a, xs[k], ys[k]))
             offs[k] = ((int)ys[k] * a.Wl + (int)xs[k]) * a.tap_stride;
         else
             wgt[k] = wgt[k] * 0.0f;
@@ -660,11 +674,8 @@ __device__ __forceinline__ void gather_setup(GatherTaps<C, NB>& g, const float* 
     constexpr int NMB = GatherTaps<C>::NMB;
     const int m = (wave % NMB) * 8 + (lane & 7);
     const float* base = view_base + 4 * (lane >> 3);
-    float4 o = tap_tab[2 * m];
+    const float4 o = tap_tab[2 * m];
     const float4 w = tap_tab[2 * m + 1];
-#if defined(PNY_EXP_GATHER) && PNY_EXP_GATHER == 1  // timing only: every tap reads pixel 0 (wrong results)
-    o = make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
     g.t[0] = base + __float_as_int(o.x);
     g.t[1] = base + __float_as_int(o.y);
     g.t[2] = base + __float_as_int(o.z);
@@ -681,19 +692,24 @@ __device__ __forceinline__ void gather_issue(GatherTaps<C, NB>& g, int c0, int w
 #pragma unroll
     for (int i = 0; i < GatherTaps<C>::QPW; ++i) {
         const int qb = wave / NMB + i * QSTEP;  // q-block (8 quads = 32 channels) within the chunk
-#if defined(PNY_EXP_GATHER) && PNY_EXP_GATHER == 2  // timing only: no tap loads (wrong results)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) g.x[B][i][k] = make_float4(g.w[k], (float)c0, (float)qb, 1.f);
-#else
 #pragma unroll
         for (int k = 0; k < 4; ++k) g.x[B][i][k] = *reinterpret_cast<const float4*>(g.t[k] + c0 + 32 * qb);
-#endif
     }
 }
 
+// The fused four-tap blend: 1 multiply + 3 fused multiply-adds per component, taps in the order nw, ne, sw, se.
+__device__ __forceinline__ float4 tap_blend(const float4 (&x)[4], const float (&w)[4]) {
+    float4 r;
+    r.x = __builtin_fmaf(x[3].x, w[3], __builtin_fmaf(x[2].x, w[2], __builtin_fmaf(x[1].x, w[1], x[0].x * w[0])));
+    r.y = __builtin_fmaf(x[3].y, w[3], __builtin_fmaf(x[2].y, w[2], __builtin_fmaf(x[1].y, w[1], x[0].y * w[0])));
+    r.z = __builtin_fmaf(x[3].z, w[3], __builtin_fmaf(x[2].z, w[2], __builtin_fmaf(x[1].z, w[1], x[0].z * w[0])));
+    r.w = __builtin_fmaf(x[3].w, w[3], __builtin_fmaf(x[2].w, w[2], __builtin_fmaf(x[1].w, w[1], x[0].w * w[0])));
+    return r;
+}
+
 // FUSED = false: ATen's operation order (nw*w + ne*w + sw*w + se*w, every product and sum rounded), used by the
-// reference-order variant.  FUSED = true: the same blend as 1 multiply + 3 fused multiply-adds per component (16
-// instead of 28 VALU instructions per float4) for the projected-latent variant, which is held to the 1e-4
+// reference-order variant.  FUSED = true: tap_blend (16 instead of 28 VALU instructions per float4) for the
+// projected-latent variant, which is held to the 1e-4
 // tolerance and not to an operation order.
 template <class C, int B = 0, bool FUSED = false, int NB>
 __device__ __forceinline__ void gather_commit(const GatherTaps<C, NB>& g, float4* act_win, int wave, int lane) {
@@ -706,10 +722,7 @@ __device__ __forceinline__ void gather_commit(const GatherTaps<C, NB>& g, float4
         const float4(&x)[4] = g.x[B][i];
         float4 r;
         if (FUSED) {
-            r.x = __builtin_fmaf(x[3].x, g.w[3], __builtin_fmaf(x[2].x, g.w[2], __builtin_fmaf(x[1].x, g.w[1], x[0].x * g.w[0])));
-            r.y = __builtin_fmaf(x[3].y, g.w[3], __builtin_fmaf(x[2].y, g.w[2], __builtin_fmaf(x[1].y, g.w[1], x[0].y * g.w[0])));
-            r.z = __builtin_fmaf(x[3].z, g.w[3], __builtin_fmaf(x[2].z, g.w[2], __builtin_fmaf(x[1].z, g.w[1], x[0].z * g.w[0])));
-            r.w = __builtin_fmaf(x[3].w, g.w[3], __builtin_fmaf(x[2].w, g.w[2], __builtin_fmaf(x[1].w, g.w[1], x[0].w * g.w[0])));
+            r = tap_blend(x, g.w);
         } else {
             r.x = ((x[0].x * g.w[0] + x[1].x * g.w[1]) + x[2].x * g.w[2]) + x[3].x * g.w[3];
             r.y = ((x[0].y * g.w[0] + x[1].y * g.w[1]) + x[2].y * g.w[2]) + x[3].y * g.w[3];
@@ -720,5 +733,38 @@ __device__ __forceinline__ void gather_commit(const GatherTaps<C, NB>& g, float4
     }
 }
 
+// XCD-aware tile order of the persistent MLP kernels: workgroups are dispatched round-robin over the 8 XCDs (XCD =
+// blockIdx % 8), each with its own L2.  XCD x walks the contiguous tile range [x*chunk, (x+1)*chunk): the 32 workgroups
+// of an XCD then work on neighbouring rays at any moment, whose samples project onto overlapping pixels of the
+// (projected) latent, instead of on every 8th ray.  A grid that is no multiple of 8 walks tiles blockIdx, + gridDim, ...
+struct TileWalk {
+    long long first, last;
+    int step;
+};
+__device__ __forceinline__ TileWalk tile_walk(int n_tiles) {
+#ifndef PNY_NO_XCD_ORDER
+    const bool xcd_order = (gridDim.x & 7) == 0;
+#else
+    const bool xcd_order = false;
+#endif
+    const long long chunk = xcd_order ? (n_tiles + 7) / 8 : n_tiles;
+    TileWalk t;
+    t.first = xcd_order ? (long long)(blockIdx.x & 7) * chunk + (blockIdx.x >> 3) : blockIdx.x;
+    t.last = xcd_order ? ((long long)((blockIdx.x & 7) + 1) * chunk < n_tiles ? (long long)((blockIdx.x & 7) + 1) * chunk : (long long)n_tiles)
+                       : (long long)n_tiles;
+    t.step = xcd_order ? (int)(gridDim.x >> 3) : (int)gridDim.x;
+    return t;
+}
+
+// output head on lin_out's row o (reference models.py:312-317): sigmoid on rgb, relu on sigma; YOLO mode keeps the raw rows
+__device__ __forceinline__ float output_head(float sum, int o, int yolo) {
+    if (!yolo) {
+        if (o < 3)
+            sum = 1.0f / (1.0f + expf(-sum));
+        else if (o == 3)
+            sum = fmaxf(sum, 0.f);
+    }
+    return sum;
+}
 
 }  // namespace pny

@@ -98,32 +98,6 @@ __device__ __forceinline__ unsigned long long h2now() {
 #define HS_LAP(cat)
 #endif
 
-// Timing-only experiment (-DPNY_H2_EXP_STAGGER=<cycles>, wrong results): the workgroup barrier replaced by a barrier among the
-// four waves of a half (waves 0-3 / 4-7: the two waves of a SIMD are in different halves), the second half started <cycles>
-// late -- an upper bound for what running the two waves of a SIMD out of phase (one's epilogue / gather under the other's
-// GEMM) can return.  Cross-half dependencies are ignored, so the values are garbage; every address stays valid (both halves
-// write the tap table).
-#ifdef PNY_H2_EXP_STAGGER
-__device__ __forceinline__ void h2group_sync(unsigned* cnt, unsigned& epoch, int wave, int lane) {
-    epoch += 4;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (lane == 0) __hip_atomic_fetch_add(cnt + (wave >> 2), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    while (__hip_atomic_load(cnt + (wave >> 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < epoch) __builtin_amdgcn_s_sleep(1);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-#define H2SYNC() h2group_sync(sync_cnt, sync_epoch, wave, lane)
-#define H2SYNC_P() H2SYNC()
-#elif defined(PNY_H2_EXP_NOSYNC)
-// Timing-only experiment (wrong results): every workgroup barrier except the two around the prologue (the tap table must be
-// valid: it holds addresses) removed -- the waves of a workgroup free-run through a view's GEMMs, epilogues and gathers.  An
-// UPPER bound for what replacing the barriers by data-flow flags (rows written / rows read) can return.
-#define H2SYNC()
-#define H2SYNC_P() __syncthreads()
-#else
-#define H2SYNC() __syncthreads()
-#define H2SYNC_P() H2SYNC()
-#endif
-
 // The 8-byte slot of feature quad (row, half) = (feature / 8, (feature / 4) & 1) of sample m in plane p is at byte
 //     (2 row + p) * ROW_BYTES + 16 m + 8 half.
 
@@ -140,15 +114,24 @@ __device__ __forceinline__ void h2group_sync(unsigned* cnt, unsigned& epoch, int
 // tools/check_store_hazard.py guards the built library against the pattern).
 __device__ __forceinline__ void stash_store(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, float a, float b, float c, float d) {
     const f32x4 v = {a, b, c, d};
-#ifdef PNY_H2_ANOM_SOFF   // diagnosis only (profiles/r03_anomalies.md): the form the compiler does not guard -- slot offset in the SGPR soffset
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, voff, __builtin_amdgcn_readfirstlane(soff), 0);
-#ifdef PNY_H2_ANOM_SOFF_NOP   // ... and the one wait state the compiler does not insert for this form, by hand
-    asm volatile("s_nop 0" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-#else
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, voff + soff, 0, 0);
-#endif
+}
+
+// put_planes (mlp_h2_core.h) with the running maximum of the f16-range guard (include/pnyolo.h pny_model_range_status): a
+// value >= 65520 rounds to an f16 infinity.  SIGNED: the values may be negative (lin_in's inputs); relu outputs are compared
+// as they are (two v_max3_f32 per quad).
+template <bool SIGNED = false>
+__device__ __forceinline__ void h2put_planes(char* slot, float r0, float r1, float r2, float r3, float& rmax) {
+    if constexpr (SIGNED)
+        rmax = fmaxf(fmaxf(rmax, fmaxf(fabsf(r0), fabsf(r1))), fmaxf(fabsf(r2), fabsf(r3)));
+    else
+        rmax = fmaxf(fmaxf(rmax, fmaxf(r0, r1)), fmaxf(r2, r3));
+    put_planes(slot, r0, r1, r2, r3);
+}
+// ... and the guard's tail: one branch per call site, the maximum local to the call (a register kept across the GEMM loops
+// costs spills there: 60 -> 169 spilled VGPRs when it was a kernel-wide running maximum)
+__device__ __forceinline__ void range_check(float rmax, unsigned* range_flag) {
+    if (__builtin_expect(!(rmax < 65520.0f), 0)) range_report(range_flag, 1u);
 }
 
 // STASH (training forward): relu(acc + ...) is also written in fp32 to `stash` in the [feature/4][sample] float4 tile layout of
@@ -160,10 +143,7 @@ __device__ __forceinline__ void h2epilogue(f32x16 (&acc)[h2::NT][h2::MT], const 
     const unsigned stash_lane = (unsigned)(((8 * NT * wave + (lane >> 5)) * TM + (lane & 31)) * 16);
     const int m0 = lane & 31, hh = lane >> 5;
     const float* bl = bias + 32 * NT * wave + 4 * hh;
-    // f16-range guard (include/pnyolo.h pny_model_range_status): the largest value this call hands to the f16 split; a relu
-    // output >= 65520 rounds to an f16 infinity.  Local to the call (a register kept across the GEMM loops costs spills
-    // there: 60 -> 169 spilled VGPRs when it was a kernel-wide running maximum); two v_max per quad, one branch per call.
-    float rmax = 0.f;
+    float rmax = 0.f;   // f16-range guard: the largest value this call hands to the planes
     // accumulator quad (nt, q) of this lane = features 32 NT wave + 32 nt + 8 q + 4 hh + 0..3: row 4 NT wave + 4 nt + q, half hh
     char* base = planes + (4 * NT * wave) * (2 * ROW_BYTES) + m0 * 16 + 8 * hh;
     // the LDS reads of a (nt, mt) tile -- bias quads, staged projection -- are issued together ahead of its arithmetic
@@ -188,7 +168,6 @@ __device__ __forceinline__ void h2epilogue(f32x16 (&acc)[h2::NT][h2::MT], const 
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 char* s0 = base + (4 * nt + q) * (2 * ROW_BYTES) + 32 * mt * 16;
-                char* s1 = s0 + ROW_BYTES;
                 float x0 = acc[nt][mt][4 * q + 0] + b[q].x, x1 = acc[nt][mt][4 * q + 1] + b[q].y;
                 float x2 = acc[nt][mt][4 * q + 2] + b[q].z, x3 = acc[nt][mt][4 * q + 3] + b[q].w;
                 if (ADDZ) {
@@ -202,23 +181,12 @@ __device__ __forceinline__ void h2epilogue(f32x16 (&acc)[h2::NT][h2::MT], const 
                 acc[nt][mt][4 * q + 2] = x2;
                 acc[nt][mt][4 * q + 3] = x3;
                 const float r0 = relu1(x0), r1 = relu1(x1), r2 = relu1(x2), r3 = relu1(x3);
-                rmax = fmaxf(fmaxf(rmax, fmaxf(r0, r1)), fmaxf(r2, r3));   // f16-range guard (two v_max3_f32 per quad)
                 if constexpr (STASH) stash_store(stash, stash_lane, stash_off + (unsigned)(((8 * nt + 2 * q) * TM + 32 * mt) * 16), r0, r1, r2, r3);
-#if PNY_H2_PLANES == 1
-                (void)s1;
-                *reinterpret_cast<h4*>(s0) = cvt4(r0, r1, r2, r3);
-#else
-                h4 p0, p1;
-                split4(r0, r1, r2, r3, p0, p1);
-                *reinterpret_cast<h4*>(s0) = p0;
-                *reinterpret_cast<h4*>(s1) = p1;
-#endif
+                h2put_planes(s0, r0, r1, r2, r3, rmax);
             }
         }
     }
-#ifndef PNY_H2_EXP_NOSYNC   // (the timing experiment computes on garbage: no reports to the host word)
-    if (__builtin_expect(!(rmax < 65520.0f), 0)) range_report(range_flag, 1u);
-#endif
+    range_check(rmax, range_flag);
 }
 
 // Cross-view running sum slab of the workgroup (layout of mlp_core.h slab_store / slab_load: register quad q of tile
@@ -341,21 +309,11 @@ __device__ __forceinline__ void h2mean_planes(const f32x16 (&net)[h2::NT][h2::MT
                 char* s0 = base + (4 * nt + q) * (2 * ROW_BYTES) + 32 * mt * 16;
                 const float r0 = net[nt][mt][4 * q + 0] * rns, r1 = net[nt][mt][4 * q + 1] * rns;
                 const float r2 = net[nt][mt][4 * q + 2] * rns, r3 = net[nt][mt][4 * q + 3] * rns;
-                rmax = fmaxf(fmaxf(rmax, fmaxf(r0, r1)), fmaxf(r2, r3));
-#if PNY_H2_PLANES == 1
-                *reinterpret_cast<h4*>(s0) = cvt4(r0, r1, r2, r3);
-#else
-                h4 p0, p1;
-                split4(r0, r1, r2, r3, p0, p1);
-                *reinterpret_cast<h4*>(s0) = p0;
-                *reinterpret_cast<h4*>(s0 + ROW_BYTES) = p1;
-#endif
+                h2put_planes(s0, r0, r1, r2, r3, rmax);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) h[nt][mt][4 * q + i] = h[nt][mt][4 * q + i] * rns;
             }
-#ifndef PNY_H2_EXP_NOSYNC
-    if (__builtin_expect(!(rmax < 65520.0f), 0)) range_report(range_flag, 1u);
-#endif
+    range_check(rmax, range_flag);
 }
 
 // gather_commit (mlp_core.h) for the staging layout above: chunk c covers feature quads [32 c, 32 c + 32)
@@ -369,20 +327,16 @@ __device__ __forceinline__ void h2gather_commit(const GatherTaps<h2::C, 2>& g, c
 #pragma unroll
     for (int i = 0; i < GatherTaps<C>::QPW; ++i) {
         const int qb = wave / NMB + i * QSTEP;
-        const float4(&x)[4] = g.x[B][i];
-        float2 lo, hi;
-        lo.x = __builtin_fmaf(x[3].x, g.w[3], __builtin_fmaf(x[2].x, g.w[2], __builtin_fmaf(x[1].x, g.w[1], x[0].x * g.w[0])));
-        lo.y = __builtin_fmaf(x[3].y, g.w[3], __builtin_fmaf(x[2].y, g.w[2], __builtin_fmaf(x[1].y, g.w[1], x[0].y * g.w[0])));
-        hi.x = __builtin_fmaf(x[3].z, g.w[3], __builtin_fmaf(x[2].z, g.w[2], __builtin_fmaf(x[1].z, g.w[1], x[0].z * g.w[0])));
-        hi.y = __builtin_fmaf(x[3].w, g.w[3], __builtin_fmaf(x[2].w, g.w[2], __builtin_fmaf(x[1].w, g.w[1], x[0].w * g.w[0])));
+        const float4 r = tap_blend(g.x[B][i], g.w);
         char* s0 = base + (4 * qb) * (2 * ROW_BYTES);
-        *reinterpret_cast<float2*>(s0) = lo;
-        *reinterpret_cast<float2*>(s0 + ROW_BYTES) = hi;
+        *reinterpret_cast<float2*>(s0) = make_float2(r.x, r.y);
+        *reinterpret_cast<float2*>(s0 + ROW_BYTES) = make_float2(r.z, r.w);
     }
 }
 
 // per (view, tile) prologue: the lin_in B operand (positional code, view dirs) as f16 planes in rows 0..7 of each plane, and
-// the tap table; the arithmetic of prologue<C>() in mlp_core.h
+// the tap table; the arithmetic is prologue<C>()'s (mlp_core.h).  STASH: the operand also goes to the stash in fp32
+// ([feature/4][sample]), and a second table holds the same taps addressing the latent itself (pixel x L).
 template <bool STASH>
 __device__ __forceinline__ void h2prologue(const MlpArgs& a, int v, long long tile, char* planes, float4* tap_tab, int tid, unsigned* range_flag,
                                            __amdgpu_buffer_rsrc_t stash = __amdgpu_buffer_rsrc_t(), unsigned stash_xin = 0, float4* tap_raw = nullptr) {
@@ -395,73 +349,26 @@ __device__ __forceinline__ void h2prologue(const MlpArgs& a, int v, long long ti
     load_point(a, s, p, d);
     const Cam cam = a.cams[tile_view_base(a, tile * TM) + v];
     float xr[3], xc[3], vd[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        xr[i] = cam.w2c[4 * i + 0] * p[0] + cam.w2c[4 * i + 1] * p[1] + cam.w2c[4 * i + 2] * p[2];
-        xc[i] = xr[i] + cam.w2c[4 * i + 3];
-        vd[i] = cam.w2c[4 * i + 0] * d[0] + cam.w2c[4 * i + 1] * d[1] + cam.w2c[4 * i + 2] * d[2];
-    }
+    camera_point(cam, p, d, xr, xc, vd);
     float rmax = 0.f;   // f16-range guard: lin_in's inputs (coordinates, view directions) go through the same split
     for (int g = part; g < D_IN_PAD / 4; g += NPART) {
         const float e0 = input_entry(4 * g + 0, xr, vd, a.freq_factor, a.num_freqs), e1 = input_entry(4 * g + 1, xr, vd, a.freq_factor, a.num_freqs);
         const float e2 = input_entry(4 * g + 2, xr, vd, a.freq_factor, a.num_freqs), e3 = input_entry(4 * g + 3, xr, vd, a.freq_factor, a.num_freqs);
-        rmax = fmaxf(fmaxf(rmax, fmaxf(fabsf(e0), fabsf(e1))), fmaxf(fabsf(e2), fabsf(e3)));
-#if PNY_H2_PLANES == 1
         if constexpr (STASH) stash_store(stash, (unsigned)((g * TM + m) * 16), stash_xin, e0, e1, e2, e3);
-        char* s0 = planes + (g >> 1) * (2 * ROW_BYTES) + m * 16 + 8 * (g & 1);
-        *reinterpret_cast<h4*>(s0) = cvt4(e0, e1, e2, e3);
-#else
-        h4 p0, p1;
-        split4(e0, e1, e2, e3, p0, p1);
-        if constexpr (STASH) stash_store(stash, (unsigned)((g * TM + m) * 16), stash_xin, e0, e1, e2, e3);   // lin_in's B operand, [feature/4][sample]
-        char* s0 = planes + (g >> 1) * (2 * ROW_BYTES) + m * 16 + 8 * (g & 1);
-        *reinterpret_cast<h4*>(s0) = p0;
-        *reinterpret_cast<h4*>(s0 + ROW_BYTES) = p1;
-#endif
+        h2put_planes<true>(planes + (g >> 1) * (2 * ROW_BYTES) + m * 16 + 8 * (g & 1), e0, e1, e2, e3, rmax);
     }
-    if (__builtin_expect(!(rmax < 65520.0f), 0)) range_report(range_flag, 1u);
-#ifdef PNY_H2_EXP_STAGGER
-    if (part == NPART - 1 || part == NPART / 2 - 1) {
-#else
+    range_check(rmax, range_flag);
     if (part == NPART - 1) {
-#endif
-        float ux, uy;
-        if (!a.yolo) {
-            ux = -xc[0] / xc[2];
-            uy = -xc[1] / xc[2];
-        } else {
-            ux = xc[0] / xc[2];
-            uy = xc[1] / xc[2];
-        }
-        ux = ux * cam.fx + cam.cx;
-        uy = uy * cam.fy + cam.cy;
-        const float gx = ux * a.sx - 1.0f, gy = uy * a.sy - 1.0f;
-        const float ix = ((gx + 1.0f) / 2.0f) * (float)(a.Wl - 1);
-        const float iy = ((gy + 1.0f) / 2.0f) * (float)(a.Hl - 1);
-        const float x0 = floorf(ix), y0 = floorf(iy);
-        const float x1 = x0 + 1.0f, y1 = y0 + 1.0f;
-        float wgt[4] = {(x1 - ix) * (y1 - iy), (ix - x0) * (y1 - iy), (x1 - ix) * (iy - y0), (ix - x0) * (iy - y0)};
-        const float xs[4] = {x0, x1, x0, x1};
-        const float ys[4] = {y0, y0, y1, y1};
-        const bool cull = a.yolo && !(xc[2] < 0.0f);
-        int offs[4], raw[4];
+        int pix[4], offs[4];
+        float wgt[4];
+        pixel_taps(a, cam, xc, 1, pix, wgt);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const bool ok = (xs[k] >= 0.f) && (xs[k] <= (float)(a.Wl - 1)) && (ys[k] >= 0.f) && (ys[k] <= (float)(a.Hl - 1));
-            offs[k] = raw[k] = 0;
-            if (ok) {
-                offs[k] = ((int)ys[k] * a.Wl + (int)xs[k]) * a.tap_stride;
-                raw[k] = ((int)ys[k] * a.Wl + (int)xs[k]) * a.L;
-            } else {
-                wgt[k] = wgt[k] * 0.0f;
-            }
-            if (cull || (a.yolo && (wgt[k] != wgt[k]))) wgt[k] = 0.0f;
-        }
-        tap_tab[2 * m] = make_float4(__int_as_float(offs[0]), __int_as_float(offs[1]), __int_as_float(offs[2]), __int_as_float(offs[3]));
-        tap_tab[2 * m + 1] = make_float4(wgt[0], wgt[1], wgt[2], wgt[3]);
-        if constexpr (STASH) {   // the same taps addressing the latent itself (pixel x L)
-            tap_raw[2 * m] = make_float4(__int_as_float(raw[0]), __int_as_float(raw[1]), __int_as_float(raw[2]), __int_as_float(raw[3]));
-            tap_raw[2 * m + 1] = make_float4(wgt[0], wgt[1], wgt[2], wgt[3]);
+        for (int k = 0; k < 4; ++k) offs[k] = pix[k] * a.tap_stride;
+        tap_record(tap_tab, m, offs, wgt);
+        if constexpr (STASH) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) offs[k] = pix[k] * a.L;
+            tap_record(tap_raw, m, offs, wgt);
         }
     }
 }
@@ -479,16 +386,6 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
     float* bias_tab = reinterpret_cast<float*>(smem_raw + ACT_BYTES + TAP_BYTES);   // [b_in, b_fc0[0], b_fc1[0], b_fc0[1], ...][512]
     float4* tap_raw = reinterpret_cast<float4*>(smem_raw + lds_bytes(a.n_blocks));   // STASH only: taps addressing the raw latent
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef PNY_H2_EXP_STAGGER
-    unsigned* sync_cnt = reinterpret_cast<unsigned*>(smem_raw + lds_bytes(a.n_blocks) + TAP_BYTES);
-    unsigned sync_epoch = 0;
-    if (tid < 2) sync_cnt[tid] = 0;
-    __syncthreads();
-    if (wave >= 4) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-        while (__builtin_amdgcn_s_memtime() - t0 < (unsigned long long)(PNY_H2_EXP_STAGGER)) __builtin_amdgcn_s_sleep(8);
-    }
-#endif
     const SlabRef slab = {__builtin_amdgcn_make_buffer_rsrc(a.scratch + (size_t)blockIdx.x * (TM * HID), 0, TM * HID * 4, 0x00020000),
                           (unsigned)((wave * (NT * MT * 16 * 64) + 4 * lane) * 4)};
     // The view-mean order (header comment) of the non-stashing two-plane instantiations; -DPNY_H2_PER_VIEW_FC1 (diagnostic
@@ -505,13 +402,8 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
     const int nvb = a.combine_layer < nb ? a.combine_layer : nb;   // >= 1 (the host only selects this kernel with a projection)
     const WStream ws = wstream(a, lane);
     const H2Seg s_in = h2seg(ws, a.h2_in, D_IN_PAD / 16, wave);
-#ifdef PNY_H2_EXP_FOOT   // timing only: every 512x512 layer streams block 0's fc_0 image (1 MiB footprint; wrong results)
-    auto fc0seg = [&](int b) { return h2seg(ws, a.h2_fc0[0], HID / 16, wave); };
-    auto fc1seg = [&](int b) { return h2seg(ws, a.h2_fc0[0], HID / 16, wave); };
-#else
     auto fc0seg = [&](int b) { return h2seg(ws, a.h2_fc0[b], HID / 16, wave); };
     auto fc1seg = [&](int b) { return h2seg(ws, a.h2_fc1[b], HID / 16, wave); };
-#endif
     // bias applied at the entry of block b (b = n_blocks: before lin_out): b_in, or the previous block's b_fc1 -- the
     // packing (pack.hip PACK_ADD2) has folded the block's lin_z bias into either
     auto entry_bias = [&](int b) -> const float* {
@@ -538,14 +430,8 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
         }
     }
 
-    const bool xcd_order = (gridDim.x & 7) == 0;   // see mlp.hip
-    const long long t_chunk = xcd_order ? (a.n_tiles + 7) / 8 : a.n_tiles;
-    const long long t_first = xcd_order ? (long long)(blockIdx.x & 7) * t_chunk + (blockIdx.x >> 3) : blockIdx.x;
-    const long long t_last = xcd_order ? ((long long)((blockIdx.x & 7) + 1) * t_chunk < a.n_tiles
-                                              ? (long long)((blockIdx.x & 7) + 1) * t_chunk : (long long)a.n_tiles)
-                                       : (long long)a.n_tiles;
-    const int t_step = xcd_order ? (int)(gridDim.x >> 3) : (int)gridDim.x;
-    for (long long tile = t_first; tile < t_last; tile += t_step) {
+    const TileWalk tw = tile_walk(a.n_tiles);   // XCD-aware order (mlp_core.h)
+    for (long long tile = tw.first; tile < tw.last; tile += tw.step) {
         f32x16 h[NT][MT];
         f32x16 net[NT][MT];
         GatherTaps<C, 2> g;   // taps of the current view; two chunks of projected channels in flight
@@ -559,11 +445,11 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
         auto block_tail = [&](int blk, const H2Seg& after, bool slab_in, int next_c0, unsigned stash_net) {
             HS_T0();
             h2zero<NT, MT>(net);
-            H2SYNC();
+            __syncthreads();
             HS_LAP(HS_EPI_WAIT);
             h2gemm(net, ring, ws, fc0seg(blk), fc1seg(blk), planes, lane);
             HS_LAP(HS_GEMM);
-            H2SYNC();
+            __syncthreads();
             HS_LAP(HS_EPI_WAIT);
             h2epilogue<false, STASH>(net, fc0_bias(blk), planes, wave, lane, a.range_flag, xr, stash_net);
             // three exclusive continuations (the running sum of the other views and the prefetched chunk both want the
@@ -571,7 +457,7 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
             if (!VIEW_MEAN && slab_in) {   // (per-view order only: the view-mean order sums in mean_tail)
                 h2slab_load(net, slab);
                 HS_LAP(HS_EPI);
-                H2SYNC();
+                __syncthreads();
                 HS_LAP(HS_EPI_WAIT);
                 h2gemm(h, ring, ws, fc1seg(blk), after, planes, lane);
                 HS_LAP(HS_GEMM);
@@ -583,13 +469,13 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
                         for (int r = 0; r < 16; ++r) h[nt][mt][r] = net[nt][mt][r] + h[nt][mt][r];
             } else if (next_c0 >= 0) {
                 HS_LAP(HS_EPI);
-                H2SYNC();
+                __syncthreads();
                 HS_LAP(HS_EPI_WAIT);
                 h2gemm(h, ring, ws, fc1seg(blk), after, planes, lane, [&]() { gather_issue<C, 0>(g, next_c0, wave); });
                 HS_LAP(HS_GEMM);
             } else {
                 HS_LAP(HS_EPI);
-                H2SYNC();
+                __syncthreads();
                 HS_LAP(HS_EPI_WAIT);
                 h2gemm(h, ring, ws, fc1seg(blk), after, planes, lane);
                 HS_LAP(HS_GEMM);
@@ -603,10 +489,10 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
             const unsigned x_view = STASH ? stash_bytes((unsigned)v * (unsigned)a.lay.x_view) : 0u;
             auto act_slot = [&](int i) { return x_view + stash_bytes((unsigned)a.lay.o_act + (unsigned)i * (unsigned)STASH_SLOT); };
             HS_T0();
-            H2SYNC_P();
+            __syncthreads();
             h2prologue<STASH>(a, v, tile, planes, tap_tab, tid, a.range_flag, xr, x_view + stash_bytes((unsigned)a.lay.o_in), tap_raw);
             h2zero<NT, MT>(h);
-            H2SYNC_P();
+            __syncthreads();
             if constexpr (STASH) {
                 // z = the interpolated latent of this view (reference encoder.py:101), the B operand of lin_z's weight
                 // gradient: gathered from the latent itself, 128 channels at a time, two chunks in flight, written straight
@@ -618,11 +504,7 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
                 auto put = [&](const float4(&x)[4][4], int c) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        float4 r;
-                        r.x = __builtin_fmaf(x[i][3].x, g.w[3], __builtin_fmaf(x[i][2].x, g.w[2], __builtin_fmaf(x[i][1].x, g.w[1], x[i][0].x * g.w[0])));
-                        r.y = __builtin_fmaf(x[i][3].y, g.w[3], __builtin_fmaf(x[i][2].y, g.w[2], __builtin_fmaf(x[i][1].y, g.w[1], x[i][0].y * g.w[0])));
-                        r.z = __builtin_fmaf(x[i][3].z, g.w[3], __builtin_fmaf(x[i][2].z, g.w[2], __builtin_fmaf(x[i][1].z, g.w[1], x[i][0].z * g.w[0])));
-                        r.w = __builtin_fmaf(x[i][3].w, g.w[3], __builtin_fmaf(x[i][2].w, g.w[2], __builtin_fmaf(x[i][1].w, g.w[1], x[i][0].w * g.w[0])));
+                        const float4 r = tap_blend(x[i], g.w);
                         stash_store(xr, zlane, xz + (unsigned)((32 * c + 8 * i) * TM * 16), r.x, r.y, r.z, r.w);
                     }
                 };
@@ -649,15 +531,7 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
                 // from here two chunks are in flight: the loads of chunk c + 1 are issued before chunk c is blended.
                 const int cb = blk * HID;
                 HS_LAP(HS_GATHER);
-#ifdef PNY_H2_ANOM_VMCNT0   // diagnosis of the packed-f32 anomaly: every load landed before chunk 0 is blended?
-                __builtin_amdgcn_sched_barrier(0);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-#endif
-                H2SYNC();  // every wave is done reading the planes (previous GEMM)
-#ifdef PNY_H2_ANOM_SCHEDBAR   // diagnosis: nothing of the blend may be scheduled above the barrier
-                __builtin_amdgcn_sched_barrier(0);
-#endif
+                __syncthreads();  // every wave is done reading the planes (previous GEMM)
                 HS_LAP(HS_GATHER_WAIT);
                 gather_issue<C, 1>(g, cb + GCH, wave);
                 __builtin_amdgcn_sched_barrier(0);
@@ -670,7 +544,7 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
                 h2gather_commit<0>(g, planes, 2, wave, lane);
                 h2gather_commit<1>(g, planes, 3, wave, lane);
                 HS_LAP(HS_GATHER);
-                H2SYNC();  // projection visible
+                __syncthreads();  // projection visible
                 HS_LAP(HS_GATHER_WAIT);
                 h2epilogue<true, STASH>(h, entry_bias(blk), planes, wave, lane, a.range_flag, xr, act_slot(2 * blk));
                 HS_LAP(HS_EPI);
@@ -686,7 +560,7 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
                 const bool last = v + 1 == a.NS;
                 HS_T0();
                 h2zero<NT, MT>(net);
-                H2SYNC();
+                __syncthreads();
                 HS_LAP(HS_EPI_WAIT);
                 h2gemm(net, ring, ws, fc0seg(blk), last ? fc1seg(blk) : s_in, planes, lane);
                 HS_LAP(HS_GEMM);
@@ -696,11 +570,11 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
                     return;
                 }
                 HS_LAP(v > 0 ? HS_SLAB : HS_EPI);
-                H2SYNC();   // every wave is done reading the planes (fc_0 GEMM)
+                __syncthreads();   // every wave is done reading the planes (fc_0 GEMM)
                 HS_LAP(HS_EPI_WAIT);
                 h2mean_planes(net, h, 1.0f / (float)a.NS, planes, wave, lane, a.range_flag);
                 HS_LAP(HS_EPI);
-                H2SYNC();
+                __syncthreads();
                 HS_LAP(HS_EPI_WAIT);
                 h2gemm(h, ring, ws, fc1seg(blk), after_view, planes, lane);
                 HS_LAP(HS_GEMM);
@@ -738,7 +612,7 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
         auto post_slot = [&](int i) { return stash_bytes((unsigned)a.lay.x_post + (unsigned)i * (unsigned)STASH_SLOT); };
         for (int blk = nvb; blk < nb; ++blk) {
             HS_T0();
-            H2SYNC();
+            __syncthreads();
             HS_LAP(HS_EPI_WAIT);
             h2epilogue<false, STASH>(h, entry_bias(blk), planes, wave, lane, a.range_flag, xr, post_slot(2 * (blk - nvb)));
             HS_LAP(HS_EPI);
@@ -746,9 +620,9 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
         }
         // out = lin_out(relu(h + b_fc1[last])) (reference resnetfc.py:185) + output head (models.py:312-317)
         HS_T0();
-        H2SYNC();
+        __syncthreads();
         h2epilogue<false, STASH>(h, entry_bias(nb), planes, wave, lane, a.range_flag, xr, post_slot(2 * (nb - nvb)));
-        H2SYNC();
+        __syncthreads();
         for (int idx = tid; idx < a.d_out * TM; idx += THREADS) {
             const int o = idx / TM, m = idx % TM;
             const float4* wrow = reinterpret_cast<const float4*>(a.w.w_out + (size_t)o * HID);
@@ -756,39 +630,29 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
 #pragma unroll 4
             for (int kg = 0; kg < HID / 8; ++kg) {
                 const h8 x0 = *reinterpret_cast<const h8*>(planes + kg * (2 * ROW_BYTES) + m * 16);
-#if PNY_H2_PLANES == 1
                 const float4 wa = wrow[2 * kg], wb = wrow[2 * kg + 1];
-                sum += (float)x0[0] * wa.x;
-                sum += (float)x0[1] * wa.y;
-                sum += (float)x0[2] * wa.z;
-                sum += (float)x0[3] * wa.w;
-                sum += (float)x0[4] * wb.x;
-                sum += (float)x0[5] * wb.y;
-                sum += (float)x0[6] * wb.z;
-                sum += (float)x0[7] * wb.w;
-#else
-                const h8 x1 = *reinterpret_cast<const h8*>(planes + kg * (2 * ROW_BYTES) + ROW_BYTES + m * 16);
-                const float4 wa = wrow[2 * kg], wb = wrow[2 * kg + 1];
-                sum += ((float)x0[0] + (float)x1[0]) * wa.x;
-                sum += ((float)x0[1] + (float)x1[1]) * wa.y;
-                sum += ((float)x0[2] + (float)x1[2]) * wa.z;
-                sum += ((float)x0[3] + (float)x1[3]) * wa.w;
-                sum += ((float)x0[4] + (float)x1[4]) * wb.x;
-                sum += ((float)x0[5] + (float)x1[5]) * wb.y;
-                sum += ((float)x0[6] + (float)x1[6]) * wb.z;
-                sum += ((float)x0[7] + (float)x1[7]) * wb.w;
-#endif
+                if constexpr (PL == 1) {
+                    sum += (float)x0[0] * wa.x;
+                    sum += (float)x0[1] * wa.y;
+                    sum += (float)x0[2] * wa.z;
+                    sum += (float)x0[3] * wa.w;
+                    sum += (float)x0[4] * wb.x;
+                    sum += (float)x0[5] * wb.y;
+                    sum += (float)x0[6] * wb.z;
+                    sum += (float)x0[7] * wb.w;
+                } else {
+                    const h8 x1 = *reinterpret_cast<const h8*>(planes + kg * (2 * ROW_BYTES) + ROW_BYTES + m * 16);
+                    sum += ((float)x0[0] + (float)x1[0]) * wa.x;
+                    sum += ((float)x0[1] + (float)x1[1]) * wa.y;
+                    sum += ((float)x0[2] + (float)x1[2]) * wa.z;
+                    sum += ((float)x0[3] + (float)x1[3]) * wa.w;
+                    sum += ((float)x0[4] + (float)x1[4]) * wb.x;
+                    sum += ((float)x0[5] + (float)x1[5]) * wb.y;
+                    sum += ((float)x0[6] + (float)x1[6]) * wb.z;
+                    sum += ((float)x0[7] + (float)x1[7]) * wb.w;
+                }
             }
-            sum += a.w.b_out[o];
-            if (!a.yolo) {
-                if (o < 3)
-                    sum = 1.0f / (1.0f + expf(-sum));
-                else if (o == 3)
-                    sum = fmaxf(sum, 0.f);
-            }
-#if defined(PNY_H2_EXP_STAGGER) || defined(PNY_H2_EXP_NOSYNC)
-            if (!(fabsf(sum) < 1e3f)) sum = 0.5f;   // (timing experiment: keep the garbage finite so that the fine pass samples real points)
-#endif
+            sum = output_head(sum + a.w.b_out[o], o, a.yolo);
             const long long s = tile * TM + m;
             if (s < a.n_points) a.out[s * a.d_out + o] = sum;
         }
@@ -808,11 +672,7 @@ bool mlp_h2_supports(int n_blocks, int combine_layer) { return n_blocks <= h2::M
 
 template <bool STASH>
 static void launch_mlp_h2_t(const MlpArgs& a, int grid, hipStream_t st) {
-#ifdef PNY_H2_EXP_STAGGER
-    const int extra = h2::TAP_BYTES + 64;
-#else
     const int extra = STASH ? h2::TAP_BYTES : 0;   // second tap table
-#endif
     static LdsLimit lds;
     (void)lds.raise(h2::lds_bytes(h2::MAX_NB) + extra, PNY_H2_KERNEL<STASH>);
 #ifdef PNY_H2_STAMP

@@ -86,23 +86,7 @@ __device__ __forceinline__ void h2ring_fill(H2Ring& r, const WStream& ws, const 
 // acc += W_slice . act over segment `cur` (its 16-k steps a multiple of the ring depth); leaves the ring holding the first
 // WD - 1 steps of `next`.  Per step and accumulator tile: x1 w1 + x2 w1 + x1 w2.  Static ring slots as in gemm_run
 // (mlp_core.h): slot d is consumed by step j + d while slot d - 1 is refilled with step j + d - 1 + WD.
-// Timing-only experiment (-DPNY_H2_EXP_MFMA16, wrong results): every 32x32x16 MFMA replaced by two 16x16x32 MFMAs on the
-// same operand registers (the same FLOPs and operand traffic) -- what the chip's clock does with the other MFMA shape.
-#ifdef PNY_H2_EXP_MFMA16
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x16 h2mfma(h8 a, h8 b, f32x16 c) {
-    f32x4v c0 = {c[0], c[1], c[2], c[3]}, c1 = {c[4], c[5], c[6], c[7]};
-    c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c1, 0, 0, 0);
-    c[0] = c0[0]; c[1] = c0[1]; c[2] = c0[2]; c[3] = c0[3];
-    c[4] = c1[0]; c[5] = c1[1]; c[6] = c1[2]; c[7] = c1[3];
-    return c;
-}
-#define PNY_H2_MFMA_PER 2
-#else
 __device__ __forceinline__ f32x16 h2mfma(h8 a, h8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-#define PNY_H2_MFMA_PER 1
-#endif
 struct NoSide {
     __device__ __forceinline__ void operator()() const {}
 };
@@ -143,7 +127,7 @@ __device__ __forceinline__ void h1gemm(f32x16 (&acc)[h2::NT][h2::MT], H2Ring& r,
 #ifndef PNY_H2_NOSCHED
 #pragma unroll
             for (int i = 0; i < NT * MT; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, PNY_H2_MFMA_PER, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 if (i < MT) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // next step's B fragments first (LDS latency)
                 if (i < NT) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // the step's weight loads
                 __builtin_amdgcn_sched_group_barrier(0x006, 2, 0);
@@ -175,9 +159,6 @@ __device__ __forceinline__ void h2gemm(f32x16 (&acc)[h2::NT][h2::MT], H2Ring& r,
         // `side` (loads whose results are needed after this GEMM: the first chunk of the next block's gather) is issued
         // from INSIDE the loop: placed in front of it the compiler sinks the loads behind the loop, to their first use
         if (j == WD) side();
-#ifdef PNY_H2_EXP_LOCKSTEP   // experiment: a workgroup barrier every PNY_H2_EXP_LOCKSTEP steps keeps the two waves of a SIMD level
-        if (j > 0 && (j % PNY_H2_EXP_LOCKSTEP) == 0) __builtin_amdgcn_s_barrier();
-#endif
 #pragma unroll
         for (int d = 0; d < WD; ++d) {
             const int jd = j + d;
@@ -205,7 +186,7 @@ __device__ __forceinline__ void h2gemm(f32x16 (&acc)[h2::NT][h2::MT], H2Ring& r,
 #ifndef PNY_H2_NOSCHED
 #pragma unroll
             for (int i = 0; i < NT * MT; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, PNY_H2_MFMA_PER, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x020, NT * 2 / (NT * MT), 0);   // the step's NT x 2 weight loads
                 __builtin_amdgcn_sched_group_barrier(0x006, 2, 0);
             }
@@ -221,7 +202,7 @@ __device__ __forceinline__ void h2gemm(f32x16 (&acc)[h2::NT][h2::MT], H2Ring& r,
 #ifndef PNY_H2_NOSCHED
 #pragma unroll
             for (int i = 0; i < NT * MT; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, PNY_H2_MFMA_PER, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 if (i < 2) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x006, 2, 0);
             }
@@ -239,7 +220,7 @@ __device__ __forceinline__ void h2gemm(f32x16 (&acc)[h2::NT][h2::MT], H2Ring& r,
 #ifndef PNY_H2_NOSCHED
 #pragma unroll
             for (int i = 0; i < NT * MT; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, PNY_H2_MFMA_PER, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 if (MT > 1 && i < 2) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x006, 2, 0);
             }
@@ -291,6 +272,19 @@ __device__ __forceinline__ h4 cvt4(float a, float b, float c, float d) {
     asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(u.x) : "v"(a), "v"(b));
     asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(u.y) : "v"(c), "v"(d));
     return __builtin_bit_cast(h4, u);
+}
+
+// Four fp32 values of one feature quad to the quad's f16 planes in the LDS activation buffer: `slot` is the quad's 8 bytes in
+// plane slot 0; the second plane of the split (PL = 2) goes ROW_BYTES behind it.
+__device__ __forceinline__ void put_planes(char* slot, float a, float b, float c, float d) {
+    if constexpr (h2::PL == 1) {
+        *reinterpret_cast<h4*>(slot) = cvt4(a, b, c, d);
+    } else {
+        h4 p0, p1;
+        split4(a, b, c, d, p0, p1);
+        *reinterpret_cast<h4*>(slot) = p0;
+        *reinterpret_cast<h4*>(slot + h2::ROW_BYTES) = p1;
+    }
 }
 
 template <int NT_, int MT_>

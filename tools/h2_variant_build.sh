@@ -1,10 +1,11 @@
 #!/bin/bash
 # Diagnostic builds of the f16x2 kernel (csrc/mlp_h2.hip) beside the product library:
 #   tools/h2_variant_build.sh <name> [-DPNY_H2_STAMP] [-DPNY_H2_WD=4] [-DPNY_H2_NOSCHED] [-DPNY_H2_NOPREFETCH]
-#                                    [-DPNY_H2_PLAIN_SPLIT] [-DPNY_H2_EXP_FOOT]
+#                                    [-DPNY_H2_PLAIN_SPLIT]
 #                                    [-DPNY_H2_PER_VIEW_FC1]   (the per-view fc_1 order, for an A/B against the view-mean order)
 # -> build_dbg/libpnyolo_<name>.so (git-ignored, travels with gpurun).  Use with PNYOLO_LIB=$PWD/build_dbg/libpnyolo_<name>.so,
 # e.g. `tools/debug/bench_variants.sh base <name>`; -DPNY_H2_STAMP prints the per-phase shares of every launch on stderr.
+# (-DPNY_H2_EXP_FOOT and the other timing-only PNY_H2_EXP_* / PNY_H2_ANOM_* switches existed up to commit 41412ff.)
 # The other objects are taken from the product build (run `make -C pixel-nerf-yolo_amd/csrc` first).
 set -e
 name=$1; shift
