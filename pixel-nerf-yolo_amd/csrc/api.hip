@@ -994,7 +994,9 @@ static bool f16_default(const pny_scene* s) {
 // whether a launch of n_points reads projected maps (force: whatever the scene's mode says)
 static bool wants_projection(const pny_scene* s, long long n_points, bool force) {
     if (!s->m->has_zproj) return false;
-    if ((long long)s->hl * s->wl * view_blocks(s->m->desc) * HID >= (1ll << 31)) return false;   // 32-bit tap offsets: stay direct
+    // 32-bit tap offsets, in BYTES in the f16 kernels' wave-owned gather (mlp_h2.hip h2wave_issue: one buffer resource per
+    // view's map): a view's map stays under 4 GiB, larger ones stay direct
+    if ((long long)s->hl * s->wl * view_blocks(s->m->desc) * HID >= (1ll << 30)) return false;
     if (force) return true;
     if (s->zp_mode == PNY_PROJECTION_OFF) return false;
     return s->zp_mode != PNY_PROJECTION_AUTO || f16_default(s) || n_points >= 2ll * s->hl * s->wl;

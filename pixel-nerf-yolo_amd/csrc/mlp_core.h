@@ -655,6 +655,8 @@ __device__ __forceinline__ void sample_taps(const MlpArgs& a, int v, long long s
 // A wave pass covers 8 samples x 8 channel quads: the lanes {l, l+8, .., l+56} read one 128-byte
 // line per tap, each 8-lane group writes 128 contiguous LDS bytes.  A lane keeps the same sample for
 // the whole gather, so its four tap pointers / weights are set up once per (view, block).
+// (The non-stashing f16 kernels enter a block through a different, wave-owned mapping -- a wave gathers its own feature rows
+// for every sample of the tile: mlp_h2.hip h2wave_issue / h2wave_commit.)
 constexpr int GCH = 128;  // channels per gather chunk = 16 k-iterations of the lin_z GEMM
 
 template <class C, int NB = 1>

@@ -16,15 +16,30 @@
 //     fragment of a 16-k step is one ds_read_b128 per plane; the epilogue splits in registers and writes 8 bytes per plane
 //     and accumulator quad;
 //   * weights are packed per 16-k step as [n-tile][plane][lane] x 16 bytes (4 bytes per weight, as before);
-//   * the interpolated projection (fp32) is staged in the very bytes its consumer lane later overwrites with the planes of
-//     relu(h): the first two floats of a feature quad in the quad's plane-0 slot, the other two in its plane-1 slot, so the
-//     block entry needs no barrier between reading the projection and writing the planes;
+//   * the block entry is WAVE-OWNED (h2wave_entry; every non-stashing instantiation: pny_mlp_h2_kernel<false>,
+//     pny_mlp_h2s_kernel, pny_mlp_h1_kernel<false>): the accumulator layout gives a lane four consecutive features of one
+//     sample, one float4 of the projected map, so wave w gathers ITS OWN features -- the 256 contiguous bytes per latent pixel
+//     that its rows hold -- for all samples of the tile, an accumulator tile (32 features x 32 samples) at a time, two in
+//     flight.  A wave load still covers 8 consecutive samples x one 128-byte line.  The blend is staged in fp32 in the
+//     tile's own plane bytes (feature quad j of sample s in the quad's slot at column s ^ j: 16 bytes per lane and free of
+//     bank conflicts on both sides), read back in accumulator layout and turned into planes by the same wave: bias, projection,
+//     relu, range guard and split run per tile inside the gather's software pipeline, while the next tile's loads are in
+//     flight, and between the barrier behind the previous GEMM and the one in front of fc_0 there is no workgroup barrier.
+//     The first tile of the next block is fetched underneath the fc_1 GEMM (in the registers of the then-dead `net`
+//     accumulators).  A lane serves four samples per tile: tap offsets and weights are re-read from the LDS tap table,
+//     and the loads go through a buffer resource of the view's map with 32-bit byte offsets (api.hip wants_projection keeps
+//     a view's map under 4 GiB).
+//     The STASH instantiations (training forwards) keep the SHARED entry: the projected channels of a block arrive in 4
+//     chunks of 128 through two register buffers, wave w fetching samples 8 w .. 8 w + 7 for all 128 channels of a chunk
+//     (first chunk of the next block underneath the fc_1 GEMM), staged in fp32 in the bytes the consumer lane later overwrites
+//     (the first two floats of a feature quad in the quad's plane-0 slot, the other two in its plane-1 slot), a workgroup
+//     barrier, then h2epilogue<true>.  With the wave-owned entry pny_mlp_h2_kernel<true> spills 198 VGPRs instead of 185, and
+//     these kernels also gather the raw latent in the shared lane mapping.  Same blends, same sums in the same order: the
+//     two entries give the same bits;
 //   * biases are applied lazily in the epilogue that follows (b_in + b_z0 and b_fc1[b-1] + b_z[b] at the next block entry,
 //     b_fc0 in the relu(net) epilogue, the last b_fc1 before lin_out) from a table in the remaining LDS (22 KiB for 5 blocks;
 //     152 of the CU's 160 KiB in use): no bias registers, no global loads between a barrier and a GEMM.  (mean over views
 //     of (h_v + b) = mean(h_v) + b, so the last per-view bias may follow the mean.)
-//   * the projected channels of a block arrive in 4 chunks of 128 through two register buffers, the first chunk of the next
-//     block fetched underneath the fc_1 GEMM (in the registers of the then-dead `net` accumulators);
 //   * stash / slab traffic goes through raw buffer resources (one VGPR of lane offset instead of per-quad 64-bit pointers);
 //   * the VIEW-MEAN order (the non-stashing two-plane instantiations, pny_mlp_h2_kernel<false> and pny_mlp_h2s_kernel): the
 //     last per-view block ends `h_v += fc_1(R_v)`, R_v =
@@ -50,7 +65,7 @@
 // -DPNY_H2_PLANES=1 (mlp_h1.hip) is the single-plane kernel of PNY_PRECISION_F16: x = f16(x), w = f16(w), one
 // v_mfma_f32_32x32x16_f16 per accumulator tile and 16 k (fp32 accumulation), weights packed per 16-k step as
 // [n-tile][lane] x 16 bytes (2 bytes per weight; api.hip build_h1_images).  The LDS layout stays the one above: relu(.) goes to
-// plane slot 0 only, and slot 1 keeps its one job of staging the second half of each fp32 projection quad -- the projection
+// plane slot 0 only, and slot 1 keeps its one job of staging half of the block entry's fp32 projection -- the projection
 // is added in fp32 exactly as in the two-plane kernel, at the same 152 KiB of LDS.  Its STASH instantiation is the training
 // forward of PNY_PRECISION_F16_TRAIN: the stash layout is unchanged and holds this kernel's own fp32 values.
 #include <cstdlib>
@@ -101,7 +116,8 @@ __device__ __forceinline__ unsigned long long h2now() {
 // The 8-byte slot of feature quad (row, half) = (feature / 8, (feature / 4) & 1) of sample m in plane p is at byte
 //     (2 row + p) * ROW_BYTES + 16 m + 8 half.
 
-// Block entry / GEMM epilogue: acc += bias (+ the staged fp32 projection, ADDZ), then the planes of relu(acc) go to the
+// GEMM epilogue, and with ADDZ the second half of the SHARED block entry (STASH instantiations; the others enter a block through
+// h2wave_entry below): acc += bias (+ the staged fp32 projection, ADDZ), then the planes of relu(acc) go to the
 // slots of the lane's own feature quads -- the bytes the staged projection was read from, so no other lane's data is touched.
 // `bias`: a 512-float vector of the workgroup's LDS bias table.
 // Stores into the tile's record of the X stash go through a raw buffer resource with 32-bit offsets (64-bit pointers per
@@ -316,7 +332,9 @@ __device__ __forceinline__ void h2mean_planes(const f32x16 (&net)[h2::NT][h2::MT
     range_check(rmax, range_flag);
 }
 
-// gather_commit (mlp_core.h) for the staging layout above: chunk c covers feature quads [32 c, 32 c + 32)
+// The shared block entry's gather_commit (mlp_core.h; STASH instantiations only): wave w blends samples 8 w .. 8 w + 7 of chunk
+// c, feature quads [32 c, 32 c + 32), and writes the first two floats of a quad to the 8 bytes its consumer lane owns in the
+// quad's plane-0 slot, the other two to those in its plane-1 slot (rows of OTHER waves: a workgroup barrier follows)
 template <int B>
 __device__ __forceinline__ void h2gather_commit(const GatherTaps<h2::C, 2>& g, char* planes, int chunk, int wave, int lane) {
     using namespace h2;
@@ -332,6 +350,111 @@ __device__ __forceinline__ void h2gather_commit(const GatherTaps<h2::C, 2>& g, c
         *reinterpret_cast<float2*>(s0) = make_float2(r.x, r.y);
         *reinterpret_cast<float2*>(s0 + ROW_BYTES) = make_float2(r.z, r.w);
     }
+}
+
+// ---- The wave-owned block entry (the non-stashing instantiations; header comment) ----------------------------------------------
+// Wave w gathers ITS OWN features of the block's projected channels -- the 32 NT consecutive floats per latent pixel that its
+// rows hold -- for all TM samples, one accumulator tile (nt, mt) = 32 features x 32 samples at a time ("sub-chunk" t =
+// nt MT + mt: 16 float4 tap loads per lane, two sub-chunks in flight).  A wave load covers 8 consecutive samples x one
+// 128-byte line: lane l reads feature quad jq = l & 7 of sample 8 pass + (l >> 3).  The lane serves four samples per
+// sub-chunk, so tap offsets and weights are re-read from the LDS tap table per sub-chunk (8 lanes per record: a broadcast),
+// and the loads go through a buffer resource of the view's map with 32-bit offsets (the wave's channel offset in an SGPR).
+struct WaveGather {
+    f32x4 x[2][4][4];   // [buffer][pass][tap]
+};
+template <int B, int T>
+__device__ __forceinline__ void h2wave_issue(WaveGather& wg, __amdgpu_buffer_rsrc_t zr, const float4* tap_tab, unsigned c0, int lane) {
+    using namespace h2;
+    constexpr int nt = T / MT, mt = T % MT;
+    asm volatile("" : "+v"(lane));   // (addresses recomputed at every call, not hoisted and spilled: h2wave_entry)
+    const float4* tt = tap_tab + 2 * (32 * mt + (lane >> 3));
+    const unsigned ql = 16u * (unsigned)(lane & 7);
+#pragma unroll
+    for (int pass = 0; pass < 4; ++pass) {
+        const float4 o = tt[16 * pass];
+        const unsigned off[4] = {(unsigned)__float_as_int(o.x), (unsigned)__float_as_int(o.y), (unsigned)__float_as_int(o.z), (unsigned)__float_as_int(o.w)};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            wg.x[B][pass][k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(zr, off[k] * 4u + ql, c0 + 128u * nt, 0));
+    }
+}
+// Blend sub-chunk T and stage it in fp32 in the tile's OWN plane bytes (4 rows x 2 slots x 512 bytes = the 4 KiB of 32 x 32
+// floats), private to the wave: feature quad j of sample s (both tile-local) at
+//     slot (row j >> 1, plane slot j & 1), byte 16 (s ^ j)
+// -- the slot whose two halves the quad's consumer lanes overwrite with planes.  The XOR makes both sides conflict-free at
+// 16 bytes per lane: the 8 lanes of a store group (one sample, j = 0..7) hit 8 different 16-byte columns, and a read group
+// (16 samples, one j) a permutation of 16 contiguous ones.  Then, in accumulator layout (lane = sample m0, half hh; quad q =
+// staged quad j = 2 q + hh): acc += bias, += projection (that order), relu, range guard, split, planes -- h2epilogue<true>'s
+// arithmetic per quad.  Wave-level ordering only (the LDS serves a wave's instructions in order): the wavefront-scope fences
+// keep the compiler from moving the read-back over the staging stores or the plane stores over the read-back.  Quad q's
+// planes overwrite slots 2 q and 2 q + 1 only, whose staged values every lane has read by then.
+template <int B, int T>
+__device__ __forceinline__ void h2wave_commit(const WaveGather& wg, f32x16 (&acc)[h2::NT][h2::MT], const float4* tap_tab, const float* bias,
+                                              char* planes, int wave, int lane, float& rmax) {
+    using namespace h2;
+    constexpr int nt = T / MT, mt = T % MT;
+    const int jq = lane & 7, sl = lane >> 3, m0 = lane & 31, hh = lane >> 5;
+    char* tb = planes + (4 * NT * wave + 4 * nt) * (2 * ROW_BYTES) + 32 * mt * 16;
+    char* wr = tb + jq * ROW_BYTES + 16 * (sl ^ jq);
+    const float4* tw = tap_tab + 2 * (32 * mt + sl) + 1;
+#pragma unroll
+    for (int pass = 0; pass < 4; ++pass) {
+        const float4 w4 = tw[16 * pass];
+        const float w[4] = {w4.x, w4.y, w4.z, w4.w};
+        float4 x[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = make_float4(wg.x[B][pass][k][0], wg.x[B][pass][k][1], wg.x[B][pass][k][2], wg.x[B][pass][k][3]);
+        *reinterpret_cast<float4*>(wr + 128 * pass) = tap_blend(x, w);   // sample 8 pass + sl: column (8 pass + sl) ^ jq
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const float* bl = bias + 32 * NT * wave + 32 * nt + 4 * hh;
+    // quad q + 1's bias and staged projection are read before quad q's planes are written (other slots)
+    auto rd_b = [&](int q) { return *reinterpret_cast<const float4*>(bl + 8 * q); };
+    auto rd_z = [&](int q) { return *reinterpret_cast<const float4*>(tb + (2 * q + hh) * ROW_BYTES + 16 * (m0 ^ (2 * q + hh))); };
+    float4 b = rd_b(0), z = rd_z(0);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float4 bq = b, zq = z;
+        if (q + 1 < 4) b = rd_b(q + 1), z = rd_z(q + 1);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        char* s0 = tb + q * (2 * ROW_BYTES) + m0 * 16 + 8 * hh;
+        float x0 = acc[nt][mt][4 * q + 0] + bq.x, x1 = acc[nt][mt][4 * q + 1] + bq.y;
+        float x2 = acc[nt][mt][4 * q + 2] + bq.z, x3 = acc[nt][mt][4 * q + 3] + bq.w;
+        x0 += zq.x;
+        x1 += zq.y;
+        x2 += zq.z;
+        x3 += zq.w;
+        acc[nt][mt][4 * q + 0] = x0;
+        acc[nt][mt][4 * q + 1] = x1;
+        acc[nt][mt][4 * q + 2] = x2;
+        acc[nt][mt][4 * q + 3] = x3;
+        const float r0 = relu1(x0), r1 = relu1(x1), r2 = relu1(x2), r3 = relu1(x3);
+        h2put_planes(s0, r0, r1, r2, r3, rmax);
+    }
+}
+// The whole entry of a per-view block behind barrier A: sub-chunk 0 is in buffer 0 already (fetched before lin_in or
+// underneath the previous fc_1 GEMM); the loads of sub-chunk t + 1 are issued before sub-chunk t is blended, staged and
+// turned into planes, so that vector work runs while they are in flight.
+__device__ __forceinline__ void h2wave_entry(WaveGather& wg, f32x16 (&acc)[h2::NT][h2::MT], __amdgpu_buffer_rsrc_t zr, const float4* tap_tab, unsigned c0,
+                                             const float* bias, char* planes, int wave, int lane, unsigned* range_flag) {
+    static_assert(h2::NT * h2::MT == 4, "four sub-chunks");
+    // the entry's lane-dependent addresses are recomputed here (a dozen VALU instructions) instead of being hoisted out of the
+    // tile loop and kept, i.e. spilled, across the GEMMs
+    asm volatile("" : "+v"(lane));
+    float rmax = 0.f;
+    h2wave_issue<1, 1>(wg, zr, tap_tab, c0, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    h2wave_commit<0, 0>(wg, acc, tap_tab, bias, planes, wave, lane, rmax);
+    h2wave_issue<0, 2>(wg, zr, tap_tab, c0, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    h2wave_commit<1, 1>(wg, acc, tap_tab, bias, planes, wave, lane, rmax);
+    h2wave_issue<1, 3>(wg, zr, tap_tab, c0, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    h2wave_commit<0, 2>(wg, acc, tap_tab, bias, planes, wave, lane, rmax);
+    h2wave_commit<1, 3>(wg, acc, tap_tab, bias, planes, wave, lane, rmax);
+    range_check(rmax, range_flag);
 }
 
 // per (view, tile) prologue: the lin_in B operand (positional code, view dirs) as f16 planes in rows 0..7 of each plane, and
@@ -396,6 +519,11 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
 #else
     constexpr bool VIEW_MEAN = !STASH;
 #endif
+    // The block entry: wave-owned (h2wave_entry) in every non-stashing instantiation -- pny_mlp_h2_kernel<false>,
+    // pny_mlp_h2s_kernel, pny_mlp_h1_kernel<false>; the STASH instantiations (training forwards) keep the shared entry
+    // (h2gather_commit, the "projection visible" barrier, h2epilogue<true>): they also gather the raw latent in the shared
+    // lane mapping and are far over the register budget already.
+    constexpr bool WAVE_ENTRY = !STASH;
     const SlabRef slab_r = {__builtin_amdgcn_make_buffer_rsrc(a.scratch + ((size_t)gridDim.x + blockIdx.x) * (TM * HID), 0, TM * HID * 4, 0x00020000),
                             slab.lane_off};
     const int nb = a.n_blocks;
@@ -434,7 +562,16 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
     for (long long tile = tw.first; tile < tw.last; tile += tw.step) {
         f32x16 h[NT][MT];
         f32x16 net[NT][MT];
-        GatherTaps<C, 2> g;   // taps of the current view; two chunks of projected channels in flight
+        GatherTaps<C, 2> g;   // shared entry: taps of the current view; two chunks of projected channels in flight
+        WaveGather wg;        // wave-owned entry: two sub-chunks in flight
+        __amdgpu_buffer_rsrc_t zr = __amdgpu_buffer_rsrc_t();   // the current view's projected map
+        const unsigned wave_c0 = (unsigned)(32 * NT * wave) * 4u;   // byte offset of the wave's first feature inside a block's 512 channels
+        auto prefetch = [&](int c0) {   // first piece of the projection of the block at channel c0 into buffer 0
+            if constexpr (WAVE_ENTRY)
+                h2wave_issue<0, 0>(wg, zr, tap_tab, (unsigned)c0 * 4u + wave_c0, lane);
+            else
+                gather_issue<C, 0>(g, c0, wave);
+        };
         // one residual block from "planes hold relu(h_in)" on: net = fc_0(.), h += fc_1(relu(net + b_fc0)).  `next_c0` >= 0:
         // the first chunk of the NEXT block's projection (channel offset next_c0) is fetched into gather buffer 0
         // underneath the fc_1 GEMM -- `net` is dead there, its registers hold the chunk.
@@ -471,7 +608,7 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
                 HS_LAP(HS_EPI);
                 __syncthreads();
                 HS_LAP(HS_EPI_WAIT);
-                h2gemm(h, ring, ws, fc1seg(blk), after, planes, lane, [&]() { gather_issue<C, 0>(g, next_c0, wave); });
+                h2gemm(h, ring, ws, fc1seg(blk), after, planes, lane, [&]() { prefetch(next_c0); });
                 HS_LAP(HS_GEMM);
             } else {
                 HS_LAP(HS_EPI);
@@ -518,8 +655,14 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
                     if (c + 1 < nch) put(g.x[1], c + 1);
                 }
             }
-            gather_setup<C>(g, a.zp + (size_t)(vb + v) * a.Hl * a.Wl * a.zp_stride, tap_tab, wave, lane);
-            gather_issue<C, 0>(g, 0, wave);   // block 0, chunk 0
+            if constexpr (WAVE_ENTRY) {
+                // (a view's map is under 4 GiB: api.hip wants_projection; a read past it would return zeros)
+                const size_t zfloats = (size_t)a.Hl * a.Wl * a.zp_stride;
+                zr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.zp) + (size_t)(vb + v) * zfloats, 0, (int)(unsigned)(zfloats * 4), 0x00020000);
+            } else {
+                gather_setup<C>(g, a.zp + (size_t)(vb + v) * a.Hl * a.Wl * a.zp_stride, tap_tab, wave, lane);
+            }
+            prefetch(0);   // block 0, first piece
             HS_LAP(HS_PROLOGUE);
             h2gemm(h, ring, ws, s_in, fc0seg(0), planes, lane);
             HS_LAP(HS_GEMM);
@@ -533,6 +676,12 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
                 HS_LAP(HS_GATHER);
                 __syncthreads();  // every wave is done reading the planes (previous GEMM)
                 HS_LAP(HS_GATHER_WAIT);
+                if constexpr (WAVE_ENTRY) {
+                    // wave-private from here to the fc_0 GEMM's barrier: gather, staging, bias + projection, relu, planes
+                    h2wave_entry(wg, h, zr, tap_tab, (unsigned)cb * 4u + wave_c0, entry_bias(blk), planes, wave, lane, a.range_flag);
+                    HS_LAP(HS_GATHER);
+                    return;
+                }
                 gather_issue<C, 1>(g, cb + GCH, wave);
                 __builtin_amdgcn_sched_barrier(0);
                 h2gather_commit<0>(g, planes, 0, wave, lane);
@@ -582,7 +731,7 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
 #if defined(PNY_H2_NOPREFETCH)
             for (int blk = 0; blk + 1 < nvb; ++blk) {
                 view_block(blk, fc0seg(blk + 1), false, -1);
-                gather_issue<C, 0>(g, (blk + 1) * HID, wave);
+                prefetch((blk + 1) * HID);
             }
 #else
             for (int blk = 0; blk + 1 < nvb; ++blk) view_block(blk, fc0seg(blk + 1), false, (blk + 1) * HID);
