@@ -569,8 +569,17 @@ int pny_model_set_deterministic(pny_model* m, int enable);
  * (0 before any). */
 int pny_scene_last_latent_grad_mode(pny_scene* s, int* deterministic);
 
+/* Bits of the `accumulate` argument of the backward calls and of pny_model_flush_weight_grads. */
+#define PNY_ACC_ADD 1            /* add to the bound gradients (0: overwrite them) */
+#define PNY_ACC_IMMEDIATE 2      /* pny_render_backward: an outstanding reservation (pny_model_defer_weight_grads) belongs to another
+                                    forward: recompute, and weight gradients at once into the bound buffers */
+#define PNY_ACC_FINE_ONLY 4      /* pny_render_backward: only the fine pass of this backward */
+#define PNY_ACC_COARSE_ONLY 8    /* pny_render_backward: only the coarse pass */
+#define PNY_FLUSH_COARSE_ONLY 16 /* pny_model_flush_weight_grads: mlp_coarse's stash only */
+#define PNY_FLUSH_FINE_ONLY 32   /* pny_model_flush_weight_grads: mlp_fine's stash only */
+
 /* Backward of pny_query: d_out_dev (n, d_out) = dL/d(out).  accumulate = 0 overwrites the bound gradients of the
- * selected MLP, 1 adds to them. */
+ * selected MLP, PNY_ACC_ADD adds to them. */
 int pny_query_backward(pny_scene* s, const float* xyz_dev, const float* viewdirs_dev, int64_t n, int coarse,
                        const float* d_out_dev, int accumulate, pny_stream stream);
 
@@ -602,9 +611,10 @@ typedef struct pny_render_grads {
 } pny_render_grads;
 /* Backward of pny_render for one scene: composite backward + MLP backward of the fine pass (mlp_fine) and of the coarse
  * pass (mlp_coarse), into the bound gradients (accumulate as above; with one shared MLP the two passes add up).
- * accumulate bit 4: only the fine pass of this backward; bit 8: only the coarse pass (call with bit 4 first: the coarse
- * pass takes the depth-sample path's gradient the fine pass left in the scene) -- lets a caller put mlp_fine's
- * weight-gradient flush (pny_model_flush_weight_grads with bit 32) between the two. */
+ * PNY_ACC_FINE_ONLY: only the fine pass of this backward; PNY_ACC_COARSE_ONLY: only the coarse pass (call with
+ * PNY_ACC_FINE_ONLY first: the coarse pass takes the depth-sample path's gradient the fine pass left in the scene) -- lets a
+ * caller put mlp_fine's weight-gradient flush (pny_model_flush_weight_grads with PNY_FLUSH_FINE_ONLY) between the two.
+ * PNY_ACC_IMMEDIATE: see above. */
 int pny_render_backward(pny_scene* s, const float* rays_dev, int64_t n, const pny_render_opts* opts,
                         const pny_render_saved* saved, const pny_render_grads* grads, int accumulate, pny_stream stream);
 /* Test / debugging aid: where the last pny_render_backward on this scene (with n_fine_depth > 0 and saved->depth_coarse) found
@@ -651,7 +661,9 @@ int pny_model_defer_weight_grads(pny_model* m, int enable, int ns, int64_t coars
  * MLP passes with the stashing instantiation (reference operation order; rgb / sigma within fp32 rounding of the
  * projected evaluation) directly into the reservation; the pny_render_backward that follows (same reservation, z_* /
  * sample_* of that forward given in pny_render_saved) then skips its forward recompute and starts at the dX chain.
- * One-shot: the flag clears itself; a pass that does not fit the reservation runs the plain forward.  * accumulate bit 16: flush mlp_coarse's stash only; bit 32: mlp_fine's only (0: both, mlp_coarse first). */
+ * One-shot: the flag clears itself; a pass that does not fit the reservation runs the plain forward.
+ * pny_model_flush_weight_grads: accumulate = PNY_ACC_ADD or 0, with PNY_FLUSH_COARSE_ONLY: flush mlp_coarse's stash only;
+ * PNY_FLUSH_FINE_ONLY: mlp_fine's only (neither: both, mlp_coarse first). */
 int pny_scene_stash_next_render(pny_scene* s, int enable);
 int pny_model_flush_weight_grads(pny_model* m, int accumulate, pny_stream stream);
 /* GEMM FLOPs and HIP-event time of the last flush. */

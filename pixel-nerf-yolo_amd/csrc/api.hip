@@ -364,19 +364,9 @@ void pny_model_destroy(pny_model* m) {
     m->repack_jobs.release();
     m->h1_packed.release();
     m->h1_jobs.release();
-    m->d_absmax.release();
     m->enc_batch_work.release();
     m->enc_batch_lat.release();
-    for (int w = 0; w < 2; ++w) {
-        m->dx_stash[w].release();
-        m->ddy_stash[w].release();
-        m->d_partial[w].release();
-        m->d_bias[w].release();
-        m->d_tables[w].release();
-        m->d_stage[w].release();
-    }
-    for (auto& e : m->flush_ev)
-        if (e) (void)hipEventDestroy(e);
+    m->stash.release();
     if (m->aux_stream) (void)hipStreamDestroy(m->aux_stream);
     if (m->aux_fork) (void)hipEventDestroy(m->aux_fork);
     if (m->aux_join) (void)hipEventDestroy(m->aux_join);
@@ -1077,7 +1067,7 @@ int fill_mlp_args(pny_scene* s, int mode, const float* xyz, const float* dirs, c
     const pny_model_desc& d = s->m->desc;
     MlpArgs& a = *pa;
     memset(&a, 0, sizeof(a));
-    const bool fine_w = !(coarse || !d.has_fine || !s->m->use_fine);
+    const bool fine_w = mlp_index(s->m, coarse) == 1;
     a.w = fine_w ? s->m->fine : s->m->coarse;
     a.n_blocks = d.n_blocks;
     use_images(a, f16_images(s->m, fine_w, false));   // (in the packed blob, like `w`)
@@ -1141,25 +1131,17 @@ static int run_mlp(pny_scene* s, int mode, const float* xyz, const float* dirs, 
     MlpArgs a;
     int rc;
     if ((rc = fill_mlp_args(s, mode, xyz, dirs, rays, z, K, n_points, coarse, out, &a))) return rc;
-    const bool fine_w = !(coarse || !d.has_fine || !m->use_fine);
-    const int which = fine_w ? 1 : 0;
+    const int which = mlp_index(m, coarse);
     bool room = false;
     if (stash_pass >= 0) {
         s->stashed[stash_pass].valid = false;
-        room = m->defer && obj_views(s) == m->defer_ns && m->defer_used[which] + a.n_tiles <= m->defer_cap[which];
+        room = m->stash.book.has_room(which, obj_views(s), a.n_tiles);
     }
     const MlpRoute r = route_mlp(s, n_points, room);
     if (r.stash) {
-        pny_scene::StashedPass& sp = s->stashed[stash_pass];
+        const StashedPass& sp = s->stashed[stash_pass] = m->stash.book.take_pass(which, a.n_tiles, n_points);
         a.lay = stash_layout(d, obj_views(s), s->L);
-        a.stash_x = a.lay.x_record(m->dx_stash[which].f(), m->defer_used[which]);
-        sp.valid = true;
-        sp.epoch = m->defer_epoch;
-        sp.which = which;
-        sp.tile0 = m->defer_used[which];
-        sp.tiles = a.n_tiles;
-        sp.n_points = n_points;
-        m->defer_used[which] += a.n_tiles;
+        a.stash_x = m->stash.x_record(a.lay, which, sp.tile0);
     }
     if (r.projected) {
         if ((rc = ensure_projection(s, which, n_points, st, &a.zp, r.stash))) return rc;
@@ -1167,7 +1149,7 @@ static int run_mlp(pny_scene* s, int mode, const float* xyz, const float* dirs, 
     }
     if (r.kernel == K_H1) {   // (F16_TRAIN scenes: the same no-grad kernel as F16's, so their no-grad results are F16's bit for bit)
         if ((rc = want_h1_images(m, s->precision == PNY_PRECISION_F16_TRAIN))) return rc;
-        use_images(a, f16_images(m, fine_w, true));
+        use_images(a, f16_images(m, which == 1, true));
     }
     const long long tiles = (n_points + r.tile - 1) / r.tile;
     if (tiles > 0x7fffffffll) return fail(PNY_ERR_ARG, "too many points for one launch");

@@ -6,6 +6,7 @@
 
 #include "pny_common.h"
 #include "encoder.h"
+#include "stash_book.h"
 
 namespace pny {
 
@@ -93,11 +94,41 @@ struct RepackEntry {
     int n_out, k_in, k_pad, count;
 };
 
-// The 0 / 1 / 2 codes pny_scene_last_precision, pny_scene_last_backward_precision and pny_model_last_flush_precision report, and
-// the matrix arithmetic of a kernel wherever the host code has to name it
-enum Prec { PREC_F32 = 0, PREC_H2 = 1 /* split f16 (F16X2) */, PREC_H1 = 2 /* single-plane f16 (F16, F16_TRAIN) */ };
 // planes per operand of the f16 weight- and latent-gradient GEMMs (ignored by their fp32 paths)
 inline int gemm_planes(Prec p) { return p == PREC_H1 ? 1 : 2; }
+
+// Deferred weight gradients (pny_model_defer_weight_grads): the reservation a training pny_render writes the GEMM operands into,
+// every scene's backward appends its dY tiles to, and pny_model_flush_weight_grads turns into ONE weight-gradient GEMM per MLP
+// ([0] mlp_coarse, [1] mlp_fine).  `book` does the counting (stash_book.h); the buffers are addressed through the accessors.
+struct DeferredStash {
+    StashBook book;
+    DevBuf x[2], dy[2];                      // the GEMMs' B operands / the dY tiles, book.cap[w] records of the stash layout
+    DevBuf partial[2], bias[2], tables[2];   // the flush GEMM's split partial sums and its work list
+    PinnedStage stage[2];
+    DevBuf absmax;                           // two words: running max |dY| of the deferred tiles per MLP (zeroed by its flush)
+    hipEvent_t flush_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    double flush_flops = 0.0;                // pny_model_last_flush_stats
+    int flush_launches = 0;
+    Prec last_flush_prec = PREC_F32;         // pny_model_last_flush_precision: the flush's GEMM
+    float* x_record(const StashLayout& lay, int which, long long tile) const { return lay.x_record(x[which].f(), tile); }
+    float* dy_record(const StashLayout& lay, int which, long long tile) const { return lay.dy_record(dy[which].f(), tile); }
+    unsigned* absmax_word(int which) const { return absmax.p ? reinterpret_cast<unsigned*>(absmax.p) + which : nullptr; }
+    void release() {
+        for (int w = 0; w < 2; ++w) {
+            x[w].release();
+            dy[w].release();
+            partial[w].release();
+            bias[w].release();
+            tables[w].release();
+            stage[w].release();
+        }
+        absmax.release();
+        for (auto& e : flush_ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+    }
+};
 
 // One set of f16 operand images of an MLP and the allocation they live in (raw-buffer addressing): lin_in / fc_0 / fc_1 as the
 // forward kernels read them (mlp_h2.hip, mlp_h1.hip) and lin_out / fc_0 / fc_1 transposed for the backward chain
@@ -183,25 +214,10 @@ struct pny_model {
     long long repack_max_elems = 0;
     bool repack_ready = false;
     std::vector<struct pny_scene*> scenes;   // scenes created on this model (stream ordering of a refresh)
-    // Deferred weight gradients (pny_model_defer_weight_grads): the scenes' backward calls append their tiles to these
-    // model-level stashes ([0] mlp_coarse, [1] mlp_fine) and ONE weight-gradient GEMM per MLP runs at the flush.
-    bool defer = false;
-    int defer_ns = 0;
-    DevBuf dx_stash[2], ddy_stash[2], d_partial[2], d_bias[2], d_tables[2];
-    PinnedStage d_stage[2];
-    long long defer_cap[2] = {0, 0}, defer_used[2] = {0, 0};
-    DevBuf d_absmax;                         // two words: running max |dY| of the deferred tiles per MLP (train_api.hip)
-    bool defer_dw_f32 = false;               // a scene pinned to F32 contributed: the flush runs the fp32 weight-gradient GEMM
-    bool defer_dw_h2 = false;                // a split-f16 scene contributed: a flush without F32 contributors runs split-f16,
-                                             // one with F16_TRAIN contributors only the single-plane GEMM
-    Prec last_flush_prec = PREC_F32;         // pny_model_last_flush_precision: the flush's GEMM
+    DeferredStash stash;                     // deferred weight gradients: the training stash reservation
     bool deterministic = false;              // pny_model_set_deterministic: the latent gradient of every scene is bit-reproducible
     hipStream_t aux_stream = nullptr;        // side stream of the weight-gradient GEMMs' clipped tiles (mlp_bwd.hip launch_dw_gemm)
     hipEvent_t aux_fork = nullptr, aux_join = nullptr;
-    uint64_t defer_epoch = 0;                // bumped by every pny_model_defer_weight_grads(enable)
-    hipEvent_t flush_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    double flush_flops = 0.0;
-    int flush_launches = 0;
     EncoderWeights enc;                       // folded conv+bn (encoder.h)
     DevBuf enc_batch_work, enc_batch_lat;     // pny_scenes_encode: workspace and result of one trunk pass over several scenes
     bool has_encoder = false;
@@ -265,12 +281,7 @@ struct pny_scene {
     // "stash in the forward": the next pny_render evaluates the MLPs with the STASH instantiation straight into the
     // model-level stash (deferred mode); what each pass wrote is remembered for the backward of the same epoch
     bool stash_next = false;
-    struct StashedPass {
-        bool valid = false;
-        uint64_t epoch = 0;
-        int which = 0;
-        long long tile0 = 0, tiles = 0, n_points = 0;
-    } stashed[2];   // [0] coarse pass, [1] fine pass
+    StashedPass stashed[2];   // [0] coarse pass, [1] fine pass
     // HIP-event timing of the backward kernels of the last backward call (enable_timing): per MLP pass 4 events
     std::vector<hipEvent_t> bev;
     int bev_used = 0;
@@ -296,6 +307,8 @@ enum MlpPass { PASS_FORWARD, PASS_FORWARD_PROJECTED, PASS_CHAIN, PASS_FORWARD_VI
 double mlp_flops_per_point(const pny_model_desc& d, int ns, MlpPass pass);
 // single-plane f16 images (PNY_PRECISION_F16): marks the model as using them and builds them if it is finalized
 int want_h1_images(pny_model* m, bool transposed = false);   // transposed: also the chain's images (PNY_PRECISION_F16_TRAIN)
+// which MLP a pass evaluates: 0 mlp_coarse (the coarse pass, and every pass of a model without a fine MLP in use), 1 mlp_fine
+inline int mlp_index(const pny_model* m, int coarse) { return (coarse || !m->desc.has_fine || !m->use_fine) ? 0 : 1; }
 // the f16 images of the coarse / fine MLP: split, or single-plane (valid after want_h1_images)
 inline const F16Images& f16_images(const pny_model* m, bool fine, bool single_plane) {
     return single_plane ? m->h1[fine ? 1 : 0] : (fine ? m->fine_t : m->coarse_t).h2;

@@ -251,210 +251,269 @@ int run_weight_grads(pny_model* m, TrainPlan& plan, int n_tiles, const float* x_
     return 0;
 }
 
-// Backward of one MLP evaluation over n_points query points (mode 0: xyz / dirs; mode 1: rays + z with K samples per
-// ray): d_out (n_points, d_out) -> bound parameter gradients.  Points are processed in chunks that fit the stash.
-// dz_sel / dz_out (mode 1 only, optional): per ray kfd sample indices (ray * K + position, or -1) whose depth gradient
-// through the MLP inputs is added to dz_out (n_points).
-int mlp_backward(pny_scene* s, int mode, const float* xyz, const float* dirs, const float* rays, const float* z, int K,
-                 long long n_points, int coarse, const float* d_out, int accumulate, hipStream_t st,
-                 const int* dz_sel = nullptr, int kfd = 0, float* dz_out = nullptr,
-                 const pny_scene::StashedPass* stashed = nullptr, const float* fwd_out = nullptr, bool immediate = false) {
-    if (n_points == 0) return 0;
-    pny_model* m = s->m;
-    // forward already stashed by pny_render (same reservation epoch): no recompute, the tiles are in the model-level stash
-    const bool have_x = !immediate && stashed && stashed->valid && m->defer && stashed->epoch == m->defer_epoch &&
-                        stashed->n_points == n_points && fwd_out;
-    const bool defer = m->defer && !immediate;
-    if (s->n_objs > 1 && !have_x && !defer)   // (the chunked recompute path would split an object's share)
+// One backward of an MLP evaluation over n_points query points, as its caller states it
+struct MlpBackwardCall {
+    int mode = 0;                  // 0: xyz / dirs; 1: rays + z with K samples per ray
+    const float* xyz = nullptr;
+    const float* dirs = nullptr;
+    const float* rays = nullptr;
+    const float* z = nullptr;
+    int K = 1;
+    long long n_points = 0;
+    int coarse = 1;
+    const float* d_out = nullptr;  // (n_points, d_out) = dL/d(out)
+    int accumulate = 0;            // add to the bound gradients (this call's own weight-gradient GEMMs)
+    // mode 1 only, optional: per ray kfd sample indices (ray * K + position, or -1) whose depth gradient through the MLP inputs is
+    // added to dz_out (n_points)
+    const int* dz_sel = nullptr;
+    int kfd = 0;
+    float* dz_out = nullptr;
+    // what the forward pny_render stashed for this pass and the per-sample output it wrote (both, or the forward is recomputed)
+    const StashedPass* stashed = nullptr;
+    const float* fwd_out = nullptr;
+    bool immediate = false;        // an outstanding reservation is not this call's: weight gradients at once, from the scene's own stash
+};
+
+// Where a backward's tiles go and who turns them into weight gradients
+struct StashTarget {
+    float* x = nullptr;            // record 0 of the call's (chunk's) tiles: the GEMMs' B operands ...
+    float* dy = nullptr;           // ... and the dY tiles
+    long long chunk_pts = 0;       // points per chunk: all of them, unless the scene's own stash is filled chunk after chunk
+    unsigned* absmax = nullptr;    // word the chain adds its max |dY| to for the f16 gradient GEMMs (null: nobody reads it)
+    bool have_x = false;           // the forward's tiles are reused: nothing is recomputed
+    bool own_dw = false;           // this call runs its own weight-gradient GEMMs (else: pny_model_flush_weight_grads)
+};
+
+// The three stash targets: the tiles the forward pny_render already wrote into the reservation (same epoch); new tiles appended to
+// the reservation, whose weight-gradient GEMM runs once over every scene's tiles at the flush; or the scene's own stash, filled in
+// chunks that fit the budget.  The running max |dY| is per model and MLP in the reservation (every scene's chain adds to it,
+// zeroed again by the flush) and per scene otherwise (zeroed in front of every chunk's chain).
+int stash_target(pny_scene* s, const MlpBackwardCall& c, const StashLayout& lay, int which, const BwdRoute& r, StashTarget* t) {
+    DeferredStash& ds = s->m->stash;
+    const bool defer = ds.book.active && !c.immediate;
+    t->have_x = defer && c.stashed && ds.book.owns(*c.stashed) && c.stashed->n_points == c.n_points && c.fwd_out;
+    t->own_dw = !defer;
+    if (s->n_objs > 1 && !defer)   // (the chunked recompute path would split an object's share)
         return fail(PNY_ERR_STATE, "grouped scene: the backward needs the deferred stash (pny_model_defer_weight_grads)");
-    const pny_model_desc& d = m->desc;
-    const bool fine_w = !(coarse || !d.has_fine || !m->use_fine);
-    const std::string pre = fine_w ? "mlp_fine." : "mlp_coarse.";
-    TrainPlan plan = build_plan(m, obj_views(s), s->L, pre);
-    const size_t tile_bytes = (size_t)(plan.lay.x_tile + plan.lay.dy_tile) * sizeof(float);
-    long long max_tiles = (long long)(stash_budget_bytes() / tile_bytes);
+    const size_t tile_bytes = (size_t)(lay.x_tile + lay.dy_tile) * sizeof(float);
+    const long long max_tiles = (long long)(stash_budget_bytes() / tile_bytes);
     if (max_tiles < 1) return fail(PNY_ERR_ARG, "stash budget smaller than one tile");
-    // chunk boundaries on whole rays (mode 1) so that sample -> ray indexing stays local to the chunk
-    const long long unit = mode == 1 ? K : 1;
-    long long chunk_pts = std::min(n_points, max_tiles * 64);
-    chunk_pts = std::max(unit, chunk_pts / unit * unit);
-    const int cus = mlp_max_grid(MLP_8x64);
     int rc;
-    const long long chunk_tiles_max = (chunk_pts + 63) / 64;
-    // Deferred mode: this call's tiles are appended to the model-level stash of its MLP; the weight-gradient GEMM runs
-    // once over every scene's tiles at pny_model_flush_weight_grads
-    const int which = fine_w ? 1 : 0;
-    float* x_base = nullptr;
-    float* dy_base = nullptr;
-    if (have_x) {
-        chunk_pts = n_points;
-        x_base = plan.lay.x_record(m->dx_stash[stashed->which].f(), stashed->tile0);
-        dy_base = plan.lay.dy_record(m->ddy_stash[stashed->which].f(), stashed->tile0);
+    t->chunk_pts = c.n_points;   // one chunk in the reservation: it was made against the budget
+    if (t->have_x) {
+        t->x = ds.x_record(lay, c.stashed->which, c.stashed->tile0);
+        t->dy = ds.dy_record(lay, c.stashed->which, c.stashed->tile0);
     } else if (defer) {
-        const long long tiles = (n_points + 63) / 64;
-        if (obj_views(s) != m->defer_ns) return fail(PNY_ERR_STATE, "deferred weight gradients: scene view count differs from the reservation");
-        if (m->defer_used[which] + tiles > m->defer_cap[which])
-            return fail(PNY_ERR_STATE, "deferred weight gradients: more tiles than pny_model_defer_weight_grads reserved");
-        chunk_pts = n_points;   // one chunk: the reservation was made against the budget
-        x_base = plan.lay.x_record(m->dx_stash[which].f(), m->defer_used[which]);
-        dy_base = plan.lay.dy_record(m->ddy_stash[which].f(), m->defer_used[which]);
-        m->defer_used[which] += tiles;
+        const long long tiles = (c.n_points + 63) / 64;
+        if (!ds.book.has_room(which, obj_views(s), tiles))
+            return fail(PNY_ERR_STATE, obj_views(s) != ds.book.ns ? "deferred weight gradients: scene view count differs from the reservation"
+                                                                  : "deferred weight gradients: more tiles than pny_model_defer_weight_grads reserved");
+        const long long tile0 = ds.book.take(which, tiles);
+        t->x = ds.x_record(lay, which, tile0);
+        t->dy = ds.dy_record(lay, which, tile0);
     } else {
-        if ((rc = s->x_stash.reserve((size_t)chunk_tiles_max * plan.lay.x_tile * sizeof(float)))) return rc;
-        if ((rc = s->dy_stash.reserve((size_t)chunk_tiles_max * plan.lay.dy_tile * sizeof(float)))) return rc;
-        x_base = s->x_stash.f();
-        dy_base = s->dy_stash.f();
+        // chunk boundaries on whole rays (mode 1) so that sample -> ray indexing stays local to the chunk
+        const long long unit = c.mode == 1 ? c.K : 1;
+        t->chunk_pts = std::max(unit, std::min(c.n_points, max_tiles * 64) / unit * unit);
+        const long long chunk_tiles_max = (t->chunk_pts + 63) / 64;
+        if ((rc = s->x_stash.reserve((size_t)chunk_tiles_max * lay.x_tile * sizeof(float)))) return rc;
+        if ((rc = s->dy_stash.reserve((size_t)chunk_tiles_max * lay.dy_tile * sizeof(float)))) return rc;
+        t->x = s->x_stash.f();
+        t->dy = s->dy_stash.f();
     }
-    if ((rc = s->out_tmp.reserve((size_t)chunk_pts * d.d_out * sizeof(float)))) return rc;
-    // running max |dY| for the split-f16 weight-gradient GEMM: per model and MLP in deferred mode (every scene's chain adds
-    // to it, zeroed again by the flush), per scene otherwise (zeroed in front of every chunk's chain)
-    const BwdRoute r = route_bwd(s);
-    if (r.chain == PREC_H1 && (rc = want_h1_images(m, true))) return rc;
-    unsigned* absmax = nullptr;
-    if (defer || have_x) {
-        if (r.gemm() == PREC_F32) m->defer_dw_f32 = true;
-        if (r.gemm() == PREC_H2) m->defer_dw_h2 = true;
-        if ((rc = ensure_absmax(m->d_absmax, 2 * sizeof(unsigned)))) return rc;
-        absmax = reinterpret_cast<unsigned*>(m->d_absmax.p) + which;
+    if (defer) {
+        ds.book.note_contributor(r.gemm());
+        if ((rc = ensure_absmax(ds.absmax, 2 * sizeof(unsigned)))) return rc;
+        t->absmax = ds.absmax_word(which);
     } else if (r.track_absmax) {
         if ((rc = ensure_absmax(s->dy_absmax, sizeof(unsigned)))) return rc;
-        absmax = reinterpret_cast<unsigned*>(s->dy_absmax.p);
+        t->absmax = reinterpret_cast<unsigned*>(s->dy_absmax.p);
     }
-    // Deterministic latent gradient (pny_model_set_deterministic, latent_grad_det.hip): the chain tracks this scene's own running
-    // max |dY| (handed on to `absmax` behind it), which sets the launch's fixed-point scale; the scene's int64 accumulator is
-    // all zero between launches
-    const bool lg_det = m->deterministic && s->latent_grad && view_blocks(d) > 0;
-    const long long lg_elems = (long long)s->ns * s->hl * s->wl * s->L;
-    unsigned* lg_max = nullptr;
-    if (lg_det) {   // (zeroed on THIS stream: a plain hipMemset would be ordered on the null stream, behind other scenes' work)
-        if (!s->lg_words.p) {
-            if ((rc = s->lg_words.reserve(32))) return rc;
-            PNY_HIP(hipMemsetAsync(s->lg_words.p, 0, 32, st));
-        }
-        lg_max = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(s->lg_words.p) + 20);
-        const size_t need = (size_t)lg_elems * sizeof(unsigned long long);
-        if (s->lg_fixed.bytes < need) {
-            if ((rc = s->lg_fixed.reserve(need))) return rc;
-            PNY_HIP(hipMemsetAsync(s->lg_fixed.p, 0, need, st));
-        }
+    return 0;
+}
+
+// Deterministic latent gradient (pny_model_set_deterministic, latent_grad_det.hip): the chain tracks this scene's own running
+// max |dY| (handed on to the stash target's word behind it), which sets the launch's fixed-point scale; the scene's int64 accumulator
+// is all zero between launches
+struct LatentGradDet {
+    bool on = false;
+    long long elems = 0;           // of the (ns, hl, wl, L) accumulator
+    unsigned* max_word = nullptr;  // 0 between launches: zeroed at allocation and reset by every deterministic launch
+};
+int latent_grad_det_setup(pny_scene* s, hipStream_t st, LatentGradDet* lg) {
+    lg->on = s->m->deterministic && s->latent_grad && view_blocks(s->m->desc) > 0;
+    lg->elems = (long long)s->ns * s->hl * s->wl * s->L;
+    if (!lg->on) return 0;
+    int rc;   // (zeroed on THIS stream: a plain hipMemset would be ordered on the null stream, behind other scenes' work)
+    if (!s->lg_words.p) {
+        if ((rc = s->lg_words.reserve(32))) return rc;
+        PNY_HIP(hipMemsetAsync(s->lg_words.p, 0, 32, st));
     }
+    lg->max_word = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(s->lg_words.p) + 20);
+    const size_t need = (size_t)lg->elems * sizeof(unsigned long long);
+    if (s->lg_fixed.bytes < need) {
+        if ((rc = s->lg_fixed.reserve(need))) return rc;
+        PNY_HIP(hipMemsetAsync(s->lg_fixed.p, 0, need, st));
+    }
+    return 0;
+}
+
+// Arguments of the dX chain over one chunk (np points from p0) whose forward output is `out`
+BwdArgs chain_args(const pny_scene* s, const MlpBackwardCall& c, int which, const BwdRoute& r, const StashLayout& lay, const StashTarget& t,
+                   const LatentGradDet& lg, const float* out, long long p0, long long np) {
+    const pny_model* m = s->m;
+    const pny_model_desc& d = m->desc;
+    const MlpWeightsT& wt = which ? m->fine_t : m->coarse_t;
+    BwdArgs b;
+    memset(&b, 0, sizeof(b));
+    b.wT_out = wt.wT_out;
+    for (int i = 0; i < d.n_blocks; ++i) {
+        b.wT_fc0[i] = wt.wT_fc0[i];
+        b.wT_fc1[i] = wt.wT_fc1[i];
+    }
+    b.w_base = m->packed.f();
+    b.w_bytes = (unsigned)m->packed.bytes;
+    b.x_stash = t.x;
+    b.dy_stash = t.dy;
+    b.lay = lay;
+    b.out = out;
+    b.d_out_grad = c.d_out + p0 * d.d_out;
+    b.n_points = np;
+    b.n_tiles = (int)((np + 63) / 64);
+    b.NS = obj_views(s);
+    b.n_blocks = d.n_blocks;
+    b.combine_layer = d.combine_layer;
+    b.d_out = d.d_out;
+    b.yolo = d.yolo;
+    b.dy_absmax = t.absmax;
+    b.range_flag = m->range_flag;
+    if (lg.on) {
+        b.dy_absmax = lg.max_word;
+        if (!t.absmax) b.range_flag = nullptr;   // (the fp32 path keeps its semantics: no f16 range guard)
+    }
+    // the chain's f16 images: split in the packed blob, single-plane in the model's h1 buffer (none: the fp32 chain)
+    if (r.chain != PREC_F32) use_images(b, f16_images(m, which == 1, r.chain == PREC_H1));
+    return b;
+}
+
+// Arguments of the depth-gradient kernel over the chunk of forward launch `a`: the selected samples' dL/dz through the MLP inputs
+DzArgs dz_args(const pny_scene* s, const MlpBackwardCall& c, int which, const MlpArgs& a, const StashLayout& lay, const float* dy,
+               const float* zp_maps, long long p0, long long np) {
+    const pny_model_desc& d = s->m->desc;
+    DzArgs dz;
+    memset(&dz, 0, sizeof(dz));
+    dz.dy_stash = dy;
+    dz.lay = lay;
+    dz.sel = c.dz_sel + (p0 / c.K) * c.kfd;
+    dz.n_sel = (int)((np / c.K) * c.kfd);
+    dz.p0 = p0;
+    dz.rays = c.rays;
+    dz.z = c.z;
+    dz.K = c.K;
+    dz.w_in = (which ? s->m->fine_t : s->m->coarse_t).w_in_plain;
+    dz.d_in = d_in(d);
+    dz.zp = zp_maps;
+    dz.zp_stride = view_blocks(d) * HID;
+    dz.NS = obj_views(s);
+    dz.obj_pts = a.obj_pts;
+    dz.Hl = s->hl;
+    dz.Wl = s->wl;
+    dz.yolo = d.yolo;
+    dz.num_freqs = d.num_freqs;
+    dz.freq_factor = d.freq_factor;
+    dz.sx = a.sx;
+    dz.sy = a.sy;
+    dz.dz = c.dz_out;
+    memcpy(dz.cams, s->cams, sizeof(Cam) * (size_t)s->ns);
+    return dz;
+}
+
+// Gradient w.r.t. the latent of the chunk of forward launch `a` (encoder training): lin_z^T GEMM off the dY tiles + scatter into the taps
+int latent_grad_step(pny_scene* s, const MlpArgs& a, int which, const BwdRoute& r, const StashLayout& lay, const StashTarget& t,
+                     const LatentGradDet& lg, hipStream_t st) {
+    const int nvb = view_blocks(s->m->desc);
+    const float* wzT_cat = (which ? s->m->fine_t : s->m->coarse_t).wzT_cat;
+    if (!wzT_cat) return fail(PNY_ERR_STATE, "latent gradient: transposed lin_z weights are missing");
+    if (s->L % 256) return fail(PNY_ERR_ARG, "latent gradient: d_latent must be a multiple of 256");
+    if (lg.on) {
+        int rc;
+        if ((rc = launch_latent_grad_det(a, t.dy, lay, wzT_cat, s->latent_grad, nvb, st, lg.max_word, r.gemm(),
+                                         reinterpret_cast<unsigned long long*>(s->lg_fixed.p), lg.elems, s->lg_words.p)))
+            return rc;
+    } else {
+        launch_latent_grad(a, t.dy, lay, wzT_cat, s->latent_grad, nvb, st, r.track_absmax ? t.absmax : nullptr, gemm_planes(r.gemm()));
+    }
+    s->last_lg_det = lg.on ? 1 : 0;
+    PNY_HIP(hipGetLastError());
+    return 0;
+}
+
+// Backward of one MLP evaluation: c.d_out -> bound parameter gradients (and the scene's latent and depth-sample gradients).
+int mlp_backward(pny_scene* s, const MlpBackwardCall& c, hipStream_t st) {
+    if (c.n_points == 0) return 0;
+    pny_model* m = s->m;
+    const pny_model_desc& d = m->desc;
+    const int which = mlp_index(m, c.coarse);
+    TrainPlan plan = build_plan(m, obj_views(s), s->L, which ? "mlp_fine." : "mlp_coarse.");
+    const StashLayout& lay = plan.lay;
+    const BwdRoute r = route_bwd(s);
+    int rc;
+    if (r.chain == PREC_H1 && (rc = want_h1_images(m, true))) return rc;
+    StashTarget t;
+    if ((rc = stash_target(s, c, lay, which, r, &t))) return rc;
+    if ((rc = s->out_tmp.reserve((size_t)t.chunk_pts * d.d_out * sizeof(float)))) return rc;
+    LatentGradDet lg;
+    if ((rc = latent_grad_det_setup(s, st, &lg))) return rc;
     auto stamp = [&]() { return stamp_event(s->timing, s->bev, s->bev_used, st); };   // kernel timing for bench.py
     {   // GEMM FLOPs of the three kernels
-        const double fwd = mlp_flops_per_point(d, obj_views(s), PASS_FORWARD) * (double)n_points;
-        if (!have_x) s->bwd_flops[0] += fwd;   // the forward already stashed: nothing is recomputed
-        s->bwd_flops[1] += mlp_flops_per_point(d, obj_views(s), PASS_CHAIN) * (double)n_points;
+        const double fwd = mlp_flops_per_point(d, obj_views(s), PASS_FORWARD) * (double)c.n_points;
+        if (!t.have_x) s->bwd_flops[0] += fwd;   // the forward already stashed: nothing is recomputed
+        s->bwd_flops[1] += mlp_flops_per_point(d, obj_views(s), PASS_CHAIN) * (double)c.n_points;
         s->bwd_flops[2] += fwd;   // every forward GEMM has one weight-gradient GEMM of the same size
     }
     const float* zp_maps = nullptr;
-    if (dz_sel && view_blocks(d) > 0) {
-        if ((rc = ensure_projection(s, fine_w ? 1 : 0, 0, st, &zp_maps, true))) return rc;
+    if (c.dz_sel && view_blocks(d) > 0) {
+        if ((rc = ensure_projection(s, which, 0, st, &zp_maps, true))) return rc;
         if (!zp_maps) return fail(PNY_ERR_ARG, "sample-depth gradients need the projected latent maps (latent too large)");
     }
-    for (long long p0 = 0; p0 < n_points; p0 += chunk_pts) {
-        const long long np = std::min(chunk_pts, n_points - p0);
+    const int cus = mlp_max_grid(MLP_8x64);
+    for (long long p0 = 0; p0 < c.n_points; p0 += t.chunk_pts) {
+        const long long np = std::min(t.chunk_pts, c.n_points - p0);
         const int n_tiles = (int)((np + 63) / 64);
-        // 1. forward in the reference's operation order, stashing every GEMM's B operand
+        const int grid = std::min(cus, n_tiles);
+        // 1. forward in the reference's operation order, stashing every GEMM's B operand (unless the forward call already did)
         MlpArgs a;
-        if ((rc = fill_mlp_args(s, mode, mode == 0 ? xyz + 3 * p0 : nullptr, mode == 0 ? dirs + 3 * p0 : nullptr,
-                                mode == 1 ? rays + (p0 / K) * 8 : nullptr, mode == 1 ? z + p0 : nullptr, K, np, coarse,
+        if ((rc = fill_mlp_args(s, c.mode, c.mode == 0 ? c.xyz + 3 * p0 : nullptr, c.mode == 0 ? c.dirs + 3 * p0 : nullptr,
+                                c.mode == 1 ? c.rays + (p0 / c.K) * 8 : nullptr, c.mode == 1 ? c.z + p0 : nullptr, c.K, np, c.coarse,
                                 s->out_tmp.f(), &a)))
             return rc;
-        a.stash_x = x_base;
-        a.lay = plan.lay;
-        const int grid = std::min(cus, n_tiles);
+        a.stash_x = t.x;
+        a.lay = lay;
         if ((rc = stamp())) return rc;
-        if (!have_x) {
+        if (!t.have_x) {
             launch_mlp_stash(a, grid, st);
             PNY_HIP(hipGetLastError());
         }
         if ((rc = stamp())) return rc;
         // 2. dX chain
-        const MlpWeightsT& wt = fine_w ? m->fine_t : m->coarse_t;
-        BwdArgs b;
-        memset(&b, 0, sizeof(b));
-        b.wT_out = wt.wT_out;
-        for (int i = 0; i < d.n_blocks; ++i) {
-            b.wT_fc0[i] = wt.wT_fc0[i];
-            b.wT_fc1[i] = wt.wT_fc1[i];
-        }
-        b.w_base = m->packed.f();
-        b.w_bytes = (unsigned)m->packed.bytes;
-        b.x_stash = x_base;
-        b.dy_stash = dy_base;
-        b.lay = plan.lay;
-        b.out = have_x ? fwd_out : s->out_tmp.f();
-        b.d_out_grad = d_out + p0 * d.d_out;
-        b.n_points = np;
-        b.n_tiles = n_tiles;
-        b.NS = obj_views(s);
-        b.n_blocks = d.n_blocks;
-        b.combine_layer = d.combine_layer;
-        b.d_out = d.d_out;
-        b.yolo = d.yolo;
-        b.dy_absmax = absmax;
-        b.range_flag = m->range_flag;
-        if (absmax && !(defer || have_x)) PNY_HIP(hipMemsetAsync(absmax, 0, sizeof(unsigned), st));
-        if (lg_det) {   // (lg_max is 0 here: zeroed at allocation and reset by every deterministic launch, latent_grad_det.hip)
-            b.dy_absmax = lg_max;
-            if (!absmax) b.range_flag = nullptr;   // (the fp32 path keeps its semantics: no f16 range guard)
-        }
-        // the chain's f16 images: split in the packed blob, single-plane in the model's h1 buffer (none: the fp32 chain)
-        if (r.chain != PREC_F32) use_images(b, f16_images(m, fine_w, r.chain == PREC_H1));
+        const BwdArgs b = chain_args(s, c, which, r, lay, t, lg, t.have_x ? c.fwd_out : s->out_tmp.f(), p0, np);
+        if (t.absmax && t.own_dw) PNY_HIP(hipMemsetAsync(t.absmax, 0, sizeof(unsigned), st));
         (r.chain == PREC_H1 ? launch_mlp_bwd_h1 : r.chain == PREC_H2 ? launch_mlp_bwd_h2 : launch_mlp_bwd)(b, grid, st);
         s->last_bwd_prec = r.chain;
         PNY_HIP(hipGetLastError());
-        if (lg_det && absmax) launch_absmax_fold(absmax, lg_max, st);
+        if (lg.on && t.absmax) launch_absmax_fold(t.absmax, lg.max_word, st);
         if ((rc = stamp())) return rc;
         // 2b. gradient w.r.t. the depths of the selected samples through the MLP inputs (fine pass of a render)
-        if (dz_sel && mode == 1) {
-            DzArgs dz;
-            memset(&dz, 0, sizeof(dz));
-            dz.dy_stash = dy_base;
-            dz.lay = plan.lay;
-            dz.sel = dz_sel + (p0 / K) * kfd;
-            dz.n_sel = (int)((np / K) * kfd);
-            dz.p0 = p0;
-            dz.rays = rays;
-            dz.z = z;
-            dz.K = K;
-            dz.w_in = wt.w_in_plain;
-            dz.d_in = d_in(d);
-            dz.zp = zp_maps;
-            dz.zp_stride = view_blocks(d) * HID;
-            dz.NS = obj_views(s);
-            dz.obj_pts = a.obj_pts;
-            dz.Hl = s->hl;
-            dz.Wl = s->wl;
-            dz.yolo = d.yolo;
-            dz.num_freqs = d.num_freqs;
-            dz.freq_factor = d.freq_factor;
-            dz.sx = a.sx;
-            dz.sy = a.sy;
-            dz.dz = dz_out;
-            memcpy(dz.cams, s->cams, sizeof(Cam) * (size_t)s->ns);
-            launch_mlp_dz(dz, st);
+        if (c.dz_sel && c.mode == 1) {
+            launch_mlp_dz(dz_args(s, c, which, a, lay, t.dy, zp_maps, p0, np), st);
             PNY_HIP(hipGetLastError());
         }
-        // 2c. gradient w.r.t. the latent (encoder training): lin_z^T GEMM off the dY stash + scatter into the taps
-        if (s->latent_grad && view_blocks(d) > 0) {
-            if (!wt.wzT_cat) return fail(PNY_ERR_STATE, "latent gradient: transposed lin_z weights are missing");
-            if (s->L % 256) return fail(PNY_ERR_ARG, "latent gradient: d_latent must be a multiple of 256");
-            if (lg_det) {
-                if ((rc = launch_latent_grad_det(a, dy_base, plan.lay, wt.wzT_cat, s->latent_grad, view_blocks(d), st, lg_max,
-                                                 r.gemm(), reinterpret_cast<unsigned long long*>(s->lg_fixed.p),
-                                                 lg_elems, s->lg_words.p)))
-                    return rc;
-            } else {
-                launch_latent_grad(a, dy_base, plan.lay, wt.wzT_cat, s->latent_grad, view_blocks(d), st, r.track_absmax ? absmax : nullptr,
-                                   gemm_planes(r.gemm()));
-            }
-            s->last_lg_det = lg_det ? 1 : 0;
-            PNY_HIP(hipGetLastError());
-        }
+        // 2c. gradient w.r.t. the latent
+        if (s->latent_grad && view_blocks(d) > 0 && (rc = latent_grad_step(s, a, which, r, lay, t, lg, st))) return rc;
         // 3. weight-gradient GEMMs over the two stashes + deterministic split reduction into the bound gradients
-        if (!defer && !have_x &&
-            (rc = run_weight_grads(m, plan, n_tiles, x_base, dy_base, s->dw_partial, s->dw_bias, s->dw_tables, s->table_stage,
-                                   (accumulate || p0 > 0) ? 1 : 0, st, absmax, gemm_planes(r.gemm()))))
+        if (t.own_dw &&
+            (rc = run_weight_grads(m, plan, n_tiles, t.x, t.dy, s->dw_partial, s->dw_bias, s->dw_tables, s->table_stage,
+                                   (c.accumulate || p0 > 0) ? 1 : 0, st, t.absmax, gemm_planes(r.gemm()))))
             return rc;
         if ((rc = stamp())) return rc;
     }
@@ -494,85 +553,85 @@ int pny_model_bind_grad(pny_model* m, const char* name, float* grad_dev) {
 
 int pny_model_defer_weight_grads(pny_model* m, int enable, int ns, int64_t coarse_tiles, int64_t fine_tiles) {
     if (!m) return fail(PNY_ERR_ARG, "pny_model_defer_weight_grads: null model");
-    m->defer = false;
-    m->defer_used[0] = m->defer_used[1] = 0;
-    ++m->defer_epoch;   // passes stashed under the previous reservation are no longer valid
+    DeferredStash& ds = m->stash;
+    ds.book.close();   // passes stashed under the previous reservation are no longer valid
     if (!enable) return PNY_OK;
     if (ns < 1 || ns > MAX_VIEWS || coarse_tiles < 0 || fine_tiles < 0) return fail(PNY_ERR_ARG, "pny_model_defer_weight_grads: bad argument");
     PNY_HIP(hipSetDevice(m->desc.device));
-    TrainPlan plan = build_plan(m, ns, m->desc.d_latent, "mlp_coarse.");   // the layout does not depend on the MLP
-    const size_t tile_bytes = (size_t)(plan.lay.x_tile + plan.lay.dy_tile) * sizeof(float);
+    const StashLayout lay = stash_layout(m->desc, ns, m->desc.d_latent);   // (does not depend on the MLP)
+    const size_t tile_bytes = (size_t)(lay.x_tile + lay.dy_tile) * sizeof(float);
     if ((size_t)(coarse_tiles + fine_tiles) * tile_bytes > stash_budget_bytes())
         return fail(PNY_ERR_ARG, "pny_model_defer_weight_grads: reservation exceeds the stash budget (PNYOLO_STASH_GB)");
-    const int64_t tiles[2] = {coarse_tiles, fine_tiles};
+    const long long tiles[2] = {coarse_tiles, fine_tiles};
     int rc;
     for (int w = 0; w < 2; ++w) {
-        if ((rc = m->dx_stash[w].reserve((size_t)tiles[w] * plan.lay.x_tile * sizeof(float)))) return rc;
-        if ((rc = m->ddy_stash[w].reserve((size_t)tiles[w] * plan.lay.dy_tile * sizeof(float)))) return rc;
-        m->defer_cap[w] = tiles[w];
+        if ((rc = ds.x[w].reserve((size_t)tiles[w] * lay.x_tile * sizeof(float)))) return rc;
+        if ((rc = ds.dy[w].reserve((size_t)tiles[w] * lay.dy_tile * sizeof(float)))) return rc;
     }
-    m->defer_ns = ns;
-    m->defer = true;
-    ++m->defer_epoch;
+    ds.book.open(ns, tiles);
     return PNY_OK;
 }
 
 int pny_model_flush_weight_grads(pny_model* m, int accumulate, pny_stream stream) {
     if (!m) return fail(PNY_ERR_ARG, "pny_model_flush_weight_grads: null model");
-    if (!m->defer) return fail(PNY_ERR_STATE, "pny_model_flush_weight_grads: not in deferred mode");
+    DeferredStash& ds = m->stash;
+    if (!ds.book.active) return fail(PNY_ERR_STATE, "pny_model_flush_weight_grads: not in deferred mode");
     PNY_HIP(hipSetDevice(m->desc.device));
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    if (!(accumulate & 16)) {   // (a coarse-only flush follows the fine-only one of the same step: keep its numbers)
-        m->flush_flops = 0.0;
-        m->flush_launches = 0;
+    // only mlp_coarse's / only mlp_fine's stash (neither: both)
+    const bool only_c = (accumulate & PNY_FLUSH_COARSE_ONLY) != 0, only_f = (accumulate & PNY_FLUSH_FINE_ONLY) != 0;
+    accumulate &= PNY_ACC_ADD;
+    if (!only_c) {   // (a coarse-only flush follows the fine-only one of the same step: keep its numbers)
+        ds.flush_flops = 0.0;
+        ds.flush_launches = 0;
     }
     for (int i = 0; i < 4; ++i)
-        if (!m->flush_ev[i]) PNY_HIP(hipEventCreate(&m->flush_ev[i]));
+        if (!ds.flush_ev[i]) PNY_HIP(hipEventCreate(&ds.flush_ev[i]));
     const pny_model_desc& d = m->desc;
-    const double fwd = mlp_flops_per_point(d, m->defer_ns, PASS_FORWARD);
-    // bits 16 / 32 of `accumulate`: only mlp_coarse's / only mlp_fine's stash (0: both)
-    const bool only_c = (accumulate & 16) != 0, only_f = (accumulate & 32) != 0;
-    accumulate &= 1;
+    const double fwd = mlp_flops_per_point(d, ds.book.ns, PASS_FORWARD);
+    const int last = only_c ? 0 : 1;   // the last MLP this call flushes
     for (int w = 0; w < 2; ++w) {
         if ((w == 0 && only_f) || (w == 1 && only_c)) continue;
-        PNY_HIP(hipEventRecord(m->flush_ev[2 * w], st));
-        if (m->defer_used[w] > 0) {
-            TrainPlan plan = build_plan(m, m->defer_ns, d.d_latent, w ? "mlp_fine." : "mlp_coarse.");
-            const unsigned* absmax = (m->d_absmax.p && !m->defer_dw_f32) ? reinterpret_cast<const unsigned*>(m->d_absmax.p) + w : nullptr;
-            // single-plane GEMM only when every contributor ran the F16_TRAIN backward (any F32 one: fp32, else split-f16)
-            const Prec gemm = !absmax ? PREC_F32 : m->defer_dw_h2 ? PREC_H2 : PREC_H1;
-            if ((rc = run_weight_grads(m, plan, (int)m->defer_used[w], m->dx_stash[w].f(), m->ddy_stash[w].f(), m->d_partial[w],
-                                       m->d_bias[w], m->d_tables[w], m->d_stage[w], accumulate, st, absmax, gemm_planes(gemm))))
+        PNY_HIP(hipEventRecord(ds.flush_ev[2 * w], st));
+        const long long n_tiles = ds.book.used[w];
+        if (n_tiles > 0) {
+            TrainPlan plan = build_plan(m, ds.book.ns, d.d_latent, w ? "mlp_fine." : "mlp_coarse.");
+            const Prec gemm = ds.book.flush_gemm(ds.absmax.p != nullptr);
+            const unsigned* absmax = gemm == PREC_F32 ? nullptr : ds.absmax_word(w);   // the f16 GEMMs scale by the running max |dY|
+            if ((rc = run_weight_grads(m, plan, (int)n_tiles, ds.x_record(plan.lay, w, 0), ds.dy_record(plan.lay, w, 0), ds.partial[w],
+                                       ds.bias[w], ds.tables[w], ds.stage[w], accumulate, st, absmax, gemm_planes(gemm))))
                 return rc;
-            m->flush_flops += fwd * 64.0 * (double)m->defer_used[w];
-            m->last_flush_prec = gemm;
-            m->flush_launches += 1;
+            ds.flush_flops += fwd * 64.0 * (double)n_tiles;
+            ds.last_flush_prec = gemm;
+            ds.flush_launches += 1;
         }
-        PNY_HIP(hipEventRecord(m->flush_ev[2 * w + 1], st));
-        m->defer_used[w] = 0;
-        if (m->d_absmax.p)   // the next step's chains start from 0
-            PNY_HIP(hipMemsetAsync(reinterpret_cast<unsigned*>(m->d_absmax.p) + w, 0, sizeof(unsigned), st));
+        PNY_HIP(hipEventRecord(ds.flush_ev[2 * w + 1], st));
+        // (contributors: a fine-only flush is followed by the coarse-only one of the same step)
+        ds.book.flushed(w, w == last && !only_f);
+        if (unsigned* word = ds.absmax_word(w))   // the next step's chains start from 0
+            PNY_HIP(hipMemsetAsync(word, 0, sizeof(unsigned), st));
     }
-    if (!only_f) m->defer_dw_f32 = m->defer_dw_h2 = false;   // (a fine-only flush is followed by the coarse-only one of the same step)
     return PNY_OK;
 }
 
+
 int pny_model_last_flush_precision(pny_model* m, int* code) {
     if (!m || !code) return fail(PNY_ERR_ARG, "pny_model_last_flush_precision: null argument");
-    *code = m->last_flush_prec;
+    *code = m->stash.last_flush_prec;
     return PNY_OK;
 }
 
 int pny_model_last_flush_stats(pny_model* m, double* flops, double* kernel_ms) {
     if (!m) return fail(PNY_ERR_ARG, "pny_model_last_flush_stats: null model");
-    if (flops) *flops = m->flush_flops;
+    const DeferredStash& ds = m->stash;
+    if (flops) *flops = ds.flush_flops;
     if (kernel_ms) {
         *kernel_ms = 0.0;
-        for (int w = 0; w < 2 && m->flush_ev[0]; ++w) {
-            PNY_HIP(hipEventSynchronize(m->flush_ev[2 * w + 1]));
+        for (int w = 0; w < 2 && ds.flush_ev[0]; ++w) {
+            PNY_HIP(hipEventSynchronize(ds.flush_ev[2 * w + 1]));
             float ms = 0.f;
-            PNY_HIP(hipEventElapsedTime(&ms, m->flush_ev[2 * w], m->flush_ev[2 * w + 1]));
+            PNY_HIP(hipEventElapsedTime(&ms, ds.flush_ev[2 * w], ds.flush_ev[2 * w + 1]));
             *kernel_ms += ms;
         }
     }
@@ -581,7 +640,7 @@ int pny_model_last_flush_stats(pny_model* m, double* flops, double* kernel_ms) {
 
 int pny_scene_stash_next_render(pny_scene* s, int enable) {
     if (!s) return fail(PNY_ERR_ARG, "pny_scene_stash_next_render: null scene");
-    if (enable && !s->m->defer) return fail(PNY_ERR_STATE, "pny_scene_stash_next_render: reserve the stash first (pny_model_defer_weight_grads)");
+    if (enable && !s->m->stash.book.active) return fail(PNY_ERR_STATE, "pny_scene_stash_next_render: reserve the stash first (pny_model_defer_weight_grads)");
     s->stash_next = enable != 0;
     return PNY_OK;
 }
@@ -597,8 +656,16 @@ int pny_query_backward(pny_scene* s, const float* xyz_dev, const float* viewdirs
     s->bwd_flops[0] = s->bwd_flops[1] = s->bwd_flops[2] = 0.0;
     // immediate: a deferred reservation that a training pny_render left outstanding belongs to that render's backward; this
     // call's weight gradients go straight into the buffers bound now
-    return mlp_backward(s, 0, xyz_dev, viewdirs_dev, nullptr, nullptr, 1, n, coarse, d_out_dev, accumulate & 1, (hipStream_t)stream,
-                        nullptr, 0, nullptr, nullptr, nullptr, true);
+    MlpBackwardCall c;
+    c.mode = 0;
+    c.xyz = xyz_dev;
+    c.dirs = viewdirs_dev;
+    c.n_points = n;
+    c.coarse = coarse;
+    c.d_out = d_out_dev;
+    c.accumulate = accumulate & PNY_ACC_ADD;
+    c.immediate = true;
+    return mlp_backward(s, c, (hipStream_t)stream);
 }
 
 int pny_composite_backward(const float* rays_dev, const float* z_dev, const float* sample_dev, int64_t n, int k, int white_bkgd,
@@ -630,11 +697,11 @@ int pny_render_backward(pny_scene* s, const float* rays_dev, int64_t n, const pn
     s->bev_used = 0;
     s->bwd_flops[0] = s->bwd_flops[1] = s->bwd_flops[2] = 0.0;
     if ((rc = s->d_samp.reserve((size_t)n * kt * 4 * sizeof(float)))) return rc;
-    const bool same_mlp = !s->m->desc.has_fine || !s->m->use_fine;  // both passes differentiate mlp_coarse
-    const bool immediate = (accumulate & 2) != 0;   // ignore a deferred reservation that belongs to another forward
-    // bits 4 / 8: only the fine / only the coarse pass of this backward (the caller runs every scene's fine pass, starts the
-    // fine MLP's weight-gradient flush beside the coarse passes, then the coarse passes: pny_model_flush_weight_grads)
-    const bool do_fine = (accumulate & 8) == 0, do_coarse = (accumulate & 4) == 0;
+    const bool same_mlp = mlp_index(s->m, 0) == 0;  // both passes differentiate mlp_coarse
+    const bool immediate = (accumulate & PNY_ACC_IMMEDIATE) != 0;   // ignore a deferred reservation that belongs to another forward
+    // only the fine / only the coarse pass of this backward (the caller runs every scene's fine pass, starts the fine MLP's
+    // weight-gradient flush beside the coarse passes, then the coarse passes: pny_model_flush_weight_grads)
+    const bool do_fine = (accumulate & PNY_ACC_COARSE_ONLY) == 0, do_coarse = (accumulate & PNY_ACC_FINE_ONLY) == 0;
     bool first = true;
     const bool any_f = o->n_fine > 0 && (g->rgb_fine || g->depth_fine || g->weights_fine);
     const bool any_c = g->rgb_coarse || g->depth_coarse || g->weights_coarse;
@@ -644,16 +711,21 @@ int pny_render_backward(pny_scene* s, const float* rays_dev, int64_t n, const pn
     const int kfd = o->n_fine_depth;
     const bool depth_path = any_f && kfd > 0 && sv->depth_coarse;
     {   // a pass that was stashed by the forward but receives no gradient must not leave stale dY tiles for the flush
-        pny_model* m = s->m;
-        const StashLayout lay = stash_layout(m->desc, obj_views(s), s->L);
-        auto zero_pass = [&](const pny_scene::StashedPass& sp) -> int {
-            if (sp.valid && m->defer && !immediate && sp.epoch == m->defer_epoch)
-                PNY_HIP(hipMemsetAsync(lay.dy_record(m->ddy_stash[sp.which].f(), sp.tile0), 0, (size_t)sp.tiles * lay.dy_tile * sizeof(float), st));
+        const DeferredStash& ds = s->m->stash;
+        const StashLayout lay = stash_layout(s->m->desc, obj_views(s), s->L);
+        auto zero_pass = [&](const StashedPass& sp) -> int {
+            if (!immediate && ds.book.owns(sp))
+                PNY_HIP(hipMemsetAsync(ds.dy_record(lay, sp.which, sp.tile0), 0, (size_t)sp.tiles * lay.dy_tile * sizeof(float), st));
             return 0;
         };
         if (do_fine && !any_f && (rc = zero_pass(s->stashed[1]))) return rc;
         if (do_coarse && !(any_c || depth_path) && (rc = zero_pass(s->stashed[0]))) return rc;
     }
+    MlpBackwardCall pass;   // what the two passes share; each fills in its own depths, gradient extras and stashed pass
+    pass.mode = 1;
+    pass.rays = rays_dev;
+    pass.d_out = s->d_samp.f();
+    pass.immediate = immediate;
     const float* g_depth_c = g->depth_coarse;
     if (any_f && !do_fine) {   // coarse-only call: the fine pass of this backward ran in an earlier call and left the depth path's sum
         if (depth_path) g_depth_c = s->gdepth_tmp.f();
@@ -674,9 +746,17 @@ int pny_render_backward(pny_scene* s, const float* rays_dev, int64_t n, const pn
         launch_composite_bwd(rays_dev, sv->z_fine, sv->sample_fine, o->sigma_noise_fine_dev, n, kt, o->white_bkgd, g->rgb_fine,
                              g->depth_fine, g->weights_fine, s->d_samp.f(), dz, st);
         PNY_HIP(hipGetLastError());
-        if ((rc = mlp_backward(s, 1, nullptr, nullptr, rays_dev, sv->z_fine, kt, (long long)n * kt, 0, s->d_samp.f(), accumulate & 1, st,
-                               sel, kfd, dz, &s->stashed[1], sv->sample_fine, immediate)))
-            return rc;
+        pass.z = sv->z_fine;
+        pass.K = kt;
+        pass.n_points = (long long)n * kt;
+        pass.coarse = 0;
+        pass.accumulate = accumulate & PNY_ACC_ADD;
+        pass.dz_sel = sel;
+        pass.kfd = kfd;
+        pass.dz_out = dz;
+        pass.stashed = &s->stashed[1];
+        pass.fwd_out = sv->sample_fine;
+        if ((rc = mlp_backward(s, pass, st))) return rc;
         if (depth_path) {
             launch_depth_grad_gather(sel, dz, g->depth_coarse, n, kfd, s->gdepth_tmp.f(), st);
             PNY_HIP(hipGetLastError());
@@ -688,10 +768,17 @@ int pny_render_backward(pny_scene* s, const float* rays_dev, int64_t n, const pn
         launch_composite_bwd(rays_dev, sv->z_coarse, sv->sample_coarse, o->sigma_noise_coarse_dev, n, kc, o->white_bkgd, g->rgb_coarse,
                              g_depth_c, g->weights_coarse, s->d_samp.f(), nullptr, st);
         PNY_HIP(hipGetLastError());
-        if ((rc = mlp_backward(s, 1, nullptr, nullptr, rays_dev, sv->z_coarse, kc, (long long)n * kc, 1, s->d_samp.f(),
-                               ((accumulate & 1) || (same_mlp && !first)) ? 1 : 0, st, nullptr, 0, nullptr, &s->stashed[0],
-                               sv->sample_coarse, immediate)))
-            return rc;
+        pass.z = sv->z_coarse;
+        pass.K = kc;
+        pass.n_points = (long long)n * kc;
+        pass.coarse = 1;
+        pass.accumulate = ((accumulate & PNY_ACC_ADD) || (same_mlp && !first)) ? 1 : 0;
+        pass.dz_sel = nullptr;
+        pass.kfd = 0;
+        pass.dz_out = nullptr;
+        pass.stashed = &s->stashed[0];
+        pass.fwd_out = sv->sample_coarse;
+        if ((rc = mlp_backward(s, pass, st))) return rc;
     }
     return PNY_OK;
 }
@@ -756,8 +843,17 @@ int pny_yolo_render_backward(pny_scene* s, const float* rays_dev, int64_t n, int
     launch_sample_coarse(rays_dev, n, n_coarse, 0, u_coarse_dev, seed, z, st);   // the forward's depths (same draws)
     launch_yolo_aggregate_bwd(raw_dev, g_out_dev, n, n_coarse, d.d_out / 7, s->d_samp.f(), st);
     PNY_HIP(hipGetLastError());
-    return mlp_backward(s, 1, nullptr, nullptr, rays_dev, z, n_coarse, (long long)n * n_coarse, 1, s->d_samp.f(), accumulate & 1, st,
-                        nullptr, 0, nullptr, nullptr, nullptr, true);   // immediate (see pny_query_backward)
+    MlpBackwardCall c;
+    c.mode = 1;
+    c.rays = rays_dev;
+    c.z = z;
+    c.K = n_coarse;
+    c.n_points = (long long)n * n_coarse;
+    c.coarse = 1;
+    c.d_out = s->d_samp.f();
+    c.accumulate = accumulate & PNY_ACC_ADD;
+    c.immediate = true;   // (see pny_query_backward)
+    return mlp_backward(s, c, st);
 }
 
 int pny_scene_last_backward_stats(pny_scene* s, double flops[3], double kernel_ms[3]) {

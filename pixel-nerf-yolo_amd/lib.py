@@ -247,6 +247,9 @@ RESIZE = {"none": 0, "bilinear_u8": 1, "area": 2}             # PNY_RESIZE_*
 YOLO_TARGETS_MAX_ANCHORS = 64                                 # PNY_YOLO_TARGETS_MAX_ANCHORS
 MC_SCAN_TILE, MC_MAX_POINTS = 1024, (2 ** 31 - 1) // 3        # csrc/pny_recon.h: points per scan tile; 3 X Y Z < 2^31
 MAX_LATENT_LEVELS = 8                                         # PNY_MAX_LATENT_LEVELS
+# bits of the `accumulate` argument of the backward calls and of pny_model_flush_weight_grads (include/pnyolo.h)
+ACC_ADD, ACC_IMMEDIATE, ACC_FINE_ONLY, ACC_COARSE_ONLY = 1, 2, 4, 8    # PNY_ACC_*
+FLUSH_COARSE_ONLY, FLUSH_FINE_ONLY = 16, 32                            # PNY_FLUSH_*
 
 
 class PnyError(RuntimeError):

@@ -1164,7 +1164,7 @@ class _QueryFunction(torch.autograd.Function):
         lat_grad = net.begin_latent_grad(ctx.lat_meta, scenes) if ctx.lat_meta is not None else None
         for sb in range(SB):
             check(L.pny_query_backward(scenes[sb], ptr(ctx.xyz[sb]), ptr(ctx.dirs[sb]), ctx.xyz.shape[1], int(use_coarse),
-                                       ptr(g_out[sb]), 1, st))
+                                       ptr(g_out[sb]), _lib.ACC_ADD, st))
         extra = () if lat_grad is None else (net.end_latent_grad(lat_grad, ctx.lat_meta, scenes),)
         net._lat_grad_event = None      # (unmarked: a trunk backward behind this one waits for the whole stream)
         return (None, None, None, None, None) + tuple(grads) + extra

@@ -343,9 +343,9 @@ class _RenderFunction(torch.autograd.Function):
 
         ups = [prep(x) for x in (g_rgb_c, g_depth_c, g_w_c, g_rgb_f, g_depth_f, g_w_f)]
         # The reservation made by the forward is still ours unless another training forward ran in between: then this
-        # call computes its weight gradients immediately (accumulate bit 1), scene after scene, with recompute.
+        # call computes its weight gradients immediately (ACC_IMMEDIATE), scene after scene, with recompute.
         deferred = ctx.deferred and getattr(model, "_defer_token", None) == ctx.token
-        acc = 1 if deferred else 3
+        acc = _lib.ACC_ADD if deferred else _lib.ACC_ADD | _lib.ACC_IMMEDIATE
         group = bool(sv.get("group"))
         if group and not deferred:
             raise RuntimeError("the grouped training forward lost its stash reservation (another training forward ran before "
@@ -380,7 +380,7 @@ class _RenderFunction(torch.autograd.Function):
         fstream = None
         if split:
             for g in range(G):
-                run(g, 4)      # (bit 4: the fine pass only; bit 8: the coarse pass only -- include/pnyolo.h pny_render_backward)
+                run(g, _lib.ACC_FINE_ONLY)      # (the fine pass only; the coarse passes follow -- include/pnyolo.h pny_render_backward)
             main = torch.cuda.current_stream(dev)
             fstream = getattr(model, "_flush_stream", None)
             if fstream is None or fstream.device != dev:
@@ -390,9 +390,9 @@ class _RenderFunction(torch.autograd.Function):
                 if st_ is not None:
                     fstream.wait_stream(st_)
             with torch.cuda.stream(fstream):
-                check(L.pny_model_flush_weight_grads(model._h_model, 1 | 32, stream_of(dev)))
+                check(L.pny_model_flush_weight_grads(model._h_model, _lib.ACC_ADD | _lib.FLUSH_FINE_ONLY, stream_of(dev)))
         for g in range(G):
-            run(g, 8 if split else 0)
+            run(g, _lib.ACC_COARSE_ONLY if split else 0)
         if deferred:
             model.join_streams(streams)
         # d loss / d latent is complete here, BEFORE the weight-gradient flush is enqueued: the encoder's backward (the trunk's
@@ -400,7 +400,7 @@ class _RenderFunction(torch.autograd.Function):
         extra = () if lat_grad is None else (model.end_latent_grad(lat_grad, ctx.lat_meta, handles),)
         _mark_latent_grad(model, extra, dev)
         if deferred:
-            check(L.pny_model_flush_weight_grads(model._h_model, 1 | (16 if split else 0), stream_of(dev)))
+            check(L.pny_model_flush_weight_grads(model._h_model, _lib.ACC_ADD | (_lib.FLUSH_COARSE_ONLY if split else 0), stream_of(dev)))
             if fstream is not None:
                 torch.cuda.current_stream(dev).wait_stream(fstream)
             check(L.pny_model_defer_weight_grads(model._h_model, 0, 0, 0, 0))
@@ -702,7 +702,7 @@ class _YoloRenderFunction(torch.autograd.Function):
         scene = net._scene(0)
         lat_grad = net.begin_latent_grad(ctx.lat_meta, [scene]) if ctx.lat_meta is not None else None
         check(L.pny_yolo_render_backward(scene, ptr(sv["rays"]), sv["rays"].shape[0], sv["n_coarse"], ptr(sv["u"]),
-                                         sv["seed"], ptr(sv["raw"]), ptr(g_out), 1, stream_of(dev)))
+                                         sv["seed"], ptr(sv["raw"]), ptr(g_out), _lib.ACC_ADD, stream_of(dev)))
         extra = () if lat_grad is None else (net.end_latent_grad(lat_grad, ctx.lat_meta, [scene]),)
         net._lat_grad_event = None      # (unmarked: a trunk backward behind this one waits for the whole stream)
         return (None, None, None) + tuple(grads) + extra

@@ -5,7 +5,7 @@ recompute term of last_backward_stats).  The expected values are written out fro
 (pny_scene_set_projection, pny_scene_set_precision, PNY_PRECISION_*), not computed by a copy of the routing code.
 
 Tiny models (2 residual blocks, combine_layer 1, d_latent 128 / 256, a 4 x 4 latent map, 1 / 2 views) with in-range random
-weights: nothing here is an error path (tests/test_gpu_range.py covers those), and no value is compared but one bit-identity.
+weights: nothing here is an error path (tests/test_gpu_range.py covers those), and no value is compared but for bit-identity.
 """
 import ctypes as C
 
@@ -219,9 +219,9 @@ def abi_train_step(coarse_tiles, fine_tiles, immediate):
                              depth_coarse=res["coarse"]["depth"][0].data_ptr())
     up = plib.RenderGrads(rgb_coarse=g.data_ptr(), rgb_fine=g.data_ptr())
     plib.check(L.pny_render_backward(net._scene(0), plib.ptr(sv["rays"][0]), B, C.byref(sv["opts"][0]), C.byref(saved),
-                                     C.byref(up), 1 | (2 if immediate else 0), st))
+                                     C.byref(up), plib.ACC_ADD | (plib.ACC_IMMEDIATE if immediate else 0), st))
     if not immediate:
-        plib.check(L.pny_model_flush_weight_grads(net._h_model, 1, st))
+        plib.check(L.pny_model_flush_weight_grads(net._h_model, plib.ACC_ADD, st))
     plib.check(L.pny_model_defer_weight_grads(net._h_model, 0, 0, 0, 0))
     torch.cuda.synchronize()
     assert all(bool(torch.isfinite(t).all()) for t in grads)
@@ -237,3 +237,56 @@ def test_reservation_one_tile_too_small():
     fwd, bwd, flops = abi_train_step(1, 1, immediate=True)
     assert fwd == ("f32", False) and bwd == "f16x2"
     assert flops[0] > 0.0 and flops[0] == flops[2]     # every forward GEMM recomputed once
+
+
+def reservation_net(lat_grad):
+    """(net, target pose, latent or None) of the foreign-backward test: the AUTO training net; lat_grad = a latent that requires
+    grad under the deterministic latent gradient, so that every gradient of the step has a fixed order of summation."""
+    net, tgt = tiny_net(256, 2, prec="auto", train=True)
+    lat = None
+    if lat_grad:
+        net.set_deterministic(True)
+        lat = torch.from_numpy(synth.latent(5107, 2, 256, HL, WL)).to(DEV).requires_grad_()
+        net.encode(torch.zeros(1, 2, 3, H, W), torch.from_numpy(synth.scene_cameras(2)[0])[None], torch.tensor(0.9 * W), latent=lat)
+    return net, tgt, lat
+
+
+def render_loss(net, tgt):
+    ren = NeRFRenderer(n_coarse=KC, n_fine=KF, n_fine_depth=KFD, white_bkgd=True).train()
+    out = ren(net, rays_of(tgt, B)[None], want_weights=True)
+    return out["coarse"]["rgb"].sum() + out["fine"]["rgb"].sum()
+
+
+def query_loss(net, n=65):      # two tiles, the second partial
+    rs = np.random.RandomState(n)
+    xyz = torch.from_numpy(rs.uniform(-0.3, 0.3, size=(1, n, 3)).astype(np.float32)).to(DEV)
+    vd = torch.nn.functional.normalize(torch.from_numpy(rs.standard_normal((1, n, 3)).astype(np.float32)), dim=-1).to(DEV)
+    return net(xyz, coarse=True, viewdirs=vd).sum()
+
+
+@pytest.mark.parametrize("lat_grad", (False, True), ids=("frozen_trunk", "deterministic_latent_grad"))
+def test_backward_on_someone_elses_reservation(lat_grad):
+    """A query's backward while a training render's reservation is outstanding: it computes its weight gradients at once from
+    the scene's own stash and leaves the reservation alone, so the render's backward still starts at the chain.  The weight-gradient
+    reduction has a fixed order and a two-term fp32 sum does not depend on its order: every gradient equals, bit for bit, the
+    sum of the two backwards run alone on fresh identical nets."""
+    net, tgt, lat = reservation_net(lat_grad)
+    l_render = render_loss(net, tgt)             # stashes into the reservation it made
+    l_query = query_loss(net)
+    l_query.backward()                           # not the reservation's owner
+    l_render.backward()
+    torch.cuda.synchronize()
+    assert net.last_backward_stats()["flops"][0] == 0.0      # the render's backward recomputed nothing
+    alone = []
+    for loss in (lambda n_, t_: render_loss(n_, t_), lambda n_, t_: query_loss(n_)):
+        other, tgt2, lat2 = reservation_net(lat_grad)
+        loss(other, tgt2).backward()
+        torch.cuda.synchronize()
+        assert lat2 is None or bool(torch.isfinite(lat2.grad).all())
+        alone.append({k: p.grad for k, p in other.trainable_mlp_parameters()})
+    named = net.trainable_mlp_parameters()
+    assert len(named) > 0 and set(alone[0]) == set(alone[1]) == {k for k, _ in named}
+    for k, p in named:
+        assert torch.equal(p.grad, alone[0][k] + alone[1][k]), k
+    if lat_grad:
+        assert net.last_latent_grad_deterministic() and bool(torch.isfinite(lat.grad).all())
