@@ -52,15 +52,25 @@ def oracle_scene(g, seed):
     return orc.Scene(mc, mf, lat, g["src_poses"], g["focal"], g["c"][None], W, H)
 
 
+def camera_ring(ns):
+    """(ns source poses, target pose) for any view count up to the ABI's 16: no two views share a camera.
+    synth.scene_cameras steps theta by 40 degrees, so its view 9 is its view 0 again and a kernel that confused the two
+    would go unnoticed; here theta steps by 22.5 degrees (16 views: 3 .. 340.5), the elevation cycles through five values
+    and the radius grows with the view."""
+    src = np.stack([synth.pose_spherical(22.5 * i + 3.0, -35.0 + 4.0 * (i % 5), 1.3 + 0.03 * i) for i in range(ns)])
+    return src, synth.pose_spherical(120.0, -20.0, 1.3)
+
+
 # --------------------------------------------------------------------------- MLP (query) backward
 def scene_pair(ns, H, W, L, d_out, n_blocks, combine_layer, seed, yolo=False, lat_hw=None, lat_grad=False, dtype=None,
-               yolo_flip=True, with_net=True):
+               yolo_flip=True, with_net=True, poses=None):
     """The same seeded scene as a HIP net (trainable MLP, frozen encoder) and as oracle state with requires_grad.
     lat_grad: the latent is a leaf that requires grad on both sides (net.test_latent on the GPU, sc.latent on the CPU).
     dtype: the oracle's arithmetic and the dtype of its leaves (None = f32; torch.float64 = the arbiter of the shape sweeps).
     yolo_flip=False (YOLO mode): world->cam extrinsics of cameras looking down -z, so that the scene lies at z < 0, where YOLO
     mode keeps the latent (models.py:224,254-264 zero it at z >= 0); the default flips y / z, which puts the scene at z > 0.
-    with_net=False: the oracle scene alone (net is None; no GPU needed)."""
+    with_net=False: the oracle scene alone (net is None; no GPU needed).
+    poses (non-YOLO mode): (ns, 4, 4) source poses instead of synth.scene_cameras(ns), e.g. camera_ring(ns)[0]."""
     import pnyolo_oracle as orc
     c = pconf.yolo() if yolo else pconf.default_mv()
     m = c.d["model"]
@@ -84,7 +94,10 @@ def scene_pair(ns, H, W, L, d_out, n_blocks, combine_layer, seed, yolo=False, la
         poses = np.stack([np.linalg.inv(p @ flipyz) for p in src_c2w]).astype(np.float32)
         focal, cc = torch.tensor([[40.0, 44.0]]), torch.tensor([[W * 0.5, H * 0.5 - 2]])
     else:
-        poses, _ = synth.scene_cameras(ns)
+        if poses is None:
+            poses, _ = synth.scene_cameras(ns)
+        poses = np.asarray(poses, dtype=np.float32)
+        assert poses.shape == (ns, 4, 4)
         focal, cc = torch.tensor(0.9 * W), torch.tensor([[W * 0.5, H * 0.5]])
     if with_net:
         net = net.to(DEV).train()

@@ -9,7 +9,8 @@ tiles (one tile: the latent gradient's one-tile kernel; two or more: its pair-of
 last pair half empty; a ragged last tile; >= 40 tiles), where the points project (every tap inside, taps straddling the
 grid edge, wholly outside one view but inside another: out-of-range taps are dropped), YOLO mode (d_out 21, L 1792, points
 behind a camera culled) and a grouped super-batch whose tile pairs span two objects.  Every case asserts on its own inputs
-that its edges occur.
+that its edges occur.  A second table, MANY_VIEW_CASES, runs 5, 8, 11 and 16 views per object (16 is the ABI's limit) on
+cameras that are all distinct, through the same body, legs and bars.
 
 Arithmetic legs (the backward's matrix products; test_gpu_backward.py has the same legs as a module fixture):
   f32            fp32 forward, fp32 backward                          1e-4 x each tensor's max, points with relu margin AMBIG
@@ -27,7 +28,7 @@ import pytest
 import torch
 
 import pnyolo_oracle as orc
-from helpers import DEV, RTOL, clean_rays, dt, grad_check, scene_pair
+from helpers import DEV, RTOL, camera_ring, clean_rays, dt, grad_check, scene_pair
 from pixel_nerf_yolo_amd import conf as pconf
 from pixel_nerf_yolo_amd import synth
 from pixel_nerf_yolo_amd.model import make_model
@@ -61,6 +62,27 @@ CASES = {
     "2-0_ns2_L512_8x8_2tiles_inside": dict(nb=2, cl=0, ns=2, L=512, hw=(8, 8), n=90, proj="inside"),
     "yolo_5-3_ns2_L1792_12x20_3tiles_culled": dict(nb=5, cl=3, ns=2, L=1792, hw=(12, 20), n=150, proj="straddle", yolo=True),
 }
+# 5 to 16 views per object (the ABI's limit) on helpers.camera_ring, whose views are all distinct: the 1 / NS scaling for NS
+# that is no power of two, the stash records' NS-sized strides, the latent gradient's grid n_tiles * NS * (L / 256) and its
+# pair-of-tiles decode (an odd tile count at 16 views), all 16 cameras of the kernel arguments.  A table of its own, so that
+# the seeds of CASES (from a case's place in that table) stay what they were; at these view counts fewer random points are
+# relu-safe (tests/test_cpu_many_views.py, profiles/many_views.md), so the points are picked from a pool MANY_VIEW_POOL x the need.
+MANY_VIEW_CASES = {
+    "5-3_ns16_L512_16x16_2tiles_inside": dict(nb=5, cl=3, ns=16, L=512, hw=(16, 16), n=128, proj="inside"),
+    "5-3_ns16_L512_16x16_3tiles_ragged_straddle": dict(nb=5, cl=3, ns=16, L=512, hw=(16, 16), n=130, proj="straddle"),
+    "2-1_ns16_L512_8x8_2tiles_outside": dict(nb=2, cl=1, ns=16, L=512, hw=(8, 8), n=128, proj="outside"),
+    "6-4_ns11_L1792_8x8_2tiles_straddle": dict(nb=6, cl=4, ns=11, L=1792, hw=(8, 8), n=128, proj="straddle"),
+    "5-3_ns5_L512_16x16_2tiles_ragged_outside": dict(nb=5, cl=3, ns=5, L=512, hw=(16, 16), n=70, proj="outside"),
+    "3-2_ns8_L512_5x9_4tiles_ragged_straddle": dict(nb=3, cl=2, ns=8, L=512, hw=(5, 9), n=200, proj="straddle"),
+}
+for _c in MANY_VIEW_CASES.values():
+    _c["ring"] = True
+POOL, MANY_VIEW_POOL = 1.6, 4.0
+# The seed base is chosen on the float64 oracle alone (an input condition): the 16-view "inside" case is the tight one, as only
+# ~300 of its 1824 candidates have every tap inside all 16 views and 37 % of those are relu-safe at AMBIG_DEFAULT; of the bases
+# 4000, 4100 .. 4500, the bases 4100 and 4500 fill every population of every case at both margins.
+MANY_VIEW_SEED = 4100
+ALL_CASES = {**CASES, **MANY_VIEW_CASES}
 H, W = 32, 40
 
 _MEMO = {}      # (case, ambig) -> inputs and float64 reference: the same for every leg that selects with that margin
@@ -108,8 +130,9 @@ def projection(sc, xyz):
     return taps, xc[..., 2]
 
 
-def pick_points(sc, case, ambig, seed):
-    """n query points with the case's projection edge, every relu unit of the float64 forward at least `ambig` from zero."""
+def pick_points(sc, case, ambig, seed, pool=POOL):
+    """n query points with the case's projection edge, every relu unit of the float64 forward at least `ambig` from zero.
+    pool: how many candidates of each population are traced, as a multiple of the population's size."""
     n, proj, yolo = case["n"], case["proj"], case.get("yolo", False)
     rs = np.random.RandomState(seed)
     m = 8 * n + 800
@@ -129,13 +152,13 @@ def pick_points(sc, case, ambig, seed):
         groups.append((live.all(dim=0) & (taps == 0).any(dim=0) & (taps == 4).any(dim=0), n // 4))
     plain = live.all(dim=0) & (taps == 4).all(dim=0)      # (non-YOLO mode: camera z >= 0 excluded, NaN in the reference)
     groups.append((plain, n - sum(c for _, c in groups)))
-    # relu-safe points of each population (the float64 forward's own pre-activations), traced on a pool 1.6x the need
+    # relu-safe points of each population (the float64 forward's own pre-activations), traced on a pool `pool` x the need
     taken = torch.zeros(m, dtype=torch.bool)
     pools = []
     for mask, cnt in groups:
-        pool = (mask & ~taken).nonzero().flatten()[:int(1.6 * cnt) + 24]
-        taken[pool] = True
-        pools.append(pool)
+        cand = (mask & ~taken).nonzero().flatten()[:int(pool * cnt) + 24]
+        taken[cand] = True
+        pools.append(cand)
     cand = torch.cat(pools)
     orc.RELU_TRACE = []
     try:
@@ -147,8 +170,8 @@ def pick_points(sc, case, ambig, seed):
     ok = torch.zeros(m, dtype=torch.bool)
     ok[cand] = ok_c
     idx = []
-    for pool, (_, cnt) in zip(pools, groups):
-        sel = pool[ok[pool]][:cnt]
+    for part, (_, cnt) in zip(pools, groups):
+        sel = part[ok[part]][:cnt]
         assert sel.numel() == cnt, "too few relu-safe points of a population: %d of %d" % (sel.numel(), cnt)
         idx.append(sel)
     idx = torch.cat(idx).numpy()[rs.permutation(n)]        # the edge points spread over every tile
@@ -175,16 +198,31 @@ def assert_edges(sc, case, xyz):
         assert float(((taps == 0).any(dim=0) & (taps == 4).any(dim=0)).float().mean()) >= 0.1
 
 
+def seed_of(name):
+    """A case's seed, from its place in its own table."""
+    if name in CASES:
+        return 3000 + 17 * sorted(CASES).index(name)
+    return MANY_VIEW_SEED + 17 * sorted(MANY_VIEW_CASES).index(name)
+
+
+def poses_of(case):
+    return camera_ring(case["ns"])[0] if case.get("ring") else None
+
+
+def pool_of(case):
+    return MANY_VIEW_POOL if case.get("ring") else POOL
+
+
 def reference(name, case, ambig):
     """Inputs and the float64 reference gradients of a case (memoised: the same for every leg with this margin)."""
     key = (name, ambig)
     if key in _MEMO:
         return _MEMO[key]
-    seed = 3000 + 17 * sorted(CASES).index(name)
+    seed = seed_of(name)
     yolo = case.get("yolo", False)
     _, sc = scene_pair(case["ns"], H, W, case["L"], 21 if yolo else 4, case["nb"], case["cl"], seed, yolo=yolo, lat_hw=case["hw"],
-                       lat_grad=True, dtype=F64, yolo_flip=False, with_net=False)
-    xyz, vd = pick_points(sc, case, ambig, seed)
+                       lat_grad=True, dtype=F64, yolo_flip=False, with_net=False, poses=poses_of(case))
+    xyz, vd = pick_points(sc, case, ambig, seed, pool_of(case))
     assert_edges(sc, case, xyz)
     G = np.random.RandomState(seed + 5).standard_normal((case["n"], 21 if yolo else 4)).astype(np.float32)
     ref = orc.query(sc, xyz, vd, coarse=True)
@@ -201,8 +239,8 @@ def tiles(case):
 
 
 # every case under the three 1e-4 legs; under f16_train the cases with >= 512 samples per pass (the bars' batch size)
-QUERY_PARAMS = [(name, lg) for name in CASES for lg in LEGS
-                if lg != "f16_train" or CASES[name]["n"] * CASES[name]["ns"] >= F16_TRAIN_MIN_SAMPLES]
+QUERY_PARAMS = [(name, lg) for name in ALL_CASES for lg in LEGS
+                if lg != "f16_train" or ALL_CASES[name]["n"] * ALL_CASES[name]["ns"] >= F16_TRAIN_MIN_SAMPLES]
 
 
 def test_sweep_covers_the_axes():
@@ -218,17 +256,24 @@ def test_sweep_covers_the_axes():
     assert any(c["n"] % 64 != 0 and tiles(c) >= 2 for c in cs)                      # a ragged last tile
     assert {c["proj"] for c in cs} >= {"inside", "straddle", "outside"} and any(c.get("yolo") and c["L"] == 1792 for c in cs)
     assert sum(lg == "f16_train" for _, lg in QUERY_PARAMS) >= 2
+    many = list(MANY_VIEW_CASES.values())
+    assert not set(MANY_VIEW_CASES) & set(CASES) and {c["ns"] for c in many} >= {5, 8, 11, 16}
+    assert any(c["ns"] == 16 and tiles(c) >= 3 and tiles(c) % 2 == 1 and c["n"] % 64 != 0 for c in many)
+    assert {c["proj"] for c in many} >= {"inside", "straddle", "outside"} and any(c["L"] == 1792 for c in many)
+    # every leg; f16_train by its rule of >= 512 samples per pass, which all but the 5-view case (70 x 5) meet
+    assert all((name, lg) in QUERY_PARAMS for name in MANY_VIEW_CASES for lg in LEGS if lg != "f16_train")
+    assert {MANY_VIEW_CASES[name]["ns"] for name, lg in QUERY_PARAMS if lg == "f16_train" and name in MANY_VIEW_CASES} >= {8, 11, 16}
 
 
 @pytest.mark.parametrize("name,legname", QUERY_PARAMS)
 def test_query_gradients_vs_fp64(name, legname, monkeypatch):
-    case = CASES[name]
+    case = ALL_CASES[name]
     leg = set_leg(legname, monkeypatch)
     t0 = time.time()
     r = reference(name, case, leg["ambig"])
     yolo = case.get("yolo", False)
     net, _ = scene_pair(case["ns"], H, W, case["L"], 21 if yolo else 4, case["nb"], case["cl"], r["seed"], yolo=yolo,
-                        lat_hw=case["hw"], lat_grad=True, yolo_flip=False)
+                        lat_hw=case["hw"], lat_grad=True, yolo_flip=False, poses=poses_of(case))
     if leg["prec"]:
         net.set_matrix_precision(leg["prec"])
     out = net(dt(r["xyz"])[None], coarse=True, viewdirs=dt(r["vd"])[None])

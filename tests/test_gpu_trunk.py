@@ -130,6 +130,7 @@ SHAPES = [
     (1, 2, 32, 40, True, "eval", 4172),       # the smallest legal height
     (1, 3, 75, 100, False, "batch", 3275),    # odd stride-2 inputs, conf/exp/sn64.conf (no first pool)
     (1, 5, 150, 200, True, "eval", 3450),     # DTU at half scale, n odd (conv1 above the cap, running statistics)
+    (1, 16, 32, 32, True, "batch", 5516),     # 16 views of one object, the ABI's limit (screen: 3516 5.5e-4, 4516 5.9e-2, 5516 2.0e-6)
 ]
 
 
@@ -227,6 +228,7 @@ INFER = [
     (2, 1, 32, 40, True),
     (3, 1, 75, 100, False),
     (5, 1, 150, 200, True),
+    (1, 16, 32, 32, True),      # 16 views of one object, the ABI's limit
 ]
 
 
