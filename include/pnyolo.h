@@ -391,7 +391,9 @@ int pny_scene_projection(pny_scene* s, int fine, float* out_dev, int64_t out_flo
  * pny_query_backward, pny_yolo_render_backward, pny_model_flush_weight_grads): scenes not pinned to F32 run the dX chain and
  * the weight-gradient GEMMs as split-f16 products with power-of-two gradient scaling (csrc/mlp_bwd_h2.hip,
  * pny_dw_gemm_h2_kernel); a deferred flush runs fp32 when any contributing scene was pinned to F32.  Env
- * PNYOLO_BWD_PRECISION=f32|f16x2 overrides the backward's choice (read at every call).
+ * PNYOLO_BWD_PRECISION=f32|f16x2 overrides the backward's choice (read at every call).  The forward's fp32 fallbacks for more
+ * than 6 residual blocks and for combine_layer = 0 do NOT apply to the backward: its kernels loop over any block count, so it
+ * follows the scene's setting (and the override) for every model, and runs fp32 only when a weight is outside the f16 range.
  * Operation order: the no-grad launches of the F16X2 kernel run the fc_1 of the last per-view block ONCE per sample, on the mean
  * over views of relu(net + b_fc0) -- mean_v(h_v + fc_1(R_v)) = mean_v(h_v) + fc_1(mean_v R_v), exact in real arithmetic, one
  * fp32 sum per sample reordered in fp32, a single view bit for bit as before (csrc/mlp_h2.hip).  F32 launches,

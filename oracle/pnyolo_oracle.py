@@ -160,7 +160,7 @@ def positional_encoding(x, num_freqs=6, freq_factor=1.5):
     ph = ph.view(1, -1, 1).to(dt)
     e = x.unsqueeze(1).repeat(1, num_freqs * 2, 1)
     e = torch.sin(ph + e * fr)
-    return torch.cat((x, e.view(x.shape[0], -1)), dim=-1)
+    return torch.cat((x, e.view(x.shape[0], 2 * num_freqs * x.shape[1])), dim=-1)   # (sized: num_freqs may be 0)
 
 
 def encode_cameras(poses, focal, c, width, height, yolo=False, dtype=None):
@@ -276,8 +276,9 @@ class Scene:
     (src/model/models.py:74-87,114-148; src/model/encoder.py:73-76,169-172)."""
 
     def __init__(self, mlp_coarse, mlp_fine, latent, poses, focal, c, width, height, yolo=False,
-                 n_blocks=5, combine_layer=3, dtype=None):
-        """dtype: the arithmetic of query / render / yolo_render on this scene (None = f32; torch.float64 = the
+                 n_blocks=5, combine_layer=3, dtype=None, num_freqs=6, freq_factor=1.5):
+        """num_freqs, freq_factor: the positional code of query() (conf model.code; d_in = 6 + 6 * num_freqs).
+        dtype: the arithmetic of query / render / yolo_render on this scene (None = f32; torch.float64 = the
         high-precision arbiter of the GPU gradient sweeps).  Parameter and latent tensors assigned after construction
         may be of any dtype: they are converted differentiably where they are used."""
         self.dtype = f32 if dtype is None else dtype
@@ -289,6 +290,7 @@ class Scene:
         self.yolo = yolo
         self.ns = self.latent.shape[0]
         self.n_blocks, self.combine_layer = n_blocks, combine_layer
+        self.num_freqs, self.freq_factor = num_freqs, freq_factor
 
 
 def query(scene, xyz, viewdirs, coarse=True, dtype=None):
@@ -302,7 +304,7 @@ def query(scene, xyz, viewdirs, coarse=True, dtype=None):
     R, t = w2c[:, :, :3], w2c[:, :, 3]
     xr = torch.matmul(R[:, None], xyz[None, :, :, None])[..., 0]  # (ns,B,3) rotation only
     xc = xr + t[:, None]
-    code = positional_encoding(xr.reshape(-1, 3))
+    code = positional_encoding(xr.reshape(-1, 3), getattr(scene, "num_freqs", 6), getattr(scene, "freq_factor", 1.5))
     vd = torch.matmul(R[:, None], viewdirs[None, :, :, None])[..., 0].reshape(-1, 3)
     x_in = torch.cat((code, vd), dim=1)
     if not scene.yolo:

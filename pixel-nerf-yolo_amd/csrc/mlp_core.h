@@ -485,7 +485,7 @@ __device__ __forceinline__ int tile_view_base(const MlpArgs& a, long long first_
     return (int)obj * a.NS;
 }
 
-// Positional-code entry e of the 64-row (42 valid) input column (reference code.py:30-42 layout:
+// Positional-code entry e of the 64-row (d_in = 6 + 6 * num_freqs valid, zeros behind) input column (reference code.py:30-42 layout:
 // [x(3), then per frequency sin(f x)(3), sin(f x + pi/2)(3)], then view dirs (models.py:207)).
 __device__ __forceinline__ float input_entry(int e, const float (&xr)[3], const float (&vd)[3], float freq_factor,
                                              int num_freqs) {

@@ -14,7 +14,7 @@ constexpr int HID = 512;        // d_hidden this build is specialised for
 constexpr int MLP_THREADS = 512;
 constexpr int MAX_BLOCKS = 8;
 constexpr int MAX_VIEWS = 16;
-constexpr int D_IN_PAD = 64;    // 42 inputs padded to 8 k-iterations (a multiple of the weight-ring depth)
+constexpr int D_IN_PAD = 64;    // d_in = 6 + 6 * num_freqs inputs (42 as shipped) padded to 8 k-iterations (a multiple of the weight-ring depth)
 constexpr int ACT_KG = 128;     // k-groups (4 features each) held by the LDS activation buffer
 static_assert(STASH_ROWS == HID && STASH_SMALL_ROWS == D_IN_PAD, "stash.h slot sizes");
 

@@ -680,6 +680,12 @@ class PixelNeRFNet(nn.Module):
             return buf
         return buf.permute(0, 3, 1, 2).contiguous().to(meta[1], meta[2])   # packed NCHW, like the latent it belongs to
 
+    def abort_latent_grad(self, handles):
+        """Unbind the accumulator of begin_latent_grad after a backward call failed: the buffer dies with the exception, and a
+        scene left bound to it would accumulate into freed memory (or fail again) in its next backward."""
+        for h in handles:
+            _lib.load().pny_scene_bind_latent_grad(h, None)
+
     def bind_mlp_grads(self):
         """Fresh zeroed gradient buffers for trainable_mlp_parameters(), bound to the native model by name
         (pny_model_bind_grad); returns them in the same order.  The buffers are views of ONE flat allocation (one fill
@@ -1162,9 +1168,14 @@ class _QueryFunction(torch.autograd.Function):
         SB = ctx.xyz.shape[0]
         scenes = [net._scene(sb) for sb in range(SB)]
         lat_grad = net.begin_latent_grad(ctx.lat_meta, scenes) if ctx.lat_meta is not None else None
-        for sb in range(SB):
-            check(L.pny_query_backward(scenes[sb], ptr(ctx.xyz[sb]), ptr(ctx.dirs[sb]), ctx.xyz.shape[1], int(use_coarse),
-                                       ptr(g_out[sb]), _lib.ACC_ADD, st))
+        try:
+            for sb in range(SB):
+                check(L.pny_query_backward(scenes[sb], ptr(ctx.xyz[sb]), ptr(ctx.dirs[sb]), ctx.xyz.shape[1], int(use_coarse),
+                                           ptr(g_out[sb]), _lib.ACC_ADD, st))
+        except Exception:
+            if lat_grad is not None:
+                net.abort_latent_grad(scenes)
+            raise
         extra = () if lat_grad is None else (net.end_latent_grad(lat_grad, ctx.lat_meta, scenes),)
         net._lat_grad_event = None      # (unmarked: a trunk backward behind this one waits for the whole stream)
         return (None, None, None, None, None) + tuple(grads) + extra

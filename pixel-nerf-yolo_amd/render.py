@@ -391,8 +391,13 @@ class _RenderFunction(torch.autograd.Function):
                     fstream.wait_stream(st_)
             with torch.cuda.stream(fstream):
                 check(L.pny_model_flush_weight_grads(model._h_model, _lib.ACC_ADD | _lib.FLUSH_FINE_ONLY, stream_of(dev)))
-        for g in range(G):
-            run(g, _lib.ACC_COARSE_ONLY if split else 0)
+        try:
+            for g in range(G):
+                run(g, _lib.ACC_COARSE_ONLY if split else 0)
+        except Exception:
+            if lat_grad is not None:
+                model.abort_latent_grad(handles)
+            raise
         if deferred:
             model.join_streams(streams)
         # d loss / d latent is complete here, BEFORE the weight-gradient flush is enqueued: the encoder's backward (the trunk's
@@ -701,8 +706,13 @@ class _YoloRenderFunction(torch.autograd.Function):
         g_out = g_out.detach().to(dev, torch.float32).contiguous()
         scene = net._scene(0)
         lat_grad = net.begin_latent_grad(ctx.lat_meta, [scene]) if ctx.lat_meta is not None else None
-        check(L.pny_yolo_render_backward(scene, ptr(sv["rays"]), sv["rays"].shape[0], sv["n_coarse"], ptr(sv["u"]),
-                                         sv["seed"], ptr(sv["raw"]), ptr(g_out), _lib.ACC_ADD, stream_of(dev)))
+        try:
+            check(L.pny_yolo_render_backward(scene, ptr(sv["rays"]), sv["rays"].shape[0], sv["n_coarse"], ptr(sv["u"]),
+                                             sv["seed"], ptr(sv["raw"]), ptr(g_out), _lib.ACC_ADD, stream_of(dev)))
+        except Exception:
+            if lat_grad is not None:
+                net.abort_latent_grad([scene])
+            raise
         extra = () if lat_grad is None else (net.end_latent_grad(lat_grad, ctx.lat_meta, [scene]),)
         net._lat_grad_event = None      # (unmarked: a trunk backward behind this one waits for the whole stream)
         return (None, None, None) + tuple(grads) + extra

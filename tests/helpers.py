@@ -63,28 +63,53 @@ def camera_ring(ns):
 
 # --------------------------------------------------------------------------- MLP (query) backward
 def scene_pair(ns, H, W, L, d_out, n_blocks, combine_layer, seed, yolo=False, lat_hw=None, lat_grad=False, dtype=None,
-               yolo_flip=True, with_net=True, poses=None):
+               yolo_flip=True, with_net=True, poses=None, code=None, out_gain=1.0):
     """The same seeded scene as a HIP net (trainable MLP, frozen encoder) and as oracle state with requires_grad.
     lat_grad: the latent is a leaf that requires grad on both sides (net.test_latent on the GPU, sc.latent on the CPU).
     dtype: the oracle's arithmetic and the dtype of its leaves (None = f32; torch.float64 = the arbiter of the shape sweeps).
     yolo_flip=False (YOLO mode): world->cam extrinsics of cameras looking down -z, so that the scene lies at z < 0, where YOLO
     mode keeps the latent (models.py:224,254-264 zero it at z >= 0); the default flips y / z, which puts the scene at z > 0.
     with_net=False: the oracle scene alone (net is None; no GPU needed).
-    poses (non-YOLO mode): (ns, 4, 4) source poses instead of synth.scene_cameras(ns), e.g. camera_ring(ns)[0]."""
+    poses (non-YOLO mode): (ns, 4, 4) source poses instead of synth.scene_cameras(ns), e.g. camera_ring(ns)[0].
+    code: (num_freqs, freq_factor) of the positional code on both sides (None = the shipped 6, 1.5): conf model.code of the net,
+    d_in = 6 + 6 * num_freqs of the weights, Scene(num_freqs, freq_factor) of the oracle.
+    out_gain: synth.mlp_state's scale of lin_out.weight (YOLO mode's raw outputs).
+    A d_latent that no backbone yields (neither 512 nor 1792), and a d_out that the conf cannot state (YOLO mode: no multiple
+    of 7), are set on the model after construction and both MLPs rebuilt at them, before the first library call."""
     import pnyolo_oracle as orc
+    from pixel_nerf_yolo_amd.model import make_mlp
     c = pconf.yolo() if yolo else pconf.default_mv()
     m = c.d["model"]
     if L != 512 and not yolo:
         m["encoder"]["backbone"] = "custom"
+    num_freqs, freq_factor = (6, 1.5) if code is None else (int(code[0]), float(code[1]))
+    d_in = 6 + 6 * num_freqs
+    if code is not None:
+        m["code"].update({"num_freqs": num_freqs, "freq_factor": freq_factor})
+    if yolo and d_out % 7 == 0:
+        m["mlp_coarse"].update({"d_out": 7, "num_anchors_per_scale": d_out // 7})
+    elif not yolo:
+        m["mlp_coarse"]["d_out"] = m["mlp_fine"]["d_out"] = d_out
     m["mlp_coarse"].update({"n_blocks": n_blocks, "combine_layer": combine_layer})
     if not yolo:
         m["mlp_fine"].update({"n_blocks": n_blocks, "combine_layer": combine_layer})
     net = make_model(c["model"], stop_encoder_grad=True)
-    sd_c = synth.mlp_state(seed + 1, d_latent=L, d_out=d_out, n_blocks=n_blocks, combine_layer=combine_layer)
+    assert net.d_in == d_in and net.code.num_freqs == num_freqs and float(net.code.freq_factor) == freq_factor
+    if net.d_latent != L or net.d_out != d_out:
+        net.d_latent = net.latent_size = L
+        net.d_out = d_out
+        for k in ("mlp_coarse", "mlp_fine"):
+            if getattr(net, k) is not None:
+                mlp = make_mlp(c["model"][k], d_in, L)
+                if mlp.d_out != d_out:
+                    mlp.lin_out, mlp.d_out = torch.nn.Linear(mlp.d_hidden, d_out), d_out
+                setattr(net, k, mlp)
+    kw = dict(d_latent=L, d_out=d_out, n_blocks=n_blocks, combine_layer=combine_layer, d_in=d_in, out_gain=out_gain)
+    sd_c = synth.mlp_state(seed + 1, **kw)
     net.mlp_coarse.load_state_dict({k: torch.from_numpy(v) for k, v in sd_c.items()})
     sd_f = None
     if net.mlp_fine is not None:
-        sd_f = synth.mlp_state(seed + 2, d_latent=L, d_out=d_out, n_blocks=n_blocks, combine_layer=combine_layer)
+        sd_f = synth.mlp_state(seed + 2, **kw)
         net.mlp_fine.load_state_dict({k: torch.from_numpy(v) for k, v in sd_f.items()})
     hl, wl = lat_hw or (H // 2, W // 2)
     lat = synth.latent(seed + 3, ns, L, hl, wl)
@@ -103,12 +128,15 @@ def scene_pair(ns, H, W, L, d_out, n_blocks, combine_layer, seed, yolo=False, la
         net = net.to(DEV).train()
         net.test_latent = torch.from_numpy(lat).to(DEV).requires_grad_() if lat_grad else torch.from_numpy(lat)
         net.encode(torch.zeros(1, ns, 3, H, W), torch.from_numpy(poses)[None], focal, c=cc, latent=net.test_latent)
+        # the same scene again on another latent tensor (e.g. a frozen copy): net.test_encode(latent)
+        net.test_encode = lambda latent: net.encode(torch.zeros(1, ns, 3, H, W), torch.from_numpy(poses)[None], focal, c=cc, latent=latent)
     else:
         net = None
     leaf_dt = torch.float32 if dtype is None else dtype
     mc = {k: torch.from_numpy(v).to(leaf_dt).requires_grad_() for k, v in sd_c.items()}
     mf = None if sd_f is None else {k: torch.from_numpy(v).to(leaf_dt).requires_grad_() for k, v in sd_f.items()}
-    sc = orc.Scene(mc, mf, lat, poses, focal, cc, W, H, yolo=yolo, n_blocks=n_blocks, combine_layer=combine_layer, dtype=dtype)
+    sc = orc.Scene(mc, mf, lat, poses, focal, cc, W, H, yolo=yolo, n_blocks=n_blocks, combine_layer=combine_layer, dtype=dtype,
+                   num_freqs=num_freqs, freq_factor=freq_factor)
     sc.mlp_coarse, sc.mlp_fine = mc, mf          # Scene() re-wraps tensors: keep the leaves
     if lat_grad:
         sc.latent = torch.from_numpy(lat).to(leaf_dt).requires_grad_()
