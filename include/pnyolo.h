@@ -88,6 +88,8 @@ int pny_model_finalize(pny_model* m);
  * lives on the device (fp32, contiguous, its state_dict shape; borrowed until rebound); after the parameters changed
  * in place (optimizer.step()), pny_model_refresh re-creates every packed operand of both MLPs from those tensors with
  * one kernel launch on `stream` (no host round trip, asynchronous; ordered behind the scenes' earlier calls).
+ * The first refresh after a pny_model_bind_param rewrites its table of parameter pointers with a copy on `stream`, ordered
+ * behind the previous refresh's launch on whatever stream that ran: a refresh still queued reads the binding it was given.
  * pny_model_finalize must have run once (it fixes the layout).  The inference trunk's folded weights are not refreshed (they
  * follow pny_model_load_weights + finalize); the training trunk (pny_trunk_train_forward) reads its bound parameters directly. */
 int pny_model_bind_param(pny_model* m, const char* name, const float* param_dev);

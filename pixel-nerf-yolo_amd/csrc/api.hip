@@ -362,6 +362,8 @@ void pny_model_destroy(pny_model* m) {
     if (!m) return;
     m->packed.release();
     m->repack_jobs.release();
+    m->repack_stage.release();
+    if (m->repack_ev) (void)hipEventDestroy(m->repack_ev);
     m->h1_packed.release();
     m->h1_jobs.release();
     m->enc_batch_work.release();
@@ -483,8 +485,15 @@ int pny_model_refresh(pny_model* m, pny_stream stream) {
         std::vector<PackJob> jobs;
         long long max_elems;
         if ((rc = build_pack_jobs(m, m->params_dev, jobs, max_elems))) return rc;
-        if ((rc = m->repack_jobs.reserve(jobs.size() * sizeof(PackJob)))) return rc;
-        PNY_HIP(hipMemcpy(m->repack_jobs.p, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice));
+        const size_t bytes = jobs.size() * sizeof(PackJob);
+        if ((rc = m->repack_jobs.reserve(bytes))) return rc;   // (a larger table: hipFree waits for the device)
+        // The table is rewritten in place.  The repack launch of an earlier refresh may still be queued on another stream (or on
+        // this one) and reads the table when it RUNS: the rewrite is a copy on `st`, ordered behind that launch by its event.  A
+        // blocking hipMemcpy would order it behind nothing that runs on a non-blocking stream.
+        if (m->repack_ev) PNY_HIP(hipStreamWaitEvent(st, m->repack_ev, 0));
+        if ((rc = m->repack_stage.prepare(bytes))) return rc;
+        memcpy(m->repack_stage.host, jobs.data(), bytes);
+        if ((rc = m->repack_stage.upload(m->repack_jobs.p, bytes, st))) return rc;
         m->n_repack_jobs = (int)jobs.size();
         m->repack_max_elems = max_elems;
         m->repack_ready = true;
@@ -507,7 +516,9 @@ int pny_model_refresh(pny_model* m, pny_stream stream) {
         s->order_ev_valid = false;
     }
     launch_repack(reinterpret_cast<const PackJob*>(m->repack_jobs.p), m->n_repack_jobs, m->repack_max_elems, st, m->range_flag);
-    if (m->h1_ready)   // single-plane images (F16 scenes): copied out of the split images just rewritten, same stream
+    if (!m->repack_ev) PNY_HIP(hipEventCreateWithFlags(&m->repack_ev, hipEventDisableTiming));
+    PNY_HIP(hipEventRecord(m->repack_ev, st));   // the last reader of the job table (see the rewrite above); no host wait
+    if (m->h1_ready)  // single-plane images (F16 scenes): copied out of the split images just rewritten, same stream
         launch_repack(reinterpret_cast<const PackJob*>(m->h1_jobs.p), m->n_h1_jobs, m->h1_max_elems, st, m->range_flag);
     PNY_HIP(hipGetLastError());
     ++m->generation;   // projected maps of every scene are stale

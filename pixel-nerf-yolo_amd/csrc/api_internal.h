@@ -213,7 +213,11 @@ struct pny_model {
     int n_repack_jobs = 0;
     long long repack_max_elems = 0;
     bool repack_ready = false;
-    std::vector<struct pny_scene*> scenes;   // scenes created on this model (stream ordering of a refresh)
+    // the job table is rewritten in place after a re-bind: staged through pinned memory and uploaded on the refresh's stream,
+    // behind the last repack launch on ANY stream (repack_ev), which may still be queued and reads the table it was given
+    PinnedStage repack_stage;
+    hipEvent_t repack_ev = nullptr;
+    std::vector<struct pny_scene*> scenes;  // scenes created on this model (stream ordering of a refresh)
     DeferredStash stash;                     // deferred weight gradients: the training stash reservation
     bool deterministic = false;              // pny_model_set_deterministic: the latent gradient of every scene is bit-reproducible
     hipStream_t aux_stream = nullptr;        // side stream of the weight-gradient GEMMs' clipped tiles (mlp_bwd.hip launch_dw_gemm)

@@ -100,9 +100,15 @@ class _MultiDeviceRenderWrapper(torch.nn.Module):
         key = (net._weights_key(), net._encode_epoch)
         if self._seen[i] != key:
             if self._seen[i] is not None and self._seen[i][0] != key[0]:
-                with torch.no_grad():      # in place: the replica's refresh path (one repack launch), not a re-upload
+                # in place, and only the tensors the master changed: the replica's refresh path (one repack launch).  Copying an
+                # untouched buffer too (code._freqs) would bump its version, and the replica's _sync() answers a change outside
+                # the MLPs and the trunk with a full re-upload, which waits for the device on every training step
+                was = self._seen[i][0]
+                same = {a[0] for a, b in zip(was, key[0]) if a == b} if len(was) == len(key[0]) else set()
+                with torch.no_grad():
                     for (k, dst), (_, src) in zip(r.state_dict().items(), net.state_dict().items()):
-                        dst.copy_(src)
+                        if k not in same:
+                            dst.copy_(src)
                 if (net.mlp_fine is None) != (r.mlp_fine is None):
                     r.mlp_fine = None
             le = net._last_encode
