@@ -34,17 +34,9 @@ using namespace pny;
 // call arrives on a DIFFERENT stream than the previous call on the same scene, the new stream is made to wait for
 // everything the previous call enqueued (one event record + one stream wait, paid only on a stream switch).
 namespace pny {
-// the scene's order event, created on first use
-static int order_event(pny_scene* s, const char* what) {
-    if (!s->order_ev && hipEventCreateWithFlags(&s->order_ev, hipEventDisableTiming) != hipSuccess) {
-        s->order_ev = nullptr;
-        return hip_fail(hipGetLastError(), what);
-    }
-    return 0;
-}
 int enter_stream(pny_scene* s, hipStream_t st) {
     if (s->has_last_stream && s->last_stream != st) {
-        if (int rc = order_event(s, "hipEventCreate(stream order)")) return rc;
+        if (int rc = s->order_ev.ensure(hipEventDisableTiming, "hipEventCreate(stream order)")) return rc;
         if (s->order_ev_valid) {   // recorded right behind the previous call's work (mark_stream_point)
             PNY_HIP(hipStreamWaitEvent(st, s->order_ev, 0));
         } else if (hipEventRecord(s->order_ev, s->last_stream) == hipSuccess) {
@@ -62,7 +54,7 @@ int enter_stream(pny_scene* s, hipStream_t st) {
 // for exactly this point and not for whatever else the first stream has been given in between (pny_scenes_encode: the scenes
 // of a super-batch are encoded on one stream and rendered on one stream each).
 int mark_stream_point(pny_scene* s, hipStream_t st) {
-    if (int rc = order_event(s, "hipEventCreate(stream order)")) return rc;
+    if (int rc = s->order_ev.ensure(hipEventDisableTiming, "hipEventCreate(stream order)")) return rc;
     PNY_HIP(hipEventRecord(s->order_ev, st));
     s->order_ev_valid = true;
     return 0;
@@ -225,8 +217,9 @@ static int build_pack_jobs(const pny_model* m, const std::map<std::string, const
 }
 
 // pny_model_finalize: every image of m->repack built by the device packer from copies of the state_dict tensors uploaded
-// into `stage`.  Synchronous; the caller releases `stage` and `table` whatever the outcome.
-static int pack_from_host(pny_model* m, DevBuf& stage, DevBuf& table) {
+// into `stage`.  Synchronous; `stage` and the job table live for this call only.
+static int pack_from_host(pny_model* m) {
+    DevBuf stage, table;
     std::map<std::string, size_t> at;   // tensor -> float offset in `stage` (several entries name the same tensor)
     size_t total = 0;
     for (const RepackEntry& e : m->repack)
@@ -310,7 +303,7 @@ static int build_h1_images(pny_model* m) {
     PNY_HIP(hipDeviceSynchronize());
     PNY_HIP(hipMemcpy(m->h1_jobs.p, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice));
     m->n_h1_jobs = (int)jobs.size();
-    launch_repack(reinterpret_cast<const PackJob*>(m->h1_jobs.p), m->n_h1_jobs, m->h1_max_elems, nullptr, m->range_flag);
+    launch_repack(reinterpret_cast<const PackJob*>(m->h1_jobs.p), m->n_h1_jobs, m->h1_max_elems, nullptr, m->range_flag());
     PNY_HIP(hipGetLastError());
     PNY_HIP(hipDeviceSynchronize());
     m->h1_ready = true;
@@ -348,33 +341,19 @@ int pny_model_create(pny_model** out, const pny_model_desc* desc) {
     pny_model* m = new pny_model();
     m->desc = *desc;
     // f16-range guard word (pny_model_range_status): pinned, device-visible host memory; the kernels OR into it
-    if (hipHostMalloc(reinterpret_cast<void**>(&m->range_flag), 64, hipHostMallocDefault) != hipSuccess) {
+    if (m->range_block.reserve(64)) {
         (void)hipGetLastError();
         delete m;
         return fail(PNY_ERR_HIP, "pny_model_create: hipHostMalloc(range flag) failed");
     }
-    *m->range_flag = 0;
+    *m->range_flag() = 0;
     *out = m;
     return PNY_OK;
 }
 
 void pny_model_destroy(pny_model* m) {
     if (!m) return;
-    m->packed.release();
-    m->repack_jobs.release();
-    m->repack_stage.release();
-    if (m->repack_ev) (void)hipEventDestroy(m->repack_ev);
-    m->h1_packed.release();
-    m->h1_jobs.release();
-    m->enc_batch_work.release();
-    m->enc_batch_lat.release();
-    m->stash.release();
-    if (m->aux_stream) (void)hipStreamDestroy(m->aux_stream);
-    if (m->aux_fork) (void)hipEventDestroy(m->aux_fork);
-    if (m->aux_join) (void)hipEventDestroy(m->aux_join);
-    m->enc.release();
-    for (float* p : m->zproj_allocs) (void)hipFree(p);
-    if (m->range_flag) (void)hipHostFree(m->range_flag);
+    drain_device(m->desc.device);
     trunk_release(m->trunk);
     delete m;
 }
@@ -420,7 +399,6 @@ int pny_model_finalize(pny_model* m) {
     }
     // encoder weights are optional (a scene may be fed through pny_scene_set_latent instead)
     // stacked lin_z maps for the projected-latent variant
-    for (float* p : m->zproj_allocs) (void)hipFree(p);
     m->zproj_allocs.clear();
     m->has_zproj = false;
     {
@@ -440,11 +418,7 @@ int pny_model_finalize(pny_model* m) {
             m->has_zproj = true;
         }
     }
-    DevBuf stage, table;
-    rc = pack_from_host(m, stage, table);
-    stage.release();
-    table.release();
-    if (rc) return rc;
+    if ((rc = pack_from_host(m))) return rc;
     ++m->generation;
     m->has_encoder = false;
     if (find(m, "encoder.model.conv1.weight")) {
@@ -492,7 +466,7 @@ int pny_model_refresh(pny_model* m, pny_stream stream) {
         // blocking hipMemcpy would order it behind nothing that runs on a non-blocking stream.
         if (m->repack_ev) PNY_HIP(hipStreamWaitEvent(st, m->repack_ev, 0));
         if ((rc = m->repack_stage.prepare(bytes))) return rc;
-        memcpy(m->repack_stage.host, jobs.data(), bytes);
+        memcpy(m->repack_stage.host.p, jobs.data(), bytes);
         if ((rc = m->repack_stage.upload(m->repack_jobs.p, bytes, st))) return rc;
         m->n_repack_jobs = (int)jobs.size();
         m->repack_max_elems = max_elems;
@@ -501,7 +475,7 @@ int pny_model_refresh(pny_model* m, pny_stream stream) {
     // order this stream behind the last call of every scene that may still read the packed weights on another stream
     for (pny_scene* s : m->scenes) {
         if (s->has_last_stream && s->last_stream != st) {
-            if ((rc = order_event(s, "hipEventCreate(refresh order)"))) return rc;
+            if ((rc = s->order_ev.ensure(hipEventDisableTiming, "hipEventCreate(refresh order)"))) return rc;
             if (hipEventRecord(s->order_ev, s->last_stream) == hipSuccess)
                 PNY_HIP(hipStreamWaitEvent(st, s->order_ev, 0));
             else
@@ -515,11 +489,11 @@ int pny_model_refresh(pny_model* m, pny_stream stream) {
         // on another stream has to wait for the repack too, so enter_stream must record a fresh event behind it
         s->order_ev_valid = false;
     }
-    launch_repack(reinterpret_cast<const PackJob*>(m->repack_jobs.p), m->n_repack_jobs, m->repack_max_elems, st, m->range_flag);
-    if (!m->repack_ev) PNY_HIP(hipEventCreateWithFlags(&m->repack_ev, hipEventDisableTiming));
+    launch_repack(reinterpret_cast<const PackJob*>(m->repack_jobs.p), m->n_repack_jobs, m->repack_max_elems, st, m->range_flag());
+    if ((rc = m->repack_ev.ensure(hipEventDisableTiming, "hipEventCreate(repack)"))) return rc;
     PNY_HIP(hipEventRecord(m->repack_ev, st));   // the last reader of the job table (see the rewrite above); no host wait
     if (m->h1_ready)  // single-plane images (F16 scenes): copied out of the split images just rewritten, same stream
-        launch_repack(reinterpret_cast<const PackJob*>(m->h1_jobs.p), m->n_h1_jobs, m->h1_max_elems, st, m->range_flag);
+        launch_repack(reinterpret_cast<const PackJob*>(m->h1_jobs.p), m->n_h1_jobs, m->h1_max_elems, st, m->range_flag());
     PNY_HIP(hipGetLastError());
     ++m->generation;   // projected maps of every scene are stale
     return PNY_OK;
@@ -554,23 +528,9 @@ int pny_scene_create(pny_scene** out, pny_model* m) {
 
 void pny_scene_destroy(pny_scene* s) {
     if (!s) return;
-    if (s->m) {
-        auto& v = s->m->scenes;
-        v.erase(std::remove(v.begin(), v.end(), s), v.end());
-    }
-    s->latent.release();
-    s->work.release();
-    s->scratch.release();
-    s->enc_work.release();
-    s->zp[0].release();
-    s->zp[1].release();
-    for (DevBuf* b : {&s->dy_absmax, &s->x_stash, &s->dy_stash, &s->dw_partial, &s->dw_bias, &s->dw_tables, &s->d_samp, &s->out_tmp, &s->dz_tmp,
-                      &s->sel_tmp, &s->gdepth_tmp, &s->lg_fixed, &s->lg_words})
-        b->release();
-    for (auto e : s->ev) (void)hipEventDestroy(e);
-    for (auto e : s->bev) (void)hipEventDestroy(e);
-    s->table_stage.release();
-    if (s->order_ev) (void)hipEventDestroy(s->order_ev);
+    drain_device(s->m->desc.device);   // (a scene always has its model: pny_scene_create refuses a null one)
+    auto& v = s->m->scenes;
+    v.erase(std::remove(v.begin(), v.end(), s), v.end());
     delete s;
 }
 
@@ -917,7 +877,7 @@ int pny_yolo_train_batch(const pny_yolo_batch_desc* d, const float* poses_host, 
 // ---------------------------------------------------------------------------------- MLP launch
 namespace pny {
 static unsigned range_bits(const pny_model* m) {
-    return m->range_flag ? __atomic_load_n(m->range_flag, __ATOMIC_RELAXED) : 0u;
+    return m->range_flag() ? __atomic_load_n(m->range_flag(), __ATOMIC_RELAXED) : 0u;
 }
 int check_ready(pny_scene* s, const char* who) {
     if (!s) return fail(PNY_ERR_ARG, std::string(who) + ": null scene");
@@ -1082,7 +1042,7 @@ int fill_mlp_args(pny_scene* s, int mode, const float* xyz, const float* dirs, c
     a.w = fine_w ? s->m->fine : s->m->coarse;
     a.n_blocks = d.n_blocks;
     use_images(a, f16_images(s->m, fine_w, false));   // (in the packed blob, like `w`)
-    a.range_flag = s->m->range_flag;
+    a.range_flag = s->m->range_flag();
     a.latent = s->latent.f();
     a.zp = nullptr;
     a.zp_stride = view_blocks(d) * HID;
@@ -1363,7 +1323,7 @@ int pny_model_range_status(pny_model* m, unsigned* bits, int clear) {
     const unsigned b = range_bits(m);
     if (bits) *bits = b;
     if (b & PNY_RANGE_WEIGHT) m->f16_weights_ok = false;   // until the next finalize re-checks on the host
-    if (clear && m->range_flag) __atomic_store_n(m->range_flag, 0u, __ATOMIC_RELAXED);
+    if (clear && m->range_flag()) __atomic_store_n(m->range_flag(), 0u, __ATOMIC_RELAXED);
     return PNY_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "pny_common.h"
+#include "dev_resource.h"
 #include "encoder.h"
 #include "stash_book.h"
 
@@ -13,75 +14,6 @@ namespace pny {
 struct HostTensor {
     std::vector<int64_t> shape;
     std::vector<float> data;
-};
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int reserve(size_t need) {
-        if (need <= bytes) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        hipError_t e = hipMalloc(&p, need);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc(workspace)");
-        bytes = need;
-        return 0;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    float* f() const { return reinterpret_cast<float*>(p); }
-};
-
-
-int fail(int code, const std::string& msg);
-
-// Small host -> device parameter tables that change from call to call (work lists of the weight-gradient GEMMs): staged
-// through a pinned block; the block is rewritten only after the previous asynchronous copy out of it has executed.
-struct PinnedStage {
-    void* host = nullptr;
-    size_t cap = 0;
-    hipEvent_t ev = nullptr;
-    bool pending = false;
-    int prepare(size_t bytes) {   // returns 0 and a writable block of >= bytes
-        if (pending) {
-            hipError_t e = hipEventSynchronize(ev);
-            if (e != hipSuccess) return hip_fail(e, "hipEventSynchronize(table stage)");
-            pending = false;
-        }
-        if (bytes > cap) {
-            if (host) (void)hipHostFree(host);
-            host = nullptr;
-            cap = 0;
-            hipError_t e = hipHostMalloc(&host, bytes * 2, hipHostMallocDefault);
-            if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(table stage)");
-            cap = bytes * 2;
-        }
-        if (!ev) {
-            hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-            if (e != hipSuccess) return hip_fail(e, "hipEventCreate(table stage)");
-        }
-        return 0;
-    }
-    int upload(void* dst_dev, size_t bytes, hipStream_t st) {
-        hipError_t e = hipMemcpyAsync(dst_dev, host, bytes, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(table stage)");
-        e = hipEventRecord(ev, st);
-        if (e != hipSuccess) return hip_fail(e, "hipEventRecord(table stage)");
-        pending = true;
-        return 0;
-    }
-    void release() {
-        if (host) (void)hipHostFree(host);
-        if (ev) (void)hipEventDestroy(ev);
-        host = nullptr;
-        ev = nullptr;
-        cap = 0;
-        pending = false;
-    }
 };
 
 // One packed sub-buffer of the model and how to build it from the state_dict tensor(s) it comes from (pack.hip): recorded by
@@ -106,28 +38,13 @@ struct DeferredStash {
     DevBuf partial[2], bias[2], tables[2];   // the flush GEMM's split partial sums and its work list
     PinnedStage stage[2];
     DevBuf absmax;                           // two words: running max |dY| of the deferred tiles per MLP (zeroed by its flush)
-    hipEvent_t flush_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    Event flush_ev[4];                       // timing events around each MLP's flush GEMM
     double flush_flops = 0.0;                // pny_model_last_flush_stats
     int flush_launches = 0;
     Prec last_flush_prec = PREC_F32;         // pny_model_last_flush_precision: the flush's GEMM
     float* x_record(const StashLayout& lay, int which, long long tile) const { return lay.x_record(x[which].f(), tile); }
     float* dy_record(const StashLayout& lay, int which, long long tile) const { return lay.dy_record(dy[which].f(), tile); }
     unsigned* absmax_word(int which) const { return absmax.p ? reinterpret_cast<unsigned*>(absmax.p) + which : nullptr; }
-    void release() {
-        for (int w = 0; w < 2; ++w) {
-            x[w].release();
-            dy[w].release();
-            partial[w].release();
-            bias[w].release();
-            tables[w].release();
-            stage[w].release();
-        }
-        absmax.release();
-        for (auto& e : flush_ev) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-    }
 };
 
 // One set of f16 operand images of an MLP and the allocation they live in (raw-buffer addressing): lin_in / fc_0 / fc_1 as the
@@ -177,22 +94,31 @@ inline void use_images(BwdArgs& a, const F16Images& im) {
 
 // Kernel timing (pny_scene_enable_timing): records the next event of `ev` on `st`, creating it on first use.  A timed launch
 // is bracketed by two calls.
-inline int stamp_event(bool timing, std::vector<hipEvent_t>& ev, int& used, hipStream_t st) {
+inline int stamp_event(bool timing, std::vector<Event>& ev, int& used, hipStream_t st) {
     if (!timing) return 0;
     if ((int)ev.size() <= used) {
-        hipEvent_t e;
-        PNY_HIP(hipEventCreate(&e));
-        ev.push_back(e);
+        Event e;
+        if (int rc = e.ensure(hipEventDefault, "hipEventCreate(timing)")) return rc;
+        ev.push_back(std::move(e));
     }
     PNY_HIP(hipEventRecord(ev[used++], st));
     return 0;
+}
+
+// The first step of every handle's destroy entry.  Pinned blocks and job tables may still be read by queued copies and
+// kernels, and freeing pinned memory waits for nothing: the device is drained before any member is released, so that no
+// order of members or of their destructors is what keeps that safe.  Like every other entry point it makes the handle's
+// device the calling thread's current one (the model's and the scene's destroy did not before).
+inline void drain_device(int device) {
+    (void)hipSetDevice(device);
+    (void)hipDeviceSynchronize();
 }
 
 }  // namespace pny
 
 namespace pny {
 struct TrunkTrain;                       // training-mode trunk: saved activations and scratch (encoder_train.hip)
-void trunk_release(TrunkTrain* t);
+void trunk_release(TrunkTrain* t);       // after the model's drain_device
 void trunk_params_rebound(TrunkTrain* t);   // a trunk parameter was bound to new storage: re-resolve its pointers
 }  // namespace pny
 
@@ -216,22 +142,23 @@ struct pny_model {
     // the job table is rewritten in place after a re-bind: staged through pinned memory and uploaded on the refresh's stream,
     // behind the last repack launch on ANY stream (repack_ev), which may still be queued and reads the table it was given
     PinnedStage repack_stage;
-    hipEvent_t repack_ev = nullptr;
+    Event repack_ev;
     std::vector<struct pny_scene*> scenes;  // scenes created on this model (stream ordering of a refresh)
     DeferredStash stash;                     // deferred weight gradients: the training stash reservation
     bool deterministic = false;              // pny_model_set_deterministic: the latent gradient of every scene is bit-reproducible
-    hipStream_t aux_stream = nullptr;        // side stream of the weight-gradient GEMMs' clipped tiles (mlp_bwd.hip launch_dw_gemm)
-    hipEvent_t aux_fork = nullptr, aux_join = nullptr;
+    Stream aux_stream;                       // side stream of the weight-gradient GEMMs' clipped tiles (mlp_bwd.hip launch_dw_gemm)
+    Event aux_fork, aux_join;
     EncoderWeights enc;                       // folded conv+bn (encoder.h)
     DevBuf enc_batch_work, enc_batch_lat;     // pny_scenes_encode: workspace and result of one trunk pass over several scenes
     bool has_encoder = false;
     TrunkTrain* trunk = nullptr;              // created by the first pny_trunk_train_forward
     // lin_z[0..nvb) of the coarse / fine MLP stacked into one (nvb*512 x d_latent) pixel-wise map
     ConvLayer zproj[2];
-    std::vector<float*> zproj_allocs;
+    std::vector<DevBuf> zproj_allocs;        // what zproj[] points into (a ConvLayer owns nothing)
     bool has_zproj = false;
     bool f16_weights_ok = true;   // every MLP weight is representable in the f16 range (checked at finalize; AUTO precision needs it)
-    unsigned* range_flag = nullptr;           // pinned host word the f16x2 kernels report PNY_RANGE_* bits into (pny_model_range_status)
+    PinnedBuf range_block;                    // pinned host word the f16x2 kernels report PNY_RANGE_* bits into (pny_model_range_status)
+    unsigned* range_flag() const { return static_cast<unsigned*>(range_block.p); }
     uint64_t generation = 0;                  // bumped by every finalize (scenes re-project)
     // single-plane f16 images of lin_in / fc_0 / fc_1 for PNY_PRECISION_F16 (mlp_h1.hip): built only once a scene of the model
     // is set to F16 (api.hip build_h1_images), then kept current by every finalize and refresh; [0] coarse, [1] fine MLP
@@ -267,7 +194,7 @@ struct pny_scene {
     double last_flops_ref = 0.0;
     // timing of the MLP launches of the last call
     bool timing = false;
-    std::vector<hipEvent_t> ev;
+    std::vector<Event> ev;
     int ev_used = 0;
     double last_flops = 0.0;
     int last_launches = 0;
@@ -287,12 +214,12 @@ struct pny_scene {
     bool stash_next = false;
     StashedPass stashed[2];   // [0] coarse pass, [1] fine pass
     // HIP-event timing of the backward kernels of the last backward call (enable_timing): per MLP pass 4 events
-    std::vector<hipEvent_t> bev;
+    std::vector<Event> bev;
     int bev_used = 0;
     double bwd_flops[3] = {0.0, 0.0, 0.0};   // stash forward, dX chain, weight-gradient GEMMs
     hipStream_t last_stream = nullptr;
     bool has_last_stream = false;
-    hipEvent_t order_ev = nullptr;
+    Event order_ev;
     bool order_ev_valid = false;             // order_ev was recorded behind the last call's work (api.hip mark_stream_point)
 };
 

@@ -7,8 +7,12 @@
 #include <string>
 #include <vector>
 
+#include "dev_resource.h"
+
 namespace pny {
 
+// Geometry of one convolution and where its operands are.  The pointers own nothing: they point into buffers someone else
+// holds (EncoderWeights::allocs, pny_model::zproj_allocs, a caller's tensors), and layers are copied freely.
 struct ConvLayer {
     float* w = nullptr;      // packed MFMA A-operand order [Cout/32][J][64][4], K = (ky,kx,ci)
     float* scale = nullptr;  // eval-mode batch norm: gamma / sqrt(var + eps)
@@ -71,16 +75,15 @@ struct Carver {
 // Inference weights: one folded conv + bn layer per entry of trunk_table(), in its order
 struct EncoderWeights {
     std::vector<ConvLayer> convs;
-    std::vector<float*> allocs;
+    std::vector<DevBuf> allocs;   // what the layers point into
     using Getter = std::function<bool(const std::string&, const float**, std::vector<int64_t>*)>;
     bool build(const Getter& get, const std::string& prefix, std::string* err);
-    void release();
 };
 
 // Pixel-wise linear map over a channel-last tensor, out[p][n] = sum_k W[n][k] in[p][k], run by the
 // same implicit-GEMM kernel as a 1x1 convolution (scale 1, shift 0, no relu).  W is nmat row-major (rows x k) matrices
 // stacked along n; rows*nmat must be a multiple of 64, k of 8.  Allocates the layer; the caller fills `w` (pack.hip PACK_NT).
-bool build_pixel_linear(int nmat, int rows, int k, ConvLayer* out, std::vector<float*>* allocs, std::string* err);
+bool build_pixel_linear(int nmat, int rows, int k, ConvLayer* out, std::vector<DevBuf>* allocs, std::string* err);
 // f16x2: split-f16 matrix products (pixel_linear_h2_kernel) instead of the fp32 MFMA
 // route (optional): the kernel that was launched -- PL_ROUTE_TILED_F32 / PL_ROUTE_TILED_H2 for the tiled GEMM, else the
 // 1x1-convolution path's conv_mfma_kernel instantiation as run_conv_ex reports it (100 SPLIT + 10 NT + MT, >= 111).

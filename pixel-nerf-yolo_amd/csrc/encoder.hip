@@ -499,20 +499,19 @@ __global__ void upsample_concat_kernel(const float* __restrict__ in, float* __re
 }
 
 // ----------------------------------------------------------------------------------- host side
-static bool upload(const std::vector<float>& v, float** out, std::vector<float*>& allocs, std::string* err) {
-    float* p = nullptr;
-    if (hipMalloc((void**)&p, v.size() * sizeof(float)) != hipSuccess ||
-        hipMemcpy(p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+static bool upload(const std::vector<float>& v, float** out, std::vector<DevBuf>& allocs, std::string* err) {
+    DevBuf b;
+    if (b.reserve(v.size() * sizeof(float)) || hipMemcpy(b.p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
         *err = "device allocation / copy of encoder weights failed";
         return false;
     }
-    allocs.push_back(p);
-    *out = p;
+    *out = b.f();
+    allocs.push_back(std::move(b));
     return true;
 }
 
 static bool build_conv(const EncoderWeights::Getter& get, const std::string& pre, const TrunkConv& c, ConvLayer& L,
-                       std::vector<float*>& allocs, std::string* err) {
+                       std::vector<DevBuf>& allocs, std::string* err) {
     const int cin = c.cin, cout = c.cout, k = c.k;
     const float* w = nullptr;
     std::vector<int64_t> shp;
@@ -549,7 +548,7 @@ static bool build_conv(const EncoderWeights::Getter& get, const std::string& pre
     return upload(pk, &L.w, allocs, err) && upload(sc, &L.scale, allocs, err) && upload(sh, &L.shift, allocs, err);
 }
 
-bool build_pixel_linear(int nmat, int rows, int k, ConvLayer* out, std::vector<float*>* allocs, std::string* err) {
+bool build_pixel_linear(int nmat, int rows, int k, ConvLayer* out, std::vector<DevBuf>* allocs, std::string* err) {
     const int cout = nmat * rows;
     if (cout % 64 || k % 8) {
         *err = "pixel-linear map needs rows*nmat % 64 == 0 and k % 8 == 0";
@@ -562,11 +561,13 @@ bool build_pixel_linear(int nmat, int rows, int k, ConvLayer* out, std::vector<f
     L.stride = 1;
     L.pad = 0;
     L.J = k / 8;
-    if (hipMalloc((void**)&L.w, (size_t)cout * k * sizeof(float)) != hipSuccess) {
+    DevBuf w;
+    if (w.reserve((size_t)cout * k * sizeof(float))) {
         *err = "device allocation of the pixel-linear weights failed";
         return false;
     }
-    allocs->push_back(L.w);
+    L.w = w.f();
+    allocs->push_back(std::move(w));
     const std::vector<float> one((size_t)cout, 1.0f), zero((size_t)cout, 0.0f);
     return upload(one, &L.scale, *allocs, err) && upload(zero, &L.shift, *allocs, err);
 }
@@ -603,18 +604,13 @@ ConvLayer conv_geometry(const TrunkConv& c) {
 }
 
 bool EncoderWeights::build(const Getter& get, const std::string& pre, std::string* err) {
-    release();
+    allocs.clear();
+    convs.clear();
     const std::vector<TrunkConv>& table = trunk_table();
     convs.resize(table.size());
     for (size_t i = 0; i < table.size(); ++i)
         if (!build_conv(get, pre, table[i], convs[i], allocs, err)) return false;
     return true;
-}
-
-void EncoderWeights::release() {
-    for (float* p : allocs) (void)hipFree(p);
-    allocs.clear();
-    convs.clear();
 }
 
 int conv_out(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }

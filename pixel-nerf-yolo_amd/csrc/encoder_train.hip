@@ -530,34 +530,18 @@ struct TrunkTrain {
     float* lat_nhwc = nullptr;
     // weight gradients run on a side stream beside the chain of input gradients (which is the critical path); an event per
     // scratch buffer says when the side stream's last reader of it is done
-    hipStream_t side = nullptr;
-    hipEvent_t ev_ready = nullptr, ev_join = nullptr, ev_buf[NSCR] = {};
+    Stream side;
+    Event ev_ready, ev_join, ev_buf[NSCR];
     // pack-job table: host copy (the source of the stream-ordered upload), and events after the last upload / pack launch
     std::vector<TrunkPackJob> host_jobs;
-    hipEvent_t ev_upload = nullptr, ev_pack = nullptr;
+    Event ev_upload, ev_pack;
     bool pend[NSCR] = {};
     bool have_forward = false;
     bool bn_eval = false;    // batch norm on the running statistics (modules in eval() mode under autograd)
     int n_jobs = 0;
 };
 
-void trunk_release(TrunkTrain* t) {
-    if (!t) return;
-    t->work.release();
-    t->packs.release();
-    t->jobs.release();
-    t->part.release();
-    t->dwpart.release();
-    t->ones.release();
-    if (t->side) (void)hipStreamDestroy(t->side);
-    if (t->ev_ready) (void)hipEventDestroy(t->ev_ready);
-    if (t->ev_join) (void)hipEventDestroy(t->ev_join);
-    if (t->ev_upload) (void)hipEventDestroy(t->ev_upload);
-    if (t->ev_pack) (void)hipEventDestroy(t->ev_pack);
-    for (auto& e : t->ev_buf)
-        if (e) (void)hipEventDestroy(e);
-    delete t;
-}
+void trunk_release(TrunkTrain* t) { delete t; }   // pny_model_destroy, its only caller, has drained the device
 
 static void dw_split(const ConvLayer& L, long long npix, int* splits, long long* chunk);
 static size_t dw_partial_floats(const ConvLayer& L, long long npix);
@@ -666,8 +650,8 @@ static int trunk_upload_jobs(pny_model* m, TrunkTrain& T, hipStream_t st) {
     // stream-ordered (no device-wide wait): a table uploaded before may still be read by the pack launch of an earlier forward
     // on another stream, and the previous upload may still be reading host_jobs (rare: after a re-bind or a new shape)
     if (!T.ev_upload) {
-        PNY_HIP(hipEventCreateWithFlags(&T.ev_upload, hipEventDisableTiming));
-        PNY_HIP(hipEventCreateWithFlags(&T.ev_pack, hipEventDisableTiming));
+        if ((rc = T.ev_upload.ensure(hipEventDisableTiming, "hipEventCreate(trunk job upload)"))) return rc;
+        if ((rc = T.ev_pack.ensure(hipEventDisableTiming, "hipEventCreate(trunk pack)"))) return rc;
     } else {
         PNY_HIP(hipEventSynchronize(T.ev_upload));     // the previous upload has read host_jobs
         PNY_HIP(hipStreamWaitEvent(st, T.ev_pack, 0));  // ... and the last pack launch (any stream) the old table
@@ -906,10 +890,11 @@ int trunk_train_backward(pny_model* m, const float* d_latent_nchw, hipStream_t s
     // residual layers, last to first.  g_x = gradient w.r.t. the current block's output.  Scratch: a pool of NSCR buffers of
     // the largest activation; at most four are live at any point.
     if (!T.side && !getenv("PNYOLO_TRUNK_NO_SIDE_STREAM")) {
-        PNY_HIP(hipStreamCreateWithFlags(&T.side, hipStreamNonBlocking));
-        PNY_HIP(hipEventCreateWithFlags(&T.ev_ready, hipEventDisableTiming));
-        PNY_HIP(hipEventCreateWithFlags(&T.ev_join, hipEventDisableTiming));
-        for (auto& e : T.ev_buf) PNY_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        if ((rc = T.side.ensure(hipStreamNonBlocking, "hipStreamCreate(trunk side stream)"))) return rc;
+        if ((rc = T.ev_ready.ensure(hipEventDisableTiming, "hipEventCreate(trunk side stream)"))) return rc;
+        if ((rc = T.ev_join.ensure(hipEventDisableTiming, "hipEventCreate(trunk side stream)"))) return rc;
+        for (Event& e : T.ev_buf)
+            if ((rc = e.ensure(hipEventDisableTiming, "hipEventCreate(trunk side stream)"))) return rc;
     }
     for (bool& b : T.pend) b = false;
     bool used[TrunkTrain::NSCR] = {};
@@ -1015,12 +1000,6 @@ int pny_trunk_train_backward(pny_model* m, const float* d_latent_nchw_dev, pny_s
 // One trunk stage per call on caller-chosen inputs (tests/test_gpu_trunk_stages.py), through the launchers the trunk itself
 // uses.  No model handle: scratch is allocated per call and the call returns once the stream has drained.
 namespace {
-struct StageScratch {
-    void* p = nullptr;
-    ~StageScratch() {
-        if (p) (void)hipFree(p);
-    }
-};
 bool bn_channels(int C) { return C == 64 || C == 128 || C == 256; }
 bool fits_int(long long a, long long b, long long c) { return a * b <= 0x7fffffffll && a * b * c <= 0x7fffffffll; }
 const TrunkConv* stage_unit(int unit) {
@@ -1056,10 +1035,10 @@ int pny_trunk_conv(int unit, int transposed, const float* weight_dev, const floa
     hipStream_t st = (hipStream_t)stream;
     const ConvLayer fwd = conv_geometry(*c);
     ConvLayer L = transposed ? transposed_geometry(*c) : fwd;
-    StageScratch scr;
+    DevBuf scr;
     const size_t job_fl = 64;   // the one-job table in front of the packed operand
     static_assert(sizeof(TrunkPackJob) <= job_fl * sizeof(float), "job table slot");
-    PNY_HIP(hipMalloc(&scr.p, (job_fl + (size_t)pack_count(L) * 4) * sizeof(float)));
+    if (int rc = scr.reserve((job_fl + (size_t)pack_count(L) * 4) * sizeof(float), "hipMalloc(trunk stage scratch)")) return rc;
     L.w = reinterpret_cast<float*>(scr.p) + job_fl;
     L.scale = const_cast<float*>(scale_dev);
     L.shift = const_cast<float*>(shift_dev);
@@ -1083,9 +1062,9 @@ int pny_trunk_conv_dw(int unit, const float* dy_dev, const float* x_dev, int n, 
     hipStream_t st = (hipStream_t)stream;
     const ConvLayer L = conv_geometry(*c);
     const int hout = conv_out(hin, c->k, c->stride, c->pad), wout = conv_out(win, c->k, c->stride, c->pad);
-    StageScratch scr;
+    DevBuf scr;
     const size_t bytes = dw_partial_floats(L, (long long)n * hout * wout) * sizeof(float);
-    PNY_HIP(hipMalloc(&scr.p, bytes));
+    if (int rc = scr.reserve(bytes, "hipMalloc(trunk stage scratch)")) return rc;
     int sp = 0;
     long long ch = 0;
     if (!launch_conv_dw(L, dy_dev, x_dev, n, hin, win, hout, wout, reinterpret_cast<float*>(scr.p), bytes, dw_dev, st, &sp, &ch))
@@ -1105,8 +1084,8 @@ int pny_trunk_bn_forward(const float* y_dev, int64_t P, int C, const float* gamm
         return fail(PNY_ERR_ARG, "pny_trunk_bn_forward: running_mean and running_var go together, and use_running needs them");
     if (!bn_channels(C) || P < 1 || P > 0x7fffffffll / C) return fail(PNY_ERR_ARG, "pny_trunk_bn_forward: C must be 64, 128 or 256 and P >= 1");
     hipStream_t st = (hipStream_t)stream;
-    StageScratch scr;
-    PNY_HIP(hipMalloc(&scr.p, BN_PART_FLOATS * sizeof(float)));
+    DevBuf scr;
+    if (int rc = scr.reserve(BN_PART_FLOATS * sizeof(float), "hipMalloc(trunk stage scratch)")) return rc;
     launch_bn_forward(y_dev, P, C, gamma_dev, beta_dev, resid_dev, relu ? 1 : 0, out_dev, mean_dev, invstd_dev, running_mean_dev, running_var_dev,
                       momentum, use_running ? 1 : 0, reinterpret_cast<float*>(scr.p), st);
     PNY_HIP(hipGetLastError());
@@ -1120,8 +1099,8 @@ int pny_trunk_bn_backward(const float* d_out_dev, const float* out_dev, const fl
     if (!d_out_dev || !y_dev || !mean_dev || !invstd_dev || !gamma_dev || !dy_dev) return fail(PNY_ERR_ARG, "pny_trunk_bn_backward: null argument");
     if (!bn_channels(C) || P < 1 || P > 0x7fffffffll / C) return fail(PNY_ERR_ARG, "pny_trunk_bn_backward: C must be 64, 128 or 256 and P >= 1");
     hipStream_t st = (hipStream_t)stream;
-    StageScratch scr;
-    PNY_HIP(hipMalloc(&scr.p, BN_PART_FLOATS * sizeof(float)));
+    DevBuf scr;
+    if (int rc = scr.reserve(BN_PART_FLOATS * sizeof(float), "hipMalloc(trunk stage scratch)")) return rc;
     launch_bn_backward(d_out_dev, out_dev, y_dev, mean_dev, invstd_dev, gamma_dev, P, C, dy_dev, g_out_dev, d_gamma_dev, d_beta_dev,
                        use_running ? 1 : 0, reinterpret_cast<float*>(scr.p), st);
     PNY_HIP(hipGetLastError());

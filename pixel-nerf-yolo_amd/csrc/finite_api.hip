@@ -16,7 +16,7 @@ struct pny_finite {
     long long chunks = 0;       // chunks of all entries
     DevBuf table;
     size_t cap = 0;             // entries the device table has room for
-    hipStream_t copy_stream = nullptr;
+    Stream copy_stream;
 };
 
 static const long long FINITE_MAX_CHUNKS = INT32_MAX;
@@ -51,9 +51,7 @@ int pny_finite_create(pny_finite** out, int device) {
 
 void pny_finite_destroy(pny_finite* f) {
     if (!f) return;
-    (void)hipSetDevice(f->device);
-    f->table.release();   // (hipFree waits for launches that still read the table)
-    if (f->copy_stream) (void)hipStreamDestroy(f->copy_stream);
+    drain_device(f->device);
     delete f;
 }
 
@@ -65,7 +63,7 @@ int pny_finite_add_tensor(pny_finite* f, const float* dev, int64_t count, int gr
     if (f->host.size() >= (size_t)1 << 24 || f->chunks + chunks_of(count) > FINITE_MAX_CHUNKS)
         return fail(PNY_ERR_ARG, who + "table full");
     PNY_HIP(hipSetDevice(f->device));
-    if (!f->copy_stream) PNY_HIP(hipStreamCreateWithFlags(&f->copy_stream, hipStreamNonBlocking));
+    if ((rc = f->copy_stream.ensure(hipStreamNonBlocking, "hipStreamCreate(table copy)"))) return rc;
     const FiniteEntry e = {dev, (long long)count, group, (int)f->chunks};
     const size_t i = f->host.size();
     f->host.push_back(e);

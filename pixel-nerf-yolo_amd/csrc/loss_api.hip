@@ -15,6 +15,7 @@ namespace {
 // The ticket counter and the partial-sum table of a launch, one per (device, stream): launches on one stream follow one
 // another, so they can share it; launches on different streams may overlap and get their own.  Allocated on the first call on
 // a stream and zeroed ON that stream (no host wait); never freed (a few KB per stream the process ever used).
+// Raw and unfreed on purpose (not a DevBuf): a global's destructor would call hipFree after the HIP runtime may have shut down.
 std::mutex g_ws_mutex;
 std::map<std::pair<int, hipStream_t>, void*> g_ws;
 

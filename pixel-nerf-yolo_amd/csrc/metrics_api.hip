@@ -20,6 +20,7 @@ namespace {
 // theirs (loss_api.hip).  The table holds METRICS_WS_ROWS rows from the first call on a stream on, zeroed ON that stream; a
 // launch of more workgroups (more than 65 536 tiles: 2 000 views of 128 x 128) replaces it by a larger one, and only that
 // replacement waits for the device (hipFree).  Never freed otherwise.
+// Raw and unfreed on purpose (not a DevBuf): a global's destructor would call hipFree after the HIP runtime may have shut down.
 constexpr size_t METRICS_WS_ROWS = 65536;
 struct Workspace {
     void* p = nullptr;

@@ -283,6 +283,7 @@ static void launch_mlp_t(const MlpArgs& a, int grid, hipStream_t st) {
     static LdsLimit lds;
     (void)lds.raise(C::LDS, pny_mlp_kernel<C, ZP>);
 #ifdef PNY_STAMP
+    // debug buffers, raw and never freed on purpose: a static's destructor would run after the HIP runtime may have shut down
     static unsigned long long* dbuf = nullptr;
     const size_t nst = (size_t)grid * C::NW * ST_N;
     if (!dbuf) {

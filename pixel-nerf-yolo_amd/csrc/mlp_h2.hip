@@ -825,6 +825,7 @@ static void launch_mlp_h2_t(const MlpArgs& a, int grid, hipStream_t st) {
     static LdsLimit lds;
     (void)lds.raise(h2::lds_bytes(h2::MAX_NB) + extra, PNY_H2_KERNEL<STASH>);
 #ifdef PNY_H2_STAMP
+    // debug buffer, raw and never freed on purpose: a static's destructor would run after the HIP runtime may have shut down
     static unsigned long long* dbuf = nullptr;
     constexpr int NWV = h2::THREADS / 64;
     const size_t nst = (size_t)grid * NWV * HS_N;

@@ -11,10 +11,10 @@ using namespace pny;
 // The gradient pointers of one launch: host-pinned, read by the kernel itself (no copy command on the stream).  A table belongs
 // to its launch until `ev` has passed; the next step takes another one of the ring, so nothing waits for the device.
 struct AdamGradTable {
-    float** host = nullptr;
-    size_t cap = 0;   // pointers
-    hipEvent_t ev = nullptr;
+    PinnedBuf host;   // float* per tensor of the launch
+    Event ev;
     bool pending = false;
+    float** ptrs() const { return static_cast<float**>(host.p); }
 };
 
 struct pny_optim {
@@ -80,14 +80,8 @@ static int free_table(pny_optim* o, size_t need, AdamGradTable** out) {
         PNY_HIP(hipEventSynchronize(t->ev));
         t->pending = false;
     }
-    if (!t->ev) PNY_HIP(hipEventCreateWithFlags(&t->ev, hipEventDisableTiming));
-    if (t->cap < need) {
-        if (t->host) (void)hipHostFree(t->host);
-        t->host = nullptr;
-        t->cap = 0;
-        PNY_HIP(hipHostMalloc(reinterpret_cast<void**>(&t->host), need * sizeof(float*), hipHostMallocDefault));
-        t->cap = need;
-    }
+    if (int rc = t->ev.ensure(hipEventDisableTiming, "hipEventCreate(gradient table)")) return rc;
+    if (int rc = t->host.reserve(need * sizeof(float*), "hipHostMalloc(gradient table)")) return rc;
     *out = t;
     return 0;
 }
@@ -108,14 +102,7 @@ int pny_optim_create(pny_optim** out, int device) {
 
 void pny_optim_destroy(pny_optim* o) {
     if (!o) return;
-    (void)hipSetDevice(o->device);
-    o->tensors_dev.release();   // (hipFree waits for launches that still read the tables)
-    o->chunks_dev.release();
-    for (AdamGradTable& t : o->ring) {
-        if (t.pending) (void)hipEventSynchronize(t.ev);
-        if (t.ev) (void)hipEventDestroy(t.ev);
-        if (t.host) (void)hipHostFree(t.host);
-    }
+    drain_device(o->device);
     delete o;
 }
 
@@ -152,7 +139,7 @@ int pny_optim_adam_step(pny_optim* o, const pny_adam_hyper* h, float* const* gra
     if (any && c1 > c0) {
         AdamGradTable* t = nullptr;
         if ((rc = free_table(o, (size_t)n, &t))) return rc;
-        for (int i = 0; i < n; ++i) t->host[i] = grads_dev[i];
+        for (int i = 0; i < n; ++i) t->ptrs()[i] = grads_dev[i];
         // torch.optim.Adam's scalars (_single_tensor_adam), in double; each reaches the kernel rounded to fp32 once
         const double bc1 = 1.0 - std::pow(h->beta1, (double)h->step), bc2 = 1.0 - std::pow(h->beta2, (double)h->step);
         AdamScalars sc;
@@ -164,7 +151,7 @@ int pny_optim_adam_step(pny_optim* o, const pny_adam_hyper* h, float* const* gra
         sc.eps = (float)h->eps;
         sc.weight_decay = (float)h->weight_decay;
         launch_adam(reinterpret_cast<const AdamTensor*>(o->tensors_dev.p), reinterpret_cast<const AdamChunk*>(o->chunks_dev.p) + c0,
-                    c1 - c0, t->host, first, sc, st);
+                    c1 - c0, t->ptrs(), first, sc, st);
         PNY_HIP(hipGetLastError());
         PNY_HIP(hipEventRecord(t->ev, st));
         t->pending = true;

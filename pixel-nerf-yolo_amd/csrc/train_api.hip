@@ -212,17 +212,15 @@ size_t stash_budget_bytes() {
 int run_weight_grads(pny_model* m, TrainPlan& plan, int n_tiles, const float* x_stash, const float* dy_stash, DevBuf& partial,
                      DevBuf& bias, DevBuf& tables, PinnedStage& stage, int accumulate, hipStream_t st,
                      const unsigned* dy_absmax = nullptr, int planes = 2) {
-    if (!m->aux_stream) {
-        PNY_HIP(hipStreamCreateWithFlags(&m->aux_stream, hipStreamNonBlocking));
-        PNY_HIP(hipEventCreateWithFlags(&m->aux_fork, hipEventDisableTiming));
-        PNY_HIP(hipEventCreateWithFlags(&m->aux_join, hipEventDisableTiming));
-    }
+    int rc;
+    if ((rc = m->aux_stream.ensure(hipStreamNonBlocking, "hipStreamCreate(weight-gradient side stream)"))) return rc;
+    if ((rc = m->aux_fork.ensure(hipEventDisableTiming, "hipEventCreate(side stream fork)"))) return rc;
+    if ((rc = m->aux_join.ensure(hipEventDisableTiming, "hipEventCreate(side stream join)"))) return rc;
     const int cus = mlp_max_grid(MLP_8x64);
     std::vector<DwItem> items;
     long long part_floats = 0, bias_floats = 0;
     int n_full = 0;
     build_items(plan, n_tiles, cus, items, &part_floats, &bias_floats, &n_full);
-    int rc;
     if ((rc = partial.reserve((size_t)part_floats * sizeof(float)))) return rc;
     if ((rc = bias.reserve((size_t)bias_floats * sizeof(float)))) return rc;
     const size_t jb_bytes = plan.jobs.size() * sizeof(DwJob), it_bytes = items.size() * sizeof(DwItem),
@@ -233,7 +231,7 @@ int run_weight_grads(pny_model* m, TrainPlan& plan, int n_tiles, const float* x_
     // the previous call's kernels (same stream) were enqueued: hipFree of DevBuf::reserve synchronises the device
     if ((rc = tables.reserve(total))) return rc;
     if ((rc = stage.prepare(total))) return rc;
-    char* h = reinterpret_cast<char*>(stage.host);
+    char* h = reinterpret_cast<char*>(stage.host.p);
     memcpy(h, plan.jobs.data(), jb_bytes);
     memcpy(h + o_items, items.data(), it_bytes);
     memcpy(h + o_targets, plan.targets.data(), tg_bytes);
@@ -386,7 +384,7 @@ BwdArgs chain_args(const pny_scene* s, const MlpBackwardCall& c, int which, cons
     b.d_out = d.d_out;
     b.yolo = d.yolo;
     b.dy_absmax = t.absmax;
-    b.range_flag = m->range_flag;
+    b.range_flag = m->range_flag();
     if (lg.on) {
         b.dy_absmax = lg.max_word;
         if (!t.absmax) b.range_flag = nullptr;   // (the fp32 path keeps its semantics: no f16 range guard)
@@ -586,8 +584,8 @@ int pny_model_flush_weight_grads(pny_model* m, int accumulate, pny_stream stream
         ds.flush_flops = 0.0;
         ds.flush_launches = 0;
     }
-    for (int i = 0; i < 4; ++i)
-        if (!ds.flush_ev[i]) PNY_HIP(hipEventCreate(&ds.flush_ev[i]));
+    for (Event& e : ds.flush_ev)
+        if ((rc = e.ensure(hipEventDefault, "hipEventCreate(flush timing)"))) return rc;
     const pny_model_desc& d = m->desc;
     const double fwd = mlp_flops_per_point(d, ds.book.ns, PASS_FORWARD);
     const int last = only_c ? 0 : 1;   // the last MLP this call flushes
