@@ -341,6 +341,70 @@ int pny_nms(const float* boxes_dev, int n, double iou_threshold, double threshol
 int pny_tp_fp_fn(const float* target_boxes_dev, int nt, const float* pred_boxes_dev, int np, double nms_iou,
                  double nms_threshold, double match_iou, int* out_dev, pny_stream stream);
 
+/* The detection scores of ALL views of a YOLO metric pass in ONE launch: what YoloTrainer.metric_step
+ * (train/trainlib/YoloTrainer.py:338-354, driven by eval/eval_yolo.py) does per destination view -- the cells of every scale
+ * turned into Python lists (:283-289, util.convert_cells_to_bboxes src/util/util.py:633-689), util.calculate_tp_fp_fn on the two
+ * lists (:348; util.py:765-802 with nms :691-722 and iou :575-611) and the running sums of tp, fp, fn (:349-351) -- without a
+ * launch chain and a device -> host read per view.  One 256-thread workgroup per view (grid = n_views) runs, for the target list
+ * and then for the prediction list, in the same LDS: decode + the confidence and size filters + order-preserving compaction of
+ * the survivors ("candidates"), the stable descending sort by confidence, the greedy suppression with the reference's list
+ * semantics (exactly pny_nms'), then the matching of pny_tp_fp_fn, the view's record, and integer atomic adds into the totals.
+ * The box decode and the IoU are the device code of pny_cells_to_bboxes / pny_nms / pny_tp_fp_fn (csrc/pny_detect.h), so every
+ * count equals the per-view path's; all results are integers or copied floats: the same bits on every run.
+ * One kernel enqueued on `stream`; no allocation, no copy, no synchronisation; anchors_host is read before the call returns.
+ *
+ * Input forms (desc->form):
+ *   PNY_DETECT_CELLS  preds_dev[s] (n_views * Hs * Ws, n_anchors, 7) and targets_dev[s] (n_views * Hs * Ws, n_anchors, 6) for each
+ *     scale s, Hs = height / cell_sizes[s], Ws = width / cell_sizes[s] (integer division), rows ordered (view, y, x): what
+ *     pny_yolo_train_batch and pny_yolo_render give.  A view's list is its cells of scale 0, 1, ... in that order and, within a
+ *     scale, in the (y, x, anchor) order of pny_cells_to_bboxes.  anchors_host (n_scales * n_anchors, 2).  The row pointers and
+ *     offsets are not looked at.
+ *   PNY_DETECT_BOXES  already decoded rows [class, score, x, y, w, h]: pred_rows_dev (n_pred_rows, 6) with pred_offsets_dev
+ *     (n_views + 1 int32, on the device): view v owns rows [offsets[v], offsets[v + 1]); targets the same.  No decode.  The
+ *     per-scale pointers, anchors_host and the geometry fields are not looked at.  The kernel checks every segment against
+ *     0 <= offsets[v] <= offsets[v + 1] <= n_rows; a view whose segment fails has status PNY_DETECT_BAD_SEGMENT.
+ *
+ * Limit: a view may hold any number of cells or rows, but at most PNY_DETECT_MAX_CANDIDATES of one list of one view may pass the
+ * filters (53 bytes of LDS each: 106 KB of gfx950's 160 KB at the limit; the real geometry, 30 x 16 + 15 x 8 + 7 x 4 cells x 3
+ * anchors = 1884 boxes, fits whatever passes).  A view above it is NOT truncated: its status is non-zero, its tp, fp, fn and
+ * kept counts are 0, it adds nothing to totals[0..2] and 1 to totals[3].
+ *
+ * Outputs:
+ *   per_view_dev (n_views, 8) int32: tp, fp, fn, kept targets, kept predictions, targets above nms_threshold, predictions above
+ *     nms_threshold (the third result of util.nms: counted before the size filter), status (0, or PNY_DETECT_* bits);
+ *   highest_conf_dev (n_views, 2): the highest score over ALL boxes of the target and of the prediction list (-inf if empty);
+ *   totals_dev 4 x int64: tp, fp, fn, failed views.  The call ADDS to them; the caller zeroes them before a pass;
+ *   kept_targets_dev, kept_preds_dev: NULL or (n_views, max_kept, 6), the first max_kept survivors of each view in the
+ *     reference's output order (the counts in the record are the full ones; rows past a view's count are left as they are).
+ * PNY_ERR_ARG, before any launch, pny_last_error naming the field: a NULL desc or required pointer, an unknown form, n_views
+ * below 1, n_scales outside 1 .. PNY_YOLO_BATCH_MAX_SCALES, n_anchors outside 1 .. 4 (the limit of pny_cells_to_bboxes), a cell
+ * size below 1 or above the image, a view of 2^31 or more cells, negative row counts, a negative max_kept or one of 0 with a kept
+ * pointer, non-finite thresholds. */
+#define PNY_DETECT_MAX_CANDIDATES 2048
+enum { PNY_DETECT_CELLS = 0, PNY_DETECT_BOXES = 1 };
+enum { PNY_DETECT_TARGETS_OVERFLOW = 1, PNY_DETECT_PREDS_OVERFLOW = 2, PNY_DETECT_BAD_SEGMENT = 4 };   /* status bits */
+#define PNY_DETECT_RECORD 8
+typedef struct pny_detect_views_desc {
+    int32_t form;          /* PNY_DETECT_CELLS or PNY_DETECT_BOXES */
+    int32_t n_views;
+    int32_t n_scales;      /* cells form: 1 .. PNY_YOLO_BATCH_MAX_SCALES */
+    int32_t height;        /* cells form: the full-resolution image, as pny_yolo_batch_desc */
+    int32_t width;
+    int32_t cell_sizes[PNY_YOLO_BATCH_MAX_SCALES];
+    int32_t n_anchors;     /* cells form: A per scale, 1 .. 4 */
+    int32_t n_pred_rows;   /* boxes form: rows of pred_rows_dev */
+    int32_t n_target_rows; /* boxes form: rows of target_rows_dev */
+    int32_t max_kept;      /* rows per view of kept_targets_dev / kept_preds_dev */
+    double nms_iou;        /* util.nms iou_threshold (compared in fp32, strictly) */
+    double nms_threshold;  /* util.nms threshold (compared in double, strictly) */
+    double match_iou;      /* calculate_tp_fp_fn's IoU (fp32; best > match_iou is a tp, best < match_iou a fn) */
+} pny_detect_views_desc;
+int pny_detect_views(const pny_detect_views_desc* desc, const float* const* preds_dev, const float* const* targets_dev,
+                     const float* anchors_host, const float* pred_rows_dev, const int32_t* pred_offsets_dev,
+                     const float* target_rows_dev, const int32_t* target_offsets_dev, int32_t* per_view_dev,
+                     float* highest_conf_dev, int64_t* totals_dev, float* kept_targets_dev, float* kept_preds_dev,
+                     pny_stream stream);
+
 /* Latent projection.  `x = x + lin_z[b](z)` (src/model/resnetfc.py:176-182) with z the bilinear
  * interpolation of the latent (src/model/encoder.py:101) is linear in the latent, so
  * lin_z[b](interp(latent)) == interp(lin_z[b](latent)) up to fp32 rounding: with projection ON the

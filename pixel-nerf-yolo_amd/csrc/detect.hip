@@ -11,24 +11,11 @@
 // These are tiny, latency-bound, integer/compare workloads (<= a few thousand boxes per view): one
 // workgroup, index lists in LDS, boxes read from L2.
 #include "pny_common.h"
+#include "pny_detect.h"
 
 namespace pny {
 
-// iou(box1, box2) of reference util.py:576-611 (is_pred=True), [x, y, w, h] boxes, fp32 op for op.
-__device__ __forceinline__ float iou_xywh(const float* a, const float* b) {
-    const float a_x1 = a[0] - a[2] / 2.0f, a_y1 = a[1] - a[3] / 2.0f;
-    const float a_x2 = a[0] + a[2] / 2.0f, a_y2 = a[1] + a[3] / 2.0f;
-    const float b_x1 = b[0] - b[2] / 2.0f, b_y1 = b[1] - b[3] / 2.0f;
-    const float b_x2 = b[0] + b[2] / 2.0f, b_y2 = b[1] + b[3] / 2.0f;
-    const float x1 = fmaxf(a_x1, b_x1), y1 = fmaxf(a_y1, b_y1);
-    const float x2 = fminf(a_x2, b_x2), y2 = fminf(a_y2, b_y2);
-    const float inter = fmaxf(x2 - x1, 0.0f) * fmaxf(y2 - y1, 0.0f);
-    const float area_a = fabsf((a_x2 - a_x1) * (a_y2 - a_y1));
-    const float area_b = fabsf((b_x2 - b_x1) * (b_y2 - b_y1));
-    const float uni = area_a + area_b - inter;
-    return inter / (uni + 1e-6f);
-}
-
+// iou_xywh and the cell decode live in pny_detect.h: detect_views.hip runs the same device code
 // ------------------------------------------------------------------ cells -> boxes
 __global__ void cells_to_bboxes_kernel(const float* __restrict__ cells, int h, int w, int na, int is_pred,
                                        float ax0, float ay0, float ax1, float ay1, float ax2, float ay2,
@@ -36,35 +23,9 @@ __global__ void cells_to_bboxes_kernel(const float* __restrict__ cells, int h, i
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= h * w * na) return;
     const int a = i % na, x = (i / na) % w, y = i / (na * w);
-    const int C = is_pred ? 7 : 6;
-    const float* c = cells + (size_t)i * C;
-    float bx = c[1], by = c[2], bw = c[3], bh = c[4], cls;
-    if (is_pred) {
-        const float aw = a == 0 ? ax0 : a == 1 ? ax1 : a == 2 ? ax2 : ax3;
-        const float ah = a == 0 ? ay0 : a == 1 ? ay1 : a == 2 ? ay2 : ay3;
-        bx = 1.0f / (1.0f + expf(-bx));
-        by = 1.0f / (1.0f + expf(-by));
-        bw = expf(bw) * aw;
-        bh = expf(bh) * ah;
-        // torch.argmax over the class logits (first maximum wins)
-        int best = 0;
-        float bv = c[5];
-        for (int k = 1; k < C - 5; ++k)
-            if (c[5 + k] > bv) {
-                bv = c[5 + k];
-                best = k;
-            }
-        cls = (float)best;
-    } else {
-        cls = c[5];
-    }
-    float* o = out + (size_t)i * 6;
-    o[0] = cls;
-    o[1] = c[0];
-    o[2] = inv_w * (bx + (float)x);
-    o[3] = inv_h * (by + (float)y);
-    o[4] = inv_w * bw;
-    o[5] = inv_h * bh;
+    const float aw = a == 0 ? ax0 : a == 1 ? ax1 : a == 2 ? ax2 : ax3;
+    const float ah = a == 0 ? ay0 : a == 1 ? ay1 : a == 2 ? ay2 : ay3;
+    cell_to_bbox(cells + (size_t)i * (is_pred ? 7 : 6), is_pred, x, y, aw, ah, inv_w, inv_h, out + (size_t)i * 6);
 }
 
 // ------------------------------------------------------------------ nms

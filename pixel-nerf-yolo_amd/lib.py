@@ -102,6 +102,12 @@ class YoloTargetsDesc(C.Structure):
                 ("n_scales", C.c_int32), ("cell_sizes", C.c_int32 * 4), ("n_anchors", C.c_int32), ("ignore_iou_thresh", C.c_float)]
 
 
+class DetectViewsDesc(C.Structure):
+    _fields_ = [("form", C.c_int32), ("n_views", C.c_int32), ("n_scales", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("cell_sizes", C.c_int32 * 4), ("n_anchors", C.c_int32), ("n_pred_rows", C.c_int32), ("n_target_rows", C.c_int32),
+                ("max_kept", C.c_int32), ("nms_iou", C.c_double), ("nms_threshold", C.c_double), ("match_iou", C.c_double)]
+
+
 # name -> (restype, argtypes); every symbol include/pnyolo.h declares
 SIGNATURES = {
     "pny_version": (C.c_int, []),
@@ -154,6 +160,9 @@ SIGNATURES = {
                           C.c_void_p]),
     "pny_tp_fp_fn": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double,
                                C.c_void_p, C.c_void_p]),
+    "pny_detect_views": (C.c_int, [C.POINTER(DetectViewsDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_float_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
     "pny_scene_set_projection": (C.c_int, [C.c_void_p, C.c_int]),
     "pny_scene_set_precision": (C.c_int, [C.c_void_p, C.c_int]),
     "pny_scene_bind_latent_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -245,6 +254,12 @@ GT_FLAT, METRICS_WIN = 2, 7                                   # PNY_GT_FLAT (uti
 IMG_F32_NCHW_PM1, IMG_U8_NHWC, JITTER_MAX_OBJS = 0, 1, 64     # PNY_IMG_*, PNY_JITTER_MAX_OBJS
 RESIZE = {"none": 0, "bilinear_u8": 1, "area": 2}             # PNY_RESIZE_*
 YOLO_TARGETS_MAX_ANCHORS = 64                                 # PNY_YOLO_TARGETS_MAX_ANCHORS
+# pny_detect_views: candidates of one list of one view (PNY_DETECT_MAX_CANDIDATES: 53 bytes of LDS each), its input forms, the
+# columns of a view's record and its status bits (PNY_DETECT_*)
+DETECT_MAX_CANDIDATES, DETECT_MAX_ANCHORS = 2048, 4
+DETECT_CELLS, DETECT_BOXES = 0, 1
+DETECT_RECORD = ("tp", "fp", "fn", "kept_targets", "kept_preds", "targets_above", "preds_above", "status")
+DETECT_TARGETS_OVERFLOW, DETECT_PREDS_OVERFLOW, DETECT_BAD_SEGMENT = 1, 2, 4
 MC_SCAN_TILE, MC_MAX_POINTS = 1024, (2 ** 31 - 1) // 3        # csrc/pny_recon.h: points per scan tile; 3 X Y Z < 2^31
 MAX_LATENT_LEVELS = 8                                         # PNY_MAX_LATENT_LEVELS
 # bits of the `accumulate` argument of the backward calls and of pny_model_flush_weight_grads (include/pnyolo.h)

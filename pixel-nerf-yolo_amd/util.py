@@ -5,7 +5,8 @@ device (that of ``poses``, or the current one when ``poses`` is a CPU tensor as 
 ``sample_train_batch`` is the trainer's ray batch and ground truth in one launch (no counterpart function in the reference:
 it replaces the per-object loop of train/trainlib/PixelNerfTrainer.py:76-123).  ``yolo_train_batch`` /
 ``stage_yolo_targets`` (``build_yolo_targets``: the grids built on the device from the label rows) and ``FiniteMonitor`` are the same for the YOLO trainer: the batch of train/trainlib/YoloTrainer.py:93-129
-in one launch, and its NaN / Inf tests (:163-194) without a host wait.  ``psnr`` is the reference's util.psnr (:502-509) on
+in one launch, and its NaN / Inf tests (:163-194) without a host wait.  ``score_detections`` / ``DetectionMeter`` score all views of
+a YOLO metric pass (YoloTrainer.py:338-354) in one launch per source-view set and one read per pass.  ``psnr`` is the reference's util.psnr (:502-509) on
 device tensors (metrics.py).
 """
 import ctypes as C
@@ -465,3 +466,217 @@ def calculate_precision_recall_f1(tp, fp, fn):
     recall = tp / (tp + fn) if tp + fn > 0 else 0
     f1 = 2 * (precision * recall) / (precision + recall) if precision + recall > 0 else 0
     return precision, recall, f1
+
+
+# ------------------------------------------------------------------ YOLO metric pass: all views in one launch
+class DetectionScores:
+    """What ``score_detections`` leaves on the device; nothing here has been read by the host.
+
+    per_view (V, 8) int32, columns ``lib.DETECT_RECORD``: tp, fp, fn, kept targets, kept predictions, targets and predictions
+    above the confidence threshold, status (0, or ``lib.DETECT_*`` bits: the view was refused and counts as 0).
+    highest_conf (V, 2): the highest score of all target / prediction boxes of the view.
+    totals (4,) int64: tp, fp, fn, refused views -- the tensor the call added to.
+    kept_targets, kept_preds: None, or (V, max_kept, 6) survivors in the reference's output order (want_boxes=True); the
+    counts are in per_view, rows past a view's count are not written."""
+
+    def __init__(self, per_view, highest_conf, totals, kept_targets=None, kept_preds=None):
+        self.per_view, self.highest_conf, self.totals = per_view, highest_conf, totals
+        self.kept_targets, self.kept_preds = kept_targets, kept_preds
+
+
+def _detect_fail(msg, exc=ValueError):
+    raise exc("pixel_nerf_yolo_amd.util.score_detections: " + msg)
+
+
+def _detect_tensor(t, name, dev):
+    """A float32 tensor on the GPU, contiguous (a copy on the device if it was not)."""
+    if not torch.is_tensor(t):
+        _detect_fail("%s must be a torch tensor, got %s" % (name, type(t).__name__), TypeError)
+    if t.dtype != torch.float32:
+        _detect_fail("%s must be float32, got %s" % (name, t.dtype), TypeError)
+    if t.device.type != "cuda":
+        _detect_fail("%s is on %s; the scorer runs on an MI355X only (the host path is calculate_tp_fp_fn per view)"
+                     % (name, t.device), _lib.PnyError)
+    if dev is not None and t.device != dev:
+        _detect_fail("%s is on %s, the other inputs on %s" % (name, t.device, dev))
+    return t.detach().contiguous()
+
+
+def _detect_offsets(off, name, n_rows, n_views):
+    """(V + 1) int32 offsets.  A host tensor / list is checked here (starts at 0, ascends, ends inside the rows) and copied over;
+    a device tensor is used in place and checked by the kernel (a bad segment is a refused view)."""
+    if torch.is_tensor(off) and off.device.type == "cuda":
+        if off.dtype != torch.int32 or off.dim() != 1:
+            _detect_fail("%s on the device must be a 1-d int32 tensor, got %s %s" % (name, off.dtype, tuple(off.shape)), TypeError)
+        if n_views is not None and off.numel() != n_views + 1:
+            _detect_fail("%s must hold n_views + 1 = %d entries, got %d" % (name, n_views + 1, off.numel()))
+        return off.contiguous(), None
+    o = torch.as_tensor(off)
+    if o.dim() != 1 or o.numel() < 2 or o.dtype.is_floating_point or o.dtype == torch.bool:
+        _detect_fail("%s must be a 1-d integer sequence of V + 1 entries, got %s %s" % (name, o.dtype, tuple(o.shape)))
+    if n_views is not None and o.numel() != n_views + 1:
+        _detect_fail("%s must hold n_views + 1 = %d entries, got %d" % (name, n_views + 1, o.numel()))
+    v = o.to(torch.int64).tolist()
+    if v[0] != 0:
+        _detect_fail("%s must start at 0, got %d" % (name, v[0]))
+    if any(b < a for a, b in zip(v, v[1:])):
+        _detect_fail("%s must ascend, got %s" % (name, v if len(v) <= 20 else v[:20] + ["..."]))
+    if v[-1] > n_rows:
+        _detect_fail("%s ends at %d, past the %d rows" % (name, v[-1], n_rows))
+    return o.to(torch.int32), max(b - a for a, b in zip(v, v[1:]))
+
+
+def score_detections(preds, targets, anchors, height, width, cell_sizes, nms_iou, nms_t, match_iou, n_views=None, totals=None,
+                     want_boxes=False, boxes=None):
+    """
+    The detection counts of all views of a YOLO metric step in ONE launch (include/pnyolo.h pny_detect_views): what the
+    reference's YoloTrainer.metric_step (train/trainlib/YoloTrainer.py:338-354) does per destination view --
+    convert_cells_to_bboxes per scale, .tolist(), calculate_tp_fp_fn -- with equal counts, for every view at once and without a
+    host read.  The call returns as soon as the kernel is enqueued.
+
+    :param preds num_scales tensors (n_views * Hs * Ws, A, 7), the renders of ``YoloRenderer`` on the rays of
+           ``yolo_train_batch``; targets num_scales tensors (n_views * Hs * Ws, A, 6), its target cells.  fp32, on the GPU;
+           non-contiguous ones are copied there.  A view's list is its cells of every scale in turn, (y, x, anchor) within one.
+    :param anchors (num_scales * A, 2) or (num_scales, A, 2), A <= 4; height, width the image; cell_sizes one per scale (<= 4)
+    :param nms_iou, nms_t, match_iou as ``calculate_tp_fp_fn`` takes them
+    :param n_views views in the lists (required for cells; for boxes implied by the offsets)
+    :param totals a (4,) int64 device tensor [tp, fp, fn, refused views] to ADD to (``DetectionMeter`` owns one); None: a fresh one
+    :param want_boxes also the kept boxes of both lists per view
+    :param boxes instead of preds / targets (pass None for both and for anchors / height / width / cell_sizes):
+           (pred_rows, pred_offsets, target_rows, target_offsets) -- decoded rows (n, 6) [class, score, x, y, w, h] on the GPU and
+           V + 1 offsets each, on the host (checked here) or int32 on the device (checked by the kernel)
+    :return DetectionScores of device tensors
+
+    At most ``lib.DETECT_MAX_CANDIDATES`` (2048) boxes of one list of one view may pass the confidence and size filters; a view
+    above that is refused, not truncated: its status is non-zero and it counts in totals[3] alone.
+    """
+    dev = None
+    keep = []
+    desc = _lib.DetectViewsDesc(nms_iou=float(nms_iou), nms_threshold=float(nms_t), match_iou=float(match_iou))
+    p_ptrs = t_ptrs = anc_ptr = None
+    rows = [None, None]
+    offs = [None, None]
+    if boxes is not None:
+        if preds is not None or targets is not None:
+            _detect_fail("give either preds / targets (cells) or boxes=, not both")
+        if len(boxes) != 4:
+            _detect_fail("boxes must be (pred_rows, pred_offsets, target_rows, target_offsets)")
+        longest = 0
+        checked = []
+        for i, name in ((0, "pred"), (2, "target")):
+            r = boxes[i]
+            if not torch.is_tensor(r) or r.dim() != 2 or r.shape[1] != 6:
+                _detect_fail("%s_rows must be a (n, 6) tensor, got %s" % (name, tuple(r.shape) if torch.is_tensor(r) else type(r).__name__))
+            o, seg = _detect_offsets(boxes[i + 1], name + "_offsets", r.shape[0], n_views)
+            if n_views is None:
+                n_views = o.numel() - 1
+            elif o.numel() != n_views + 1:
+                _detect_fail("%s_offsets must hold n_views + 1 = %d entries, got %d" % (name, n_views + 1, o.numel()))
+            longest = max(longest, r.shape[0] if seg is None else seg)
+            checked.append((r, o, name))
+        for k, (r, o, name) in enumerate(checked):
+            rows[k] = _detect_tensor(r, name + "_rows", dev)
+            dev = rows[k].device
+            offs[k] = o if o.device == dev else o.to(dev, non_blocking=True)
+        desc.form, desc.n_views = _lib.DETECT_BOXES, int(n_views)
+        desc.n_pred_rows, desc.n_target_rows = rows[0].shape[0], rows[1].shape[0]
+    else:
+        if preds is None or targets is None:
+            _detect_fail("preds and targets (one tensor per scale), or boxes=, are required")
+        preds, targets = list(preds), list(targets)
+        cells = [int(v) for v in cell_sizes]
+        if not 1 <= len(cells) <= _lib.YOLO_BATCH_MAX_SCALES:
+            _detect_fail("cell_sizes must hold 1 .. %d scales, got %d" % (_lib.YOLO_BATCH_MAX_SCALES, len(cells)))
+        if len(preds) != len(cells) or len(targets) != len(cells):
+            _detect_fail("one prediction and one target tensor per scale: %d scales, %d preds, %d targets" % (len(cells), len(preds), len(targets)))
+        anc = torch.as_tensor(anchors, dtype=torch.float32).detach().cpu()
+        if anc.dim() == 3 and anc.shape[0] == len(cells) and anc.shape[2] == 2:
+            anc = anc.reshape(-1, 2)
+        if anc.dim() != 2 or anc.shape[1] != 2 or anc.shape[0] == 0 or anc.shape[0] % len(cells):
+            _detect_fail("anchors must be (num_scales * A, 2) with %d scale%s, got %s" % (len(cells), "" if len(cells) == 1 else "s", tuple(anc.shape)))
+        A = anc.shape[0] // len(cells)
+        if A > _lib.DETECT_MAX_ANCHORS:
+            _detect_fail("at most %d anchors per scale, got %d" % (_lib.DETECT_MAX_ANCHORS, A))
+        anc = anc.contiguous()
+        height, width = int(height), int(width)
+        if n_views is None or int(n_views) < 1:
+            _detect_fail("n_views (the views in the lists) must be given and positive, got %r" % (n_views,))
+        n_views = int(n_views)
+        longest = 0
+        for s, cell in enumerate(cells):
+            if not 1 <= cell <= min(height, width):
+                _detect_fail("cell_sizes[%d] = %d must be 1 .. min(height, width)" % (s, cell))
+            per = (height // cell) * (width // cell)
+            longest += per * A
+            for t, name, cols in ((preds[s], "preds", 7), (targets[s], "targets", 6)):
+                if not torch.is_tensor(t) or t.dim() != 3:
+                    _detect_fail("%s[%d] must be a (n_views * Hs * Ws, A, %d) tensor, got %s"
+                                 % (name, s, cols, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+                if tuple(t.shape) != (n_views * per, A, cols):
+                    _detect_fail("%s[%d] must be (n_views * Hs * Ws, A, %d) = %s, got %s" % (name, s, cols, (n_views * per, A, cols), tuple(t.shape)))
+        for s in range(len(cells)):
+            preds[s] = _detect_tensor(preds[s], "preds[%d]" % s, dev)
+            dev = preds[s].device
+            targets[s] = _detect_tensor(targets[s], "targets[%d]" % s, dev)
+        desc.form, desc.n_views, desc.n_scales, desc.height, desc.width = _lib.DETECT_CELLS, n_views, len(cells), height, width
+        desc.cell_sizes, desc.n_anchors = (C.c_int32 * 4)(*cells), A
+        p_ptrs = (C.c_void_p * len(cells))(*[t.data_ptr() for t in preds])
+        t_ptrs = (C.c_void_p * len(cells))(*[t.data_ptr() for t in targets])
+        anc_ptr = C.cast(anc.data_ptr(), _lib.c_float_p)
+        keep = [preds, targets, anc]
+    if totals is None:
+        totals = torch.zeros(4, device=dev, dtype=torch.int64)
+    elif not (torch.is_tensor(totals) and totals.dtype == torch.int64 and tuple(totals.shape) == (4,) and totals.device == dev
+              and totals.is_contiguous()):
+        _detect_fail("totals must be a contiguous (4,) int64 tensor on %s" % dev)
+    V = desc.n_views
+    per_view = torch.empty(V, len(_lib.DETECT_RECORD), device=dev, dtype=torch.int32)
+    hc = torch.empty(V, 2, device=dev, dtype=torch.float32)
+    kt = kp = None
+    if want_boxes:
+        desc.max_kept = max(1, min(int(longest), _lib.DETECT_MAX_CANDIDATES))
+        kt = torch.zeros(V, desc.max_kept, 6, device=dev, dtype=torch.float32)
+        kp = torch.zeros(V, desc.max_kept, 6, device=dev, dtype=torch.float32)
+    vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+    with torch.cuda.device(dev):
+        check(_lib.load().pny_detect_views(C.byref(desc), p_ptrs, t_ptrs, anc_ptr, vp(rows[0]), vp(offs[0]), vp(rows[1]), vp(offs[1]),
+                                           vp(per_view), vp(hc), vp(totals), vp(kt), vp(kp), stream_of(dev)))
+    del keep
+    return DetectionScores(per_view, hc, totals, kt, kp)
+
+
+class DetectionMeter:
+    """
+    The running tp / fp / fn of a YOLO metric pass (the three sums of YoloTrainer.metric_step, train/trainlib/YoloTrainer.py:349-351,
+    over the whole test loader): ``update`` is ``score_detections`` adding into the meter's own four device words -- one launch, no
+    read -- and ``report`` is the pass's ONE device-to-host read.
+
+        meter = DetectionMeter(device)
+        for batch in test_loader:  meter.update(renders, target_cells, anchors, H, W, cell_sizes, nms_iou, nms_t, match_iou, n_views=NS)
+        precision, recall, f1 = meter.report(prf=True);  meter.reset()
+    """
+
+    def __init__(self, device):
+        self.device = _device_of(torch.empty(0), device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.totals = torch.zeros(4, device=self.device, dtype=torch.int64)
+
+    def update(self, *args, **kwargs):
+        """``score_detections(...)`` into this meter's totals -> its DetectionScores (per-view records, still on the device)."""
+        assert "totals" not in kwargs, "the meter adds into its own totals"
+        return score_detections(*args, totals=self.totals, **kwargs)
+
+    def reset(self):
+        self.totals.zero_()
+
+    def report(self, prf=False):
+        """(tp, fp, fn), or with prf=True (precision, recall, f1) by ``calculate_precision_recall_f1``.  Raises PnyError when
+        views were refused (more than ``lib.DETECT_MAX_CANDIDATES`` candidates, or a bad segment): the sums would miss them."""
+        tp, fp, fn, failed = (int(v) for v in self.totals.cpu().tolist())
+        if failed:
+            raise _lib.PnyError("pixel_nerf_yolo_amd.util.DetectionMeter.report: %d view%s refused since the last reset (more than %d "
+                                "candidates in one list of a view, or a bad segment): tp, fp, fn would miss them; the per-view "
+                                "status of every update names them" % (failed, " was" if failed == 1 else "s were",
+                                                                       _lib.DETECT_MAX_CANDIDATES))
+        return calculate_precision_recall_f1(tp, fp, fn) if prf else (tp, fp, fn)
