@@ -316,6 +316,13 @@ def check(rc):
         raise PnyError("libpnyolo: %s (status %d)" % (load().pny_last_error().decode("utf-8", "replace"), rc))
 
 
+def _get_int(fn, handle):
+    """The value of a one-integer getter ``int fn(handle, int* out)``."""
+    v = C.c_int(0)
+    check(fn(handle, C.byref(v)))
+    return int(v.value)
+
+
 def ptr(t):
     """Raw device / host pointer of a contiguous fp32 torch tensor (or None)."""
     if t is None:

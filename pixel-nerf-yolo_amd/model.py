@@ -9,9 +9,11 @@ No torch operator runs on the hot path: ``encode`` and ``forward`` hand raw devi
 the C ABI (include/pnyolo.h).  Forward only -- a call under autograd raises (backward is the
 "next" row of SURVEY.md 8f).
 """
+import contextlib
 import ctypes as C
 import os
 import os.path as osp
+import types
 import warnings
 
 import numpy as np
@@ -222,6 +224,18 @@ class PixelNeRFNet(nn.Module):
 
     def __init__(self, conf, stop_encoder_grad=False):
         super().__init__()
+        # native handles (created lazily on the module's CUDA device); first, so that _free_native() finds them on an object
+        # whose construction raised below
+        self._h_model = None
+        self._h_device = None
+        self._h_has_fine = False
+        self._h_scenes = []
+        # Super-batch in ONE scene (include/pnyolo.h pny_scene_set_groups): the training render of SB > 1 objects runs on this
+        # handle -- one MLP launch per pass over every object's tiles.  _group = dict(SB, NS) while it holds the last encode();
+        # the per-object handles are then filled on first use (_scenes_pending: the encode()'s cameras, _fill_scene).
+        self._h_group = None
+        self._group = None
+        self._scenes_pending = None
         self._conf = conf                  # kept for replicas on other devices (render._MultiDeviceRenderWrapper)
         self._encode_epoch = 0             # bumped by every encode(): replicas re-fetch the scene state when it moved
         self._last_encode = None
@@ -257,20 +271,20 @@ class PixelNeRFNet(nn.Module):
         self.d_latent = d_latent
         self.num_objs = 0
         self.num_views_per_obj = 1
-        # native handles (created lazily on the module's CUDA device)
-        self._h_model = None
-        self._h_device = None
-        self._h_has_fine = False
-        self._h_scenes = []
-        # Super-batch in ONE scene (include/pnyolo.h pny_scene_set_groups): the training render of SB > 1 objects runs on this
-        # handle -- one MLP launch per pass over every object's tiles.  _group = dict(SB, NS) while it holds the last encode();
-        # the per-object handles are then filled on first use (_scenes_pending).
-        self._h_group = None
-        self._group = None
-        self._scenes_pending = None
         self._last_call_group = False
-        self._synced_key = None
-        self._dev_bound = False
+        self._tracked, self._tracked_sig = [], None   # _weights_key: the (name, tensor) list and the structure it was built for
+        self._synced_key = None            # the weights key the native copy holds
+        self._dev_bound = False            # the library reads every MLP parameter in place (pny_model_bind_param)
+        self._trunk_bound = False          # ... and every parameter of the trunk: the training trunk can run
+        self._enc_stale = False            # the inference trunk's folded copy is behind the live encoder tensors
+        self._latent_src = None            # the latent of the last encode() that takes a gradient (differentiable_latent)
+        self._latent_channel_last = False  # ... stands for a list of feature maps: (SB * NS, Hl, Wl, L) (latent_meta)
+        self._defer_token = 0              # bumped by every training forward: whose stash reservation is it (render._RenderFunction)
+        self._bound_grads = None           # the flat gradient buffer of the last backward, alive while it is bound
+        self._side_streams, self._flush_stream, self._trunk_stream = None, None, None   # _own_streams: made on first use
+        self._lat_grad_event = None        # where the last latent gradient was complete (render._mark_latent_grad)
+        self._last_trunk_wait = None       # which ordering the last trunk backward took (for the tests)
+        self._trunk_generation = 0         # bumped by every training-trunk forward: whose activations does the library hold
         self._timing = False
         # What a no-grad call does when one of its f16 (F16X2 / F16) launches met a value outside the f16 range (include/pnyolo.h
         # pny_model_range_status): 'relaunch' (default) = wait for the call, and if the guard fired repeat it on the fp32
@@ -295,7 +309,7 @@ class PixelNeRFNet(nn.Module):
         for s in self._h_scenes:
             L.pny_scene_destroy(s)
         self._h_scenes = []
-        if getattr(self, "_h_group", None) is not None:
+        if self._h_group is not None:
             L.pny_scene_destroy(self._h_group)
         self._h_group, self._group, self._scenes_pending = None, None, None
         if self._h_model is not None:
@@ -315,7 +329,7 @@ class PixelNeRFNet(nn.Module):
         anywhere (a parameter, buffer or submodule registered or replaced: PyTorch's global registration hooks bump
         _STRUCT_EPOCH) or when the fine MLP is attached / detached."""
         sig = (_STRUCT_EPOCH[0], id(self.mlp_fine))
-        if sig != getattr(self, "_tracked_sig", None):
+        if sig != self._tracked_sig:
             self._tracked = list(self.state_dict(keep_vars=True).items())
             self._tracked_sig = sig
         return tuple((k, v.data_ptr(), v._version) for k, v in self._tracked)
@@ -344,16 +358,8 @@ class PixelNeRFNet(nn.Module):
             raise RuntimeError("a fine MLP was attached after the native model was created without one")
         if key != self._synced_key:
             h = self._h_model
-            old = self._synced_key
-            # Only MLP tensors changed IN PLACE (same storage, new version: an optimizer step) -> device-side refresh:
-            # one kernel launch re-creates the packed operands from the live parameters (pny_model_refresh).
-            # Encoder tensors stepped in place (encoder training: the training trunk reads the live parameters itself) only mark
-            # the INFERENCE trunk's folded copy stale; it is re-uploaded when that trunk is next needed (encode() outside training).
-            in_place = (old is not None and self._dev_bound and len(old) == len(key) and
-                        all(a[:2] == b[:2] and (a[2] == b[2] or a[0].startswith(("mlp_", "encoder."))) for a, b in zip(old, key)))
-            if in_place:
-                if any(a[2] != b[2] and a[0].startswith("encoder.") for a, b in zip(old, key)):
-                    self._enc_stale = True
+            if self._follows_in_place(self._synced_key, key):
+                self._mark_trunk_stale(self._synced_key, key)
                 check(L.pny_model_refresh(h, stream_of(dev)))
             else:
                 for name, t in self.state_dict().items():
@@ -383,6 +389,21 @@ class PixelNeRFNet(nn.Module):
             self._synced_key = key
         # `net.mlp_fine = None` (reference eval.py:140): fine pass falls back to the coarse MLP
         check(L.pny_model_use_fine(self._h_model, int(self.mlp_fine is not None)))
+
+    def _follows_in_place(self, old, new):
+        """Can the native copy follow the change of the weights key from `old` to `new` on the device, without a re-upload?
+        Yes when it reads the MLP parameters in place and only MLP or encoder tensors changed IN PLACE (same storage, new
+        version: an optimizer step).  _sync() then refreshes the packed operands with one launch; optim.Adam's step does it
+        in its own launch.  Anything else (a tensor replaced, a buffer outside them written) is a re-upload."""
+        return (old is not None and self._dev_bound and len(old) == len(new) and
+                all(a[:2] == b[:2] and (a[2] == b[2] or a[0].startswith(("mlp_", "encoder."))) for a, b in zip(old, new)))
+
+    def _mark_trunk_stale(self, old, new):
+        """Encoder tensors stepped in place between the keys `old` and `new` (encoder training: the training trunk reads the
+        live parameters itself) only mark the INFERENCE trunk's folded copy stale; it is re-uploaded when that trunk is next
+        needed (encode() outside training)."""
+        if any(a[2] != b[2] and a[0].startswith("encoder.") for a, b in zip(old, new)):
+            self._enc_stale = True
 
     def _new_scene(self):
         L = _lib.load()
@@ -431,25 +452,45 @@ class PixelNeRFNet(nn.Module):
             return t[sb:sb + 1]
         raise ValueError("focal / c batch must be 1, SB or SB*NS")
 
+    def _fill_scene(self, s, cams, first, count, n_objs=1, levels=None, latent=None, images=None):
+        """Give scene handle `s` the views [first, first + count) of an encode(): their cameras (`cams`: the host-side poses
+        (SB * NS, 4, 4), focal and c rows, W, H, SB, NS) and their latent from ONE source, on the current stream -- the
+        feature maps (`levels` = (device maps, their shapes): pny_scene_set_latent_levels), a latent tensor
+        (SB * NS, L, Hl, Wl) on the device (the caller's, or the rows copied out of the grouped handle), or the images (the
+        library's trunk).  No source: the scene is encoded already (pny_scenes_encode).  One object's scene takes that object's
+        focal / c rows as they are (the library broadcasts a single row); n_objs > 1 makes `s` the grouped scene of that
+        many objects (pny_scene_set_groups), with one row per view."""
+        L = _lib.load()
+        st = stream_of(self._device())
+        SB, NS = cams["SB"], cams["NS"]
+
+        def rows(t):
+            if n_objs == 1:
+                return self._cam_rows(t, first // NS, SB, NS).contiguous()
+            return torch.cat([self._cam_rows(t, sb, SB, NS).expand(NS, 2) for sb in range(first // NS, (first + count) // NS)],
+                             dim=0).contiguous()
+        f, c, p = rows(cams["focal"]), rows(cams["c"]), cams["poses"][first:first + count].contiguous()
+        check(L.pny_scene_set_cameras(s, ptr(p), count, ptr(f), f.shape[0], ptr(c), c.shape[0], cams["W"], cams["H"]))
+        if n_objs > 1:
+            check(L.pny_scene_set_groups(s, n_objs))
+        if levels is not None:
+            maps, shapes = levels
+            ptrs = (C.c_void_p * len(maps))(*[m[first:first + count].data_ptr() for m in maps])
+            ch, hs, ws = _levels_arrays(shapes)
+            check(L.pny_scene_set_latent_levels(s, ptrs, ch, hs, ws, len(maps), count, st))
+        elif latent is not None:
+            lat = latent[first:first + count]
+            check(L.pny_scene_set_latent(s, ptr(lat), count, lat.shape[1], lat.shape[2], lat.shape[3], st))
+        elif images is not None:
+            check(L.pny_scene_encode(s, ptr(images[first:first + count]), count, cams["H"], cams["W"], st))
+
     def _materialise_scenes(self):
         """Per-object scene handles from the grouped one (cameras from the encode() arguments, latent copied out of it): only
         when something other than the training render asks for them after a grouped encode()."""
-        pend, self._scenes_pending = self._scenes_pending, None
-        L = _lib.load()
-        dev = self._device()
-        SB, NS = self._group["SB"], self._group["NS"]
-        dims = [C.c_int() for _ in range(4)]
-        check(L.pny_scene_latent_shape(self._h_group, *[C.byref(d) for d in dims]))
-        lat = torch.empty([d.value for d in dims], device=dev, dtype=torch.float32)
-        check(L.pny_scene_get_latent(self._h_group, ptr(lat), stream_of(dev)))
-        for sb in range(SB):
-            s = self._scene(sb)
-            f_s = self._cam_rows(pend["focal"], sb, SB, NS).contiguous()
-            c_s = self._cam_rows(pend["c"], sb, SB, NS).contiguous()
-            p_s = pend["poses"][sb * NS:(sb + 1) * NS].contiguous()
-            check(L.pny_scene_set_cameras(s, ptr(p_s), NS, ptr(f_s), f_s.shape[0], ptr(c_s), c_s.shape[0], pend["W"], pend["H"]))
-            part = lat[sb * NS:(sb + 1) * NS]
-            check(L.pny_scene_set_latent(s, ptr(part), NS, part.shape[1], part.shape[2], part.shape[3], stream_of(dev)))
+        cams, self._scenes_pending = self._scenes_pending, None
+        lat = self._read_latent(self._h_group)
+        for sb in range(cams["SB"]):
+            self._fill_scene(self._scene(sb), cams, sb * cams["NS"], cams["NS"], latent=lat)
 
     def enable_kernel_timing(self, on=True):
         """HIP-event timing of the MLP launches (bench.py's roofline leg)."""
@@ -511,9 +552,7 @@ class PixelNeRFNet(nn.Module):
     def last_latent_grad_deterministic(self, scene=0):
         """True when the last backward of scene `scene` (or of the grouped scene, when the last call was grouped) that
         computed a latent gradient took the deterministic path (include/pnyolo.h pny_scene_last_latent_grad_mode)."""
-        v = C.c_int(0)
-        check(_lib.load().pny_scene_last_latent_grad_mode(self._last_handle(scene), C.byref(v)))
-        return bool(v.value)
+        return bool(_lib._get_int(_lib.load().pny_scene_last_latent_grad_mode, self._last_handle(scene)))
 
     def range_status(self, clear=False):
         """Bits (include/pnyolo.h PNY_RANGE_*) the F16X2 kernels of this model have reported so far; does not synchronise."""
@@ -575,14 +614,10 @@ class PixelNeRFNet(nn.Module):
     def last_backward_precision(self, scene=0):
         """The arithmetic of the dX chain of the last backward of scene `scene` (or of the grouped scene, when the last
         call was grouped): 'f32' | 'f16x2' | 'f16' (include/pnyolo.h pny_scene_last_backward_precision)."""
-        v = C.c_int(0)
-        check(_lib.load().pny_scene_last_backward_precision(self._last_handle(scene), C.byref(v)))
-        return _lib.LAST_PRECISION[int(v.value)]
+        return _lib.LAST_PRECISION[_lib._get_int(_lib.load().pny_scene_last_backward_precision, self._last_handle(scene))]
 
     def _last_precision_code(self, scene):
-        v = C.c_int(0)
-        check(_lib.load().pny_scene_last_precision(self._last_handle(scene), C.byref(v)))
-        return int(v.value)
+        return _lib._get_int(_lib.load().pny_scene_last_precision, self._last_handle(scene))
 
     def project_latent(self):
         """Compute the projected maps of the encoded scenes now (otherwise done lazily by the first
@@ -648,64 +683,81 @@ class PixelNeRFNet(nn.Module):
         """The latent tensor of the last encode(latent=...) if it requires grad and autograd is recording in train() mode
         (the render / query backward then returns d loss / d latent for it), else None."""
         if torch.is_grad_enabled() and self.training:
-            return getattr(self, "_latent_src", None)
+            return self._latent_src
         return None
 
     def latent_meta(self, lat):
         """What a render / query backward needs of the differentiable latent `lat`: ((SB * NS, L, Hl, Wl), device, dtype,
         channel-last).  A tensor latent is NCHW and takes its gradient in that layout; the stand-in of a list of feature maps
         (_LevelsFunction) is shaped like the library's own (SB * NS, Hl, Wl, L) buffer and takes that buffer as it is."""
-        if getattr(self, "_latent_channel_last", False):
+        if self._latent_channel_last:
             n, hl, wl, l_ch = lat.shape
             return (n, l_ch, hl, wl), lat.device, lat.dtype, True
         return tuple(lat.shape), lat.device, lat.dtype, False
 
-    def begin_latent_grad(self, meta, handles):
-        """Zeroed (SB * NS, Hl, Wl, L) accumulator bound in equal slices to the scene handles (pny_scene_bind_latent_grad):
-        the per-object scenes take their own views each, the grouped scene takes it whole."""
-        n_lat, l_ch, hl, wl = meta[0]
+    @contextlib.contextmanager
+    def latent_grad(self, meta, handles):
+        """``with net.latent_grad(meta, handles) as lg:`` around the library's backward calls on the scene handles, for the
+        latent that `meta` describes (latent_meta).  Entry: a zeroed (SB * NS, Hl, Wl, L) accumulator bound in equal slices to
+        the handles (pny_scene_bind_latent_grad): the per-object scenes take their own views each, the grouped scene takes it
+        whole.  Its zero fill runs on the current stream, so enter BEFORE side streams fork from that stream.  ``lg.result()``
+        unbinds and is what the backward returns for the latent: (gradient,) in the latent's own layout (SB * NS, L, Hl, Wl),
+        device and dtype -- for a list of feature maps the channel-last buffer itself, which pny_latent_levels_backward reads
+        (_LevelsFunction) -- or () for meta = None (no differentiable latent: nothing is bound).  A block that raises leaves
+        nothing bound either: the buffer dies with the exception, and a scene left bound to it would accumulate into freed
+        memory (or fail again) in its next backward."""
+        if meta is None:
+            yield types.SimpleNamespace(result=tuple)
+            return
+        bind = _lib.load().pny_scene_bind_latent_grad
+        (n_lat, l_ch, hl, wl), lat_dev, lat_dtype, channel_last = meta
         self._latent_grad_deterministic()
         buf = torch.zeros(n_lat, hl, wl, l_ch, device=self._device(), dtype=torch.float32)
         nsv = n_lat // len(handles)
         for i, h in enumerate(handles):
-            check(_lib.load().pny_scene_bind_latent_grad(h, ptr(buf[i * nsv:(i + 1) * nsv])))
-        return buf
+            check(bind(h, ptr(buf[i * nsv:(i + 1) * nsv])))
 
-    def end_latent_grad(self, buf, meta, handles):
-        """Unbind and return the gradient in the latent's own layout (SB * NS, L, Hl, Wl), device and dtype; for a list of
-        feature maps the channel-last buffer itself, which pny_latent_levels_backward reads (_LevelsFunction)."""
-        for h in handles:
-            check(_lib.load().pny_scene_bind_latent_grad(h, None))
-        if len(meta) > 3 and meta[3]:
-            return buf
-        return buf.permute(0, 3, 1, 2).contiguous().to(meta[1], meta[2])   # packed NCHW, like the latent it belongs to
+        def result():
+            for h in handles:
+                check(bind(h, None))
+            return (buf if channel_last else buf.permute(0, 3, 1, 2).contiguous().to(lat_dev, lat_dtype),)   # packed NCHW
+        try:
+            yield types.SimpleNamespace(result=result)
+        except Exception:
+            for h in handles:
+                bind(h, None)
+            raise
 
-    def abort_latent_grad(self, handles):
-        """Unbind the accumulator of begin_latent_grad after a backward call failed: the buffer dies with the exception, and a
-        scene left bound to it would accumulate into freed memory (or fail again) in its next backward."""
-        for h in handles:
-            _lib.load().pny_scene_bind_latent_grad(h, None)
+    def _bind_flat_grads(self, named_shapes, dev):
+        """Zeroed gradient buffers on `dev` for (state_dict name, shape) pairs, bound to the native model by name
+        (pny_model_bind_grad) -> (flat, buffers in the same order).  The buffers are views of ONE flat allocation (one fill, on
+        the current stream, instead of one per tensor) and start at multiples of 64 floats (the reduction writes float4 rows)."""
+        sizes = [int(np.prod(shape)) for _, shape in named_shapes]
+        offs = np.concatenate([[0], np.cumsum([(n + 63) // 64 * 64 for n in sizes])]).astype(np.int64)
+        flat = torch.zeros(max(int(offs[-1]), 1), device=dev, dtype=torch.float32)
+        grads = [flat[int(o):int(o) + n].view(shape) for o, n, (_, shape) in zip(offs, sizes, named_shapes)]
+        for (name, _), g in zip(named_shapes, grads):
+            check(_lib.load().pny_model_bind_grad(self._h_model, name.encode(), ptr(g)))
+        return flat, grads
 
     def bind_mlp_grads(self):
-        """Fresh zeroed gradient buffers for trainable_mlp_parameters(), bound to the native model by name
-        (pny_model_bind_grad); returns them in the same order.  The buffers are views of ONE flat allocation (one fill
-        instead of one per tensor); only the flat tensor is kept alive here, so that autograd's AccumulateGrad can adopt the
-        returned views as `.grad` instead of cloning each of them."""
+        """Fresh zeroed gradient buffers for trainable_mlp_parameters(), bound to the native model by name; returns them in
+        the same order.  Only the flat tensor they are views of is kept alive here, so that autograd's AccumulateGrad can
+        adopt the returned views as `.grad` instead of cloning each of them."""
         self._sync()
-        L = _lib.load()
-        named = list(self.trainable_mlp_parameters())
-        offs, total = [], 0
-        for _, p in named:
-            offs.append(total)
-            total += (p.numel() + 63) // 64 * 64          # 256-byte aligned starts (the reduction writes float4 rows)
-        flat = torch.zeros(max(total, 1), device=self._device(), dtype=torch.float32)
-        grads = []
-        for (name, p), o in zip(named, offs):
-            g = flat[o:o + p.numel()].view(p.shape)
-            check(L.pny_model_bind_grad(self._h_model, name.encode(), ptr(g)))
-            grads.append(g)
-        self._bound_grads = flat   # keeps the memory alive while it is bound
+        named_shapes = [(k, tuple(p.shape)) for k, p in self.trainable_mlp_parameters()]
+        self._bound_grads, grads = self._bind_flat_grads(named_shapes, self._device())
         return grads
+
+    def _own_streams(self, attr, dev, n=None):
+        """self.<attr>, the side streams this model keeps for one purpose, on `dev`: a list of at least n streams (n = None:
+        a single stream, not a list), made on first use and remade when the device changed or more are needed."""
+        have = getattr(self, attr)
+        pool = [have] if n is None and have is not None else (have or [])
+        if len(pool) < (n or 1) or pool[0].device != dev:
+            pool = [torch.cuda.Stream(dev) for _ in range(n or 1)]
+            setattr(self, attr, pool[0] if n is None else pool)
+        return pool[0] if n is None else pool
 
     def fork_streams(self, n):
         """n stream contexts for n independent scenes: the current stream for the first scene (None) and n - 1 side streams
@@ -713,13 +765,10 @@ class PixelNeRFNet(nn.Module):
         stream takes part because the runtime maps streams onto FOUR hardware queues, one of which is the current stream's:
         with four side streams two scenes of the reference's default super-batch (SB = 4) shared a queue and ran one after
         the other while two queues idled (kernel trace of a training step)."""
-        import os
         if n <= 1 or os.environ.get("PNYOLO_SCENE_STREAMS", "1") == "0":
             return [None] * n
         dev = self._device()
-        pool = getattr(self, "_side_streams", None)
-        if pool is None or len(pool) < n - 1 or pool[0].device != dev:
-            pool = self._side_streams = [torch.cuda.Stream(dev) for _ in range(n - 1)]
+        pool = self._own_streams("_side_streams", dev, n - 1)
         main = torch.cuda.current_stream(dev)
         for st in pool[:n - 1]:
             st.wait_stream(main)
@@ -740,9 +789,7 @@ class PixelNeRFNet(nn.Module):
     def last_flush_precision(self):
         """The arithmetic of the last deferred weight-gradient flush's GEMM: 'f32' | 'f16x2' | 'f16'
         (include/pnyolo.h pny_model_last_flush_precision)."""
-        v = C.c_int(0)
-        check(_lib.load().pny_model_last_flush_precision(self._h_model, C.byref(v)))
-        return _lib.LAST_PRECISION[int(v.value)]
+        return _lib.LAST_PRECISION[_lib._get_int(_lib.load().pny_model_last_flush_precision, self._h_model)]
 
     def invalidate_weights(self):
         """Force a re-upload of the parameters at the next call.  Needed after writes that PyTorch does not version:
@@ -787,27 +834,12 @@ class PixelNeRFNet(nn.Module):
             # only the ATen training graph (forward_torch: PNYOLO_TRUNK=torch, or batch norm modules in mixed modes) takes any size
             raise ValueError("encode(): the library's ResNet-34 trunk needs images of at least 32 x 32 pixels, got %d x %d "
                              "(H x W); pass the latent via encode(..., latent=...) instead" % (H, W))
-        # focal / principal point formats: reference models.py:125-148
-        focal = torch.as_tensor(focal, dtype=torch.float32).cpu()
-        if focal.dim() == 0:
-            focal = focal[None, None].repeat(1, 2)
-        elif focal.dim() == 1:
-            focal = focal.unsqueeze(-1).repeat(1, 2)
-        focal = focal.contiguous()
-        if c is None:
-            c = torch.tensor([[W * 0.5, H * 0.5]], dtype=torch.float32)
-        else:
-            c = torch.as_tensor(c, dtype=torch.float32).cpu()
-            if c.dim() == 0:
-                c = c[None, None].repeat(1, 2)
-            elif c.dim() == 1:
-                c = c.unsqueeze(-1).repeat(1, 2)
-        c = c.contiguous()
+        focal, c = _camera_pairs(focal), _camera_pairs(c, default=(W * 0.5, H * 0.5))
         poses_h = poses.detach().to("cpu", torch.float32).contiguous()
         self._encode_epoch += 1
         self._last_encode = dict(poses=poses_h.reshape(SB, NS, 4, 4) if images is not None else poses_h, focal=focal, c=c, H=H, W=W,
                                  NS=NS, SB=SB, five_d=self.num_views_per_obj == NS)
-        st = stream_of(dev)
+        cams = dict(poses=poses_h, focal=focal, c=c, W=W, H=H, SB=SB, NS=NS)   # what _fill_scene reads
         if latent is None and self.encoder.use_custom_resnet:
             raise RuntimeError("backbone=custom (YOLOv7) has no kernels in this build (its source and weights are "
                                "outside the reference tree): pass the backbone output via encode(..., latent=...)")
@@ -830,15 +862,17 @@ class PixelNeRFNet(nn.Module):
             maps = [m.detach().to(dev, torch.float32).contiguous() for m in latent]
             token = _LevelsFunction.apply(self, levels, *latent)
             self._latent_src = token if token.requires_grad else None
-            latent = None
+            source = dict(levels=(maps, levels))
         elif latent is not None:
             latent = latent.detach().to(dev, torch.float32).contiguous()
             assert latent.dim() == 4 and latent.shape[0] == SB * NS, "latent must be (SB*NS, L, Hl, Wl)"
-        elif levels is None:
-            if getattr(self, "_enc_stale", False):   # the trunk's weights were trained since their last upload
+            source = dict(latent=latent)
+        else:
+            if self._enc_stale:   # the trunk's weights were trained since their last upload
                 self._synced_key = None
                 self._sync()
             images = images.detach().to(dev, torch.float32).contiguous()
+            source = dict(images=images)
         self._group, self._scenes_pending = None, None
         if (SB > 1 and SB * NS <= 16 and os.environ.get("PNYOLO_GROUP", "1") != "0" and torch.is_grad_enabled() and self.training
                 and (self.trainable_mlp_parameters() or self._latent_src is not None)):
@@ -847,45 +881,22 @@ class PixelNeRFNet(nn.Module):
             # super-batch the same way, nerf.py:283-288).  The per-object handles are filled only if something asks for them.
             if self._h_group is None:
                 self._h_group = self._new_scene()
-            g = self._h_group
-
-            def all_rows(t):
-                return torch.cat([self._cam_rows(t, sb, SB, NS).expand(NS, 2) for sb in range(SB)], dim=0).contiguous()
-            f_all, c_all = all_rows(focal), all_rows(c)
-            check(L.pny_scene_set_cameras(g, ptr(poses_h), SB * NS, ptr(f_all), SB * NS, ptr(c_all), SB * NS, W, H))
-            check(L.pny_scene_set_groups(g, SB))
-            if levels is not None:
-                set_latent_levels(g, maps, levels, 0, SB * NS, st)
-            elif latent is not None:
-                check(L.pny_scene_set_latent(g, ptr(latent), SB * NS, latent.shape[1], latent.shape[2], latent.shape[3], st))
-            else:
-                check(L.pny_scene_encode(g, ptr(images), SB * NS, H, W, st))
+            self._fill_scene(self._h_group, cams, 0, SB * NS, n_objs=SB, **source)
             self._group = dict(SB=SB, NS=NS)
-            self._scenes_pending = dict(poses=poses_h, focal=focal, c=c, W=W, H=H)
+            self._scenes_pending = cams
             return
         scenes = [self._scene(sb) for sb in range(SB)]
         # the library's trunk over a super-batch: ONE pass over all SB * NS images (as the reference's encode flattens them),
         # cameras per scene below
-        batch_encode = latent is None and levels is None and SB > 1
+        batch_encode = "images" in source and SB > 1
         if batch_encode:
             arr = (C.c_void_p * SB)(*[s_ for s_ in scenes])
             check(L.pny_scenes_encode(arr, SB, ptr(images), NS, H, W, stream_of(dev)))
+            source = {}
         streams = [None] * SB if batch_encode else self.fork_streams(SB)   # independent scenes: one stream each
         for sb in range(SB):
-          with torch.cuda.stream(streams[sb]):
-            s = scenes[sb]
-            st = stream_of(dev)
-            f_s, c_s = self._cam_rows(focal, sb, SB, NS).contiguous(), self._cam_rows(c, sb, SB, NS).contiguous()
-            p_s = poses_h[sb * NS:(sb + 1) * NS].contiguous()
-            check(L.pny_scene_set_cameras(s, ptr(p_s), NS, ptr(f_s), f_s.shape[0], ptr(c_s), c_s.shape[0], W, H))
-            if levels is not None:
-                set_latent_levels(s, maps, levels, sb * NS, NS, st)
-            elif latent is not None:
-                lat = latent[sb * NS:(sb + 1) * NS]
-                check(L.pny_scene_set_latent(s, ptr(lat), NS, lat.shape[1], lat.shape[2], lat.shape[3], st))
-            elif not batch_encode:
-                img = images[sb * NS:(sb + 1) * NS]
-                check(L.pny_scene_encode(s, ptr(img), NS, H, W, st))
+            with torch.cuda.stream(streams[sb]):
+                self._fill_scene(scenes[sb], cams, sb * NS, NS, **source)
         self.join_streams(streams)
 
     # ---------------------------------------------------------------- encoder training on the library's trunk
@@ -901,7 +912,7 @@ class PixelNeRFNet(nn.Module):
         """The training-mode trunk runs on the library's kernels (csrc/encoder_train.hip) when batch norm works on batch
         statistics (every BatchNorm2d of the trunk in train() mode, momentum set, affine) and the parameters are readable in
         place; PNYOLO_TRUNK=torch forces the ATen graph (SpatialEncoder.forward_torch)."""
-        if os.environ.get("PNYOLO_TRUNK", "native") == "torch" or not getattr(self, "_trunk_bound", False):
+        if os.environ.get("PNYOLO_TRUNK", "native") == "torch" or not self._trunk_bound:
             return False
         bns = self._trunk_bn_modules()
         return (all(b.momentum is not None and b.affine and b.track_running_stats for b in bns)
@@ -914,8 +925,11 @@ class PixelNeRFNet(nn.Module):
 
     def latent(self, sb=0):
         """(NS, L, Hl, Wl) latent of scene `sb` as the reference keeps it in encoder.latent."""
+        return self._read_latent(self._scene(sb))
+
+    def _read_latent(self, s):
+        """The latent that scene handle `s` holds, (ns, L, Hl, Wl), copied out on the current stream."""
         L = _lib.load()
-        s = self._scene(sb)
         dims = [C.c_int() for _ in range(4)]
         check(L.pny_scene_latent_shape(s, *[C.byref(d) for d in dims]))
         out = torch.empty([d.value for d in dims], device=self._device(), dtype=torch.float32)
@@ -1024,11 +1038,18 @@ def _levels_arrays(levels):
     return [(C.c_int * n)(*[lv[k] for lv in levels]) for k in range(3)]
 
 
-def set_latent_levels(scene, maps, levels, first, count, stream):
-    """pny_scene_set_latent_levels on views [first, first + count) of fp32 packed NCHW device maps."""
-    ptrs = (C.c_void_p * len(maps))(*[m[first:first + count].data_ptr() for m in maps])
-    ch, hs, ws = _levels_arrays(levels)
-    check(_lib.load().pny_scene_set_latent_levels(scene, ptrs, ch, hs, ws, len(maps), count, stream))
+def _camera_pairs(v, default=None):
+    """focal / c in the formats of the reference (models.py:125-148) -> (N, 2) fp32 rows on the host: a scalar is both
+    components of one row, (N,) is one value per row for both components, (N, 2) is taken as it is; None is the one row
+    `default` (c: the image centre)."""
+    if v is None:
+        return torch.tensor([default], dtype=torch.float32)
+    v = torch.as_tensor(v, dtype=torch.float32).cpu()
+    if v.dim() == 0:
+        v = v[None, None].repeat(1, 2)
+    elif v.dim() == 1:
+        v = v.unsqueeze(-1).repeat(1, 2)
+    return v.contiguous()
 
 
 class _LevelsFunction(torch.autograd.Function):
@@ -1036,7 +1057,7 @@ class _LevelsFunction(torch.autograd.Function):
     render / query calls: it has the shape of the library's channel-last latent, (SB * NS, Hl, Wl, L), and no storage of that
     size (one element, expanded) -- the latent itself lives in the scene handles, where encode() assembles it
     (pny_scene_set_latent_levels).  Backward: the channel-last d loss / d latent buffer of the render backward
-    (begin_latent_grad / end_latent_grad) goes to pny_latent_levels_backward, one launch, which writes the gradient of every map
+    (PixelNeRFNet.latent_grad) goes to pny_latent_levels_backward, one launch, which writes the gradient of every map
     that requires grad in the map's own NCHW shape.  No (n, L, Hl, Wl) tensor and no transpose on the way there or back."""
 
     @staticmethod
@@ -1080,30 +1101,27 @@ class _TrunkFunction(torch.autograd.Function):
                                         stream_of(dev)))
         # The library keeps the saved activations of ONE training forward per model: a later forward replaces them, and the
         # backward of this graph must then refuse instead of differentiating against the other forward's activations
-        net._trunk_generation = ctx.generation = getattr(net, "_trunk_generation", 0) + 1
+        net._trunk_generation = ctx.generation = net._trunk_generation + 1
         if not bn_eval:
             with torch.no_grad():
                 for b in bns:
                     b.num_batches_tracked += 1
             net._enc_stale = True     # the inference trunk's folded batch norm is stale now (running statistics moved)
         ctx.net = net
-        ctx.names = [k for k, _ in net._trunk_trainable()]
-        ctx.shapes = [tuple(p.shape) for p in params]
+        ctx.named_shapes = [(k, tuple(p.shape)) for (k, _), p in zip(net._trunk_trainable(), params)]
         return lat
 
     @staticmethod
     def backward(ctx, d_lat):
         net = ctx.net
-        if getattr(net, "_trunk_generation", None) != ctx.generation:
+        if net._trunk_generation != ctx.generation:
             raise RuntimeError("the library's training trunk holds the activations of a later encode() than this graph's: a "
                                "training encode() was superseded before its backward (call backward() before the next "
                                "training encode(), or PNYOLO_TRUNK=torch for gradient accumulation over several encodes)")
         L = _lib.load()
         dev = net._device()
         h = net._h_model
-        sizes = [int(np.prod(s)) for s in ctx.shapes]
-        offs = np.concatenate([[0], np.cumsum([(s + 63) // 64 * 64 for s in sizes])]).astype(np.int64)
-        ev, net._lat_grad_event = getattr(net, "_lat_grad_event", None), None
+        ev, net._lat_grad_event = net._lat_grad_event, None
         ev = ev[0] if ev is not None and ev[1]() is d_lat and d_lat._version == ev[2] else None
         d_lat = d_lat.detach().to(dev, torch.float32).contiguous()
         # The trunk's backward needs d loss / d latent and nothing else of the renderer's backward: it runs on a stream of its
@@ -1113,11 +1131,7 @@ class _TrunkFunction(torch.autograd.Function):
         # (two renders, another loss term on the latent, bind_parallel's per-device shares) or the event is a leftover of
         # another latent's render, d_lat is another tensor, written on the caller's stream after the event -- wait for that.
         main = torch.cuda.current_stream(dev)
-        side = getattr(net, "_trunk_stream", None)
-        if os.environ.get("PNYOLO_TRUNK_STREAM", "1") == "0":
-            side = main
-        elif side is None or side.device != dev:
-            side = net._trunk_stream = torch.cuda.Stream(dev)
+        side = main if os.environ.get("PNYOLO_TRUNK_STREAM", "1") == "0" else net._own_streams("_trunk_stream", dev)
         # (which of the two orderings ran, for the tests: "event" overlaps the weight-gradient flush, "stream" waits for it)
         net._last_trunk_wait = "same stream" if side is main else ("event" if ev is not None else "stream")
         if side is not main:
@@ -1126,14 +1140,11 @@ class _TrunkFunction(torch.autograd.Function):
             else:
                 side.wait_stream(main)
         with torch.cuda.stream(side):
-            flat = torch.zeros(int(offs[-1]), device=dev, dtype=torch.float32)
-            grads = [flat[int(o):int(o) + s].view(shp) for o, s, shp in zip(offs[:-1], sizes, ctx.shapes)]
-            for k, g in zip(ctx.names, grads):
-                check(L.pny_model_bind_grad(h, k.encode(), C.c_void_p(g.data_ptr())))
+            flat, grads = net._bind_flat_grads(ctx.named_shapes, dev)
             try:
                 check(L.pny_trunk_train_backward(h, ptr(d_lat), stream_of(dev)))
             finally:
-                for k in ctx.names:
+                for k, _ in ctx.named_shapes:
                     check(L.pny_model_bind_grad(h, k.encode(), None))
         if side is not main:
             d_lat.record_stream(side)
@@ -1167,16 +1178,11 @@ class _QueryFunction(torch.autograd.Function):
         st = stream_of(dev)
         SB = ctx.xyz.shape[0]
         scenes = [net._scene(sb) for sb in range(SB)]
-        lat_grad = net.begin_latent_grad(ctx.lat_meta, scenes) if ctx.lat_meta is not None else None
-        try:
+        with net.latent_grad(ctx.lat_meta, scenes) as lg:
             for sb in range(SB):
                 check(L.pny_query_backward(scenes[sb], ptr(ctx.xyz[sb]), ptr(ctx.dirs[sb]), ctx.xyz.shape[1], int(use_coarse),
                                            ptr(g_out[sb]), _lib.ACC_ADD, st))
-        except Exception:
-            if lat_grad is not None:
-                net.abort_latent_grad(scenes)
-            raise
-        extra = () if lat_grad is None else (net.end_latent_grad(lat_grad, ctx.lat_meta, scenes),)
+            extra = lg.result()
         net._lat_grad_event = None      # (unmarked: a trunk backward behind this one waits for the whole stream)
         return (None, None, None, None, None) + tuple(grads) + extra
 

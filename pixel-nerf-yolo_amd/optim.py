@@ -153,16 +153,13 @@ class Adam(torch.optim.Optimizer):
                                 "%s)" % (what, t.dtype, "contiguous" if t.is_sparse or t.is_contiguous() else "strided"))
 
     def _model_in_step(self, net):
-        """The model's parameter key if its native copy can follow this step on the device (it exists, reads its parameters in
-        place, and differs from them by in-place updates at most: PixelNeRFNet._sync's own condition for a refresh), else None:
-        the step then only updates, and the model's next _sync() does what it always did."""
-        if net._h_model is None or not net._dev_bound or net._synced_key is None or net._h_device != str(net._device()):
+        """The model's parameter key if its native copy can follow this step on the device (it exists on the model's device and
+        differs from the parameters by in-place updates at most: PixelNeRFNet._follows_in_place, _sync's own condition for a
+        refresh), else None: the step then only updates, and the model's next _sync() does what it always did."""
+        if net._h_model is None or net._h_device != str(net._device()):
             return None
-        old, key = net._synced_key, net._weights_key()
-        if len(old) != len(key) or not all(a[:2] == b[:2] and (a[2] == b[2] or a[0].startswith(("mlp_", "encoder.")))
-                                           for a, b in zip(old, key)):
-            return None
-        return key
+        key = net._weights_key()
+        return key if net._follows_in_place(net._synced_key, key) else None
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -233,7 +230,6 @@ class Adam(torch.optim.Optimizer):
             if refresh_on is None and any(a[2] != b[2] and a[0].startswith("mlp_") for a, b in zip(old, key)):
                 return loss   # (MLP weights moved and no launch of this step ran on the model's device: _sync() refreshes)
             new = net._weights_key()
-            if any(a[2] != b[2] and a[0].startswith("encoder.") for a, b in zip(old, new)):
-                net._enc_stale = True     # as _sync(): the inference trunk's folded copy is re-uploaded when next needed
+            net._mark_trunk_stale(old, new)     # as _sync(): the inference trunk's folded copy is re-uploaded when next needed
             net._synced_key = new
         return loss

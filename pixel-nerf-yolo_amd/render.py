@@ -120,7 +120,7 @@ class _MultiDeviceRenderWrapper(torch.nn.Module):
                 images = torch.zeros(le["SB"], le["NS"], 3, le["H"], le["W"])
                 r.encode(images, le["poses"], le["focal"], c=le["c"], latent=lat)
             self._seen[i] = key
-        r._latent_channel_last = getattr(net, "_latent_channel_last", False)   # (the layout of the master's latent leaf: latent_meta)
+        r._latent_channel_last = net._latent_channel_last   # (the layout of the master's latent leaf: latent_meta)
         return r
 
     def forward(self, rays, want_weights=False):
@@ -320,8 +320,7 @@ class _RenderFunction(torch.autograd.Function):
         ct = tiles(B * kc) + (tiles(B * kt) if (has_fine and not fine_mlp) else 0)
         ft = tiles(B * kt) if (has_fine and fine_mlp) else 0
         ctx.deferred = L.pny_model_defer_weight_grads(model._h_model, 1, model.num_views_per_obj, SB * ct, SB * ft) == 0
-        model._defer_token = getattr(model, "_defer_token", 0) + 1
-        ctx.token = model._defer_token
+        model._defer_token = ctx.token = model._defer_token + 1
         res, saved = renderer._render(model, rays, want_weights=True, save=True, stash=ctx.deferred)
         saved["depth_coarse"] = res["coarse"]["depth"]
         ctx.renderer, ctx.model, ctx.saved, ctx.has_fine = renderer, model, saved, has_fine
@@ -350,21 +349,16 @@ class _RenderFunction(torch.autograd.Function):
         ups = [prep(x) for x in (g_rgb_c, g_depth_c, g_w_c, g_rgb_f, g_depth_f, g_w_f)]
         # The reservation made by the forward is still ours unless another training forward ran in between: then this
         # call computes its weight gradients immediately (ACC_IMMEDIATE), scene after scene, with recompute.
-        deferred = ctx.deferred and getattr(model, "_defer_token", None) == ctx.token
+        deferred = ctx.deferred and model._defer_token == ctx.token
         acc = _lib.ACC_ADD if deferred else _lib.ACC_ADD | _lib.ACC_IMMEDIATE
         group = bool(sv.get("group"))
         if group and not deferred:
             raise RuntimeError("the grouped training forward lost its stash reservation (another training forward ran before "
                                "this backward): call backward() before the next forward, or set PNYOLO_GROUP=0")
         handles, G, R = _launches(model, group, SB, B)    # the forward's launches (NeRFRenderer._render)
-        # d loss / d latent, accumulated by every scene's call into its own slice (channel-last).  Its zero fill runs on the
-        # current stream, so it is enqueued BEFORE the side streams fork from that stream: scenes 1.. add into the buffer
-        # with atomics from their own streams, and nothing else would order those behind the fill.
-        lat_grad = model.begin_latent_grad(ctx.lat_meta, handles) if ctx.lat_meta is not None else None
-        streams = model.fork_streams(G) if deferred else [None] * G
         rows = lambda t: None if t is None else t.view(G, R, *t.shape[2:])
         names = [k for k in _SAVED_BUFFERS if k in sv]
-        if not getattr(ren, "_detach_fine_depth", False):   # test aid: treat the depth samples as constants
+        if not ren._detach_fine_depth:
             names.append("depth_coarse")
         rays, sv_rows, up_rows = rows(sv["rays"]), {k: rows(sv[k]) for k in names}, [rows(p) for p in ups]
 
@@ -372,43 +366,41 @@ class _RenderFunction(torch.autograd.Function):
             return (_lib.RenderSaved(**{k: t[g].data_ptr() for k, t in sv_rows.items()}),
                     _lib.RenderGrads(*[None if t is None else t[g].data_ptr() for t in up_rows]))
         calls = [structs(g) for g in range(G)]
+        # d loss / d latent, accumulated by every scene's call into its own slice (channel-last).  Its zero fill runs on the
+        # current stream, so it is enqueued BEFORE the side streams fork from that stream: scenes 1.. add into the buffer
+        # with atomics from their own streams, and nothing else would order those behind the fill.
+        with model.latent_grad(ctx.lat_meta, handles) as lg:
+            streams = model.fork_streams(G) if deferred else [None] * G
 
-        def run(g, bits):
-            with torch.cuda.stream(streams[g]):
-                check(L.pny_render_backward(handles[g], ptr(rays[g]), R, C.byref(sv["opts"][g]), C.byref(calls[g][0]),
-                                            C.byref(calls[g][1]), acc | bits, stream_of(dev)))
-        # Optional (PNYOLO_SPLIT_FLUSH=1, per-object scenes): every scene's FINE pass first, then mlp_fine's weight-gradient flush on a
-        # stream of its own BESIDE the coarse passes instead of behind them.  Measured: no gain -- 12.5-13.5 ms per step against
-        # 12.3-12.5: the chain kernels hold 152 KiB of a CU's LDS and the weight-gradient GEMM 128 KiB, so the two never share a CU and
-        # the "quarter-busy" coarse chains cannot be filled in.  Off by default; kept because it is tested (bits 4 / 8 of accumulate).
-        split = (deferred and not group and ctx.has_fine and model.mlp_fine is not None
-                 and os.environ.get("PNYOLO_SPLIT_FLUSH", "0") == "1")
-        fstream = None
-        if split:
-            for g in range(G):
-                run(g, _lib.ACC_FINE_ONLY)      # (the fine pass only; the coarse passes follow -- include/pnyolo.h pny_render_backward)
-            main = torch.cuda.current_stream(dev)
-            fstream = getattr(model, "_flush_stream", None)
-            if fstream is None or fstream.device != dev:
-                fstream = model._flush_stream = torch.cuda.Stream(dev)
-            fstream.wait_stream(main)
-            for st_ in streams:
-                if st_ is not None:
-                    fstream.wait_stream(st_)
-            with torch.cuda.stream(fstream):
-                check(L.pny_model_flush_weight_grads(model._h_model, _lib.ACC_ADD | _lib.FLUSH_FINE_ONLY, stream_of(dev)))
-        try:
+            def run(g, bits):
+                with torch.cuda.stream(streams[g]):
+                    check(L.pny_render_backward(handles[g], ptr(rays[g]), R, C.byref(sv["opts"][g]), C.byref(calls[g][0]),
+                                                C.byref(calls[g][1]), acc | bits, stream_of(dev)))
+            # Optional (PNYOLO_SPLIT_FLUSH=1, per-object scenes): every scene's FINE pass first, then mlp_fine's weight-gradient flush
+            # on a stream of its own BESIDE the coarse passes instead of behind them.  Measured: no gain -- 12.5-13.5 ms per step
+            # against 12.3-12.5: the chain kernels hold 152 KiB of a CU's LDS and the weight-gradient GEMM 128 KiB, so the two never
+            # share a CU and the "quarter-busy" coarse chains cannot be filled in.  Off by default; kept because it is tested (bits
+            # 4 / 8 of accumulate).
+            split = (deferred and not group and ctx.has_fine and model.mlp_fine is not None
+                     and os.environ.get("PNYOLO_SPLIT_FLUSH", "0") == "1")
+            fstream = None
+            if split:
+                for g in range(G):
+                    run(g, _lib.ACC_FINE_ONLY)      # (the fine pass only; the coarse passes follow -- include/pnyolo.h pny_render_backward)
+                fstream = model._own_streams("_flush_stream", dev)
+                fstream.wait_stream(torch.cuda.current_stream(dev))
+                for st_ in streams:
+                    if st_ is not None:
+                        fstream.wait_stream(st_)
+                with torch.cuda.stream(fstream):
+                    check(L.pny_model_flush_weight_grads(model._h_model, _lib.ACC_ADD | _lib.FLUSH_FINE_ONLY, stream_of(dev)))
             for g in range(G):
                 run(g, _lib.ACC_COARSE_ONLY if split else 0)
-        except Exception:
-            if lat_grad is not None:
-                model.abort_latent_grad(handles)
-            raise
-        if deferred:
-            model.join_streams(streams)
-        # d loss / d latent is complete here, BEFORE the weight-gradient flush is enqueued: the encoder's backward (the trunk's
-        # kernels, model._TrunkFunction) starts behind this point on its own stream and runs beside the flush
-        extra = () if lat_grad is None else (model.end_latent_grad(lat_grad, ctx.lat_meta, handles),)
+            if deferred:
+                model.join_streams(streams)
+            # d loss / d latent is complete here, BEFORE the weight-gradient flush is enqueued: the encoder's backward (the
+            # trunk's kernels, model._TrunkFunction) starts behind this point on its own stream and runs beside the flush
+            extra = lg.result()
         _mark_latent_grad(model, extra, dev)
         if deferred:
             check(L.pny_model_flush_weight_grads(model._h_model, _lib.ACC_ADD | (_lib.FLUSH_COARSE_ONLY if split else 0), stream_of(dev)))
@@ -454,6 +446,8 @@ class NeRFRenderer(torch.nn.Module):
         self.draws = None          # explicit random draws for the next call (parity mode)
         self.base_seed = 1234
         self._calls = 0
+        self._debug_out = None             # test aid: {RenderOut field: tensor} that the next calls also write (one launch per scene)
+        self._detach_fine_depth = False    # test aid: the backward treats the depth samples as constants
 
     def forward(self, model, rays, want_weights=False):
         """
@@ -512,7 +506,7 @@ class NeRFRenderer(torch.nn.Module):
             if want_weights:
                 res["fine"]["weights"] = torch.empty(SB, B, kc + kf, **f32)
         saved = None
-        extra = dict(getattr(self, "_debug_out", None) or {})
+        extra = dict(self._debug_out or {})
         if save:
             saved = {"rays": rays, "z_coarse": torch.empty(SB, B, kc, **f32), "sample_coarse": torch.empty(SB, B, kc, 4, **f32),
                      "opts": []}
@@ -631,6 +625,7 @@ class YoloRenderer(torch.nn.Module):
         self.draws = None
         self.base_seed = 4321
         self._calls = 0
+        self._debug_raw = None     # test aid: (n, n_coarse, d_out) tensor that the next calls write the per-sample vectors to
 
     def bind_net(self, net):
         self.net = net
@@ -674,7 +669,7 @@ class YoloRenderer(torch.nn.Module):
         u = None
         if draws is not None:
             u = torch.as_tensor(draws["u_coarse"], dtype=torch.float32).reshape(n, self.n_coarse).to(dev).contiguous()
-        raw = getattr(self, "_debug_raw", None)
+        raw = self._debug_raw
         if raw is None and keep_raw:
             raw = torch.empty(n, int(self.n_coarse), net.d_out, device=dev, dtype=torch.float32)
         seed = (self.base_seed + 7919 * self._calls) & 0xFFFFFFFFFFFFFFFF
@@ -711,15 +706,10 @@ class _YoloRenderFunction(torch.autograd.Function):
         grads = net.bind_mlp_grads()
         g_out = g_out.detach().to(dev, torch.float32).contiguous()
         scene = net._scene(0)
-        lat_grad = net.begin_latent_grad(ctx.lat_meta, [scene]) if ctx.lat_meta is not None else None
-        try:
+        with net.latent_grad(ctx.lat_meta, [scene]) as lg:
             check(L.pny_yolo_render_backward(scene, ptr(sv["rays"]), sv["rays"].shape[0], sv["n_coarse"], ptr(sv["u"]),
                                              sv["seed"], ptr(sv["raw"]), ptr(g_out), _lib.ACC_ADD, stream_of(dev)))
-        except Exception:
-            if lat_grad is not None:
-                net.abort_latent_grad([scene])
-            raise
-        extra = () if lat_grad is None else (net.end_latent_grad(lat_grad, ctx.lat_meta, [scene]),)
+            extra = lg.result()
         net._lat_grad_event = None      # (unmarked: a trunk backward behind this one waits for the whole stream)
         return (None, None, None) + tuple(grads) + extra
 

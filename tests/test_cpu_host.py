@@ -212,6 +212,49 @@ def test_weight_change_detection():
     assert net._weights_key() != k5
 
 
+def test_refresh_rule_on_hand_made_keys():
+    """PixelNeRFNet._follows_in_place / _mark_trunk_stale, the one statement of the rule that _sync() and optim.Adam.step() both
+    follow: the native copy follows a change of the weights key on the device only when it reads the MLP parameters in place
+    and nothing but MLP / encoder tensors moved, in place; an encoder tensor that moved marks the inference trunk stale."""
+    net = make_model(pconf.default_mv()["model"]).eval()
+    old = (("mlp_coarse.lin_in.weight", 1000, 3), ("encoder.model.conv1.weight", 2000, 5), ("code._freqs", 3000, 0))
+
+    def changed(i, ptr=None, version=None):
+        row = old[i]
+        return old[:i] + ((row[0], row[1] if ptr is None else ptr, row[2] if version is None else version),) + old[i + 1:]
+
+    assert not net._follows_in_place(old, old)                      # a fresh model: the library reads no parameter in place
+    net._dev_bound = True                                           # (what _sync() finds on the device for contiguous fp32 MLPs)
+    assert net._follows_in_place(old, old) is True
+    assert net._follows_in_place(old, changed(0, version=4)) is True
+    net._mark_trunk_stale(old, changed(0, version=4))
+    assert net._enc_stale is False                                  # an MLP step does not touch the trunk
+    assert net._follows_in_place(old, changed(1, version=6)) is True
+    net._mark_trunk_stale(old, changed(1, version=6))
+    assert net._enc_stale is True
+    assert net._follows_in_place(old, changed(2, version=1)) is False      # a code. buffer written: re-upload
+    assert net._follows_in_place(old, changed(0, ptr=1064)) is False       # a storage moved
+    assert net._follows_in_place(old, changed(1, ptr=2064, version=6)) is False
+    assert net._follows_in_place(old, old[:2]) is False and net._follows_in_place(old[:2], old) is False
+    assert net._follows_in_place(None, old) is False
+
+
+def test_camera_pair_formats():
+    """model._camera_pairs: focal / c as encode() takes them (reference models.py:125-148) -> (N, 2) fp32 host rows."""
+    from pixel_nerf_yolo_amd.model import _camera_pairs
+
+    def rows(v, **kw):
+        out = _camera_pairs(v, **kw)
+        assert out.dtype == torch.float32 and out.device.type == "cpu" and out.is_contiguous() and out.dim() == 2
+        return out.tolist()
+    assert rows(65.5) == [[65.5, 65.5]]
+    assert rows(torch.tensor(65.5, dtype=torch.float64)) == [[65.5, 65.5]]
+    assert rows(torch.tensor([10.0, 20.0, 30.0])) == [[10.0, 10.0], [20.0, 20.0], [30.0, 30.0]]
+    assert rows(np.array([[31.5, 24.25]])) == [[31.5, 24.25]]
+    assert rows(torch.tensor([[1.0, 2.0], [3.0, 4.0], [5.0, 6.0]]).t().contiguous().t()) == [[1.0, 2.0], [3.0, 4.0], [5.0, 6.0]]
+    assert rows(None, default=(63 * 0.5, 48 * 0.5)) == [[31.5, 24.0]]     # c = None: the centre of a 63 x 48 (W x H) image
+
+
 def test_sched_step_matches_reference(golden):
     """tests/golden/sched.npz: the reference's NeRFRenderer driven through the same step sequence."""
     g = golden("sched")

@@ -986,7 +986,8 @@ def test_trunk_training_batch_statistics_vs_oracle_autograd(use_first_pool):
     net.mlp_coarse.load_state_dict({k: torch.from_numpy(v) for k, v in synth.mlp_state(1801).items()})
     net.mlp_fine.load_state_dict({k: torch.from_numpy(v) for k, v in synth.mlp_state(1802).items()})
     net = net.to(DEV).train()
-    assert net._native_trunk_training() if hasattr(net, "_trunk_bound") else True
+    net._sync()
+    assert net._native_trunk_training()
     images = torch.from_numpy(np.stack([synth.images(seed + 1 + i, ns, H, W) for i in range(SB)]))
     poses = np.stack([synth.scene_cameras(ns, radius=1.3 + 0.1 * i)[0] for i in range(SB)])
     type(net.encoder).forward_torch, keep = (lambda self, x: (_ for _ in ()).throw(AssertionError("torch trunk used"))), type(net.encoder).forward_torch
@@ -1302,3 +1303,61 @@ def test_latent_gradient_super_batch_side_streams():
         assert float(scs[i].latent.grad.abs().max()) > 0.0
         grad_check("d latent, scene %d" % i, lat_hip.grad[i * ns:(i + 1) * ns], scs[i].latent.grad)
     compare_param_grads(net, scs[0])
+
+
+@pytest.mark.one_backward_leg
+def test_failed_backward_leaves_no_latent_gradient_bound(monkeypatch):
+    """A backward whose library call fails (pny_query_backward made to return an error, in Python) unbinds the latent-gradient
+    accumulator from every scene handle it had bound it to (PixelNeRFNet.latent_grad: the buffer dies with the exception), and
+    the same forward and backward run again on that model give, bit for bit under set_deterministic(True), the parameter and
+    latent gradients of a fresh model that never failed.  3 blocks (2 per view) at L = 512, SB = 2 objects of NS = 2 views on
+    supplied 8 x 8 latents that require grad, 64 query points per object."""
+    SB, ns, H, W, n = 2, 2, 32, 32, 64
+    kw = dict(d_latent=512, d_out=4, n_blocks=3, combine_layer=2)
+    c = pconf.default_mv()
+    for k in ("mlp_coarse", "mlp_fine"):
+        c.d["model"][k].update({"n_blocks": 3, "combine_layer": 2})
+    rs = np.random.RandomState(41)
+    xyz, vd, G = dt(rs.uniform(-0.5, 0.5, size=(SB, n, 3))), dt(rs.standard_normal((SB, n, 3))), dt(rs.standard_normal((SB, n, 4)))
+    poses = torch.from_numpy(np.stack([synth.scene_cameras(ns, radius=1.3 + 0.1 * i)[0] for i in range(SB)]))
+    L = plib.load()
+
+    def fresh():
+        net = make_model(c["model"], stop_encoder_grad=True)
+        net.mlp_coarse.load_state_dict({k: torch.from_numpy(v) for k, v in synth.mlp_state(4101, **kw).items()})
+        net.mlp_fine.load_state_dict({k: torch.from_numpy(v) for k, v in synth.mlp_state(4102, **kw).items()})
+        net = net.to(DEV).train().set_deterministic(True)
+        lat = torch.from_numpy(np.concatenate([synth.latent(4110 + i, ns, 512, 8, 8) for i in range(SB)])).to(DEV).requires_grad_()
+        net.encode(torch.zeros(SB, ns, 3, H, W), poses, torch.tensor(0.9 * W), latent=lat)
+        return net, lat
+
+    def step(net):
+        (net(xyz, coarse=True, viewdirs=vd) * G).sum().backward()
+
+    def grads(net, lat):
+        torch.cuda.synchronize()
+        assert lat.grad is not None and float(lat.grad.abs().max()) > 0.0
+        return [lat.grad.clone()] + [p.grad.clone() for _, p in net.trainable_mlp_parameters()]
+
+    net, lat = fresh()
+    bound = {}      # scene handle -> is a latent-gradient buffer bound to it (the library has no getter: follow the calls)
+    bind = L.pny_scene_bind_latent_grad
+
+    def recording_bind(h, p):
+        bound[h.value] = p is not None
+        return bind(h, p)
+    with monkeypatch.context() as mp:
+        mp.setattr(L, "pny_scene_bind_latent_grad", recording_bind)
+        mp.setattr(L, "pny_query_backward", lambda *a: -1)
+        with pytest.raises(plib.PnyError):
+            step(net)
+    assert len(bound) == SB and not any(bound.values()), bound
+    assert lat.grad is None and all(p.grad is None for _, p in net.trainable_mlp_parameters())
+    step(net)
+    got = grads(net, lat)
+    ref_net, ref_lat = fresh()
+    step(ref_net)
+    want = grads(ref_net, ref_lat)
+    assert len(got) == len(want) == 1 + 2 * 20      # the latent; 20 tensors per MLP (lin_in, lin_out, 3 blocks, 2 lin_z)
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)

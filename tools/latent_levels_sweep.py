@@ -4,7 +4,7 @@ Time per PixelNeRFNet.encode(latent=[m0, m1, m2]) call and per backward from the
 gradients, against yardsticks taken in the same run on the same inputs:
   * the ATen sequence the list path replaces: F.interpolate(bilinear, align_corners=True) per level, torch.cat,
     encode(latent=tensor) (which transposes to channel-last); backwards, the channel-last gradient made NCHW
-    (permute + contiguous, what end_latent_grad does for a tensor latent) and autograd through cat and the interpolations;
+    (permute + contiguous, what PixelNeRFNet.latent_grad's result() does for a tensor latent) and autograd through cat and the interpolations;
   * a plain device copy of the latent's bytes (``dst.copy_(src)``): what moving the result alone costs.
 The two stage entries alone (pny_latent_levels, pny_latent_levels_backward: one launch each) are timed beside them.
 
@@ -81,7 +81,7 @@ def main():
         (h0, w0), ltot = sizes[0], sum(CHANNELS)
         images = torch.zeros(1, NS, 3, 2 * h0, 2 * w0)
         maps = [torch.from_numpy(rs.randn(NS, ch, h, w).astype(np.float32)).to(dev).requires_grad_() for ch, (h, w) in zip(CHANNELS, sizes)]
-        g = torch.from_numpy(rs.randn(NS, h0, w0, ltot).astype(np.float32)).to(dev)       # channel-last, as begin_latent_grad's buffer
+        g = torch.from_numpy(rs.randn(NS, h0, w0, ltot).astype(np.float32)).to(dev)       # channel-last, as latent_grad's buffer
         src = torch.empty(NS, h0, w0, ltot, device=dev)
         dst = torch.empty_like(src)
 
