@@ -818,6 +818,35 @@ typedef struct pny_yolo_loss_desc {
 int pny_yolo_loss(const pny_yolo_loss_desc* desc, const float* pred_dev, const float* target_dev, const float* anchors_dev,
                   int64_t cells, float* terms_dev, int32_t* counts_dev, float* d_pred_dev, pny_stream stream);
 
+/* pny_yolo_loss_batches: the YOLO losses of ALL mini-batches of a training step in one launch, with the trainer's
+ * per-mini-batch normalisation (train/trainlib/YoloTrainer.py:149-208: the rays of every scale are split into mini-batches
+ * of ray_batch_size rows, YoloLoss is called and backpropagated per mini-batch, the five values are summed on the host and
+ * divided by the number of mini-batches).  The accumulated gradient of that loop is the gradient of sum_m loss_m, which is
+ * not YoloLoss over all rows: every loss_m divides by its own mini-batch's n_obj and n_noobj.
+ * pred_dev (N, A, 5 + C) and target_dev (N, A, 6) hold the rows of all scales in flat order (pny_yolo_train_batch's row
+ * order), N = sum rows[s]; anchors_dev (n_scales, A, 2).  Scale s owns ceil(rows[s] / batch_rows) consecutive mini-batches,
+ * the last of a scale may be short, none straddles two scales; M = their number, pny_yolo_loss_batches_count.  One
+ * workgroup per mini-batch; which rows it takes is computed from `batches` in the kernel (no table, no upload).
+ * Per mini-batch m the arithmetic is pny_yolo_loss's on that slice with that scale's anchors (the same per-item code, the
+ * n_obj == 0, n_noobj == 0 and class-out-of-range rules included): terms_seg_dev (M, 5) rows {total, box, object, no_object,
+ * class}, counts_seg_dev (M, 2) (or NULL) rows {n_obj, n_noobj}, and d_pred_dev (N, A, 5 + C) (or NULL) = d (sum_m total_m) /
+ * dpred, every element written.  A mini-batch of at most 1024 (row, anchor) pairs gives the bits of pny_yolo_loss on its slice;
+ * a longer one the same counts and gradient, and terms that differ by the summation order.
+ * step_dev[6] = {S(total), S(total) / M, S(box) / M, S(object) / M, S(no_object) / M, S(class) / M}: S adds the fp32 values
+ * of terms_seg_dev in mini-batch order in fp64 (the trainer's `total += loss.item()`), each entry rounded to fp32 once.
+ * step_dev[0] is the value whose gradient d_pred_dev is; step_dev[1..5] are the trainer's loss_dict.
+ * PNY_ERR_ARG: a NULL required pointer, n_scales outside 1 .. 4, a non-positive rows[s] or batch_rows, M > 4096 (refused,
+ * never truncated), num_anchors < 1, num_classes < 1, N * A >= 2^31. */
+typedef struct pny_yolo_batches_desc {
+    int32_t n_scales;      /* 1 .. 4 */
+    int32_t batch_rows;    /* conf yolo.ray_batch_size */
+    int64_t rows[4];       /* rows (rays) of each scale, flat order */
+} pny_yolo_batches_desc;
+int pny_yolo_loss_batches(const pny_yolo_loss_desc* desc, const pny_yolo_batches_desc* batches, const float* pred_dev,
+                          const float* target_dev, const float* anchors_dev, float* terms_seg_dev, int32_t* counts_seg_dev,
+                          float* step_dev, float* d_pred_dev, pny_stream stream);
+int pny_yolo_loss_batches_count(const pny_yolo_batches_desc* batches); /* M, or a negative status */
+
 /* ---- NaN / Inf monitor: the finiteness tests of a YOLO training step without a host wait (csrc/finite.hip).  Replaces the
  * `if torch.isnan(x).any()` / `torch.isinf(x).any()` tests on the render and the targets (train/trainlib/YoloTrainer.py:
  * 163-178) and the two per-parameter generator expressions over p.grad (:188-194), each of which is two launches and a

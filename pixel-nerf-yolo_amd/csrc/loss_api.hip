@@ -82,4 +82,54 @@ int pny_yolo_loss(const pny_yolo_loss_desc* desc, const float* pred_dev, const f
     return PNY_OK;
 }
 
+// M and N of a mini-batch description, or PNY_ERR_ARG with a message that starts with `who`.
+static int batches_geometry(const char* who, const pny_yolo_batches_desc* b, int64_t* n_rows) {
+    if (!b) return fail(PNY_ERR_ARG, std::string(who) + "null argument");
+    if (b->n_scales < 1 || b->n_scales > LOSS_MAX_SCALES) return fail(PNY_ERR_ARG, std::string(who) + "n_scales must be 1 .. 4");
+    if (b->batch_rows <= 0) return fail(PNY_ERR_ARG, std::string(who) + "batch_rows must be positive");
+    int64_t m = 0, n = 0;
+    for (int s = 0; s < b->n_scales; ++s) {
+        if (b->rows[s] <= 0) return fail(PNY_ERR_ARG, std::string(who) + "rows[" + std::to_string(s) + "] must be positive");
+        if (b->rows[s] > (int64_t)INT32_MAX) return fail(PNY_ERR_ARG, std::string(who) + "more than 2^31 - 1 (row, anchor) pairs");
+        m += b->rows[s] / b->batch_rows + (b->rows[s] % b->batch_rows != 0);
+        n += b->rows[s];
+        if (m > LOSS_MAX_SEGMENTS)
+            return fail(PNY_ERR_ARG, std::string(who) + "more than " + std::to_string(LOSS_MAX_SEGMENTS) + " mini-batches");
+    }
+    if (n_rows) *n_rows = n;
+    return (int)m;
+}
+
+int pny_yolo_loss_batches_count(const pny_yolo_batches_desc* batches) {
+    return batches_geometry("pny_yolo_loss_batches_count: ", batches, nullptr);
+}
+
+int pny_yolo_loss_batches(const pny_yolo_loss_desc* desc, const pny_yolo_batches_desc* batches, const float* pred_dev,
+                          const float* target_dev, const float* anchors_dev, float* terms_seg_dev, int32_t* counts_seg_dev,
+                          float* step_dev, float* d_pred_dev, pny_stream stream) {
+    const char* who = "pny_yolo_loss_batches: ";
+    if (!desc || !batches || !pred_dev || !target_dev || !anchors_dev || !terms_seg_dev || !step_dev)
+        return fail(PNY_ERR_ARG, std::string(who) + "null argument");
+    int64_t n_rows = 0;
+    const int m = batches_geometry(who, batches, &n_rows);
+    if (m < 0) return m;
+    if (desc->num_anchors < 1) return fail(PNY_ERR_ARG, std::string(who) + "num_anchors must be at least 1");
+    if (desc->num_classes < 1) return fail(PNY_ERR_ARG, std::string(who) + "num_classes must be at least 1");
+    if (n_rows > (int64_t)INT32_MAX / desc->num_anchors)   // (the counts are int32)
+        return fail(PNY_ERR_ARG, std::string(who) + "more than 2^31 - 1 (row, anchor) pairs");
+    YoloBatchesArgs a;
+    a.pred = pred_dev, a.target = target_dev, a.anchors = anchors_dev;
+    a.n_scales = batches->n_scales, a.batch_rows = batches->batch_rows, a.segments = m;
+    for (int s = 0; s < LOSS_MAX_SCALES; ++s) a.rows[s] = s < batches->n_scales ? batches->rows[s] : 0;
+    a.A = desc->num_anchors, a.C = desc->num_classes;
+    a.w_box = desc->box_loss, a.w_obj = desc->object_loss, a.w_noobj = desc->no_object_loss, a.w_cls = desc->class_loss;
+    a.terms_seg = terms_seg_dev, a.counts_seg = counts_seg_dev, a.step = step_dev, a.d_pred = d_pred_dev;
+    int rc;
+    double* unused = nullptr;   // (the partial-sum table: the mini-batches' terms are their own table)
+    if ((rc = loss_workspace((hipStream_t)stream, &a.ticket, &unused))) return rc;
+    launch_yolo_loss_batches(a, (hipStream_t)stream);
+    PNY_HIP(hipGetLastError());
+    return PNY_OK;
+}
+
 }  // extern "C"

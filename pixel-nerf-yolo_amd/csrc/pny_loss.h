@@ -40,8 +40,30 @@ struct YoloLossArgs {
     double* partials;
 };
 
+constexpr int LOSS_MAX_SCALES = 4;        // scales of one yolo_loss_batches launch
+constexpr int LOSS_MAX_SEGMENTS = 4096;   // mini-batches ("segments") of one yolo_loss_batches launch = its workgroups
+
+// yolo_loss_batches_kernel: the YOLO loss of every mini-batch of a training step, one workgroup per mini-batch.  The
+// mini-batches are computed from rows / batch_rows in the kernel: scale s owns ceil(rows[s] / batch_rows) consecutive ones.
+struct YoloBatchesArgs {
+    const float* pred;       // (sum rows, A, 5 + C)
+    const float* target;     // (sum rows, A, 6)
+    const float* anchors;    // (n_scales, A, 2)
+    int n_scales, batch_rows;
+    long long rows[LOSS_MAX_SCALES];
+    int segments;            // M = the grid
+    int A, C;
+    float w_box, w_obj, w_noobj, w_cls;
+    float* terms_seg;        // (M, 5) {total, box, object, no_object, class} per mini-batch
+    int* counts_seg;         // (M, 2) {n_obj, n_noobj}, or null
+    float* step;             // [6] {sum total, sum total / M, sum box / M, sum object / M, sum no_object / M, sum class / M}
+    float* d_pred;           // or null
+    unsigned* ticket;
+};
+
 int loss_grid(long long items, int per_group);
 void launch_rgb_loss(const RgbLossArgs& a, hipStream_t st);
 void launch_yolo_loss(const YoloLossArgs& a, hipStream_t st);
+void launch_yolo_loss_batches(const YoloBatchesArgs& a, hipStream_t st);
 
 }  // namespace pny

@@ -82,6 +82,10 @@ class YoloLossDesc(C.Structure):
                 ("no_object_loss", C.c_float), ("class_loss", C.c_float)]
 
 
+class YoloBatchesDesc(C.Structure):
+    _fields_ = [("n_scales", C.c_int32), ("batch_rows", C.c_int32), ("rows", C.c_int64 * 4)]
+
+
 class ViewMetricsDesc(C.Structure):
     _fields_ = [("n_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("gt_layout", C.c_int32),
                 ("win_size", C.c_int32)]
@@ -218,6 +222,9 @@ SIGNATURES = {
                                C.c_void_p, C.c_void_p]),
     "pny_yolo_loss": (C.c_int, [C.POINTER(YoloLossDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]),
+    "pny_yolo_loss_batches": (C.c_int, [C.POINTER(YoloLossDesc), C.POINTER(YoloBatchesDesc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pny_yolo_loss_batches_count": (C.c_int, [C.POINTER(YoloBatchesDesc)]),
     "pny_finite_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
     "pny_finite_destroy": (None, [C.c_void_p]),
     "pny_finite_add_tensor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),

@@ -8,6 +8,8 @@ reference's module, so its trainers bind with ``from pixel_nerf_yolo_amd import 
   get_rgb_loss(conf, coarse, using_bg, reduction)  MSE or L1 criterion, ``forward(outputs, targets)`` -> 0-dim loss
   NerfLoss                                         PixelNerfTrainer.py:147-154 whole: both passes, the lambdas and the sum
   YoloLoss                                         loss.py:107-179; unlike loss.py:145,147 it leaves ``pred`` and ``target`` untouched
+  YoloLoss.forward_batches                         the losses of ALL mini-batches of a YoloTrainer step (YoloTrainer.py:149-208) in
+                                                   one launch, each normalised by its own counts, with the gradient of their sum
 
 What the shipped configs disable or never reach is refused by name (``AlphaLossNV2``, ``get_alpha_loss``,
 ``RGBWithUncertainty``, ``RGBWithBackground``, ``use_uncertainty``, a reduction other than "mean").  fp32 tensors on an
@@ -19,7 +21,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import lib as _lib
-from .lib import RgbLossDesc, YoloLossDesc, check, stream_of
+from .lib import RgbLossDesc, YoloBatchesDesc, YoloLossDesc, check, stream_of
 
 
 def _unsupported(name, why):
@@ -193,6 +195,56 @@ class _YoloLossFn(torch.autograd.Function):
         return (None if d_pred is None or g is None else d_pred * g, None, None, None, None, None)
 
 
+class _YoloLossBatchesFn(torch.autograd.Function):
+    """(pred, target, anchors (S, A, 2)) -> (step (6,), step[0] as a 0-dim view); only step[0], the sum of the mini-batches'
+    totals, carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, target, anchors, desc, batches, owner, grad_on):
+        who = "pixel_nerf_yolo_amd.loss.YoloLoss.forward_batches: "
+        A, S = desc.num_anchors, batches.n_scales
+        pred = _dev_f32(pred, "pred")
+        dev = pred.device
+        target = _dev_f32(target, "target", dev)
+        anchors = _dev_f32(anchors, "anchors", dev)
+        ctx.pred_shape = pred.shape
+        if pred.dim() == 4 and pred.shape[0] == 1:
+            pred = pred[0]
+        if pred.dim() != 3 or pred.shape[1] != A or pred.shape[2] < 6:
+            raise ValueError(who + "pred must be (N, %d, 5 + C) or (1, N, %d, 5 + C) with C >= 1, got %s" % (A, A, tuple(pred.shape)))
+        N = pred.shape[0]
+        if tuple(target.shape) not in ((N, A, 6), (1, N, A, 6)):
+            raise ValueError(who + "target must be %s, got %s" % ((N, A, 6), tuple(target.shape)))
+        if tuple(anchors.shape) != (S, A, 2):
+            raise ValueError(who + "anchors must be (%d, %d, 2), one (A, 2) per entry of rows_per_scale, got %s"
+                             % (S, A, tuple(anchors.shape)))
+        if sum(batches.rows[:S]) != N:
+            raise ValueError(who + "rows_per_scale %s add up to %d rows, pred has %d" % (list(batches.rows[:S]), sum(batches.rows[:S]), N))
+        desc.num_classes = pred.shape[2] - 5
+        L = _lib.load()
+        M = L.pny_yolo_loss_batches_count(C.byref(batches))
+        if M < 0:
+            check(M)
+        step = torch.empty(6, device=dev, dtype=torch.float32)
+        terms = torch.empty(M, 5, device=dev, dtype=torch.float32)
+        counts = torch.empty(M, 2, device=dev, dtype=torch.int32)
+        d_pred = torch.empty_like(pred) if grad_on and ctx.needs_input_grad[0] else None
+        with torch.cuda.device(dev):
+            check(L.pny_yolo_loss_batches(C.byref(desc), C.byref(batches), _p(pred), _p(target), _p(anchors), _p(terms), _p(counts),
+                                          _p(step), _p(d_pred), stream_of(dev)))
+        ctx.save_for_backward(d_pred)
+        ctx.set_materialize_grads(False)
+        owner.batch_terms, owner.batch_counts, owner.saved_grad = terms, counts, d_pred
+        ctx.mark_non_differentiable(step)
+        return step, step[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, _g_step, g):
+        (d_pred,) = ctx.saved_tensors
+        return (None if d_pred is None or g is None else (d_pred * g).reshape(ctx.pred_shape), None, None, None, None, None, None)
+
+
 class YoloLoss(torch.nn.Module):
     """model/loss.py:107-179: ``forward(pred, target, anchors)`` -> (total, box_loss, object_loss, no_object_loss, class_loss),
     0-dim views of one device tensor (``.terms``); ``.counts`` is the (2,) int32 device tensor {n_obj, n_noobj} of the last
@@ -204,7 +256,7 @@ class YoloLoss(torch.nn.Module):
         self.num_anchors_per_scale = int(num_anchors_per_scale)
         self.box_loss, self.object_loss = float(box_loss), float(object_loss)
         self.no_object_loss, self.class_loss = float(no_object_loss), float(class_loss)
-        self.terms = self.counts = self.saved_grad = None
+        self.terms = self.counts = self.saved_grad = self.batch_terms = self.batch_counts = None
 
     def forward(self, pred, target, anchors):
         desc = YoloLossDesc(num_anchors=self.num_anchors_per_scale, num_classes=0, box_loss=self.box_loss,
@@ -212,6 +264,30 @@ class YoloLoss(torch.nn.Module):
         out = _YoloLossFn.apply(pred, target, anchors, desc, self, torch.is_grad_enabled())
         self.terms = out[0]
         return out[1:]
+
+    def forward_batches(self, pred, target, anchors, rows_per_scale, ray_batch_size):
+        """The losses of ALL mini-batches of a training step in one launch, normalised per mini-batch as the trainer's loop
+        normalises them (train/trainlib/YoloTrainer.py:149-208; include/pnyolo.h pny_yolo_loss_batches).
+
+        :param pred (N, A, 5 + C) or (1, N, A, 5 + C): the render of all rows of all scales, flat (util.yolo_train_batch(flat=True))
+        :param target (N, A, 6) or (1, N, A, 6)
+        :param anchors (S, A, 2) device tensor, or a list of S device tensors (A, 2)
+        :param rows_per_scale S row counts that add up to N; scale s is cut into ceil(rows / ray_batch_size) mini-batches
+        :return (loss_sum, step_terms): step_terms (6,) on the device = {sum of the mini-batches' totals, then the trainer's
+                loss_dict: t, box_loss, object_loss, no_object_loss, class_loss (sums divided by the number of mini-batches)};
+                loss_sum = step_terms[0] as a 0-dim view, the only value with a gradient: loss_sum.backward() gives what the
+                loop's loss.backward(retain_graph=True) calls accumulate.  ``.batch_terms`` (M, 5) and ``.batch_counts``
+                (M, 2) are the mini-batches' own values, on the device."""
+        if isinstance(anchors, (list, tuple)):
+            anchors = torch.stack([_dev_f32(a, "anchors[%d]" % i) for i, a in enumerate(anchors)])
+        rows = [int(r) for r in rows_per_scale]
+        if not 1 <= len(rows) <= 4:
+            raise ValueError("pixel_nerf_yolo_amd.loss.YoloLoss.forward_batches: rows_per_scale must hold 1 .. 4 row counts, got %d" % len(rows))
+        desc = YoloLossDesc(num_anchors=self.num_anchors_per_scale, num_classes=0, box_loss=self.box_loss,
+                            object_loss=self.object_loss, no_object_loss=self.no_object_loss, class_loss=self.class_loss)
+        batches = YoloBatchesDesc(n_scales=len(rows), batch_rows=int(ray_batch_size), rows=(C.c_int64 * 4)(*rows))
+        step, loss_sum = _YoloLossBatchesFn.apply(pred, target, anchors, desc, batches, self, torch.is_grad_enabled())
+        return loss_sum, step
 
     @classmethod
     def from_conf(cls, conf, num_anchors_per_scale):

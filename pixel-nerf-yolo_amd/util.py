@@ -239,7 +239,7 @@ def build_yolo_targets(labels, n_labels, height, width, cell_sizes, anchors, ign
     return grids
 
 
-def yolo_train_batch(poses, view_ids, focal, c, targets, height, width, cell_sizes, z_near, z_far, device=None):
+def yolo_train_batch(poses, view_ids, focal, c, targets, height, width, cell_sizes, z_near, z_far, device=None, flat=False):
     """
     The rays and target cells of one YOLO training step for one object, over all scales and selected views, in one kernel
     launch: what the reference's YoloTrainer.calc_losses:93-129 prepares per scale (gen_rays_yolo at the scale's grid size,
@@ -252,6 +252,8 @@ def yolo_train_batch(poses, view_ids, focal, c, targets, height, width, cell_siz
     :return (rays_per_scale, targets_per_scale): lists of views (NS * Hs * Ws, 8) and (NS * Hs * Ws, A, 6) into two flat
             buffers, rows ordered (position in view_ids, y, x).  torch.split(rays_per_scale[s].unsqueeze(0), ray_batch_size,
             dim=1) gives the trainer's mini-batches.
+            flat=True: (rays (N, 8), targets (N, A, 6), rows_per_scale) instead -- the two flat buffers themselves and the
+            row count of each scale, as loss.YoloLoss.forward_batches takes them (one render, one loss, one backward per step).
     """
     dev = _device_of(targets[0], device)
     cells = [int(v) for v in cell_sizes]
@@ -278,6 +280,8 @@ def yolo_train_batch(poses, view_ids, focal, c, targets, height, width, cell_siz
                                                _pair(c, "c"), (C.c_void_p * len(grids))(*grids), ptr(rays), ptr(tout), got,
                                                stream_of(dev)))
     assert list(got) == off
+    if flat:
+        return rays, tout, [b - a for a, b in zip(off, off[1:])]
     return [rays[a:b] for a, b in zip(off, off[1:])], [tout[a:b] for a, b in zip(off, off[1:])]
 
 

@@ -10,7 +10,17 @@
       reference_style: YoloTrainer.py:163-178 and :188-194 -- four `if torch.is{nan,inf}(x).any()` on the render and the targets,
                        then torch.isnan(p.grad).any() and torch.isinf(p.grad).any() for every parameter of the net;
       monitor:         util.FiniteMonitor: check(render), check(targets), check(grads) -- three launches, no read (the step's
-                       single read, report(), is timed on its own).
+                       single read, report(), is timed on its own);
+  (c) a whole training step: encode of a supplied latent that requires grad, the renders, the losses, the backwards, the
+      finiteness tests and the logged values, on the model of conf.yolo() (L = 1792)
+      looped:          the trainer's loop (YoloTrainer.py:149-208) on the per-mini-batch API: per mini-batch of 128 rays one
+                       render, loss.YoloLoss, backward(retain_graph=True), three FiniteMonitor checks and five .item();
+      one_pass:        util.yolo_train_batch(flat=True), ONE render of all rays, loss.YoloLoss.forward_batches, ONE backward,
+                       the three checks once, one step_terms.tolist();
+      at the shipped geometry (960 x 512, cell 32, 3 views: 1440 rays, 12 mini-batches) and at three scales (cells 8, 16, 32).
+      Both legs end with FiniteMonitor.report() + reset() and start from gradients set to None.  blocking_reads counts the
+      step's device -> host reads at the tool's own call sites (.item(), .tolist(), report()); torch.profiler files a 4-byte
+      .item() under copies_other.
 
 Shapes: the shipped configuration (conf/exp/yolo.conf of the reference: one scale of cell 32, 3 of 49 views, 3 anchors,
 128-ray mini-batches) on a 600 x 800 frame, and the same with three scales (cells 8, 16, 32).  The gradients are zero-filled
@@ -24,7 +34,7 @@ and so reads them back once per scale inside gen_rays_yolo; the one-launch leg t
 them over: that part of the difference is the call site's, not the kernels'.  Prints one JSON line per leg and writes them
 to profiles/yolo_step_sweep.json.
 
-usage: python tools/yolo_step_sweep.py [--calls 30] [--warmup 5] [--out profiles/yolo_step_sweep.json]"""
+usage: python tools/yolo_step_sweep.py [--calls 30] [--warmup 5] [--step-calls 20] [--out profiles/yolo_step_sweep.json]"""
 import argparse
 import json
 import os
@@ -43,9 +53,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--step-calls", type=int, default=20, help="timed calls of each whole-step leg (c)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "yolo_step_sweep.json"))
     args = ap.parse_args()
-    assert args.calls >= 20, "median of at least 20 calls"
+    assert args.calls >= 20 and args.step_calls >= 20, "median of at least 20 calls"
 
     import numpy as np
     import torch
@@ -54,6 +65,7 @@ def main():
     pnyolo_pkg.load()
     from pixel_nerf_yolo_amd import conf as pconf, synth
     from pixel_nerf_yolo_amd.model import make_model
+    from pixel_nerf_yolo_amd.lib import PnyError as plib_errors
     from pixel_nerf_yolo_amd.util import FiniteMonitor, gen_rays_yolo, stage_yolo_targets, yolo_train_batch
 
     dev = torch.device("cuda", 0)
@@ -77,9 +89,10 @@ def main():
                 c["host_synchronisations"] += 1
         return c
 
-    def timed(fn):
+    def timed(fn, calls=None):
+        calls = args.calls if calls is None else calls
         wall, issue = [], []
-        for it in range(args.warmup + args.calls):
+        for it in range(args.warmup + calls):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             out = fn()
@@ -168,6 +181,103 @@ def main():
                    parameter_tensors=len(params), parameter_elements=n_el, mini_batch=MB, calls=args.calls, **timed(fn))
         rows.append(row)
         print(json.dumps(row), flush=True)
+    mon.close()
+    del net, params, mon
+
+    # ---- (c) a whole training step, looped and in one pass
+    from pixel_nerf_yolo_amd import loss as ploss
+    from pixel_nerf_yolo_amd.render import YoloRenderer
+    SH, SW, LAT_HW = 512, 960, (64, 120)                         # the shipped frame (1920 x 1080 by yolo.image_scale) and a latent of 1 / 8
+    conf = pconf.yolo()
+    net = make_model(conf["model"]).to(dev).train()
+    ren = YoloRenderer.from_conf(conf)
+    render_par = ren.bind_parallel(net)
+    crit = ploss.YoloLoss(A, 1.0, 20.0, 1.0, 1.0)                # yolo.weights of the shipped conf
+    lat = (0.5 * torch.randn(NS, net.d_latent, *LAT_HW, generator=torch.Generator().manual_seed(5))).to(dev).requires_grad_()
+    s_focal, s_c = torch.tensor([840.0, 846.0]), torch.tensor([480.0, 256.0])
+    src_poses, no_images = poses[image_ord][None], torch.zeros(1, NS, 3, SH, SW)   # (encode reads the poses on the host)
+    names = [n for n, _ in net.named_parameters()]
+    params = list(net.parameters())
+    mon = FiniteMonitor(("render", "targets", "grads"), dev)
+    mon.watch("grads", params, names, grads=True)
+    all_anchors = [torch.tensor(a, device=dev) for a in conf["yolo.anchors"]]
+
+    failed = False
+    for shape, cells in SHAPES.items():
+        if failed:
+            break
+        anchors = all_anchors[-len(cells):]
+        gen = torch.Generator().manual_seed(6)
+        grids = []
+        for cell in cells:                                       # dataset-like targets: 25 % object cells, 10 % ignored
+            g = torch.rand(NV, SH // cell, SW // cell, A, 6, generator=gen)
+            u = g[..., 0].clone()
+            g[..., 0] = torch.where(u < 0.25, torch.ones(()), torch.where(u < 0.35, -torch.ones(()), torch.zeros(())))
+            g[..., 3:5] = 0.02 + 0.88 * g[..., 3:5]
+            g[..., 5] = torch.floor(2.0 * g[..., 5]).clamp(max=1.0)
+            grids.append(g.to(dev))
+
+        def begin():
+            net.zero_grad(set_to_none=True)
+            lat.grad = None
+            net.encode(no_images, src_poses, s_focal[None], c=s_c[None], latent=lat)
+
+        reads = [0]                                              # blocking device -> host reads, counted where the step makes them
+
+        def end():
+            report = mon.report()
+            reads[0] += 1
+            mon.reset()
+            return report
+
+        def looped():
+            begin()
+            all_rays, all_bboxes_gt = yolo_train_batch(poses, image_ord, s_focal, s_c, grids, SH, SW, cells, Z_NEAR, Z_FAR)
+            totals, mini_batch = [0.0] * 5, 0
+            for s, (rays_on_scale, bboxes_on_scale) in enumerate(zip(all_rays, all_bboxes_gt)):
+                for rays, bboxes_gt in zip(torch.split(rays_on_scale.unsqueeze(0), MB, dim=1),
+                                           torch.split(bboxes_on_scale.unsqueeze(0), MB, dim=1)):
+                    mini_batch += 1
+                    render = render_par(rays).reshape(1, rays.shape[1], A, 7)
+                    mon.check("render", render)
+                    mon.check("targets", bboxes_gt)
+                    out = crit(render, bboxes_gt, anchors[s])
+                    out[0].backward(retain_graph=True)
+                    mon.check("grads")
+                    for j, o in enumerate(out):
+                        totals[j] += o.item()
+                        reads[0] += 1
+            return [t / mini_batch for t in totals], end()
+
+        def one_pass():
+            begin()
+            rays, bboxes_gt, rows = yolo_train_batch(poses, image_ord, s_focal, s_c, grids, SH, SW, cells, Z_NEAR, Z_FAR, flat=True)
+            render = render_par(rays[None]).reshape(1, rays.shape[0], A, 7)
+            mon.check("render", render)
+            mon.check("targets", bboxes_gt)
+            loss_sum, step_terms = crit.forward_batches(render, bboxes_gt[None], anchors, rows, MB)
+            loss_sum.backward()
+            mon.check("grads")
+            logged = step_terms.tolist()[1:]
+            reads[0] += 1
+            return logged, end()
+
+        n_rays = int(sum(NS * (SH // cl) * (SW // cl) for cl in cells))
+        n_mb = int(sum(-(-NS * (SH // cl) * (SW // cl) // MB) for cl in cells))
+        for leg, fn in (("looped", looped), ("one_pass", one_pass)):
+            row = dict(part="whole_step", shape=shape, cells=cells, H=SH, W=SW, NS=NS, A=A, rays=n_rays, mini_batches=n_mb,
+                       d_latent=int(net.d_latent), latent_hw=list(LAT_HW), leg=leg, calls=args.step_calls)
+            try:
+                reads[0] = 0
+                logged, report = fn()
+                row.update(logged=[round(v, 6) for v in logged], clean=not any(r[0] or r[1] for r in report.values()),
+                           blocking_reads=reads[0], **timed(fn, args.step_calls))
+            except (plib_errors, RuntimeError) as e:             # reported, not hidden; nothing more is started behind an error
+                row["error"], failed = "%s: %s" % (type(e).__name__, e), True
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            if failed:
+                break
     mon.close()
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as fh:
