@@ -915,6 +915,64 @@ int pny_view_metrics(const pny_view_metrics_desc* desc, const float* rgb_dev, co
                      double* metrics_dev /* (NV, 2) {psnr, ssim}, or NULL */,
                      uint8_t* rgb8_dev /* (NV, H, W, 3), or NULL */, pny_stream stream);
 
+/* ---- LPIPS (VGG-16): the third number of the reference's eval tail (eval/calc_metrics.py:186-246) on the device
+ * (csrc/lpips.hip, csrc/pny_lpips.h; the 13 convolutions run on the trunk's exact-fp32 MFMA kernel).  LPIPS v0.1 with
+ * net = "vgg", normalize = False, spatial = False, restated from the published definition:
+ *   x in [-1, 1] -> (x - shift) / scale per channel, shift = (-.030, -.088, -.188), scale = (.458, .448, .450) (compiled in);
+ *   VGG-16 `features` 0 .. 29 (3x3 convolutions with bias and relu, max_pool2d(2, 2) in floor mode), tapped behind relu1_2,
+ *   relu2_2, relu3_3, relu4_3 and relu5_3; per tap f^ = f / (sqrt(sum_c f^2) + 1e-10), sum_c w[c] (f^0[c] - f^1[c])^2, the mean
+ *   over the tap's pixels in fp64; the value is the sum of the five taps.
+ * A handle holds the weights.  pny_lpips_load_weights takes host tensors by name, one call each: "conv0.weight" ..
+ * "conv12.weight" (cout, cin, 3, 3) and "conv0.bias" .. "conv12.bias" (cout) in execution order, "lin0.weight" .. "lin4.weight"
+ * with 64, 128, 256, 512, 512 elements in any shape; an unknown name or a wrong shape is PNY_ERR_ARG and names the tensor.
+ * pny_lpips_finalize uploads them to the current device and packs the convolutions there, on `stream`; it returns when the
+ * packing has run, names the first missing tensor (PNY_ERR_STATE), and may be called again after further loads.
+ *
+ * pny_lpips_forward scores n_pairs pairs: pred and gt are device tensors of n_pairs images in the forms below, out (n_pairs)
+ * fp64 on the device.  It allocates nothing and waits for nothing: the caller passes `work`, pny_lpips_workspace_bytes(
+ * desc->batch_size, H, W) bytes of device memory, 256-byte aligned.  desc->batch_size >= n_pairs is the batch the caller walks
+ * its views in; the kernels' arithmetic follows from the layer, H and W alone, so a pair's value has the same bits in every
+ * batch and on every run (no float atomics; the five taps add to `out` in stream order).  23 launches.
+ *   PNY_LPIPS_F32_NHWC_01   (n, H, W, 3) fp32 in [0, 1]: t * 2 - 1 (a prediction is clamped to [0, 1] first if desc->clamp)
+ *   PNY_LPIPS_F32_NCHW_PM1  (n, 3, H, W) fp32 in [-1, 1], taken as given
+ *   PNY_LPIPS_U8_NHWC       (n, H, W, 3) bytes: (b / 255) * 2 - 1
+ *   PNY_LPIPS_F32_NCHW_01   (n, 3, H, W) fp32 in [0, 1]: as NHWC_01
+ * PNY_ERR_ARG: H or W below 16 (relu5_3 would be empty), or a batch whose largest activation, 2 n H W 64 floats, is 2^31
+ * elements or more; the message says which.  PNY_ERR_STATE: not finalized.
+ * pny_lpips_workspace_bytes runs on the host alone: 4 (r64(2n H W 4) + 2 r64(2n H W 64)) bytes, r64 = rounded up to 64 floats.
+ *
+ * The stages, for tests: pny_lpips_prepare writes the (2n, H, W, 4) scaled channel-last images (predictions first);
+ * pny_lpips_maxpool2 pools a channel-last (n, h, w, c) tensor, c % 4 == 0, to (n, h / 2, w / 2, c); pny_lpips_distance scores one
+ * tap tensor (2n, h, w, c), c in {64, 128, 256, 512}, against weights (c) and writes (accumulate = 0) or adds to out (n);
+ * pny_lpips_conv runs VGG convolution `layer` (0 .. 12) alone on n channel-last images (n, h, w, cin; 4 channels for layer 0)
+ * into (n, h, w, cout) and reports the instantiation it launched (100 SPLIT + 10 NT + MT), chosen as pny_lpips_forward chooses
+ * it for a batch of n images at that layer. */
+#define PNY_LPIPS_F32_NHWC_01 0
+#define PNY_LPIPS_F32_NCHW_PM1 1
+#define PNY_LPIPS_U8_NHWC 2
+#define PNY_LPIPS_F32_NCHW_01 3
+typedef struct pny_lpips pny_lpips;
+typedef struct pny_lpips_desc {
+    int32_t height, width;      /* channels = 3 */
+    int32_t pred_kind, gt_kind; /* PNY_LPIPS_* */
+    int32_t clamp;              /* clamp a float [0, 1] prediction to [0, 1] first (the lpips package does not: 0) */
+    int32_t batch_size;         /* pairs per batch the workspace was sized for; 0: n_pairs */
+} pny_lpips_desc;
+int pny_lpips_create(pny_lpips** out);
+void pny_lpips_destroy(pny_lpips* h);
+int pny_lpips_load_weights(pny_lpips* h, const char* name, const float* data_host, const int64_t* shape, int ndim);
+int pny_lpips_finalize(pny_lpips* h, pny_stream stream);
+int pny_lpips_workspace_bytes(int n_pairs, int height, int width, size_t* bytes);
+int pny_lpips_forward(pny_lpips* h, const pny_lpips_desc* desc, const void* pred_dev, const void* gt_dev, int n_pairs,
+                      void* work_dev, double* out_dev, pny_stream stream);
+int pny_lpips_prepare(const pny_lpips_desc* desc, const void* pred_dev, const void* gt_dev, int n_pairs, float* out_dev,
+                      pny_stream stream);
+int pny_lpips_maxpool2(const float* in_dev, int n, int h, int w, int c, float* out_dev, pny_stream stream);
+int pny_lpips_distance(const float* tap_dev, const float* weight_dev, int n_pairs, int h, int w, int c, int accumulate,
+                       double* out_dev, pny_stream stream);
+int pny_lpips_conv(pny_lpips* h, int layer, const float* in_dev, int n, int height, int width, float* out_dev, int* variant,
+                   pny_stream stream);
+
 /* ---- colour jitter: the training-time augmentation of all views of all objects in ONE launch (csrc/augment.hip).
  * Replaces the four passes per view that the reference's ColorJitterDataset runs on CPU tensors in every __getitem__
  * (src/data/data_util.py:34-47; get_split_dataset wraps the training split of `yolo` and `dvr_dtu` in it,

@@ -94,8 +94,10 @@ bool run_pixel_linear(const ConvLayer& L, const float* in, long long npix, float
 // One convolution through conv_mfma_kernel (encoder.hip): out = relu?(conv(in) * L.scale + L.shift + resid), channel-last.
 // hout / wout explicit; dil_shift > 0 reads the input as if 2^dil_shift - 1 zeros stood between its samples.
 // variant (optional): the conv_mfma_kernel<SPLIT, NT, MT> instantiation that was launched, as 100 SPLIT + 10 NT + MT.
+// force_variant (optional): launch that instantiation (811, 822, 111 or 122) instead of choosing one from the launch's tile
+// count; 0 keeps the choice.  811 and 822 need L.J >= 32, as the unforced choice does; anything else fails.  For callers whose bits must not depend on how many images share the launch (pny_lpips.h).
 bool run_conv_ex(const ConvLayer& L, const float* in, int n, int hin, int win, int hout, int wout, int dil_shift, const float* resid,
-                 int relu, float* out, hipStream_t st, int* variant = nullptr);
+                 int relu, float* out, hipStream_t st, int* variant = nullptr, int force_variant = 0);
 // The trunk's other forward kernels (encoder.hip), shared by inference and training:
 // images (n,3,H,W) NCHW -> (n,H,W,4) channel-last with a zero 4th channel
 void launch_image_to_nhwc4(const float* images, float* out, int n, int height, int width, hipStream_t st);

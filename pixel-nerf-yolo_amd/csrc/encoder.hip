@@ -660,7 +660,7 @@ static bool run_conv(const ConvLayer& L, const float* in, int n, int hin, int wi
 
 // The general form: explicit output size and an input dilation (transposed convolutions of the trunk's backward).
 bool run_conv_ex(const ConvLayer& L, const float* in, int n, int hin, int win, int hout, int wout, int dil_shift, const float* resid,
-                 int relu, float* out, hipStream_t st, int* variant) {
+                 int relu, float* out, hipStream_t st, int* variant, int force_variant) {
     ConvArgs a;
     a.in = in;
     a.w = L.w;
@@ -692,9 +692,15 @@ bool run_conv_ex(const ConvLayer& L, const float* in, int n, int hin, int win, i
     }
     const long long tiles64 = ((a.npix + 63) / 64) * (L.cout / 64);
     const long long tiles32 = ((a.npix + 31) / 32) * (L.cout / 32);
-    const bool small = tiles64 < 2 * (long long)cus;
+    bool small = tiles64 < 2 * (long long)cus;
+    bool split = L.J >= 32 && (small ? tiles32 : tiles64) <= 4 * (long long)cus;
+    if (force_variant) {
+        if (force_variant != 811 && force_variant != 822 && force_variant != 111 && force_variant != 122) return false;
+        split = force_variant / 100 == 8;
+        small = force_variant % 10 == 1;
+        if (split && L.J < 32) return false;   // as the unforced choice: no K split of a short reduction
+    }
     const long long tiles = small ? tiles32 : tiles64;
-    const bool split = L.J >= 32 && tiles <= 4 * (long long)cus;
     static LdsLimit lds;
     (void)lds.raise(8 * 4 * 16 * 64 * sizeof(float), conv_mfma_kernel<8, 2, 2>);
     int launched;   // 100 SPLIT + 10 NT + MT of the instantiation below

@@ -91,6 +91,11 @@ class ViewMetricsDesc(C.Structure):
                 ("win_size", C.c_int32)]
 
 
+class LpipsDesc(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("pred_kind", C.c_int32), ("gt_kind", C.c_int32),
+                ("clamp", C.c_int32), ("batch_size", C.c_int32)]
+
+
 class ColorJitterDesc(C.Structure):
     _fields_ = [("n_objs", C.c_int32), ("n_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
                 ("in_format", C.c_int32)]
@@ -232,6 +237,18 @@ SIGNATURES = {
     "pny_finite_check_tensors": (C.c_int, [C.POINTER(C.c_void_p), c_i64_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p]),
     "pny_finite_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "pny_view_metrics": (C.c_int, [C.POINTER(ViewMetricsDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pny_lpips_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "pny_lpips_destroy": (None, [C.c_void_p]),
+    "pny_lpips_load_weights": (C.c_int, [C.c_void_p, C.c_char_p, c_float_p, c_i64_p, C.c_int]),
+    "pny_lpips_finalize": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pny_lpips_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "pny_lpips_forward": (C.c_int, [C.c_void_p, C.POINTER(LpipsDesc), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "pny_lpips_prepare": (C.c_int, [C.POINTER(LpipsDesc), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "pny_lpips_maxpool2": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pny_lpips_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pny_lpips_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int),
+                                 C.c_void_p]),
     "pny_color_jitter": (C.c_int, [C.POINTER(ColorJitterDesc), C.c_void_p, c_float_p, C.c_void_p, C.c_void_p]),
     "pny_ingest_views": (C.c_int, [C.POINTER(IngestDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pny_yolo_build_targets": (C.c_int, [C.POINTER(YoloTargetsDesc), C.c_void_p, C.c_void_p, c_float_p, C.POINTER(C.c_void_p),
@@ -258,6 +275,14 @@ YOLO_BATCH_MAX_VIEWS, YOLO_BATCH_MAX_SCALES = 16, 4           # PNY_YOLO_BATCH_M
 FINITE_NAN, FINITE_INF, FINITE_MAX_IMMEDIATE = 1, 2, 8        # PNY_FINITE_*
 GT_LAYOUT = {"nhwc01": 0, "nchw_pm1": 1}                      # PNY_GT_NHWC_01, PNY_GT_NCHW_PM1
 GT_FLAT, METRICS_WIN = 2, 7                                   # PNY_GT_FLAT (util.psnr's form); the SSIM window of this build
+# pny_lpips_desc::pred_kind / gt_kind (PNY_LPIPS_*), the smallest image side, the channels of the 13 convolutions and 5 taps
+LPIPS_KIND = {"nhwc01": 0, "nchw_pm1": 1, "u8": 2, "nchw01": 3}
+LPIPS_MIN_SIZE = 16
+LPIPS_CIN = (3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512)
+LPIPS_COUT = (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)
+LPIPS_TAP_CH = (64, 128, 256, 512, 512)
+VGG16_FEATURES = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)   # torchvision vgg16().features: indices of the convolutions
+VGG16_SLICE = (1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5)               # the lpips package's slice of each
 IMG_F32_NCHW_PM1, IMG_U8_NHWC, JITTER_MAX_OBJS = 0, 1, 64     # PNY_IMG_*, PNY_JITTER_MAX_OBJS
 RESIZE = {"none": 0, "bilinear_u8": 1, "area": 2}             # PNY_RESIZE_*
 YOLO_TARGETS_MAX_ANCHORS = 64                                 # PNY_YOLO_TARGETS_MAX_ANCHORS

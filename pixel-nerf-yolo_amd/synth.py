@@ -119,3 +119,19 @@ def resnet34_state(seed, prefix="encoder.model.", residual_gain=1.0):
                 bn(p + "downsample.1", cout)
         cin = cout
     return sd
+
+
+def vgg16_lpips_state(seed):
+    """Seeded stand-in weights of LPIPS (VGG-16) under the lpips package's state-dict names (metrics.LPIPS.load_state_dict):
+    ``net.slice{s}.{i}.weight / .bias`` He-normal with small biases, so that activations stay O(1) through the 13 layers, and
+    non-negative ``lin{k}.model.1.weight`` (1, C, 1, 1) as the trained linear layers are.  No trained weights ship with this
+    project; these only exercise the arithmetic."""
+    rs = np.random.RandomState(seed)
+    sd = {}
+    from . import lib as _lib      # the one table of VGG-16's convolutions and LPIPS's taps
+    for i, s, cin, cout in zip(_lib.VGG16_FEATURES, _lib.VGG16_SLICE, _lib.LPIPS_CIN, _lib.LPIPS_COUT):
+        sd["net.slice%d.%d.weight" % (s, i)] = (rs.standard_normal((cout, cin, 3, 3)) * math.sqrt(2.0 / (9 * cin))).astype(np.float32)
+        sd["net.slice%d.%d.bias" % (s, i)] = (rs.standard_normal((cout,)) * 0.05).astype(np.float32)
+    for k, c in enumerate(_lib.LPIPS_TAP_CH):
+        sd["lin%d.model.1.weight" % k] = rs.uniform(0.0, 2.0 / c, size=(1, c, 1, 1)).astype(np.float32)
+    return sd
