@@ -72,6 +72,7 @@ static int pack_count(int kind, int n_out, int k_in, int k_pad, int count) {
     if (kind == PACK_AT || kind == PACK_H2T) return (k_in / 32) * (k_pad / 8) * 64;   // the matrix is W^T: k_in rows, K = n_out padded
     if (kind == PACK_NTT) return (n_out / 32) * (k_in / 8) * 64;
     if (kind == PACK_H1) return (k_pad / 16) * (n_out / 32) * 64;
+    if (kind == PACK_H2O) return (k_pad / 16) * (n_out > 32 ? 2 : 1) * 2 * 64;
     return count;
 }
 
@@ -121,7 +122,7 @@ static int pack_mlp(pny_model* m, const std::string& pre, MlpWeights& w, MlpWeig
             e.k_in = (int)shape[1];
             e.k_pad = k_pad;
         }
-        if (kind == PACK_H2 || kind == PACK_H2T)
+        if (kind == PACK_H2 || kind == PACK_H2T || kind == PACK_H2O)
             for (float v : t->data)
                 if (!(std::fabs(v) <= 65504.0f)) m->f16_weights_ok = false;   // out of the f16 range (or NaN): AUTO stays on fp32
         e.dst_off = plan.reserve((plain ? 1 : 4) * (size_t)pack_count(kind, e.n_out, e.k_in, e.k_pad, e.count));
@@ -158,6 +159,8 @@ static int pack_mlp(pny_model* m, const std::string& pre, MlpWeights& w, MlpWeig
         if ((rc = add(PACK_H2, block(b) + ".fc_0.weight", "", {HID, HID}, HID, &wt.h2.fc0[b]))) return rc;
         if ((rc = add(PACK_H2, block(b) + ".fc_1.weight", "", {HID, HID}, HID, &wt.h2.fc1[b]))) return rc;
     }
+    // ... and lin_out, its d_out rows padded with zero rows to whole n-tiles (d_out <= 64: pny_model_create)
+    if ((rc = add(PACK_H2O, pre + "lin_out.weight", "", {d.d_out, HID}, HID, &wt.h2.out))) return rc;
     // stacked transposed lin_z for the latent gradient (latent_grad.hip): W_cat[c][b * 512 + f] = lin_z[b].weight[f][c], one
     // n-tile-major image of K = nvb * 512 in which block b owns k-iterations [64 b, 64 b + 64) of every n-tile
     wt.wzT_cat = nullptr;

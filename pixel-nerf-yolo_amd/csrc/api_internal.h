@@ -55,6 +55,7 @@ struct F16Images {
     const float* in;
     const float* fc0[MAX_BLOCKS];
     const float* fc1[MAX_BLOCKS];
+    const float* out;         // lin_out for the forward's split-K product (PACK_H2O; split-f16 images only)
     const float* T_out;
     const float* T_fc0[MAX_BLOCKS];
     const float* T_fc1[MAX_BLOCKS];
@@ -77,6 +78,7 @@ inline void use_images(MlpArgs& a, const F16Images& im) {
     a.w_base = im.base;
     a.w_bytes = (unsigned)im.bytes;
     a.h2_in = im.in;
+    a.h2_out = im.out;
     for (int b = 0; b < a.n_blocks; ++b) {
         a.h2_fc0[b] = im.fc0[b];
         a.h2_fc1[b] = im.fc1[b];

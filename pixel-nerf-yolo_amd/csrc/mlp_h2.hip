@@ -40,6 +40,15 @@
 //     b_fc0 in the relu(net) epilogue, the last b_fc1 before lin_out) from a table in the remaining LDS (22 KiB for 5 blocks;
 //     152 of the CU's 160 KiB in use): no bias registers, no global loads between a barrier and a GEMM.  (mean over views
 //     of (h_v + b) = mean(h_v) + b, so the last per-view bias may follow the mean.)
+//   * lin_out runs on the matrix cores as well (every two-plane instantiation; h2linout_product / h2linout_reduce below):
+//     W_out is one more split-f16 image (pack.hip PACK_H2O, d_out rows padded with zero rows to one or two n-tiles), wave w
+//     multiplies the k-steps of its own features with the planes it has just written in the last epilogue -- wave-level
+//     ordering, no workgroup barrier -- into one fp32 partial per 64-k chunk, the partials go to the wave's own plane rows,
+//     and behind ONE barrier they are added in chunk order, + b_out, output head, store (16 bytes per sample at d_out = 4).
+//     24 MFMAs per wave and tile at d_out <= 32, where 256 of the 512 threads ran 64 x 512 scalar fp32 FMAs each on converted
+//     planes before.  Both shapes add the same products in the same order (a wave of the 32-sample shape keeps its two chunks
+//     apart), so they still agree bit for bit, and a result still does not depend on the batch.  The single-plane kernel keeps
+//     the fp32 dot products on w_out as stored: its tests sit close to their bars (profiles/view_mean_fc1.md);
 //   * stash / slab traffic goes through raw buffer resources (one VGPR of lane offset instead of per-quad 64-bit pointers);
 //   * the VIEW-MEAN order (the non-stashing two-plane instantiations, pny_mlp_h2_kernel<false> and pny_mlp_h2s_kernel): the
 //     last per-view block ends `h_v += fc_1(R_v)`, R_v =
@@ -457,6 +466,130 @@ __device__ __forceinline__ void h2wave_entry(WaveGather& wg, f32x16 (&acc)[h2::N
     range_check(rmax, range_flag);
 }
 
+// ---- lin_out as a split-K product on the matrix cores (the two-plane instantiations; header comment) ------------------------------
+// out^T = W_out relu(h_top)^T, W_out as a split-f16 image of its own (pack.hip PACK_H2O: one n-tile of 32 output rows, two
+// for d_out > 32, the rows past d_out zero).  Wave w multiplies the k-steps of ITS OWN features with the planes its own
+// lanes have just written in h2epilogue -- wave-level ordering as in h2wave_commit, no workgroup barrier between epilogue
+// and product -- into ONE partial per 64-k chunk (the 64-sample shape: the wave's 64 features are chunk w; the 32-sample
+// shape: two chunks, 2 w and 2 w + 1, in separate accumulators), so that both shapes add the same products in the same order.
+// Per k-step the products come in h2gemm's order: x1 w1, x2 w1, x1 w2.  The partials go to the wave's own plane rows, which
+// are free once the B fragments are in registers (all of them are read first: with two n-tiles the first one's partials
+// already cover rows the second would still read): chunk c of the wave at c * TM * QO * 16 bytes of the wave's 16 KiB, output
+// quad qd (outputs 4 qd .. 4 qd + 3; QO = ceil(d_out / 4) of them) of sample m at (m QO + qd) * 16 -- for d_out = 4 the 32
+// lanes of an m-tile write 512 contiguous bytes.  Behind one workgroup barrier h2linout_reduce adds the 8 chunks in chunk
+// order in fp32.
+#if PNY_H2_PLANES == 2
+struct LinOutW {
+    h8 f[2 * h2::NT][2];   // [k-step of the wave][plane] of one n-tile of the lin_out image
+};
+// fragment (step j, n-tile nto, plane p) of the image at byte `img_off` of the weight blob: this lane's W_out[32 nto + (l & 31)][16 j + 8 (l >> 5) + 0..7]
+__device__ __forceinline__ void h2linout_issue(LinOutW& lw, const WStream& ws, unsigned img_off, int nto_n, int nto, int wave) {
+    using namespace h2;
+    // (the 4 NT scalar offsets are formed here, per call: hoisted out of the tile loop they are SGPRs spilled across the GEMMs)
+    unsigned base = img_off + (unsigned)(((2 * NT * wave * nto_n + nto) * 2) * 64) * 16u, step = (unsigned)(nto_n * 2 * 64) * 16u;
+    asm volatile("" : "+s"(base), "+s"(step));
+#pragma unroll
+    for (int ks = 0; ks < 2 * NT; ++ks)
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+            lw.f[ks][p] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(ws.rsrc, ws.lane_off, base + ks * step + (unsigned)(p * 64) * 16u, 0));
+}
+constexpr int LINOUT_WAVE_BYTES = 4 * h2::NT * 2 * h2::ROW_BYTES;   // the plane rows of one wave: 16 KiB in both shapes
+static_assert((h2::NT / 2) * h2::TM * 16 * 16 <= LINOUT_WAVE_BYTES, "a wave's partials (64 outputs) fit its own rows");
+__device__ __forceinline__ void h2linout_product(LinOutW& lw, const WStream& ws, unsigned img_off, int d_out, char* planes, int wave, int lane) {
+    using namespace h2;
+    constexpr int NCH = NT / 2;   // 64-k chunks of the wave
+    asm volatile("" : "+v"(lane));   // (addresses recomputed here, not hoisted over the GEMMs and spilled: h2wave_entry)
+    const int m0 = lane & 31, hh = lane >> 5;
+    const int qo = (d_out + 3) >> 2, nto_n = d_out > 32 ? 2 : 1;
+    char* region = planes + wave * LINOUT_WAVE_BYTES;
+    // the planes come from other lanes of this wave (h2epilogue); the LDS serves a wave's instructions in order
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    h8 B[NCH][MT][4][2];   // k-step 4 c + ks of the wave = rows 2 (4 c + ks) + hh of its rows
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                for (int p = 0; p < 2; ++p)
+                    B[c][mt][ks][p] = *reinterpret_cast<const h8*>(region + (2 * (4 * c + ks) + hh) * (2 * ROW_BYTES) + p * ROW_BYTES + (32 * mt + m0) * 16);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the partial stores below stay behind these reads
+    for (int nto = 0; nto < nto_n; ++nto) {
+        if (nto > 0) h2linout_issue(lw, ws, img_off, nto_n, nto, wave);   // (n-tile 0 was fetched ahead of the epilogue)
+        f32x16 acc[NCH][MT];
+        h2zero<NCH, MT>(acc);
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+#pragma unroll
+            for (int c = 0; c < NCH; ++c)
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) acc[c][mt] = h2mfma(lw.f[4 * c + ks][0], B[c][mt][ks][0], acc[c][mt]);
+#pragma unroll
+            for (int c = 0; c < NCH; ++c)
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) acc[c][mt] = h2mfma(lw.f[4 * c + ks][0], B[c][mt][ks][1], acc[c][mt]);
+#pragma unroll
+            for (int c = 0; c < NCH; ++c)
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) acc[c][mt] = h2mfma(lw.f[4 * c + ks][1], B[c][mt][ks][0], acc[c][mt]);
+        }
+        // accumulator quad q of this lane = outputs 32 nto + 8 q + 4 hh + 0..3 of sample 32 mt + m0: output quad 8 nto + 2 q + hh
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int qd = 8 * nto + 2 * q + hh;
+                    if (qd < qo)
+                        *reinterpret_cast<f32x4*>(region + c * (TM * qo * 16) + ((32 * mt + m0) * qo + qd) * 16) =
+                            f32x4{acc[c][mt][4 * q + 0], acc[c][mt][4 * q + 1], acc[c][mt][4 * q + 2], acc[c][mt][4 * q + 3]};
+                }
+    }
+}
+// ... and behind the workgroup barrier: the chunks' partials summed in chunk order 0 .. 7, + b_out, the output head, the store
+// (one thread per sample and output quad; d_out = 4: one 16-byte store per sample)
+__device__ __forceinline__ void h2linout_reduce(const MlpArgs& a, long long tile, const char* planes, int tid) {
+    using namespace h2;
+    constexpr int NCH = NT / 2, NCHUNK = (THREADS / 64) * NCH;
+    static_assert(NCHUNK * 64 == HID, "eight chunks of 64 k");
+    asm volatile("" : "+v"(tid));   // (as in h2linout_product)
+    const int qo = (a.d_out + 3) >> 2;
+    const bool vec = a.d_out == 4 && (reinterpret_cast<size_t>(a.out) & 15) == 0;
+    for (int idx = tid; idx < qo * TM; idx += THREADS) {
+        const int qd = idx / TM, m = idx % TM;
+        const char* src = planes + (m * qo + qd) * 16;
+        f32x4 part[NCHUNK];
+#pragma unroll
+        for (int g = 0; g < NCHUNK; ++g) part[g] = *reinterpret_cast<const f32x4*>(src + (g / NCH) * LINOUT_WAVE_BYTES + (g % NCH) * (TM * qo * 16));
+        float sum[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            sum[i] = part[0][i];
+#pragma unroll
+            for (int g = 1; g < NCHUNK; ++g) sum[i] = sum[i] + part[g][i];
+        }
+        const long long s = tile * TM + m;
+        if (s >= a.n_points) continue;
+        if (vec) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sum[i] = output_head(sum[i] + a.w.b_out[i], i, a.yolo);
+            *reinterpret_cast<float4*>(a.out + s * 4) = make_float4(sum[0], sum[1], sum[2], sum[3]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int o = 4 * qd + i;
+                if (o < a.d_out) a.out[s * a.d_out + o] = output_head(sum[i] + a.w.b_out[o], o, a.yolo);
+            }
+        }
+    }
+}
+#endif
+
 // per (view, tile) prologue: the lin_in B operand (positional code, view dirs) as f16 planes in rows 0..7 of each plane, and
 // the tap table; the arithmetic is prologue<C>()'s (mlp_core.h).  STASH: the operand also goes to the stash in fp32
 // ([feature/4][sample]), and a second table holds the same taps addressing the latent itself (pixel x L).
@@ -769,6 +902,22 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
         }
         // out = lin_out(relu(h + b_fc1[last])) (reference resnetfc.py:185) + output head (models.py:312-317)
         HS_T0();
+#if PNY_H2_PLANES == 2
+        // Two planes: lin_out is a split-K product on the matrix cores (h2linout_product).  The wave's fragments of the first
+        // n-tile are fetched ahead of the barrier and the epilogue; between epilogue and product there is no workgroup barrier.
+        // The reduction's readers are done before they reach the barrier in front of the next tile's h2prologue, which
+        // overwrites rows 0..7.
+        const unsigned out_off = (unsigned)(reinterpret_cast<const char*>(a.h2_out) - ws.base);
+        LinOutW lw;
+        h2linout_issue(lw, ws, out_off, a.d_out > 32 ? 2 : 1, 0, wave);
+        __builtin_amdgcn_sched_barrier(0);
+        __syncthreads();
+        h2epilogue<false, STASH>(h, entry_bias(nb), planes, wave, lane, a.range_flag, xr, post_slot(2 * (nb - nvb)));
+        h2linout_product(lw, ws, out_off, a.d_out, planes, wave, lane);
+        __syncthreads();
+        h2linout_reduce(a, tile, planes, tid);
+#else
+        // One plane: fp32 dot products with w_out as stored, on the planes behind a workgroup barrier
         __syncthreads();
         h2epilogue<false, STASH>(h, entry_bias(nb), planes, wave, lane, a.range_flag, xr, post_slot(2 * (nb - nvb)));
         __syncthreads();
@@ -780,31 +929,20 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
             for (int kg = 0; kg < HID / 8; ++kg) {
                 const h8 x0 = *reinterpret_cast<const h8*>(planes + kg * (2 * ROW_BYTES) + m * 16);
                 const float4 wa = wrow[2 * kg], wb = wrow[2 * kg + 1];
-                if constexpr (PL == 1) {
-                    sum += (float)x0[0] * wa.x;
-                    sum += (float)x0[1] * wa.y;
-                    sum += (float)x0[2] * wa.z;
-                    sum += (float)x0[3] * wa.w;
-                    sum += (float)x0[4] * wb.x;
-                    sum += (float)x0[5] * wb.y;
-                    sum += (float)x0[6] * wb.z;
-                    sum += (float)x0[7] * wb.w;
-                } else {
-                    const h8 x1 = *reinterpret_cast<const h8*>(planes + kg * (2 * ROW_BYTES) + ROW_BYTES + m * 16);
-                    sum += ((float)x0[0] + (float)x1[0]) * wa.x;
-                    sum += ((float)x0[1] + (float)x1[1]) * wa.y;
-                    sum += ((float)x0[2] + (float)x1[2]) * wa.z;
-                    sum += ((float)x0[3] + (float)x1[3]) * wa.w;
-                    sum += ((float)x0[4] + (float)x1[4]) * wb.x;
-                    sum += ((float)x0[5] + (float)x1[5]) * wb.y;
-                    sum += ((float)x0[6] + (float)x1[6]) * wb.z;
-                    sum += ((float)x0[7] + (float)x1[7]) * wb.w;
-                }
+                sum += (float)x0[0] * wa.x;
+                sum += (float)x0[1] * wa.y;
+                sum += (float)x0[2] * wa.z;
+                sum += (float)x0[3] * wa.w;
+                sum += (float)x0[4] * wb.x;
+                sum += (float)x0[5] * wb.y;
+                sum += (float)x0[6] * wb.z;
+                sum += (float)x0[7] * wb.w;
             }
             sum = output_head(sum + a.w.b_out[o], o, a.yolo);
             const long long s = tile * TM + m;
             if (s < a.n_points) a.out[s * a.d_out + o] = sum;
         }
+#endif
         HS_LAP(HS_LINOUT);
     }
 #ifdef PNY_H2_STAMP

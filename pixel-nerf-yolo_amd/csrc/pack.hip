@@ -18,6 +18,8 @@
 // PACK_H2  split-f16 image for mlp_h2.hip: w = w1 + w2, w1 = f16(w), w2 = f16(w - w1) (round to nearest); per 16-k step j
 //          [n-tile][plane][lane] x 8 halves, lane l holding W[32 nt + (l & 31)][16 j + 8 (l >> 5) + 0..7].  4 bytes per weight.
 // PACK_H2T the same of W^T (mlp_bwd_h2.hip).
+// PACK_H2O the PACK_H2 image of lin_out (mlp_h2.hip's split-K product): n_out <= 64 rows padded with zero rows to 32, or to 64
+//          for n_out > 32, so per 16-k step one or two n-tiles instead of 16 (the same branch of the kernel as PACK_H2).
 // PACK_H1  plane 0 of a PACK_H2 / PACK_H2T image, 2 bytes per weight (mlp_h1.hip, mlp_bwd_h1.hip).
 // PACK_COPY / PACK_ADD2  the tensor as stored / the sum of two (a lin_z bias folded into the bias before it); count floats.
 #include "pny_common.h"
@@ -41,16 +43,19 @@ __global__ __launch_bounds__(256) void repack_kernel(const PackJob* __restrict__
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = jb.src[(size_t)(f + r) * jb.n_out + c];
             reinterpret_cast<float4*>(jb.dst)[((size_t)nt * (jb.k_pad / 8) + jl) * 64 + l] = make_float4(v[0], v[1], v[2], v[3]);
-        } else if (jb.kind == PACK_H2 || jb.kind == PACK_H2T) {   // [16-k step][n-tile 0..15][plane][lane] x 8 halves
-            const int l = (int)(i & 63), p = (int)((i >> 6) & 1), nt = (int)((i >> 7) & 15), j = (int)(i >> 11);
+        } else if (jb.kind == PACK_H2 || jb.kind == PACK_H2T || jb.kind == PACK_H2O) {   // [16-k step][n-tile][plane][lane] x 8 halves
+            // n-tiles per step: the 16 of a 512-row matrix, or lin_out's one or two (PACK_H2O: rows past n_out are zero)
+            const int ntn = jb.kind == PACK_H2O ? (jb.n_out > 32 ? 2 : 1) : 16;
+            const int l = (int)(i & 63), p = (int)((i >> 6) & 1), nt = (int)((i >> 7) % ntn), j = (int)((i >> 7) / ntn);
             const int row = 32 * nt + (l & 31), col = 16 * j + 8 * (l >> 5);
+            const bool row_ok = jb.kind != PACK_H2O || row < jb.n_out;
             typedef _Float16 h8 __attribute__((ext_vector_type(8)));
             h8 o;
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
                 // PACK_H2T: the matrix is W^T, element (row, col + r) = W[col + r][row], W is (n_out x k_in)
                 const float w = jb.kind == PACK_H2T ? ((col + r < jb.n_out) ? jb.src[(size_t)(col + r) * jb.k_in + row] : 0.f)
-                                                    : ((col + r < jb.k_in) ? jb.src[(size_t)row * jb.k_in + col + r] : 0.f);
+                                                    : ((row_ok && col + r < jb.k_in) ? jb.src[(size_t)row * jb.k_in + col + r] : 0.f);
                 out_of_range |= !(fabsf(w) <= 65504.0f);
                 const _Float16 w1 = (_Float16)w;
                 o[r] = p == 0 ? w1 : (_Float16)(w - (float)w1);

@@ -79,6 +79,8 @@ struct MlpArgs {
     const float* h2_in;
     const float* h2_fc0[MAX_BLOCKS];
     const float* h2_fc1[MAX_BLOCKS];
+    // ... and of lin_out (pack.hip PACK_H2O; the two-plane kernels' split-K product, mlp_h2.hip); null with single-plane images
+    const float* h2_out;
     // f16-range guard (include/pnyolo.h pny_model_range_status): host-visible word the f16x2 kernels OR PNY_RANGE_* bits into
     unsigned* range_flag;
     // Source-view cameras travel in the kernel-argument segment (NS entries used; 64 B each): a launch carries its own
@@ -87,7 +89,7 @@ struct MlpArgs {
 };
 
 // ---- weight packing (pack.hip): the packed operand layouts, built from the state_dict tensors on the device
-enum { PACK_A = 0, PACK_AT = 1, PACK_NT = 2, PACK_COPY = 3, PACK_ADD2 = 4, PACK_H2 = 5, PACK_NTT = 6, PACK_H2T = 7, PACK_H1 = 9 };
+enum { PACK_A = 0, PACK_AT = 1, PACK_NT = 2, PACK_COPY = 3, PACK_ADD2 = 4, PACK_H2 = 5, PACK_NTT = 6, PACK_H2T = 7, PACK_H1 = 9, PACK_H2O = 10 };
 struct PackJob {
     const float* src;
     const float* src2;
