@@ -263,6 +263,7 @@ SIGNATURES = {
 
 _lib = None
 ABI_VERSION = 11
+OK, ERR_ARG, ERR_STATE, ERR_HIP, ERR_NOGPU, ERR_RANGE = 0, -1, -2, -3, -4, -5   # pny_status
 PROJECTION = {"off": 0, "on": 1, "auto": 2}
 # f16: opt-in single-plane mode for no-grad launches, f16_train: the same for training too; both outside the 1e-4 parity bar
 PRECISION = {"f32": 0, "f16x2": 1, "auto": 2, "f16": 3, "f16_train": 5}
@@ -342,7 +343,7 @@ def load():
 
 
 def check(rc):
-    if rc == -5:   # PNY_ERR_RANGE
+    if rc == ERR_RANGE:
         raise PnyRangeError("libpnyolo: %s (status %d)" % (load().pny_last_error().decode("utf-8", "replace"), rc))
     if rc != 0:
         raise PnyError("libpnyolo: %s (status %d)" % (load().pny_last_error().decode("utf-8", "replace"), rc))

@@ -8,7 +8,7 @@ The colour jitter without a GPU (include/pnyolo.h pny_color_jitter, augment.colo
     sets;
   * the kernel's own arithmetic (csrc/pny_augment.h compiled by g++, the way tests/test_cpu_metrics.py compiles its header):
     the per-pixel functions and the whole chain on 10 000 random pixels and edge pixels, within the bar;
-  * the C ABI: declared, bound, exported, still version 11, still strict C99, every listed refusal before any launch;
+  * the C ABI: every listed refusal before any launch (the boundary itself: tests/test_cpu_abi.py);
   * Python: refusals by name; the deferred dataset returns untouched images and exactly the factors the host path draws;
     get_split_dataset(jitter_on_device=True) wires it for `dvr_dtu` and `yolo`.
 
@@ -20,29 +20,19 @@ map.  The chain is continuous across each of its branches, so no pixel is left o
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import augment_ref as ar
+from host_tools import CSRC, built_lib, header_code, header_text, host_header_program  # noqa: F401
 from pixel_nerf_yolo_amd import augment as paug
 from pixel_nerf_yolo_amd import data as pdata
 from pixel_nerf_yolo_amd import lib as plib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pixel-nerf-yolo_amd", "csrc")
 # (hue, saturation, brightness, contrast): the identity, the extremes, two corners of the reference's ranges
 FACTOR_SETS = np.array([(0, 1, 1, 1), (0.5, 0, 3, 0), (-0.5, 2, 0.5, 2), (0.1, 0.9, 1.1, 0.9), (-0.1, 1.1, 0.9, 1.1)], np.float32)
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(plib.LIB_PATH):
-        plib.build()
-    return plib.load()
 
 
 def random_images(seed, nv, h, w):
@@ -186,21 +176,10 @@ int main(int argc, char** argv) {
 def host_header(tmp_path_factory):
     """csrc/pny_augment.h compiled by g++: __device__ defined away, no fused multiply-add -- the product's own code, run on lines
     of queries."""
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not installed")
-    tmp = tmp_path_factory.mktemp("augment_host")
-    src, exe = tmp / "host.cpp", tmp / "host"
-    src.write_text(HOST_MAIN)
-    cc = subprocess.run(["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-D__device__=", "-D__forceinline__=inline", "-I", CSRC,
-                         str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
+    program = host_header_program(tmp_path_factory.mktemp("augment_host"), HOST_MAIN, include_dirs=(CSRC,))
 
     def run(queries):
-        q = tmp / "queries.txt"
-        q.write_text("".join(line + "\n" for line in queries))
-        out = subprocess.run([str(exe), str(q)], capture_output=True, text=True)
-        assert out.returncode == 0, (out.returncode, out.stderr)
-        lines = out.stdout.strip().split("\n")
+        lines = program(queries)
         assert lines[0] == "jitter 1024 64"
         return [[float.fromhex(v) for v in line.split()] for line in lines[1:]]
     return run
@@ -285,51 +264,17 @@ def test_header_chain_against_the_restatement(host_header, fmt):
 
 
 # --------------------------------------------------------------------------- C ABI
-def test_entry_is_declared_bound_and_exported(built_lib):
-    hdr = open(os.path.join(ROOT, "include", "pnyolo.h")).read()
-    assert re.search(r"#define\s+PNY_ABI_VERSION\s+11\b", hdr)
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+def test_entry_is_declared_bound_and_exported():
+    """What is this entry's own (declared, bound, exported, its layout and constants: tests/test_cpu_abi.py)."""
+    hdr = header_text()
     assert re.search(r"\bint\s+pny_color_jitter\s*\(\s*const\s+pny_color_jitter_desc\s*\*\s*desc\s*,\s*const\s+void\s*\*\s*images_dev\s*,"
-                     r"\s*const\s+float\s*\*\s*factors_host\s*,\s*float\s*\*\s*out_dev\s*,\s*pny_stream\s+stream\s*\)", code)
-    assert re.search(r"PNY_IMG_F32_NCHW_PM1\s*=\s*0\s*,\s*PNY_IMG_U8_NHWC\s*=\s*1", code)
-    assert re.search(r"#define\s+PNY_JITTER_MAX_OBJS\s+64\b", hdr)
-    res, args = plib.SIGNATURES["pny_color_jitter"]
-    assert res is C.c_int and len(args) == 5
-    assert hasattr(built_lib, "pny_color_jitter")
-    assert built_lib.pny_version() == plib.ABI_VERSION == 11
-    assert (plib.IMG_F32_NCHW_PM1, plib.IMG_U8_NHWC, plib.JITTER_MAX_OBJS) == (0, 1, 64)
+                     r"\s*const\s+float\s*\*\s*factors_host\s*,\s*float\s*\*\s*out_dev\s*,\s*pny_stream\s+stream\s*\)", header_code())
     # the comment of the entry names the reference lines it replaces, as every other entry does
     block = hdr[hdr.index("---- colour jitter"):hdr.index("int pny_color_jitter")]
     assert "data_util.py:34-47" in block
     # the sources are part of the build
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert " augment.hip" in mk and " augment_api.hip" in mk and " pny_augment.h" in mk
-
-
-STRUCT_MAIN = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "pnyolo.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu %zu %d %d %d\n", sizeof(pny_color_jitter_desc), offsetof(pny_color_jitter_desc, n_objs),
-           offsetof(pny_color_jitter_desc, n_views), offsetof(pny_color_jitter_desc, height), offsetof(pny_color_jitter_desc, width),
-           offsetof(pny_color_jitter_desc, in_format), (int)PNY_IMG_F32_NCHW_PM1, (int)PNY_IMG_U8_NHWC, PNY_JITTER_MAX_OBJS);
-    return 0;
-}
-"""
-
-
-def test_header_is_strict_c99_and_the_mirror_has_its_layout(tmp_path):
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not installed")
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text(STRUCT_MAIN)
-    cc = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
-                         "-o", str(exe)], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True).stdout.split()]
-    D = plib.ColorJitterDesc
-    assert got == [C.sizeof(D), D.n_objs.offset, D.n_views.offset, D.height.offset, D.width.offset, D.in_format.offset, 0, 1, 64]
 
 
 def test_bad_arguments_are_refused_before_any_launch(built_lib):

@@ -1,7 +1,6 @@
 """
 The batched detection scorer without a GPU (include/pnyolo.h pny_detect_views, util.score_detections / DetectionMeter):
-  * the entry and its descriptor are declared (PNY_ABI_VERSION still 11), bound in lib.SIGNATURES with the header's layout,
-    and exported by the built library;
+  * the entry's comment cites the reference, its limits are the restatement's (the boundary itself: tests/test_cpu_abi.py);
   * the C entry refuses bad arguments with PNY_ERR_ARG and a message naming the field, before any launch;
   * util.score_detections refuses on the host, by name: wrong ranks, more than 4 scales, anchors that do not divide into the
     scales, offsets that do not start at 0 or do not ascend, CPU tensors;
@@ -11,54 +10,32 @@ The batched detection scorer without a GPU (include/pnyolo.h pny_detect_views, u
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import detect_views_ref as dr
+from host_tools import CSRC, ROOT, built_lib, header_code, header_text  # noqa: F401
 import pnyolo_oracle as orc
 import stage_ref as sr
 from pixel_nerf_yolo_amd import lib as plib
 from pixel_nerf_yolo_amd import util as putil
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pixel-nerf-yolo_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(plib.LIB_PATH):
-        plib.build()
-    return plib.load()
-
-
 # --------------------------------------------------------------------------- C ABI
-def test_entry_is_declared_bound_and_exported(built_lib):
-    hdr = open(os.path.join(ROOT, "include", "pnyolo.h")).read()
-    assert re.search(r"#define\s+PNY_ABI_VERSION\s+11\b", hdr)
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"\bint\s+pny_detect_views\s*\(\s*const\s+pny_detect_views_desc\s*\*", code)
-    assert re.search(r"typedef\s+struct\s+pny_detect_views_desc\s*\{", code)
-    for field in ("form", "n_views", "n_scales", "height", "width", "cell_sizes", "n_anchors", "nms_iou", "nms_threshold", "match_iou",
-                  "max_kept"):
-        assert field in [f[0] for f in plib.DetectViewsDesc._fields_]
-    res, args = plib.SIGNATURES["pny_detect_views"]
-    assert res is C.c_int and len(args) == 14
-    assert hasattr(built_lib, "pny_detect_views")
-    assert built_lib.pny_version() == plib.ABI_VERSION == 11
+def test_entry_is_declared_bound_and_exported():
+    """What is this entry's own (declared, bound, exported, its layout and constants: tests/test_cpu_abi.py)."""
+    hdr = header_text()
+    assert re.search(r"\bint\s+pny_detect_views\s*\(\s*const\s+pny_detect_views_desc\s*\*", header_code())
     # the comment of the entry names the reference lines it replaces, as every other entry does
     block = hdr[hdr.index("The detection scores of ALL views"):hdr.index("int pny_detect_views")]
     assert "YoloTrainer.py:338-354" in block and "util.py:765-802" in block and "util.py:633-689" in block
-    # the limit is stated in the header and in lib.py, lies in the range the LDS allows, and is what the restatement assumes
-    m = re.search(r"#define\s+PNY_DETECT_MAX_CANDIDATES\s+(\d+)\b", hdr)
-    assert m and 2048 <= int(m.group(1)) <= 8192
-    assert int(m.group(1)) == plib.DETECT_MAX_CANDIDATES == dr.MAX_CANDIDATES
+    # the limit (the header's, tests/test_cpu_abi.py) lies in the range the LDS allows and is what the restatement assumes
+    assert 2048 <= plib.DETECT_MAX_CANDIDATES <= 8192 and plib.DETECT_MAX_CANDIDATES == dr.MAX_CANDIDATES
     assert len(plib.DETECT_RECORD) == 8 and tuple(plib.DETECT_RECORD) == dr.RECORD
-    assert re.search(r"#define\s+PNY_DETECT_RECORD\s+8\b", hdr)
     # one copy of the decode and of the IoU: the per-image kernels take them from the shared header
     det, views = (open(os.path.join(CSRC, f)).read() for f in ("detect.hip", "detect_views.hip"))
     shared = open(os.path.join(CSRC, "pny_detect.h")).read()
@@ -66,35 +43,6 @@ def test_entry_is_declared_bound_and_exported(built_lib):
     for src in (det, views):
         assert '#include "pny_detect.h"' in src and "float iou_xywh(" not in src and "expf(" not in src
     assert "detect_views.hip" in open(os.path.join(CSRC, "Makefile")).read()
-
-
-STRUCT_MAIN = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "pnyolo.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(pny_detect_views_desc), offsetof(pny_detect_views_desc, n_scales),
-           offsetof(pny_detect_views_desc, cell_sizes), offsetof(pny_detect_views_desc, n_anchors),
-           offsetof(pny_detect_views_desc, n_target_rows), offsetof(pny_detect_views_desc, max_kept),
-           offsetof(pny_detect_views_desc, nms_iou), offsetof(pny_detect_views_desc, nms_threshold),
-           offsetof(pny_detect_views_desc, match_iou));
-    return 0;
-}
-"""
-
-
-def test_the_mirror_has_the_headers_layout(tmp_path):
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not installed")
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text(STRUCT_MAIN)
-    cc = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
-                         "-o", str(exe)], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True).stdout.split()]
-    D = plib.DetectViewsDesc
-    assert got == [C.sizeof(D), D.n_scales.offset, D.cell_sizes.offset, D.n_anchors.offset, D.n_target_rows.offset, D.max_kept.offset,
-                   D.nms_iou.offset, D.nms_threshold.offset, D.match_iou.offset]
 
 
 def test_bad_arguments_are_refused_before_any_launch(built_lib):

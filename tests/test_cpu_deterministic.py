@@ -6,23 +6,19 @@ import re
 
 import pytest
 
+from host_tools import CSRC, header_text
 from pixel_nerf_yolo_amd import conf as pconf
 from pixel_nerf_yolo_amd import lib as plib
 from pixel_nerf_yolo_amd.model import make_model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "pnyolo.h")
-CSRC = os.path.join(ROOT, "pixel-nerf-yolo_amd", "csrc")
-
-
 def test_header_declares_the_two_functions():
-    src = open(HEADER).read()
+    src = header_text()
     assert re.search(r"^int pny_model_set_deterministic\(pny_model\* m, int enable\);", src, re.M)
     assert re.search(r"^int pny_scene_last_latent_grad_mode\(pny_scene\* s, int\* deterministic\);", src, re.M)
 
 
 def test_abi_version_is_still_11():
-    assert re.search(r"^#define PNY_ABI_VERSION 11\b", open(HEADER).read(), re.M)   # the mode only adds functions
+    assert re.search(r"^#define PNY_ABI_VERSION 11\b", header_text(), re.M)   # the mode only adds functions
     assert plib.ABI_VERSION == 11
 
 

@@ -1,22 +1,18 @@
 """The single-plane f16 precision mode (include/pnyolo.h PNY_PRECISION_F16) at the levels that need no GPU: the ABI constant,
 the Python mirror, and the argument check of PixelNeRFNet.set_matrix_precision before any scene exists."""
-import os
 import re
 
 import pytest
 
+from host_tools import header_text
 from pixel_nerf_yolo_amd import conf as pconf
 from pixel_nerf_yolo_amd import lib as plib
 from pixel_nerf_yolo_amd.model import make_model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
 def test_precision_constant_matches_the_header():
     assert plib.PRECISION["f16"] == 3
-    src = open(os.path.join(ROOT, "include", "pnyolo.h")).read()
+    src = header_text()
     assert re.search(r"^#define PNY_PRECISION_F16 3\b", src, re.M)
-    assert re.search(r"^#define PNY_ABI_VERSION 11\b", src, re.M)   # the mode only adds a value
     for name, code in plib.PRECISION.items():
         assert re.search(r"^#define PNY_PRECISION_%s %d\b" % (name.upper(), code), src, re.M), name
     assert plib.LAST_PRECISION == {0: "f32", 1: "f16x2", 2: "f16"}

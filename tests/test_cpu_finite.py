@@ -1,47 +1,23 @@
 """
-The NaN / Inf monitor without a GPU (include/pnyolo.h pny_finite_*, util.FiniteMonitor): the entries are declared, bound and
-exported with the ABI still 11, the header's constants are the Python ones, the header compiles as strict C99 with a program
-that uses every new entry, and every bad argument comes back as PNY_ERR_ARG before anything is launched (the device pointers
-here are made up and never dereferenced; no call in this file is a valid scan).
+The NaN / Inf monitor without a GPU (include/pnyolo.h pny_finite_*, util.FiniteMonitor): the header compiles as strict C99
+with a program that uses every entry under its exact type, and every bad argument comes back as PNY_ERR_ARG before anything
+is launched (the device pointers here are made up and never dereferenced; no call in this file is a valid scan).
 """
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
 
 import pytest
 import torch
 
-from pixel_nerf_yolo_amd import lib as plib
+from host_tools import built_lib, c99_program, header_text  # noqa: F401
 from pixel_nerf_yolo_amd import util as putil
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENTRIES = {"pny_finite_create": 2, "pny_finite_destroy": 1, "pny_finite_add_tensor": 4, "pny_finite_check": 5,
-           "pny_finite_check_tensors": 6, "pny_finite_reset": 3}
 DEVP = 4096     # stands for a device pointer; never dereferenced by the host
 
 
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(plib.LIB_PATH):
-        plib.build()
-    return plib.load()
-
-
-def test_entries_are_declared_bound_and_exported(built_lib):
-    hdr = open(os.path.join(ROOT, "include", "pnyolo.h")).read()
-    assert re.search(r"#define\s+PNY_ABI_VERSION\s+11\b", hdr)
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name, n_args in ENTRIES.items():
-        assert re.search(r"\b(int|void)\s+%s\s*\(" % name, code), name
-        assert name in plib.SIGNATURES and len(plib.SIGNATURES[name][1]) == n_args, name
-        assert hasattr(built_lib, name), name
-    assert built_lib.pny_version() == plib.ABI_VERSION == 11
-    for macro, value in (("PNY_FINITE_NAN", plib.FINITE_NAN), ("PNY_FINITE_INF", plib.FINITE_INF),
-                         ("PNY_FINITE_MAX_IMMEDIATE", plib.FINITE_MAX_IMMEDIATE)):
-        assert re.search(r"#define\s+%s\s+%d\b" % (macro, value), hdr), macro
-    assert (plib.FINITE_NAN, plib.FINITE_INF, plib.FINITE_MAX_IMMEDIATE) == (1, 2, 8)
+def test_entries_are_declared_bound_and_exported():
+    """The comment of the entries names the reference lines they replace (declared, bound, exported, the argument counts and
+    the constants: tests/test_cpu_abi.py)."""
+    hdr = header_text()
     block = hdr[hdr.index("NaN / Inf monitor"):hdr.index("typedef struct pny_finite pny_finite")]
     assert "YoloTrainer.py:" in block and "163-178" in block and "188-194" in block
 
@@ -67,14 +43,10 @@ int main(void) {
 """
 
 
-def test_header_compiles_as_strict_c99(tmp_path):
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not installed")
-    src = tmp_path / "finite.c"
-    src.write_text(C99_MAIN)
-    cc = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                         "-o", str(tmp_path / "finite.o")], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
+def test_header_compiles_as_strict_c99(built_lib, tmp_path):
+    """Every entry has exactly the C type a host would write for it."""
+    run = c99_program(tmp_path, C99_MAIN, link=True)()
+    assert run.returncode == 0 and run.stdout.split() == ["1", "2", "8", "1"], (run.returncode, run.stdout, run.stderr)
 
 
 def now(L, ptrs, counts, groups, n=None, flags=DEVP, arrays=True):

@@ -1,10 +1,9 @@
 """
-CPU-side checks (no GPU): the C-ABI library loads and exports every symbol include/pnyolo.h
-declares, the host mirrors expose the reference's interface (names, state_dict keys, config
-defaults), errors are loud without a GPU, and the multi-process sharding logic works over gloo.
+CPU-side checks (no GPU): the C-ABI library loads (its boundary is tests/test_cpu_abi.py's), the host mirrors expose the
+reference's interface (names, state_dict keys, config defaults), errors are loud without a GPU, and the multi-process sharding
+logic works over gloo.
 """
 import os
-import re
 import socket
 
 import numpy as np
@@ -12,52 +11,13 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from host_tools import ROOT, built_lib  # noqa: F401
 from pixel_nerf_yolo_amd import conf as pconf
 from pixel_nerf_yolo_amd import dist as pdist
 from pixel_nerf_yolo_amd import lib as plib
 from pixel_nerf_yolo_amd import synth
 from pixel_nerf_yolo_amd.model import PixelNeRFNet, make_model
 from pixel_nerf_yolo_amd.render import NeRFRenderer, YoloRenderer, make_renderer
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(plib.LIB_PATH):
-        plib.build()
-    return plib.load()
-
-
-def test_abi_exports_every_declared_symbol(built_lib):
-    hdr = open(os.path.join(ROOT, "include", "pnyolo.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(pny_[a-z0-9_]+)\s*\(", hdr))
-    assert len(declared) >= 20
-    assert declared == set(plib.SIGNATURES.keys()), declared ^ set(plib.SIGNATURES.keys())
-    for name in declared:
-        assert hasattr(built_lib, name)
-    assert built_lib.pny_version() == plib.ABI_VERSION == 11
-
-
-def test_header_is_plain_c_and_links(built_lib, tmp_path):
-    """include/pnyolo.h is the boundary a C / cgo / JNI host binds: it compiles as strict C99 (-pedantic, no warnings) without
-    any HIP or torch header, and a C program linked against the shared library gets the ABI version it was compiled for."""
-    import shutil
-    import subprocess
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not installed")
-    src = tmp_path / "abi.c"
-    src.write_text('#include "pnyolo.h"\n#include <stdio.h>\n'
-                   "int main(void) { pny_render_opts o; pny_render_out r; pny_model_desc d; (void)o; (void)r; (void)d;\n"
-                   '  printf("%d\\n", pny_version()); return pny_version() == PNY_ABI_VERSION ? 0 : 1; }\n')
-    exe = tmp_path / "abi"
-    libdir = os.path.dirname(plib.LIB_PATH)
-    cc = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                         "-L", libdir, "-lpnyolo", "-Wl,-rpath," + libdir], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert run.returncode == 0 and run.stdout.strip() == str(plib.ABI_VERSION), (run.returncode, run.stdout, run.stderr)
 
 
 def test_no_wide_store_with_sgpr_soffset_is_followed_by_a_write_of_its_data(built_lib):

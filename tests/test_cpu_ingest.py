@@ -8,21 +8,20 @@ util.build_yolo_targets, data.get_split_dataset(ingest_on_device=True)):
     on 200 random views against YOLODataset._get_all_bboxes, bit for bit, with distinct IoUs asserted;
   * the float64 restatements the GPU tests compare against (tests/ingest_ref.py) against data.py's host functions and closed
     forms: a constant image stays constant under every resize, 2:1 area is the 4-pixel mean;
-  * the C ABI: declared, bound, exported, still version 11, still strict C99, every listed refusal before any launch;
+  * the C ABI: every listed refusal before any launch (the boundary itself: tests/test_cpu_abi.py);
   * Python: refusals by argument name; on synthetic trees the ingest_on_device items of `yolo` and `srn` hold exactly the bytes,
     labels and intrinsics the default items are computed from; the `dvr*` and `multi_obj` types refuse the flag.
 """
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from host_tools import CSRC, built_lib, header_code, host_header_program  # noqa: F401
 import ingest_ref as ir
 from pixel_nerf_yolo_amd import augment as paug
 from pixel_nerf_yolo_amd import conf as pconf
@@ -30,18 +29,6 @@ from pixel_nerf_yolo_amd import data as pdata
 from pixel_nerf_yolo_amd import lib as plib
 from pixel_nerf_yolo_amd import util as putil
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pixel-nerf-yolo_amd", "csrc")
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(plib.LIB_PATH):
-        plib.build()
-    return plib.load()
-
-
-# --------------------------------------------------------------------------- the kernels' header on the host
 HOST_MAIN = r"""
 #include <stdio.h>
 #include <stdlib.h>
@@ -144,22 +131,9 @@ int main(int argc, char** argv) {
 @pytest.fixture(scope="module")
 def host_header(tmp_path_factory):
     """csrc/pny_ingest.h compiled by g++: __host__ / __device__ defined away, no fused multiply-add -- the product's own code."""
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not installed")
-    tmp = tmp_path_factory.mktemp("ingest_host")
-    src, exe = tmp / "host.cpp", tmp / "host"
-    src.write_text(HOST_MAIN)
-    cc = subprocess.run(["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-D__device__=", "-D__host__=", "-D__forceinline__=inline",
-                         "-I", CSRC, str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-
-    def run(queries):
-        q = tmp / "queries.txt"
-        q.write_text("".join(line + "\n" for line in queries))
-        out = subprocess.run([str(exe), str(q)], capture_output=True, text=True)
-        assert out.returncode == 0, (out.returncode, out.stderr)
-        return [line.split() for line in out.stdout.strip().split("\n")]
-    return run
+    program = host_header_program(tmp_path_factory.mktemp("ingest_host"), HOST_MAIN,
+                                  defines=("__device__=", "__host__=", "__forceinline__=inline"), include_dirs=(CSRC,))
+    return lambda queries: [line.split() for line in program(queries)]
 
 
 def test_header_byte_map_is_the_hosts_for_all_256_bytes(host_header):
@@ -352,54 +326,16 @@ def test_restatement_of_the_srn_mask_and_box():
 
 
 # --------------------------------------------------------------------------- C ABI
-def test_entries_are_declared_bound_and_exported(built_lib):
-    hdr = open(os.path.join(ROOT, "include", "pnyolo.h")).read()
-    assert re.search(r"#define\s+PNY_ABI_VERSION\s+11\b", hdr)
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+def test_entries_are_declared_bound_and_exported():
+    """What is these entries' own (declared, bound, exported, their layouts and constants: tests/test_cpu_abi.py)."""
+    code = header_code()
     assert re.search(r"\bint\s+pny_ingest_views\s*\(\s*const\s+pny_ingest_desc\s*\*\s*desc\s*,\s*const\s+uint8_t\s*\*\s*images_dev\s*,"
                      r"\s*float\s*\*\s*out_dev\s*,\s*float\s*\*\s*mask_dev\s*,\s*float\s*\*\s*bbox_dev\s*,\s*pny_stream\s+stream\s*\)", code)
     assert re.search(r"\bint\s+pny_yolo_build_targets\s*\(\s*const\s+pny_yolo_targets_desc\s*\*\s*desc\s*,\s*const\s+double\s*\*\s*boxes_dev\s*,"
                      r"\s*const\s+int32_t\s*\*\s*n_boxes_dev\s*,\s*const\s+float\s*\*\s*anchors_host\s*,\s*float\s*\*\s*const\s*\*\s*targets_dev\s*,"
                      r"\s*pny_stream\s+stream\s*\)", code)
-    assert re.search(r"PNY_RESIZE_NONE\s*=\s*0\s*,\s*PNY_RESIZE_BILINEAR_U8\s*=\s*1\s*,\s*PNY_RESIZE_AREA\s*=\s*2", code)
-    for name, n_args in (("pny_ingest_views", 6), ("pny_yolo_build_targets", 6)):
-        res, args = plib.SIGNATURES[name]
-        assert res is C.c_int and len(args) == n_args and hasattr(built_lib, name)
-    assert built_lib.pny_version() == plib.ABI_VERSION == 11
-    assert plib.RESIZE == {"none": 0, "bilinear_u8": 1, "area": 2} and plib.YOLO_TARGETS_MAX_ANCHORS == 64
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert " ingest.hip" in mk and " ingest_api.hip" in mk and " pny_ingest.h" in mk
-
-
-STRUCT_MAIN = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "pnyolo.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu %zu ", sizeof(pny_ingest_desc), offsetof(pny_ingest_desc, channels), offsetof(pny_ingest_desc, out_height),
-           offsetof(pny_ingest_desc, out_width), offsetof(pny_ingest_desc, resize), offsetof(pny_ingest_desc, white_mask));
-    printf("%zu %zu %zu %zu %zu %zu ", sizeof(pny_yolo_targets_desc), offsetof(pny_yolo_targets_desc, max_boxes),
-           offsetof(pny_yolo_targets_desc, n_scales), offsetof(pny_yolo_targets_desc, cell_sizes),
-           offsetof(pny_yolo_targets_desc, n_anchors), offsetof(pny_yolo_targets_desc, ignore_iou_thresh));
-    printf("%d %d %d %d\n", (int)PNY_RESIZE_NONE, (int)PNY_RESIZE_BILINEAR_U8, (int)PNY_RESIZE_AREA, PNY_YOLO_TARGETS_MAX_ANCHORS);
-    return 0;
-}
-"""
-
-
-def test_header_is_strict_c99_and_the_mirrors_have_its_layout(tmp_path):
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not installed")
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text(STRUCT_MAIN)
-    cc = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
-                         "-o", str(exe)], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True).stdout.split()]
-    D, T = plib.IngestDesc, plib.YoloTargetsDesc
-    assert got == [C.sizeof(D), D.channels.offset, D.out_height.offset, D.out_width.offset, D.resize.offset, D.white_mask.offset,
-                   C.sizeof(T), T.max_boxes.offset, T.n_scales.offset, T.cell_sizes.offset, T.n_anchors.offset,
-                   T.ignore_iou_thresh.offset, 0, 1, 2, 64]
 
 
 def test_ingest_refuses_bad_arguments_before_any_launch(built_lib):

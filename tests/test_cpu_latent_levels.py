@@ -16,19 +16,12 @@ import pytest
 import torch
 
 import latent_levels_ref as lr
+from host_tools import CSRC, built_lib, header_code, header_text  # noqa: F401
 from pixel_nerf_yolo_amd import conf as pconf
 from pixel_nerf_yolo_amd import lib as plib
 from pixel_nerf_yolo_amd.model import check_latent_levels, make_model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("pny_latent_levels", "pny_latent_levels_backward", "pny_scene_set_latent_levels")
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(plib.LIB_PATH):
-        plib.build()
-    return plib.load()
 
 
 @pytest.fixture(scope="module")
@@ -96,12 +89,9 @@ def test_level_of_the_latents_size_is_a_copy():
 
 
 # --------------------------------------------------------------------------- the C ABI
-def test_entries_are_declared_bound_and_exported(built_lib):
-    hdr = open(os.path.join(ROOT, "include", "pnyolo.h")).read()
-    assert re.search(r"#define\s+PNY_ABI_VERSION\s+11\b", hdr)
-    assert re.search(r"#define\s+PNY_MAX_LATENT_LEVELS\s+8\b", hdr)
-    assert "encoder.py:126-137" in hdr
-    flat = re.sub(r"\s+", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
+def test_entries_are_declared_bound_and_exported():
+    assert plib.MAX_LATENT_LEVELS == 8 and "encoder.py:126-137" in header_text()      # (the header's 8: tests/test_cpu_abi.py)
+    flat = re.sub(r"\s+", "", header_code())
     levels = ["const int* channels", "const int* h", "const int* w", "int n_levels"]
     decls = {
         "pny_latent_levels": ["const float* const* maps_dev"] + levels + ["int n", "float* latent_nhwc_dev", "pny_stream stream"],
@@ -118,9 +108,8 @@ def test_entries_are_declared_bound_and_exported(built_lib):
     for name, args in decls.items():
         assert "int" + name + "(" + ",".join(a.replace(" ", "") for a in args) + ");" in flat, name
         res, argtypes = plib.SIGNATURES[name]
-        assert res is C.c_int and argtypes == types[name] and hasattr(built_lib, name), name
-    assert built_lib.pny_version() == plib.ABI_VERSION == 11
-    mk = open(os.path.join(ROOT, "pixel-nerf-yolo_amd", "csrc", "Makefile")).read()
+        assert res is C.c_int and argtypes == types[name], name
+    mk = open(os.path.join(CSRC, "Makefile")).read()
     assert " latent_levels.hip" in mk
 
 

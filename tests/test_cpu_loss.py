@@ -3,30 +3,20 @@ The training losses without a GPU: the fp64 restatement (tests/loss_ref.py) agai
 (tests/golden/losses.npz, tools/make_loss_golden.py), the two new ABI functions in the header and the built library, and
 what pixel_nerf_yolo_amd.loss refuses.
 """
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 import torch
 
 import loss_ref
+from host_tools import built_lib, c99_program, header_code  # noqa: F401
 from pixel_nerf_yolo_amd import conf as pconf
 from pixel_nerf_yolo_amd import lib as plib
 from pixel_nerf_yolo_amd import loss as ploss
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 YOLO_CASES = ("y128", "y37", "ynoobj", "ya1c1", "ya3c5")
 RGB_CASES = ("mse_mse", "l1_mse", "coarse_only")
 NEW_FUNCTIONS = ("pny_rgb_loss", "pny_yolo_loss")
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(plib.LIB_PATH):
-        plib.build()
-    return plib.load()
 
 
 def rel_to_max(a, b):
@@ -72,37 +62,23 @@ def test_rgb_restatement_equals_the_reference(golden, name):
 
 
 # --------------------------------------------------------------------------- the ABI
-def test_header_declares_and_library_exports_the_loss_functions(built_lib):
-    hdr = open(os.path.join(ROOT, "include", "pnyolo.h")).read()
-    assert re.search(r"#define\s+PNY_ABI_VERSION\s+11\b", hdr)
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+def test_header_declares_and_library_exports_the_loss_functions():
+    """Each takes its descriptor first (declared, bound, exported: tests/test_cpu_abi.py)."""
     for name in NEW_FUNCTIONS:
-        assert re.search(r"\bint\s+%s\s*\(\s*const\s+%s_desc\s*\*" % (name, name), code), name + " is not declared"
-        assert name in plib.SIGNATURES and hasattr(built_lib, name), name + " is not exported"
-    assert built_lib.pny_version() == plib.ABI_VERSION == 11
+        assert re.search(r"\bint\s+%s\s*\(\s*const\s+%s_desc\s*\*" % (name, name), header_code()), name + " is not declared"
 
 
 def test_header_with_the_loss_functions_is_plain_c(built_lib, tmp_path):
-    """Strict C99, no warnings, no HIP or torch header; a C program that names both functions and both descriptors links
-    against the shared library."""
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not installed")
-    src = tmp_path / "loss_abi.c"
-    src.write_text('#include "pnyolo.h"\n#include <stdio.h>\n'
-                   "int main(void) {\n"
-                   "  pny_rgb_loss_desc r = {0, 1, 0.5f, 2.0f}; pny_yolo_loss_desc y = {3, 2, 1.0f, 20.0f, 1.0f, 1.0f};\n"
-                   "  float terms[5];\n"
-                   "  /* argument errors come back before anything touches a device */\n"
-                   "  int a = pny_rgb_loss(&r, NULL, NULL, NULL, 4, terms, NULL, NULL, NULL);\n"
-                   "  int b = pny_yolo_loss(&y, NULL, NULL, NULL, 4, terms, NULL, NULL, NULL);\n"
-                   '  printf("%d %d %d\\n", a, b, pny_version());\n'
-                   "  return a == PNY_ERR_ARG && b == PNY_ERR_ARG && pny_version() == PNY_ABI_VERSION ? 0 : 1; }\n")
-    exe = tmp_path / "loss_abi"
-    libdir = os.path.dirname(plib.LIB_PATH)
-    cc = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
-                         "-o", str(exe), "-L", libdir, "-lpnyolo", "-Wl,-rpath," + libdir], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    """A C program that names both functions and both descriptors, linked against the shared library: argument errors come
+    back before anything touches a device."""
+    run = c99_program(tmp_path, '#include "pnyolo.h"\n#include <stdio.h>\n'
+                      "int main(void) {\n"
+                      "  pny_rgb_loss_desc r = {0, 1, 0.5f, 2.0f}; pny_yolo_loss_desc y = {3, 2, 1.0f, 20.0f, 1.0f, 1.0f};\n"
+                      "  float terms[5];\n"
+                      "  int a = pny_rgb_loss(&r, NULL, NULL, NULL, 4, terms, NULL, NULL, NULL);\n"
+                      "  int b = pny_yolo_loss(&y, NULL, NULL, NULL, 4, terms, NULL, NULL, NULL);\n"
+                      '  printf("%d %d %d\\n", a, b, pny_version());\n'
+                      "  return a == PNY_ERR_ARG && b == PNY_ERR_ARG && pny_version() == PNY_ABI_VERSION ? 0 : 1; }\n", link=True)()
     assert run.returncode == 0 and run.stdout.split() == ["-1", "-1", "11"], (run.returncode, run.stdout, run.stderr)
 
 

@@ -10,33 +10,22 @@ The view metrics without a GPU (include/pnyolo.h pny_view_metrics, metrics.compa
     bright (0.98 +- 1e-3) pairs -- fp32 sums miss by 1e-6 to 4e-5 there, a different fp64 summation order by about 1e-12 --
     and the byte conversion bit-equal to numpy's on every k / 255, both fp32 neighbours of each, the clamp's cases and
     10 000 uniform draws;
-  * the C ABI: declared, bound, exported, still version 11, still strict C99, bad arguments refused before any launch;
+  * the C ABI: bad arguments refused before any launch (the boundary itself: tests/test_cpu_abi.py);
   * the Python entry points refuse CPU tensors, fp64 tensors, mismatched shapes, H < 7 and an unknown layout by name.
 """
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import metrics_ref as mr
+from host_tools import CSRC, built_lib, header_code, header_text, host_header_program  # noqa: F401
 from pixel_nerf_yolo_amd import lib as plib
 from pixel_nerf_yolo_amd import metrics as pmetrics
 from pixel_nerf_yolo_amd import util as putil
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pixel-nerf-yolo_amd", "csrc")
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(plib.LIB_PATH):
-        plib.build()
-    return plib.load()
 
 
 # --------------------------------------------------------------------------- the restatement against closed forms
@@ -123,21 +112,10 @@ int main(int argc, char** argv) {
 def host_header(tmp_path_factory):
     """csrc/pny_metrics.h compiled by g++: __device__ defined away, no fused multiply-add -- the product's own code, run on
     lines of queries."""
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not installed")
-    tmp = tmp_path_factory.mktemp("metrics_host")
-    src, exe = tmp / "host.cpp", tmp / "host"
-    src.write_text(HOST_MAIN)
-    cc = subprocess.run(["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-D__device__=", "-D__forceinline__=inline", "-I", CSRC,
-                         str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
+    program = host_header_program(tmp_path_factory.mktemp("metrics_host"), HOST_MAIN, include_dirs=(CSRC,))
 
     def run(queries):
-        q = tmp / "queries.txt"
-        q.write_text("".join(line + "\n" for line in queries))
-        out = subprocess.run([str(exe), str(q)], capture_output=True, text=True)
-        assert out.returncode == 0, (out.returncode, out.stderr)
-        lines = out.stdout.strip().split("\n")
+        lines = program(queries)
         assert lines[0].startswith("tile ") and lines[0].split()[3] == "7" and len(lines) == 1 + len(queries)
         return lines[1:]
     return run
@@ -220,48 +198,16 @@ def test_header_ground_truth_and_psnr(host_header):
 
 
 # --------------------------------------------------------------------------- C ABI
-def test_entry_is_declared_bound_and_exported(built_lib):
-    hdr = open(os.path.join(ROOT, "include", "pnyolo.h")).read()
-    assert re.search(r"#define\s+PNY_ABI_VERSION\s+11\b", hdr)
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"\bint\s+pny_view_metrics\s*\(\s*const\s+pny_view_metrics_desc\s*\*", code)
-    res, args = plib.SIGNATURES["pny_view_metrics"]
-    assert res is C.c_int and len(args) == 6
-    assert hasattr(built_lib, "pny_view_metrics")
-    assert built_lib.pny_version() == plib.ABI_VERSION == 11
+def test_entry_is_declared_bound_and_exported():
+    """What is this entry's own (declared, bound, exported, its layout and constants: tests/test_cpu_abi.py)."""
+    hdr = header_text()
+    assert re.search(r"\bint\s+pny_view_metrics\s*\(\s*const\s+pny_view_metrics_desc\s*\*", header_code())
     # the comment of the entry names the reference lines it replaces, as every other entry does
     block = hdr[hdr.index("---- view metrics"):hdr.index("int pny_view_metrics")]
     assert "eval.py:288-345" in block and "calc_metrics.py:189-191" in block and "util.py:502" in block
-    assert re.search(r"#define\s+PNY_GT_NHWC_01\s+0\b", hdr) and re.search(r"#define\s+PNY_GT_NCHW_PM1\s+1\b", hdr)
-    assert plib.GT_LAYOUT == {"nhwc01": 0, "nchw_pm1": 1}
     # the header's tile extents are the ones the GPU tests are built around
     h = open(os.path.join(CSRC, "pny_metrics.h")).read()
     assert re.search(r"METRICS_TILE_H\s*=\s*16\b", h) and re.search(r"METRICS_TILE_W\s*=\s*32\b", h)
-
-
-STRUCT_MAIN = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "pnyolo.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu\n", sizeof(pny_view_metrics_desc), offsetof(pny_view_metrics_desc, height),
-           offsetof(pny_view_metrics_desc, width), offsetof(pny_view_metrics_desc, gt_layout), offsetof(pny_view_metrics_desc, win_size));
-    return 0;
-}
-"""
-
-
-def test_header_is_strict_c99_and_the_mirror_has_its_layout(tmp_path):
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not installed")
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text(STRUCT_MAIN)
-    cc = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
-                         "-o", str(exe)], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True).stdout.split()]
-    D = plib.ViewMetricsDesc
-    assert got == [C.sizeof(D), D.height.offset, D.width.offset, D.gt_layout.offset, D.win_size.offset]
 
 
 def test_bad_arguments_are_refused_before_any_launch(built_lib):

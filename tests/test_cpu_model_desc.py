@@ -10,7 +10,6 @@ something.
     RTOL.  The same for the render-backward cases.
 """
 import ctypes as C
-import os
 
 import pytest
 import torch
@@ -18,18 +17,12 @@ import torch
 import test_gpu_grad_shapes as gs
 import test_gpu_model_desc as md
 from helpers import RTOL
+from host_tools import built_lib  # noqa: F401
 from pixel_nerf_yolo_amd import lib as plib
 from test_gpu_parity import TOL
 
 PNY_ERR_ARG, PNY_ERR_NOGPU = -1, -4
 ADMIT = 0.5 * RTOL
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(plib.LIB_PATH):
-        plib.build()
-    return plib.load()
 
 
 def create(lib, **over):

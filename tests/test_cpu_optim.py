@@ -6,18 +6,15 @@ that tests/test_gpu_optim.py measures the kernel against -- pinned here to torch
 """
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from host_tools import ROOT, built_lib, c99_program, header_code  # noqa: F401
 from pixel_nerf_yolo_amd import lib as plib
 from pixel_nerf_yolo_amd.optim import Adam
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENTRY_POINTS = ("pny_optim_create", "pny_optim_destroy", "pny_optim_add_tensor", "pny_optim_adam_step")
 
 
 # --------------------------------------------------------------------------- the yardstick
@@ -65,39 +62,15 @@ def test_fp64_restatement_is_torch_adam(weight_decay, decay):
 
 
 # --------------------------------------------------------------------------- C ABI
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(plib.LIB_PATH):
-        plib.build()
-    return plib.load()
-
-
 def test_header_declares_the_entry_points_and_keeps_the_abi_version():
-    hdr = open(os.path.join(ROOT, "include", "pnyolo.h")).read()
-    assert re.search(r"#define\s+PNY_ABI_VERSION\s+11\b", hdr)
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name in ENTRY_POINTS:
-        assert re.search(r"\b%s\s*\(" % name, code), name
+    """(Declared, bound, exported, the version and the mirror's layout: tests/test_cpu_abi.py.)"""
+    code = header_code()
     assert "typedef struct pny_optim pny_optim;" in code
     fields = re.search(r"typedef struct pny_adam_hyper \{(.*?)\} pny_adam_hyper;", code, flags=re.S).group(1)
     assert re.sub(r"\s+", " ", fields).strip() == "double lr, beta1, beta2, eps, weight_decay; int64_t step;"
 
 
-def test_lib_signature_table_knows_them():
-    import ctypes as C
-    for name in ENTRY_POINTS:
-        assert name in plib.SIGNATURES, name
-    assert plib.ABI_VERSION == 11
-    assert [f[0] for f in plib.AdamHyper._fields_] == ["lr", "beta1", "beta2", "eps", "weight_decay", "step"]
-    assert C.sizeof(plib.AdamHyper) == 48
-    res, args = plib.SIGNATURES["pny_optim_adam_step"]
-    assert res is C.c_int and len(args) == 7
-
-
 def test_library_exports_them_and_holds_the_kernel(built_lib, tmp_path):
-    for name in ENTRY_POINTS:
-        assert hasattr(built_lib, name), name
-    assert built_lib.pny_version() == 11
     import importlib.util
     spec = importlib.util.spec_from_file_location("check_store_hazard", os.path.join(ROOT, "tools", "check_store_hazard.py"))
     chk = importlib.util.module_from_spec(spec)
@@ -125,18 +98,9 @@ def test_argument_errors_follow_the_convention(built_lib):
 
 
 def test_header_with_the_optimizer_is_plain_c(built_lib, tmp_path):
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not installed")
-    src = tmp_path / "optim_abi.c"
-    src.write_text('#include "pnyolo.h"\n'
-                   "int main(void) { pny_adam_hyper h; pny_optim* o = 0; h.step = 1; h.lr = 1e-3; (void)h;\n"
-                   "  pny_optim_destroy(o); return pny_optim_create(0, 0) == PNY_ERR_ARG ? 0 : 1; }\n")
-    exe = tmp_path / "optim_abi"
-    libdir = os.path.dirname(plib.LIB_PATH)
-    cc = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
-                         "-o", str(exe), "-L", libdir, "-lpnyolo", "-Wl,-rpath," + libdir], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    run = c99_program(tmp_path, '#include "pnyolo.h"\n'
+                      "int main(void) { pny_adam_hyper h; pny_optim* o = 0; h.step = 1; h.lr = 1e-3; (void)h;\n"
+                      "  pny_optim_destroy(o); return pny_optim_create(0, 0) == PNY_ERR_ARG ? 0 : 1; }\n", link=True)()
     assert run.returncode == 0, (run.returncode, run.stdout, run.stderr)
 
 

@@ -4,17 +4,11 @@ oracle's independent restatement of the generator (oracle/pnyolo_oracle.py: phil
 seeded_draws).  No GPU: the published known-answer vectors, the kernels' own header compiled for the host, and the index
 layouts of seeded_draws.  tests/test_gpu_seeded.py holds the kernels to the same restatement.
 """
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 import pnyolo_oracle as orc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pixel-nerf-yolo_amd", "csrc")
+from host_tools import CSRC, host_header_program
 
 # |g_kernel - g_float64| of one Box-Muller normal: the fp32 product 2 pi u2 is off by at most half an ulp of 6.28 (2.4e-7) and
 # enters through |r sin| <= 5.77; accurate logf / sqrtf / cosf add a few ulp of a value below 5.77 (ulp 4.8e-7): about 4e-6.
@@ -58,9 +52,11 @@ HOST_MAIN = r"""
 int main(int argc, char** argv) {
     static const unsigned ids[4] = {pny::STREAM_COARSE, pny::STREAM_FINE, pny::STREAM_FINE2, pny::STREAM_DEPTH};
     printf("streams %u %u %u %u\n", ids[0], ids[1], ids[2], ids[3]);
-    for (int i = 1; i + 2 < argc; i += 3) {
-        const uint64_t seed = strtoull(argv[i], 0, 10), idx = strtoull(argv[i + 2], 0, 10);
-        const uint32_t stream = (uint32_t)strtoul(argv[i + 1], 0, 10);
+    FILE* f = argc > 1 ? fopen(argv[1], "r") : 0;
+    if (!f) return 2;
+    unsigned long long seed, idx;
+    unsigned stream;
+    while (fscanf(f, "%llu %u %llu", &seed, &stream, &idx) == 3) {   // one `seed stream idx` per line
         uint32_t r[4];
         pny::Philox(seed).draw(idx, stream, r);   // the raw words of COUNTER idx
         printf("%08x %08x %08x %08x %a %a\n", r[0], r[1], r[2], r[3], (double)pny::uniform_at(seed, stream, idx),
@@ -76,19 +72,9 @@ def test_kernel_header_on_the_host_equals_the_oracle(tmp_path):
     raw words and uniforms equal the oracle's exactly; the fp32 Box-Muller normal (glibc's logf / cosf / sqrtf here) is within
     NORMAL_ABS_TOL of the float64 value.  Measured: max |g - g64| = 7.9e-7 over the 420 cases (the
     kernels on the MI355X: 1.6e-6 over 5 x 2^16 normals, tests/test_gpu_seeded.py)."""
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not installed")
     (tmp_path / "hip").mkdir()
     (tmp_path / "hip" / "hip_runtime.h").write_text("")
-    src, exe = tmp_path / "rng_host.cpp", tmp_path / "rng_host"
-    src.write_text(HOST_MAIN)
-    cc = subprocess.run(["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-D__device__=", "-D__forceinline__=inline", "-I", str(tmp_path),
-                         "-I", CSRC, str(src), "-o", str(exe), "-lm"], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    args = [str(v) for case in HOST_CASES for v in case]
-    run = subprocess.run([str(exe)] + args, capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr
-    lines = run.stdout.strip().split("\n")
+    lines = host_header_program(tmp_path, HOST_MAIN, include_dirs=(tmp_path, CSRC))(["%d %d %d" % case for case in HOST_CASES])
     assert lines[0] == "streams %d %d %d %d" % (orc.STREAM_COARSE, orc.STREAM_FINE, orc.STREAM_FINE2, orc.STREAM_DEPTH)
     assert len(lines) == 1 + len(HOST_CASES)
     worst = 0.0

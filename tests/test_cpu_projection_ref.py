@@ -5,16 +5,15 @@ magnitude range include/pnyolo.h states for the split arithmetic is the measured
 promises, and the ABI declares the read-out.
 """
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
 import projection_ref as pr
+from host_tools import built_lib, header_text  # noqa: F401
 from pixel_nerf_yolo_amd import lib as plib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HELD_SLACK = 1.1
 
 _ERRS = {}
@@ -26,13 +25,6 @@ def errs(case):
         x, w, r = pr.reference(case)
         _ERRS[case["name"]] = (pr.err(pr.project32(x, w), r), pr.err(pr.project_split(x, w), r), pr.err(pr.split_flushed(x, w), r))
     return _ERRS[case["name"]]
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(plib.LIB_PATH):
-        plib.build()
-    return plib.load()
 
 
 def held(name, measured, recorded):
@@ -114,7 +106,7 @@ def test_split_magnitude_range(K):
     rs = np.random.RandomState(1)
     w0 = rs.standard_normal((512, K)).astype(np.float32)
     x0 = rs.standard_normal((128, K)).astype(np.float32)
-    hdr = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "pnyolo.h")).read())
+    hdr = re.sub(r"\s+", " ", header_text())
     assert "standard deviation 0.05" in hdr and "1.7e-8 / s" in hdr
     for what in ("latent", "weights"):
         ratio = {}
@@ -162,13 +154,7 @@ def test_case_list_covers_the_sweep():
 
 
 def test_abi_declares_the_projection_read_out(built_lib):
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pnyolo.h")).read(), flags=re.S)
-    assert re.search(r"#define\s+PNY_ABI_VERSION\s+11\b", hdr)                     # an addition: the ABI number stays
-    decl = re.search(r"\bpny_scene_projection\s*\(([^;]*)\)\s*;", hdr)
-    assert decl and decl.group(1).count(",") + 1 == 6 == len(plib.SIGNATURES["pny_scene_projection"][1])
-    assert hasattr(built_lib, "pny_scene_projection")
-    assert re.search(r"#define\s+PNY_PROJECTION_ROUTE_TILED_F32\s+%d\b" % pr.ROUTE_TILED_F32, hdr)
-    assert re.search(r"#define\s+PNY_PROJECTION_ROUTE_TILED_F16X2\s+%d\b" % pr.ROUTE_TILED_SPLIT, hdr)
+    """The route codes are the restatement's (they are the header's: tests/test_cpu_abi.py), and a bad call is refused."""
     assert plib.PROJECTION_ROUTE_TILED == {pr.ROUTE_TILED_F32: "f32", pr.ROUTE_TILED_SPLIT: "f16x2"}
     route = C.c_int(-7)
     assert built_lib.pny_scene_projection(None, 0, None, 0, C.byref(route), None) == -1

@@ -15,27 +15,17 @@ The mesh extraction without a GPU (include/pnyolo.h pny_grid_points / pny_mc_*, 
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 import recon_ref as rr
+from host_tools import CSRC, ROOT, built_lib, c99_program, header_code, host_header_program  # noqa: F401
 from pixel_nerf_yolo_amd import lib as plib
 from pixel_nerf_yolo_amd import recon as precon
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pixel-nerf-yolo_amd", "csrc")
 TABLE_H = os.path.join(CSRC, "mc_table.h")
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(plib.LIB_PATH):
-        plib.build()
-    return plib.load()
 
 
 @pytest.fixture(scope="module")
@@ -185,12 +175,14 @@ def test_restated_grid_is_numpys_and_the_origin_has_no_direction():
 HOST_MAIN = r"""
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <vector>
 #include "pny_recon.h"
 #include "mc_table.h"
 using namespace pny;
-// M file     : int32 X Y Z, float iso, X*Y*Z floats  ->  int32 V T, V*3 floats, T*3 int32 (a sequential marching cubes)
-// G file     : int32 X Y Z, 6 doubles c1 c2          ->  X*Y*Z*6 floats (xyz, dirs)
+// one query per input line:
+// M in out   : int32 X Y Z, float iso, X*Y*Z floats  ->  int32 V T, V*3 floats, T*3 int32 (a sequential marching cubes)
+// G in out   : int32 X Y Z, 6 doubles c1 c2          ->  X*Y*Z*6 floats (xyz, dirs)
 // L X Y Z    : prints the workspace layout
 static unsigned cuts(const std::vector<float>& s, int X, int Y, int Z, int x, int y, int z, float iso) {
     const size_t p = ((size_t)x * Y + y) * Z + z;
@@ -201,7 +193,7 @@ static unsigned cuts(const std::vector<float>& s, int X, int Y, int Z, int x, in
     if (z + 1 < Z && mc_inside(s[p + 1], iso) != in) m |= 4u;
     return m;
 }
-int main(int argc, char** argv) {
+static int query(int argc, char** argv) {
     if (argc < 3) return 2;
     if (argv[1][0] == 'L') {
         const McLayout l = mc_layout(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]));
@@ -274,30 +266,35 @@ int main(int argc, char** argv) {
     fclose(o);
     return 0;
 }
+int main(int argc, char** argv) {
+    FILE* f = argc > 1 ? fopen(argv[1], "r") : 0;
+    if (!f) return 2;
+    static char line[4096];
+    while (fgets(line, sizeof line, f)) {
+        char* a[8] = {argv[0]};
+        int n = 1;
+        for (char* t = strtok(line, " \n"); t && n < 8; t = strtok(0, " \n")) a[n++] = t;
+        const int rc = query(n, a);
+        if (rc) return rc;
+    }
+    return 0;
+}
 """
 
 
 @pytest.fixture(scope="module")
 def host_header(tmp_path_factory):
     """csrc/pny_recon.h and csrc/mc_table.h compiled by g++: __host__ / __device__ defined away, no fused multiply-add."""
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not installed")
     tmp = tmp_path_factory.mktemp("recon_host")
-    src, exe = tmp / "host.cpp", tmp / "host"
-    src.write_text(HOST_MAIN)
-    cc = subprocess.run(["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-D__device__=", "-D__host__=", "-D__forceinline__=inline",
-                         "-I", CSRC, str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    return str(exe), tmp
+    return host_header_program(tmp, HOST_MAIN, defines=("__device__=", "__host__=", "__forceinline__=inline"), include_dirs=(CSRC,)), tmp
 
 
 def host_mesh(host_header, field, iso):
-    exe, tmp = host_header
+    run, tmp = host_header
     fin, fout = str(tmp / "in.bin"), str(tmp / "out.bin")
     with open(fin, "wb") as f:
         f.write(np.array(field.shape, dtype=np.int32).tobytes() + np.float32(iso).tobytes() + np.ascontiguousarray(field, dtype=np.float32).tobytes())
-    run = subprocess.run([exe, "M", fin, fout], capture_output=True, text=True)
-    assert run.returncode == 0, (run.returncode, run.stderr)
+    run(["M %s %s" % (fin, fout)])
     raw = open(fout, "rb").read()
     nv, nt = np.frombuffer(raw[:8], dtype=np.int32)
     v = np.frombuffer(raw[8:8 + 12 * nv], dtype=np.float32).reshape(-1, 3)
@@ -327,13 +324,13 @@ def test_header_arithmetic_and_table_give_the_restated_mesh_bit_for_bit(host_hea
 
 
 def test_header_grid_is_numpys_linspace_bit_for_bit(host_header):
-    exe, tmp = host_header
+    run, tmp = host_header
     for c1, c2, reso in (((-1, -0.5, 0.25), (1, 2, 0.75), (5, 4, 3)), ((-1, -1, -1), (1, 1, 1), (3, 3, 3)),
                          ((-0.3, 0.1, -7.7), (0.9, 0.30000001, 1e-3), (128, 7, 33))):
         fin, fout = str(tmp / "g.bin"), str(tmp / "g_out.bin")
         with open(fin, "wb") as f:
             f.write(np.array(reso, dtype=np.int32).tobytes() + np.array(c1 + c2, dtype=np.float64).tobytes())
-        assert subprocess.run([exe, "G", fin, fout]).returncode == 0
+        run(["G %s %s" % (fin, fout)])
         got = np.fromfile(fout, dtype=np.float32).reshape(-1, 6)
         grid = rr.gen_grid(c1, c2, reso)
         assert same_bits(np.ascontiguousarray(got[:, :3]), grid), reso
@@ -341,9 +338,9 @@ def test_header_grid_is_numpys_linspace_bit_for_bit(host_header):
 
 
 def test_workspace_layout(host_header, built_lib):
-    exe, _ = host_header
+    run, _ = host_header
     for dims in ((2, 2, 2), (17, 15, 13), (32, 32, 1024 // 32 + 1), (128, 128, 65), (1024, 1024, 682)):
-        got = [int(v) for v in subprocess.run([exe, "L"] + [str(d) for d in dims], capture_output=True, text=True).stdout.split()]
+        got = [int(v) for v in run(["L %d %d %d" % dims])[0].split()]
         n = dims[0] * dims[1] * dims[2]
         n1 = -(-n // plib.MC_SCAN_TILE)
         n2 = -(-n1 // plib.MC_SCAN_TILE) if n1 > plib.MC_SCAN_TILE else 0
@@ -354,11 +351,9 @@ def test_workspace_layout(host_header, built_lib):
 
 
 # --------------------------------------------------------------------------- the C ABI
-def test_entries_are_declared_bound_and_exported(built_lib):
-    hdr = open(os.path.join(ROOT, "include", "pnyolo.h")).read()
-    assert re.search(r"#define\s+PNY_ABI_VERSION\s+11\b", hdr)
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    flat = re.sub(r"\s+", "", code)
+def test_entries_are_declared_bound_and_exported():
+    """The entries' exact parameter lists (declared, bound, exported, the argument counts: tests/test_cpu_abi.py)."""
+    flat = re.sub(r"\s+", "", header_code())
     decls = {
         "pny_grid_points": ["const double* c1_host", "const double* c2_host", "const int32_t* reso_host", "int64_t i0", "int64_t i1",
                             "float* xyz_dev", "float* dirs_dev", "pny_stream stream"],
@@ -370,9 +365,6 @@ def test_entries_are_declared_bound_and_exported(built_lib):
     }
     for name, args in decls.items():
         assert "int" + name + "(" + ",".join(arg.replace(" ", "") for arg in args) + ");" in flat, name
-        res, argtypes = plib.SIGNATURES[name]
-        assert res is C.c_int and len(argtypes) == len(args) and hasattr(built_lib, name)
-    assert built_lib.pny_version() == plib.ABI_VERSION == 11
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert " recon.hip" in mk and " recon_api.hip" in mk and " pny_recon.h" in mk and " mc_table.h" in mk
 
@@ -391,14 +383,10 @@ int main(void) {
 """
 
 
-def test_header_is_strict_c99(tmp_path):
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not installed")
-    src = tmp_path / "c99.c"
-    src.write_text(C99_MAIN)
-    cc = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                         "-o", str(tmp_path / "c99.o")], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
+def test_header_is_strict_c99(built_lib, tmp_path):
+    """Every entry has exactly the C type a host would write for it."""
+    run = c99_program(tmp_path, C99_MAIN, link=True)()
+    assert run.returncode == 0 and run.stdout.split() == ["1"], (run.returncode, run.stdout, run.stderr)
 
 
 def test_grid_points_refuses_bad_arguments_before_any_launch(built_lib):

@@ -449,18 +449,16 @@ def test_locate_cases_are_robust_and_their_check_holds_on_the_float32_oracle():
 
 
 def test_backward_stage_entry_points_are_declared_and_refuse_on_the_host():
-    """The three stage entry points: declared with the reference lines they restate, bound with the header's argument counts,
-    and every bad argument refused before anything touches a device (so this runs without one)."""
+    """The three stage entry points: declared with the reference lines they restate (bound with the header's argument counts:
+    tests/test_cpu_abi.py), and every bad argument refused before anything touches a device (so this runs without one)."""
     import re
+    from host_tools import header_text
     from pixel_nerf_yolo_amd import lib as plib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hdr = open(os.path.join(root, "include", "pnyolo.h")).read()
-    assert re.search(r"#define\s+PNY_ABI_VERSION\s+11\b", hdr)                     # additions: the ABI number stays
-    for name, n_args, cites in (("pny_yolo_aggregate_backward", 7, "yolo.py:96-114"), ("pny_locate_depth_samples", 11, "nerf.py:156-167"),
-                                ("pny_depth_grad_gather", 7, "nerf.py:156-167")):
+    hdr = header_text()
+    for name, cites in (("pny_yolo_aggregate_backward", "yolo.py:96-114"), ("pny_locate_depth_samples", "nerf.py:156-167"),
+                        ("pny_depth_grad_gather", "nerf.py:156-167")):
         decl = re.search(r"\bint\s+%s\s*\(([^;]*)\)\s*;" % name, hdr)
-        assert decl and decl.group(1).count(",") + 1 == n_args == len(plib.SIGNATURES[name][1]), name
-        assert cites in hdr[hdr.rindex("/*", 0, decl.start()):decl.start()], name
+        assert decl and cites in hdr[hdr.rindex("/*", 0, decl.start()):decl.start()], name
     if not os.path.exists(plib.LIB_PATH):
         plib.build()
     L = plib.load()

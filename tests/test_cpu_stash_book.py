@@ -5,14 +5,10 @@ the flush's weight-gradient GEMM for every set of contributors.
 """
 import itertools
 import os
-import shutil
-import subprocess
 
 import pytest
 
-from pixel_nerf_yolo_amd import lib as plib
-
-CSRC = plib.CSRC
+from host_tools import CSRC, host_header_program
 
 HOST_MAIN = r"""
 #include <cstdio>
@@ -79,22 +75,9 @@ NS = 2
 def book(tmp_path_factory):
     """-> run(commands): the printed lines of a fresh StashBook driven by `commands`.  Nothing but <cstdint> under the header:
     no HIP include path, no defines."""
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not installed")
-    tmp = tmp_path_factory.mktemp("stash_book_host")
-    src, exe = tmp / "host.cpp", tmp / "host"
-    src.write_text(HOST_MAIN)
-    cc = subprocess.run(["g++", "-std=c++14", "-O1", "-Wall", "-Wextra", "-Werror", "-I", CSRC, str(src), "-o", str(exe)],
-                        capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-
-    def run(commands):
-        q = tmp / "commands.txt"
-        q.write_text("".join(line + "\n" for line in commands))
-        out = subprocess.run([str(exe), str(q)], capture_output=True, text=True)
-        assert out.returncode == 0, (out.returncode, out.stderr)
-        return out.stdout.split("\n")[:-1]
-    return run
+    program = host_header_program(tmp_path_factory.mktemp("stash_book_host"), HOST_MAIN, defines=(), include_dirs=(CSRC,),
+                                  extra_flags=("-O1", "-Wall", "-Wextra", "-Werror"))
+    return lambda commands: [line for line in program(commands) if line]
 
 
 def test_header_includes_nothing_but_cstdint():

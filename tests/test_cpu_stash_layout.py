@@ -1,25 +1,23 @@
 """The training stash's layout (pixel-nerf-yolo_amd/csrc/stash.h): a stand-alone host program prints every named slot, and
 the numbers are checked against a transcription of the layout COMMENT of that header (not of its code)."""
 import itertools
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pixel-nerf-yolo_amd", "csrc")
+from host_tools import CSRC, host_header_program
+
 MODELS = [(5, 3), (3, 1000), (2, 0), (4, 1), (7, 3)]   # (n_blocks, combine_layer)
 CONFIGS = [(nb, cl, ns, L) for (nb, cl), ns, L in itertools.product(MODELS, (1, 3), (512, 1792))]
 SLOT, SMALL = 64 * 512, 64 * 64
 
 PROGRAM = r"""
 #include <cstdio>
-#include <cstdlib>
 #include "stash.h"
 int main(int argc, char** argv) {
-    for (int k = 1; k + 3 < argc; k += 4) {
-        const int nb = atoi(argv[k]), cl = atoi(argv[k + 1]), ns = atoi(argv[k + 2]), L = atoi(argv[k + 3]);
+    FILE* f = argc > 1 ? fopen(argv[1], "r") : 0;
+    if (!f) return 2;
+    int nb, cl, ns, L;
+    while (fscanf(f, "%d %d %d %d", &nb, &cl, &ns, &L) == 4) {   // one `n_blocks combine_layer ns L` per line
         const pny::StashLayout l = pny::stash_layout(nb, cl, ns, L);
         const int nvb = l.nvb(), npost = l.npost();
         printf("cfg %d %d %d %d\nnvb %d\nnpost %d\nx_tile %lld\ndy_tile %lld\n", nb, cl, ns, L, nvb, npost, l.x_tile, l.dy_tile);
@@ -70,17 +68,10 @@ def expected(nb, cl, ns, L):
 
 @pytest.fixture(scope="module")
 def printed(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not installed")
-    d = tmp_path_factory.mktemp("stash")
-    src, exe = d / "stash_print.cpp", d / "stash_print"
-    src.write_text(PROGRAM)
-    cc = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", CSRC, str(src), "-o", str(exe)],
-                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert cc.returncode == 0, cc.stdout
-    run = subprocess.run([str(exe)] + [str(a) for c in CONFIGS for a in c], stdout=subprocess.PIPE, text=True, check=True)
+    program = host_header_program(tmp_path_factory.mktemp("stash"), PROGRAM, std="c++17", defines=(), include_dirs=(CSRC,),
+                                  extra_flags=("-O0", "-Wall", "-Wextra", "-Werror"))
     out, cur = {}, None
-    for line in run.stdout.splitlines():
+    for line in program(["%d %d %d %d" % c for c in CONFIGS]):
         k, *vals = line.split()
         if k == "cfg":
             cur = out.setdefault(tuple(int(t) for t in vals), {})

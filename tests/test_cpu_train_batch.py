@@ -1,8 +1,8 @@
 """
 The training batch sampler without a GPU (include/pnyolo.h pny_sample_train_batch, util.sample_train_batch):
 
-  * the C ABI: the header declares the entry, lib.SIGNATURES holds it, the built library exports it, the ABI is still 11,
-    the ctypes mirrors have the C structs' layout, and bad arguments come back as PNY_ERR_ARG before anything is launched;
+  * the C ABI: bad arguments come back as PNY_ERR_ARG before anything is launched (the boundary itself:
+    tests/test_cpu_abi.py);
   * the kernel's own pixel arithmetic (csrc/pny_train_batch.h compiled by g++, the way tests/test_cpu_philox.py compiles
     pny_rng.h) gives exactly the (view, y, x) the reference's trainer chose for the draws recorded in
     tests/golden/train_batch.npz (tools/make_train_batch_golden.py);
@@ -10,73 +10,30 @@ The training batch sampler without a GPU (include/pnyolo.h pny_sample_train_batc
     with a non-zero high word, a draw index beyond 2^32 - 1, n = 1, 2, 819 200 and 2^31.
 """
 import ctypes as C
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import pnyolo_oracle as orc
+from host_tools import CSRC, built_lib, header_code, header_text, host_header_program  # noqa: F401
 import train_batch_ref as tb
 from pixel_nerf_yolo_amd import lib as plib
 from pixel_nerf_yolo_amd import util as putil
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pixel-nerf-yolo_amd", "csrc")
 CASES = ("a_uni", "a_box", "b_uni", "b_box")
 
 
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(plib.LIB_PATH):
-        plib.build()
-    return plib.load()
-
-
 # --------------------------------------------------------------------------- C ABI
-def test_entry_is_declared_bound_and_exported(built_lib):
-    hdr = open(os.path.join(ROOT, "include", "pnyolo.h")).read()
-    assert re.search(r"#define\s+PNY_ABI_VERSION\s+11\b", hdr)
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"\bint\s+pny_sample_train_batch\s*\(\s*const\s+pny_train_batch_desc\s*\*", code)
-    assert "pny_sample_train_batch" in plib.SIGNATURES
-    res, args = plib.SIGNATURES["pny_sample_train_batch"]
-    assert res is C.c_int and len(args) == 11
-    assert hasattr(built_lib, "pny_sample_train_batch")
-    assert built_lib.pny_version() == plib.ABI_VERSION == 11
+def test_entry_is_declared_bound_and_exported():
+    """What is this entry's own (declared, bound, exported, its mirrors' layout: tests/test_cpu_abi.py)."""
+    hdr = header_text()
+    assert re.search(r"\bint\s+pny_sample_train_batch\s*\(\s*const\s+pny_train_batch_desc\s*\*", header_code())
     # the comment of the entry names the reference lines it replaces, as every other entry does
     block = hdr[:hdr.index("int pny_sample_train_batch")]
     block = block[block.rindex("pny_gen_rays_range"):]
     assert "PixelNerfTrainer.py:76-123" in block and "util.py:222-237" in block
-
-
-STRUCT_MAIN = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "pnyolo.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(pny_train_batch_desc), offsetof(pny_train_batch_desc, n_rays),
-           offsetof(pny_train_batch_desc, z_near), offsetof(pny_train_batch_desc, c_rows), offsetof(pny_train_batch_desc, seed),
-           offsetof(pny_train_batch_desc, draw_offset), sizeof(pny_train_batch_draws));
-    return 0;
-}
-"""
-
-
-def test_ctypes_mirrors_have_the_c_layout(tmp_path):
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not installed")
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text(STRUCT_MAIN)
-    cc = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
-                         "-o", str(exe)], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True).stdout.split()]
-    D, R = plib.TrainBatchDesc, plib.TrainBatchDraws
-    assert got == [C.sizeof(D), D.n_rays.offset, D.z_near.offset, D.c_rows.offset, D.seed.offset, D.draw_offset.offset, C.sizeof(R)]
 
 
 def test_bad_arguments_are_refused_before_any_launch(built_lib):
@@ -163,23 +120,13 @@ int main(int argc, char** argv) {
 def host_header(tmp_path_factory):
     """csrc/pny_train_batch.h (and pny_rng.h under it) compiled by g++: an empty hip/hip_runtime.h, __device__ defined away,
     no fused multiply-add -- the product's own code, run on lines of queries."""
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not installed")
     tmp = tmp_path_factory.mktemp("train_batch_host")
     (tmp / "hip").mkdir()
     (tmp / "hip" / "hip_runtime.h").write_text("")
-    src, exe = tmp / "host.cpp", tmp / "host"
-    src.write_text(HOST_MAIN)
-    cc = subprocess.run(["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-D__device__=", "-D__forceinline__=inline", "-I", str(tmp),
-                         "-I", CSRC, str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
+    program = host_header_program(tmp, HOST_MAIN, include_dirs=(tmp, CSRC))
 
     def run(queries):
-        q = tmp / "queries.txt"
-        q.write_text("".join(line + "\n" for line in queries))
-        out = subprocess.run([str(exe), str(q)], capture_output=True, text=True)
-        assert out.returncode == 0, (out.returncode, out.stderr)
-        lines = out.stdout.strip().split("\n")
+        lines = program(queries)
         assert lines[0] == "streams 5 6 7 8" and len(lines) == 1 + len(queries)
         return lines[1:]
     return run

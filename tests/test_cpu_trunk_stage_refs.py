@@ -4,27 +4,16 @@ behind the bars still hold, every bar stays under the whole-trunk bound it sits 
 is F.batch_norm (forward and autograd, float64), F.max_pool2d's backward sends a tied window's gradient to the first maximum in
 scan order, and the case lists cover what the sweep promises.
 """
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as Fn
 
 import trunk_stage_ref as tr
-from pixel_nerf_yolo_amd import lib as plib
+from host_tools import built_lib  # noqa: F401
 
 F32, F64 = tr.F32, tr.F64
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HELD_SLACK = 1.1    # a float32 convolution may be blocked otherwise on another CPU or build: the last digit may move
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(plib.LIB_PATH):
-        plib.build()
-    return plib.load()
 
 
 def held(name, measured, recorded):
@@ -269,14 +258,8 @@ def test_case_lists_cover_the_sweep(built_lib):
 
 
 def test_abi_declares_the_trunk_stage_entries(built_lib):
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pnyolo.h")).read(), flags=re.S)
-    assert re.search(r"#define\s+PNY_ABI_VERSION\s+11\b", hdr)                     # additions: the ABI number stays
-    for name, n_args in (("pny_trunk_unit", 6), ("pny_trunk_conv", 16), ("pny_trunk_conv_dw", 10), ("pny_trunk_bn_forward", 15),
-                         ("pny_trunk_bn_backward", 14), ("pny_trunk_maxpool", 7), ("pny_trunk_maxpool_backward", 9),
-                         ("pny_trunk_upsample", 9), ("pny_trunk_upsample_backward", 10)):
-        decl = re.search(r"\b%s\s*\(([^;]*)\)\s*;" % name, hdr)
-        assert decl and decl.group(1).count(",") + 1 == n_args == len(plib.SIGNATURES[name][1]), name
-        assert hasattr(built_lib, name)
+    """(Declared, bound and exported with the header's argument counts: tests/test_cpu_abi.py.)  pny_trunk_unit refuses an index
+    outside the table."""
     assert built_lib.pny_trunk_unit(len(tr.table(built_lib)), None, None, None, None, None) == -1
     assert b"pny_trunk_unit" in built_lib.pny_last_error()
     assert built_lib.pny_trunk_unit(-1, None, None, None, None, None) == -1

@@ -1,8 +1,7 @@
 """
 The YOLO training batch without a GPU (include/pnyolo.h pny_yolo_train_batch, util.yolo_train_batch / stage_yolo_targets):
 
-  * the C ABI: the header declares the entry and cites what it replaces, lib.SIGNATURES holds it, the built library exports
-    it, the ABI is still 11, the ctypes mirror has the C struct's layout, the header compiles as strict C99;
+  * the header declares the entry and cites what it replaces (the boundary itself: tests/test_cpu_abi.py);
   * every bad argument comes back as PNY_ERR_ARG before anything is launched (the device pointers here are made up and are
     never dereferenced);
   * the offsets the entry reports (its size query: no launch) equal the reference's for the three cases of
@@ -11,71 +10,26 @@ The YOLO training batch without a GPU (include/pnyolo.h pny_yolo_train_batch, ut
   * the numpy restatement of the row order (tests/yolo_batch_ref.py) agrees with the fixture.
 """
 import ctypes as C
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import yolo_batch_ref as yb
+from host_tools import built_lib, header_code, header_text  # noqa: F401
 from pixel_nerf_yolo_amd import lib as plib
 from pixel_nerf_yolo_amd import util as putil
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(plib.LIB_PATH):
-        plib.build()
-    return plib.load()
-
 
 # --------------------------------------------------------------------------- C ABI
-def test_entry_is_declared_bound_and_exported(built_lib):
-    hdr = open(os.path.join(ROOT, "include", "pnyolo.h")).read()
-    assert re.search(r"#define\s+PNY_ABI_VERSION\s+11\b", hdr)
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"\bint\s+pny_yolo_train_batch\s*\(\s*const\s+pny_yolo_batch_desc\s*\*", code)
-    res, args = plib.SIGNATURES["pny_yolo_train_batch"]
-    assert res is C.c_int and len(args) == 10
-    assert hasattr(built_lib, "pny_yolo_train_batch")
-    assert built_lib.pny_version() == plib.ABI_VERSION == 11
+def test_entry_is_declared_bound_and_exported():
+    """What is this entry's own (declared, bound, exported, its layout and limits: tests/test_cpu_abi.py)."""
+    hdr = header_text()
+    assert re.search(r"\bint\s+pny_yolo_train_batch\s*\(\s*const\s+pny_yolo_batch_desc\s*\*", header_code())
     block = hdr[:hdr.index("int pny_yolo_train_batch")]
     block = block[block.rindex("int pny_sample_train_batch"):]
     assert "YoloTrainer.py:93-129" in block and "util.py:808-876" in block
-    assert (plib.YOLO_BATCH_MAX_VIEWS, plib.YOLO_BATCH_MAX_SCALES) == (16, 4)
-    assert re.search(r"#define\s+PNY_YOLO_BATCH_MAX_VIEWS\s+16\b", hdr) and re.search(r"#define\s+PNY_YOLO_BATCH_MAX_SCALES\s+4\b", hdr)
-
-
-STRUCT_MAIN = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "pnyolo.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(pny_yolo_batch_desc), offsetof(pny_yolo_batch_desc, n_views),
-           offsetof(pny_yolo_batch_desc, n_scales), offsetof(pny_yolo_batch_desc, cell_sizes), offsetof(pny_yolo_batch_desc, n_anchors),
-           offsetof(pny_yolo_batch_desc, z_near), offsetof(pny_yolo_batch_desc, z_far));
-    return 0;
-}
-"""
-
-
-def test_ctypes_mirror_has_the_c_layout_and_the_header_is_c99(tmp_path):
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not installed")
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text(STRUCT_MAIN)
-    cc = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
-                         "-o", str(exe)], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True).stdout.split()]
-    D = plib.YoloBatchDesc
-    assert got == [C.sizeof(D), D.n_views.offset, D.n_scales.offset, D.cell_sizes.offset, D.n_anchors.offset, D.z_near.offset,
-                   D.z_far.offset]
 
 
 # --------------------------------------------------------------------------- argument checks

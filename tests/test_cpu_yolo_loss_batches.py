@@ -6,10 +6,7 @@ the summed losses, and what the Python layer refuses.
 """
 import ctypes as C
 import inspect
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,21 +14,13 @@ import torch
 
 import loss_batches_ref
 import loss_ref
+from host_tools import built_lib, c99_program, header_code  # noqa: F401
 from pixel_nerf_yolo_amd import lib as plib
 from pixel_nerf_yolo_amd import loss as ploss
 from pixel_nerf_yolo_amd import util as putil
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_FUNCTIONS = ("pny_yolo_loss_batches", "pny_yolo_loss_batches_count")
 # (rows per scale, batch_rows, M)
 COUNT_CASES = [((1,), 1, 1), ((5,), 2, 3), ((165,), 128, 2), ((7, 3), 4, 3), ((64, 16, 4, 1), 64, 4)]
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(plib.LIB_PATH):
-        plib.build()
-    return plib.load()
 
 
 def batches(rows, batch_rows, n_scales=None):
@@ -40,40 +29,26 @@ def batches(rows, batch_rows, n_scales=None):
 
 
 # --------------------------------------------------------------------------- the ABI
-def test_header_declares_and_library_exports_the_functions(built_lib):
-    hdr = open(os.path.join(ROOT, "include", "pnyolo.h")).read()
-    assert re.search(r"#define\s+PNY_ABI_VERSION\s+11\b", hdr)
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+def test_header_declares_and_library_exports_the_functions():
+    """The types of the descriptors' slots (declared, bound, exported, the mirror's layout: tests/test_cpu_abi.py)."""
+    code = header_code()
     assert re.search(r"\bint\s+pny_yolo_loss_batches\s*\(\s*const\s+pny_yolo_loss_desc\s*\*\s*\w+\s*,\s*const\s+pny_yolo_batches_desc\s*\*", code)
     assert re.search(r"\bint\s+pny_yolo_loss_batches_count\s*\(\s*const\s+pny_yolo_batches_desc\s*\*", code)
     assert re.search(r"typedef\s+struct\s+pny_yolo_batches_desc\s*\{[^}]*int32_t\s+n_scales;[^}]*int32_t\s+batch_rows;[^}]*int64_t\s+rows\[4\];[^}]*\}", code)
-    for name in NEW_FUNCTIONS:
-        assert name in plib.SIGNATURES and hasattr(built_lib, name), name + " is not exported"
-    assert C.sizeof(plib.YoloBatchesDesc) == 40
-    assert built_lib.pny_version() == plib.ABI_VERSION == 11
 
 
 def test_header_with_the_functions_is_plain_c(built_lib, tmp_path):
-    """Strict C99, no warnings; a C program that names the descriptor and both functions links against the shared library,
-    and a NULL call comes back with PNY_ERR_ARG before anything touches a device."""
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not installed")
-    src = tmp_path / "loss_batches_abi.c"
-    src.write_text('#include "pnyolo.h"\n#include <stdio.h>\n'
-                   "int main(void) {\n"
-                   "  pny_yolo_loss_desc y = {3, 2, 1.0f, 20.0f, 1.0f, 1.0f};\n"
-                   "  pny_yolo_batches_desc b = {2, 4, {7, 3, 0, 0}};\n"
-                   "  float terms[15], step[6];\n"
-                   "  int a = pny_yolo_loss_batches(&y, &b, NULL, NULL, NULL, terms, NULL, step, NULL, NULL);\n"
-                   "  int m = pny_yolo_loss_batches_count(&b);\n"
-                   '  printf("%d %d %d\\n", a, m, pny_version());\n'
-                   "  return a == PNY_ERR_ARG && m == 3 && pny_version() == PNY_ABI_VERSION ? 0 : 1; }\n")
-    exe = tmp_path / "loss_batches_abi"
-    libdir = os.path.dirname(plib.LIB_PATH)
-    cc = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
-                         "-o", str(exe), "-L", libdir, "-lpnyolo", "-Wl,-rpath," + libdir], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    """A C program that names the descriptor and both functions links against the shared library, and a NULL call comes back
+    with PNY_ERR_ARG before anything touches a device."""
+    run = c99_program(tmp_path, '#include "pnyolo.h"\n#include <stdio.h>\n'
+                      "int main(void) {\n"
+                      "  pny_yolo_loss_desc y = {3, 2, 1.0f, 20.0f, 1.0f, 1.0f};\n"
+                      "  pny_yolo_batches_desc b = {2, 4, {7, 3, 0, 0}};\n"
+                      "  float terms[15], step[6];\n"
+                      "  int a = pny_yolo_loss_batches(&y, &b, NULL, NULL, NULL, terms, NULL, step, NULL, NULL);\n"
+                      "  int m = pny_yolo_loss_batches_count(&b);\n"
+                      '  printf("%d %d %d\\n", a, m, pny_version());\n'
+                      "  return a == PNY_ERR_ARG && m == 3 && pny_version() == PNY_ABI_VERSION ? 0 : 1; }\n", link=True)()
     assert run.returncode == 0 and run.stdout.split() == ["-1", "3", "11"], (run.returncode, run.stdout, run.stderr)
 
 
