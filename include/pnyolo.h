@@ -405,6 +405,41 @@ int pny_detect_views(const pny_detect_views_desc* desc, const float* const* pred
                      float* highest_conf_dev, int64_t* totals_dev, float* kept_targets_dev, float* kept_preds_dev,
                      pny_stream stream);
 
+/* The three thresholds of a YOLO metric pass SWEPT in ONE launch: the integers of pny_detect_views at every setting of a grid
+ * NMS IoU x confidence cut x match IoU, on a render that is made once.  The reference has one setting per pass:
+ * YoloTrainer.metric_step (train/trainlib/YoloTrainer.py:338-354) scores at the config's nms_iou_threshold, nms_threshold and
+ * match_iou_threshold, eval/eval_yolo.py runs the test loader again for another setting, and eval/gen_images_yolo.py:110-117 asks
+ * for nms_threshold and nms_iou_threshold on stdin and encodes and renders again for every answer.  util.nms (src/util/util.py:691-722)
+ * removes rows from the list it iterates over, so the kept lists at one (cut, NMS IoU) do not follow from those at another: one
+ * 256-thread workgroup per (view, NMS IoU i, cut t) -- grid = n_views * n_nms_ious * n_conf_cuts -- runs the device code of
+ * pny_detect_views for its view at its two values (csrc/pny_detect_views_core.h: one copy), in the same LDS map.  The match IoU
+ * enters util.calculate_tp_fp_fn (util.py:765-802; the whole tail is util.py:691-797) only through the last comparison: the best
+ * IoU of every kept prediction over the kept targets, and of every kept target over the kept predictions, is computed once
+ * (util.py:776-797) and compared with all n_match_ious values: tp = predictions with best > m, fp = kept predictions - tp,
+ * fn = targets with best < m; without a kept target (0, kept predictions, 0), without a kept prediction (0, 0, kept targets).
+ * Setting (i, t, m) gives the integers pny_detect_views gives at nms_iou = nms_ious_host[i], nms_threshold = conf_cuts_host[t],
+ * match_iou = match_ious_host[m]: cuts are compared in double, the IoUs rounded to fp32 once on the host, as there.
+ * One kernel enqueued on `stream`; the thresholds travel by value in its arguments: no allocation, no copy, no
+ * synchronisation; anchors_host and the three threshold arrays are read before the call returns.
+ *
+ * desc and the eight input pointers: as pny_detect_views, with the same checks.  desc->nms_iou, nms_threshold and match_iou are
+ * ignored; desc->max_kept must be 0 (a sweep keeps no boxes: pny_detect_views at the chosen setting gives them).
+ * Limits: 1 <= n_nms_ious <= 8, 1 <= n_conf_cuts <= 32, 1 <= n_match_ious <= 8, every value finite; order and duplicates are the
+ * caller's.  Outputs, in C order:
+ *   counts_dev (n_views, n_nms_ious, n_conf_cuts, n_match_ious, 3) int32: tp, fp, fn;
+ *   lists_dev  (n_views, n_nms_ious, n_conf_cuts, 3) int32: kept targets, kept predictions, status (0, or PNY_DETECT_* bits);
+ *   totals_dev (n_nms_ious, n_conf_cuts, n_match_ious, 4) int64: tp, fp, fn, refused views.  The call ADDS to them.
+ * A (view, setting) is refused when more than PNY_DETECT_MAX_CANDIDATES boxes of one of its lists pass the filters at that cut,
+ * or when the view's segment is bad: never truncated, its counts and kept counts are 0, it adds nothing to tp, fp, fn and 1 to
+ * the refused word of every m of its (i, t).  The same view may be scored at a higher cut.
+ * PNY_ERR_ARG, before any launch, pny_last_error naming the argument: what pny_detect_views refuses, a NULL output or threshold
+ * array, a count outside its limits, a value that is not finite, max_kept != 0, 2^31 or more workgroups. */
+int pny_detect_sweep(const pny_detect_views_desc* desc, const float* const* preds_dev, const float* const* targets_dev,
+                     const float* anchors_host, const float* pred_rows_dev, const int32_t* pred_offsets_dev,
+                     const float* target_rows_dev, const int32_t* target_offsets_dev, const double* nms_ious_host,
+                     int32_t n_nms_ious, const double* conf_cuts_host, int32_t n_conf_cuts, const double* match_ious_host,
+                     int32_t n_match_ious, int32_t* counts_dev, int32_t* lists_dev, int64_t* totals_dev, pny_stream stream);
+
 /* Latent projection.  `x = x + lin_z[b](z)` (src/model/resnetfc.py:176-182) with z the bilinear
  * interpolation of the latent (src/model/encoder.py:101) is linear in the latent, so
  * lin_z[b](interp(latent)) == interp(lin_z[b](latent)) up to fp32 rounding: with projection ON the

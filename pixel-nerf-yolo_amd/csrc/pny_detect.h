@@ -1,8 +1,11 @@
 // Device arithmetic shared by the YOLO detection tail's kernels: the per-image ones of detect.hip (pny_cells_to_bboxes,
 // pny_nms, pny_tp_fp_fn) and the batched scorer of detect_views.hip (pny_detect_views).  One copy of the box decode and of the
 // IoU, so that the batched counts equal the per-view path's by construction.  Also the batched kernel's argument block and its
-// LDS map.
+// LDS map, and the argument block of the threshold sweep (detect_sweep.hip, pny_detect_sweep), which runs the batched kernel's
+// device code (pny_detect_views_core.h) at a grid of settings.
 #pragma once
+#include <string>
+
 #include "pny_common.h"
 
 namespace pny {
@@ -103,5 +106,31 @@ constexpr size_t detect_lds_bytes(int cap) {
 static_assert(detect_lds_bytes(DETECT_MAXC) <= 160 * 1024, "PNY_DETECT_MAX_CANDIDATES must fit gfx950's 160 KB of LDS");
 
 void launch_detect_views(const DetectViewsArgs& a, size_t lds_bytes, hipStream_t st);
+
+// Host side of both entries (detect_views.hip): form and n_views; then geometry or rows, the eight input pointers and `cap`
+// into *a.  PNY_OK, or PNY_ERR_ARG with pny_last_error = who + the field.
+int detect_check_form(const std::string& who, const pny_detect_views_desc* desc);
+int detect_fill_inputs(const std::string& who, const pny_detect_views_desc* desc, const float* const* preds_dev,
+                       const float* const* targets_dev, const float* anchors_host, const float* pred_rows_dev,
+                       const int32_t* pred_offsets_dev, const float* target_rows_dev, const int32_t* target_offsets_dev,
+                       DetectViewsArgs* a);
+
+// ------------------------------------------------------------------ pny_detect_sweep (detect_sweep.hip)
+// The limits of a sweep (include/pnyolo.h states them in pny_detect_sweep's comment, lib.py as DETECT_SWEEP_MAX_*): they bound
+// the thresholds that travel by value in the kernel arguments (8 + 8 floats, 32 doubles and 32 bytes: 352 bytes).
+constexpr int DETECT_SWEEP_MAX_NMS_IOUS = 8, DETECT_SWEEP_MAX_CUTS = 32, DETECT_SWEEP_MAX_MATCH_IOUS = 8;
+
+struct DetectSweepArgs {
+    DetectViewsArgs in;                              // lists, geometry, cap, totals; its thresholds, per_view, highest_conf, kept unused
+    int n_nms, n_cuts, n_match;                      // I, T, M
+    float nms_ious[DETECT_SWEEP_MAX_NMS_IOUS];       // rounded to fp32 once on the host, as DetectViewsArgs::nms_iou
+    float match_ious[DETECT_SWEEP_MAX_MATCH_IOUS];
+    double cuts[DETECT_SWEEP_MAX_CUTS];              // compared in double, as DetectViewsArgs::nms_thr
+    unsigned char cut_order[DETECT_SWEEP_MAX_CUTS];  // the cuts' indices, lowest cut first: the order in which the grid takes them
+    int32_t* counts;                                 // (V, I, T, M, 3)
+    int32_t* lists;                                  // (V, I, T, 3)
+};
+
+void launch_detect_sweep(const DetectSweepArgs& s, size_t lds_bytes, hipStream_t st);
 
 }  // namespace pny

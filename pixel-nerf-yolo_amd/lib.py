@@ -172,6 +172,9 @@ SIGNATURES = {
     "pny_detect_views": (C.c_int, [C.POINTER(DetectViewsDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_float_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    "pny_detect_sweep": (C.c_int, [C.POINTER(DetectViewsDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_float_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.c_int32,
+                                   C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pny_scene_set_projection": (C.c_int, [C.c_void_p, C.c_int]),
     "pny_scene_set_precision": (C.c_int, [C.c_void_p, C.c_int]),
     "pny_scene_bind_latent_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -293,6 +296,12 @@ DETECT_MAX_CANDIDATES, DETECT_MAX_ANCHORS = 2048, 4
 DETECT_CELLS, DETECT_BOXES = 0, 1
 DETECT_RECORD = ("tp", "fp", "fn", "kept_targets", "kept_preds", "targets_above", "preds_above", "status")
 DETECT_TARGETS_OVERFLOW, DETECT_PREDS_OVERFLOW, DETECT_BAD_SEGMENT = 1, 2, 4
+# pny_detect_sweep: the most NMS IoUs, confidence cuts and match IoUs of one sweep (the header states them in its comment), and
+# the columns of its three outputs
+DETECT_SWEEP_MAX_NMS_IOUS, DETECT_SWEEP_MAX_CUTS, DETECT_SWEEP_MAX_MATCH_IOUS = 8, 32, 8
+DETECT_SWEEP_COUNTS = ("tp", "fp", "fn")
+DETECT_SWEEP_LISTS = ("kept_targets", "kept_preds", "status")
+DETECT_SWEEP_TOTALS = ("tp", "fp", "fn", "refused")
 MC_SCAN_TILE, MC_MAX_POINTS = 1024, (2 ** 31 - 1) // 3        # csrc/pny_recon.h: points per scan tile; 3 X Y Z < 2^31
 MAX_LATENT_LEVELS = 8                                         # PNY_MAX_LATENT_LEVELS
 # bits of the `accumulate` argument of the backward calls and of pny_model_flush_weight_grads (include/pnyolo.h)

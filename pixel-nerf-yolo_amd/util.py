@@ -488,46 +488,128 @@ class DetectionScores:
         self.kept_targets, self.kept_preds = kept_targets, kept_preds
 
 
-def _detect_fail(msg, exc=ValueError):
-    raise exc("pixel_nerf_yolo_amd.util.score_detections: " + msg)
+def _detect_fail(msg, exc=ValueError, who="score_detections"):
+    raise exc("pixel_nerf_yolo_amd.util.%s: %s" % (who, msg))
 
 
-def _detect_tensor(t, name, dev):
+def _detect_tensor(t, name, dev, who="score_detections"):
     """A float32 tensor on the GPU, contiguous (a copy on the device if it was not)."""
     if not torch.is_tensor(t):
-        _detect_fail("%s must be a torch tensor, got %s" % (name, type(t).__name__), TypeError)
+        _detect_fail("%s must be a torch tensor, got %s" % (name, type(t).__name__), TypeError, who=who)
     if t.dtype != torch.float32:
-        _detect_fail("%s must be float32, got %s" % (name, t.dtype), TypeError)
+        _detect_fail("%s must be float32, got %s" % (name, t.dtype), TypeError, who=who)
     if t.device.type != "cuda":
         _detect_fail("%s is on %s; the scorer runs on an MI355X only (the host path is calculate_tp_fp_fn per view)"
-                     % (name, t.device), _lib.PnyError)
+                     % (name, t.device), _lib.PnyError, who=who)
     if dev is not None and t.device != dev:
-        _detect_fail("%s is on %s, the other inputs on %s" % (name, t.device, dev))
+        _detect_fail("%s is on %s, the other inputs on %s" % (name, t.device, dev), who=who)
     return t.detach().contiguous()
 
 
-def _detect_offsets(off, name, n_rows, n_views):
+def _detect_offsets(off, name, n_rows, n_views, who="score_detections"):
     """(V + 1) int32 offsets.  A host tensor / list is checked here (starts at 0, ascends, ends inside the rows) and copied over;
     a device tensor is used in place and checked by the kernel (a bad segment is a refused view)."""
     if torch.is_tensor(off) and off.device.type == "cuda":
         if off.dtype != torch.int32 or off.dim() != 1:
-            _detect_fail("%s on the device must be a 1-d int32 tensor, got %s %s" % (name, off.dtype, tuple(off.shape)), TypeError)
+            _detect_fail("%s on the device must be a 1-d int32 tensor, got %s %s" % (name, off.dtype, tuple(off.shape)), TypeError, who=who)
         if n_views is not None and off.numel() != n_views + 1:
-            _detect_fail("%s must hold n_views + 1 = %d entries, got %d" % (name, n_views + 1, off.numel()))
+            _detect_fail("%s must hold n_views + 1 = %d entries, got %d" % (name, n_views + 1, off.numel()), who=who)
         return off.contiguous(), None
     o = torch.as_tensor(off)
     if o.dim() != 1 or o.numel() < 2 or o.dtype.is_floating_point or o.dtype == torch.bool:
-        _detect_fail("%s must be a 1-d integer sequence of V + 1 entries, got %s %s" % (name, o.dtype, tuple(o.shape)))
+        _detect_fail("%s must be a 1-d integer sequence of V + 1 entries, got %s %s" % (name, o.dtype, tuple(o.shape)), who=who)
     if n_views is not None and o.numel() != n_views + 1:
-        _detect_fail("%s must hold n_views + 1 = %d entries, got %d" % (name, n_views + 1, o.numel()))
+        _detect_fail("%s must hold n_views + 1 = %d entries, got %d" % (name, n_views + 1, o.numel()), who=who)
     v = o.to(torch.int64).tolist()
     if v[0] != 0:
-        _detect_fail("%s must start at 0, got %d" % (name, v[0]))
+        _detect_fail("%s must start at 0, got %d" % (name, v[0]), who=who)
     if any(b < a for a, b in zip(v, v[1:])):
-        _detect_fail("%s must ascend, got %s" % (name, v if len(v) <= 20 else v[:20] + ["..."]))
+        _detect_fail("%s must ascend, got %s" % (name, v if len(v) <= 20 else v[:20] + ["..."]), who=who)
     if v[-1] > n_rows:
-        _detect_fail("%s ends at %d, past the %d rows" % (name, v[-1], n_rows))
+        _detect_fail("%s ends at %d, past the %d rows" % (name, v[-1], n_rows), who=who)
     return o.to(torch.int32), max(b - a for a, b in zip(v, v[1:]))
+
+
+def _detect_inputs(who, preds, targets, anchors, height, width, cell_sizes, n_views, boxes):
+    """The inputs of ``score_detections`` and ``sweep_detections``, validated once: -> (desc with the form, the view count and the
+    geometry or row counts, the device, the eight input arguments of pny_detect_views / pny_detect_sweep, the boxes of the longest
+    list, what must stay alive until the launch is enqueued)."""
+    dev = None
+    keep = []
+    desc = _lib.DetectViewsDesc()
+    p_ptrs = t_ptrs = anc_ptr = None
+    rows = [None, None]
+    offs = [None, None]
+    if boxes is not None:
+        if preds is not None or targets is not None:
+            _detect_fail("give either preds / targets (cells) or boxes=, not both", who=who)
+        if len(boxes) != 4:
+            _detect_fail("boxes must be (pred_rows, pred_offsets, target_rows, target_offsets)", who=who)
+        longest = 0
+        checked = []
+        for i, name in ((0, "pred"), (2, "target")):
+            r = boxes[i]
+            if not torch.is_tensor(r) or r.dim() != 2 or r.shape[1] != 6:
+                _detect_fail("%s_rows must be a (n, 6) tensor, got %s" % (name, tuple(r.shape) if torch.is_tensor(r) else type(r).__name__), who=who)
+            o, seg = _detect_offsets(boxes[i + 1], name + "_offsets", r.shape[0], n_views, who=who)
+            if n_views is None:
+                n_views = o.numel() - 1
+            elif o.numel() != n_views + 1:
+                _detect_fail("%s_offsets must hold n_views + 1 = %d entries, got %d" % (name, n_views + 1, o.numel()), who=who)
+            longest = max(longest, r.shape[0] if seg is None else seg)
+            checked.append((r, o, name))
+        for k, (r, o, name) in enumerate(checked):
+            rows[k] = _detect_tensor(r, name + "_rows", dev, who=who)
+            dev = rows[k].device
+            offs[k] = o if o.device == dev else o.to(dev, non_blocking=True)
+        desc.form, desc.n_views = _lib.DETECT_BOXES, int(n_views)
+        desc.n_pred_rows, desc.n_target_rows = rows[0].shape[0], rows[1].shape[0]
+    else:
+        if preds is None or targets is None:
+            _detect_fail("preds and targets (one tensor per scale), or boxes=, are required", who=who)
+        preds, targets = list(preds), list(targets)
+        cells = [int(v) for v in cell_sizes]
+        if not 1 <= len(cells) <= _lib.YOLO_BATCH_MAX_SCALES:
+            _detect_fail("cell_sizes must hold 1 .. %d scales, got %d" % (_lib.YOLO_BATCH_MAX_SCALES, len(cells)), who=who)
+        if len(preds) != len(cells) or len(targets) != len(cells):
+            _detect_fail("one prediction and one target tensor per scale: %d scales, %d preds, %d targets" % (len(cells), len(preds), len(targets)), who=who)
+        anc = torch.as_tensor(anchors, dtype=torch.float32).detach().cpu()
+        if anc.dim() == 3 and anc.shape[0] == len(cells) and anc.shape[2] == 2:
+            anc = anc.reshape(-1, 2)
+        if anc.dim() != 2 or anc.shape[1] != 2 or anc.shape[0] == 0 or anc.shape[0] % len(cells):
+            _detect_fail("anchors must be (num_scales * A, 2) with %d scale%s, got %s" % (len(cells), "" if len(cells) == 1 else "s", tuple(anc.shape)), who=who)
+        A = anc.shape[0] // len(cells)
+        if A > _lib.DETECT_MAX_ANCHORS:
+            _detect_fail("at most %d anchors per scale, got %d" % (_lib.DETECT_MAX_ANCHORS, A), who=who)
+        anc = anc.contiguous()
+        height, width = int(height), int(width)
+        if n_views is None or int(n_views) < 1:
+            _detect_fail("n_views (the views in the lists) must be given and positive, got %r" % (n_views,), who=who)
+        n_views = int(n_views)
+        longest = 0
+        for s, cell in enumerate(cells):
+            if not 1 <= cell <= min(height, width):
+                _detect_fail("cell_sizes[%d] = %d must be 1 .. min(height, width)" % (s, cell), who=who)
+            per = (height // cell) * (width // cell)
+            longest += per * A
+            for t, name, cols in ((preds[s], "preds", 7), (targets[s], "targets", 6)):
+                if not torch.is_tensor(t) or t.dim() != 3:
+                    _detect_fail("%s[%d] must be a (n_views * Hs * Ws, A, %d) tensor, got %s"
+                                 % (name, s, cols, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__), who=who)
+                if tuple(t.shape) != (n_views * per, A, cols):
+                    _detect_fail("%s[%d] must be (n_views * Hs * Ws, A, %d) = %s, got %s" % (name, s, cols, (n_views * per, A, cols), tuple(t.shape)), who=who)
+        for s in range(len(cells)):
+            preds[s] = _detect_tensor(preds[s], "preds[%d]" % s, dev, who=who)
+            dev = preds[s].device
+            targets[s] = _detect_tensor(targets[s], "targets[%d]" % s, dev, who=who)
+        desc.form, desc.n_views, desc.n_scales, desc.height, desc.width = _lib.DETECT_CELLS, n_views, len(cells), height, width
+        desc.cell_sizes, desc.n_anchors = (C.c_int32 * 4)(*cells), A
+        p_ptrs = (C.c_void_p * len(cells))(*[t.data_ptr() for t in preds])
+        t_ptrs = (C.c_void_p * len(cells))(*[t.data_ptr() for t in targets])
+        anc_ptr = C.cast(anc.data_ptr(), _lib.c_float_p)
+        keep = [preds, targets, anc]
+    vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+    return desc, dev, (p_ptrs, t_ptrs, anc_ptr, vp(rows[0]), vp(offs[0]), vp(rows[1]), vp(offs[1])), longest, [keep, rows, offs]
 
 
 def score_detections(preds, targets, anchors, height, width, cell_sizes, nms_iou, nms_t, match_iou, n_views=None, totals=None,
@@ -554,80 +636,8 @@ def score_detections(preds, targets, anchors, height, width, cell_sizes, nms_iou
     At most ``lib.DETECT_MAX_CANDIDATES`` (2048) boxes of one list of one view may pass the confidence and size filters; a view
     above that is refused, not truncated: its status is non-zero and it counts in totals[3] alone.
     """
-    dev = None
-    keep = []
-    desc = _lib.DetectViewsDesc(nms_iou=float(nms_iou), nms_threshold=float(nms_t), match_iou=float(match_iou))
-    p_ptrs = t_ptrs = anc_ptr = None
-    rows = [None, None]
-    offs = [None, None]
-    if boxes is not None:
-        if preds is not None or targets is not None:
-            _detect_fail("give either preds / targets (cells) or boxes=, not both")
-        if len(boxes) != 4:
-            _detect_fail("boxes must be (pred_rows, pred_offsets, target_rows, target_offsets)")
-        longest = 0
-        checked = []
-        for i, name in ((0, "pred"), (2, "target")):
-            r = boxes[i]
-            if not torch.is_tensor(r) or r.dim() != 2 or r.shape[1] != 6:
-                _detect_fail("%s_rows must be a (n, 6) tensor, got %s" % (name, tuple(r.shape) if torch.is_tensor(r) else type(r).__name__))
-            o, seg = _detect_offsets(boxes[i + 1], name + "_offsets", r.shape[0], n_views)
-            if n_views is None:
-                n_views = o.numel() - 1
-            elif o.numel() != n_views + 1:
-                _detect_fail("%s_offsets must hold n_views + 1 = %d entries, got %d" % (name, n_views + 1, o.numel()))
-            longest = max(longest, r.shape[0] if seg is None else seg)
-            checked.append((r, o, name))
-        for k, (r, o, name) in enumerate(checked):
-            rows[k] = _detect_tensor(r, name + "_rows", dev)
-            dev = rows[k].device
-            offs[k] = o if o.device == dev else o.to(dev, non_blocking=True)
-        desc.form, desc.n_views = _lib.DETECT_BOXES, int(n_views)
-        desc.n_pred_rows, desc.n_target_rows = rows[0].shape[0], rows[1].shape[0]
-    else:
-        if preds is None or targets is None:
-            _detect_fail("preds and targets (one tensor per scale), or boxes=, are required")
-        preds, targets = list(preds), list(targets)
-        cells = [int(v) for v in cell_sizes]
-        if not 1 <= len(cells) <= _lib.YOLO_BATCH_MAX_SCALES:
-            _detect_fail("cell_sizes must hold 1 .. %d scales, got %d" % (_lib.YOLO_BATCH_MAX_SCALES, len(cells)))
-        if len(preds) != len(cells) or len(targets) != len(cells):
-            _detect_fail("one prediction and one target tensor per scale: %d scales, %d preds, %d targets" % (len(cells), len(preds), len(targets)))
-        anc = torch.as_tensor(anchors, dtype=torch.float32).detach().cpu()
-        if anc.dim() == 3 and anc.shape[0] == len(cells) and anc.shape[2] == 2:
-            anc = anc.reshape(-1, 2)
-        if anc.dim() != 2 or anc.shape[1] != 2 or anc.shape[0] == 0 or anc.shape[0] % len(cells):
-            _detect_fail("anchors must be (num_scales * A, 2) with %d scale%s, got %s" % (len(cells), "" if len(cells) == 1 else "s", tuple(anc.shape)))
-        A = anc.shape[0] // len(cells)
-        if A > _lib.DETECT_MAX_ANCHORS:
-            _detect_fail("at most %d anchors per scale, got %d" % (_lib.DETECT_MAX_ANCHORS, A))
-        anc = anc.contiguous()
-        height, width = int(height), int(width)
-        if n_views is None or int(n_views) < 1:
-            _detect_fail("n_views (the views in the lists) must be given and positive, got %r" % (n_views,))
-        n_views = int(n_views)
-        longest = 0
-        for s, cell in enumerate(cells):
-            if not 1 <= cell <= min(height, width):
-                _detect_fail("cell_sizes[%d] = %d must be 1 .. min(height, width)" % (s, cell))
-            per = (height // cell) * (width // cell)
-            longest += per * A
-            for t, name, cols in ((preds[s], "preds", 7), (targets[s], "targets", 6)):
-                if not torch.is_tensor(t) or t.dim() != 3:
-                    _detect_fail("%s[%d] must be a (n_views * Hs * Ws, A, %d) tensor, got %s"
-                                 % (name, s, cols, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
-                if tuple(t.shape) != (n_views * per, A, cols):
-                    _detect_fail("%s[%d] must be (n_views * Hs * Ws, A, %d) = %s, got %s" % (name, s, cols, (n_views * per, A, cols), tuple(t.shape)))
-        for s in range(len(cells)):
-            preds[s] = _detect_tensor(preds[s], "preds[%d]" % s, dev)
-            dev = preds[s].device
-            targets[s] = _detect_tensor(targets[s], "targets[%d]" % s, dev)
-        desc.form, desc.n_views, desc.n_scales, desc.height, desc.width = _lib.DETECT_CELLS, n_views, len(cells), height, width
-        desc.cell_sizes, desc.n_anchors = (C.c_int32 * 4)(*cells), A
-        p_ptrs = (C.c_void_p * len(cells))(*[t.data_ptr() for t in preds])
-        t_ptrs = (C.c_void_p * len(cells))(*[t.data_ptr() for t in targets])
-        anc_ptr = C.cast(anc.data_ptr(), _lib.c_float_p)
-        keep = [preds, targets, anc]
+    desc, dev, inputs, longest, keep = _detect_inputs("score_detections", preds, targets, anchors, height, width, cell_sizes, n_views, boxes)
+    desc.nms_iou, desc.nms_threshold, desc.match_iou = float(nms_iou), float(nms_t), float(match_iou)
     if totals is None:
         totals = torch.zeros(4, device=dev, dtype=torch.int64)
     elif not (torch.is_tensor(totals) and totals.dtype == torch.int64 and tuple(totals.shape) == (4,) and totals.device == dev
@@ -643,8 +653,7 @@ def score_detections(preds, targets, anchors, height, width, cell_sizes, nms_iou
         kp = torch.zeros(V, desc.max_kept, 6, device=dev, dtype=torch.float32)
     vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
     with torch.cuda.device(dev):
-        check(_lib.load().pny_detect_views(C.byref(desc), p_ptrs, t_ptrs, anc_ptr, vp(rows[0]), vp(offs[0]), vp(rows[1]), vp(offs[1]),
-                                           vp(per_view), vp(hc), vp(totals), vp(kt), vp(kp), stream_of(dev)))
+        check(_lib.load().pny_detect_views(C.byref(desc), *inputs, vp(per_view), vp(hc), vp(totals), vp(kt), vp(kp), stream_of(dev)))
     del keep
     return DetectionScores(per_view, hc, totals, kt, kp)
 
@@ -684,3 +693,145 @@ class DetectionMeter:
                                 "status of every update names them" % (failed, " was" if failed == 1 else "s were",
                                                                        _lib.DETECT_MAX_CANDIDATES))
         return calculate_precision_recall_f1(tp, fp, fn) if prf else (tp, fp, fn)
+
+
+# ------------------------------------------------------------------ YOLO metric pass: its three thresholds swept in one launch
+class DetectionSweep:
+    """What ``sweep_detections`` leaves on the device; nothing here has been read by the host.  With V views and
+    I = len(nms_ious), T = len(nms_ts), M = len(match_ious), in C order:
+
+    counts (V, I, T, M, 3) int32: tp, fp, fn of the view at setting (nms_ious[i], nms_ts[t], match_ious[m]);
+    lists (V, I, T, 3) int32: kept targets, kept predictions, status (0, or ``lib.DETECT_*`` bits: refused at that cut, counts 0);
+    totals (I, T, M, 4) int64: tp, fp, fn, refused views -- the tensor the call added to;
+    nms_ious, nms_ts, match_ious: the three tuples as given."""
+
+    def __init__(self, counts, lists, totals, nms_ious, nms_ts, match_ious):
+        self.counts, self.lists, self.totals = counts, lists, totals
+        self.nms_ious, self.nms_ts, self.match_ious = nms_ious, nms_ts, match_ious
+
+
+def _sweep_thresholds(who, nms_ious, nms_ts, match_ious):
+    """The three threshold arguments as tuples of floats, order and duplicates kept; ValueError naming the argument for an empty
+    or too long list or a value that is not finite.  Touches no tensor and no library: it runs first."""
+    out = []
+    for name, values, most in (("nms_ious", nms_ious, _lib.DETECT_SWEEP_MAX_NMS_IOUS), ("nms_ts", nms_ts, _lib.DETECT_SWEEP_MAX_CUTS),
+                               ("match_ious", match_ious, _lib.DETECT_SWEEP_MAX_MATCH_IOUS)):
+        if isinstance(values, (int, float)):
+            values = (values,)
+        try:
+            values = tuple(float(v) for v in values)
+        except (TypeError, ValueError):
+            _detect_fail("%s must be a float or a sequence of floats, got %r" % (name, values), who=who)
+        if not 1 <= len(values) <= most:
+            _detect_fail("%s must hold 1 .. %d values, got %d" % (name, most, len(values)), who=who)
+        for k, v in enumerate(values):
+            if v != v or v in (float("inf"), float("-inf")):
+                _detect_fail("%s[%d] = %r must be finite" % (name, k, v), who=who)
+        out.append(values)
+    return tuple(out)
+
+
+def sweep_detections(preds, targets, anchors, height, width, cell_sizes, nms_ious, nms_ts, match_ious, n_views=None, totals=None,
+                     boxes=None, _who="sweep_detections"):
+    """
+    The detection counts of all views of a YOLO metric step at EVERY setting of a grid of thresholds, in ONE launch
+    (include/pnyolo.h pny_detect_sweep): setting (i, t, m) holds the integers ``score_detections`` gives at
+    (nms_ious[i], nms_ts[t], match_ious[m]), on a render that is made once.  The reference scores one setting per pass
+    (eval/eval_yolo.py) and asks for the next on stdin (eval/gen_images_yolo.py:110-117), with an encode and a render each time.
+    The call returns as soon as the kernel is enqueued and reads nothing.
+
+    :param preds, targets, anchors, height, width, cell_sizes, n_views, boxes as ``score_detections`` takes them
+    :param nms_ious (util.nms iou_threshold), nms_ts (util.nms threshold, the confidence cut), match_ious: each a float or a
+           sequence of floats: at most ``lib.DETECT_SWEEP_MAX_NMS_IOUS`` (8), ``lib.DETECT_SWEEP_MAX_CUTS`` (32) and
+           ``lib.DETECT_SWEEP_MAX_MATCH_IOUS`` (8), all finite; order and duplicates are kept.  Checked before anything else.
+    :param totals a contiguous (I, T, M, 4) int64 device tensor to ADD to (``DetectionSweepMeter`` owns one); None: a fresh one
+    :return DetectionSweep of device tensors
+
+    A view with more than ``lib.DETECT_MAX_CANDIDATES`` boxes of one list past the filters at a cut is refused at that cut, not
+    truncated: its status there is non-zero, its counts are 0 and it counts in totals[i, t, :, 3] alone.  Kept boxes are not part
+    of a sweep: ``score_detections(..., want_boxes=True)`` at the chosen setting gives them.
+    """
+    nms_ious, nms_ts, match_ious = _sweep_thresholds(_who, nms_ious, nms_ts, match_ious)
+    desc, dev, inputs, _, keep = _detect_inputs(_who, preds, targets, anchors, height, width, cell_sizes, n_views, boxes)
+    shape = (len(nms_ious), len(nms_ts), len(match_ious))
+    if totals is None:
+        totals = torch.zeros(*shape, 4, device=dev, dtype=torch.int64)
+    elif not (torch.is_tensor(totals) and totals.dtype == torch.int64 and tuple(totals.shape) == shape + (4,) and totals.device == dev
+              and totals.is_contiguous()):
+        _detect_fail("totals must be a contiguous %s int64 tensor on %s" % (shape + (4,), dev), who=_who)
+    V = desc.n_views
+    counts = torch.empty(V, *shape, 3, device=dev, dtype=torch.int32)
+    lists = torch.empty(V, shape[0], shape[1], 3, device=dev, dtype=torch.int32)
+    arr = lambda v: (C.c_double * len(v))(*v)   # noqa: E731
+    vp = lambda t: C.c_void_p(t.data_ptr())     # noqa: E731
+    with torch.cuda.device(dev):
+        check(_lib.load().pny_detect_sweep(C.byref(desc), *inputs, arr(nms_ious), shape[0], arr(nms_ts), shape[1], arr(match_ious), shape[2],
+                                           vp(counts), vp(lists), vp(totals), stream_of(dev)))
+    del keep
+    return DetectionSweep(counts, lists, totals, nms_ious, nms_ts, match_ious)
+
+
+class DetectionSweepReport:
+    """A sweep's totals on the host (``DetectionSweepMeter.report``), every array (I, T, M) over nms_ious x nms_ts x match_ious:
+
+    tp, fp, fn, refused: numpy int64;
+    precision, recall, f1: float64 by ``calculate_precision_recall_f1`` on the setting's three integers, NaN where views were
+    refused at the setting (its sums miss them)."""
+
+    def __init__(self, totals, nms_ious, nms_ts, match_ious):
+        import numpy as np
+        self.nms_ious, self.nms_ts, self.match_ious = tuple(nms_ious), tuple(nms_ts), tuple(match_ious)
+        shape = (len(self.nms_ious), len(self.nms_ts), len(self.match_ious))
+        totals = np.ascontiguousarray(totals, dtype=np.int64)
+        if totals.shape != shape + (4,):
+            raise ValueError("pixel_nerf_yolo_amd.util.DetectionSweepReport: totals must be %s, got %s" % (shape + (4,), totals.shape))
+        self.tp, self.fp, self.fn, self.refused = (totals[..., k].copy() for k in range(4))
+        self.precision, self.recall, self.f1 = (np.full(shape, np.nan, np.float64) for _ in range(3))
+        for idx in np.ndindex(*shape):
+            if not self.refused[idx]:
+                self.precision[idx], self.recall[idx], self.f1[idx] = calculate_precision_recall_f1(
+                    int(self.tp[idx]), int(self.fp[idx]), int(self.fn[idx]))
+
+    def best(self):
+        """(nms_iou, nms_t, match_iou, precision, recall, f1) of the highest F1 among the settings without refused views; the
+        first such setting in C order on a tie.  PnyError when every setting has refused views."""
+        import numpy as np
+        ok = self.refused == 0
+        if not ok.any():
+            raise _lib.PnyError("pixel_nerf_yolo_amd.util.DetectionSweepReport.best: all %d settings have refused views (%d refusals "
+                                "of a view at a setting in all: more than %d candidates in one list of a view, or a bad segment)"
+                                % (ok.size, int(self.refused.sum()), _lib.DETECT_MAX_CANDIDATES))
+        i, t, m = np.unravel_index(int(np.argmax(np.where(ok, self.f1, -np.inf))), ok.shape)    # argmax: the first maximum
+        return (self.nms_ious[i], self.nms_ts[t], self.match_ious[m], float(self.precision[i, t, m]), float(self.recall[i, t, m]),
+                float(self.f1[i, t, m]))
+
+
+class DetectionSweepMeter:
+    """
+    The running tp / fp / fn of a YOLO metric pass at every setting of a grid of thresholds: ``update`` is ``sweep_detections``
+    adding into the meter's own (I, T, M, 4) device words -- one launch, no read -- and ``report`` is the pass's ONE
+    device-to-host read: the precision / recall / F1 table from which the operating point is picked.
+
+        meter = DetectionSweepMeter(device, nms_ious=(0.45, 0.6, 0.75), nms_ts=[0.05 * k for k in range(1, 17)], match_ious=(0.2, 0.5))
+        for batch in test_loader:  meter.update(renders, target_cells, anchors, H, W, cell_sizes, n_views=NS)
+        table = meter.report();  nms_iou, nms_t, match_iou, precision, recall, f1 = table.best();  meter.reset()
+    """
+
+    def __init__(self, device, nms_ious, nms_ts, match_ious):
+        self.nms_ious, self.nms_ts, self.match_ious = _sweep_thresholds("DetectionSweepMeter", nms_ious, nms_ts, match_ious)
+        self.device = _device_of(torch.empty(0), device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.totals = torch.zeros(len(self.nms_ious), len(self.nms_ts), len(self.match_ious), 4, device=self.device, dtype=torch.int64)
+
+    def update(self, preds, targets, anchors, height, width, cell_sizes, n_views=None, boxes=None):
+        """``sweep_detections(...)`` at the meter's thresholds into its totals -> its DetectionSweep (still on the device)."""
+        return sweep_detections(preds, targets, anchors, height, width, cell_sizes, self.nms_ious, self.nms_ts, self.match_ious,
+                                n_views=n_views, totals=self.totals, boxes=boxes, _who="DetectionSweepMeter.update")
+
+    def reset(self):
+        self.totals.zero_()
+
+    def report(self):
+        """The DetectionSweepReport of everything added since the last reset."""
+        return DetectionSweepReport(self.totals.cpu().numpy(), self.nms_ious, self.nms_ts, self.match_ious)
