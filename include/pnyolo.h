@@ -1107,6 +1107,59 @@ int pny_yolo_build_targets(const pny_yolo_targets_desc* desc, const double* boxe
                            const int32_t* n_boxes_dev /* (NV) */, const float* anchors_host /* (n_scales * A, 2) */,
                            float* const* targets_dev /* n_scales pointers, (NV, Hs, Ws, A, 6) */, pny_stream stream);
 
+/* ---- resident views: a dataset's decoded views stay on the device as bytes, and a training step's ray batch, ground truth
+ * and source views are drawn straight from them (csrc/resident.hip; arithmetic in csrc/pny_resident.h, shared with
+ * pny_ingest_views and pny_sample_train_batch).  Replaces what runs per step on the host before the trainer starts: the
+ * reference's SRNDataset.__getitem__ (src/data/SRNDataset.py:61-136) and DVRDataset.__getitem__ (src/data/DVRDataset.py:110-275)
+ * decode, normalise and resize ALL views of every object of the super-batch, the DataLoader copies them to the device, and
+ * train/trainlib/PixelNerfTrainer.py:76-133 then reads ray_batch_size pixels and at most three source views per object from
+ * them.  The caller owns the store; these entries only read it.
+ *
+ * The store: one decoded geometry (height, width, channels = 3 or 4, of which the first three bytes of a pixel are used) and
+ * one output geometry (out_height, out_width, resize = PNY_RESIZE_*, as pny_ingest_views has them).  objs_dev is a device
+ * table of n_store_objs 16-byte records
+ *     { const uint8_t* views;   (n_views, height, width, channels) bytes of the object, on the device
+ *       int32_t n_views;        1 .. max_views; objects may differ
+ *       int32_t first_row; }    the object's first row of poses_dev and bboxes_dev
+ * poses_dev (n_rows, 4, 4) cam->world and bboxes_dev (n_rows, 4) `cmin rmin cmax rmax` at output resolution (or NULL: uniform
+ * mode) hold the views of all objects one after another; focal_dev (n_store_objs, 2) fx fy and c_dev (n_store_objs, 2) (or
+ * NULL: (out_width / 2, out_height / 2)) are at output resolution.  All offsets are 64-bit.
+ *
+ * Both entries take raw device pointers and enqueue ONE kernel on `stream`: no allocation, no copy, no synchronisation, no
+ * atomics; the same input gives the same bits on every run.  The call cannot look at device-side indices without waiting, so
+ * the kernels clamp them into range (memory safety, as for replayed draws): an object id into [0, n_store_objs), a view id
+ * into [0, n_views), a record's n_views into [1, max_views], its first_row into [0, n_rows - n_views], a draw as
+ * pny_sample_train_batch clamps it.
+ *
+ * pny_resident_train_batch: share s of the batch is object obj_ids_dev[s] (repeats allowed).  Of `desc` it reads n_objs = SB,
+ * n_views = max_views (the largest n_views of the store: the bound the draw's limit is checked against), height, width =
+ * the DECODED size, n_rays = B, z_near, z_far, seed and draw_offset; focal_rows, focal_cols and c_rows are ignored (focal_dev
+ * and c_dev have one row per store object).  Share s has the bits that pny_sample_train_batch gives for a ONE-object call
+ * with draw_offset + s * B (or with rows s of `draws`) on pny_ingest_views(store resize) of that object's views, with its
+ * poses, focal, c and boxes; the object's own n_views enters the draws as NV does there.  rgb_gt_dev = v * 0.5f + 0.5f with v
+ * the fp32 pny_ingest_views writes at that output pixel, computed for the sampled pixel only.  Writes rays_dev (SB, B, 8)
+ * 16-byte aligned, rgb_gt_dev (SB, B, 3) and, unless NULL, pix_dev (SB, B, 3) int32 [view within the object, y, x] at output
+ * resolution.
+ *
+ * pny_ingest_views_indexed: pny_ingest_views without white_mask whose output view i is view view_of_dev[i] of object
+ * obj_of_dev[i] of the store: out_dev (desc->n_views, 3, out_height, out_width), bit-equal to pny_ingest_views on the gathered
+ * views.  desc->white_mask must be 0.
+ *
+ * PNY_ERR_ARG, before any launch, naming the argument: a NULL required pointer; a non-positive size or count; channels not 3
+ * or 4; an unknown resize; out size != size under PNY_RESIZE_NONE; max_views * out_height * out_width >= 2^32 (the draw's
+ * limit); 2^31 or more rays, bytes in a view, or output elements; a replay without the draws its mode reads; rays_dev not
+ * 16-byte aligned; white_mask set. */
+int pny_resident_train_batch(const pny_train_batch_desc* desc, int32_t channels, int32_t out_height, int32_t out_width,
+                             int32_t resize, const void* objs_dev /* n_store_objs records */, int32_t n_store_objs,
+                             const int32_t* obj_ids_dev /* (SB) */, const float* poses_dev /* (n_rows, 4, 4) */, int64_t n_rows,
+                             const float* focal_dev /* (n_store_objs, 2) */, const float* c_dev /* (n_store_objs, 2) or NULL */,
+                             const float* bboxes_dev /* (n_rows, 4) or NULL */, const pny_train_batch_draws* draws,
+                             float* rays_dev, float* rgb_gt_dev, int32_t* pix_dev, pny_stream stream);
+int pny_ingest_views_indexed(const pny_ingest_desc* desc, const void* objs_dev /* n_store_objs records */, int32_t n_store_objs,
+                             int32_t max_views, const int32_t* obj_of_dev /* (n_views) */,
+                             const int32_t* view_of_dev /* (n_views) */, float* out_dev /* (n_views, 3, OH, OW) */,
+                             pny_stream stream);
+
 /* ---- mesh extraction: the sigma grid and marching cubes of the reference's src/util/recon.py on the device (csrc/recon.hip;
  * conventions and arithmetic in csrc/pny_recon.h, the case table in csrc/mc_table.h, generated by tools/gen_mc_table.py).
  * Model-free, raw device pointers, enqueued on `stream`: no allocation, no copy, no synchronisation, no atomics; the same

@@ -30,21 +30,8 @@
 namespace pny {
 namespace {
 
-struct Px {
-    uint32_t r, g, b;
-};
-
 // the three bytes at p, through aligned dword loads
-__device__ __forceinline__ Px load_px(const uint8_t* p) {
-    const uintptr_t a = (uintptr_t)p;
-    const unsigned sh = (unsigned)(a & 3);
-    const uint32_t* q = (const uint32_t*)(a - sh);
-    uint32_t v = q[0] >> (8 * sh);
-    if (sh > 1) v |= q[1] << (32 - 8 * sh);        // bytes sh .. sh + 2 run into the next dword
-    Px px;
-    px.r = v & 255u, px.g = (v >> 8) & 255u, px.b = (v >> 16) & 255u;
-    return px;
-}
+__device__ __forceinline__ IngestPx load_px(const uint8_t* p) { return IngestLoadDwords()(p); }
 
 __global__ __launch_bounds__(INGEST_TILE_X* INGEST_TILE_Y) void ingest_kernel(IngestArgs a) {
     const unsigned per_view = (unsigned)a.tiles_x * (unsigned)a.tiles_y;
@@ -53,42 +40,11 @@ __global__ __launch_bounds__(INGEST_TILE_X* INGEST_TILE_Y) void ingest_kernel(In
     const int x = tx * INGEST_TILE_X + (int)threadIdx.x, y = ty * INGEST_TILE_Y + (int)threadIdx.y;
     if (x >= a.ow || y >= a.oh) return;
     const uint8_t* img = a.in + (size_t)view * a.h * a.w * a.c;
-    const size_t row_bytes = (size_t)a.w * a.c;
     const size_t plane = (size_t)a.oh * a.ow;
     const size_t o = (size_t)y * a.ow + x;
     float* out = a.out + (size_t)view * 3 * plane + o;
-    float r, g, b, m = 0.0f;
-    if (a.resize == INGEST_RESIZE_NONE) {
-        const Px p = load_px(img + (size_t)y * row_bytes + (size_t)x * a.c);
-        r = ingest_byte_map(p.r), g = ingest_byte_map(p.g), b = ingest_byte_map(p.b);
-        m = ingest_white_mask(p.r, p.g, p.b);
-    } else if (a.resize == INGEST_RESIZE_BILINEAR_U8) {
-        int y0, y1, x0, x1;
-        float ly, lx;
-        ingest_bilinear_taps(y, a.scale_y, a.h, y0, y1, ly);
-        ingest_bilinear_taps(x, a.scale_x, a.w, x0, x1, lx);
-        const uint8_t *r0 = img + (size_t)y0 * row_bytes, *r1 = img + (size_t)y1 * row_bytes;
-        const Px p00 = load_px(r0 + (size_t)x0 * a.c), p01 = load_px(r0 + (size_t)x1 * a.c);
-        const Px p10 = load_px(r1 + (size_t)x0 * a.c), p11 = load_px(r1 + (size_t)x1 * a.c);
-        r = ingest_byte_map(ingest_bilinear_u8(p00.r, p01.r, p10.r, p11.r, lx, ly));
-        g = ingest_byte_map(ingest_bilinear_u8(p00.g, p01.g, p10.g, p11.g, lx, ly));
-        b = ingest_byte_map(ingest_bilinear_u8(p00.b, p01.b, p10.b, p11.b, lx, ly));
-    } else {
-        int ys, ye, xs, xe;
-        ingest_area_window(y, a.h, a.oh, ys, ye);
-        ingest_area_window(x, a.w, a.ow, xs, xe);
-        r = g = b = 0.0f;
-        for (int yy = ys; yy < ye; ++yy) {
-            const uint8_t* row = img + (size_t)yy * row_bytes;
-            for (int xx = xs; xx < xe; ++xx) {
-                const Px p = load_px(row + (size_t)xx * a.c);
-                r += ingest_byte_map(p.r), g += ingest_byte_map(p.g), b += ingest_byte_map(p.b);
-                m += ingest_white_mask(p.r, p.g, p.b);
-            }
-        }
-        const float count = (float)((ye - ys) * (xe - xs));
-        r = r / count, g = g / count, b = b / count, m = m / count;
-    }
+    float r, g, b, m;
+    ingest_pixel(img, a, y, x, IngestLoadDwords(), r, g, b, m);
     out[0] = r, out[plane] = g, out[2 * plane] = b;
     if (a.mask) a.mask[(size_t)view * plane + o] = m;
 }
@@ -102,7 +58,7 @@ __global__ __launch_bounds__(INGEST_BOX_THREADS) void ingest_box_kernel(IngestBo
     int cmin = a.w, rmin = a.h, cmax = -1, rmax = -1;
 #pragma unroll 4
     for (unsigned i = (unsigned)tid; i < hw; i += INGEST_BOX_THREADS) {     // consecutive lanes, consecutive pixels
-        const Px p = load_px(img + (size_t)i * a.c);
+        const IngestPx p = load_px(img + (size_t)i * a.c);
         if (ingest_white_mask(p.r, p.g, p.b) != 0.0f) {
             const int y = (int)(i / (unsigned)a.w), x = (int)(i - (unsigned)y * (unsigned)a.w);
             cmin = min(cmin, x), cmax = max(cmax, x);

@@ -11,6 +11,7 @@
 // runs it without a GPU.
 #pragma once
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace pny {
@@ -57,6 +58,75 @@ __host__ __device__ inline uint32_t ingest_bilinear_u8(uint32_t a, uint32_t b, u
 __host__ __device__ inline void ingest_area_window(int i, int in, int out, int& start, int& end) {
     start = (int)(((int64_t)i * in) / out);
     end = (int)((((int64_t)i + 1) * in + out - 1) / out);
+}
+
+// ---- one output pixel of the ingest, for ingest_kernel (ingest.hip) and the resident store's kernels (resident.hip)
+struct IngestPx {
+    uint32_t r, g, b;
+};
+
+// the three bytes at p, one byte load each (the host's loader; any alignment, nothing beyond the pixel is read)
+struct IngestLoadBytes {
+    __host__ __device__ inline IngestPx operator()(const uint8_t* p) const {
+        IngestPx px;
+        px.r = p[0], px.g = p[1], px.b = p[2];
+        return px;
+    }
+};
+
+// the three bytes at p, through the one or two ALIGNED dwords that hold them (the kernels' loader): both dwords hold at least
+// one byte of the pixel, so they lie in pages the buffer owns
+struct IngestLoadDwords {
+    __host__ __device__ inline IngestPx operator()(const uint8_t* p) const {
+        const uintptr_t a = (uintptr_t)p;
+        const unsigned sh = (unsigned)(a & 3);
+        const uint32_t* q = (const uint32_t*)(a - sh);
+        uint32_t v = q[0] >> (8 * sh);
+        if (sh > 1) v |= q[1] << (32 - 8 * sh);        // bytes sh .. sh + 2 run into the next dword
+        IngestPx px;
+        px.r = v & 255u, px.g = (v >> 8) & 255u, px.b = (v >> 16) & 255u;
+        return px;
+    }
+};
+
+// Output pixel (y, x) of the view at img (H, W, C bytes): r g b as pny_ingest_views writes them and the mask value m (none and
+// area only; 0 under bilinear).  Geom carries h, w, c, oh, ow, resize, scale_y, scale_x (IngestArgs, ResidentGeom).
+template <class Geom, class Load>
+__host__ __device__ inline void ingest_pixel(const uint8_t* img, const Geom& a, int y, int x, Load load, float& r, float& g,
+                                             float& b, float& m) {
+    const size_t row_bytes = (size_t)a.w * a.c;
+    m = 0.0f;
+    if (a.resize == INGEST_RESIZE_NONE) {
+        const IngestPx p = load(img + (size_t)y * row_bytes + (size_t)x * a.c);
+        r = ingest_byte_map(p.r), g = ingest_byte_map(p.g), b = ingest_byte_map(p.b);
+        m = ingest_white_mask(p.r, p.g, p.b);
+    } else if (a.resize == INGEST_RESIZE_BILINEAR_U8) {
+        int y0, y1, x0, x1;
+        float ly, lx;
+        ingest_bilinear_taps(y, a.scale_y, a.h, y0, y1, ly);
+        ingest_bilinear_taps(x, a.scale_x, a.w, x0, x1, lx);
+        const uint8_t *r0 = img + (size_t)y0 * row_bytes, *r1 = img + (size_t)y1 * row_bytes;
+        const IngestPx p00 = load(r0 + (size_t)x0 * a.c), p01 = load(r0 + (size_t)x1 * a.c);
+        const IngestPx p10 = load(r1 + (size_t)x0 * a.c), p11 = load(r1 + (size_t)x1 * a.c);
+        r = ingest_byte_map(ingest_bilinear_u8(p00.r, p01.r, p10.r, p11.r, lx, ly));
+        g = ingest_byte_map(ingest_bilinear_u8(p00.g, p01.g, p10.g, p11.g, lx, ly));
+        b = ingest_byte_map(ingest_bilinear_u8(p00.b, p01.b, p10.b, p11.b, lx, ly));
+    } else {
+        int ys, ye, xs, xe;
+        ingest_area_window(y, a.h, a.oh, ys, ye);
+        ingest_area_window(x, a.w, a.ow, xs, xe);
+        r = g = b = 0.0f;
+        for (int yy = ys; yy < ye; ++yy) {
+            const uint8_t* row = img + (size_t)yy * row_bytes;
+            for (int xx = xs; xx < xe; ++xx) {
+                const IngestPx p = load(row + (size_t)xx * a.c);
+                r += ingest_byte_map(p.r), g += ingest_byte_map(p.g), b += ingest_byte_map(p.b);
+                m += ingest_white_mask(p.r, p.g, p.b);
+            }
+        }
+        const float count = (float)((ye - ys) * (xe - xs));
+        r = r / count, g = g / count, b = b / count, m = m / count;
+    }
 }
 
 // ---- YOLO target grids

@@ -3,6 +3,7 @@
 // that a render call never leaves the device and never launches an ATen op.
 #include "pny_common.h"
 #include "pny_rng.h"
+#include "pny_ray.h"
 #include "pny_train_batch.h"
 
 namespace pny {
@@ -294,18 +295,7 @@ struct GenRaysCams {              // no device staging buffer, no copy, nothing 
     float cam[GEN_RAYS_IMGS][16];
 };
 
-// The ray of pixel (x, y) through a pinhole camera c (cam16, yolo=0): the unit direction in camera space, and the row
-// [origin, R d, near, far] written as two 16-byte words.  One copy of the arithmetic for gen_rays_kernel and
-// train_batch_kernel, so a sampled training ray carries the bits of the same pixel of a full gen_rays call.
-__device__ __forceinline__ void pinhole_dir(const float* c, int x, int y, float& d0, float& d1, float& d2) {
-    d0 = ((float)x - c[14]) / c[12];
-    d1 = -(((float)y - c[15]) / c[13]);
-    d2 = -1.0f;
-    const float nrm = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
-    d0 /= nrm;
-    d1 /= nrm;
-    d2 /= nrm;
-}
+// The ray of pixel (x, y) through a pinhole camera c (cam16, yolo=0): pinhole_dir and store_ray of pny_ray.h.
 // The same for yolo=1: Kinv [x + .49, y + .49, 1], not normalised (c[12..15] hold the entries of Kinv).  One copy for
 // gen_rays_kernel and yolo_train_batch_kernel.
 __device__ __forceinline__ void yolo_dir(const float* c, int x, int y, float& d0, float& d1, float& d2) {
@@ -313,12 +303,6 @@ __device__ __forceinline__ void yolo_dir(const float* c, int x, int y, float& d0
     d0 = c[12] * px + c[14];
     d1 = c[13] * py + c[15];
     d2 = 1.0f;
-}
-__device__ __forceinline__ void store_ray(const float* c, float d0, float d1, float d2, float znear, float zfar,
-                                          float* row) {
-    float4* o = reinterpret_cast<float4*>(row);  // hipMalloc / torch allocations: rows are 32-byte aligned
-    o[0] = make_float4(c[9], c[10], c[11], c[0] * d0 + c[1] * d1 + c[2] * d2);
-    o[1] = make_float4(c[3] * d0 + c[4] * d1 + c[5] * d2, c[6] * d0 + c[7] * d1 + c[8] * d2, znear, zfar);
 }
 
 // Pixels [first, first + count) of the flattened (img, y, x) index space of images [img0, img0 + GEN_RAYS_IMGS).
@@ -383,24 +367,10 @@ __global__ __launch_bounds__(256) void train_batch_kernel(const TrainBatchArgs a
         p = pixel_from_bbox(view, ux, uy, a.bboxes + ((size_t)s * a.nv + view) * 4, a.h, a.w);
     }
     const float* P = a.poses + ((size_t)s * a.nv + p.view) * 16;
-    float c[16];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) c[3 * r + q] = P[4 * r + q];
-        c[9 + r] = P[4 * r + 3];
-    }
     const float* f = a.focal + (size_t)(a.focal_rows > 1 ? s : 0) * a.focal_cols;
-    c[12] = f[0];
-    c[13] = f[a.focal_cols - 1];
-    if (a.c) {
-        const float* cc = a.c + (size_t)(a.c_rows > 1 ? s : 0) * 2;
-        c[14] = cc[0];
-        c[15] = cc[1];
-    } else {
-        c[14] = (float)a.w * 0.5f;
-        c[15] = (float)a.h * 0.5f;
-    }
+    const float* cc = a.c ? a.c + (size_t)(a.c_rows > 1 ? s : 0) * 2 : nullptr;
+    float c[16];
+    cam16_from_pose(P, f[0], f[a.focal_cols - 1], cc ? cc[0] : (float)a.w * 0.5f, cc ? cc[1] : (float)a.h * 0.5f, c);
     float d0, d1, d2;
     pinhole_dir(c, p.x, p.y, d0, d1, d2);
     store_ray(c, d0, d1, d2, a.znear, a.zfar, a.rays + i * 8);

@@ -11,6 +11,8 @@ Host-side Python mirroring the reference's interface (same class names, construc
                       ``defer=True`` only draws the factors, for ``augment.color_jitter`` to apply on the device)
   get_split_dataset  reference src/data/__init__.py:12-76 (types ``srn``, ``multi_obj``, ``dvr``, ``dvr_gen``, ``dvr_dtu`` and ``yolo``)
   psnr / ssim / write_views  what eval/eval.py:291-359 does with skimage / imageio
+  ResidentViews  no counterpart in the reference: the decoded views of a whole split kept on the device as bytes, and a
+                      training step (rays, ground truth, source views, cameras) drawn from them without the DataLoader
 
 PARITY UNPINNED against the third-party libraries the reference uses here -- imageio (decoding), cv2 (resize, projection-
 matrix decomposition), torchvision (colour jitter), skimage (metrics) are not importable in this environment, so the reference's classes cannot be imported to capture
@@ -587,6 +589,376 @@ class ColorJitterDataset(torch.utils.data.Dataset):
         else:
             data["images"] = self.apply_color_jitter(data["images"])
         return data
+
+
+# ------------------------------------------------------------------ resident views
+_WHO_RV = "pixel_nerf_yolo_amd.data.ResidentViews"
+
+
+def _host_ids(v, name, who, ndim):
+    """``v`` as a host int64 array of ``ndim`` dimensions, or None when it is a device tensor (used as it is, clamped by the
+    kernels); an error that names the argument otherwise."""
+    if isinstance(v, torch.Tensor):
+        if v.device.type != "cpu":
+            if v.dtype not in (torch.int32, torch.int64) or v.dim() != ndim:
+                raise ValueError("%s: %s on the device must be an int32 or int64 tensor of %d dimension%s, got %s %s"
+                                 % (who, name, ndim, "" if ndim == 1 else "s", tuple(v.shape), v.dtype))
+            return None
+        v = v.numpy()
+    a = np.asarray(v)
+    if a.ndim != ndim or a.size == 0 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("%s: %s must be %d-dimensional, non-empty and of integers, got shape %s %s" % (who, name, ndim, a.shape, a.dtype))
+    return a.astype(np.int64)
+
+
+def _pair_of(v, name, kind, who):
+    try:
+        a, b = (kind(x) for x in v)
+    except (TypeError, ValueError):
+        raise ValueError(who + "%s must be a pair, got %r" % (name, v))
+    return a, b
+
+
+class ResidentViews:
+    """A dataset's decoded views kept on the device as bytes, once, and a training step drawn straight from them
+    (include/pnyolo.h "resident views").  What the DataLoader path does per step -- decode ALL views of every
+    object of the super-batch, copy them over, normalise and resize them -- is done for the pixels and source views the step
+    keeps: ``batch`` is one launch for the rays and their ground truth, one for the source views, and device-side indexing of
+    the small camera tensors; nothing waits for the device.
+
+    One decoded geometry (H, W, C), fixed by the first ``add``, and one output geometry: ``scale=(fx, fy)`` (bilinear_u8, the
+    ``yolo`` dataset's rule), ``size=(OH, OW)`` with ``resize="area"`` (``srn``) or ``"bilinear_u8"``, or neither (no resize),
+    as ``augment.ingest_views`` takes them.  ``white_bbox=True`` computes SRN's boxes once, when an object is added.
+    ``device="cpu"`` holds the store for bookkeeping only: ``batch`` and ``source_views`` then raise PnyError."""
+
+    def __init__(self, device, size=None, scale=None, resize=None, white_bbox=False):
+        from . import lib as _lib
+        who = _WHO_RV + ": "
+        self.device = torch.device(device)
+        if resize is not None and resize not in _lib.RESIZE:
+            raise ValueError(who + "resize must be None, 'none', 'bilinear_u8' or 'area', got %r" % (resize,))
+        if scale is not None and size is not None:
+            raise ValueError(who + "scale and size are both given; scale=(fx, fy) or size=(OH, OW)")
+        if scale is not None:
+            if resize not in (None, "bilinear_u8"):
+                raise ValueError(who + "scale goes with resize='bilinear_u8' (cv2's output-size rule), got resize=%r" % (resize,))
+            scale, resize = _pair_of(scale, "scale", float, who), "bilinear_u8"
+        elif size is not None:
+            if resize not in ("area", "bilinear_u8"):
+                raise ValueError(who + "size needs resize='area' or resize='bilinear_u8', got resize=%r" % (resize,))
+            size = _pair_of(size, "size", int, who)
+            if min(size) < 1:
+                raise ValueError(who + "size must be positive, got %r" % (size,))
+        elif resize not in (None, "none"):
+            raise ValueError(who + "resize=%r needs size=(OH, OW)%s" % (resize, " or scale=(fx, fy)" if resize == "bilinear_u8" else ""))
+        else:
+            resize = "none"
+        if white_bbox and resize == "bilinear_u8":
+            raise ValueError(who + "white_bbox goes with resize='area' or no resize (no dataset resizes a mask bilinearly)")
+        self.resize, self._size, self._scale, self.white_bbox = resize, size, scale, bool(white_bbox)
+        self.decoded = None            # (H, W, C) of every view of the store
+        self.out_size = None           # (OH, OW)
+        self._views, self._poses, self._focal, self._c, self._bbox, self._labels = [], [], [], [], [], []
+        self._tab = None               # the device tables of the objects added so far; rebuilt, never rewritten
+
+    # ---- filling
+    def add(self, images_u8, poses, focal, c=None, bbox=None, labels=None):
+        """One object: ``images_u8`` (NV, H, W, C) uint8 on the host or the device, C = 3 or 4 (alpha ignored); ``poses``
+        (NV, 4, 4) cam->world; ``focal`` a scalar or (fx, fy), ``c`` None (the image centre) or (cx, cy) and ``bbox`` None or
+        (NV, 4) `cmin rmin cmax rmax`, all at OUTPUT resolution, as the ``ingest_on_device`` items carry them; ``labels`` anything
+        (the item's YOLO rows), kept on the host for ``labels(obj)``.  Returns the object's index."""
+        who = _WHO_RV + ".add: "
+        img = torch.from_numpy(np.ascontiguousarray(images_u8)) if isinstance(images_u8, np.ndarray) else images_u8
+        if not isinstance(img, torch.Tensor):
+            raise TypeError(who + "images_u8 must be a tensor or an array, got %s" % type(images_u8).__name__)
+        if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[-1] not in (3, 4) or img.numel() == 0:
+            raise ValueError(who + "images_u8 must be (NV, H, W, C) uint8 with C = 3 or 4, got %s %s" % (tuple(img.shape), img.dtype))
+        nv, geom = int(img.shape[0]), tuple(int(v) for v in img.shape[1:])
+        if self.decoded is not None and geom != self.decoded:
+            raise ValueError(who + "images_u8 is (H, W, C) = %s; the store holds %s (one decoded geometry)" % (geom, self.decoded))
+        h, w = geom[:2]
+        if self._scale is not None:
+            oh, ow = int(round(h * self._scale[1])), int(round(w * self._scale[0]))
+            if oh < 1 or ow < 1:
+                raise ValueError(who + "scale %r gives an empty %d x %d output" % (self._scale, oh, ow))
+        else:
+            oh, ow = self._size if self._size is not None else (h, w)
+        if nv * oh * ow >= 2 ** 32:
+            raise ValueError(who + "images_u8: n_views * OH * OW = %d * %d * %d must be below 2^32 (the draw's limit)" % (nv, oh, ow))
+        p = torch.as_tensor(poses).detach().to("cpu", torch.float32)
+        if tuple(p.shape) != (nv, 4, 4):
+            raise ValueError(who + "poses must be (%d, 4, 4), got %s" % (nv, tuple(p.shape)))
+        f = torch.as_tensor(focal).detach().to("cpu", torch.float32).reshape(-1)
+        if f.numel() not in (1, 2):
+            raise ValueError(who + "focal must be a scalar or (fx, fy), got shape %s" % (tuple(torch.as_tensor(focal).shape),))
+        f = f.repeat(2) if f.numel() == 1 else f
+        cc = torch.tensor([ow * 0.5, oh * 0.5], dtype=torch.float32) if c is None else \
+            torch.as_tensor(c).detach().to("cpu", torch.float32).reshape(-1)
+        if cc.numel() != 2:
+            raise ValueError(who + "c must be None or (cx, cy), got shape %s" % (tuple(torch.as_tensor(c).shape),))
+        img = img.detach().to(self.device).contiguous()
+        if self.white_bbox:
+            if bbox is not None:
+                raise ValueError(who + "bbox is given and the store computes its own (white_bbox=True)")
+            from . import augment
+            _, _, bb = augment.ingest_views(img, size=self._size, resize=None if self.resize == "none" else self.resize, white_mask=True)
+            bb = bb.cpu()                                   # fill time may wait
+            empty = (bb[:, 2] < 0).nonzero().reshape(-1)
+            if empty.numel():
+                raise ValueError(who + "images_u8[%d] has an empty white-background mask (every pixel has a byte at 255): "
+                                 "no box to sample from" % int(empty[0]))
+        elif bbox is not None:
+            bb = torch.as_tensor(bbox).detach().to("cpu", torch.float32)
+            if tuple(bb.shape) != (nv, 4):
+                raise ValueError(who + "bbox must be (%d, 4) `cmin rmin cmax rmax`, got %s" % (nv, tuple(bb.shape)))
+        else:
+            bb = None
+        if self._views and (bb is None) != (self._bbox[0] is None):
+            raise ValueError(who + "bbox is %s, the objects of the store %s boxes: all or none"
+                             % ("None" if bb is None else "given", "have no" if self._bbox[0] is None else "have"))
+        self.decoded, self.out_size = geom, (oh, ow)
+        self._views.append(img)
+        self._poses.append(p.contiguous())
+        self._focal.append(f)
+        self._c.append(cc)
+        self._bbox.append(bb)
+        self._labels.append(labels)
+        self._tab = None
+        return len(self._views) - 1
+
+    @classmethod
+    def from_dataset(cls, dset, device, indices=None, white_bbox=None):
+        """The objects ``indices`` (default: all) of a dataset of this module.  ``ingest_on_device=True`` items (``srn``: area
+        resize to the item's ``image_size`` and, unless ``white_bbox=False``, the white-background boxes; ``yolo``: the item's
+        ``image_scale`` and label rows) are taken as they are.  Items that carry fp32 ``images`` (``dvr``, ``dvr_gen``,
+        ``dvr_dtu``, ``multi_obj``) are re-quantised to bytes; an image that is not the byte map of bytes is refused."""
+        who = _WHO_RV + ".from_dataset: "
+        store = None
+        for i in (range(len(dset)) if indices is None else indices):
+            it = dset[int(i)]
+            if not it:                                       # MultiObjectDataset's {} for an instance it skips
+                continue
+            if "images_u8" in it:
+                u8 = it["images_u8"]
+                if store is None:
+                    if "image_scale" in it:
+                        store = cls(device, scale=tuple(float(v) for v in it["image_scale"]))
+                    else:
+                        size = tuple(int(v) for v in it["image_size"])
+                        resized = size != tuple(u8.shape[1:3])
+                        store = cls(device, size=size if resized else None, resize="area" if resized else None,
+                                    white_bbox=True if white_bbox is None else white_bbox)
+                labels = (it["labels"], it["n_labels"]) if "labels" in it else None
+                store.add(u8, it["poses"], it["focal"], c=it.get("c"), labels=labels)
+                continue
+            x = it["images"]
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
+                raise ValueError(who + "item %d: images must be (NV, 3, H, W) fp32, got %s" % (int(i), getattr(x, "shape", type(x))))
+            u8 = ((x * 0.5 + 0.5) * 255.0).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+            back = ((u8.permute(0, 3, 1, 2).to(torch.float32).div(255.0)) - 0.5) / 0.5        # image_to_tensor_balanced
+            if not torch.equal(back, x):
+                v = int((back != x).flatten(1).any(1).nonzero()[0])
+                raise ValueError(who + "item %d (%s): images[%d] is not the byte map of 8-bit pixels (resized or jittered on the host?); "
+                                 "the store holds bytes" % (int(i), it.get("path"), v))
+            if store is None:
+                store = cls(device, white_bbox=bool(white_bbox))
+            bbox = it.get("bbox")
+            store.add(u8, it["poses"], it["focal"], c=it.get("c"), bbox=None if bbox is None or len(bbox) == 0 or store.white_bbox else bbox)
+        if store is None:
+            raise ValueError(who + "no object to hold")
+        return store
+
+    # ---- bookkeeping
+    def __len__(self):
+        return len(self._views)
+
+    def n_views(self, obj):
+        return int(self._views[obj].shape[0])
+
+    def labels(self, obj):
+        """What ``add`` was given as ``labels`` for this object (the YOLO rows, for ``util.build_yolo_targets``)."""
+        return self._labels[obj]
+
+    @property
+    def nbytes(self):
+        """Bytes the store holds on its device: the views and the camera tables."""
+        n, rows = len(self._views), sum(int(v.shape[0]) for v in self._views)
+        per_row = 64 + (16 if n and self._bbox[0] is not None else 0)          # a pose, a box
+        return sum(v.numel() for v in self._views) + rows * per_row + n * (16 + 8 + 8 + 16)   # record, focal, c, n_views and first_row
+
+    def epoch(self, batch_size, seed, epoch=0, drop_last=True):
+        """The object ids of one epoch in batches of ``batch_size``: a permutation seeded by (seed, epoch), on the host -- what
+        the DataLoader's shuffle and batching did."""
+        g = torch.Generator()
+        g.manual_seed((int(seed) * 1000003 + int(epoch)) % (2 ** 63))
+        order = torch.randperm(len(self), generator=g).tolist()
+        for k in range(0, len(order), int(batch_size)):
+            ids = order[k:k + int(batch_size)]
+            if len(ids) == int(batch_size) or (ids and not drop_last):
+                yield ids
+
+    def tables(self):
+        """The small tables of the objects added so far, on the store's device, built on the host and uploaded once after the
+        last ``add`` into FRESH tensors (launches in flight keep the ones they were given): ``objs`` (n, 16) bytes -- the ABI's
+        records {views pointer, n_views, first_row} --, ``n_views`` and ``first_row`` (n,) int64, ``poses`` (N_total, 4, 4),
+        ``bboxes`` (N_total, 4) or None, ``focal`` and ``c`` (n, 2)."""
+        if self._tab is not None:
+            return self._tab
+        if not self._views:
+            raise ValueError(_WHO_RV + ": the store is empty")
+        nv = np.array([v.shape[0] for v in self._views], np.int64)
+        first = np.concatenate([[0], np.cumsum(nv)[:-1]])
+        if int(nv.sum()) >= 2 ** 31:
+            raise ValueError(_WHO_RV + ": 2^31 views or more")
+        rec = np.zeros(len(nv), np.dtype([("views", np.uint64), ("n_views", np.int32), ("first_row", np.int32)]))
+        rec["views"], rec["n_views"], rec["first_row"] = [v.data_ptr() for v in self._views], nv, first
+        up = lambda t: t.to(self.device, non_blocking=True)
+        self._tab = {
+            "objs": up(torch.from_numpy(rec.view(np.uint8).reshape(len(nv), 16).copy())),
+            "n_views": up(torch.from_numpy(nv)), "first_row": up(torch.from_numpy(first.astype(np.int64))),
+            "poses": up(torch.cat(self._poses)), "focal": up(torch.stack(self._focal)), "c": up(torch.stack(self._c)),
+            "bboxes": None if self._bbox[0] is None else up(torch.cat(self._bbox)),
+            "max_views": int(nv.max()), "n_rows": int(nv.sum()),
+        }
+        return self._tab
+
+    # ---- drawing
+    def _ids(self, obj_ids, view_ids, who, view_name):
+        """(SB,) int32 object ids and (SB, NS) int32 view ids on the device; host lists are validated first."""
+        n = len(self)
+        o = _host_ids(obj_ids, "obj_ids", who, 1)
+        if o is not None and (o.min() < 0 or o.max() >= n):
+            raise ValueError("%s: obj_ids holds %d; the store has %d object%s" % (who, int(o[(o < 0) | (o >= n)][0]), n, "" if n == 1 else "s"))
+        sb = len(o) if o is not None else int(obj_ids.shape[0])
+        o_dev = self._upload_ids(o, obj_ids)
+        if view_ids is None:
+            return o_dev, None
+        v = _host_ids(view_ids, view_name, who, 2)
+        shape = v.shape if v is not None else tuple(view_ids.shape)
+        if shape[0] != sb:
+            raise ValueError("%s: %s must be (%d, NS), one row per entry of obj_ids, got %s" % (who, view_name, sb, tuple(shape)))
+        if v is not None and o is not None:
+            lim = np.array([self.n_views(int(k)) for k in o])[:, None]
+            bad = np.argwhere((v < 0) | (v >= lim))
+            if len(bad):
+                s, k = (int(t) for t in bad[0])
+                raise ValueError("%s: %s[%d][%d] = %d; object %d has %d view%s" % (who, view_name, s, k, int(v[s, k]), int(o[s]), int(lim[s, 0]),
+                                                                                   "" if lim[s, 0] == 1 else "s"))
+        elif v is not None and v.min() < 0:
+            raise ValueError("%s: %s holds %d" % (who, view_name, int(v.min())))
+        v_dev = self._upload_ids(v, view_ids)
+        return o_dev, v_dev
+
+    def _upload_ids(self, host, given):
+        """int32 ids on the store's device: a validated host array goes through pinned memory (a copy from pageable memory may
+        wait for the stream), a device tensor is used as it is."""
+        if host is None:
+            return given.to(self.device, torch.int32).contiguous()
+        t = torch.from_numpy(host.astype(np.int32))
+        if self.device.type == "cuda":
+            t = t.pin_memory()
+        return t.to(self.device, non_blocking=True)
+
+    def _need_device(self, who):
+        from . import lib as _lib
+        if self.device.type != "cuda":
+            raise _lib.PnyError("%s: the store is on %s; drawing from it runs on an MI355X only (the host path is the DataLoader over "
+                                "data.py's datasets)" % (who, self.device))
+        return _lib
+
+    def _source_views(self, _lib, tab, o_dev, v_dev, jitter):
+        import ctypes as C
+        sb, ns = (int(t) for t in v_dev.shape)
+        h, w, ch = self.decoded
+        oh, ow = self.out_size
+        out = torch.empty(sb, ns, 3, oh, ow, device=self.device, dtype=torch.float32)
+        obj_of = o_dev[:, None].expand(sb, ns).contiguous()
+        desc = _lib.IngestDesc(n_views=sb * ns, height=h, width=w, channels=ch, out_height=oh, out_width=ow,
+                               resize=_lib.RESIZE[self.resize], white_mask=0)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pny_ingest_views_indexed(
+                C.byref(desc), C.c_void_p(tab["objs"].data_ptr()), len(self), tab["max_views"], C.c_void_p(obj_of.data_ptr()),
+                C.c_void_p(v_dev.data_ptr()), C.c_void_p(out.data_ptr()), _lib.stream_of(self.device)))
+        if jitter is not None:
+            from . import augment
+            augment.color_jitter(out, jitter, out=out)
+        return out
+
+    def source_views(self, obj_ids, view_ids, jitter=None):
+        """Views ``view_ids`` (SB, NS) of objects ``obj_ids`` (SB,) -- or (NS,) of ONE object given as an int -- as
+        ``augment.ingest_views`` gives them: (SB, NS, 3, OH, OW) (or (NS, 3, OH, OW)) fp32 in [-1, 1], in one launch;
+        ``jitter`` (SB, 4) applies ``augment.color_jitter`` behind it.  Ids are host lists (validated) or device tensors (clamped)."""
+        who = _WHO_RV + ".source_views"
+        one = isinstance(obj_ids, (int, np.integer))
+        if one:
+            obj_ids = [int(obj_ids)]
+            view_ids = view_ids[None] if isinstance(view_ids, torch.Tensor) else [list(view_ids)]
+        if view_ids is None:
+            raise ValueError(who + ": view_ids is None")
+        o_dev, v_dev = self._ids(obj_ids, view_ids, who, "view_ids")
+        _lib = self._need_device(who)
+        out = self._source_views(_lib, self.tables(), o_dev, v_dev, jitter)
+        return out[0] if one else out
+
+    def batch(self, obj_ids, src_view_ids, ray_batch_size, z_near, z_far, seed=None, draws=None, draw_offset=0, jitter=None):
+        """One training step's inputs for the objects ``obj_ids`` (SB,; repeats allowed), with nothing the size of a view set
+        decoded, copied or normalised: a dict of ``rays`` (SB, B, 8), ``rgb_gt`` (SB, B, 3) and ``pix`` (SB, B, 3) int32
+        [view, y, x] -- share s bit-equal to ``util.sample_train_batch`` on ``augment.ingest_views`` of that object's views with
+        ``draw_offset + s * B`` (bbox mode when the store holds boxes) --, ``src_images`` (SB, NS, 3, OH, OW) of the views
+        ``src_view_ids`` (SB, NS) (None: no source views), ``src_poses`` (SB, NS, 4, 4), ``focal`` (SB, 2) and ``c`` (SB, 2).
+        ``seed`` / ``draws`` / ``draw_offset`` as ``util.sample_train_batch`` takes them; ``jitter`` (SB, 4) for the source views."""
+        import ctypes as C
+        who = _WHO_RV + ".batch"
+        B = int(ray_batch_size)
+        if B < 1:
+            raise ValueError(who + ": ray_batch_size must be positive, got %r" % (ray_batch_size,))
+        o_dev, v_dev = self._ids(obj_ids, src_view_ids, who, "src_view_ids")
+        sb = int(o_dev.shape[0])
+        if draws is not None and seed is not None:
+            raise ValueError(who + ": draws replay the pixel choice; seed has no effect with them")
+        _lib = self._need_device(who)
+        tab = self.tables()
+        h, w, ch = self.decoded
+        oh, ow = self.out_size
+        desc = _lib.TrainBatchDesc(n_objs=sb, n_views=tab["max_views"], height=h, width=w, n_rays=B, z_near=float(z_near),
+                                   z_far=float(z_far), focal_rows=0, focal_cols=0, c_rows=0, seed=0, draw_offset=int(draw_offset))
+        dr, keep = None, []
+        if draws is not None:
+            names = ("image_ids", "u_x", "u_y") if tab["bboxes"] is not None else ("pix_inds",)
+            if set(draws) != set(names):
+                raise ValueError(who + ": draws must hold exactly %s (the store has %s boxes), got %s"
+                                 % (names, "no" if tab["bboxes"] is None else "its", sorted(draws)))
+            keep = [torch.as_tensor(draws[k]).detach().to(self.device, torch.float32 if k.startswith("u_") else torch.int64,
+                                                           non_blocking=True).contiguous() for k in names]
+            for k, t in zip(names, keep):
+                if tuple(t.shape) != (sb, B):
+                    raise ValueError(who + ": draws[%r] must be (%d, %d), got %s" % (k, sb, B, tuple(t.shape)))
+            dr = _lib.TrainBatchDraws(**{k + "_dev": t.data_ptr() for k, t in zip(names, keep)})
+        elif seed is None:
+            hi, lo = torch.randint(0, 2 ** 32, (2,), dtype=torch.int64).tolist()   # the CPU generator: nothing to wait for
+            desc.seed = (hi << 32) | lo
+        else:
+            desc.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        rays = torch.empty(sb, B, 8, device=self.device, dtype=torch.float32)
+        rgb_gt = torch.empty(sb, B, 3, device=self.device, dtype=torch.float32)
+        pix = torch.empty(sb, B, 3, device=self.device, dtype=torch.int32)
+        vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pny_resident_train_batch(
+                C.byref(desc), ch, oh, ow, _lib.RESIZE[self.resize], vp(tab["objs"]), len(self), vp(o_dev), vp(tab["poses"]),
+                tab["n_rows"], vp(tab["focal"]), vp(tab["c"]), vp(tab["bboxes"]), None if dr is None else C.byref(dr), vp(rays),
+                vp(rgb_gt), vp(pix), _lib.stream_of(self.device)))
+        # the small camera tensors by device-side indexing, with the kernels' clamps
+        o = o_dev.to(torch.int64).clamp(0, len(self) - 1)
+        out = {"rays": rays, "rgb_gt": rgb_gt, "pix": pix, "focal": tab["focal"][o], "c": tab["c"][o], "src_images": None,
+               "src_poses": None}
+        if v_dev is not None:
+            v = torch.minimum(v_dev.to(torch.int64).clamp(min=0), (tab["n_views"][o] - 1)[:, None])
+            out["src_poses"] = tab["poses"][tab["first_row"][o][:, None] + v]
+            out["src_images"] = self._source_views(_lib, tab, o_dev, v_dev, jitter)
+        elif jitter is not None:
+            raise ValueError(who + ": jitter is given without src_view_ids (it applies to the source views)")
+        return out
 
 
 # ------------------------------------------------------------------ metrics / writers (eval/eval.py:291-359)

@@ -256,6 +256,11 @@ SIGNATURES = {
     "pny_ingest_views": (C.c_int, [C.POINTER(IngestDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pny_yolo_build_targets": (C.c_int, [C.POINTER(YoloTargetsDesc), C.c_void_p, C.c_void_p, c_float_p, C.POINTER(C.c_void_p),
                                          C.c_void_p]),
+    "pny_resident_train_batch": (C.c_int, [C.POINTER(TrainBatchDesc), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(TrainBatchDraws), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pny_ingest_views_indexed": (C.c_int, [C.POINTER(IngestDesc), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
     "pny_grid_points": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int64, C.c_int64, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
     "pny_mc_workspace_bytes": (C.c_int, [C.POINTER(C.c_int32), c_i64_p]),
