@@ -1199,6 +1199,50 @@ int pny_mc_emit(const float* sigma_dev, const int32_t* dims_host, float iso, con
                 int64_t n_triangles, float* vertices_dev /* (V, 3) index coordinates */, int32_t* triangles_dev /* (T, 3) */,
                 pny_stream stream);
 
+/* ---- occupancy grid: skip empty space in no-grad renders of ONE encoded object (csrc/occupancy.hip; conventions and arithmetic
+ * in csrc/pny_occupancy.h).  An opt-in, approximate mode the reference does not have.  The contract: a scene with a grid
+ * attached renders, on the same rays and draws, what it renders without one if the MLP's (r, g, b, sigma) at every sample the
+ * grid rejects were (0, 0, 0, 0) before the composite, in both passes; the MLP runs on the kept samples only.  With no grid
+ * attached pny_render enqueues exactly what it always did.
+ *
+ * Cells: a sigma volume of dims = {X, Y, Z} grid points (x slowest, z fastest, as the mesh extraction reads it) has
+ * (X - 1, Y - 1, Z - 1) cells; flat index f = (ix (Y - 1) + iy) (Z - 1) + iz is bit f & 31 of uint32 word f >> 5; bits past the
+ * last cell are 0.  A corner is occupied when !(sigma <= thresh) -- a NaN is occupied -- in sigma_dev or, when given, in
+ * sigma2_dev (the same shape: the fine MLP's sigma); a cell is occupied when a cell within Chebyshev distance `dilate` (0 .. 4)
+ * has an occupied corner.  Sample to cell: p_a = fmaf(z, d_a, o_a), t_a = (p_a - (float)c1_a) * (float)((double)cells_a /
+ * (c2_a - c1_a)), each operation rounded to fp32; inside iff 0 <= t_a < cells_a on all axes (a NaN is outside), cell index
+ * (int)t_a.  outside_empty is a flag: 0 keeps a sample outside the box [c1, c2), 1 rejects it.
+ *
+ * pny_occupancy_words: the uint32 words of the bitfield of a volume.
+ * pny_occupancy_build: ONE launch writes bits_dev (every word by one thread: the same bits on every run) and, unless NULL,
+ *   occupied_dev = the int64 number of occupied cells (zeroed on the stream first, then integer atomic adds).
+ * pny_occupancy_classify: a stage entry like pny_sample_coarse: the kernels a culled pny_render runs on its (n, k) depths
+ *   z_dev of rays_dev (n, 8), 16-byte aligned.  slot_dev (n, k) int32 = the rank of a kept sample among the kept samples in
+ *   ascending sample order, -1 for a rejected one; kept_dev = their int64 number, left on the device.  3 launches up to 2^20
+ *   samples, 5 above; n k <= 2^30.  workspace_dev: 256-byte aligned, pny_occupancy_classify_workspace_bytes(n k) bytes.
+ * pny_scene_set_occupancy: the scene COPIES the bits into a buffer it owns (on `stream`); bits_dev = NULL clears the grid (the
+ *   other arguments are then ignored).  Refused for a YOLO model (its aggregation weighs by objectness, not sigma) and for a
+ *   grouped scene.  Whatever changes the scene's sigma clears the grid: pny_scene_encode / pny_scenes_encode,
+ *   pny_scene_set_latent, pny_scene_set_latent_levels, pny_scene_set_cameras; so does pny_scene_set_groups above 1.
+ *   With a grid attached each pass of pny_render is: classify, ONE host read of the kept count M (so TWO host waits per call),
+ *   gather M compact rows (40 bytes each), the MLP on M points, expand.  M = 0 launches no MLP kernel.  A pny_render told to
+ *   stash for a backward (pny_scene_stash_next_render) returns PNY_ERR_STATE; pny_query, pny_yolo_render and every training
+ *   entry ignore the grid.
+ * pny_scene_last_cull: kept and total samples of the coarse [0] and fine [1] pass of the last pny_render; all 0 when it used
+ *   no grid.
+ * PNY_ERR_ARG, before any launch: a NULL pointer, a dimension below 2, 3 X Y Z >= 2^31, non-finite bounds, c2 <= c1 on an
+ * axis, a NaN thresh, dilate outside 0 .. 4, n < 0, k < 1, n k > 2^30, a workspace too small or misaligned. */
+int pny_occupancy_words(const int32_t dims[3], int64_t* words);
+int pny_occupancy_build(const float* sigma_dev /* (X, Y, Z) */, const float* sigma2_dev /* or NULL */, const int32_t dims[3],
+                        float thresh, int dilate, uint32_t* bits_dev, int64_t* occupied_dev /* or NULL */, pny_stream stream);
+int pny_occupancy_classify_workspace_bytes(int64_t n_samples, int64_t* bytes);
+int pny_occupancy_classify(const uint32_t* bits_dev, const int32_t dims[3], const double c1[3], const double c2[3],
+                           int outside_empty, const float* rays_dev, const float* z_dev, int64_t n, int k, int32_t* slot_dev,
+                           int64_t* kept_dev, void* workspace_dev, int64_t workspace_bytes, pny_stream stream);
+int pny_scene_set_occupancy(pny_scene* s, const uint32_t* bits_dev /* NULL clears */, const int32_t dims[3], const double c1[3],
+                            const double c2[3], int outside_empty, pny_stream stream);
+int pny_scene_last_cull(pny_scene* s, int64_t kept[2], int64_t total[2]);
+
 #ifdef __cplusplus
 }
 #endif

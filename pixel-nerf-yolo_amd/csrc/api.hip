@@ -569,6 +569,7 @@ int pny_scene_set_cameras(pny_scene* s, const float* poses, int ns, const float*
     s->width = width;
     s->height = height;
     s->have_cams = true;
+    s->occ_on = false;   // the grid was learnt on another sigma
     return PNY_OK;
 }
 
@@ -576,6 +577,7 @@ int pny_scene_set_groups(pny_scene* s, int n_objs) {
     if (!s) return fail(PNY_ERR_ARG, "pny_scene_set_groups: null scene");
     if (n_objs < 1 || n_objs > MAX_VIEWS) return fail(PNY_ERR_ARG, "pny_scene_set_groups: n_objs out of range [1,16]");
     s->n_objs = n_objs;   // (the view count is checked against it when a call needs both: check_ready)
+    if (n_objs > 1) s->occ_on = false;   // one occupancy grid serves one object
     return PNY_OK;
 }
 
@@ -587,6 +589,7 @@ static void set_latent_shape(pny_scene* s, int ns, int L, int hl, int wl) {
     s->wl = wl;
     s->have_latent = true;
     s->zp_valid[0] = s->zp_valid[1] = false;
+    s->occ_on = false;   // the grid was learnt on another sigma
 }
 
 // what pny_scene_encode and pny_scenes_encode ask of the model and the images; selects the device, returns the latent's size
@@ -1161,6 +1164,47 @@ static void begin_call(pny_scene* s) {
     s->last_launches = 0;
 }
 
+// One MLP pass of a pny_render with an occupancy grid attached (pny_occupancy.h): classify the n x K depth samples, read the
+// kept count M (the pass's ONE host wait), gather the kept samples' points into M compact rows, evaluate the MLP on them as a
+// point list (pny_query's launch) and expand into `samp` (n, K, 4), a rejected sample getting (0, 0, 0, 0).  M == 0 launches
+// no MLP kernel.
+static int culled_mlp(pny_scene* s, const float* rays, const float* z, int64_t n, int K, int coarse, float* samp, hipStream_t st,
+                      int pass) {
+    const int64_t S = n * K;
+    if (n > OCC_MAX_SAMPLES / K) return fail(PNY_ERR_ARG, "pny_render: more than 2^30 samples in a pass with an occupancy grid attached");
+    if (reinterpret_cast<uintptr_t>(samp) % 16)
+        return fail(PNY_ERR_ARG, "pny_render: per-sample buffers must be 16-byte aligned with an occupancy grid attached");
+    int rc;
+    const OccLayout l = occ_layout(S);
+    const size_t o_sums = mc_align((size_t)S * sizeof(int32_t)), o_kept = o_sums + l.bytes;
+    if ((rc = s->occ_work.reserve(o_kept + 256, "hipMalloc(occupancy workspace)"))) return rc;
+    if ((rc = s->occ_count.reserve(sizeof(int64_t), "hipHostMalloc(occupancy count)"))) return rc;
+    char* W = reinterpret_cast<char*>(s->occ_work.p);
+    int32_t* slot = reinterpret_cast<int32_t*>(W);
+    int64_t* kept_dev = reinterpret_cast<int64_t*>(W + o_kept);
+    occupancy_classify(s->occ, rays, z, S, K, slot, kept_dev, W + o_sums, st);
+    PNY_HIP(hipGetLastError());
+    PNY_HIP(hipMemcpyAsync(s->occ_count.p, kept_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    PNY_HIP(hipStreamSynchronize(st));
+    const int64_t M = *static_cast<const int64_t*>(s->occ_count.p);
+    if (M < 0 || M > S) return fail(PNY_ERR_HIP, "pny_render: the occupancy classification returned an impossible count");
+    s->cull_kept[pass] = M, s->cull_total[pass] = S;
+    float* outc = nullptr;
+    if (M > 0) {
+        const size_t m3 = ((size_t)M * 3 + 63) & ~(size_t)63;
+        if ((rc = s->occ_rows.reserve((2 * m3 + (size_t)M * 4) * sizeof(float), "hipMalloc(occupancy rows)"))) return rc;
+        float* xyz = s->occ_rows.f();
+        float* dirs = xyz + m3;
+        outc = dirs + m3;
+        launch_occupancy_gather(slot, rays, z, S, K, M, xyz, dirs, st);
+        PNY_HIP(hipGetLastError());
+        if ((rc = run_mlp(s, 0, xyz, dirs, nullptr, nullptr, 1, M, coarse, outc, st))) return rc;
+    }
+    launch_occupancy_expand(slot, outc, S, M, samp, st);
+    PNY_HIP(hipGetLastError());
+    return 0;
+}
+
 extern "C" {
 
 int pny_query(pny_scene* s, const float* xyz_dev, const float* viewdirs_dev, int64_t n, int coarse, float* out_dev,
@@ -1227,6 +1271,14 @@ int pny_render(pny_scene* s, const float* rays_dev, int64_t n, const pny_render_
         if (!o->u_coarse_dev || (kimp > 0 && (!o->u_fine_dev || !o->u_fine2_dev)) || (o->n_fine_depth > 0 && !o->g_depth_dev))
             return fail(PNY_ERR_ARG, "pny_render: explicit random draws must be given for every stage or for none");
     }
+    // an occupancy grid (pny_scene_set_occupancy) is for no-grad renders: a culled pass writes no stash
+    const bool cull = s->occ_on;
+    if (cull && s->stash_next) {
+        s->stash_next = false;
+        return fail(PNY_ERR_STATE, "pny_render: the scene has an occupancy grid attached and was told to stash for a backward "
+                                   "(pny_scene_stash_next_render); clear the grid with pny_scene_set_occupancy(s, NULL, ...) to train");
+    }
+    s->cull_kept[0] = s->cull_kept[1] = s->cull_total[0] = s->cull_total[1] = 0;
     if (n == 0) return PNY_OK;
     PNY_HIP(hipSetDevice(s->m->desc.device));
     hipStream_t st = (hipStream_t)stream;
@@ -1255,7 +1307,11 @@ int pny_render(pny_scene* s, const float* rays_dev, int64_t n, const pny_render_
     s->stash_next = false;
     s->stashed[0].valid = s->stashed[1].valid = false;
     launch_sample_coarse(rays_dev, n, kc, o->lindisp, o->u_coarse_dev, o->seed, zc, st);
-    if ((rc = run_mlp(s, 1, nullptr, nullptr, rays_dev, zc, kc, (long long)n * kc, 1, sc, st, stash ? 0 : -1))) return rc;
+    if (cull) {
+        if ((rc = culled_mlp(s, rays_dev, zc, n, kc, 1, sc, st, 0))) return rc;
+    } else if ((rc = run_mlp(s, 1, nullptr, nullptr, rays_dev, zc, kc, (long long)n * kc, 1, sc, st, stash ? 0 : -1))) {
+        return rc;
+    }
     launch_composite(rays_dev, zc, sc, n, kc, o->white_bkgd, wc, rgbc, dc, st, o->sigma_noise_coarse_dev);
     if (o->n_fine > 0) {
         float* zf = out->z_fine ? out->z_fine : W + o_zf;
@@ -1264,7 +1320,11 @@ int pny_render(pny_scene* s, const float* rays_dev, int64_t n, const pny_render_
             return fail(PNY_ERR_ARG, "pny_render: n_coarse + n_fine too large for the LDS-resident sort");
         launch_sample_fine(rays_dev, zc, wc, dc, n, kc, o->n_fine, o->n_fine_depth, o->depth_std, o->lindisp,
                            o->u_fine_dev, o->u_fine2_dev, o->g_depth_dev, o->seed, zf, st);
-        if ((rc = run_mlp(s, 1, nullptr, nullptr, rays_dev, zf, kt, (long long)n * kt, 0, sf, st, stash ? 1 : -1))) return rc;
+        if (cull) {
+            if ((rc = culled_mlp(s, rays_dev, zf, n, kt, 0, sf, st, 1))) return rc;
+        } else if ((rc = run_mlp(s, 1, nullptr, nullptr, rays_dev, zf, kt, (long long)n * kt, 0, sf, st, stash ? 1 : -1))) {
+            return rc;
+        }
         launch_composite(rays_dev, zf, sf, n, kt, o->white_bkgd, out->weights_fine, out->rgb_fine, out->depth_fine, st,
                          o->sigma_noise_fine_dev);
     }

@@ -7,6 +7,7 @@
 #include "pny_common.h"
 #include "dev_resource.h"
 #include "encoder.h"
+#include "pny_occupancy.h"
 #include "stash_book.h"
 
 namespace pny {
@@ -223,6 +224,14 @@ struct pny_scene {
     bool has_last_stream = false;
     Event order_ev;
     bool order_ev_valid = false;             // order_ev was recorded behind the last call's work (api.hip mark_stream_point)
+    // occupancy grid (pny_scene_set_occupancy; pny_occupancy.h): the scene's own copy of the bits, the workspace of a culled
+    // pass (slot per sample, tile sums, the kept count), its compact rows (10 floats per KEPT sample) and the pinned word the
+    // count is read into; cleared by everything that changes what the scene's sigma is
+    bool occ_on = false;
+    OccGrid occ{};
+    DevBuf occ_bits, occ_work, occ_rows;
+    PinnedBuf occ_count;
+    int64_t cull_kept[2] = {0, 0}, cull_total[2] = {0, 0};   // pny_scene_last_cull: [0] coarse pass, [1] fine pass
 };
 
 
@@ -259,4 +268,13 @@ int latent_levels_check(const char* who, const float* const* maps, const int* ch
                         long long* total_channels);
 int latent_levels_assemble(const char* who, const float* const* maps, const int* channels, const int* h, const int* w, int n_levels, int n,
                            float* latent_nhwc, hipStream_t st);
+// occupancy.hip
+void launch_occupancy_build(const OccBuildArgs& a, hipStream_t st);
+void launch_occupancy_classify(const OccClassifyArgs& a, const OccLayout& l, uint32_t* sums2, int64_t* kept, hipStream_t st);
+void launch_occupancy_gather(const int32_t* slot, const float* rays, const float* z, int64_t n_samples, int K, int64_t m, float* xyz,
+                             float* dirs, hipStream_t st);
+void launch_occupancy_expand(const int32_t* slot, const float* outc, int64_t n_samples, int64_t m, float* out, hipStream_t st);
+// the classification of n x k depth samples against grid g (occupancy_api.hip): checks nothing, launches
+void occupancy_classify(const OccGrid& g, const float* rays, const float* z, int64_t n_samples, int k, int32_t* slot, int64_t* kept,
+                        void* workspace, hipStream_t st);
 }  // namespace pny

@@ -267,6 +267,16 @@ SIGNATURES = {
     "pny_mc_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pny_mc_emit": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_float, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                               C.c_void_p]),
+    "pny_occupancy_words": (C.c_int, [C.POINTER(C.c_int32), c_i64_p]),
+    "pny_occupancy_build": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_float, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "pny_occupancy_classify_workspace_bytes": (C.c_int, [C.c_int64, c_i64_p]),
+    "pny_occupancy_classify": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_void_p]),
+    "pny_scene_set_occupancy": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                          C.c_int, C.c_void_p]),
+    "pny_scene_last_cull": (C.c_int, [C.c_void_p, c_i64_p, c_i64_p]),
 }
 
 _lib = None

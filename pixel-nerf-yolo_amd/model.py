@@ -286,6 +286,7 @@ class PixelNeRFNet(nn.Module):
         self._last_trunk_wait = None       # which ordering the last trunk backward took (for the tests)
         self._trunk_generation = 0         # bumped by every training-trunk forward: whose activations does the library hold
         self._timing = False
+        self._occupancy = None             # set_occupancy: the grid attached to the one encoded object
         # What a no-grad call does when one of its f16 (F16X2 / F16) launches met a value outside the f16 range (include/pnyolo.h
         # pny_model_range_status): 'relaunch' (default) = wait for the call, and if the guard fired repeat it on the fp32
         # kernels with a warning, keeping the scenes pinned to f32 from then on; 'raise' = wait and raise PnyRangeError;
@@ -524,6 +525,48 @@ class PixelNeRFNet(nn.Module):
         for s in self._handles():
             check(_lib.load().pny_scene_set_precision(s, _lib.PRECISION[mode]))
         return self
+
+    def set_occupancy(self, grid):
+        """Attach ``grid`` (recon.OccupancyGrid, from ``recon.occupancy_grid``) to the ONE encoded object, or detach with None
+        (include/pnyolo.h pny_scene_set_occupancy; csrc/pny_occupancy.h).  No-grad renders then evaluate the MLPs only at the depth
+        samples the grid keeps and composite as if the others had returned (0, 0, 0, 0): an opt-in, approximate mode, like
+        set_matrix_precision('f16').  Each render waits for the device twice (the kept count of each pass).  The scene copies the
+        bits.  ``encode()`` drops the grid; queries, YOLO renders and training ignore or refuse it."""
+        L = _lib.load()
+        if grid is None:
+            if self._h_model is not None:
+                for s in self._handles():
+                    check(L.pny_scene_set_occupancy(s, None, None, None, None, 0, None))
+            self._occupancy = None
+            return self
+        if self.yolo:
+            raise _lib.PnyError("PixelNeRFNet.set_occupancy: a YOLO model aggregates by objectness, not by sigma; an occupancy grid "
+                                "does not apply to it")
+        if self.num_objs != 1:
+            raise _lib.PnyError("PixelNeRFNet.set_occupancy: net must hold ONE encoded object (call net.encode() with one object "
+                                "first); it holds %d" % self.num_objs)
+        self._sync()
+        dev = self._device()
+        bits = grid.bits
+        if bits.device != dev or bits.dtype != torch.uint32 or not bits.is_contiguous():
+            raise ValueError("PixelNeRFNet.set_occupancy: grid.bits must be a contiguous uint32 tensor on %s" % dev)
+        d, a, b = (C.c_int32 * 3)(*grid.dims), (C.c_double * 3)(*grid.c1), (C.c_double * 3)(*grid.c2)
+        with torch.cuda.device(dev):
+            check(L.pny_scene_set_occupancy(self._scene(0), C.c_void_p(bits.data_ptr()), d, a, b, int(grid.outside_empty), stream_of(dev)))
+        self._occupancy = grid
+        return self
+
+    @property
+    def occupancy(self):
+        """The attached recon.OccupancyGrid, or None."""
+        return self._occupancy
+
+    def last_cull(self):
+        """{"coarse": (kept, total), "fine": (kept, total)} samples of the last render of the object; zeros when it used no grid
+        (include/pnyolo.h pny_scene_last_cull)."""
+        kept, total = (C.c_int64 * 2)(), (C.c_int64 * 2)()
+        check(_lib.load().pny_scene_last_cull(self._scene(0), kept, total))
+        return {"coarse": (int(kept[0]), int(total[0])), "fine": (int(kept[1]), int(total[1]))}
 
     def set_deterministic(self, mode):
         """'auto' | True | False: whether d loss / d latent is computed bit-reproducibly (include/pnyolo.h
@@ -816,6 +859,8 @@ class PixelNeRFNet(nn.Module):
         self._sync()
         L = _lib.load()
         dev = self._device()
+        if self._occupancy is not None:     # learnt on the object encoded before (the library drops its copy on its own too)
+            self.set_occupancy(None)
         self.num_objs = images.size(0)
         if images.dim() == 5:
             assert poses.dim() == 4 and poses.size(1) == images.size(1)

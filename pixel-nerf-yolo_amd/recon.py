@@ -154,6 +154,91 @@ def workspace_bytes(dims):
     return int(out.value)
 
 
+class OccupancyGrid:
+    """A bitfield over the cells of a sigma volume (csrc/pny_occupancy.h), as ``occupancy_grid`` builds it and
+    ``net.set_occupancy`` attaches it: ``bits`` (uint32 device tensor, cell f = bit f & 31 of word f >> 5), ``dims`` (X, Y, Z grid
+    points: (X - 1)(Y - 1)(Z - 1) cells), the box ``c1`` .. ``c2``, ``outside_empty``; ``n_cells`` and ``n_occupied`` (the count is
+    on the device until first asked for: one host read)."""
+
+    def __init__(self, bits, dims, c1, c2, outside_empty, occupied):
+        self.bits, self.dims, self.c1, self.c2 = bits, tuple(int(v) for v in dims), tuple(float(v) for v in c1), tuple(float(v) for v in c2)
+        self.outside_empty = bool(outside_empty)
+        self.n_cells = (self.dims[0] - 1) * (self.dims[1] - 1) * (self.dims[2] - 1)
+        self._occupied, self._n_occupied = occupied, None
+
+    @property
+    def n_occupied(self):
+        if self._n_occupied is None:
+            self._n_occupied = int(self._occupied.item())
+        return self._n_occupied
+
+    def __repr__(self):
+        return "OccupancyGrid(dims=%s, c1=%s, c2=%s, outside_empty=%s)" % (self.dims, self.c1, self.c2, self.outside_empty)
+
+
+def occupancy_words(dims):
+    """uint32 words of the bitfield of a (X, Y, Z) volume (pny_occupancy_words)."""
+    out = C.c_int64(0)
+    check(_lib.load().pny_occupancy_words((C.c_int32 * 3)(*[int(v) for v in dims]), C.byref(out)))
+    return int(out.value)
+
+
+def _volume(v, dev, what):
+    if not isinstance(v, torch.Tensor):
+        v = torch.as_tensor(np.asarray(v, dtype=np.float32))
+    v = v.detach().to(dev, torch.float32).contiguous()
+    if v.dim() != 3 or min(v.shape) < 2:
+        raise ValueError("%s.occupancy_grid: %s must be a (X, Y, Z) volume with every dimension at least 2, got %s"
+                         % (_WHO, what, tuple(v.shape)))
+    return v
+
+
+def occupancy_grid(net, c1=(-1, -1, -1), c2=(1, 1, 1), reso=(128, 128, 128), *, sigma_thresh, dilate=1, outside_empty=False,
+                   eval_batch_size=100000, sigma=None):
+    """The occupancy grid of ONE encoded object for ``net.set_occupancy``: the cells of the box c1 .. c2 where no-grad renders may
+    skip the MLP (csrc/pny_occupancy.h).  A cell is occupied when any of its 8 corners has ``not sigma <= sigma_thresh`` (a NaN is
+    occupied) in the coarse MLP's volume or, when the net has ``mlp_fine``, in the fine MLP's, or when a cell within Chebyshev
+    distance ``dilate`` (0 .. 4) is.  Without ``sigma`` the volumes come from ``sigma_grid`` (``coarse=True``, and ``coarse=False``
+    with a fine MLP).
+    WARNING (marching_cubes' own): sigma depends on the view direction here, and the grid is learnt on fake directions pointing at
+    the origin.  The mode is therefore approximate: ``dilate`` and a low threshold are the safety margin.
+    :param sigma_thresh required: the library does not choose one
+    :param outside_empty False keeps the samples outside the box (they are evaluated as without a grid), True rejects them
+    :param sigma one (X, Y, Z) fp32 volume or a pair of the same shape to build from instead (``reso`` is then their shape):
+        synthetic fields of tests and tools; ``net`` may be None when they are device tensors
+    :return OccupancyGrid"""
+    thresh, dilate = float(sigma_thresh), int(dilate)
+    if np.isnan(thresh):
+        raise ValueError("%s.occupancy_grid: sigma_thresh must not be a NaN" % _WHO)
+    if not 0 <= dilate <= 4:
+        raise ValueError("%s.occupancy_grid: dilate must be in 0 .. 4, got %d" % (_WHO, dilate))
+    if sigma is None:
+        vols = [sigma_grid(net, c1, c2, reso, eval_batch_size=eval_batch_size, coarse=True)]
+        if getattr(net, "mlp_fine", None) is not None:
+            vols.append(sigma_grid(net, c1, c2, reso, eval_batch_size=eval_batch_size, coarse=False))
+    else:
+        pair = list(sigma) if isinstance(sigma, (list, tuple)) else [sigma]
+        if not 1 <= len(pair) <= 2:
+            raise ValueError("%s.occupancy_grid: sigma must be one volume or a pair, got %d" % (_WHO, len(pair)))
+        dev = pair[0].device if isinstance(pair[0], torch.Tensor) and pair[0].device.type == "cuda" else net._device()
+        vols = [_volume(v, dev, "sigma") for v in pair]
+        if len(vols) == 2 and vols[1].shape != vols[0].shape:
+            raise ValueError("%s.occupancy_grid: the two sigma volumes differ in shape: %s and %s"
+                             % (_WHO, tuple(vols[0].shape), tuple(vols[1].shape)))
+    dims = [int(v) for v in vols[0].shape]
+    a, b, d, _ = _grid_args(c1, c2, dims)
+    dev = vols[0].device
+    if dev.type != "cuda":
+        raise _lib.PnyError("%s.occupancy_grid: the grid is built on an MI355X only (there is no CPU path)" % _WHO)
+    bits = torch.empty(occupancy_words(dims), device=dev, dtype=torch.int32)
+    occupied = torch.empty(1, device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        check(_lib.load().pny_occupancy_build(C.c_void_p(vols[0].data_ptr()), C.c_void_p(vols[1].data_ptr()) if len(vols) == 2 else None,
+                                              d, thresh, dilate, C.c_void_p(bits.data_ptr()), C.c_void_p(occupied.data_ptr()),
+                                              stream_of(dev)))
+    return OccupancyGrid(bits.view(torch.uint32), dims, list(a), list(b), outside_empty, occupied)
+
+
 def marching_cubes(occu_net, c1=[-1, -1, -1], c2=[1, 1, 1], reso=[128, 128, 128], isosurface=50.0, sigma_idx=3,
                    eval_batch_size=100000, coarse=True, device=None, return_tensors=False):
     """The reference's ``recon.marching_cubes`` (recon.py:12-78), same signature and defaults, on the device.

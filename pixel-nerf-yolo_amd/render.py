@@ -127,6 +127,9 @@ class _MultiDeviceRenderWrapper(torch.nn.Module):
         if rays.shape[0] == 0:
             return (torch.zeros(0, 3, device=rays.device), torch.zeros(0, device=rays.device))
         net, ren = self.net, self.renderer
+        if net.occupancy is not None:
+            raise _lib.PnyError("bind_parallel(net, gpus): the net has an occupancy grid attached (net.set_occupancy), which the "
+                                "per-device replicas do not carry; render on one device, or detach it with net.set_occupancy(None)")
         want_weights = want_weights and not self.simple_output
         training = torch.is_grad_enabled() and net.training and (net.trainable_mlp_parameters() or net.differentiable_latent() is not None)
         B = rays.shape[1]
@@ -474,6 +477,10 @@ class NeRFRenderer(torch.nn.Module):
                 self.draws, self._calls = draws, calls
                 return self._render(model, rays, want_weights, save=False)[0]
             return model.guard_f16_range(call)
+        if model.occupancy is not None:
+            raise _lib.PnyError("NeRFRenderer: the net has an occupancy grid attached (net.set_occupancy), which serves no-grad "
+                                "renders only; this call takes gradients: detach the grid with net.set_occupancy(None), or render "
+                                "under torch.no_grad()")
         if lat_src is None:
             model.check_differentiable()     # (with a differentiable latent the caller's own encoder takes the gradient)
         kf = int(self.n_fine) if (self.using_fine and self.n_fine > 0) else 0
