@@ -1,4 +1,4 @@
-// Private declarations shared by the host-side translation units of libpnyolo (api.hip, train_api.hip).
+// Private declarations shared by the host-side translation units of libpnyolo (the *_api.hip files).
 #pragma once
 #include <map>
 #include <string>
@@ -164,7 +164,7 @@ struct pny_model {
     unsigned* range_flag() const { return static_cast<unsigned*>(range_block.p); }
     uint64_t generation = 0;                  // bumped by every finalize (scenes re-project)
     // single-plane f16 images of lin_in / fc_0 / fc_1 for PNY_PRECISION_F16 (mlp_h1.hip): built only once a scene of the model
-    // is set to F16 (api.hip build_h1_images), then kept current by every finalize and refresh; [0] coarse, [1] fine MLP
+    // is set to F16 (model_api.hip build_h1_images), then kept current by every finalize and refresh; [0] coarse, [1] fine MLP
     bool want_h1 = false, h1_ready = false;
     DevBuf h1_packed, h1_jobs;
     int n_h1_jobs = 0;
@@ -201,7 +201,6 @@ struct pny_scene {
     int ev_used = 0;
     double last_flops = 0.0;
     int last_launches = 0;
-    // stream the last call on this scene was enqueued on (see enter_stream)
     // training workspace (train_api.hip)
     DevBuf dy_absmax;                        // one word: running max |dY| of the chunk in flight (non-deferred backward)
     // deterministic latent gradient (latent_grad_det.hip): the (ns, hl, wl, L) int64 fixed-point accumulator (all zero between
@@ -220,10 +219,7 @@ struct pny_scene {
     std::vector<Event> bev;
     int bev_used = 0;
     double bwd_flops[3] = {0.0, 0.0, 0.0};   // stash forward, dX chain, weight-gradient GEMMs
-    hipStream_t last_stream = nullptr;
-    bool has_last_stream = false;
-    Event order_ev;
-    bool order_ev_valid = false;             // order_ev was recorded behind the last call's work (api.hip mark_stream_point)
+    StreamOrder order;                       // of this scene's calls across streams (dev_resource.h)
     // occupancy grid (pny_scene_set_occupancy; pny_occupancy.h): the scene's own copy of the bits, the workspace of a culled
     // pass (slot per sample, tile sums, the kept count), its compact rows (10 floats per KEPT sample) and the pinned word the
     // count is read into; cleared by everything that changes what the scene's sigma is
@@ -236,7 +232,9 @@ struct pny_scene {
 
 
 namespace pny {
-int enter_stream(pny_scene* s, hipStream_t st);
+inline int enter_stream(pny_scene* s, hipStream_t st) { return s->order.enter(st); }
+// the PNY_RANGE_* bits the f16 kernels have reported so far (pny_model_range_status)
+inline unsigned range_bits(const pny_model* m) { return m->range_flag() ? __atomic_load_n(m->range_flag(), __ATOMIC_RELAXED) : 0u; }
 int check_ready(pny_scene* s, const char* who);
 int view_blocks(const pny_model_desc& d);
 inline int d_in(const pny_model_desc& d) { return 3 + 6 * d.num_freqs + 3; }   // xyz, its positional code, view direction

@@ -7,7 +7,7 @@
 // One kernel per (64-sample tile, view): dz as a tiled fp32-MFMA GEMM straight off the dY stash -- the dX chain
 // (mlp_bwd.hip) has left dh_in(b) there in [feature/4][sample] float4 tiles, which IS the LDS B-operand layout of
 // pixel_linear_kernel (encoder.hip), so staging is a plain copy -- with K = n_view_blocks x 512 and the stacked transposed
-// weights [lin_z[0]^T | lin_z[1]^T | ...] as the packed A operand (api.hip pack_mlp, kept current by pny_model_refresh);
+// weights [lin_z[0]^T | lin_z[1]^T | ...] as the packed A operand (model_api.hip pack_mlp, kept current by pny_model_refresh);
 // the epilogue turns the accumulators through LDS and scatters 64 consecutive latent channels of one sample per atomic
 // instruction into the sample's four taps (float atomics).  The sum order over samples is therefore not fixed: latent gradients are reproducible to fp32
 // rounding, not bit for bit (the MLP parameter gradients stay deterministic).  The deterministic mode (pny_model_set_deterministic)

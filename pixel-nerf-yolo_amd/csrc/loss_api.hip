@@ -1,9 +1,7 @@
 // C entry points of the training losses (include/pnyolo.h, "training losses" section; kernels in loss.hip): argument checks,
 // the per-stream reduction workspace, one launch.
-#include <map>
 #include <mutex>
 #include <string>
-#include <utility>
 
 #include "api_internal.h"
 #include "pny_loss.h"
@@ -12,28 +10,13 @@ using namespace pny;
 
 namespace {
 
-// The ticket counter and the partial-sum table of a launch, one per (device, stream): launches on one stream follow one
-// another, so they can share it; launches on different streams may overlap and get their own.  Allocated on the first call on
-// a stream and zeroed ON that stream (no host wait); never freed (a few KB per stream the process ever used).
-// Raw and unfreed on purpose (not a DevBuf): a global's destructor would call hipFree after the HIP runtime may have shut down.
-std::mutex g_ws_mutex;
-std::map<std::pair<int, hipStream_t>, void*> g_ws;
+// The ticket counter and the partial-sum table of a launch, one per (device, stream) (dev_resource.h StreamBlocks): a fixed
+// LOSS_WS_BYTES, all of it zeroed.
+StreamBlocks<std::mutex> g_ws{"hipMalloc(&q, LOSS_WS_BYTES)", "hipMemsetAsync(loss workspace)"};
 
 int loss_workspace(hipStream_t st, unsigned** ticket, double** partials) {
-    int dev = 0;
-    PNY_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_ws_mutex);
-    void*& p = g_ws[std::make_pair(dev, st)];
-    if (!p) {
-        void* q = nullptr;
-        PNY_HIP(hipMalloc(&q, LOSS_WS_BYTES));
-        hipError_t e = hipMemsetAsync(q, 0, LOSS_WS_BYTES, st);
-        if (e != hipSuccess) {
-            (void)hipFree(q);
-            return hip_fail(e, "hipMemsetAsync(loss workspace)");
-        }
-        p = q;
-    }
+    void* p = nullptr;
+    if (int rc = g_ws.get(st, LOSS_WS_BYTES, LOSS_WS_BYTES, &p)) return rc;
     *ticket = reinterpret_cast<unsigned*>(p);
     *partials = reinterpret_cast<double*>(reinterpret_cast<char*>(p) + 256);
     return 0;

@@ -1,9 +1,7 @@
 // C entry point of the view metrics (include/pnyolo.h, "view metrics" section; kernel in metrics.hip): argument checks, the
 // per-stream reduction workspace, one launch.
-#include <map>
 #include <mutex>
 #include <string>
-#include <utility>
 
 #include "api_internal.h"
 #include "pny_metrics.h"
@@ -16,40 +14,19 @@ using namespace pny;
 
 namespace {
 
-// The ticket counter (its own 256 bytes) and the table of one row per workgroup, one per (device, stream), as the losses keep
-// theirs (loss_api.hip).  The table holds METRICS_WS_ROWS rows from the first call on a stream on, zeroed ON that stream; a
-// launch of more workgroups (more than 65 536 tiles: 2 000 views of 128 x 128) replaces it by a larger one, and only that
-// replacement waits for the device (hipFree).  Never freed otherwise.
-// Raw and unfreed on purpose (not a DevBuf): a global's destructor would call hipFree after the HIP runtime may have shut down.
+// The ticket counter (its own 256 bytes, the part that is zeroed) and the table of one row per workgroup, one per (device,
+// stream) (dev_resource.h StreamBlocks), as the losses keep theirs (loss_api.hip).  The table holds METRICS_WS_ROWS rows from
+// the first call on a stream on; a launch of more workgroups (more than 65 536 tiles: 2 000 views of 128 x 128) replaces it by
+// a larger one, and only that replacement waits for the device (hipFree).
 constexpr size_t METRICS_WS_ROWS = 65536;
-struct Workspace {
-    void* p = nullptr;
-    size_t rows = 0;
-};
-std::mutex g_ws_mutex;
-std::map<std::pair<int, hipStream_t>, Workspace> g_ws;
+StreamBlocks<std::mutex> g_ws{"hipMalloc(&q, bytes)", "hipMemsetAsync(metrics workspace)"};
 
 int metrics_workspace(hipStream_t st, size_t rows, unsigned** ticket, double** partials) {
-    int dev = 0;
-    PNY_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_ws_mutex);
-    Workspace& w = g_ws[std::make_pair(dev, st)];
-    if (rows > w.rows) {
-        const size_t want = rows > METRICS_WS_ROWS ? rows : METRICS_WS_ROWS;
-        const size_t bytes = 256 + want * METRICS_SUMS * sizeof(double);
-        if (w.p) PNY_HIP(hipFree(w.p));
-        w.p = nullptr, w.rows = 0;
-        void* q = nullptr;
-        PNY_HIP(hipMalloc(&q, bytes));
-        hipError_t e = hipMemsetAsync(q, 0, 256, st);
-        if (e != hipSuccess) {
-            (void)hipFree(q);
-            return hip_fail(e, "hipMemsetAsync(metrics workspace)");
-        }
-        w.p = q, w.rows = want;
-    }
-    *ticket = reinterpret_cast<unsigned*>(w.p);
-    *partials = reinterpret_cast<double*>(reinterpret_cast<char*>(w.p) + 256);
+    const size_t want = rows > METRICS_WS_ROWS ? rows : METRICS_WS_ROWS;
+    void* p = nullptr;
+    if (int rc = g_ws.get(st, 256 + want * METRICS_SUMS * sizeof(double), 256, &p)) return rc;
+    *ticket = reinterpret_cast<unsigned*>(p);
+    *partials = reinterpret_cast<double*>(reinterpret_cast<char*>(p) + 256);
     return 0;
 }
 

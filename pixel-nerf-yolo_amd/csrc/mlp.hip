@@ -24,7 +24,7 @@
 //   * persistent over tiles; the cross-view running sum lives in a per-workgroup slab accessed
 //     non-temporally.
 //   * two instantiations: ZP = false runs lin_z per sample as written in the reference; ZP = true
-//     uses the per-scene projected latent (lin_z applied to every latent pixel once, api.hip
+//     uses the per-scene projected latent (lin_z applied to every latent pixel once, render_api.hip
 //     ensure_projection): bilinear interpolation and lin_z are both linear, so
 //     lin_z(interp(latent)) = interp(lin_z(latent)) up to fp32 rounding, and the per-sample lin_z
 //     GEMMs (29 % of the FLOPs at L = 512, 64 % at L = 1792) become a 512-channel gather that is

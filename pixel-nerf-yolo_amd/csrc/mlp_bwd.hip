@@ -488,7 +488,7 @@ void launch_composite_bwd(const float* rays, const float* z, const float* samp, 
 // Only the kfd depth samples per ray need it, so this is a separate small kernel over the dY stash of the fine pass
 // (one wavefront per selected sample) and not part of the chain kernel:
 //   dL/d(code input) = lin_in^T dh_in(0);   dL/d(ix, iy) = sum_b dh_in(b) . d interp(ZP_b) / d(ix, iy)
-// with ZP_b the per-scene projected maps lin_z[b](latent) (the lookup is linear in the latent, api.hip
+// with ZP_b the per-scene projected maps lin_z[b](latent) (the lookup is linear in the latent, render_api.hip
 // ensure_projection), so the lin_z^T GEMMs are not needed.
 
 // sel[ray * kfd + j] = index (ray * kt + position) of depth sample j in the sorted fine depths, or -1 when the sample

@@ -14,7 +14,7 @@
 // Compiled without SLP vectorisation like mlp_h2.hip (csrc/Makefile).
 //
 // -DPNY_H2_PLANES=1 (mlp_bwd_h1.hip) is the single-plane chain of PNY_PRECISION_F16_TRAIN, pny_mlp_bwd_h1_kernel: dY^T goes to
-// plane slot 0 only (f16, round to nearest), the transposed weights are single-plane images (plane 0 of PACK_H2T; api.hip
+// plane slot 0 only (f16, round to nearest), the transposed weights are single-plane images (plane 0 of PACK_H2T; model_api.hip
 // build_h1_images), one MFMA per accumulator tile and 16 k (h1gemm).  The scaled domain stays, and its headroom for ONE
 // plane: the upper limit is unchanged (a value 2^11 above the head's 2^4..2^5 reaches 65504 and overflows; reported as
 // PNY_RANGE_GRADIENT through the stash maximum); the lower limit is no longer the second plane's absolute 2^-25 but f16's

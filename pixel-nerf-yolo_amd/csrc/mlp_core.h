@@ -465,7 +465,7 @@ __device__ __forceinline__ void load_point(const MlpArgs& a, long long s, float 
         // points = o + z * d (reference nerf.py:191), view dir = ray dir (nerf.py:210)
         // (a 64-bit software division per thread is ~100 instructions: 32-bit whenever the launch fits)
         const long long ray = a.idx32 ? (long long)((unsigned)s / (unsigned)a.K) : s / a.K;
-        const float4* r = reinterpret_cast<const float4*>(a.rays + ray * 8);  // rows are 32 bytes (api.hip checks alignment)
+        const float4* r = reinterpret_cast<const float4*>(a.rays + ray * 8);  // rows are 32 bytes (render_api.hip checks alignment)
         const float4 r0 = r[0], r1 = r[1];
         const float zz = a.z[s];
         d[0] = r0.w;

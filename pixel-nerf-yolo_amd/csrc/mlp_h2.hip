@@ -27,7 +27,7 @@
 //     flight, and between the barrier behind the previous GEMM and the one in front of fc_0 there is no workgroup barrier.
 //     The first tile of the next block is fetched underneath the fc_1 GEMM (in the registers of the then-dead `net`
 //     accumulators).  A lane serves four samples per tile: tap offsets and weights are re-read from the LDS tap table,
-//     and the loads go through a buffer resource of the view's map with 32-bit byte offsets (api.hip wants_projection keeps
+//     and the loads go through a buffer resource of the view's map with 32-bit byte offsets (render_api.hip wants_projection keeps
 //     a view's map under 4 GiB).
 //     The STASH instantiations (training forwards) keep the SHARED entry: the projected channels of a block arrive in 4
 //     chunks of 128 through two register buffers, wave w fetching samples 8 w .. 8 w + 7 for all 128 channels of a chunk
@@ -73,7 +73,7 @@
 //
 // -DPNY_H2_PLANES=1 (mlp_h1.hip) is the single-plane kernel of PNY_PRECISION_F16: x = f16(x), w = f16(w), one
 // v_mfma_f32_32x32x16_f16 per accumulator tile and 16 k (fp32 accumulation), weights packed per 16-k step as
-// [n-tile][lane] x 16 bytes (2 bytes per weight; api.hip build_h1_images).  The LDS layout stays the one above: relu(.) goes to
+// [n-tile][lane] x 16 bytes (2 bytes per weight; model_api.hip build_h1_images).  The LDS layout stays the one above: relu(.) goes to
 // plane slot 0 only, and slot 1 keeps its one job of staging half of the block entry's fp32 projection -- the projection
 // is added in fp32 exactly as in the two-plane kernel, at the same 152 KiB of LDS.  Its STASH instantiation is the training
 // forward of PNY_PRECISION_F16_TRAIN: the stash layout is unchanged and holds this kernel's own fp32 values.
@@ -789,7 +789,7 @@ __global__ __launch_bounds__(h2::THREADS, 2) void PNY_H2_KERNEL(const MlpArgs a)
                 }
             }
             if constexpr (WAVE_ENTRY) {
-                // (a view's map is under 4 GiB: api.hip wants_projection; a read past it would return zeros)
+                // (a view's map is under 4 GiB: render_api.hip wants_projection; a read past it would return zeros)
                 const size_t zfloats = (size_t)a.Hl * a.Wl * a.zp_stride;
                 zr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.zp) + (size_t)(vb + v) * zfloats, 0, (int)(unsigned)(zfloats * 4), 0x00020000);
             } else {

@@ -1,5 +1,5 @@
 // The occupancy grid on the device (conventions and arithmetic in pny_occupancy.h; entry points in occupancy_api.hip, the culled
-// passes of pny_render in api.hip): the bitfield from one or two sigma volumes, and the classify / gather / expand kernels that
+// passes of pny_render in render_api.hip): the bitfield from one or two sigma volumes, and the classify / gather / expand kernels that
 // let a render evaluate the MLP at the kept samples only.  Wave64 throughout.  No atomics on the bits and none in the ranking:
 // every output element has one writer, so the same input gives the same bits on every run.
 //

@@ -1,5 +1,5 @@
 // C entry points of the occupancy grid (include/pnyolo.h, "occupancy grid" section; kernels in occupancy.hip; the culled passes of
-// pny_render in api.hip): argument checks, then the launches.  The model-free entries allocate nothing and wait for nothing;
+// pny_render in render_api.hip): argument checks, then the launches.  The model-free entries allocate nothing and wait for nothing;
 // pny_scene_set_occupancy copies the bits into a buffer the scene owns.
 #include <math.h>
 

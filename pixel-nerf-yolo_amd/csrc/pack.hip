@@ -1,7 +1,7 @@
 // The packed weight operands of the fused MLP and of the latent projection, and the ONE kernel that builds them from the
 // state_dict tensors: pny_model_finalize runs it on uploaded copies, pny_model_refresh (after an optimizer step) on the
 // live parameter tensors where PyTorch keeps them -- no state_dict round trip through the host (27 MB of repacking and a
-// synchronous upload per step before).  This file is the description of the formats; api.hip only lays the images out
+// synchronous upload per step before).  This file is the description of the formats; model_api.hip only lays the images out
 // and lists the jobs (pack_mlp), encoder.hip build_pixel_linear allocates the projection weights.  A job writes `count`
 // 16-byte elements, element i as below; W is the (n_out x k_in) row-major tensor, K padded with zeros to k_pad.
 //

@@ -45,7 +45,7 @@ struct MlpArgs {
     unsigned w_bytes;
     const float* latent;  // (NS, Hl, Wl, L) channel-last
     // Projected latent (NS, Hl, Wl, zp_stride = n_view_blocks*512): lin_z[b] applied to every latent
-    // pixel once per scene (api.hip ensure_projection).  Non-null selects the kernel variant that
+    // pixel once per scene (render_api.hip ensure_projection).  Non-null selects the kernel variant that
     // interpolates these maps instead of running the lin_z GEMMs per sample (both maps are linear).
     const float* zp;
     int zp_stride;
@@ -123,7 +123,7 @@ struct BwdArgs {
     const float* wT_out;              // lin_out^T: 512 x d_out, K padded to D_IN_PAD
     const float* wT_fc0[MAX_BLOCKS];
     const float* wT_fc1[MAX_BLOCKS];
-    // the same matrices as split-f16 images (mlp_bwd_h2.hip; api.hip pack_mlp PACK_H2T); null when the fp32 chain runs
+    // the same matrices as split-f16 images (mlp_bwd_h2.hip; model_api.hip pack_mlp PACK_H2T); null when the fp32 chain runs
     const float* h2T_out;
     const float* h2T_fc0[MAX_BLOCKS];
     const float* h2T_fc1[MAX_BLOCKS];
@@ -176,7 +176,7 @@ struct DzArgs {
     int K;
     const float* w_in;    // lin_in.weight (512, d_in) row-major
     int d_in;
-    const float* zp;      // projected maps of this MLP (api.hip ensure_projection) or null
+    const float* zp;      // projected maps of this MLP (render_api.hip ensure_projection) or null
     int zp_stride;
     int NS, Hl, Wl, yolo, num_freqs;
     long long obj_pts;    // grouped scene (MlpArgs::obj_pts): samples per object, 0 = one object

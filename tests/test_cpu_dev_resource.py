@@ -31,6 +31,17 @@ static std::set<void*> g_dev, g_pin, g_ev, g_st;
 static std::vector<unsigned> g_flags;          // of every event / stream created, in order
 static long g_made[4], g_gone[4];              // device, pinned, event, stream
 static int g_fail_next = 0;                    // the next allocation / creation fails
+static int g_fail_record = 0, g_fail_memset = 0;   // the next hipEventRecord / hipMemsetAsync fails
+static int g_device = 0;                       // what hipGetDevice answers
+struct StreamCall {                            // which stream a record, a wait or a zero fill names, and its event or block
+    std::string op;
+    hipStream_t st;
+    void* what;
+    size_t bytes;
+    bool operator==(const StreamCall& o) const { return op == o.op && st == o.st && what == o.what && bytes == o.bytes; }
+};
+static std::vector<StreamCall> g_slog;
+static std::string g_what;                     // the site the last hip_fail named
 #define CHECK(c) do { if (!(c)) { printf("FAILED line %d: %s\n", __LINE__, #c); exit(1); } } while (0)
 static void gone(std::set<void*>& live, void* p, int kind, const char* name) {
     if (!live.erase(p)) { printf("FAILED: %s of a handle that is not live (double free)\n", name); exit(1); }
@@ -57,7 +68,29 @@ hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned flags) {
 }
 hipError_t hipEventCreate(hipEvent_t* e) { return hipEventCreateWithFlags(e, 0); }
 hipError_t hipEventDestroy(hipEvent_t e) { gone(g_ev, e, 2, "hipEventDestroy"); free(e); return hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { CHECK(g_ev.count(e)); g_log.push_back("hipEventRecord"); return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+    CHECK(g_ev.count(e));
+    g_log.push_back("hipEventRecord");
+    g_slog.push_back({"record", s, e, 0});
+    if (g_fail_record) { g_fail_record = 0; return hipErrorInvalidHandle; }   // (the stream is gone)
+    return hipSuccess;
+}
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned flags) {
+    CHECK(g_ev.count(e) && flags == 0);
+    g_log.push_back("hipStreamWaitEvent");
+    g_slog.push_back({"wait", s, e, 0});
+    return hipSuccess;
+}
+hipError_t hipGetLastError(void) { g_log.push_back("hipGetLastError"); return hipSuccess; }
+hipError_t hipGetDevice(int* d) { g_log.push_back("hipGetDevice"); *d = g_device; return hipSuccess; }
+hipError_t hipMemsetAsync(void* p, int value, size_t n, hipStream_t s) {
+    CHECK(g_dev.count(p) && value == 0);
+    g_log.push_back("hipMemsetAsync");
+    g_slog.push_back({"zero", s, p, n});
+    if (g_fail_memset) { g_fail_memset = 0; return hipErrorInvalidValue; }
+    memset(p, 0, n);   // (past the block's end: the sanitizer reports it)
+    return hipSuccess;
+}
 hipError_t hipEventSynchronize(hipEvent_t e) { CHECK(g_ev.count(e)); g_log.push_back("hipEventSynchronize"); return hipSuccess; }
 hipError_t hipEventQuery(hipEvent_t e) { CHECK(g_ev.count(e)); g_log.push_back("hipEventQuery"); return hipSuccess; }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned flags) {
@@ -76,7 +109,7 @@ const char* hipGetErrorString(hipError_t) { return "fake"; }
 }
 namespace pny {
 int fail(int code, const std::string&) { return code; }
-int hip_fail(hipError_t e, const char*) { return 1000 + (int)e; }
+int hip_fail(hipError_t e, const char* what) { g_what = what; return 1000 + (int)e; }
 }
 static long count(const char* name) {
     long n = 0;
@@ -257,6 +290,168 @@ static void release_then_destructor() {
     CHECK(balanced() && g_made[0] == 2 && g_made[1] == 1 && g_made[2] == 1 && g_made[3] == 1);
 }
 
+// ------------------------------------------------------------------ StreamOrder: the exact calls of a scene's stream order
+static const hipStream_t A = (hipStream_t)0x10, B = (hipStream_t)0x20, C = (hipStream_t)0x30;   // never dereferenced
+typedef std::vector<std::string> Log;
+typedef std::vector<StreamCall> SLog;
+
+static void order_enter() {
+    StreamOrder o;
+    CHECK(o.enter(A) == 0 && o.enter(A) == 0);                       // the first call and the same stream: nothing
+    CHECK(g_log.empty() && g_slog.empty() && g_made[2] == 0 && o.has_last && o.last == A);
+    CHECK(o.enter(B) == 0 && o.last == B && !o.ev_valid);            // a switch: one event, recorded on A, awaited on B
+    CHECK(g_log == Log({"hipEventCreateWithFlags", "hipEventRecord", "hipStreamWaitEvent"}));
+    CHECK(g_flags == std::vector<unsigned>({hipEventDisableTiming}) && g_made[2] == 1);
+    hipEvent_t ev = o.ev;
+    CHECK(g_slog == SLog({{"record", A, ev, 0}, {"wait", B, ev, 0}}));
+    CHECK(o.enter(B) == 0 && g_log.size() == 3);
+    CHECK(o.enter(A) == 0 && g_made[2] == 1);                        // the event is kept
+    CHECK(g_slog == SLog({{"record", A, ev, 0}, {"wait", B, ev, 0}, {"record", B, ev, 0}, {"wait", A, ev, 0}}));
+    StreamOrder moved(std::move(o));                                 // move-only: the event goes along, once
+    CHECK(!(hipEvent_t)o.ev && (hipEvent_t)moved.ev == ev && moved.last == A && moved.has_last);
+}
+
+static void order_mark() {
+    StreamOrder o;
+    CHECK(o.enter(A) == 0 && o.mark(A) == 0 && o.ev_valid);          // the record happens at the mark ...
+    hipEvent_t ev = o.ev;
+    CHECK(g_log == Log({"hipEventCreateWithFlags", "hipEventRecord"}) && g_slog == SLog({{"record", A, ev, 0}}));
+    CHECK(g_flags == std::vector<unsigned>({hipEventDisableTiming}));
+    CHECK(o.enter(B) == 0 && !o.ev_valid);                           // ... and enter only waits
+    CHECK(g_slog == SLog({{"record", A, ev, 0}, {"wait", B, ev, 0}}) && count("hipEventRecord") == 1);
+    CHECK(o.enter(A) == 0);                                          // the mark is spent: records on B, waits on A
+    CHECK(g_slog == SLog({{"record", A, ev, 0}, {"wait", B, ev, 0}, {"record", B, ev, 0}, {"wait", A, ev, 0}}));
+    CHECK(g_made[2] == 1 && count("hipGetLastError") == 0);
+}
+
+static void order_mark_spent() {
+    for (int entered_before = 0; entered_before < 2; ++entered_before) {
+        g_slog.clear();
+        StreamOrder o;
+        if (entered_before) CHECK(o.enter(A) == 0);
+        CHECK(o.mark(A) == 0 && o.enter(A) == 0 && !o.ev_valid);     // the same-stream call enqueues new work behind the mark
+        hipEvent_t ev = o.ev;
+        CHECK(g_slog == SLog({{"record", A, ev, 0}}));
+        CHECK(o.enter(B) == 0);                                      // so the switch records again
+        CHECK(g_slog == SLog({{"record", A, ev, 0}, {"record", A, ev, 0}, {"wait", B, ev, 0}}));
+    }
+}
+
+static void order_record_fails() {
+    StreamOrder o;
+    CHECK(o.enter(A) == 0);
+    g_fail_record = 1;                                               // A was destroyed: its work has drained
+    CHECK(o.enter(B) == 0 && o.last == B && o.has_last && !o.ev_valid);
+    CHECK(g_log == Log({"hipEventCreateWithFlags", "hipEventRecord", "hipGetLastError"}));   // no wait, the sticky error cleared once
+    CHECK(g_slog == SLog({{"record", A, (hipEvent_t)o.ev, 0}}));
+    g_fail_record = 1;
+    CHECK(o.hand_over(A) == 0 && o.last == A && count("hipStreamWaitEvent") == 0 && count("hipGetLastError") == 2);
+}
+
+static void order_create_fails() {
+    StreamOrder o;
+    CHECK(o.enter(A) == 0);
+    g_fail_next = 1;
+    CHECK(o.enter(B) == 1000 + (int)hipErrorOutOfMemory && g_what == "hipEventCreate(stream order)");
+    CHECK(o.last == A && o.has_last && !(hipEvent_t)o.ev && g_slog.empty());   // returned before any state changed
+    g_fail_next = 1;
+    CHECK(o.hand_over(B) == 1000 + (int)hipErrorOutOfMemory && g_what == "hipEventCreate(refresh order)");
+    CHECK(o.last == A && o.has_last && g_slog.empty());
+    g_fail_next = 1;
+    CHECK(o.mark(A) == 1000 + (int)hipErrorOutOfMemory && g_what == "hipEventCreate(stream order)" && !o.ev_valid);
+    CHECK(o.enter(B) == 0 && o.last == B && g_slog.size() == 2);     // and the next call tries again
+}
+
+static void order_hand_over() {
+    {   // last A, argument B: records on A, waits on B, B adopted; the mark made before no longer shortens the next enter
+        StreamOrder o;
+        CHECK(o.enter(A) == 0 && o.mark(A) == 0);
+        hipEvent_t ev = o.ev;
+        CHECK(o.hand_over(B) == 0 && o.last == B && o.has_last && !o.ev_valid);
+        CHECK(g_slog == SLog({{"record", A, ev, 0}, {"record", A, ev, 0}, {"wait", B, ev, 0}}));
+        CHECK(o.enter(C) == 0);
+        CHECK(g_slog == SLog({{"record", A, ev, 0}, {"record", A, ev, 0}, {"wait", B, ev, 0}, {"record", B, ev, 0}, {"wait", C, ev, 0}}));
+        CHECK(g_made[2] == 1 && g_flags == std::vector<unsigned>({hipEventDisableTiming}));
+    }
+    g_slog.clear();
+    {   // no last: no call, B adopted
+        StreamOrder o;
+        CHECK(o.mark(A) == 0);
+        hipEvent_t ev = o.ev;
+        const size_t calls = g_log.size();
+        CHECK(o.hand_over(B) == 0 && g_log.size() == calls && o.last == B && o.has_last && !o.ev_valid);
+        CHECK(o.enter(C) == 0);
+        CHECK(g_slog == SLog({{"record", A, ev, 0}, {"record", B, ev, 0}, {"wait", C, ev, 0}}));
+    }
+    g_slog.clear();
+    {   // last B: no call
+        StreamOrder o;
+        CHECK(o.enter(B) == 0 && o.mark(B) == 0);
+        hipEvent_t ev = o.ev;
+        const size_t calls = g_log.size();
+        CHECK(o.hand_over(B) == 0 && g_log.size() == calls && o.last == B && !o.ev_valid);
+        CHECK(o.enter(C) == 0);
+        CHECK(g_slog == SLog({{"record", B, ev, 0}, {"record", B, ev, 0}, {"wait", C, ev, 0}}));
+    }
+    {   // a scene that was never used: nothing is created
+        StreamOrder o;
+        const long made = g_made[2];
+        CHECK(o.hand_over(A) == 0 && o.hand_over(A) == 0 && g_made[2] == made && o.last == A);
+    }
+}
+
+// ------------------------------------------------------------------ StreamBlocks: one block per (device, stream)
+struct CountingMutex {
+    int locks = 0, unlocks = 0;
+    void lock() { CHECK(locks == unlocks); ++locks; }
+    void unlock() { ++unlocks; CHECK(locks == unlocks); }
+};
+static StreamBlocks<CountingMutex> g_blocks{"alloc site", "zero site"};   // a global, as in the library: its slots stay reachable
+
+static void blocks() {
+    void *a = nullptr, *a2 = nullptr, *b = nullptr;
+    CHECK(g_blocks.get(A, 100, 100, &a) == 0 && a && g_dev.count(a));
+    CHECK(g_log == Log({"hipGetDevice", "hipMalloc", "hipMemsetAsync"}) && g_slog == SLog({{"zero", A, a, 100}}));
+    CHECK(g_blocks.get(A, 100, 100, &a2) == 0 && a2 == a);             // the same (device, stream): the same block, no fill
+    CHECK(g_log == Log({"hipGetDevice", "hipMalloc", "hipMemsetAsync", "hipGetDevice"}));
+    CHECK(g_blocks.get(B, 100, 100, &b) == 0 && b != a && g_dev.size() == 2);   // a second stream: a second block, filled on B
+    CHECK(g_slog == SLog({{"zero", A, a, 100}, {"zero", B, b, 100}}) && count("hipMalloc") == 2);
+    size_t at = g_log.size();
+    CHECK(g_blocks.get(A, 300, 16, &a2) == 0 && g_dev.count(a2) && !g_dev.count(a) && g_dev.size() == 2);   // grows: frees, then allocates
+    CHECK(Log(g_log.begin() + at, g_log.end()) == Log({"hipGetDevice", "hipFree", "hipMalloc", "hipMemsetAsync"}));
+    CHECK(g_slog.size() == 3 && g_slog.back() == StreamCall({"zero", A, a2, 16}));                   // only the head is zeroed
+    a = a2;
+    at = g_log.size();
+    CHECK(g_blocks.get(A, 50, 16, &a2) == 0 && a2 == a && g_blocks.get(A, 300, 16, &a2) == 0 && a2 == a);   // grows only
+    CHECK(g_log.size() == at + 2 && count("hipMalloc") == 3);
+    g_device = 1;                                                    // the same stream handle on another device
+    void* d1 = nullptr;
+    CHECK(g_blocks.get(A, 100, 100, &d1) == 0 && d1 != a && d1 != b && g_dev.size() == 3);
+    g_device = 0;
+    CHECK(g_blocks.get(A, 100, 100, &a2) == 0 && a2 == a && g_dev.size() == 3);
+    // a zero fill that fails: the new block is freed, the slot stays empty and the next request allocates afresh
+    void* c = nullptr;
+    at = g_log.size();
+    g_fail_memset = 1;
+    CHECK(g_blocks.get(C, 64, 64, &c) == 1000 + (int)hipErrorInvalidValue && g_what == "zero site" && !c && g_dev.size() == 3);
+    CHECK(Log(g_log.begin() + at, g_log.end()) == Log({"hipGetDevice", "hipMalloc", "hipMemsetAsync", "hipFree"}));
+    at = g_log.size();
+    CHECK(g_blocks.get(C, 64, 64, &c) == 0 && c && g_dev.size() == 4);
+    CHECK(Log(g_log.begin() + at, g_log.end()) == Log({"hipGetDevice", "hipMalloc", "hipMemsetAsync"}));
+    g_fail_memset = 1;                                               // ... also when it was growing: the old block is gone too
+    CHECK(g_blocks.get(C, 128, 64, &a2) != 0 && !g_dev.count(c) && g_dev.size() == 3);
+    CHECK(g_blocks.get(C, 128, 64, &c) == 0 && g_dev.size() == 4);
+    g_fail_next = 1;                                                 // an allocation that fails
+    void* d = nullptr;
+    CHECK(g_blocks.get((hipStream_t)0x40, 8, 8, &d) == 1000 + (int)hipErrorOutOfMemory && g_what == "alloc site" && !d);
+    CHECK(g_blocks.get((hipStream_t)0x40, 8, 8, &d) == 0 && d && g_dev.size() == 5);
+    CHECK(g_blocks.mu.locks == count("hipGetDevice") && g_blocks.mu.unlocks == g_blocks.mu.locks);
+    // never freed, on purpose: the books are squared by hand
+    CHECK(g_made[0] - g_gone[0] == 5);
+    for (void* p : g_dev) { free(p); ++g_gone[0]; }
+    g_dev.clear();
+}
+
 int main(int argc, char** argv) {
     if (argc != 2) return 2;
     const std::string which = argv[1];
@@ -266,6 +461,13 @@ int main(int argc, char** argv) {
     else if (which == "stage") stage();
     else if (which == "lazy") lazy();
     else if (which == "release_then_destructor") release_then_destructor();
+    else if (which == "order_enter") order_enter();
+    else if (which == "order_mark") order_mark();
+    else if (which == "order_mark_spent") order_mark_spent();
+    else if (which == "order_record_fails") order_record_fails();
+    else if (which == "order_create_fails") order_create_fails();
+    else if (which == "order_hand_over") order_hand_over();
+    else if (which == "blocks") blocks();
     else return 3;
     CHECK(balanced());   // whatever the case left in scope is gone by now or was never made
     printf("ok\n");
@@ -273,7 +475,8 @@ int main(int argc, char** argv) {
 }
 """
 
-CASES = ["scope_exit", "moves", "reserve", "stage", "lazy", "release_then_destructor"]
+CASES = ["scope_exit", "moves", "reserve", "stage", "lazy", "release_then_destructor",
+         "order_enter", "order_mark", "order_mark_spent", "order_record_fails", "order_create_fails", "order_hand_over", "blocks"]
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
 """
-Which kernel each call runs (-m gpu): a table of the routes of csrc/api.hip route_mlp / train_api.hip route_bwd, as the calls
+Which kernel each call runs (-m gpu): a table of the routes of csrc/render_api.hip route_mlp / train_api.hip route_bwd, as the calls
 report them (last_launch_precision, the `projected` flag of last_mlp_stats, last_backward_precision, last_flush_precision, the
 recompute term of last_backward_stats).  The expected values are written out from the rules of include/pnyolo.h
 (pny_scene_set_projection, pny_scene_set_precision, PNY_PRECISION_*), not computed by a copy of the routing code.

@@ -1,7 +1,7 @@
 """
 The library's ordering between streams (-m gpu, real MI355X): include/pnyolo.h promises that a scene "may migrate between
 streams" -- a call that arrives on another stream than the previous call on its scene is ordered behind it by the library
-(csrc/api.hip enter_stream / mark_stream_point), pny_model_refresh orders itself behind every scene's last call and every
+(csrc/dev_resource.h StreamOrder::enter / mark), pny_model_refresh orders itself behind every scene's last call and every
 scene's next call behind itself, and the Python classes fork side streams from torch's current stream (model.py fork_streams /
 join_streams, render.py _flush_stream, model.py _trunk_stream).  The rest of the suite drives all of this on the default stream,
 where a missing wait cannot show.
@@ -677,7 +677,7 @@ def test_trunk_rebind_between_two_forwards_on_a_side_stream(rig, streams):
 @pytest.mark.parametrize("leg", list(LEGS))
 def test_order_event_invalidated_by_a_refresh(leg, rig, streams):
     """pny_scenes_encode of two scenes on s1 leaves a marked stream point (an order event recorded right behind the encode,
-    mark_stream_point); then, on s1, a spin and pny_model_refresh; then one query per scene on s2 and s3.  The queries must wait
+    StreamOrder::mark); then, on s1, a spin and pny_model_refresh; then one query per scene on s2 and s3.  The queries must wait
     for the refresh and not for the marked point in front of it: they read the refreshed weights.  The queries' float64
     reference takes the scenes' latents as the library's inference trunk produced them (read out with pny_scene_get_latent in
     a serial run beforehand; the trunk itself is held to float64 in test_gpu_trunk.py)."""
