@@ -1243,6 +1243,47 @@ int pny_scene_set_occupancy(pny_scene* s, const uint32_t* bits_dev /* NULL clear
                             const double c2[3], int outside_empty, pny_stream stream);
 int pny_scene_last_cull(pny_scene* s, int64_t kept[2], int64_t total[2]);
 
+/* ---- early ray termination: stop evaluating a no-grad ray once it is opaque (csrc/termination.hip and the segment kernels of
+ * csrc/occupancy.hip; conventions and arithmetic in csrc/pny_termination.h).  An opt-in, approximate mode the reference does not
+ * have; it works with or without an occupancy grid.  A pass with K samples per ray is cut into S' = min(segments, K) depth
+ * segments, segment j holding the samples [floor(j K / S'), floor((j + 1) K / S')).  The transmittance T at a segment boundary is
+ * the product of the composite's own (1 - alpha + 1e-10f) over the samples before it, from the masked per-sample output.  Every
+ * ray is alive in segment 0; it is alive in the next segment iff it was alive and !(T < t_min) at the boundary (a NaN keeps it
+ * alive; a dead ray stays dead).  A sample is evaluated iff its ray is alive in its segment and the grid, when one is attached,
+ * keeps it.  The contract is the grid's: the render equals the default render with the MLP's output at every sample that was not
+ * evaluated replaced by (0, 0, 0, 0) before the composite, in both passes.  With the mode off pny_render enqueues what it
+ * always did.
+ *
+ * pny_scene_set_termination: 0 < t_min < 1 and segments in 1 .. 16 switch the mode on, t_min == 0 switches it off (segments is
+ *   then ignored).  Refused (PNY_ERR_ARG): a NaN t_min, t_min outside [0, 1), segments outside 1 .. 16, a YOLO model, a grouped
+ *   scene.  The setting is a rendering option: unlike the grid it survives pny_scene_encode, pny_scene_set_latent and
+ *   pny_scene_set_cameras; pny_scene_set_groups above 1 switches it off.  With the mode on each pass of pny_render is, per
+ *   segment: classify, ONE host read of the kept count and the alive-ray count (one wait per issued segment), gather, the MLP on
+ *   the kept points, expand, transmittance update.  A pass stops issuing segments once no ray is alive.  A pny_render told to
+ *   stash for a backward returns PNY_ERR_STATE; pny_query, pny_yolo_render and every training entry ignore the setting.
+ * pny_scene_last_segments: the record of pass 0 (coarse) or 1 (fine) of the last pny_render: *n_issued segments were issued
+ *   (0 when the pass took no culled path, 1 with only a grid attached); alive_rays[j] and kept[j] of the first min(cap, *n_issued)
+ *   are written.  alive_rays and kept may be NULL with cap = 0.
+ * pny_termination_update: a stage entry, model-free, allocates nothing: T_dev[ray] *= the factors of the samples
+ *   [k_begin, k_end) of sample_dev (n, k, 4) at the depths z_dev (n, k) (the delta after the last sample of a ray reaches to the
+ *   ray's far, rays_dev column 7); alive_dev[ray] (bytes) = alive_dev[ray] && !(T_dev[ray] < t_min); alive_count_dev, unless
+ *   NULL, = the int64 number of alive rays (zeroed on the stream first, then integer atomic adds).  ONE launch.  sample_dev is
+ *   16-byte aligned.
+ * pny_occupancy_classify_segment: pny_occupancy_classify on the columns [k_begin, k_end) of z_dev (n, k): slot_dev is
+ *   (n, k_end - k_begin).  bits_dev = NULL: every cell is occupied (dims, c1, c2 are then ignored and may be NULL).
+ *   alive_dev (n bytes) or NULL: a ray whose byte is 0 rejects all its samples.  workspace_dev: 256-byte aligned,
+ *   pny_occupancy_classify_workspace_bytes(n (k_end - k_begin)) bytes.
+ * PNY_ERR_ARG, before any launch: a NULL pointer, n < 0, k < 1, a column range outside 0 <= k_begin < k_end <= k, n k > 2^30, a
+ *   NaN t_min or one outside [0, 1), a misaligned buffer, a workspace too small. */
+int pny_scene_set_termination(pny_scene* s, float t_min, int segments);
+int pny_scene_last_segments(pny_scene* s, int pass, int64_t* alive_rays, int64_t* kept, int cap, int* n_issued);
+int pny_termination_update(const float* rays_dev, const float* z_dev, const float* sample_dev, int64_t n, int k, int k_begin,
+                           int k_end, float t_min, float* T_dev, uint8_t* alive_dev, int64_t* alive_count_dev, pny_stream stream);
+int pny_occupancy_classify_segment(const uint32_t* bits_dev /* or NULL */, const int32_t dims[3], const double c1[3],
+                                   const double c2[3], int outside_empty, const float* rays_dev, const float* z_dev, int64_t n,
+                                   int k, int k_begin, int k_end, const uint8_t* alive_dev /* or NULL */, int32_t* slot_dev,
+                                   int64_t* kept_dev, void* workspace_dev, int64_t workspace_bytes, pny_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
 #include "dev_resource.h"
 #include "encoder.h"
 #include "pny_occupancy.h"
+#include "pny_termination.h"
 #include "stash_book.h"
 
 namespace pny {
@@ -228,6 +229,15 @@ struct pny_scene {
     DevBuf occ_bits, occ_work, occ_rows;
     PinnedBuf occ_count;
     int64_t cull_kept[2] = {0, 0}, cull_total[2] = {0, 0};   // pny_scene_last_cull: [0] coarse pass, [1] fine pass
+    // early ray termination (pny_scene_set_termination; pny_termination.h): a rendering option, so nothing clears it but the
+    // setter and pny_scene_set_groups above 1.  The per-ray T and alive byte live in occ_work, the two counts of a segment
+    // (kept samples, alive rays) are read into occ_count together.
+    bool term_on = false;
+    float term_t_min = 0.0f;
+    int term_segments = 1;
+    // pny_scene_last_segments: per pass the issued segments' alive rays and kept samples
+    int seg_issued[2] = {0, 0};
+    int64_t seg_alive[2][TERM_MAX_SEGMENTS] = {}, seg_kept[2][TERM_MAX_SEGMENTS] = {};
 };
 
 
@@ -272,7 +282,18 @@ void launch_occupancy_classify(const OccClassifyArgs& a, const OccLayout& l, uin
 void launch_occupancy_gather(const int32_t* slot, const float* rays, const float* z, int64_t n_samples, int K, int64_t m, float* xyz,
                              float* dirs, hipStream_t st);
 void launch_occupancy_expand(const int32_t* slot, const float* outc, int64_t n_samples, int64_t m, float* out, hipStream_t st);
+// ... the same three on the columns [k_begin, k_end) of the (n, K) buffers; slot is (n, k_end - k_begin)
+void launch_occupancy_classify_segment(const OccSegmentArgs& a, const OccLayout& l, uint32_t* sums2, int64_t* kept, hipStream_t st);
+void launch_occupancy_gather_segment(const int32_t* slot, const float* rays, const float* z, int64_t n, int K, int k_begin, int k_end,
+                                     int64_t m, float* xyz, float* dirs, hipStream_t st);
+void launch_occupancy_expand_segment(const int32_t* slot, const float* outc, int64_t n, int K, int k_begin, int k_end, int64_t m,
+                                     float* out, hipStream_t st);
+// termination.hip
+void launch_termination_update(const TermUpdateArgs& a, hipStream_t st);
 // the classification of n x k depth samples against grid g (occupancy_api.hip): checks nothing, launches
 void occupancy_classify(const OccGrid& g, const float* rays, const float* z, int64_t n_samples, int k, int32_t* slot, int64_t* kept,
                         void* workspace, hipStream_t st);
+// ... of the columns [k_begin, k_end) of n x k depth samples; g.bits null: every cell occupied; alive null: every ray alive
+void occupancy_classify_segment(const OccGrid& g, const float* rays, const float* z, int64_t n, int k, int k_begin, int k_end,
+                                const uint8_t* alive, int32_t* slot, int64_t* kept, void* workspace, hipStream_t st);
 }  // namespace pny

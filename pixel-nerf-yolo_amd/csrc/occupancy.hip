@@ -21,6 +21,8 @@
 //                       mlp_core.h load_point, not the fused form of the classification) and the ray's d to its compact row.
 //   expand              ONE: occupancy_expand_kernel, a thread per sample: 16 bytes, the compact row's or zeros.  The reads
 //                       ascend with the sample index, so they coalesce.
+//   depth segments      the *_segment_kernel forms of classify, gather and expand read and write the columns [k_begin, k_end) of
+//                       the (n, K) buffers (early ray termination: pny_termination.h); the sums are scanned by the same kernels.
 // Every kernel runs OCC_THREADS = 256 threads on at most RECON_MAX_BLOCKS workgroups and strides over the rest.
 #include <hip/hip_runtime.h>
 
@@ -182,6 +184,78 @@ __global__ __launch_bounds__(OCC_THREADS) void occupancy_expand_kernel(const int
     }
 }
 
+// ---------------------------------------------------------------------------------- depth segments (pny_termination.h)
+// The same three kernels on the columns [k_begin, k_begin + Ks) of the (n, K) buffers.  Sample s of a segment is column s % Ks
+// of ray s / Ks; slot is (n, Ks), ranked in ascending s, which is ascending sample order inside the segment.
+__global__ __launch_bounds__(OCC_THREADS) void occupancy_classify_segment_kernel(OccSegmentArgs a, unsigned n_tiles) {
+    __shared__ unsigned counts[OCC_TILE_STEPS * OCC_WAVES];
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    for (unsigned tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        bool keep[OCC_TILE_STEPS];
+        unsigned rank[OCC_TILE_STEPS];
+#pragma unroll
+        for (int j = 0; j < OCC_TILE_STEPS; ++j) {
+            const uint32_t s = tile * (uint32_t)OCC_TILE + (uint32_t)j * OCC_THREADS + threadIdx.x;
+            keep[j] = false;
+            if (s < a.n_samples) {
+                const uint32_t ray = s / a.Ks, col = s - ray * a.Ks;
+                const float4* r = reinterpret_cast<const float4*>(a.rays + (size_t)ray * 8);
+                const float4 r0 = r[0], r1 = r[1];
+                const float o[3] = {r0.x, r0.y, r0.z}, d[3] = {r0.w, r1.x, r1.y};
+                keep[j] = occ_keep_segment(a, ray, o, d, a.z[(size_t)ray * a.K + a.k_begin + col]);
+            }
+            const unsigned long long b = __ballot(keep[j]);
+            rank[j] = __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+            if (lane == 0) counts[j * OCC_WAVES + wave] = (unsigned)__popcll(b);
+        }
+        __syncthreads();
+        unsigned before = 0;
+#pragma unroll
+        for (int j = 0; j < OCC_TILE_STEPS; ++j) {
+            unsigned base = before;
+#pragma unroll
+            for (int w = 0; w < OCC_WAVES; ++w) {
+                const unsigned c = counts[j * OCC_WAVES + w];
+                base += w < wave ? c : 0u;
+                before += c;
+            }
+            const uint32_t s = tile * (uint32_t)OCC_TILE + (uint32_t)j * OCC_THREADS + threadIdx.x;
+            if (s < a.n_samples) a.slot[s] = keep[j] ? (int32_t)(base + rank[j]) : -1;
+        }
+        if (threadIdx.x == 0) a.sums1[tile] = before;
+        __syncthreads();       // counts is free for the next tile
+    }
+}
+
+__global__ __launch_bounds__(OCC_THREADS) void occupancy_gather_segment_kernel(const int32_t* slot, const float* rays, const float* z,
+                                                                               unsigned n, unsigned K, unsigned k_begin, unsigned Ks,
+                                                                               long long m, float* xyz, float* dirs) {
+    for (unsigned s = blockIdx.x * (unsigned)OCC_THREADS + threadIdx.x; s < n; s += gridDim.x * (unsigned)OCC_THREADS) {
+        const long long at = slot[s];
+        if (at < 0 || at >= m) continue;
+        const unsigned ray = s / Ks, col = s - ray * Ks;
+        const float4* r = reinterpret_cast<const float4*>(rays + (size_t)ray * 8);
+        const float4 r0 = r[0], r1 = r[1];
+        const float zz = z[(size_t)ray * K + k_begin + col];
+        float* p = xyz + 3 * at;
+        float* d = dirs + 3 * at;
+        d[0] = r0.w, d[1] = r1.x, d[2] = r1.y;
+        p[0] = r0.x + zz * r0.w;
+        p[1] = r0.y + zz * r1.x;
+        p[2] = r0.z + zz * r1.y;
+    }
+}
+
+__global__ __launch_bounds__(OCC_THREADS) void occupancy_expand_segment_kernel(const int32_t* slot, const float4* outc, unsigned n,
+                                                                               unsigned K, unsigned k_begin, unsigned Ks, long long m,
+                                                                               float4* out) {
+    for (unsigned s = blockIdx.x * (unsigned)OCC_THREADS + threadIdx.x; s < n; s += gridDim.x * (unsigned)OCC_THREADS) {
+        const long long at = slot[s];
+        const unsigned ray = s / Ks, col = s - ray * Ks;
+        out[(size_t)ray * K + k_begin + col] = (at >= 0 && at < m) ? outc[at] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+}
+
 inline unsigned capped(int64_t blocks) {
     if (blocks < 1) blocks = 1;
     return (unsigned)(blocks < (int64_t)RECON_MAX_BLOCKS ? blocks : (int64_t)RECON_MAX_BLOCKS);
@@ -218,6 +292,37 @@ void launch_occupancy_gather(const int32_t* slot, const float* rays, const float
 void launch_occupancy_expand(const int32_t* slot, const float* outc, int64_t n_samples, int64_t m, float* out, hipStream_t st) {
     hipLaunchKernelGGL(occupancy_expand_kernel, dim3(capped((n_samples + OCC_THREADS - 1) / OCC_THREADS)), dim3(OCC_THREADS), 0, st, slot,
                        reinterpret_cast<const float4*>(outc), (unsigned)n_samples, (long long)m, reinterpret_cast<float4*>(out));
+}
+
+// the segment forms: the classification's first kernel differs, the scan of the tile sums and the add pass are the same launches
+void launch_occupancy_classify_segment(const OccSegmentArgs& a, const OccLayout& l, uint32_t* sums2, int64_t* kept, hipStream_t st) {
+    hipLaunchKernelGGL(occupancy_classify_segment_kernel, dim3(capped(l.n1)), dim3(OCC_THREADS), 0, st, a, (unsigned)l.n1);
+    if (l.n2 == 0) {
+        hipLaunchKernelGGL(occupancy_scan_sums_kernel, dim3(1), dim3(OCC_THREADS), 0, st, a.sums1, (unsigned)l.n1, (uint32_t*)nullptr, kept);
+    } else {
+        hipLaunchKernelGGL(occupancy_scan_sums_kernel, dim3(capped(l.n2)), dim3(OCC_THREADS), 0, st, a.sums1, (unsigned)l.n1, sums2,
+                           (int64_t*)nullptr);
+        hipLaunchKernelGGL(occupancy_scan_sums_kernel, dim3(1), dim3(OCC_THREADS), 0, st, sums2, (unsigned)l.n2, (uint32_t*)nullptr, kept);
+        hipLaunchKernelGGL(occupancy_add_sums_kernel, dim3(capped((l.n1 + OCC_THREADS - 1) / OCC_THREADS)), dim3(OCC_THREADS), 0, st, a.sums1,
+                           (unsigned)l.n1, (const uint32_t*)sums2);
+    }
+    hipLaunchKernelGGL(occupancy_add_kernel, dim3(capped(((int64_t)a.n_samples + OCC_THREADS - 1) / OCC_THREADS)), dim3(OCC_THREADS), 0, st,
+                       a.slot, a.n_samples, (const uint32_t*)a.sums1);
+}
+
+void launch_occupancy_gather_segment(const int32_t* slot, const float* rays, const float* z, int64_t n, int K, int k_begin, int k_end,
+                                     int64_t m, float* xyz, float* dirs, hipStream_t st) {
+    const int64_t n_samples = n * (k_end - k_begin);
+    hipLaunchKernelGGL(occupancy_gather_segment_kernel, dim3(capped((n_samples + OCC_THREADS - 1) / OCC_THREADS)), dim3(OCC_THREADS), 0, st,
+                       slot, rays, z, (unsigned)n_samples, (unsigned)K, (unsigned)k_begin, (unsigned)(k_end - k_begin), (long long)m, xyz, dirs);
+}
+
+void launch_occupancy_expand_segment(const int32_t* slot, const float* outc, int64_t n, int K, int k_begin, int k_end, int64_t m,
+                                     float* out, hipStream_t st) {
+    const int64_t n_samples = n * (k_end - k_begin);
+    hipLaunchKernelGGL(occupancy_expand_segment_kernel, dim3(capped((n_samples + OCC_THREADS - 1) / OCC_THREADS)), dim3(OCC_THREADS), 0, st,
+                       slot, reinterpret_cast<const float4*>(outc), (unsigned)n_samples, (unsigned)K, (unsigned)k_begin,
+                       (unsigned)(k_end - k_begin), (long long)m, reinterpret_cast<float4*>(out));
 }
 
 }  // namespace pny

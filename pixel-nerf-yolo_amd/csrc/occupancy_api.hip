@@ -1,5 +1,5 @@
-// C entry points of the occupancy grid (include/pnyolo.h, "occupancy grid" section; kernels in occupancy.hip; the culled passes of
-// pny_render in render_api.hip): argument checks, then the launches.  The model-free entries allocate nothing and wait for nothing;
+// C entry points of the occupancy grid and of early ray termination (include/pnyolo.h, "occupancy grid" and "early ray
+// termination" sections; kernels in occupancy.hip and termination.hip; the culled passes of pny_render in render_api.hip): argument checks, then the launches.  The model-free entries allocate nothing and wait for nothing;
 // pny_scene_set_occupancy copies the bits into a buffer the scene owns.
 #include <math.h>
 
@@ -38,6 +38,18 @@ void occupancy_classify(const OccGrid& g, const float* rays, const float* z, int
     a.g = g, a.rays = rays, a.z = z, a.n_samples = (uint32_t)n_samples, a.K = (uint32_t)k, a.slot = slot;
     a.sums1 = reinterpret_cast<uint32_t*>(ws + l.sums1);
     launch_occupancy_classify(a, l, reinterpret_cast<uint32_t*>(ws + l.sums2), kept, st);
+}
+
+void occupancy_classify_segment(const OccGrid& g, const float* rays, const float* z, int64_t n, int k, int k_begin, int k_end,
+                                const uint8_t* alive, int32_t* slot, int64_t* kept, void* workspace, hipStream_t st) {
+    const int64_t n_samples = n * (k_end - k_begin);
+    const OccLayout l = occ_layout(n_samples);
+    char* ws = reinterpret_cast<char*>(workspace);
+    OccSegmentArgs a;
+    a.g = g, a.rays = rays, a.z = z, a.alive = alive, a.n_samples = (uint32_t)n_samples;
+    a.K = (uint32_t)k, a.k_begin = (uint32_t)k_begin, a.Ks = (uint32_t)(k_end - k_begin), a.slot = slot;
+    a.sums1 = reinterpret_cast<uint32_t*>(ws + l.sums1);
+    launch_occupancy_classify_segment(a, l, reinterpret_cast<uint32_t*>(ws + l.sums2), kept, st);
 }
 }  // namespace pny
 
@@ -131,6 +143,82 @@ int pny_scene_set_occupancy(pny_scene* s, const uint32_t* bits_dev, const int32_
 int pny_scene_last_cull(pny_scene* s, int64_t kept[2], int64_t total[2]) {
     if (!s || !kept || !total) return fail(PNY_ERR_ARG, "pny_scene_last_cull: null argument");
     for (int p = 0; p < 2; ++p) kept[p] = s->cull_kept[p], total[p] = s->cull_total[p];
+    return PNY_OK;
+}
+
+// ---------------------------------------------------------------------------------- early ray termination (pny_termination.h)
+int pny_occupancy_classify_segment(const uint32_t* bits_dev, const int32_t dims[3], const double c1[3], const double c2[3],
+                                   int outside_empty, const float* rays_dev, const float* z_dev, int64_t n, int k, int k_begin, int k_end,
+                                   const uint8_t* alive_dev, int32_t* slot_dev, int64_t* kept_dev, void* workspace_dev,
+                                   int64_t workspace_bytes, pny_stream stream) {
+    const char* who = "pny_occupancy_classify_segment: ";
+    if (!kept_dev || !workspace_dev || (bits_dev && (!dims || !c1 || !c2))) return fail(PNY_ERR_ARG, std::string(who) + "null argument");
+    if (n < 0 || k < 1) return fail(PNY_ERR_ARG, std::string(who) + "need n >= 0 and k >= 1");
+    if (k_begin < 0 || k_begin >= k_end || k_end > k) return fail(PNY_ERR_ARG, std::string(who) + "need 0 <= k_begin < k_end <= k");
+    if (n > 0 && (!rays_dev || !z_dev || !slot_dev)) return fail(PNY_ERR_ARG, std::string(who) + "null argument");
+    int rc;
+    if (bits_dev && ((rc = check_dims(who, dims)) || (rc = check_box(who, c1, c2)))) return rc;
+    if (n > OCC_MAX_SAMPLES / k) return fail(PNY_ERR_ARG, std::string(who) + "need n k <= 2^30 samples");
+    if (reinterpret_cast<uintptr_t>(rays_dev) % 16) return fail(PNY_ERR_ARG, std::string(who) + "rays_dev must be 16-byte aligned");
+    if (workspace_bytes < (int64_t)occ_layout(n * (k_end - k_begin)).bytes || reinterpret_cast<uintptr_t>(workspace_dev) % 256)
+        return fail(PNY_ERR_ARG, std::string(who) + "workspace too small (pny_occupancy_classify_workspace_bytes) or not 256-byte aligned");
+    if (n == 0) {
+        PNY_HIP(hipMemsetAsync(kept_dev, 0, sizeof(int64_t), (hipStream_t)stream));
+        return PNY_OK;
+    }
+    OccGrid g{};
+    g.bits = bits_dev, g.outside_empty = outside_empty != 0;
+    if (bits_dev) occ_grid_axes(g, dims, c1, c2);
+    occupancy_classify_segment(g, rays_dev, z_dev, n, k, k_begin, k_end, alive_dev, slot_dev, kept_dev, workspace_dev, (hipStream_t)stream);
+    PNY_HIP(hipGetLastError());
+    return PNY_OK;
+}
+
+int pny_termination_update(const float* rays_dev, const float* z_dev, const float* sample_dev, int64_t n, int k, int k_begin, int k_end,
+                           float t_min, float* T_dev, uint8_t* alive_dev, int64_t* alive_count_dev, pny_stream stream) {
+    const char* who = "pny_termination_update: ";
+    if (n < 0 || k < 1) return fail(PNY_ERR_ARG, std::string(who) + "need n >= 0 and k >= 1");
+    if (k_begin < 0 || k_begin >= k_end || k_end > k) return fail(PNY_ERR_ARG, std::string(who) + "need 0 <= k_begin < k_end <= k");
+    if (t_min != t_min) return fail(PNY_ERR_ARG, std::string(who) + "t_min must not be a NaN");
+    if (!(t_min >= 0.0f && t_min < 1.0f)) return fail(PNY_ERR_ARG, std::string(who) + "t_min out of range [0,1)");
+    if (n > 0 && (!rays_dev || !z_dev || !sample_dev || !T_dev || !alive_dev)) return fail(PNY_ERR_ARG, std::string(who) + "null argument");
+    if (n > OCC_MAX_SAMPLES / k) return fail(PNY_ERR_ARG, std::string(who) + "need n k <= 2^30 samples");
+    if (reinterpret_cast<uintptr_t>(sample_dev) % 16) return fail(PNY_ERR_ARG, std::string(who) + "sample_dev must be 16-byte aligned");
+    if (alive_count_dev) PNY_HIP(hipMemsetAsync(alive_count_dev, 0, sizeof(int64_t), (hipStream_t)stream));
+    if (n == 0) return PNY_OK;
+    TermUpdateArgs a;
+    a.rays = rays_dev, a.z = z_dev, a.samp = sample_dev, a.n = n, a.K = k, a.k_begin = k_begin, a.k_end = k_end, a.t_min = t_min;
+    a.T = T_dev, a.alive = alive_dev, a.alive_count = reinterpret_cast<unsigned long long*>(alive_count_dev);
+    launch_termination_update(a, (hipStream_t)stream);
+    PNY_HIP(hipGetLastError());
+    return PNY_OK;
+}
+
+int pny_scene_set_termination(pny_scene* s, float t_min, int segments) {
+    const char* who = "pny_scene_set_termination: ";
+    if (!s) return fail(PNY_ERR_ARG, std::string(who) + "null scene");
+    if (t_min != t_min) return fail(PNY_ERR_ARG, std::string(who) + "t_min must not be a NaN");
+    if (!(t_min >= 0.0f && t_min < 1.0f)) return fail(PNY_ERR_ARG, std::string(who) + "t_min out of range [0,1)");
+    if (t_min == 0.0f) {
+        s->term_on = false;
+        return PNY_OK;
+    }
+    if (segments < 1 || segments > TERM_MAX_SEGMENTS) return fail(PNY_ERR_ARG, std::string(who) + "segments out of range [1,16]");
+    if (s->m->desc.yolo || s->m->desc.d_out != 4)
+        return fail(PNY_ERR_ARG, std::string(who) + "the model is in YOLO mode: its aggregation weighs by objectness, not by sigma");
+    if (s->n_objs > 1)
+        return fail(PNY_ERR_ARG, std::string(who) + "the scene is grouped (pny_scene_set_groups): termination serves one object's rays");
+    s->term_t_min = t_min, s->term_segments = segments;
+    s->term_on = true;
+    return PNY_OK;
+}
+
+int pny_scene_last_segments(pny_scene* s, int pass, int64_t* alive_rays, int64_t* kept, int cap, int* n_issued) {
+    const char* who = "pny_scene_last_segments: ";
+    if (!s || !n_issued || (cap > 0 && (!alive_rays || !kept))) return fail(PNY_ERR_ARG, std::string(who) + "null argument");
+    if (pass < 0 || pass > 1 || cap < 0) return fail(PNY_ERR_ARG, std::string(who) + "need pass 0 or 1 and cap >= 0");
+    *n_issued = s->seg_issued[pass];
+    for (int j = 0; j < cap && j < s->seg_issued[pass]; ++j) alive_rays[j] = s->seg_alive[pass][j], kept[j] = s->seg_kept[pass][j];
     return PNY_OK;
 }
 

@@ -152,4 +152,22 @@ struct OccClassifyArgs {
     uint32_t* sums1;
 };
 
+// The classification of the columns [k_begin, k_begin + Ks) of the (n, K) depths (a depth segment: pny_termination.h).
+// g.bits null: every cell occupied; alive null: every ray alive, else the rays with alive[ray] == 0 reject all of theirs.
+struct OccSegmentArgs {
+    OccGrid g;
+    const float* rays;       // (n, 8), rows 16-byte aligned
+    const float* z;          // (n, K)
+    const uint8_t* alive;    // (n) or null
+    uint32_t n_samples;      // n * Ks
+    uint32_t K, k_begin, Ks;
+    int32_t* slot;           // (n, Ks)
+    uint32_t* sums1;
+};
+
+__host__ __device__ inline bool occ_keep_segment(const OccSegmentArgs& a, uint32_t ray, const float* o, const float* d, float z) {
+    if (a.alive && a.alive[ray] == 0) return false;
+    return a.g.bits ? occ_keep(a.g, o, d, z) : true;
+}
+
 }  // namespace pny

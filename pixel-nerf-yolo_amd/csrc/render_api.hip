@@ -1,6 +1,6 @@
 // C entry points that evaluate the MLP (include/pnyolo.h): pny_query, the render stages, pny_render / pny_yolo_render and the
 // latent projection, with the one place that decides which kernel a launch runs.  Host-side C++; all arithmetic of the hot
-// path is in the kernels (mlp.hip, mlp_h2.hip, render_kernels.hip, occupancy.hip).
+// path is in the kernels (mlp.hip, mlp_h2.hip, render_kernels.hip, occupancy.hip, termination.hip).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -325,6 +325,83 @@ static int culled_mlp(pny_scene* s, const float* rays, const float* z, int64_t n
     }
     launch_occupancy_expand(slot, outc, S, M, samp, st);
     PNY_HIP(hipGetLastError());
+    s->seg_issued[pass] = 1, s->seg_alive[pass][0] = n, s->seg_kept[pass][0] = M;
+    return 0;
+}
+
+// One MLP pass of a pny_render with early ray termination on (pny_termination.h), with or without a grid: the pass in
+// S' = min(segments, K) depth segments.  Per segment: classify its columns for the rays still alive, read the kept count M and
+// the alive-ray count together (the segment's ONE host wait), gather, the MLP on M points, expand into the segment's columns of
+// `samp`, then multiply the rays' carried T by the segment's factors and clear the alive bytes of the rays below t_min (not
+// after the last segment: nothing reads it).  Once no ray is alive the remaining columns are zeroed and no further segment is
+// issued.  The workspace is sized by the largest segment and reused.
+static int terminated_mlp(pny_scene* s, const float* rays, const float* z, int64_t n, int K, int coarse, float* samp, hipStream_t st,
+                          int pass) {
+    if (n > OCC_MAX_SAMPLES / K) return fail(PNY_ERR_ARG, "pny_render: more than 2^30 samples in a pass with early ray termination on");
+    if (reinterpret_cast<uintptr_t>(samp) % 16)
+        return fail(PNY_ERR_ARG, "pny_render: per-sample buffers must be 16-byte aligned with early ray termination on");
+    int rc;
+    const int Sp = term_segments(K, s->term_segments);
+    const int ks_max = (K + Sp - 1) / Sp;
+    const int64_t s_max = n * ks_max;
+    const size_t o_sums = mc_align((size_t)s_max * sizeof(int32_t)), o_counts = o_sums + occ_layout(s_max).bytes;
+    const size_t o_T = o_counts + 256, o_alive = o_T + mc_align((size_t)n * sizeof(float));
+    if ((rc = s->occ_work.reserve(o_alive + mc_align((size_t)n), "hipMalloc(termination workspace)"))) return rc;
+    if ((rc = s->occ_count.reserve(2 * sizeof(int64_t), "hipHostMalloc(termination counts)"))) return rc;
+    char* W = reinterpret_cast<char*>(s->occ_work.p);
+    int32_t* slot = reinterpret_cast<int32_t*>(W);
+    int64_t* counts_dev = reinterpret_cast<int64_t*>(W + o_counts);   // [0] kept samples of the segment, [1] alive rays in it
+    float* T = reinterpret_cast<float*>(W + o_T);
+    uint8_t* alive = reinterpret_cast<uint8_t*>(W + o_alive);
+    OccGrid g = s->occ;
+    if (!s->occ_on) g.bits = nullptr;
+    const float one = 1.0f;
+    uint32_t one_bits;
+    memcpy(&one_bits, &one, sizeof(one_bits));
+    PNY_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(T), (int)one_bits, (size_t)n, st));
+    PNY_HIP(hipMemsetAsync(alive, 1, (size_t)n, st));
+    int64_t kept_total = 0;
+    s->cull_total[pass] = n * K;
+    for (int j = 0; j < Sp; ++j) {
+        const int kb = term_bound(K, Sp, j), ke = term_bound(K, Sp, j + 1);
+        const int64_t Sj = n * (ke - kb);
+        occupancy_classify_segment(g, rays, z, n, K, kb, ke, alive, slot, counts_dev, W + o_sums, st);
+        PNY_HIP(hipGetLastError());
+        // (segment 0: every ray is alive, no update has counted yet)
+        PNY_HIP(hipMemcpyAsync(s->occ_count.p, counts_dev, (j ? 2 : 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        PNY_HIP(hipStreamSynchronize(st));
+        const int64_t M = static_cast<const int64_t*>(s->occ_count.p)[0], A = j ? static_cast<const int64_t*>(s->occ_count.p)[1] : n;
+        if (M < 0 || M > Sj || A < 0 || A > n) return fail(PNY_ERR_HIP, "pny_render: the segment classification returned an impossible count");
+        s->seg_alive[pass][j] = A, s->seg_kept[pass][j] = M;
+        s->seg_issued[pass] = j + 1;
+        kept_total += M;
+        s->cull_kept[pass] = kept_total;
+        if (A == 0) {   // every later sample is rejected too: columns [kb, K) of every row are zeros
+            PNY_HIP(hipMemset2DAsync(samp + (size_t)kb * 4, (size_t)K * 4 * sizeof(float), 0, (size_t)(K - kb) * 4 * sizeof(float), (size_t)n, st));
+            break;
+        }
+        float* outc = nullptr;
+        if (M > 0) {
+            const size_t m3 = ((size_t)M * 3 + 63) & ~(size_t)63;
+            if ((rc = s->occ_rows.reserve((2 * m3 + (size_t)M * 4) * sizeof(float), "hipMalloc(occupancy rows)"))) return rc;
+            float* xyz = s->occ_rows.f();
+            float* dirs = xyz + m3;
+            outc = dirs + m3;
+            launch_occupancy_gather_segment(slot, rays, z, n, K, kb, ke, M, xyz, dirs, st);
+            PNY_HIP(hipGetLastError());
+            if ((rc = run_mlp(s, 0, xyz, dirs, nullptr, nullptr, 1, M, coarse, outc, st))) return rc;
+        }
+        launch_occupancy_expand_segment(slot, outc, n, K, kb, ke, M, samp, st);
+        PNY_HIP(hipGetLastError());
+        if (j + 1 < Sp) {
+            PNY_HIP(hipMemsetAsync(counts_dev + 1, 0, sizeof(int64_t), st));
+            TermUpdateArgs u;
+            u.rays = rays, u.z = z, u.samp = samp, u.n = n, u.K = K, u.k_begin = kb, u.k_end = ke, u.t_min = s->term_t_min;
+            u.T = T, u.alive = alive, u.alive_count = reinterpret_cast<unsigned long long*>(counts_dev + 1);
+            launch_termination_update(u, st);
+            PNY_HIP(hipGetLastError());
+        }
+    }
     return 0;
 }
 
@@ -395,13 +472,19 @@ int pny_render(pny_scene* s, const float* rays_dev, int64_t n, const pny_render_
             return fail(PNY_ERR_ARG, "pny_render: explicit random draws must be given for every stage or for none");
     }
     // an occupancy grid (pny_scene_set_occupancy) is for no-grad renders: a culled pass writes no stash
-    const bool cull = s->occ_on;
+    // ... and so is early ray termination (pny_scene_set_termination)
+    const bool cull = s->occ_on || s->term_on;
     if (cull && s->stash_next) {
         s->stash_next = false;
+        if (!s->occ_on)
+            return fail(PNY_ERR_STATE, "pny_render: the scene has early ray termination on and was told to stash for a backward "
+                                       "(pny_scene_stash_next_render); switch it off with pny_scene_set_termination(s, 0, 1) to train");
         return fail(PNY_ERR_STATE, "pny_render: the scene has an occupancy grid attached and was told to stash for a backward "
                                    "(pny_scene_stash_next_render); clear the grid with pny_scene_set_occupancy(s, NULL, ...) to train");
     }
     s->cull_kept[0] = s->cull_kept[1] = s->cull_total[0] = s->cull_total[1] = 0;
+    s->seg_issued[0] = s->seg_issued[1] = 0;
+    const auto culled_pass = s->term_on ? terminated_mlp : culled_mlp;
     if (n == 0) return PNY_OK;
     PNY_HIP(hipSetDevice(s->m->desc.device));
     hipStream_t st = (hipStream_t)stream;
@@ -431,7 +514,7 @@ int pny_render(pny_scene* s, const float* rays_dev, int64_t n, const pny_render_
     s->stashed[0].valid = s->stashed[1].valid = false;
     launch_sample_coarse(rays_dev, n, kc, o->lindisp, o->u_coarse_dev, o->seed, zc, st);
     if (cull) {
-        if ((rc = culled_mlp(s, rays_dev, zc, n, kc, 1, sc, st, 0))) return rc;
+        if ((rc = culled_pass(s, rays_dev, zc, n, kc, 1, sc, st, 0))) return rc;
     } else if ((rc = run_mlp(s, 1, nullptr, nullptr, rays_dev, zc, kc, (long long)n * kc, 1, sc, st, stash ? 0 : -1))) {
         return rc;
     }
@@ -444,7 +527,7 @@ int pny_render(pny_scene* s, const float* rays_dev, int64_t n, const pny_render_
         launch_sample_fine(rays_dev, zc, wc, dc, n, kc, o->n_fine, o->n_fine_depth, o->depth_std, o->lindisp,
                            o->u_fine_dev, o->u_fine2_dev, o->g_depth_dev, o->seed, zf, st);
         if (cull) {
-            if ((rc = culled_mlp(s, rays_dev, zf, n, kt, 0, sf, st, 1))) return rc;
+            if ((rc = culled_pass(s, rays_dev, zf, n, kt, 0, sf, st, 1))) return rc;
         } else if ((rc = run_mlp(s, 1, nullptr, nullptr, rays_dev, zf, kt, (long long)n * kt, 0, sf, st, stash ? 1 : -1))) {
             return rc;
         }

@@ -81,6 +81,7 @@ int pny_scene_set_groups(pny_scene* s, int n_objs) {
     if (n_objs < 1 || n_objs > MAX_VIEWS) return fail(PNY_ERR_ARG, "pny_scene_set_groups: n_objs out of range [1,16]");
     s->n_objs = n_objs;   // (the view count is checked against it when a call needs both: check_ready)
     if (n_objs > 1) s->occ_on = false;   // one occupancy grid serves one object
+    if (n_objs > 1) s->term_on = false;  // ... and termination one object's rays
     return PNY_OK;
 }
 

@@ -277,6 +277,13 @@ SIGNATURES = {
     "pny_scene_set_occupancy": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.c_int, C.c_void_p]),
     "pny_scene_last_cull": (C.c_int, [C.c_void_p, c_i64_p, c_i64_p]),
+    "pny_scene_set_termination": (C.c_int, [C.c_void_p, C.c_float, C.c_int]),
+    "pny_scene_last_segments": (C.c_int, [C.c_void_p, C.c_int, c_i64_p, c_i64_p, C.c_int, C.POINTER(C.c_int)]),
+    "pny_termination_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pny_occupancy_classify_segment": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 _lib = None

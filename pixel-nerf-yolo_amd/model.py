@@ -287,6 +287,7 @@ class PixelNeRFNet(nn.Module):
         self._trunk_generation = 0         # bumped by every training-trunk forward: whose activations does the library hold
         self._timing = False
         self._occupancy = None             # set_occupancy: the grid attached to the one encoded object
+        self._termination = None           # set_termination: (t_min, segments), a rendering option that outlives encode()
         # What a no-grad call does when one of its f16 (F16X2 / F16) launches met a value outside the f16 range (include/pnyolo.h
         # pny_model_range_status): 'relaunch' (default) = wait for the call, and if the guard fired repeat it on the fp32
         # kernels with a warning, keeping the scenes pinned to f32 from then on; 'raise' = wait and raise PnyRangeError;
@@ -406,7 +407,7 @@ class PixelNeRFNet(nn.Module):
         if any(a[2] != b[2] and a[0].startswith("encoder.") for a, b in zip(old, new)):
             self._enc_stale = True
 
-    def _new_scene(self):
+    def _new_scene(self, group=False):
         L = _lib.load()
         s = C.c_void_p()
         check(L.pny_scene_create(C.byref(s), self._h_model))
@@ -415,6 +416,8 @@ class PixelNeRFNet(nn.Module):
             check(L.pny_scene_set_projection(s, _lib.PROJECTION[self._projection]))
         if self._precision is not None:
             check(L.pny_scene_set_precision(s, _lib.PRECISION[self._precision]))
+        if self._termination is not None and not group:
+            check(L.pny_scene_set_termination(s, *self._termination))
         return s
 
     def _scene(self, i):
@@ -567,6 +570,56 @@ class PixelNeRFNet(nn.Module):
         kept, total = (C.c_int64 * 2)(), (C.c_int64 * 2)()
         check(_lib.load().pny_scene_last_cull(self._scene(0), kept, total))
         return {"coarse": (int(kept[0]), int(total[0])), "fine": (int(kept[1]), int(total[1]))}
+
+    def set_termination(self, t_min, segments=4):
+        """Early ray termination for no-grad renders of the ONE encoded object, or off with ``t_min=None`` (include/pnyolo.h
+        pny_scene_set_termination; csrc/pny_termination.h).  Each pass is rendered in ``segments`` (1 .. 16) depth-ordered segments,
+        and a ray whose transmittance has fallen below ``t_min`` (0 < t_min < 1) at a segment boundary is not evaluated in the
+        later ones; the composite sees (0, 0, 0, 0) there.  An opt-in, approximate mode, like set_occupancy, and it works with or
+        without a grid; how close the frame stays to the default one is the caller's choice of ``t_min`` (there is no default).
+        Each render waits for the device once per issued segment.  The setting is a rendering option, not a property of the
+        encoded object: UNLIKE the grid, which ``encode()`` drops, it survives ``encode()``.  Queries, YOLO renders and training
+        ignore or refuse it."""
+        L = _lib.load()
+        if t_min is None:
+            if self._h_model is not None:
+                for s in self._handles():
+                    check(L.pny_scene_set_termination(s, 0.0, 1))
+            self._termination = None
+            return self
+        t_min, segments = float(t_min), int(segments)
+        if not 0.0 < t_min < 1.0:
+            raise ValueError("PixelNeRFNet.set_termination: t_min must be in (0, 1) (None switches the mode off), got %r" % t_min)
+        if not 1 <= segments <= 16:
+            raise ValueError("PixelNeRFNet.set_termination: segments must be in 1 .. 16, got %d" % segments)
+        if self.yolo:
+            raise _lib.PnyError("PixelNeRFNet.set_termination: a YOLO model aggregates by objectness, not by sigma; early ray "
+                                "termination does not apply to it")
+        if self.num_objs != 1:
+            raise _lib.PnyError("PixelNeRFNet.set_termination: net must hold ONE encoded object (call net.encode() with one object "
+                                "first); it holds %d" % self.num_objs)
+        self._sync()
+        self._termination = (t_min, segments)
+        self._scene(0)                     # (a handle created from here on takes the setting in _new_scene)
+        for s in self._h_scenes:
+            check(L.pny_scene_set_termination(s, t_min, segments))
+        return self
+
+    @property
+    def termination(self):
+        """(t_min, segments) of set_termination, or None."""
+        return self._termination
+
+    def last_termination(self):
+        """{"coarse": [(alive_rays, kept), ...], "fine": [...]}: per pass of the last render of the object, the rays alive in and
+        the samples evaluated by every segment that was issued (include/pnyolo.h pny_scene_last_segments).  One segment per pass
+        with only a grid attached, none when the render took no culled path."""
+        out = {}
+        for i, name in enumerate(("coarse", "fine")):
+            alive, kept, n = (C.c_int64 * 16)(), (C.c_int64 * 16)(), C.c_int(0)
+            check(_lib.load().pny_scene_last_segments(self._scene(0), i, alive, kept, 16, C.byref(n)))
+            out[name] = [(int(alive[j]), int(kept[j])) for j in range(n.value)]
+        return out
 
     def set_deterministic(self, mode):
         """'auto' | True | False: whether d loss / d latent is computed bit-reproducibly (include/pnyolo.h
@@ -861,6 +914,9 @@ class PixelNeRFNet(nn.Module):
         dev = self._device()
         if self._occupancy is not None:     # learnt on the object encoded before (the library drops its copy on its own too)
             self.set_occupancy(None)
+        if self._termination is not None and images.size(0) != 1:
+            raise _lib.PnyError("PixelNeRFNet.encode: the net has early ray termination on (net.set_termination), which serves ONE "
+                                "encoded object; this call encodes %d: switch it off with net.set_termination(None)" % images.size(0))
         self.num_objs = images.size(0)
         if images.dim() == 5:
             assert poses.dim() == 4 and poses.size(1) == images.size(1)
@@ -925,7 +981,7 @@ class PixelNeRFNet(nn.Module):
             # pass of the render and of its backward is one launch over all objects' tiles (the reference flattens the
             # super-batch the same way, nerf.py:283-288).  The per-object handles are filled only if something asks for them.
             if self._h_group is None:
-                self._h_group = self._new_scene()
+                self._h_group = self._new_scene(group=True)
             self._fill_scene(self._h_group, cams, 0, SB * NS, n_objs=SB, **source)
             self._group = dict(SB=SB, NS=NS)
             self._scenes_pending = cams

@@ -130,6 +130,9 @@ class _MultiDeviceRenderWrapper(torch.nn.Module):
         if net.occupancy is not None:
             raise _lib.PnyError("bind_parallel(net, gpus): the net has an occupancy grid attached (net.set_occupancy), which the "
                                 "per-device replicas do not carry; render on one device, or detach it with net.set_occupancy(None)")
+        if net.termination is not None:
+            raise _lib.PnyError("bind_parallel(net, gpus): the net has early ray termination on (net.set_termination), which the "
+                                "per-device replicas do not carry; render on one device, or switch it off with net.set_termination(None)")
         want_weights = want_weights and not self.simple_output
         training = torch.is_grad_enabled() and net.training and (net.trainable_mlp_parameters() or net.differentiable_latent() is not None)
         B = rays.shape[1]
@@ -480,6 +483,10 @@ class NeRFRenderer(torch.nn.Module):
         if model.occupancy is not None:
             raise _lib.PnyError("NeRFRenderer: the net has an occupancy grid attached (net.set_occupancy), which serves no-grad "
                                 "renders only; this call takes gradients: detach the grid with net.set_occupancy(None), or render "
+                                "under torch.no_grad()")
+        if model.termination is not None:
+            raise _lib.PnyError("NeRFRenderer: the net has early ray termination on (net.set_termination), which serves no-grad "
+                                "renders only; this call takes gradients: switch it off with net.set_termination(None), or render "
                                 "under torch.no_grad()")
         if lat_src is None:
             model.check_differentiable()     # (with a differentiable latent the caller's own encoder takes the gradient)
